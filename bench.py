@@ -2,6 +2,7 @@
 """Hot-path benchmark: the W8A8 real-int8 QLinear step at TinyLlama-1.1B's headline shape.
 
     python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + the last timed step's output as DIR/qlinear_out.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -64,7 +65,28 @@ def parse():
     p.add_argument("--overlap", action="store_true",
                    help="experiment: quantize(batch i+1) on a side stream next to GEMM(batch i); measured SLOWER "
                         "(36.3 vs 34.7 us/step): the GEMM's one workgroup per CU leaves no room to co-schedule")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, rank 0): "
+                        "the same arguments give the same inputs, so two builds can be compared output for output")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes {name: array} as out_dir/<name>.npy in float32 / float64 (at most DUMP_LIMIT_BYTES in all)."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def maybe_spawn(args):
@@ -615,7 +637,7 @@ def calibration_run(dev, rank, world, layers, n_samples, seq, per_channel, stub_
     act = col.act_dict()
     return {"seconds": dt, "samples_per_s": n_samples / dt, "collectives": getattr(col, "n_collectives", 0), "tensors": len(col.slots),
             "hooked_bytes_per_sample": hooked_bytes, "fused_bytes_per_sample": fused_bytes, "model_seconds_per_sample": t_model,
-            "reduction_seconds_per_sample": max(per_sample - t_model, 0.0), "modules": len(act)}
+            "reduction_seconds_per_sample": max(per_sample - t_model, 0.0), "modules": len(act), "act": act}
 
 
 def decode_block(dev):
@@ -660,12 +682,18 @@ def bench_calibration(args, rank, world, dev):
     r = calibration_run(dev, rank, world, args.calib_layers, args.calib_samples, args.calib_seq, args.per_channel, args.calib_stub_gemm)
     if rank != 0:
         return
+    if args.dump_outputs:
+        # the merged act_dict every rank receives: minima and maxima of every hooked (module, field), in sorted order, flattened
+        # (per-tensor: one value each; per-channel: one per channel)
+        keys = sorted((m, f) for m in r["act"] for f in r["act"][m])
+        rows = [np.asarray(r["act"][m][f], dtype=np.float32).reshape(2, -1) for m, f in keys]
+        dump_outputs(args.dump_outputs, {"act_range_min": np.concatenate([x[0] for x in rows]),
+                                         "act_range_max": np.concatenate([x[1] for x in rows])})
     mm = bench_minmax(dev, args.calib_seq)
     cpu = None
     if world == 1 and not args.no_cpu_baseline:
         # the oracle's running min / max (oracle/mq_oracle.py: compute_min_max_from_tensor + update_act_range) over a bounded sample of
         # the hooked bytes; samples/s = rate / hooked bytes per sample
-        import numpy as np
         from oracle import mq_oracle as O
         x = np.random.default_rng(0).standard_normal((4 * args.calib_seq, args.calib_seq), dtype=np.float32)
         orc = O.ActRangeOracle(args.per_channel)
@@ -731,6 +759,10 @@ def main():
         step = Step(dev, MQ_U8, seed=rank)
         pipelined = args.overlap and not args.no_graph
         sec = run_steps(step, args.steps, args.warmup, world, use_graph=not args.no_graph, pipelined=pipelined)
+        if args.dump_outputs and rank == 0:
+            # the last timed step's output indices [M, N] (u8, exact in float32), before the roofline legs below reuse the buffers
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, {"qlinear_out": step.out.float().cpu().numpy()})
         spread = [round(t * 1e3, 5) for t in getattr(run_steps, "last", [sec])]
         run_steps.host_wall_main = max_over_ranks(run_steps.host_wall, world)
         host_spread = [round(t * 1e3, 5) for t in run_steps.host_last]

@@ -59,6 +59,29 @@ def test_gpus_flag_relaunches_under_torch_distributed_run(monkeypatch):
     assert cmd[-4:] == ["--gpus", "4", "--steps", "20"]
 
 
+def test_dump_outputs_flag_and_steps_bound(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.steps == 3 and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
+def test_dump_outputs_writes_float_npy_within_the_size_limit(tmp_path):
+    b = _bench()
+    y = np.arange(12, dtype=np.float32).reshape(3, 4)
+    b.dump_outputs(str(tmp_path / "out"), {"y": y})
+    got = np.load(tmp_path / "out" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y)
+    with pytest.raises(AssertionError):
+        b.dump_outputs(str(tmp_path / "bad"), {"q": np.zeros(4, dtype=np.uint8)})
+    with pytest.raises(AssertionError):
+        b.dump_outputs(str(tmp_path / "big"), {"z": np.zeros(b.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "bad").exists() and not (tmp_path / "big").exists()
+
+
 # ---- the torch-CPU baseline computes the oracle's arithmetic --------------------------------------------------------
 @pytest.mark.parametrize("bits,sym", [(8, False), (8, True), (4, False), (16, False)])
 def test_torch_baseline_quantizer_is_bit_exact_with_the_oracle(bits, sym):

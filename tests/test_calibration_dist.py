@@ -173,10 +173,11 @@ def test_four_rank_merge_with_rank_divergent_observations(mode):
     assert res == [(r, True if mode == "verify" else "raised") for r in range(4)], res
 
 
-def _cpu_reductions():
+def _cpu_reductions(patch=setattr):
     """Test stand-ins for the three HIP reductions get_act_range launches (mq_minmax_init / _tensor / _cols: covered on the GPU box):
     the same running update with torch's amin / amax, so that the WHOLE data-parallel path -- hooks on a real model, round-robin shards,
-    the duplicate of a sample-less rank, packing, the layout checksum, the one collective, unpacking -- runs on CPU ranks."""
+    the duplicate of a sample-less rank, packing, the layout checksum, the one collective, unpacking -- runs on CPU ranks.
+    patch: how the stand-ins are installed; inside the pytest process pass monkeypatch.setattr so later tests get the HIP ops back."""
     from mobilequant_amd import ops
 
     def new(n, device):
@@ -189,7 +190,8 @@ def _cpu_reductions():
     def cols_(x2d, mn, mx):
         mn.copy_(torch.minimum(mn, x2d.amin(0).float()))
         mx.copy_(torch.maximum(mx, x2d.amax(0).float()))
-    ops.minmax_new, ops.minmax_tensor_, ops.minmax_cols_ = new, tensor_, cols_
+    for name, fn in (("minmax_new", new), ("minmax_tensor_", tensor_), ("minmax_cols_", cols_)):
+        patch(ops, name, fn)
 
 
 def _toy_llama():
@@ -230,13 +232,13 @@ def _full_path_worker(rank, world, port, per_channel, n_samples, q):
 
 
 @pytest.mark.parametrize("per_channel,n_samples", [(False, 12), (True, 12), (False, 5)])
-def test_eight_rank_get_act_range_on_a_real_model_equals_the_single_process_run(per_channel, n_samples):
+def test_eight_rank_get_act_range_on_a_real_model_equals_the_single_process_run(per_channel, n_samples, monkeypatch):
     """the first real 8-GPU run must not fail on plumbing.  EIGHT gloo ranks run the full get_act_range path
     (ptq/generate_act_range.py:49-122's data-parallel counterpart) on the toy llama graph -- forward hooks on every calibrated leaf
     incl. both matmuls, samples round-robin (12 samples: ranks own 2 or 1; 5 samples: three ranks own none and re-run a duplicate),
     ONE all-reduce of the packed statistics and no other collective -- and every rank ends with exactly the act_dict a single
     process computes over all samples (min / max are exact and order independent)."""
-    _cpu_reductions()
+    _cpu_reductions(monkeypatch.setattr)
     from mobilequant_amd.calibration import get_act_range
     want = get_act_range(_toy_llama(), _toy_samples(n_samples), per_channel=per_channel)
     want = {f"{n}|{f}": (v.numpy().tolist() if torch.is_tensor(v) else [float(v[0]), float(v[1])]) for n, d in want.items() for f, v in d.items()}
