@@ -1510,14 +1510,30 @@ int mq_decode_gemv(const mq_decode_gemv_args* args, mq_stream_t stream) {
   return MQ_OK;
 }
 
+// ---- the largest cache_len each attention launch serves: LDS per workgroup on gfx950 (160 KiB) = static + dynamic LDS ------------------
+// Static LDS in bytes (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage on this file), head_dim 32 / 64 / 128 / 256:
+//   decode_attention_kernel<D>                      8336 / 8432 / 8624 / 9008   + 4 B per cached position (scores)
+//   decode_attention_oproj_kernel<D, 256>           2240 / 2368 / 2624 / 3136   + 7 B per cached position (scores + 3 digit planes)
+//   decode_attention_oproj_kernel<D, 1024>          8528 / 8656 / 8912 / 9424
+// five launches: 4 x 32768 + 9008 fits at every head_dim, so the entry's own 32768 is the bound; four launches: the largest multiple of
+// 16 with 7 cache_len + static <= 163840 -- 23072 / 23056 / 23024 / 22944 (256 threads), 22176 / 22160 / 22128 / 22048 (1024 threads).
+// mobilequant_amd/decode.py (DecodeEngine.max_cache_len) mirrors these numbers to choose the chain.
+constexpr int kLdsPerWorkgroup = 160 * 1024;
+constexpr int kAttnMaxCache = 32768;
+static int ao_max_cache(int head_dim, bool lng) {
+  const int ki = head_dim == 32 ? 0 : head_dim == 64 ? 1 : head_dim == 128 ? 2 : 3;
+  static const int static_lds[2][4] = {{2240, 2368, 2624, 3136}, {8528, 8656, 8912, 9424}};
+  return (kLdsPerWorkgroup - static_lds[lng ? 1 : 0][ki]) / 7 / 16 * 16;
+}
+
 int mq_decode_attention(const mq_decode_attention_args* args, mq_stream_t stream) {
   MQ_REQUIRE(args != nullptr, "mq_decode_attention: null argument block");
   const mq_decode_attention_args& a = *args;
   MQ_REQUIRE(a.qkv && a.k_cache && a.v_cache && a.cos && a.sin && a.pos && a.consts && (a.out || a.out_q), "mq_decode_attention: null pointer");
   MQ_REQUIRE(a.heads > 0 && a.kv_heads > 0 && a.heads % a.kv_heads == 0 && (a.head_dim == 32 || a.head_dim == 64 || a.head_dim == 128 || a.head_dim == 256) &&
-                 a.cache_len > 0 && a.cache_len <= 32768 && a.rot_dim > 0 && a.rot_dim <= a.head_dim && a.rot_dim % 2 == 0,
-             "mq_decode_attention: heads=%d kv_heads=%d head_dim=%d (32 / 64 / 128 / 256) cache_len=%d (<= 32768) rot_dim=%d", a.heads, a.kv_heads, a.head_dim,
-             a.cache_len, a.rot_dim);
+                 a.cache_len > 0 && a.cache_len <= kAttnMaxCache && a.rot_dim > 0 && a.rot_dim <= a.head_dim && a.rot_dim % 2 == 0,
+             "mq_decode_attention: heads=%d kv_heads=%d head_dim=%d (32 / 64 / 128 / 256) cache_len=%d (<= %d) rot_dim=%d", a.heads, a.kv_heads, a.head_dim,
+             a.cache_len, kAttnMaxCache, a.rot_dim);
   MQ_REQUIRE(a.nsplit >= 1 && a.nsplit <= 16 && (a.nsplit == 1 || (a.part && a.ticket)), "mq_decode_attention: nsplit=%d (1..16; > 1 needs part and ticket)", a.nsplit);
   MQ_REQUIRE(a.qk_a.scale && a.qk_b.scale && a.pv_a.scale && a.pv_b.scale && a.qk_a.qmin == 0.f && a.qk_a.qmax == 255.f && a.qk_b.qmin == 0.f &&
                  a.qk_b.qmax == 255.f && a.pv_b.qmin == 0.f && a.pv_b.qmax == 255.f && a.pv_a.qmin == 0.f && a.pv_a.qmax <= 65535.f,
@@ -1558,8 +1574,8 @@ int mq_decode_attention_oproj(const mq_decode_attention_oproj_args* args, mq_str
   const mq_decode_attention_oproj_args& a = *args;
   MQ_REQUIRE(a.qkv && a.k_cache && a.v_cache && a.rope_row && a.pos && a.consts && a.o_w && a.o_wzp && a.o_acc, "mq_decode_attention_oproj: null pointer");
   MQ_REQUIRE(a.heads > 0 && a.kv_heads > 0 && a.heads % a.kv_heads == 0 && (a.head_dim == 32 || a.head_dim == 64 || a.head_dim == 128 || a.head_dim == 256) &&
-                 a.cache_len > 0 && a.cache_len <= 32768 && a.rot_dim > 0 && a.rot_dim <= a.head_dim && a.rot_dim % 2 == 0,
-             "mq_decode_attention_oproj: heads=%d kv_heads=%d head_dim=%d (32 / 64 / 128 / 256) cache_len=%d (<= 32768) rot_dim=%d", a.heads, a.kv_heads, a.head_dim,
+                 a.cache_len > 0 && a.rot_dim > 0 && a.rot_dim <= a.head_dim && a.rot_dim % 2 == 0,
+             "mq_decode_attention_oproj: heads=%d kv_heads=%d head_dim=%d (32 / 64 / 128 / 256) cache_len=%d rot_dim=%d", a.heads, a.kv_heads, a.head_dim,
              a.cache_len, a.rot_dim);
   MQ_REQUIRE(a.qk_a.scale && a.qk_b.scale && a.pv_a.scale && a.pv_b.scale && a.qk_a.qmin == 0.f && a.qk_a.qmax == 255.f && a.qk_b.qmin == 0.f &&
                  a.qk_b.qmax == 255.f && a.pv_b.qmin == 0.f && a.pv_b.qmax == 255.f && a.pv_a.qmin == 0.f && a.pv_a.qmax <= 65535.f,
@@ -1579,14 +1595,16 @@ int mq_decode_attention_oproj(const mq_decode_attention_oproj_args* args, mq_str
                                     a.prefetch_stride >= a.prefetch_bytes_per_wg && a.prefetch_stride % 16 == 0 && a.prefetch_delay >= 0 && a.prefetch_delay <= 100000),
              "mq_decode_attention_oproj: prefetch needs a 16-byte aligned range, 1..4096 workgroups, stride >= bytes per workgroup, delay in 0..100000 (10 ns units)");
   MQ_REQUIRE(a.cache_len % 16 == 0, "mq_decode_attention_oproj: cache_len=%d must be a multiple of 16 (transposed value cache, 16-byte chunks)", a.cache_len);
-  const size_t lds = (size_t)a.cache_len * (sizeof(float) + 3);
   const bool lng = a.threads == AO_THREADS_LONG;
+  MQ_REQUIRE(a.cache_len <= ao_max_cache(a.head_dim, lng), "mq_decode_attention_oproj: cache_len=%d exceeds %d, the most the %d-thread launch holds in LDS at head_dim %d",
+             a.cache_len, ao_max_cache(a.head_dim, lng), lng ? AO_THREADS_LONG : AO_THREADS, a.head_dim);
+  const size_t lds = (size_t)a.cache_len * (sizeof(float) + 3);
 #define MQ_AO_FN(DD) (lng ? reinterpret_cast<const void*>(decode_attention_oproj_kernel<DD, AO_THREADS_LONG>) : reinterpret_cast<const void*>(decode_attention_oproj_kernel<DD, AO_THREADS>))
   const void* fn = a.head_dim == 32 ? MQ_AO_FN(32) : a.head_dim == 64 ? MQ_AO_FN(64) : a.head_dim == 128 ? MQ_AO_FN(128) : MQ_AO_FN(256);
 #undef MQ_AO_FN
   static std::atomic<size_t> lds_set[kMaxDevices][8];
   const int dev = current_device(), ki = (a.head_dim == 32 ? 0 : a.head_dim == 64 ? 1 : a.head_dim == 128 ? 2 : 3) + (lng ? 4 : 0);
-  if (lds > 16384 && lds_set[dev][ki].load(std::memory_order_relaxed) < lds) {      // (the kernel holds ~33 KB of static LDS)
+  if (lds > 16384 && lds_set[dev][ki].load(std::memory_order_relaxed) < lds) {      // (plus 2.2 - 9.2 KB of static LDS: ao_max_cache)
     MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
                "mq_decode_attention_oproj: %zu bytes of dynamic LDS rejected", lds);
     lds_set[dev][ki].store(lds, std::memory_order_relaxed);

@@ -125,12 +125,30 @@ class DecodeEngine:
     LONG_FROM, LONG_SPLITS = 768, 4      # five launches: the split attention launch from LONG_FROM cached positions on
     LONG4_FROM = 1024                    # four launches: the 1024-thread attention + o_proj launch from here on (mq_decode_attention_oproj_args.threads):
                                          # 256 / 1024 threads at 256 | 512 | 1024 | 2048 positions: 1768 | 1701 | 1555 | 1331 against 1669 | 1646 | 1595 | 1482 tok/s
+    # The largest cache_len each attention launch serves (csrc/mq_decode.hip, ao_max_cache / kAttnMaxCache): 160 KiB of LDS per workgroup
+    # holds the kernel's static LDS plus 4 (five launches) or 7 (four launches) bytes per cached position.  Static LDS from hipcc
+    # -Rpass-analysis=kernel-resource-usage, head_dim -> bytes: five launches 8336 / 8432 / 8624 / 9008 (4 x 32768 fits: the C entry's
+    # 32768 binds); four launches 2240 / 2368 / 2624 / 3136 at 256 threads, 8528 / 8656 / 8912 / 9424 at 1024 threads.
+    LDS_BYTES = 160 * 1024
+    ATTN_MAX_CACHE = 32768
+    AO_STATIC_LDS = {256: {32: 2240, 64: 2368, 128: 2624, 256: 3136}, 1024: {32: 8528, 64: 8656, 128: 8912, 256: 9424}}
+
+    @classmethod
+    def max_cache_len(cls, launches: int, head_dim: int, threads: Optional[int] = None) -> int:
+        """Largest cache_len the attention launch of the `launches` chain admits at this head_dim.  Four launches: threads 256 / 1024 for
+        one variant, None for what an engine needs (it replays both, the 1024-thread one from long_from on)."""
+        if launches == 5:
+            return cls.ATTN_MAX_CACHE
+        if threads is None:
+            return min(cls.max_cache_len(4, head_dim, t) for t in cls.AO_STATIC_LDS)
+        return (cls.LDS_BYTES - cls.AO_STATIC_LDS[threads][head_dim]) // 7 // 16 * 16
 
     def __init__(self, model, cache_len: int = 2048, attn_splits: Optional[int] = None, prefetch: float = 0.5, prefetch_delay_us: Optional[float] = None,
                  launches: int = 4, long_from: Optional[int] = None):
         """launches: 4 (round 6, default) = per layer {norm + q|k|v, RoPE / cache append / attention + o_proj's contraction, o_proj's
         epilogue + norm + w1|w3 + gate, w2}; 5 = round 2-5's chain with o_proj as a launch of its own.  A geometry the 4-launch kernels
-        do not serve falls back to 5 (self.launches says which).  The 4-launch chain keeps the VALUE cache transposed in 16-position chunks
+        do not serve -- incl. a cache_len above max_cache_len(4, head_dim) -- falls back to 5 (self.launches says which); a cache_len
+        above max_cache_len(5, head_dim) raises RuntimeError.  The 4-launch chain keeps the VALUE cache transposed in 16-position chunks
         ([kv_heads, cache_len / 16, head_dim, 16]: its p.v sweep is v_dot4 work on coalesced KiB requests); use cached_values() / load_cached_values() to read / write it in
         the logical [kv_heads, positions, head_dim] layout."""
         from .llama import LlamaForCausalLM
@@ -142,7 +160,7 @@ class DecodeEngine:
         self.dev, self.cache_len = dev, int(cache_len)
         self._prefetch = (prefetch, prefetch_delay_us)           # (delay None: by chain, once self.launches is known)
         self.cos, self.sin = model.cos.contiguous(), model.sin.contiguous()
-        self.oproj_geom = self._oproj_geometry(s, self.cos.shape[1]) if launches == 4 and self.cache_len % 16 == 0 else None
+        self.oproj_geom = self._chain_geometry(s, self.cos.shape[1], self.cache_len, launches)
         self.launches = 4 if self.oproj_geom is not None else 5
         self.v_transposed = self.launches == 4
         self.long_from = self.LONG4_FROM if long_from is None else int(long_from)      # (four launches) first position of the long-cache graph
@@ -181,6 +199,17 @@ class DecodeEngine:
         self.graph = None
         self.graph_long = None
         self._lower()
+
+    @classmethod
+    def _chain_geometry(cls, s, rot_dim, cache_len, launches):
+        """_oproj_geometry when the four-launch chain is asked for and serves this shape AND cache_len, else None (five launches);
+        RuntimeError when the five-launch attention cannot hold cache_len either."""
+        if not 0 < cache_len <= cls.max_cache_len(5, s.head_dim):
+            raise RuntimeError(f"DecodeEngine: cache_len={cache_len} is outside 1 .. {cls.max_cache_len(5, s.head_dim)}, the cached positions "
+                               f"the attention launch holds in LDS")
+        if launches != 4 or cache_len % 16 or s.head_dim not in cls.AO_STATIC_LDS[256] or cache_len > cls.max_cache_len(4, s.head_dim):
+            return None
+        return cls._oproj_geometry(s, rot_dim)
 
     @staticmethod
     def _oproj_geometry(s, rot_dim):
@@ -513,6 +542,7 @@ class DecodeEngine:
                     self.pos.add_(1)
             graphs.append(g)
             self.tok.copy_(tok0); self.pos.copy_(pos0)
+        self._set_splits(*self._variants()[0])                  # a direct launch after capture() runs the base variant again
         self._host_pos = hp0
         self.graph, self.graph_long = graphs[0], (graphs[1] if len(graphs) > 1 else None)
         return self

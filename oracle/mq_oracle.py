@@ -566,3 +566,101 @@ def attention_sim(q, k, v, cos, sin, heads, kv_heads, qk: tuple, pv: tuple, exac
     p = (e / e.sum(axis=-1, keepdims=True, dtype=F32)).astype(F32)
     out = _qmatmul_exact(p, vh, *pv, double_scale=True) if exact_int else qmatmul_sim(p, vh, *pv)
     return out.transpose(1, 0, 2).reshape(S, heads * D)
+
+
+# ----------------------------------------------------------------------------------------------
+# a10 (one decode step)  row `pos` of attention_sim from a KV cache of int8 indices
+# ----------------------------------------------------------------------------------------------
+def quantizer_oracle_from(scale, offset, qmin, qmax) -> QuantizerOracle:
+    """A static per-tensor QuantizerOracle on a given grid (e.g. a torch Quantizer's scale / offset / qmin / qmax)."""
+    g = QuantizerOracle(bitwidth=int(round(np.log2(float(qmax) - float(qmin) + 1))))
+    g.scale, g.offset, g.qmin, g.qmax = F32(scale), F32(offset), int(qmin), int(qmax)
+    return g
+
+
+def _index(x, g: QuantizerOracle):
+    return quantize_index(x, g.scale, g.offset, g.qmin, g.qmax)
+
+
+def decode_attention_step(q, k, v, k_cache, v_cache, pos, cos_row, sin_row, heads, kv_heads, qk: tuple, pv: tuple,
+                          o_in: QuantizerOracle | None = None):
+    """One head-group's decode step at position `pos` as the reference computes row `pos` of attention_sim(..., exact_int=True), from
+    the engine's state: q [heads*D], k / v [kv_heads*D] fp32 rows of the new token (before RoPE); k_cache / v_cache [kv_heads, >= pos, D]
+    int8 indices - 128 on qk.input2 / pv.input2 (the LOGICAL value layout); cos_row / sin_row [rot_dim] (rot_dim < D: partial rotary).
+    qk = (input, input2, output) and pv = (input, input2, output) QuantizerOracles; o_in: the grid o_proj reads pv's output on (None: pv's
+    output grid).  The softmax is evaluated twice: in fp32 in the reference's order (np.exp, np.sum of the row, one division) and in
+    float64 (from the same fp32 scores).  Returns a dict:
+      k_new / v_new [kv_heads, D] int8   the bytes the step appends at `pos`
+      scores [heads, T] fp32             qk_bmm output / sqrt(D), T = pos + 1
+      p_idx / p_idx64 [heads, T] int64   pv.input indices of the probabilities (fp32 / float64 softmax)
+      p_t64 [heads, T] float64           the float64 probabilities divided by pv.input's scale (pre-rounding value of the index)
+      iv [kv_heads, T, D] fp32           the value indices (0 .. 255) incl. the new position's
+      acc [heads, D] int64               sum_t (ip - zp)(iv - zv) from the fp32 probabilities
+      y [heads*D] fp32                   pv_bmm's output (row `pos` of attention_sim)
+      out_q [heads*D] int8               o_proj's input image (index on o_in - 128): what attn_q / out_q hold
+    """
+    qa, qb, qo = qk
+    pa, pb, po = pv
+    o_in = po if o_in is None else o_in
+    q = np.asarray(q, F32).reshape(heads, 1, -1)
+    D = q.shape[-1]
+    k = np.asarray(k, F32).reshape(kv_heads, 1, D)
+    v = np.asarray(v, F32).reshape(kv_heads, D)
+    cos_row, sin_row = np.asarray(cos_row, F32)[None], np.asarray(sin_row, F32)[None]
+    T = int(pos) + 1
+    iq = _index(rope_partial(q, cos_row, sin_row)[:, 0], qa)                        # [heads, D]
+    ik_new = _index(rope_partial(k, cos_row, sin_row)[:, 0], qb)
+    iv_new = _index(v, pb)
+    k_new = (ik_new.astype(np.int64) - 128).astype(np.int8)
+    v_new = (iv_new.astype(np.int64) - 128).astype(np.int8)
+    ik = np.concatenate([np.asarray(k_cache)[:, :pos].astype(F32) + F32(128), ik_new[:, None]], axis=1)        # [kv, T, D] indices
+    iv = np.concatenate([np.asarray(v_cache)[:, :pos].astype(F32) + F32(128), iv_new[:, None]], axis=1)
+    rep = heads // kv_heads
+    # q.k^T exactly over the indices (every partial sum is an integer below D 255^2 < 2^24: exact in fp32), one fp32 multiply, the output
+    # quantizer, / sqrt(D)       (_qmatmul_exact, double_scale False; a KV head's query heads together: no repeat_kv copy)
+    acc_qk = np.matmul((iq - F32(qa.offset)).reshape(kv_heads, rep, D), (ik - F32(qb.offset)).transpose(0, 2, 1)).reshape(heads, T)
+    acc_qk = np.rint(acc_qk).astype(np.int64)
+    alpha_qk = F32(F32(qa.scale) * F32(qb.scale))
+    scores = (qo.forward((acc_qk.astype(F32) * alpha_qk).astype(F32)) / F32(np.sqrt(F32(D)))).astype(F32)
+    # softmax: fp32 in attention_sim's order, and float64
+    x = (scores - scores.max(axis=-1, keepdims=True)).astype(F32)
+    e = np.exp(x, dtype=F32)
+    p = (e / e.sum(axis=-1, keepdims=True, dtype=F32)).astype(F32)
+    s64 = scores.astype(np.float64)
+    e64 = np.exp(s64 - s64.max(axis=-1, keepdims=True))
+    p_t64 = e64 / e64.sum(axis=-1, keepdims=True) / np.float64(F32(pa.scale))
+    p_idx = _index(p, pa).astype(np.int64)
+    p_idx64 = np.clip(np.rint(p_t64) + np.float64(F32(pa.offset)), pa.qmin, pa.qmax).astype(np.int64)
+    acc = decode_pv_sums(p_idx, iv, pa, pb)
+    y, out_q = decode_pv_output(acc, pa, pb, po, o_in)
+    return dict(k_new=k_new, v_new=v_new, iv=iv, scores=scores, p_idx=p_idx, p_idx64=p_idx64, p_t64=p_t64, acc=acc, y=y, out_q=out_q)
+
+
+def decode_pv_sums(p_idx, iv, pa: QuantizerOracle, pb: QuantizerOracle, p_hi=None):
+    """Exact p.v sums [heads, D] of one decode step: sum_t (ip - zp)(iv - zv) from the probability indices p_idx [heads, T] and the value
+    indices iv [kv_heads, T, D] (0 .. 255; float64 products and sums of integers below 2^53: exact).  p_hi: per-position upper indices --
+    then (lowest, highest) sums over every choice of indices between p_idx and p_hi (the sum is linear in each index)."""
+    kv, T, D = iv.shape
+    heads = p_idx.shape[0]
+    w = np.asarray(iv, np.float64) - np.float64(pb.offset)
+    pl = (np.asarray(p_idx, np.float64) - np.float64(pa.offset)).reshape(kv, heads // kv, T)
+    mm = lambda a, b: np.rint(np.matmul(a, b)).astype(np.int64).reshape(heads, D)      # noqa: E731
+    if p_hi is None:
+        return mm(pl, w)
+    ph = (np.asarray(p_hi, np.float64) - np.float64(pa.offset)).reshape(kv, heads // kv, T)
+    wp, wn = np.maximum(w, 0.0), np.minimum(w, 0.0)
+    return mm(pl, wp) + mm(ph, wn), mm(ph, wp) + mm(pl, wn)
+
+
+def decode_pv_output(acc, pa: QuantizerOracle, pb: QuantizerOracle, po: QuantizerOracle, o_in: QuantizerOracle):
+    """Exact p.v sums acc [heads, D] -> (pv output y [heads*D] fp32, o_proj's input image [heads*D] int8); monotone in acc."""
+    alpha = F32(F32(pa.scale) * F32(pb.scale))
+    y = po.forward((np.asarray(acc).astype(np.float64) * np.float64(alpha)).astype(F32)).reshape(-1)
+    out_q = (_index(y, o_in).astype(np.int64) - 128).astype(np.int8)
+    return y, out_q
+
+
+def oproj_int_sums(w, w_zp, a8):
+    """o_proj's exact split-K sums over an int8 image: sum_k w[n, k] a8[k] - w_zp[n] sum_k a8[k]  (w [N, K] int8, a8 [K] int8)."""
+    a = np.asarray(a8).astype(np.int64)
+    return np.asarray(w).astype(np.int64) @ a - np.asarray(w_zp).astype(np.int64) * a.sum()
