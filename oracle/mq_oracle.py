@@ -664,3 +664,252 @@ def oproj_int_sums(w, w_zp, a8):
     """o_proj's exact split-K sums over an int8 image: sum_k w[n, k] a8[k] - w_zp[n] sum_k a8[k]  (w [N, K] int8, a8 [K] int8)."""
     a = np.asarray(a8).astype(np.int64)
     return np.asarray(w).astype(np.int64) @ a - np.asarray(w_zp).astype(np.int64) * a.sum()
+
+
+# ----------------------------------------------------------------------------------------------
+# a8 / a9 (one decode step)  mq_decode_gemv and mq_decode_head launch by launch
+# ----------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24                 # unit roundoff of fp32
+
+
+def _gamma(n):
+    """gamma_n = n u / (1 - n u): the relative error bound of n fp32 roundings in a row (Higham, Lemma 3.1)."""
+    return n * U32 / (1.0 - n * U32)
+
+
+def _tie_dist(t):
+    """Distance of each pre-rounding value t (float64) from the nearest rounding boundary (a half-integer)."""
+    t = np.asarray(t, np.float64)
+    return np.abs(np.abs(t - np.floor(t) - 0.5))
+
+
+def _fq_div(v, g):
+    """Division-form fake quant (the reference's, and the kernel's Grid.fq); g None: the grid is off."""
+    if g is None:
+        return np.asarray(v, F32)
+    return dequantize_index(quantize_index(v, g.scale, g.offset, g.qmin, g.qmax), g.scale, g.offset)
+
+
+def _inv(g):
+    """1 / scale rounded to fp32, as mq_decode_pack_grids stores it."""
+    return (F32(1.0) / F32(g.scale)).astype(F32)
+
+
+def _fq_recip(v, g):
+    """The GEMV epilogues' output quantizer in its reciprocal form: clamp(rint(v * fl(1/s)) + o) -> (q - o) s; fminf / fmaxf clamp."""
+    v = np.asarray(v, F32)
+    if g is None:
+        return v
+    q = (np.rint((v * _inv(g)).astype(F32)) + F32(g.offset)).astype(F32)
+    q = np.minimum(np.maximum(q, F32(g.qmin)), F32(g.qmax))
+    return ((q - F32(g.offset)).astype(F32) * F32(g.scale)).astype(F32)
+
+
+def _wrap32(v):
+    return (np.asarray(v, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def decode_gemv_prologue(K, x=None, xq=None, norm_w=None, norm_bias=None, layernorm=0, norm_in=None, eps=0.0, a_grid=None,
+                         o_acc=None, o_alpha=None, o_ct=None, o_bias=None, o_out=None):
+    """The int8 activation image a mq_decode_gemv launch contracts, from the fields of mq_decode_gemv_args (grids: QuantizerOracle or
+    None for an absent grid; norm_w is the already fake-quantised weight vector the engine passes).  Modes as the C entry picks them:
+    xq -> the image as given (XM_I8); norm_w -> QRMSNorm / QLayerNorm (XM_NORM / XM_LNORM: norm_in fake quant, then the norm); else the
+    fp32 row itself (XM_F32).  o_acc given (OPRE): the row is first x + Qo(fl(fl(float(acc + ct)) o_alpha) + o_bias)) in the kernel's
+    order, Qo in the reciprocal form -- returned as x_mid, bit for bit.
+    Returns a dict:
+      image [K] int8      index - 128 on a_grid, with the norm evaluated in float64 (rint of t64: the exact image away from ties)
+      rs int              sum of the image
+      t64 [K] float64     the pre-rounding value of each index: (norm value in float64) / scale (None for XM_I8)
+      tie [K] bool        where the kernel's fp32 norm may round to the neighbouring index: |t64| within the fp32 error bound of the
+                          kernel's documented order (prologue reduction: <= 16 adds per thread, a 6-level DPP tree, 8 waves in turn)
+                          of a rounding boundary
+      x_mid [K] fp32      (OPRE) the activation row behind o_proj's epilogue and the residual add"""
+    if xq is not None:
+        img = np.asarray(xq, np.int8).reshape(-1)[:K].copy()
+        return dict(image=img, rs=int(img.astype(np.int64).sum()), t64=None, tie=np.zeros(K, bool), x_mid=None)
+    x = np.asarray(x, F32).reshape(-1)[:K].copy()
+    x_mid = None
+    if o_acc is not None:
+        tt = _wrap32(np.asarray(o_acc, np.int64) + np.asarray(o_ct, np.int64))
+        f = (tt.astype(F32) * np.asarray(o_alpha, F32)).astype(F32)
+        f = (f + (np.asarray(o_bias, F32) if o_bias is not None else F32(0))).astype(F32)
+        x = (x + _fq_recip(f, o_out)).astype(F32)
+        x_mid = x.copy()
+    n_red = 4 * ((K + 2047) // 2048) + 6 + 8       # adds on the longest path of the prologue's float reductions
+    if norm_w is None:                             # XM_F32: the row itself
+        v64, err = x.astype(np.float64), np.zeros(K)
+    else:
+        xi = _fq_div(x, norm_in).astype(np.float64)
+        w = np.asarray(norm_w, F32).astype(np.float64)
+        b = np.asarray(norm_bias, F32).astype(np.float64) if norm_bias is not None else None
+        v64, err = _norm64(xi, w, b, bool(layernorm), float(F32(eps)), n_red)
+    s, o = np.float64(F32(a_grid.scale)), np.float64(F32(a_grid.offset))
+    t64 = v64 / s
+    idx = np.clip(np.rint(t64) + o, a_grid.qmin, a_grid.qmax)
+    bound = (err + U32 * np.abs(v64)) / s * (1.0 + 1e-6) + 1e-300   # + the quotient's rounding (div_by_scale is the IEEE quotient)
+    tie = _tie_dist(t64) <= bound
+    img = (idx.astype(np.int64) - 128).astype(np.int8)
+    return dict(image=img, rs=int(img.astype(np.int64).sum()), t64=t64, tie=tie, x_mid=x_mid)
+
+
+def _norm64(xi, w, b, layernorm, eps, n_red):
+    """Norm value of an fp32 row in float64 and a per-element bound of the fp32 kernel's error against it, for a reduction whose
+    longest accumulation path has n_red adds; then ((xi r + (-r mu)) w + b) (LayerNorm) or w (xi r) (RMS) in fp32 rounding.
+    w / b None: no weight / bias (the head's optional affine)."""
+    K = xi.shape[0]
+    ax = np.abs(xi)
+    if layernorm:
+        mu = xi.sum() / K
+        var = ((xi - mu) ** 2).sum() / K
+        r = 1.0 / np.sqrt(var + eps)
+        z = (xi - mu) * r
+        e_mu = _gamma(n_red + 1) * ax.sum() / K
+        dv = (_gamma(n_red + 4) * (var + e_mu ** 2) + e_mu ** 2) / (var + eps) + 2 * U32
+        dr = dv / 2 + dv * dv + 3 * U32
+        ez = dr * np.abs(z) + r * (1 + dr) * (e_mu + U32 * (ax + abs(mu) + e_mu))
+        ez = ez + U32 * (np.abs(z) + ez)
+    else:
+        ms = (xi * xi).sum() / K
+        r = 1.0 / np.sqrt(ms + eps)
+        z = xi * r
+        ez = _gamma(n_red + 5) * np.abs(z)          # squares, the reduction, / K, + eps, sqrt, 1 / ., x r
+    v, ev = z, ez
+    if w is not None:
+        v = z * w
+        ev = np.abs(w) * ez + U32 * (np.abs(v) + np.abs(w) * ez)
+    if b is not None:
+        v = v + b
+        ev = ev + U32 * (np.abs(v) + ev)
+    return v, ev
+
+
+def decode_gemv_sums(image, w, w4=False):
+    """Exact contractions sum_k w[n, k] image[k] (int64) of the launch's weight rows: w int8 [N, K] (index - 128) or, w4, packed unsigned
+    nibbles [N, K / 2] (pack_w4's layout: 16-byte group g of a row holds k = 32 g + j in the low and 32 g + j + 16 in the high nibble
+    of byte j).  Gate launches: rows 2i / 2i+1 are w1 / w3 row i; [N] in row order either way.  (float64 products and sums of integers
+below 2^53: exact.)"""
+    a = np.asarray(image, np.int64)
+    wi = unpack_w4(w, 0) if w4 else np.asarray(w, np.int8)
+    assert wi.shape[1] * 128 * 128 < 2 ** 53
+    return np.rint(wi.astype(np.float64) @ a.astype(np.float64)).astype(np.int64)
+
+
+def decode_gemv_epilogue(sums, rs, alpha, w_zp, col_term, bias=None, seg_end=None, out_grid=(None, None, None), resid=None, gate=False,
+                         gate_act=0, gate_mid=None, gate_actout=None, gate_out=None):
+    """The epilogue of mq_decode_gemv, bit for bit in fp32: tt = sum - zp rs + ct (int32 wraparound), e = fl(fl(float(tt) alpha) + bias)
+    (two roundings, no fma); not gate: the output quantizer of row n's segment (seg_end) in the reciprocal form, then fl(resid + .);
+    gate: fa / fb = Qout0 / Qout1 of rows 2i / 2i+1 (reciprocal form), QSiLU (gate_act 0: fa Qmid(1 / (1 + exp(-fa))) ) or QGELU
+    (0.5 fa (1 + erf(fa / sqrt 2))), Qactout, the product with fb, and the index on gate_out (division form) - 128.
+    Every quantizer is also evaluated in the reference's division form (qmodule.py): `y_div`, `gate_q_div`.
+    Returns a dict: tt [N] int32, e [N] fp32, y [N or N / 2] fp32, y_div; gate: fa, fb, gate_q [N / 2] int8, gate_q_div, prod (fp32,
+    what y holds in gate mode), and for the transcendental chain (exp / erf are not correctly rounded anywhere) the pre-rounding value
+    of each quantizer in float64 (t_mid, t_act, t_out; None where the grid is off) and `tie`: where one of them lies within 2^-17
+    relative of a rounding boundary, so that a different last bit of exp / erf may move gate_q by one."""
+    sums = np.asarray(sums, np.int64)
+    N = sums.shape[0]
+    tt = _wrap32(sums - np.asarray(w_zp, np.int64) * np.int64(rs) + np.asarray(col_term, np.int64))
+    e = (tt.astype(F32) * np.asarray(alpha, F32)).astype(F32)
+    e = (e + (np.asarray(bias, F32) if bias is not None else F32(0))).astype(F32)
+    out = dict(tt=tt, e=e)
+    if not gate:
+        s0, s1 = (seg_end if seg_end is not None else (N, N))
+        rows = np.arange(N)
+        seg = np.where(rows < s0, 0, np.where(rows < s1, 1, 2))
+        y, y_div = e.copy(), e.copy()
+        for k in range(3):
+            m = seg == k
+            y[m], y_div[m] = _fq_recip(e[m], out_grid[k]), _fq_div(e[m], out_grid[k])
+        if resid is not None:
+            r = np.asarray(resid, F32)
+            y, y_div = (r + y).astype(F32), (r + y_div).astype(F32)
+        out.update(y=y, y_div=y_div)
+        return out
+    ea, eb = e[0::2], e[1::2]
+    fa, fb = _fq_recip(ea, out_grid[0]), _fq_recip(eb, out_grid[1])
+    chain = _gate_chain(fa, fb, gate_act, gate_mid, gate_actout, gate_out)
+    chain_div = _gate_chain(_fq_div(ea, out_grid[0]), _fq_div(eb, out_grid[1]), gate_act, gate_mid, gate_actout, gate_out)
+    out.update(fa=fa, fb=fb, gate_q=chain["q"], prod=chain["prod"], y=chain["prod"], t_mid=chain["t_mid"], t_act=chain["t_act"],
+               t_out=chain["t_out"], tie=chain["tie"], gate_q_div=chain_div["q"], y_div=chain_div["prod"], tie_div=chain_div["tie"])
+    return out
+
+
+def _gate_chain(fa, fb, act, g_mid, g_act, g_out):
+    tol = 2.0 ** -17
+
+    def near(t):
+        return _tie_dist(t) <= tol * np.abs(t) + 1e-30
+
+    tie = np.zeros(fa.shape, bool)
+    t_mid = t_act = None
+    if act == 0:
+        with np.errstate(over="ignore"):
+            g = (F32(1.0) / (F32(1.0) + np.exp(-fa).astype(F32)).astype(F32)).astype(F32)
+            g64 = 1.0 / (1.0 + np.exp(-fa.astype(np.float64)))
+        if g_mid is not None:
+            t_mid = g64 / np.float64(F32(g_mid.scale))
+            tie |= near(t_mid)
+        rr = (fa * _fq_div(g, g_mid)).astype(F32)
+        rr64 = fa.astype(np.float64) * (_fq_div(g, g_mid).astype(np.float64) if g_mid is not None else g64)
+    else:
+        from scipy.special import erf
+        h = (fa * F32(0.70710678118654752440)).astype(F32)
+        rr = ((F32(0.5) * fa).astype(F32) * (F32(1.0) + erf(h.astype(np.float64)).astype(F32)).astype(F32)).astype(F32)
+        rr64 = 0.5 * fa.astype(np.float64) * (1.0 + erf(fa.astype(np.float64) / np.sqrt(2.0)))
+    if g_act is not None:
+        t_act = rr64 / np.float64(F32(g_act.scale))
+        tie |= near(t_act)
+        a64 = _fq_div(rr, g_act).astype(np.float64)
+    else:
+        a64 = rr64
+    prod = (_fq_div(rr, g_act) * fb).astype(F32)
+    t_out = a64 * fb.astype(np.float64) / np.float64(F32(g_out.scale))
+    tie |= near(t_out)
+    qi = quantize_index(prod, g_out.scale, g_out.offset, g_out.qmin, g_out.qmax)
+    qi = np.where(np.isnan(qi), F32(g_out.qmin), qi)
+    q = (qi.astype(np.int64) - 128).astype(np.int8)
+    return dict(q=q, prod=prod, t_mid=t_mid, t_act=t_act, t_out=t_out, tie=tie)
+
+
+def decode_gemv_launch(K, N, w, alpha, w_zp, col_term, w4=False, gate=False, bias=None, seg_end=None, out_grid=(None, None, None),
+                       resid=None, gate_act=0, gate_mid=None, gate_actout=None, gate_out=None, **prologue):
+    """One mq_decode_gemv launch from the fields of mq_decode_gemv_args: decode_gemv_prologue (the image and its row sum) ->
+    decode_gemv_sums -> decode_gemv_epilogue.  Returns the epilogue's dict plus image, rs, t64, tie_image (the prologue's `tie`), x_mid."""
+    pro = decode_gemv_prologue(K, **prologue)
+    sums = decode_gemv_sums(pro["image"], w, w4)
+    assert sums.shape[0] == N
+    out = decode_gemv_epilogue(sums, pro["rs"], alpha, w_zp, col_term, bias, seg_end, out_grid, resid, gate, gate_act, gate_mid,
+                               gate_actout, gate_out)
+    out.update(image=pro["image"], rs=pro["rs"], t64=pro["t64"], tie_image=pro["tie"], x_mid=pro["x_mid"], sums=sums)
+    return out
+
+
+def decode_head_norm(x, norm_w=None, norm_b=None, layernorm=0, eps=1e-5):
+    """mq_decode_head's activation row in float64 and a per-element bound of the kernel's fp32 error on it: final RMSNorm
+    (w (x r), r = 1 / sqrt(mean(x^2) + eps); no weight: x itself, unnormalised) or LayerNorm (x r + (-r mu), then * w, + b, each
+    optional).  The kernel's reductions: ceil(K / 256) adds per thread, a 6-level DPP tree, then (s0 + s1) + (s2 + s3).
+    Returns (s64 [K], err [K])."""
+    x = np.asarray(x, F32).reshape(-1).astype(np.float64)
+    K = x.shape[0]
+    n_red = (K + 255) // 256 + 6 + 2
+    w = np.asarray(norm_w, F32).astype(np.float64) if norm_w is not None else None
+    b = np.asarray(norm_b, F32).astype(np.float64) if norm_b is not None else None
+    if not layernorm and w is None:
+        return x, np.zeros(K)
+    return _norm64(x, w, b if layernorm else None, bool(layernorm), float(F32(eps)), n_red)
+
+
+def decode_head_logits(w64, s64, err, bias64=None):
+    """Logits of rows of the fp32 lm_head in float64 and a per-logit bound of the kernel's fp32 error: w64 [R, K] float64 rows (numpy or
+    torch: only @, abs and arithmetic are used), s64 / err [K] from decode_head_norm (same array type).  The kernel's dot product:
+    one rounded product per term, 4 ceil(K / 256) terms added in order per lane, a 6-level DPP tree, then fl(acc + bias).
+    Returns (logits64 [R], bound [R])."""
+    K = s64.shape[0]
+    n = 4 * ((K + 255) // 256) + 6
+    aw = abs(w64)
+    lg = w64 @ s64
+    mag = aw @ (abs(s64) + err)
+    bound = aw @ err + _gamma(n) * mag + K * 2.0 ** -52 * mag        # (the last term: this float64 evaluation's own rounding)
+    if bias64 is not None:
+        lg = lg + bias64
+        bound = bound + U32 * (abs(lg) + bound)
+    return lg, bound
