@@ -539,7 +539,14 @@ int mq_decode_head(const float* x, const float* norm_weight, const float* norm_b
  * Causal mask only (the mask of hf_model.py:1180-1205 at prefill); the scores are divided by sqrt(D) AFTER qk_out, as the reference.
  * Scratch (caller-owned, overwritten): q_i8 [heads][seq][D], k_i8 [kv_heads][seq][D], vt_i8 [kv_heads][seq/64][D][64] (values
  * transposed, keys permuted inside each 64-block), q_rowsum [heads][seq], k_rowsum [kv_heads][seq] (the zero-point terms of the integer
- * q.k^T, derived from the row sums of the images).  q_i8 / q_rowsum may be left untouched: at head_dim 64 with a 16-bit score grid and
+ * q.k^T, derived from the row sums of the images).  Stored bytes are index - 128.  Exactly:
+ *   k_i8[h][t][d]             = ik(t, d) - 128
+ *   k_rowsum[h][t]            = -(zq - 128) * sum_d (ik(t, d) - 128)                      (zq: qk_a's offset)
+ *   vt_i8[h][t/64][d][kappa]  = iv(t, d) - 128, key t = 64 b + 16 j + 4 tq + e stored at kappa = 16 tq + 4 j + e (j, tq, e in 0..3)
+ *   v_prefix[h][b][d]         = sum over keys 0 .. 64 b + 63 of (iv(t, d) - 128)            (head_dim 128 / 256)
+ *   k_f16 (head_dim 64)       = fp16(ik(t, d) - zk), fragment-blocked per 64-key block b: half index
+ *                               ((h * blocks + b) * 8 + 2 (r / 16) + (d % 16) / 8) * 512 + ((r % 16) + 16 (d / 16)) * 8 + d % 8, r = t - 64 b
+ *   (blocks = seq / 64, or cache_seq / 64 with a cache.)  q_i8 / q_rowsum may be left untouched: at head_dim 64 with a 16-bit score grid and
  * full rotary the attention workgroups prepare their own q rows in registers (mq_attention_set_fused_q in the tuning header).
  * Limits: head_dim 64, 128 or 256 (every "64" of a layout above reads head_dim; the int8 output image is [rows, heads*head_dim]),
  * seq % 64 == 0, seq <= 65536.  The integer contractions are exact; see DESIGN.md 4.5 for the rounding points. */

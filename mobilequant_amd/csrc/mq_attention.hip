@@ -267,8 +267,10 @@ __global__ void __launch_bounds__(256) attention_prep_kernel(const mq_attention_
       for (int i = 0; i < 8; ++i) hw[i] = pack_h2(__fsub_rn(qi[2 * i], g.o), __fsub_rn(qi[2 * i + 1], g.o));
       // index - offset is exact in fp16 and sum_d (iq - zq)(ik - zk) < 2^24 only while |index - offset| <= 511, i.e. for an
       // offset in [-256, 511].  compute_scale_offset_from_min_max (qmodule.py:55-62) does not force zero into the range, so a narrow
-      // range far from zero (or a loaded / trained offset) lies outside: poison the image (NaN scores -> NaN outputs, as mq_qmatmul's
-      // `sane`) instead of contracting inexactly in silence; ops.attention_quant(f16=False) serves such a grid on the int8 contraction
+      // range far from zero (or a loaded / trained offset) lies outside: poison the image (NaN scores; the score clamp's v_med3 turns
+      // them into a grid end, so the outputs come out WRONG, not NaN -- measured: 96 % of them).  Callers route such a grid to the
+      // int8 contraction: ops.attention_quant passes no fp16 images when an offset lies outside ops.F16_OFFSETS (f16=None reads them
+      // on the host; the fused layer passes f16)
       if (!(g.o >= -256.f && g.o <= 511.f)) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) hw[i] = 0x7e007e00u;

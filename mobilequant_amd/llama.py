@@ -236,13 +236,15 @@ def _fused_attention_forward(self, x, cos, sin, mask, cache=None, pos: int = 0, 
             quantizer.scale.data, quantizer.offset.data = quantizer.scale.to(x.device), quantizer.offset.to(x.device)
             g = Q.QRMSNorm._grid_or_none(quantizer)
         grids[name] = g
+    akw_f16 = dict(f16=_f16_scores_ok(qk.input_quantizer, qk.input2_quantizer))
     img = cache if isinstance(cache, ImageCache) else None      # chunked prefill: K / vT images of the earlier chunks
     if img is not None:
         cache = None
         if len(img.per_sequence) != B or pos + S > img.per_sequence[0]["rows"]:
             raise RuntimeError("mobilequant_amd: image cache built for another batch size or too short for this position")
         img.filled = pos + S
-    akw = [dict(head_dim=s.head_dim) if img is None else dict(head_dim=s.head_dim, cache=img.per_sequence[b], pos0=pos) for b in range(B)]
+    akw = [dict(head_dim=s.head_dim, **akw_f16) if img is None else dict(head_dim=s.head_dim, cache=img.per_sequence[b], pos0=pos, **akw_f16)
+           for b in range(B)]
     fused_qkv = _qkv_indices(self, x) if cache is None and getattr(self, "fuse_qkv", True) else None
     if fused_qkv is not None:
         idx, in_grids = fused_qkv                    # uint8 [B*S, (H + 2 KV) * 64]: one GEMM, three output grids
@@ -277,20 +279,39 @@ def _fused_attention_forward(self, x, cos, sin, mask, cache=None, pos: int = 0, 
             rs = torch.empty(M, dtype=torch.int32, device=x.device)
             if img is None and B > 1:                # the whole batch in one launch pair (sequence b owns image rows b * S ...)
                 ops.attention_quant(*batched, cos, sin, s.heads, s.kv_heads, grids, image=(q_i8, rs, 0, 128, tiled), want_out=False,
-                                    qkv_idx=batched_idx, head_dim=s.head_dim)
+                                    qkv_idx=batched_idx, head_dim=s.head_dim, **akw_f16)
             else:
                 for b in range(B):
                     ops.attention_quant(q[b], k[b], v[b], cos, sin, s.heads, s.kv_heads, grids, image=(q_i8, rs, b * S, 128, tiled), want_out=False,
                                         qkv_idx=qkv[b], **akw[b])
             return o_proj._int8_from_image(None, w_o, o_proj.bias, oq, q_i8, rs, 128, M if tiled else None, lead_shape=(B, S), resid=resid)
     if img is None and B > 1:
-        out = ops.attention_quant(*batched, cos, sin, s.heads, s.kv_heads, grids, qkv_idx=batched_idx, head_dim=s.head_dim)
+        out = ops.attention_quant(*batched, cos, sin, s.heads, s.kv_heads, grids, qkv_idx=batched_idx, head_dim=s.head_dim, **akw_f16)
     else:
         out = torch.stack([ops.attention_quant(q[b], k[b], v[b], cos, sin, s.heads, s.kv_heads, grids, qkv_idx=qkv[b], **akw[b]) for b in range(B)])
     if oq is not None and not oq.bypassed():
         Q._tag_grid(out, oq)
     out = o_proj(out)
     return out if resid is None else resid + out
+
+
+def _f16_scores_ok(*quantizers) -> bool:
+    """Whether the q / k grids' offsets let ops.attention_quant contract the scores in fp16 (ops.F16_OFFSETS).  The offsets are read on
+    the host once per grid version and kept on the quantizer; while a graph is being captured an unread grid takes the int8
+    contraction (exact for any grid) instead of a device read."""
+    from . import ops
+    from .quantization.qmodule import _ver
+    ok = True
+    for q in quantizers:
+        key = (q._gen if hasattr(q, "_gen") else 0, id(q.offset), _ver(q.offset))
+        hit = q.__dict__.get("_mq_offset_host")
+        if hit is None or hit[0] != key:
+            if torch.cuda.is_current_stream_capturing():
+                return False
+            hit = (key, float(q.offset.detach().reshape(-1)[0]))
+            q.__dict__["_mq_offset_host"] = hit
+        ok = ok and ops.attention_f16_offsets_ok(hit[1])
+    return ok
 
 
 def _qkv_indices(self, x):

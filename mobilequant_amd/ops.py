@@ -834,9 +834,17 @@ def attention_image_cache(kv_heads: int, head_dim: int, max_len: int, device) ->
             "v_pre": torch.zeros(kv_heads * (rows // 64) * head_dim, dtype=torch.int32, device=dev) if head_dim != 64 else None}
 
 
+F16_OFFSETS = (-256.0, 511.0)     # q / k offsets the f16 score contraction holds exactly: |index - offset| <= 511 (mq_attention.hip)
+
+
+def attention_f16_offsets_ok(*offsets: float) -> bool:
+    """True when the f16 score contraction of attention_quant is exact for q / k grids with these offsets."""
+    return all(F16_OFFSETS[0] <= float(o) <= F16_OFFSETS[1] for o in offsets)
+
+
 def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Optional[torch.Tensor], cos: torch.Tensor, sin: torch.Tensor,
                     heads: int, kv_heads: int, grids: dict, image=None, want_out: bool = True, qkv_idx=None, head_dim: int = 64,
-                    cache=None, pos0: int = 0):
+                    cache=None, pos0: int = 0, f16: Optional[bool] = None):
     """Quantized causal prefill attention of ONE sequence (mq_attention_quant; head_dim 64 or 256 -- "64" below reads head_dim): q [S, heads*64], k / v [S, kv_heads*64] fp32
     projection outputs before RoPE, cos / sin [S, 64]; grids: qk_a, qk_b, qk_out, pv_a, pv_b, pv_out -> (scale, offset, qmin, qmax)
     per tensor or None (qk_out / pv_out only).  Returns pv_bmm's output [S, heads*64] fp32 (o_proj's input layout).
@@ -847,7 +855,10 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     result is [B, S, heads*64] and sequence b owns rows row0 + b * S of the image.
     cache = attention_image_cache(...) + pos0: cache continuation (chunked prefill).  The cache already holds positions 0 .. pos0 - 1
     from earlier calls (same grids); q / k / v / cos / sin describe positions pos0 .. pos0 + S - 1, which are appended and attend to
-    everything before them.  pos0 % 64 == 0 (every chunk but the last is a multiple of 64 long)."""
+    everything before them.  pos0 % 64 == 0 (every chunk but the last is a multiple of 64 long).
+    f16: head_dim 64 with a score grid contracts q.k^T over fp16 images of the centred indices, exact only while both q / k offsets
+    lie in F16_OFFSETS (the prep kernel poisons the images with NaN otherwise).  True / False choose; None reads the offsets on the
+    host (int8 contraction while a graph is being captured: no device read there).  The int8 contraction is exact for any grid."""
     cos, sin = _f32(cos, "cos"), _f32(sin, "sin")
     D = int(head_dim)
     if D not in (64, 128, 256):
@@ -923,11 +934,20 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
         k_rs = torch.empty(nb * kv_heads * S, dtype=torch.int32, device=dev)
         v_pre = torch.empty(nb * kv_heads * (S // 64) * D, dtype=torch.int32, device=dev) if D != 64 else None
         k_f16 = torch.empty(nb * kv_heads * S * D, dtype=torch.float16, device=dev) if D == 64 else None
-    if k_f16 is not None and grids.get("qk_out") is not None:
+    if k_f16 is not None and grids.get("qk_out") is not None and f16 is None:
+        f16 = not torch.cuda.is_current_stream_capturing() and attention_f16_offsets_ok(
+            *(float(grids[n][1].detach().reshape(-1)[0]) for n in ("qk_a", "qk_b")))
+    if cache is not None:                # the f16 form reads the fp16 K image of the earlier chunks: only where every one wrote it
+        if pos0 == 0:
+            cache["k_f16_valid"] = True
+        f16 = f16 and cache.get("k_f16_valid", False)
+    if k_f16 is not None and grids.get("qk_out") is not None and f16:
         # head_dim 64 with a score grid: fp16 images of the centred q / k indices -> the f16 score contraction (mq_attention_args.q_f16)
         q_f16 = torch.empty(nb * heads * S * D, dtype=torch.float16, device=dev)
         keep += [q_f16, k_f16]
         a.q_f16, a.k_f16 = q_f16.data_ptr(), k_f16.data_ptr()
+    elif cache is not None:
+        cache["k_f16_valid"] = False
     if v_pre is not None:
         keep.append(v_pre)
         a.v_prefix = v_pre.data_ptr()

@@ -913,3 +913,187 @@ def decode_head_logits(w64, s64, err, bias64=None):
         lg = lg + bias64
         bound = bound + U32 * (abs(lg) + bound)
     return lg, bound
+
+
+# ----------------------------------------------------------------------------------------------
+# a10 (prefill, by rows)  rows of attention_sim(exact_int=True) for one sequence, and the kernel's error envelope
+# ----------------------------------------------------------------------------------------------
+def prefill_attention_rows(q, k, v, cos, sin, heads, kv_heads, qk: tuple, pv: tuple, rows, qkv_idx=None, in_grids=None):
+    """The requested query rows of attention_sim(..., exact_int=True) for one sequence of S positions, without an S x S tensor: the
+    cost is rows x S.  q [S, heads*D], k / v [S, kv_heads*D] fp32 before RoPE -- or qkv_idx uint8 [S, (heads + 2 kv_heads) * D] with
+    in_grids = (q_in, k_in, v_in) (anything with .scale / .offset): each segment reads (idx - o) * s in fp32, as mq_attention_quant
+    does.  cos / sin [S, rot_dim]; qk = (input, input2, output) and pv = (input, input2, output) QuantizerOracles (qk[2] / pv[2] may be
+    None); rows: absolute query positions.  Returns a dict (R = len(rows), T = S: keys past a row are masked):
+      ik8 / iv8 [kv, S, D] int8       the K / V images (index - 128) of every position
+      acc_qk [heads, R, T] int64      sum_d (iq - zq)(ik - zk), exact (0 where masked)
+      t64 [heads, R, T] float64       pre-rounding score index acc alpha / s_out + o (qk[2] None: acc alpha / sqrt(D), the value)
+      s_idx [heads, R, T] fp32        the reference's division-form score index (qk[2] None: the fp32 score)
+      scores [heads, R, T] fp32       qk_bmm output / sqrt(D), -inf where masked
+      p [heads, R, T] fp32            softmax in attention_sim's order (row of length S, masked terms 0, numpy's fp32 row sum)
+      p64 [heads, R, T] float64       softmax of the same scores in float64
+      p_idx / p_idx64 [heads, R, T]   pv.input indices of p / p64 (int64; masked keys: the zero point)
+      acc [heads, R, D] int64         sum_t (ip - zp)(iv - zv), exact
+      y [R, heads*D] fp32             pv_bmm's output (rows of attention_sim)
+      out_idx [R, heads*D]            its index on pv[2] (None when pv[2] is None)"""
+    qa, qb, qo = qk
+    pa, pb, po = pv
+    rows = np.asarray(rows, np.int64)
+    H, KV = int(heads), int(kv_heads)
+    if qkv_idx is not None:
+        idx = np.asarray(qkv_idx)
+        S = idx.shape[0]
+        D = idx.shape[1] // (H + 2 * KV)
+        idx = idx.reshape(S, H + 2 * KV, D).astype(F32)
+        q, k, v = (dequantize_index(idx[:, a:b], g.scale, g.offset).reshape(S, -1)
+                   for (a, b), g in zip(((0, H), (H, H + KV), (H + KV, H + 2 * KV)), in_grids))
+    S = np.asarray(k).shape[0]
+    D = np.asarray(q).shape[1] // H
+    cos, sin = np.asarray(cos, F32), np.asarray(sin, F32)
+    kr = rope_partial(np.asarray(k, F32).reshape(S, KV, D).transpose(1, 0, 2), cos, sin)
+    ik = _index(kr, qb)                                                               # [kv, S, D]
+    iv = _index(np.asarray(v, F32).reshape(S, KV, D).transpose(1, 0, 2), pb)
+    qr = rope_partial(np.asarray(q, F32)[rows].reshape(len(rows), H, D).transpose(1, 0, 2), cos[rows], sin[rows])
+    iq = _index(qr, qa)                                                               # [heads, R, D]
+    rep, R = H // KV, len(rows)
+    acc_qk = np.matmul((iq.astype(np.float64) - np.float64(qa.offset)).reshape(KV, rep * R, D),
+                       (ik.astype(np.float64) - np.float64(qb.offset)).transpose(0, 2, 1))
+    acc_qk = np.rint(acc_qk).astype(np.int64).reshape(H, R, S)
+    live = np.arange(S)[None, None, :] <= rows[None, :, None]
+    acc_qk = np.where(live, acc_qk, 0)
+    alpha_qk = F32(F32(qa.scale) * F32(qb.scale))
+    sqrt_d = F32(np.sqrt(F32(D)))
+    x32 = (acc_qk.astype(F32) * alpha_qk).astype(F32)
+    if qo is not None:
+        t64 = acc_qk.astype(np.float64) * np.float64(alpha_qk) / np.float64(F32(qo.scale)) + np.float64(F32(qo.offset))
+        s_idx = _index(x32, qo)
+        sval = dequantize_index(s_idx, qo.scale, qo.offset)
+        v64 = (s_idx.astype(np.float64) - np.float64(F32(qo.offset))) * np.float64(F32(qo.scale)) / np.sqrt(np.float64(D))
+    else:
+        t64 = acc_qk.astype(np.float64) * np.float64(alpha_qk) / np.sqrt(np.float64(D))
+        s_idx = sval = x32
+        v64 = t64
+    scores = np.where(live, (sval / sqrt_d).astype(F32), F32(-np.inf)).astype(F32)
+    att = (scores - scores.max(axis=-1, keepdims=True)).astype(F32)
+    e = np.exp(att, dtype=F32)
+    p = (e / e.sum(axis=-1, keepdims=True, dtype=F32)).astype(F32)
+    v64 = np.where(live, v64, -np.inf)
+    e64 = np.exp(v64 - v64.max(axis=-1, keepdims=True))
+    p64 = e64 / e64.sum(axis=-1, keepdims=True)
+    p_idx = _index(p, pa).astype(np.int64)
+    p_idx64 = np.clip(np.rint(p64 / np.float64(F32(pa.scale))) + np.float64(F32(pa.offset)), pa.qmin, pa.qmax).astype(np.int64)
+    acc = decode_pv_sums(p_idx.reshape(H * R, S), iv, pa, pb).reshape(H, R, D)
+    alpha_pv = F32(F32(pa.scale) * F32(pb.scale))
+    pre = (acc.astype(np.float64) * np.float64(alpha_pv)).astype(F32)
+    y = po.forward(pre) if po is not None else pre
+    out_idx = _index(pre, po) if po is not None else None
+    lay = lambda a: a.transpose(1, 0, 2).reshape(R, H * D)                          # noqa: E731  [heads, R, D] -> [R, heads*D]
+    return dict(ik8=(ik.astype(np.int64) - 128).astype(np.int8), iv8=(iv.astype(np.int64) - 128).astype(np.int8), iv=iv, rows=rows,
+                acc_qk=acc_qk, t64=t64, s_idx=s_idx, scores=scores, p=p, p64=p64, p_idx=p_idx, p_idx64=p_idx64, acc=acc,
+                y=lay(y), out_idx=None if out_idx is None else lay(out_idx), live=live, D=D)
+
+
+def prefill_fixed_ref(qo, D):
+    """mq_attention_quant's choice of the grid top as the exponent reference: a score grid whose span is < 96 in exp2 units."""
+    if qo is None:
+        return False
+    inv = {64: F32(0.125), 128: F32(0.08838834764831845), 256: F32(0.0625)}[D]
+    cexp = F32(F32(F32(qo.scale) * inv) * F32(1.4426950408889634))
+    flo, fhi = F32(12582912.0) + F32(qo.qmin), F32(12582912.0) + F32(qo.qmax)
+    return bool(F32(F32(fhi - flo) * cexp) < F32(96.0))
+
+
+EXP2_ULP = 8          # assumed error of v_exp_f32, in ulp of its result (unmeasured on gfx950; the ISA documents 1 ulp)
+
+
+def prefill_envelope(r, qk: tuple, pv: tuple, exp2_ulp: int = EXP2_ULP):
+    """Sound per-output range for mq_attention_quant on the rows of r = prefill_attention_rows(...): every output index the kernel may
+    produce given its documented rounding points, and every one attention_sim's fp32 order produces.  Interval arithmetic in float64
+    (u = 2^-24; relative errors below are bounds, each counted generously):
+      * Score index.  The kernel evaluates rint(ti beta + o) as fma(float(ti), beta, o + 1.5 2^23) clamped by med3, with
+        beta = fl(fl(s_a s_b) fl(1 / s_out)); the reference divides: rint(fl(fl(ti) alpha) / s_out) + o.  Both are rint of
+        t = ti alpha / s_out times (1 + d), |d| <= 3u, + u once |ti| >= 2^24 (ti -> float).  So the index lies in
+        [ceil(t - e|t| - 1/2), floor(t + e|t| + 1/2)] + o: both neighbours where t lies within e|t| of a half-integer.  Without an output
+        grid the score value itself carries 4u (head_dim 128: RN(1 / sqrt 128) against fl(sqrt 128)).
+      * Exponentials.  exp2(fma(f, cexp, -R)): cexp = fl(fl(s_out / sqrt D) log2e) carries <= 3u; with f = magic + index the fma is exact
+        up to its result's rounding, so the argument x_t (log2 distance from R: the grid top when fixed_ref, the row maximum otherwise)
+        is off by <= 4u |x_t|; v_exp_f32 adds exp2_ulp ulp (2u each: an assumption, not a measurement).  The reference rounds each fp32
+        score (2u |s_t|) and s_t - max (u |s_t - max|) and calls numpy's expf (covered by the same ulp allowance).  So e_t carries
+        a_t = 8u (ln2 |x_t| + |s_t| + |s_max|) + 2u exp2_ulp + 4u.
+      * Row sum l.  16 terms per lane per key block in order, one partial per block into the lane's l (running form: l * exp2(R - Rn)
+        + bs, two roundings), two cross-lane adds: at most n = 2 nkb + 24 roundings on the path of any term (numpy's pairwise row sum
+        needs fewer): gamma_n.  Each rescale of the running form multiplies by one more v_exp_f32 result: (2u exp2_ulp + 2u) per
+        rescale, counted per row as the blocks whose highest score can exceed every lower score before them.
+      * p index.  rp = fl(fl(1 / s_p) / l), rint(fma(e, rp, zp + magic)): e rp carries 2u beyond e / (l s_p); the reference's fl(e / sum)
+        and fl(p / s_p) as much.  t_p = p / s_p lies in [E_lo (1 - a) / L_hi, E_hi (1 + a) / L_lo] / s_p (1 -+ 4u), the index in
+        [ceil(lo - 1/2), floor(hi + 1/2)] + zp, clamped.  Masked keys: exactly zp.
+      * Output.  The exact sums over each p index range (decode_pv_sums(p_hi=...)); the double product with fl(s_p s_v) rounded once,
+        as the kernel and the reference do; then the index in both the division form (reference) and a_index_fast's reciprocal form,
+        the lower of both at the low end and the higher at the high end (all four are monotone in the sum).  pv_out None: the fp32
+        interval of the pre-quantizer value.
+    Returns dict(p_lo, p_hi [heads, R, T], acc_lo, acc_hi [heads, R, D], lo, hi [R, heads*D] (indices, or fp32 values without an
+    output grid), n_amb_score, n_amb_p)."""
+    qa, qb, qo = qk
+    pa, pb, po = pv
+    u = 2.0 ** -24
+    D, live, acc_qk, rows = r["D"], r["live"], r["acc_qk"], r["rows"]
+    H, R, S = acc_qk.shape
+    big = np.abs(acc_qk) >= 2 ** 24
+    alpha = np.float64(F32(F32(qa.scale) * F32(qb.scale)))
+    sd = np.sqrt(np.float64(D))
+    if qo is not None:
+        so, oo = np.float64(F32(qo.scale)), np.float64(F32(qo.offset))
+        t = acc_qk * alpha / so
+        e = (3 * u + u * big) * np.abs(t)
+        j_lo = np.clip(np.ceil(t - e - 0.5) + oo, qo.qmin, qo.qmax)
+        j_hi = np.clip(np.floor(t + e + 0.5) + oo, qo.qmin, qo.qmax)
+        sv_lo, sv_hi = (j_lo - oo) * so / sd, (j_hi - oo) * so / sd
+        n_amb_score = int(((j_hi != j_lo) & live).sum())
+    else:
+        t = acc_qk * alpha / sd
+        e = (4 * u + u * big) * np.abs(t)
+        sv_lo, sv_hi = t - e, t + e
+        n_amb_score = 0
+    sv_lo, sv_hi = np.where(live, sv_lo, -np.inf), np.where(live, sv_hi, -np.inf)
+    M = sv_hi.max(axis=-1, keepdims=True)
+    log2e, ln2 = 1.0 / np.log(2.0), np.log(2.0)
+    fixed = prefill_fixed_ref(qo, D)
+    x = np.where(live, (M - sv_lo) * log2e, 0.0)
+    if fixed:
+        x = np.maximum(x, np.where(live, (qo.qmax - j_lo) * so / sd * log2e, 0.0))
+    a = 8 * u * (ln2 * x + np.abs(np.where(live, sv_hi, 0.0)) + np.abs(M)) + 2 * u * exp2_ulp + 4 * u
+    E_lo = np.where(live, np.exp(sv_lo - M), 0.0) * (1 - a)
+    E_hi = np.where(live, np.exp(sv_hi - M), 0.0) * (1 + a)
+    nkb = rows // 64 + 1                                                              # [R]
+    gam = (2 * nkb + 24) * u / (1 - (2 * nkb + 24) * u)
+    if fixed:
+        n_r = np.zeros((H, R))
+    else:                                                                             # blocks that may raise the running maximum
+        nb = S // 64 if S % 64 == 0 else S // 64 + 1
+        pad = nb * 64 - S
+        bl = np.pad(sv_lo, ((0, 0), (0, 0), (0, pad)), constant_values=-np.inf).reshape(H, R, nb, 64).max(-1)
+        bh = np.pad(sv_hi, ((0, 0), (0, 0), (0, pad)), constant_values=-np.inf).reshape(H, R, nb, 64).max(-1)
+        run = np.maximum.accumulate(bl, axis=-1)
+        n_r = ((bh[..., 1:] > run[..., :-1]) & (bh[..., 1:] > -np.inf)).sum(-1).astype(np.float64)
+    er = n_r * (2 * u * exp2_ulp + 2 * u)
+    L_lo = E_lo.sum(-1) * (1 - gam[None]) * (1 - er)
+    L_hi = E_hi.sum(-1) * (1 + gam[None]) * (1 + er)
+    sp, zp = np.float64(F32(pa.scale)), np.float64(F32(pa.offset))
+    tp_lo = E_lo / L_hi[..., None] / sp * (1 - 4 * u) - 1e-12
+    tp_hi = E_hi / L_lo[..., None] / sp * (1 + 4 * u) + 1e-12
+    p_lo = np.where(live, np.clip(np.ceil(tp_lo - 0.5) + zp, pa.qmin, pa.qmax), zp).astype(np.int64)
+    p_hi = np.where(live, np.clip(np.floor(tp_hi + 0.5) + zp, pa.qmin, pa.qmax), zp).astype(np.int64)
+    acc_lo, acc_hi = decode_pv_sums(p_lo.reshape(H * R, S), r["iv"], pa, pb, p_hi=p_hi.reshape(H * R, S))
+    acc_lo, acc_hi = acc_lo.reshape(H, R, D), acc_hi.reshape(H, R, D)
+    alpha_pv = np.float64(F32(F32(pa.scale) * F32(pb.scale)))
+    pre_lo, pre_hi = ((a_.astype(np.float64) * alpha_pv).astype(F32) for a_ in (acc_lo, acc_hi))
+    if po is not None:
+        def recip(x):
+            inv = (F32(1.0) / F32(po.scale)).astype(F32)
+            return np.clip((np.rint((x * inv).astype(F32)) + F32(po.offset)).astype(F32), F32(po.qmin), F32(po.qmax))
+        lo = np.minimum(_index(pre_lo, po), recip(pre_lo))
+        hi = np.maximum(_index(pre_hi, po), recip(pre_hi))
+    else:
+        lo, hi = pre_lo, pre_hi
+    lay = lambda z: z.transpose(1, 0, 2).reshape(R, H * D)                          # noqa: E731
+    return dict(p_lo=p_lo, p_hi=p_hi, acc_lo=acc_lo, acc_hi=acc_hi, lo=lay(lo), hi=lay(hi), n_amb_score=n_amb_score,
+                n_amb_p=int(((p_hi != p_lo) & live).sum()))
