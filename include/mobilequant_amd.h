@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 301 /* 0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 302 /* 0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -531,6 +531,57 @@ int mq_decode_embed(const float* table, const int64_t* tok, int64_t hidden, int6
  * nn.LayerNorm with optional weight / bias (StableLM-2: hf_model.py:1440-1441). */
 int mq_decode_head(const float* x, const float* norm_weight, const float* norm_bias, int layernorm, float eps, const float* w,
                    const float* bias, int64_t K, int64_t V, float* logits, mq_stream_t stream);
+
+/* ---- f2b: batched decode step -- up to MQ_DECODE_MAX_BATCH independent sequences per launch ------------------- */
+/* Row b of every batched launch computes, bit for bit, what the single-sequence launch above computes for that sequence alone; the
+ * weights are streamed ONCE per launch for all rows.  Rows are independent: their positions, caches and outputs never mix. */
+#define MQ_DECODE_MAX_BATCH 8
+/* mq_decode_gemv for `batch` activation rows (the five-launch subset: zero_acc and o_acc must be NULL).  g's x / xq / resid / y /
+ * gate_q point at row 0; row b is at + b * x_stride (x and xq), b * y_stride (resid and y), b * gate_stride (gate_q) elements.
+ * Every row's norm -> quantize prologue is decode_gemv's arithmetic and reduction order; the B int8 images sit in LDS together
+ * (batch * K <= 131072 bytes) and every 16-byte weight chunk is contracted with all of them.  Alignment: x rows 16 bytes, xq rows
+ * 16 bytes. */
+typedef struct mq_decode_gemv_batch_args {
+  mq_decode_gemv_args g;
+  int batch; /* 1 .. MQ_DECODE_MAX_BATCH */
+  int64_t x_stride, y_stride, gate_stride;
+} mq_decode_gemv_batch_args;
+int mq_decode_gemv_batch(const mq_decode_gemv_batch_args* args, mq_stream_t stream);
+
+/* mq_decode_attention for `batch` sequences in one launch: grid (heads, a.nsplit, batch).  a.pos [batch] holds each sequence's
+ * position; a sequence with pos[b] >= cache_len does nothing (an idle slot inside a captured graph).  Sequence b reads qkv + b *
+ * qkv_stride floats; its caches are k_cache / v_cache + b * kv_heads * cache_len * head_dim ([batch][kv_heads][cache_len][head_dim]),
+ * its outputs out / out_q + b * heads * head_dim, its split scratch part + b * nsplit * heads * head_dim and ticket + b * heads.
+ * Split count per sequence, chosen on the device: a.nsplit from split_from cached positions on, else 1 (the surplus workgroups exit;
+ * the result bits do not depend on the split count).  No prefetch rows: a.prefetch_wgs must be 0. */
+typedef struct mq_decode_attention_batch_args {
+  mq_decode_attention_args a;
+  int batch; /* 1 .. MQ_DECODE_MAX_BATCH */
+  int split_from;
+  int64_t qkv_stride;
+} mq_decode_attention_batch_args;
+int mq_decode_attention_batch(const mq_decode_attention_batch_args* args, mq_stream_t stream);
+
+/* mq_decode_head for `batch` rows: x [batch][x_stride] -> logits [batch][logits_stride], every row's norm and dot products in
+ * mq_decode_head's order, the fp32 lm_head streamed once for all rows (batch * K <= 32768: the normalised rows sit in LDS).  pos
+ * (nullable) [batch]: a row whose pos[b] is outside [0, cache_len) is skipped, its logits keep their bytes. */
+typedef struct mq_decode_head_batch_args {
+  const float* x;
+  int64_t x_stride;
+  const float* norm_weight;
+  const float* norm_bias;
+  int layernorm;
+  float eps;
+  const float* w;
+  const float* bias;
+  int64_t K, V;
+  int batch; /* 1 .. MQ_DECODE_MAX_BATCH */
+  float* logits;
+  int64_t logits_stride;
+  const int* pos;
+  int cache_len;
+} mq_decode_head_batch_args;
+int mq_decode_head_batch(const mq_decode_head_batch_args* args, mq_stream_t stream);
 
 /* ---- a10: quantized causal attention at prefill (hf_model.py:486-534 with the two QMatMuls of qmodule.py:453-466) ------------ */
 /* One sequence.  q [seq, heads*D], k / v [seq, kv_heads*D] fp32 = the q / k / v projection outputs BEFORE RoPE; cos / sin [seq, D]

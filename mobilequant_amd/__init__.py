@@ -4,6 +4,7 @@ Layout: csrc/ (HIP kernels + C ABI), _lib.py (ctypes binding), ops.py (tensor wr
 quantization/ (the reference's qmodule API), calibration.py (generate_act_range counterpart).
 """
 from . import _lib, ops  # noqa: F401
+from .decode_batch import BatchDecodeEngine  # noqa: F401
 from .quantization import *  # noqa: F401,F403
 
 __version__ = "0.1.0"

@@ -59,6 +59,20 @@ class MqDecodeAttentionArgs(ctypes.Structure):
                 ("prefetch_stride", c_int64), ("prefetch_total", c_int64), ("prefetch_wgs", c_int), ("prefetch_delay", c_int)]
 
 
+class MqDecodeGemvBatchArgs(ctypes.Structure):
+    _fields_ = [("g", MqDecodeGemvArgs), ("batch", c_int), ("x_stride", c_int64), ("y_stride", c_int64), ("gate_stride", c_int64)]
+
+
+class MqDecodeAttentionBatchArgs(ctypes.Structure):
+    _fields_ = [("a", MqDecodeAttentionArgs), ("batch", c_int), ("split_from", c_int), ("qkv_stride", c_int64)]
+
+
+class MqDecodeHeadBatchArgs(ctypes.Structure):
+    _fields_ = [("x", c_void_p), ("x_stride", c_int64), ("norm_weight", c_void_p), ("norm_bias", c_void_p), ("layernorm", c_int),
+                ("eps", c_float), ("w", c_void_p), ("bias", c_void_p), ("K", c_int64), ("V", c_int64), ("batch", c_int),
+                ("logits", c_void_p), ("logits_stride", c_int64), ("pos", c_void_p), ("cache_len", c_int)]
+
+
 class MqAttentionArgs(ctypes.Structure):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("seq", c_int),
                 ("heads", c_int), ("kv_heads", c_int), ("head_dim", c_int), ("inv_sqrt_d", c_float), ("qk_a", MqGrid),
@@ -138,6 +152,9 @@ _SIGNATURES = {
     "mq_decode_attention_oproj": (c_int, [POINTER(MqDecodeAttentionOprojArgs), _P]),
     "mq_decode_embed": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, c_int, c_int, _P, _P, _P]),
     "mq_decode_head": (c_int, [_P, _P, _P, c_int, c_float, _P, _P, c_int64, c_int64, _P, _P]),
+    "mq_decode_gemv_batch": (c_int, [POINTER(MqDecodeGemvBatchArgs), _P]),
+    "mq_decode_attention_batch": (c_int, [POINTER(MqDecodeAttentionBatchArgs), _P]),
+    "mq_decode_head_batch": (c_int, [POINTER(MqDecodeHeadBatchArgs), _P]),
     "mq_attention_quant": (c_int, [POINTER(MqAttentionArgs), _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),

@@ -1,0 +1,938 @@
+// Batched decode step: up to MQ_DECODE_MAX_BATCH independent sequences advanced by the same launches (BatchDecodeEngine,
+// mobilequant_amd/decode_batch.py).  At one token per step every launch of mq_decode.hip streams the whole weight image for one
+// activation row and leaves the dot-product units almost idle; here the same stream feeds B rows.  The contract is PER SEQUENCE: row b
+// of every launch computes, bit for bit, what the single-sequence launch computes for that sequence alone -- the same fp32 expressions
+// in the same reduction orders (integer sums are exact in any order).
+//   mq_decode_gemv_batch      : decode_gemv_kernel (five-launch subset) for B rows: B prologues interleaved over shared barriers, the
+//                               B int8 images side by side in LDS, every 16-byte weight chunk contracted with all of them
+//   mq_decode_attention_batch : decode_attention_kernel<D> on a (heads, nsplit, B) grid, per-sequence positions, caches and scratch
+//   mq_decode_head_batch      : decode_head_kernel's final norm for B rows, then the fp32 lm_head streamed once for all of them
+#include "mq_decode_common.h"
+
+namespace mq {
+
+#pragma clang fp contract(off)
+
+constexpr int DB_MAXB = MQ_DECODE_MAX_BATCH;
+constexpr int DB_INFLIGHT = 12;      // weight chunks per lane in flight, as decode_gemv_kernel
+constexpr int DB_XH = 1;             // float4 per row and thread the prologue holds between its passes (K <= 2048); beyond that it re-reads
+constexpr int DB_MAX_IMAGE = 128 * 1024;
+
+// ---- weight stream x B activation rows ---------------------------------------------------------------------------------------------
+// Roles, barriers, geometry and epilogue as decode_gemv_kernel (mq_decode.hip): PROLOGUE waves 0 .. DG_PRO-1 build the images, STREAM
+// waves request weights and epilogue parameters first.  Per row b the prologue is thread p's walk over float4 p + 512 u, the per-thread
+// partial in that order, wave_sum_f, then the DG_PRO wave partials added in wave order -- the rows' chains interleave, the barriers are
+// shared.  Beyond DB_XH float4 per row the prologue re-reads x (and the norm weights) instead of holding them: the same values, so the
+// same bits.
+template <int XMODE, bool GATE, bool W4>
+__global__ void __launch_bounds__(DG_THREADS) decode_gemv_batch_kernel(const mq_decode_gemv_batch_args ba, const int rows_per_wg) {
+  const mq_decode_gemv_args& g = ba.g;
+  const int B = ba.batch;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // [B][K] int8 activation images
+  __shared__ float s_red[DB_MAXB][DG_PRO], s_red2[DB_MAXB][DG_PRO];
+  __shared__ int s_redi[DB_MAXB][DG_PRO];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int K = g.K;
+  const float cv = g.consts[lane & 63];
+
+  if (wave < DG_PRO) {
+    // ================================================ PROLOGUE role ====================================================================
+    const int p = threadIdx.x;                                     // 0 .. 511
+    int my_sum[DB_MAXB];
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) my_sum[b] = 0;
+    if constexpr (XMODE == XM_I8) {                                // ready int8 images: copy + row sums
+      const int nq = K >> 4;
+      for (int i = p; i < nq; i += DG_PRO * 64) {
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          if (b < B) {
+            const v4i v = reinterpret_cast<const v4i*>(g.xq + (size_t)b * ba.x_stride)[i];
+            reinterpret_cast<v4i*>(smem + (size_t)b * K)[i] = v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) my_sum[b] = __builtin_amdgcn_sdot4(v[e], 0x01010101, my_sum[b], false);
+          }
+        }
+      }
+    } else {
+      const int nvec = K >> 2;
+      constexpr bool ANYNORM = XMODE == XM_NORM || XMODE == XM_LNORM;
+      const Grid ag = const_grid(cv, CG_A, g.a_grid);
+      const Grid ng = const_grid(cv, CG_NORM_IN, g.norm_in);
+      float4 xv[DB_MAXB][DB_XH], nw[DB_XH], nb[DB_XH];
+      auto xrow = [&](int b, int ic) { return reinterpret_cast<const float4*>(g.x + (size_t)b * ba.x_stride)[ic]; };
+      auto fqv = [&](float4 v) {                                   // the norm's input quantizer, two elements per instruction
+        const v2f lo2 = ng.fq2((v2f){v.x, v.y}), hi2 = ng.fq2((v2f){v.z, v.w});
+        return make_float4(lo2.x, lo2.y, hi2.x, hi2.y);
+      };
+#pragma unroll
+      for (int u = 0; u < DB_XH; ++u) {
+        if (u * DG_PRO * 64 < nvec) {                              // wave-uniform
+          const int i = p + u * DG_PRO * 64;
+          const int ic = i < nvec ? i : nvec - 1;
+#pragma unroll
+          for (int b = 0; b < DB_MAXB; ++b)
+            if (b < B) xv[b][u] = xrow(b, ic);
+          if constexpr (ANYNORM) nw[u] = reinterpret_cast<const float4*>(g.norm_w)[ic];
+          if constexpr (XMODE == XM_LNORM)
+            nb[u] = g.norm_bias ? reinterpret_cast<const float4*>(g.norm_bias)[ic] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      // row b's (normalised-input) float4 u: held, or re-read and re-quantised (fq: the norm modes' input quantizer applied)
+      auto xval = [&](int b, int u, int ic, bool fq) {
+        if (u < DB_XH) return xv[b][u < DB_XH ? u : 0];
+        const float4 v = xrow(b, ic);
+        return fq ? fqv(v) : v;
+      };
+      float r[DB_MAXB], shiftv[DB_MAXB];
+#pragma unroll
+      for (int b = 0; b < DB_MAXB; ++b) r[b] = 1.f, shiftv[b] = 0.f;
+      if constexpr (XMODE == XM_LNORM) {                           // QLayerNorm.forward, decode_gemv_kernel's arithmetic
+        float s1[DB_MAXB];
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) s1[b] = 0.f;
+#pragma unroll
+        for (int u = 0; u < DG_XPRE; ++u) {
+          if (u * DG_PRO * 64 < nvec) {
+            const int i = p + u * DG_PRO * 64, ic = i < nvec ? i : nvec - 1;
+#pragma unroll
+            for (int b = 0; b < DB_MAXB; ++b) {
+              if (b < B) {
+                float4 v;
+                if (u < DB_XH) v = xv[b][u < DB_XH ? u : 0] = fqv(xv[b][u < DB_XH ? u : 0]);
+                else v = fqv(xrow(b, ic));
+                if (i < nvec) s1[b] += (v.x + v.y) + (v.z + v.w);
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          if (b < B) {
+            const float t = wave_sum_f(s1[b]);
+            if (lane == 0) s_red[b][wave] = t;
+          }
+        }
+        __syncthreads();                                           // barrier 1 of 3
+        float mu[DB_MAXB], s2[DB_MAXB];
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          float tot = 0.f;
+#pragma unroll
+          for (int w = 0; w < DG_PRO; ++w) tot += s_red[b][w];
+          mu[b] = __fdiv_rn(tot, (float)K);
+          s2[b] = 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < DG_XPRE; ++u) {
+          if (u * DG_PRO * 64 < nvec && p + u * DG_PRO * 64 < nvec) {
+            const int ic = p + u * DG_PRO * 64;
+#pragma unroll
+            for (int b = 0; b < DB_MAXB; ++b) {
+              if (b < B) {
+                const float4 v = xval(b, u, ic, true);
+                const float d0 = v.x - mu[b], d1 = v.y - mu[b], d2 = v.z - mu[b], d3 = v.w - mu[b];
+                s2[b] += d0 * d0;
+                s2[b] += d1 * d1;
+                s2[b] += d2 * d2;
+                s2[b] += d3 * d3;
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          if (b < B) {
+            const float t = wave_sum_f(s2[b]);
+            if (lane == 0) s_red2[b][wave] = t;
+          }
+        }
+        __syncthreads();                                           // barrier 2 of 3
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          float tot2 = 0.f;
+#pragma unroll
+          for (int w = 0; w < DG_PRO; ++w) tot2 += s_red2[b][w];
+          const float var = __fdiv_rn(tot2, (float)K);
+          r[b] = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, g.eps)));
+          shiftv[b] = __fmul_rn(-r[b], mu[b]);
+        }
+      }
+      if constexpr (XMODE == XM_NORM) {                            // QRMSNorm.forward, decode_gemv_kernel's arithmetic
+        float ss[DB_MAXB];
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) ss[b] = 0.f;
+#pragma unroll
+        for (int u = 0; u < DG_XPRE; ++u) {
+          if (u * DG_PRO * 64 < nvec) {
+            const int i = p + u * DG_PRO * 64, ic = i < nvec ? i : nvec - 1;
+#pragma unroll
+            for (int b = 0; b < DB_MAXB; ++b) {
+              if (b < B) {
+                float4 v;
+                if (u < DB_XH) v = xv[b][u < DB_XH ? u : 0] = fqv(xv[b][u < DB_XH ? u : 0]);
+                else v = fqv(xrow(b, ic));
+                if (i < nvec) {
+                  const v2f lo2 = (v2f){v.x, v.y}, hi2 = (v2f){v.z, v.w};
+                  const v2f sl = lo2 * lo2, sh = hi2 * hi2;
+                  ss[b] += sl.x;
+                  ss[b] += sl.y;
+                  ss[b] += sh.x;
+                  ss[b] += sh.y;
+                }
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          if (b < B) {
+            const float t = wave_sum_f(ss[b]);
+            if (lane == 0) s_red[b][wave] = t;
+          }
+        }
+        __syncthreads();                                           // barrier 1 of 2
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          float tot = 0.f;
+#pragma unroll
+          for (int w = 0; w < DG_PRO; ++w) tot += s_red[b][w];
+          const float mean = __fdiv_rn(tot, (float)K);
+          r[b] = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(mean, g.eps)));
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < DG_XPRE; ++u) {
+        if (u * DG_PRO * 64 < nvec) {
+          const int i = p + u * DG_PRO * 64, ic = i < nvec ? i : nvec - 1;
+          float4 w = make_float4(0.f, 0.f, 0.f, 0.f), bb = w;
+          if constexpr (ANYNORM) w = u < DB_XH ? nw[u < DB_XH ? u : 0] : reinterpret_cast<const float4*>(g.norm_w)[ic];
+          if constexpr (XMODE == XM_LNORM)
+            bb = u < DB_XH ? nb[u < DB_XH ? u : 0] : (g.norm_bias ? reinterpret_cast<const float4*>(g.norm_bias)[ic] : make_float4(0.f, 0.f, 0.f, 0.f));
+#pragma unroll
+          for (int b = 0; b < DB_MAXB; ++b) {
+            if (b < B) {
+              float4 v = xval(b, u, ic, ANYNORM);
+              if constexpr (XMODE == XM_NORM) {
+                const v2f a2 = (v2f){w.x, w.y} * ((v2f){v.x, v.y} * splat2(r[b])), b2 = (v2f){w.z, w.w} * ((v2f){v.z, v.w} * splat2(r[b]));
+                v = make_float4(a2.x, a2.y, b2.x, b2.y);
+              }
+              if constexpr (XMODE == XM_LNORM) {
+                v.x = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.x, r[b]), shiftv[b]), w.x), bb.x);
+                v.y = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.y, r[b]), shiftv[b]), w.y), bb.y);
+                v.z = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.z, r[b]), shiftv[b]), w.z), bb.z);
+                v.w = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.w, r[b]), shiftv[b]), w.w), bb.w);
+              }
+              const v2f u01 = image_u8f2((v2f){v.x, v.y}, ag.s, ag.inv_s, ag.o, ag.qmin, ag.qmax, 0.f);
+              const v2f u23 = image_u8f2((v2f){v.z, v.w}, ag.s, ag.inv_s, ag.o, ag.qmin, ag.qmax, 0.f);
+              uint32_t usum = 0;
+              const uint32_t pk = image_pack4(u01.x, u01.y, u23.x, u23.y, usum);
+              if (i < nvec) {
+                my_sum[b] += (int)usum - 512;
+                reinterpret_cast<unsigned*>(smem + (size_t)b * K)[i] = pk;
+              }
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (b < B) {
+        const int part = wave_sum_dpp(my_sum[b]);
+        if (lane == 0) s_redi[b][wave] = part;
+      }
+    }
+    __syncthreads();                                               // the images and the row sums are complete
+    return;
+  }
+
+  // ================================================== STREAM role ======================================================================
+  const int sw = wave - DG_PRO;
+  const int NL = GATE ? g.N >> 1 : g.N;                            // logical rows
+  const int kchunks = W4 ? K >> 5 : K >> 4;                        // 16-byte chunks per weight row
+  const int wrow = W4 ? K >> 1 : K;                                // bytes per weight row
+  const int lchunks = GATE ? 2 * kchunks : kchunks;                // chunks per logical row
+  const int cpl = (lchunks + 63) >> 6;
+  const int row0 = blockIdx.x * rows_per_wg + sw;
+  const int row_end = (blockIdx.x + 1) * rows_per_wg < NL ? (blockIdx.x + 1) * rows_per_wg : NL;
+  const int prow = row0 + DG_STR * lane;                           // lane t keeps the parameters / results of row slot t
+  const bool prow_ok = prow < row_end;
+  v4i buf[DB_INFLIGHT];
+  auto issue_pass = [&](int t, int j) {
+#pragma unroll
+    for (int u = 0; u < DB_INFLIGHT; ++u) {
+      const int row = row0 + DG_STR * t;
+      const int c = lane + 64 * j;
+      if (row < row_end && c < lchunks)
+        buf[u] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g.w + (size_t)row * (GATE ? 2 : 1) * wrow) + c);
+      else
+        buf[u] = v4i{0, 0, 0, 0};
+      if (++j == cpl) { j = 0; ++t; }
+    }
+  };
+  issue_pass(0, 0);
+  float p_alpha[GATE ? 2 : 1], p_bias[GATE ? 2 : 1];
+  int p_zp[GATE ? 2 : 1], p_ct[GATE ? 2 : 1];
+#pragma unroll
+  for (int h = 0; h < (GATE ? 2 : 1); ++h) {
+    const int wr = GATE ? 2 * prow + h : prow;
+    p_alpha[h] = prow_ok ? g.alpha[wr] : 0.f;
+    p_zp[h] = prow_ok ? g.w_zp[wr] : 0;
+    p_ct[h] = prow_ok ? g.col_term[wr] : 0;
+    p_bias[h] = (prow_ok && g.bias) ? g.bias[wr] : 0.f;
+  }
+  float p_res[DB_MAXB];
+#pragma unroll
+  for (int b = 0; b < DB_MAXB; ++b) p_res[b] = (!GATE && g.resid && prow_ok && b < B) ? g.resid[(size_t)b * ba.y_stride + prow] : 0.f;
+  if constexpr (XMODE == XM_LNORM) {                               // the prologue waves' mean and variance reductions
+    __syncthreads();
+    __syncthreads();
+  }
+  if constexpr (XMODE == XM_NORM) __syncthreads();                 // barrier 1 of 2: the prologue waves' sums of squares
+  __syncthreads();                                                 // the images and the row sums are complete
+  if (row0 >= row_end) return;
+
+  const Grid og0 = const_grid(cv, CG_OUT0, g.out_grid[0]), og1 = const_grid(cv, CG_OUT1, g.out_grid[1]), og2 = const_grid(cv, CG_OUT2, g.out_grid[2]);
+  const Grid gmid = const_grid(cv, CG_GATE_MID, g.gate_mid), gact = const_grid(cv, CG_GATE_ACTOUT, g.gate_actout),
+             gout = const_grid(cv, CG_GATE_OUT, g.gate_out);
+  auto out_q = [&](const Grid& q, float f) {        // output quantizer as the GEMM / GEMV epilogues evaluate it (reciprocal multiply)
+    if (!q.on) return f;
+    float v = rintf(f * q.inv_s) + q.o;
+    v = fminf(fmaxf(v, q.qmin), q.qmax);
+    return __fmul_rn(__fsub_rn(v, q.o), q.s);
+  };
+
+  // ---- dot products against all B images, DPP reductions per completed logical row ----------------------------------------------
+  const int nslots = (row_end - row0 + DG_STR - 1) / DG_STR;
+  int acc0[DB_MAXB], acc1[DB_MAXB], sum0[DB_MAXB], sum1[DB_MAXB];
+#pragma unroll
+  for (int b = 0; b < DB_MAXB; ++b) acc0[b] = acc1[b] = sum0[b] = sum1[b] = 0;
+  int t = 0, j = 0;
+  while (t < nslots) {
+    int t2 = t, j2 = j;
+#pragma unroll
+    for (int u = 0; u < DB_INFLIGHT; ++u) {
+      if (t2 < nslots) {
+        int c = lane + 64 * j2;
+        c = c < lchunks ? c : lchunks - 1;                       // buf[u] is zero there
+        const int ck = GATE ? (c >= kchunks ? c - kchunks : c) : c;
+        const bool second = GATE && c >= kchunks;
+        v4i w_lo = buf[u], w_hi = buf[u];
+        if constexpr (W4) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            w_lo[e] = buf[u][e] & 0x0f0f0f0f;
+            w_hi[e] = (int)(((unsigned)buf[u][e] >> 4) & 0x0f0f0f0fu);
+          }
+        }
+#pragma unroll
+        for (int b = 0; b < DB_MAXB; ++b) {
+          if (b < B) {
+            const char* img = smem + (size_t)b * K;
+            int part;
+            if constexpr (W4) {
+              const v4i a_lo = *reinterpret_cast<const v4i*>(img + (size_t)ck * 32), a_hi = *reinterpret_cast<const v4i*>(img + (size_t)ck * 32 + 16);
+              part = dot16(w_hi, a_hi, dot16(w_lo, a_lo, 0));
+            } else {
+              part = dot16(w_lo, *reinterpret_cast<const v4i*>(img + (size_t)ck * 16), 0);
+            }
+            if (second) acc1[b] += part;
+            else acc0[b] += part;
+          }
+        }
+        if (j2 == cpl - 1) {                                     // logical row slot t2 complete
+#pragma unroll
+          for (int b = 0; b < DB_MAXB; ++b) {
+            if (b < B) {
+              const int s0 = wave_sum_dpp(acc0[b]), s1 = GATE ? wave_sum_dpp(acc1[b]) : 0;
+              acc0[b] = acc1[b] = 0;
+              if (lane == t2) {
+                sum0[b] = s0;
+                sum1[b] = s1;
+              }
+            }
+          }
+        }
+        if (++j2 == cpl) { j2 = 0; ++t2; }
+      }
+    }
+    t = t2;
+    j = j2;
+    if (t < nslots) issue_pass(t, j);
+  }
+  // ---- epilogue, one row per LANE, every batch row in turn ----------------------------------------------------------------------------
+  if (lane < nslots) {
+    const int row = prow;
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (b < B) {
+        int rsb = 0;                                             // row b's image sum (read here: no registers held over the stream)
+#pragma unroll
+        for (int w = 0; w < DG_PRO; ++w) rsb += s_redi[b][w];
+        float e0, e1 = 0.f;
+        {
+          const int tt = (int)((unsigned)sum0[b] - (unsigned)p_zp[0] * (unsigned)rsb + (unsigned)p_ct[0]);
+          e0 = __fadd_rn(__fmul_rn((float)tt, p_alpha[0]), p_bias[0]);
+        }
+        if constexpr (GATE) {
+          const int tt = (int)((unsigned)sum1[b] - (unsigned)p_zp[GATE ? 1 : 0] * (unsigned)rsb + (unsigned)p_ct[GATE ? 1 : 0]);
+          e1 = __fadd_rn(__fmul_rn((float)tt, p_alpha[GATE ? 1 : 0]), p_bias[GATE ? 1 : 0]);
+          const float fa = out_q(og0, e0), fb = out_q(og1, e1);
+          float rr;
+          if (g.gate_act == 0) {                                 // QSiLU (qmodule.py:739-753)
+            const float gate = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-fa)));
+            rr = __fmul_rn(fa, gmid.fq(gate));
+          } else {                                               // QGELU (qmodule.py:790-798), erf form
+            rr = __fmul_rn(__fmul_rn(0.5f, fa), __fadd_rn(1.0f, erff(__fmul_rn(fa, 0.70710678118654752440f))));
+          }
+          const float prod = __fmul_rn(gact.fq(rr), fb);
+          const float qi = dq_index(prod, gout.s, gout.inv_s, gout.o, gout.qmin, gout.qmax);
+          g.gate_q[(size_t)b * ba.gate_stride + row] = (int8_t)((qi != qi ? (int)gout.qmin : (int)qi) - 128);
+          if (g.y) g.y[(size_t)b * ba.y_stride + row] = prod;
+        } else {
+          float v = row < g.seg_end[0] ? out_q(og0, e0) : (row < g.seg_end[1] ? out_q(og1, e0) : out_q(og2, e0));
+          if (g.resid) v = __fadd_rn(p_res[b], v);
+          g.y[(size_t)b * ba.y_stride + row] = v;
+        }
+      }
+    }
+  }
+}
+
+// ---- attention of one query token per sequence over its own static INTEGER KV cache -------------------------------------------------
+// decode_attention_kernel<D> (mq_decode.hip) with a third grid dimension: workgroup (h, c, b) is head h, split c of sequence b, with
+// that sequence's position, q | k | v row, caches, output row and split scratch.  The split count is chosen here from the position
+// (nsplit from split_from cached positions on, else 1; the other workgroups exit): the scores and the softmax are computed whole by
+// every split and the p.v partials are exact integers, so the result bits do not depend on it.  No prefetch rows.
+template <int D>
+__global__ void __launch_bounds__(256) decode_attention_batch_kernel(const mq_decode_attention_batch_args ba) {
+  const mq_decode_attention_args& a = ba.a;
+  constexpr int LPP = D >= 64 ? 4 : 2, CH = D >= 64 ? D / 64 : 1, PPP = 256 / LPP, KB = 8 / CH;
+  constexpr int DQ = D / 4, G = 256 / DQ, PPB = 64 / G, VB = 16;
+  static_assert(PPB * G == 64 && VB % PPB == 0, "block mapping");
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* s_sc = reinterpret_cast<float*>(smem_raw);              // [cache_len] scores -> exp -> (p index - zp) as int
+  __shared__ __attribute__((aligned(16))) int8_t s_q8[D], s_k8[D], s_v8[D];
+  __shared__ float s_redf[4];
+  __shared__ int s_redq[4];
+  __shared__ long long s_acc[1024];                              // [G][D] partial p.v sums
+  __shared__ unsigned s_ticket;
+  const int H = a.heads, rot = a.rot_dim, sb = blockIdx.z;
+  const int pos = a.pos[sb];
+  if (pos < 0 || pos >= a.cache_len) return;                       // an idle slot (or a step past the cache): nothing is read or written
+  const int nsplit = pos >= ba.split_from ? a.nsplit : 1;
+  const int h = blockIdx.x, c = blockIdx.y, kvh = h / (H / a.kv_heads);
+  if (c >= nsplit) return;                                         // surplus split workgroup of a short sequence
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float cv = a.consts[lane];
+  const size_t cache_seq = (size_t)a.kv_heads * a.cache_len * D;
+  int8_t* const k_cache = a.k_cache + sb * cache_seq;
+  int8_t* const v_cache = a.v_cache + sb * cache_seq;
+  const float* qkv = a.qkv + (size_t)sb * ba.qkv_stride;
+  const float* qp = qkv + (size_t)h * D;
+  const float* kp = qkv + (size_t)H * D + (size_t)kvh * D;
+  const float* vp = qkv + (size_t)(H + a.kv_heads) * D + (size_t)kvh * D;
+  const int dd = tid < D ? tid : D - 1;
+  const int half = rot >> 1;
+  const int dpart = dd < rot ? (dd < half ? dd + half : dd - half) : dd;
+  const float q_raw = qp[dd], q_par = qp[dpart], k_raw = kp[dd], k_par = kp[dpart], v_raw = vp[dd];
+  const int T = pos + 1;
+  const int dr = dd < rot ? dd : 0;
+  const float cs = a.cos[(size_t)pos * rot + dr], sn = a.sin[(size_t)pos * rot + dr];
+  const int8_t* kc = k_cache + (size_t)kvh * a.cache_len * D;
+  const int8_t* vc = v_cache + (size_t)kvh * a.cache_len * D;
+  const int sub = tid & (LPP - 1), slot = tid / LPP;
+  v4i kbuf[KB][CH];
+  auto load_keys = [&](int t0) {
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      const int t = t0 + u * PPP + slot;
+      const int tc = (t < T && t != pos) ? t : 0;                   // position 0 stands in (always valid memory); masked below
+#pragma unroll
+      for (int ch = 0; ch < CH; ++ch) kbuf[u][ch] = *reinterpret_cast<const v4i*>(kc + (size_t)tc * D + (sub * CH + ch) * 16);
+    }
+  };
+  load_keys(0);
+  const int dq = tid & (DQ - 1), grp = tid / DQ;
+  int vbuf[VB];
+  auto item_pos = [&](int i) { return 64 * (c + nsplit * (i / PPB)) + grp + G * (i % PPB); };
+  auto load_values = [&](int i0) {
+#pragma unroll
+    for (int u = 0; u < VB; ++u) {
+      const int t = item_pos(i0 + u);
+      vbuf[u] = *reinterpret_cast<const int*>(vc + (size_t)(t < pos ? t : 0) * D + dq * 4);
+    }
+  };
+  load_values(0);
+  // ---- RoPE + the three input quantizers of the new token ---------------------------------------------------------------------------
+  const Grid qa = const_grid(cv, AG_QK_A, a.qk_a), qb = const_grid(cv, AG_QK_B, a.qk_b), qo = const_grid(cv, AG_QK_OUT, a.qk_out);
+  const Grid pa = const_grid(cv, AG_PV_A, a.pv_a), pb = const_grid(cv, AG_PV_B, a.pv_b), po = const_grid(cv, AG_PV_OUT, a.pv_out);
+  const Grid oi = const_grid(cv, AG_O_IN, a.o_in);
+  int qsum_part = 0;
+  if (tid < D) {
+    float qv = q_raw, kv = k_raw;
+    if (tid < rot) {
+      const float sg = tid < half ? -1.f : 1.f;
+      qv = __fadd_rn(__fmul_rn(q_raw, cs), __fmul_rn(sg * q_par, sn));
+      kv = __fadd_rn(__fmul_rn(k_raw, cs), __fmul_rn(sg * k_par, sn));
+    }
+    const float iq = dq_index(qv, qa.s, qa.inv_s, qa.o, qa.qmin, qa.qmax), ik = dq_index(kv, qb.s, qb.inv_s, qb.o, qb.qmin, qb.qmax);
+    const float iv = dq_index(v_raw, pb.s, pb.inv_s, pb.o, pb.qmin, pb.qmax);
+    const int sq = (iq != iq ? 0 : (int)iq) - 128, sk = (ik != ik ? 0 : (int)ik) - 128, sv = (iv != iv ? 0 : (int)iv) - 128;
+    s_q8[tid] = (int8_t)sq;
+    s_k8[tid] = (int8_t)sk;
+    s_v8[tid] = (int8_t)sv;
+    qsum_part = sq;
+    if (c == 0 && h % (H / a.kv_heads) == 0) {                     // the group's first head appends to this sequence's cache
+      k_cache[((size_t)kvh * a.cache_len + pos) * D + tid] = (int8_t)sk;
+      v_cache[((size_t)kvh * a.cache_len + pos) * D + tid] = (int8_t)sv;
+    }
+  }
+  {
+    const int w = wave_sum_dpp(qsum_part);
+    if (lane == 0) s_redq[wv] = w;
+  }
+  __syncthreads();
+  const int qsum = (s_redq[0] + s_redq[1]) + (s_redq[2] + s_redq[3]);
+  const int zq = (int)qa.o - 128, zk = (int)qb.o - 128, zv = (int)pb.o - 128, zp = (int)pa.o;
+  const float alpha_qk = __fmul_rn(qa.s, qb.s), alpha_pv = __fmul_rn(pa.s, pb.s);
+  const int qconst = D * zq * zk - zk * qsum;
+  constexpr bool pow2 = (D == 64 || D == 256);
+  const float sqrt_d = __fsqrt_rn((float)D), inv_sqrt_d = 1.0f / (D == 64 ? 8.0f : 16.0f);
+  v4i qf[CH], kn[CH];
+#pragma unroll
+  for (int ch = 0; ch < CH; ++ch) {
+    qf[ch] = *reinterpret_cast<const v4i*>(s_q8 + (sub * CH + ch) * 16);
+    kn[ch] = *reinterpret_cast<const v4i*>(s_k8 + (sub * CH + ch) * 16);
+  }
+  const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+  // ---- scores ----------------------------------------------------------------------------------------------------------------------
+  float lmax = -INFINITY;
+  for (int t0 = 0; t0 < T; t0 += KB * PPP) {
+    if (t0 > 0) load_keys(t0);
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      if (t0 + u * PPP >= T) break;
+      const int t = t0 + u * PPP + slot;
+      int dot = 0, ks = 0;
+#pragma unroll
+      for (int ch = 0; ch < CH; ++ch) {
+        const v4i kf = t == pos ? kn[ch] : kbuf[u][ch];
+        dot = dot16(kf, qf[ch], dot);
+        ks = dot16(kf, ones, ks);
+      }
+      dot = quad_sum<LPP>(dot);
+      ks = quad_sum<LPP>(ks);
+      if (t < T && sub == 0) {
+        const int ti = dot - zq * ks + qconst;
+        const float val = __fmul_rn((float)ti, alpha_qk);
+        const float qv = qo.fq(val);
+        const float sc = pow2 ? __fmul_rn(qv, inv_sqrt_d) : __fdiv_rn(qv, sqrt_d);
+        s_sc[t] = sc;
+        lmax = fmaxf(lmax, sc);
+      }
+    }
+  }
+  lmax = wave_max_f(lmax);
+  if (lane == 0) s_redf[wv] = lmax;
+  __syncthreads();
+  const float mx = fmaxf(fmaxf(s_redf[0], s_redf[1]), fmaxf(s_redf[2], s_redf[3]));
+  __syncthreads();
+  float lsum = 0.f;
+  for (int t = tid; t < T; t += 256) {
+    const float e = expf(s_sc[t] - mx);
+    s_sc[t] = e;
+    lsum += e;
+  }
+  lsum = wave_sum_f(lsum);
+  if (lane == 0) s_redf[wv] = lsum;
+  __syncthreads();
+  const float tot_e = (s_redf[0] + s_redf[1]) + (s_redf[2] + s_redf[3]);
+  int* s_pi = reinterpret_cast<int*>(s_sc);
+  for (int t = tid; t < T; t += 256) {
+    if (nsplit == 1 || ((t >> 6) % nsplit) == c) {
+      const float p = __fdiv_rn(s_sc[t], tot_e);
+      const float ip = dq_index(p, pa.s, pa.inv_s, pa.o, pa.qmin, pa.qmax);
+      s_pi[t] = (ip != ip ? 0 : (int)ip) - zp;
+    }
+  }
+  __syncthreads();
+  // ---- p.v over this split's blocks: exact integers ------------------------------------------------------------------------------
+  long long acc[4] = {0, 0, 0, 0};
+  long long psum = 0;
+  const int nblk = (pos + 63) >> 6;
+  const int my_blocks = c < nblk ? (nblk - 1 - c) / nsplit + 1 : 0;
+  const int items = my_blocks * PPB;
+  for (int i0 = 0; i0 < items; i0 += VB) {
+    if (i0 > 0) load_values(i0);
+    int a32[4] = {0, 0, 0, 0}, p32 = 0;
+#pragma unroll
+    for (int u = 0; u < VB; ++u) {
+      const int t = item_pos(i0 + u);
+      const bool ok = i0 + u < items && t < pos;
+      const int pi = s_pi[ok ? t : 0];
+      const int pim = ok ? pi : 0;
+      p32 += pim;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a32[e] += (int)__builtin_amdgcn_sbfe(vbuf[u], 8 * e, 8) * pim;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] += a32[e];
+    psum += p32;
+  }
+  if (grp == 0 && ((pos >> 6) % nsplit) == c) {
+    const int sv4 = *reinterpret_cast<const int*>(s_v8 + dq * 4);
+    const int pi = s_pi[pos];
+    psum += pi;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] += (long long)((int)__builtin_amdgcn_sbfe(sv4, 8 * e, 8) * pi);
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] -= (long long)zv * psum;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) s_acc[grp * D + dq * 4 + e] = acc[e];
+  __syncthreads();
+  long long tot = 0;
+  if (tid < D) {
+#pragma unroll
+    for (int gq = 0; gq < G; ++gq) tot += s_acc[gq * D + tid];
+  }
+  if (nsplit > 1) {
+    // this sequence's split scratch and tickets; the protocol of decode_attention_kernel
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(a.part) + (size_t)sb * a.nsplit * H * D;
+    unsigned* ticket = a.ticket + (size_t)sb * H;
+    if (tid < D) __hip_atomic_store(part + ((size_t)c * H + h) * D + tid, (unsigned long long)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) s_ticket = __hip_atomic_fetch_add(ticket + h, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (s_ticket != (unsigned)(nsplit - 1)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (tid == 0) __hip_atomic_store(ticket + h, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < D) {
+      tot = 0;
+      for (int cc = 0; cc < nsplit; ++cc)
+        tot += (long long)__hip_atomic_load(part + ((size_t)cc * H + h) * D + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  if (tid < D) {
+    const size_t o = ((size_t)sb * H + h) * D + tid;
+    const float pre = (float)((double)tot * (double)alpha_pv);
+    const float y = po.fq(pre);
+    if (a.out) a.out[o] = y;
+    if (a.out_q) {
+      const float qi = dq_index(y, oi.s, oi.inv_s, oi.o, oi.qmin, oi.qmax);
+      a.out_q[o] = (int8_t)((qi != qi ? (int)oi.qmin : (int)qi) - 128);
+    }
+  }
+}
+
+// ---- final norm for B rows + the fp32 lm_head streamed once -----------------------------------------------------------------------
+// decode_head_kernel's arithmetic per row: the norm's reductions over 256 threads (i = tid, tid + 256, ...), wave_sum_f, the four wave
+// partials as (w0 + w1) + (w2 + w3); a vocabulary row per wave, lane l summing float4 chunks l, l + 64, ... ascending with four adds
+// each, then wave_sum_f.  Each lane holds B accumulators against one weight request.
+__global__ void __launch_bounds__(256) decode_head_batch_kernel(const mq_decode_head_batch_args hb) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* s_x = reinterpret_cast<float*>(smem_raw);               // [B][K] normalised rows
+  __shared__ float s_red[DB_MAXB][4], s_red2[DB_MAXB][4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int B = hb.batch, K = (int)hb.K, V = (int)hb.V;
+  const float* __restrict__ norm_w = hb.norm_weight;
+  const float* __restrict__ norm_b = hb.norm_bias;
+  const float eps = hb.eps;
+  bool act[DB_MAXB];
+#pragma unroll
+  for (int b = 0; b < DB_MAXB; ++b) {
+    const int pb = (hb.pos && b < B) ? hb.pos[b] : 0;
+    act[b] = b < B && pb >= 0 && (!hb.pos || pb < hb.cache_len);
+  }
+  auto xr = [&](int b) { return hb.x + (size_t)b * hb.x_stride; };
+  if (hb.layernorm) {
+    float s1[DB_MAXB];
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) s1[b] = 0.f;
+    for (int i = tid; i < K; i += 256) {
+#pragma unroll
+      for (int b = 0; b < DB_MAXB; ++b)
+        if (act[b]) s1[b] += xr(b)[i];
+    }
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (act[b]) {
+        const float t = wave_sum_f(s1[b]);
+        if (lane == 0) s_red[b][wv] = t;
+      }
+    }
+    __syncthreads();
+    float mu[DB_MAXB], s2[DB_MAXB];
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      mu[b] = act[b] ? __fdiv_rn((s_red[b][0] + s_red[b][1]) + (s_red[b][2] + s_red[b][3]), (float)K) : 0.f;
+      s2[b] = 0.f;
+    }
+    for (int i = tid; i < K; i += 256) {
+#pragma unroll
+      for (int b = 0; b < DB_MAXB; ++b) {
+        if (act[b]) {
+          const float d = xr(b)[i] - mu[b];
+          s2[b] += d * d;
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (act[b]) {
+        const float t = wave_sum_f(s2[b]);
+        if (lane == 0) s_red2[b][wv] = t;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (act[b]) {
+        const float var = __fdiv_rn((s_red2[b][0] + s_red2[b][1]) + (s_red2[b][2] + s_red2[b][3]), (float)K);
+        const float r = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, eps))), sh = __fmul_rn(-r, mu[b]);
+        for (int i = tid; i < K; i += 256) {
+          float y = __fadd_rn(__fmul_rn(xr(b)[i], r), sh);
+          if (norm_w) y = __fmul_rn(y, norm_w[i]);
+          if (norm_b) y = __fadd_rn(y, norm_b[i]);
+          s_x[(size_t)b * K + i] = y;
+        }
+      }
+    }
+  } else {
+    float ss[DB_MAXB];
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) ss[b] = 0.f;
+    for (int i = tid; i < K; i += 256) {
+#pragma unroll
+      for (int b = 0; b < DB_MAXB; ++b) {
+        if (act[b]) {
+          const float v = xr(b)[i];
+          ss[b] += v * v;
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (act[b]) {
+        const float t = wave_sum_f(ss[b]);
+        if (lane == 0) s_red[b][wv] = t;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (act[b]) {
+        const float mean = __fdiv_rn((s_red[b][0] + s_red[b][1]) + (s_red[b][2] + s_red[b][3]), (float)K);
+        const float r = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(mean, eps)));
+        for (int i = tid; i < K; i += 256) s_x[(size_t)b * K + i] = norm_w ? __fmul_rn(norm_w[i], __fmul_rn(xr(b)[i], r)) : xr(b)[i];
+      }
+    }
+  }
+  __syncthreads();
+  // a wave per vocabulary row; NV requests per lane in flight, each contracted with every active row
+  constexpr int NV = 8;
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  const int nvec = K >> 2;
+  const int stride = gridDim.x * 4;
+  for (int row = blockIdx.x * 4 + wv; row < V; row += stride) {
+    const v4f* wr = reinterpret_cast<const v4f*>(hb.w + (size_t)row * K);
+    float acc[DB_MAXB];
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) acc[b] = 0.f;
+    for (int i0 = lane; i0 < nvec; i0 += 64 * NV) {
+      v4f wb[NV];
+#pragma unroll
+      for (int jj = 0; jj < NV; ++jj) {
+        const int i = i0 + 64 * jj;
+        wb[jj] = __builtin_nontemporal_load(wr + (i < nvec ? i : i0));
+      }
+#pragma unroll
+      for (int jj = 0; jj < NV; ++jj) {
+        const int i = i0 + 64 * jj;
+        if (i < nvec) {
+#pragma unroll
+          for (int b = 0; b < DB_MAXB; ++b) {
+            if (act[b]) {
+              const float4 xb = reinterpret_cast<const float4*>(s_x + (size_t)b * K)[i];
+              acc[b] += wb[jj][0] * xb.x;
+              acc[b] += wb[jj][1] * xb.y;
+              acc[b] += wb[jj][2] * xb.z;
+              acc[b] += wb[jj][3] * xb.w;
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < DB_MAXB; ++b) {
+      if (act[b]) {
+        const float s = wave_sum_f(acc[b]);
+        if (lane == 0) hb.logits[(size_t)b * hb.logits_stride + row] = hb.bias ? s + hb.bias[row] : s;
+      }
+    }
+  }
+}
+
+}  // namespace mq
+
+using namespace mq;
+
+extern "C" {
+
+static int batch_gemv_geometry(int NL, int* rows_per_wg, unsigned* grid) {
+  static std::atomic<int> cus_of[kMaxDevices];
+  const int dev = current_device();
+  int cus = cus_of[dev].load(std::memory_order_relaxed);
+  if (!cus) {
+    hipDeviceProp_t prop;
+    cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    cus_of[dev].store(cus, std::memory_order_relaxed);
+  }
+  int rpw = (NL + cus - 1) / cus;
+  if (rpw > DG_STR * 64) rpw = DG_STR * 64;
+  *rows_per_wg = rpw;
+  *grid = (unsigned)((NL + rpw - 1) / rpw);
+  return NL;
+}
+
+// raise a kernel's dynamic-LDS ceiling once per device (above the default 64 KiB)
+static int set_lds(const void* fn, std::atomic<size_t>* cache, size_t lds, const char* name) {
+  if (lds > 32768 && cache[current_device()].load(std::memory_order_relaxed) < lds) {
+    MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess, "%s: %zu bytes of dynamic LDS rejected", name, lds);
+    cache[current_device()].store(lds, std::memory_order_relaxed);
+  }
+  return MQ_OK;
+}
+
+int mq_decode_gemv_batch(const mq_decode_gemv_batch_args* args, mq_stream_t stream) {
+  MQ_REQUIRE(args != nullptr, "mq_decode_gemv_batch: null argument block");
+  const mq_decode_gemv_args& g = args->g;
+  const int B = args->batch;
+  MQ_REQUIRE(B >= 1 && B <= MQ_DECODE_MAX_BATCH, "mq_decode_gemv_batch: batch=%d outside 1..%d", B, MQ_DECODE_MAX_BATCH);
+  MQ_REQUIRE(g.w && g.alpha && g.w_zp && g.col_term && (g.x || g.xq), "mq_decode_gemv_batch: null pointer");
+  MQ_REQUIRE(g.consts != nullptr && aligned(g.consts, 16), "mq_decode_gemv_batch: consts (mq_decode_pack_grids of this launch's grids) is required, 16-byte aligned");
+  MQ_REQUIRE(g.K > 0 && g.K % 256 == 0 && g.K <= 32768 && g.N > 0, "mq_decode_gemv_batch: K=%d must be a positive multiple of 256 (<= 32768), N=%d", g.K, g.N);
+  MQ_REQUIRE((int64_t)B * g.K <= DB_MAX_IMAGE, "mq_decode_gemv_batch: batch * K = %lld exceeds the %d bytes of int8 images the workgroup holds in LDS",
+             (long long)B * g.K, DB_MAX_IMAGE);
+  MQ_REQUIRE(g.xq || g.K <= DG_XPRE * 4 * DG_PRO * 64, "mq_decode_gemv_batch: K=%d exceeds the fp32 activation row the prologue serves (8192)", g.K);
+  MQ_REQUIRE(!g.zero_acc && !g.o_acc, "mq_decode_gemv_batch: zero_acc / o_acc (the four-launch chain) are not served by the batched launch");
+  MQ_REQUIRE(g.xq || (g.a_grid.scale && g.a_grid.offset && g.a_grid.qmin == 0.f && g.a_grid.qmax == 255.f),
+             "mq_decode_gemv_batch: fp32 activations need an 8-bit unsigned activation grid");
+  MQ_REQUIRE(args->x_stride >= (B > 1 ? g.K : 0) && args->x_stride % 16 == 0 && aligned(g.w, 16) && (!g.x || aligned(g.x, 16)) &&
+                 (!g.xq || aligned(g.xq, 16)) && (!g.norm_w || aligned(g.norm_w, 16)),
+             "mq_decode_gemv_batch: pointers must be 16-byte aligned and x_stride a multiple of 16 covering K");
+  const bool gate = g.gate_q != nullptr;
+  MQ_REQUIRE(gate || g.y, "mq_decode_gemv_batch: no output");
+  MQ_REQUIRE(!gate || (g.norm_w && !g.xq), "mq_decode_gemv_batch: gate mode is served for the norm-fused prologue (fp32 x + norm_w)");
+  MQ_REQUIRE(!gate || (g.N % 2 == 0 && g.gate_out.scale && g.out_grid[0].scale && g.out_grid[1].scale && (g.gate_act == 0 || g.gate_act == 1)),
+             "mq_decode_gemv_batch: gate mode needs an even N (interleaved w1 / w3 rows), both output grids and the w2 input grid");
+  const int NLr = gate ? g.N / 2 : g.N;
+  MQ_REQUIRE(B == 1 || ((!g.y || args->y_stride >= NLr) && (!g.resid || args->y_stride >= NLr) && (!gate || args->gate_stride >= NLr)),
+             "mq_decode_gemv_batch: y_stride / gate_stride must cover a row (%d)", NLr);
+  MQ_REQUIRE(!g.norm_bias || (g.layernorm && aligned(g.norm_bias, 16)), "mq_decode_gemv_batch: norm_bias belongs to the LayerNorm prologue (layernorm = 1), 16-byte aligned");
+  int rows_per_wg;
+  unsigned grid;
+  batch_gemv_geometry(NLr, &rows_per_wg, &grid);
+  const size_t lds = (size_t)B * g.K;
+  hipStream_t st = as_stream(stream);
+  const int xmode = g.xq ? XM_I8 : (g.norm_w ? (g.layernorm ? XM_LNORM : XM_NORM) : XM_F32);
+  // instantiation index: xmode (4) x gate (2) x w4 (2)
+  static std::atomic<size_t> lds_set[16][kMaxDevices];
+  const int ki = (xmode * 2 + (gate ? 1 : 0)) * 2 + (g.w4 ? 1 : 0);
+#define MQ_DB_LAUNCH(XM, GT, W4)                                                                                            \
+  do {                                                                                                                      \
+    const int rc = set_lds(reinterpret_cast<const void*>(decode_gemv_batch_kernel<XM, GT, W4>), lds_set[ki], lds, "mq_decode_gemv_batch"); \
+    if (rc != MQ_OK) return rc;                                                                                             \
+    decode_gemv_batch_kernel<XM, GT, W4><<<grid, DG_THREADS, lds, st>>>(*args, rows_per_wg);                                \
+  } while (0)
+#define MQ_DB_LAUNCH_W4(XM, GT)                 \
+  do {                                          \
+    if (g.w4) MQ_DB_LAUNCH(XM, GT, true);       \
+    else MQ_DB_LAUNCH(XM, GT, false);           \
+  } while (0)
+  if (gate) {
+    if (xmode == XM_LNORM) MQ_DB_LAUNCH_W4(XM_LNORM, true);
+    else MQ_DB_LAUNCH_W4(XM_NORM, true);
+  } else if (xmode == XM_LNORM) {
+    MQ_DB_LAUNCH_W4(XM_LNORM, false);
+  } else if (xmode == XM_NORM) {
+    MQ_DB_LAUNCH_W4(XM_NORM, false);
+  } else if (xmode == XM_F32) {
+    MQ_DB_LAUNCH_W4(XM_F32, false);
+  } else {
+    MQ_DB_LAUNCH_W4(XM_I8, false);
+  }
+#undef MQ_DB_LAUNCH_W4
+#undef MQ_DB_LAUNCH
+  MQ_LAUNCH_CHECK("mq_decode_gemv_batch");
+  return MQ_OK;
+}
+
+// the five-launch attention's bound (mq_decode.hip kAttnMaxCache): 4 bytes of LDS per cached position plus <= 9 KB static
+constexpr int kBatchAttnMaxCache = 32768;
+
+int mq_decode_attention_batch(const mq_decode_attention_batch_args* args, mq_stream_t stream) {
+  MQ_REQUIRE(args != nullptr, "mq_decode_attention_batch: null argument block");
+  const mq_decode_attention_args& a = args->a;
+  const int B = args->batch;
+  MQ_REQUIRE(B >= 1 && B <= MQ_DECODE_MAX_BATCH, "mq_decode_attention_batch: batch=%d outside 1..%d", B, MQ_DECODE_MAX_BATCH);
+  MQ_REQUIRE(a.qkv && a.k_cache && a.v_cache && a.cos && a.sin && a.pos && a.consts && (a.out || a.out_q), "mq_decode_attention_batch: null pointer");
+  MQ_REQUIRE(a.heads > 0 && a.kv_heads > 0 && a.heads % a.kv_heads == 0 && (a.head_dim == 32 || a.head_dim == 64 || a.head_dim == 128 || a.head_dim == 256) &&
+                 a.cache_len > 0 && a.cache_len <= kBatchAttnMaxCache && a.rot_dim > 0 && a.rot_dim <= a.head_dim && a.rot_dim % 2 == 0,
+             "mq_decode_attention_batch: heads=%d kv_heads=%d head_dim=%d (32 / 64 / 128 / 256) cache_len=%d (<= %d) rot_dim=%d", a.heads, a.kv_heads,
+             a.head_dim, a.cache_len, kBatchAttnMaxCache, a.rot_dim);
+  MQ_REQUIRE(a.nsplit >= 1 && a.nsplit <= 16 && (a.nsplit == 1 || (a.part && a.ticket)), "mq_decode_attention_batch: nsplit=%d (1..16; > 1 needs part and ticket)", a.nsplit);
+  MQ_REQUIRE(a.qk_a.scale && a.qk_b.scale && a.pv_a.scale && a.pv_b.scale && a.qk_a.qmin == 0.f && a.qk_a.qmax == 255.f && a.qk_b.qmin == 0.f &&
+                 a.qk_b.qmax == 255.f && a.pv_b.qmin == 0.f && a.pv_b.qmax == 255.f && a.pv_a.qmin == 0.f && a.pv_a.qmax <= 65535.f,
+             "mq_decode_attention_batch: q / k / v need 8-bit unsigned grids, the probabilities an unsigned grid of at most 16 bits");
+  MQ_REQUIRE(!a.out_q || (a.o_in.scale && a.o_in.qmin == 0.f && a.o_in.qmax == 255.f), "mq_decode_attention_batch: the int8 output image needs the consumer's 8-bit unsigned grid (o_in)");
+  MQ_REQUIRE(aligned(a.k_cache, 16) && aligned(a.v_cache, 16) && aligned(a.consts, 16) && aligned(a.qkv, 4), "mq_decode_attention_batch: caches / consts must be 16-byte aligned");
+  MQ_REQUIRE(a.prefetch_wgs == 0, "mq_decode_attention_batch: no prefetch rows (prefetch_wgs must be 0)");
+  MQ_REQUIRE(B == 1 || args->qkv_stride >= (int64_t)(a.heads + 2 * a.kv_heads) * a.head_dim, "mq_decode_attention_batch: qkv_stride must cover a q | k | v row");
+  const size_t lds = (size_t)a.cache_len * sizeof(float);
+  const void* fn = a.head_dim == 32 ? reinterpret_cast<const void*>(decode_attention_batch_kernel<32>)
+                   : a.head_dim == 64 ? reinterpret_cast<const void*>(decode_attention_batch_kernel<64>)
+                   : a.head_dim == 128 ? reinterpret_cast<const void*>(decode_attention_batch_kernel<128>)
+                                       : reinterpret_cast<const void*>(decode_attention_batch_kernel<256>);
+  static std::atomic<size_t> lds_set[4][kMaxDevices];
+  const int rc = set_lds(fn, lds_set[a.head_dim == 32 ? 0 : a.head_dim == 64 ? 1 : a.head_dim == 128 ? 2 : 3], lds, "mq_decode_attention_batch");
+  if (rc != MQ_OK) return rc;
+  const dim3 grid((unsigned)a.heads, (unsigned)a.nsplit, (unsigned)B);
+  hipStream_t st = as_stream(stream);
+  switch (a.head_dim) {
+    case 32: decode_attention_batch_kernel<32><<<grid, 256, lds, st>>>(*args); break;
+    case 64: decode_attention_batch_kernel<64><<<grid, 256, lds, st>>>(*args); break;
+    case 128: decode_attention_batch_kernel<128><<<grid, 256, lds, st>>>(*args); break;
+    default: decode_attention_batch_kernel<256><<<grid, 256, lds, st>>>(*args); break;
+  }
+  MQ_LAUNCH_CHECK("mq_decode_attention_batch");
+  return MQ_OK;
+}
+
+int mq_decode_head_batch(const mq_decode_head_batch_args* args, mq_stream_t stream) {
+  MQ_REQUIRE(args != nullptr, "mq_decode_head_batch: null argument block");
+  const mq_decode_head_batch_args& h = *args;
+  const int B = h.batch;
+  MQ_REQUIRE(B >= 1 && B <= MQ_DECODE_MAX_BATCH, "mq_decode_head_batch: batch=%d outside 1..%d", B, MQ_DECODE_MAX_BATCH);
+  MQ_REQUIRE(h.x && h.w && h.logits, "mq_decode_head_batch: null pointer");
+  MQ_REQUIRE(h.K > 0 && h.K % 4 == 0 && h.K <= 12288 && h.V > 0 && h.V <= INT32_MAX, "mq_decode_head_batch: bad arguments (K %% 4 == 0, K <= 12288, V > 0)");
+  MQ_REQUIRE((int64_t)B * h.K <= 32768, "mq_decode_head_batch: batch * K = %lld exceeds the 32768 normalised floats the workgroup holds in LDS", (long long)B * h.K);
+  MQ_REQUIRE(B == 1 || (h.x_stride >= h.K && h.logits_stride >= h.V), "mq_decode_head_batch: x_stride / logits_stride must cover a row");
+  MQ_REQUIRE(aligned(h.w, 16), "mq_decode_head_batch: the weight must be 16-byte aligned");
+  MQ_REQUIRE(!h.pos || h.cache_len > 0, "mq_decode_head_batch: pos needs cache_len > 0");
+  int64_t blocks = (h.V + 3) / 4;
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  const size_t lds = (size_t)B * h.K * sizeof(float);
+  static std::atomic<size_t> lds_set[kMaxDevices];
+  const int rc = set_lds(reinterpret_cast<const void*>(decode_head_batch_kernel), lds_set, lds, "mq_decode_head_batch");
+  if (rc != MQ_OK) return rc;
+  decode_head_batch_kernel<<<(unsigned)blocks, 256, lds, as_stream(stream)>>>(h);
+  MQ_LAUNCH_CHECK("mq_decode_head_batch");
+  return MQ_OK;
+}
+
+}  // extern "C"

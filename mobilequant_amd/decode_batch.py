@@ -1,0 +1,367 @@
+"""Batched decode: up to eight independent sequences ("slots") advanced by one step together, each with its own position and its own
+int8 KV cache (csrc/mq_decode_batch.hip).
+
+``DecodeEngine`` streams the whole model for one token per step.  ``BatchDecodeEngine`` lowers every decoder layer to the same five
+launches (norm + q|k|v, attention, o_proj + residual, norm + w1|w3 + gate, w2 + residual) but each launch serves B activation rows:
+the weights are read once per step for all slots.  The contract is per sequence: slot b of a batched step computes exactly -- bit for
+bit -- what ``DecodeEngine`` computes for that sequence alone.
+
+Positions live in device memory (``pos [B]``), so ONE captured hipGraph serves every mix of slot positions: the attention launch
+chooses each sequence's split count on the device, and a slot whose position is the ``cache_len`` sentinel is idle -- its cache and
+its logits row do not change.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import _lib
+from ._lib import MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs, MqDecodeHeadBatchArgs
+from .decode import DecodeEngine, _grid, _Keep, _Linear
+from .quantization import qmodule as Q
+
+MAX_BATCH = 8
+
+
+class BatchDecodeEngine:
+    """B single-token decode streams over one model.  Slots are filled with prefill(slot, ids), emptied with release(slot) and all
+    active slots advance together with step()."""
+
+    LONG_FROM, LONG_SPLITS = DecodeEngine.LONG_FROM, DecodeEngine.LONG_SPLITS      # per sequence, on the device
+    MAX_IMAGE_BYTES = 128 * 1024                                                   # B * K int8 images in the GEMV launches' LDS
+    MAX_HEAD_FLOATS = 32768                                                        # B * hidden normalised floats in the head's LDS
+
+    # the lowering helpers of the single-sequence engine, shared as they are (they only touch self._keep / self.dev)
+    _norm_args = DecodeEngine._norm_args
+    _gemv = DecodeEngine._gemv
+    _pack = DecodeEngine._pack
+    _finish_gemv = DecodeEngine._finish_gemv
+    _attention_grids = DecodeEngine._attention_grids
+
+    def __init__(self, model, batch: int, cache_len: int = 2048):
+        from .llama import LlamaForCausalLM
+        assert isinstance(model, LlamaForCausalLM)
+        B = int(batch)
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError(f"BatchDecodeEngine: batch={batch} outside 1..{MAX_BATCH}")
+        self.model, self.shape, self.batch = model, model.shape, B
+        s = self.shape
+        dev = next(model.parameters()).device
+        self.dev, self.cache_len = dev, int(cache_len)
+        if not 0 < self.cache_len <= DecodeEngine.max_cache_len(5, s.head_dim):
+            raise RuntimeError(f"BatchDecodeEngine: cache_len={cache_len} is outside 1 .. {DecodeEngine.max_cache_len(5, s.head_dim)}")
+        big = max(s.hidden, s.ffn, s.heads * s.head_dim)
+        if B * big > self.MAX_IMAGE_BYTES or B * s.hidden > self.MAX_HEAD_FLOATS:
+            raise RuntimeError(f"BatchDecodeEngine: batch {B} x K {big} exceeds the {self.MAX_IMAGE_BYTES} bytes of activation images a launch holds")
+        self.cos, self.sin = model.cos.contiguous(), model.sin.contiguous()
+        assert self.cos.shape[0] >= self.cache_len, "rope tables shorter than the cache"
+        qkv_n = (s.heads + 2 * s.kv_heads) * s.head_dim
+        self.x = torch.zeros(B, s.hidden, device=dev)
+        self.qkv = torch.zeros(B, qkv_n, device=dev)
+        self.attn_q = torch.zeros(B, s.heads * s.head_dim, dtype=torch.int8, device=dev)
+        self.attn_part = torch.zeros(B, self.LONG_SPLITS, s.heads * s.head_dim, dtype=torch.int64, device=dev)
+        self.attn_ticket = torch.zeros(B, s.heads, dtype=torch.int32, device=dev)
+        self.gate_q = torch.zeros(B, s.ffn, dtype=torch.int8, device=dev)
+        self.logits = torch.zeros(B, s.vocab, device=dev)
+        self.pos = torch.full((B,), self.cache_len, dtype=torch.int32, device=dev)       # every slot idle
+        self.tok = torch.zeros(B, dtype=torch.int64, device=dev)
+        # [B][kv_heads][cache_len][head_dim] int8 indices (index - 128) on qk_bmm.input2 / pv_bmm.input2's grids
+        self.k_cache = [torch.zeros(B, s.kv_heads, self.cache_len, s.head_dim, dtype=torch.int8, device=dev) for _ in model.layers]
+        self.v_cache = [torch.zeros(B, s.kv_heads, self.cache_len, s.head_dim, dtype=torch.int8, device=dev) for _ in model.layers]
+        self._host_pos = [self.cache_len] * B
+        self._active = [False] * B
+        self.graph = None
+        self._lower()
+
+    # -- lowering ----------------------------------------------------------------------------------------------------------
+    def _lower(self):
+        """Launch records from the model as it is now (snapshots, as DecodeEngine._lower)."""
+        model, s = self.model, self.shape
+        self._keep = _Keep()
+        self.phases = []
+        self.embed = model.embed_tokens.weight.detach()
+        if s.embed_scale:
+            self.embed = self.embed * (s.hidden ** 0.5)
+        self.norm_ln = isinstance(model.norm, torch.nn.LayerNorm)
+        self.norm_w = model.norm.weight.detach().float().contiguous()
+        self.norm_b = model.norm.bias.detach().float().contiguous() if getattr(model.norm, "bias", None) is not None else None
+        self.lm_w = model.lm_head.weight.detach().float().contiguous()
+        self.lm_b = model.lm_head.bias.detach().float().contiguous() if model.lm_head.bias is not None else None
+        for w in (model.embed_tokens.weight, model.norm.weight, getattr(model.norm, "bias", None), model.lm_head.weight, model.lm_head.bias):
+            if w is not None:
+                self._keep.weights.append((w, Q._ver(w)))
+        for q in model.modules():
+            if isinstance(q, Q.Quantizer) and q._has_grid() and q.scale.device != self.dev:
+                q.scale.data, q.offset.data = q.scale.to(self.dev), q.offset.to(self.dev)
+        with torch.no_grad():
+            for li, layer in enumerate(model.layers):
+                self._lower_layer(li, layer)
+        hb = MqDecodeHeadBatchArgs()
+        hb.x, hb.x_stride = self.x.data_ptr(), s.hidden
+        hb.norm_weight, hb.norm_bias = self.norm_w.data_ptr(), (self.norm_b.data_ptr() if self.norm_b is not None else None)
+        hb.layernorm, hb.eps = int(self.norm_ln), float(model.norm.eps)
+        hb.w, hb.bias = self.lm_w.data_ptr(), (self.lm_b.data_ptr() if self.lm_b is not None else None)
+        hb.K, hb.V, hb.batch = s.hidden, s.vocab, self.batch
+        hb.logits, hb.logits_stride = self.logits.data_ptr(), s.vocab
+        hb.pos, hb.cache_len = self.pos.data_ptr(), self.cache_len
+        self.head = hb
+        self.weight_bytes = sum(p[1]._mq_bytes for p in self.phases if hasattr(p[1], "_mq_bytes"))
+        self.head_bytes = self.lm_w.numel() * 4
+
+    def _batched(self, a: MqDecodeGemvArgs, x_stride: int, y_stride: int, gate_stride: int = 0) -> MqDecodeGemvBatchArgs:
+        b = MqDecodeGemvBatchArgs()
+        b.g, b.batch, b.x_stride, b.y_stride, b.gate_stride = a, self.batch, x_stride, y_stride, gate_stride
+        b._mq_bytes = a._mq_bytes
+        return b
+
+    def _lower_layer(self, li, layer):
+        """The five launches of DecodeEngine._lower_layer, each over the B rows of the slot buffers."""
+        s, keep = self.shape, self._keep
+        attn, mlp = layer.self_attn, layer.mlp
+        for m in (attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj, mlp.w1, mlp.w2, mlp.w3):
+            if not isinstance(m, Q.QLinear):
+                raise RuntimeError("BatchDecodeEngine: run create_sim_qmodel first")
+        H, D = s.heads, s.head_dim
+        # (1) input_layernorm + q|k|v
+        a = MqDecodeGemvArgs()
+        g_in = self._norm_args(layer.input_layernorm, a)
+        qkv = _Linear([attn.q_proj, attn.k_proj, attn.v_proj], g_in)
+        p1 = self._gemv(qkv, x=self.x.data_ptr(), norm_w=a.norm_w, norm_bias=a.norm_bias, layernorm=a.layernorm, norm_in=a.norm_in, eps=a.eps,
+                        a_grid=a.a_grid, y=self.qkv.data_ptr())
+        p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
+        for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
+            p1.out_grid[k] = _grid(lin.output_quantizer, keep)
+        self.phases.append(("gemv", self._batched(self._finish_gemv(p1), s.hidden, self.qkv.shape[1])))
+        # (2) attention core, per sequence
+        at = MqDecodeAttentionArgs()
+        at.qkv, at.k_cache, at.v_cache = self.qkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
+        at.cos, at.sin, at.pos = self.cos.data_ptr(), self.sin.data_ptr(), self.pos.data_ptr()
+        at.heads, at.kv_heads, at.head_dim, at.cache_len = H, s.kv_heads, D, self.cache_len
+        at.rot_dim, at.nsplit = self.cos.shape[1], self.LONG_SPLITS
+        g_o = self._attention_grids(attn, at, keep)
+        at.out_q, at.part, at.ticket = self.attn_q.data_ptr(), self.attn_part.data_ptr(), self.attn_ticket.data_ptr()
+        ab = MqDecodeAttentionBatchArgs()
+        ab.a, ab.batch, ab.split_from, ab.qkv_stride = at, self.batch, self.LONG_FROM, self.qkv.shape[1]
+        self.phases.append(("attn", ab))
+        # (3) o_proj + residual from the int8 image
+        op = _Linear([attn.o_proj], g_o)
+        p3 = self._gemv(op, xq=self.attn_q.data_ptr(), a_grid=_grid(g_o, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
+        p3.out_grid[0] = _grid(attn.o_proj.output_quantizer, keep)
+        self.phases.append(("gemv", self._batched(self._finish_gemv(p3), H * D, s.hidden)))
+        # (4) post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
+        a2 = MqDecodeGemvArgs()
+        g_ffn = self._norm_args(layer.post_attention_layernorm, a2)
+        w13 = _Linear([mlp.w1, mlp.w3], g_ffn, interleave=True)
+        act = mlp.act_fn
+        if not isinstance(act, (Q.QSiLU, Q.QGELU)) or (act.input_quantizer is not None and not act.input_quantizer.bypassed()):
+            raise RuntimeError("BatchDecodeEngine: act_fn must be QSiLU / QGELU without an input quantizer (the reference's surgery)")
+        iq2 = mlp.w2.input_quantizer
+        if iq2 is None or iq2.qmax != 255:
+            raise RuntimeError("BatchDecodeEngine: w2 needs its own 8-bit unsigned input quantizer")
+        p4 = self._gemv(w13, x=self.x.data_ptr(), norm_w=a2.norm_w, norm_bias=a2.norm_bias, layernorm=a2.layernorm, norm_in=a2.norm_in,
+                        eps=a2.eps, a_grid=a2.a_grid,
+                        gate_q=self.gate_q.data_ptr(), gate_act=0 if isinstance(act, Q.QSiLU) else 1,
+                        gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
+                        gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep))
+        p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
+        self.phases.append(("gemv", self._batched(self._finish_gemv(p4), s.hidden, 0, s.ffn)))
+        # (5) w2 from the int8 image + residual
+        w2 = _Linear([mlp.w2], iq2)
+        p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
+        p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
+        self.phases.append(("gemv", self._batched(self._finish_gemv(p5), s.ffn, s.hidden)))
+
+    def grids_stale(self) -> bool:
+        return self._keep.stale()
+
+    def refresh_grids(self):
+        """Re-derive every launch record from the model's current quantizers (DecodeEngine.refresh_grids); re-records the graph."""
+        had_graph = self.graph is not None
+        self.graph = None
+        self._lower()
+        if had_graph:
+            self.capture()
+        return self
+
+    def _sync_grids(self):
+        if self._keep.stale():
+            self.refresh_grids()
+
+    # -- running -------------------------------------------------------------------------------------------------------------
+    _ENTRY = {"gemv": "mq_decode_gemv_batch", "attn": "mq_decode_attention_batch"}
+
+    def _launch(self):
+        """embedding gather + 5 launches per layer + norm / lm_head for all slots, on the current stream; reads self.tok / self.pos."""
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        torch.index_select(self.embed, 0, self.tok, out=self.x)
+        for kind, a in self.phases:
+            _lib.call(self._ENTRY[kind], ctypes.byref(a), st)
+        _lib.call("mq_decode_head_batch", ctypes.byref(self.head), st)
+
+    def _advance(self):
+        self.pos.add_((self.pos < self.cache_len).to(torch.int32))         # active slots only (idle ones hold the sentinel)
+
+    def capture(self):
+        """Record one step for all slots (incl. the position advance) as ONE hipGraph on one stream; step() replays it.  Every mix of
+        slot positions replays the same graph: the attention launch picks each sequence's split count from its position."""
+        self._sync_grids()
+        pos0 = self.pos.clone()
+        self.pos.fill_(self.cache_len)            # the warm-up below runs with every slot idle: no cache or logits row changes
+        self.attn_ticket.zero_()
+        with torch.cuda.device(self.dev):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._launch()                    # (sets the launches' LDS ceilings outside the capture)
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launch()
+                self._advance()
+        self.pos.copy_(pos0)
+        self.graph = g
+        return self
+
+    def position(self, slot: int) -> int:
+        """Cached positions of the slot's sequence (what the next step appends at); cache_len for an idle slot."""
+        return self._host_pos[slot]
+
+    def active(self, slot: int) -> bool:
+        return self._active[slot]
+
+    def cached_keys(self, slot: int, li: int, n: Optional[int] = None) -> torch.Tensor:
+        """Layer li's cached keys of the slot: [kv_heads, n positions, head_dim] int8 indices (index - 128)."""
+        n = self.position(slot) if n is None else int(n)
+        return self.k_cache[li][slot, :, :n]
+
+    def cached_values(self, slot: int, li: int, n: Optional[int] = None) -> torch.Tensor:
+        """Layer li's cached values of the slot: [kv_heads, n positions, head_dim] int8 indices (index - 128)."""
+        n = self.position(slot) if n is None else int(n)
+        return self.v_cache[li][slot, :, :n]
+
+    def _check_slot(self, slot: int):
+        if not 0 <= int(slot) < self.batch:
+            raise IndexError(f"BatchDecodeEngine: slot {slot} outside 0..{self.batch - 1}")
+
+    def set_position(self, slot: int, pos: int):
+        """Make the slot active with `pos` cached positions (benchmarks and prefill())."""
+        self._check_slot(slot)
+        assert 0 <= int(pos) <= self.cache_len
+        self.pos[slot] = int(pos)
+        self._host_pos[slot] = int(pos)
+        self._active[slot] = True
+
+    def release(self, slot: int):
+        """The slot goes idle: its position becomes the cache_len sentinel, its cache and logits row stop changing."""
+        self._check_slot(slot)
+        self.pos[slot] = self.cache_len
+        self._host_pos[slot] = self.cache_len
+        self._active[slot] = False
+
+    def fill_cache_random(self, slot: int, n: int, seed: int = 0):
+        """Benchmark helper: n positions of random cached indices in one slot, which becomes active at position n."""
+        g = torch.Generator(device=self.dev).manual_seed(seed)
+        s = self.shape
+        for c in self.k_cache + self.v_cache:
+            c[slot, :, :n] = torch.randint(-128, 128, (s.kv_heads, n, s.head_dim), generator=g, device=self.dev, dtype=torch.int8)
+        self.set_position(slot, n)
+
+    @torch.no_grad()
+    def prefill(self, slot: int, context_ids) -> torch.Tensor:
+        """DecodeEngine.prefill for one slot: one module-graph forward over the context, its keys / values on their QMatMul input
+        grids into the slot's caches, the slot's position behind the context.  The other slots are untouched.  Returns the logits row
+        of the last context position."""
+        self._check_slot(slot)
+        ids = torch.as_tensor([int(t) for t in context_ids], dtype=torch.long, device=self.dev).view(1, -1)
+        S = ids.shape[1]
+        assert 0 < S <= self.cache_len
+        self._sync_grids()
+        raw = self.model.new_cache(1, S, device=self.dev)
+        logits = self.model(ids, cache=raw, last_logits_only=True)
+        for li, layer in enumerate(self.model.layers):
+            att = layer.self_attn
+            self.k_cache[li][slot].zero_()
+            self.v_cache[li][slot].zero_()
+            self.k_cache[li][slot, :, :S] = att.qk_bmm.input2_quantizer.quantize_to_int(raw[li][0][0].contiguous())[0]
+            self.v_cache[li][slot, :, :S] = att.pv_bmm.input2_quantizer.quantize_to_int(raw[li][1][0].contiguous())[0]
+        self.set_position(slot, S)
+        self.logits[slot].copy_(logits[0, -1])
+        return self.logits[slot]
+
+    def start(self, slot: int):
+        """Make the slot active at position 0 with an empty cache (a sequence fed token by token through step())."""
+        self._check_slot(slot)
+        for c in self.k_cache + self.v_cache:
+            c[slot].zero_()
+        self.set_position(slot, 0)
+
+    @torch.no_grad()
+    def step(self, tokens: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """One step for every active slot: tokens (length B; entries of idle slots are ignored) or None to use the device-side tok [B].
+        Returns logits [B, vocab] (device tensor, overwritten by the next step); active slots advance by one position."""
+        for b in range(self.batch):
+            if self._active[b] and self._host_pos[b] >= self.cache_len:
+                raise RuntimeError(f"BatchDecodeEngine.step: slot {b}'s KV cache is full ({self.cache_len} positions); release() it first")
+        if tokens is not None:
+            t = [int(v) for v in tokens]
+            if len(t) != self.batch:
+                raise ValueError(f"BatchDecodeEngine.step: {len(t)} tokens for {self.batch} slots")
+            self.tok.copy_(torch.tensor(t, dtype=torch.int64), non_blocking=False)
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            with torch.cuda.device(self.dev):
+                self._launch()
+            self._advance()
+        for b in range(self.batch):
+            if self._active[b]:
+                self._host_pos[b] += 1
+        return self.logits
+
+    @torch.no_grad()
+    def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_token_id=None, do_sample: bool = False,
+                 temperature: float = 0.5, generator: Optional[torch.Generator] = None) -> List[List[int]]:
+        """DecodeEngine.generate for up to `batch` prompts at once, each in its own slot: prompt i's list is what DecodeEngine.generate
+        returns for it alone (context + new tokens).  Per step the next tokens are chosen on the device (argmax, or multinomial of
+        softmax(logits / temperature) per row); the host reads the B token ids.  A sequence stops at its own EOS, after max_new_tokens
+        or at the cache end, and its slot is released."""
+        n = len(prompts)
+        if not 0 < n <= self.batch:
+            raise ValueError(f"BatchDecodeEngine.generate: {n} prompts for {self.batch} slots")
+        prompts = [[int(t) for t in p] for p in prompts]
+        assert all(len(p) > 0 for p in prompts)
+        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        if max_new_tokens <= 0:
+            return prompts
+        for b in range(self.batch):
+            self.release(b)
+        # one-token prompts go through the step kernels (as DecodeEngine.generate), alone; longer ones through the prefill forward
+        short = [i for i, p in enumerate(prompts) if len(p) == 1]
+        if short:
+            for i in short:
+                self.start(i)
+            self.step([prompts[i][0] if i in short else 0 for i in range(self.batch)])
+        for i, p in enumerate(prompts):
+            if len(p) > 1:
+                self.prefill(i, p)
+        outs = [list(p) for p in prompts]
+        made = [0] * n
+        live = list(range(n))
+        while live:
+            if do_sample:
+                probs = torch.softmax(self.logits / temperature, dim=-1)
+                self.tok.copy_(torch.multinomial(probs, num_samples=1, generator=generator).view(-1))
+            else:
+                torch.argmax(self.logits, dim=-1, out=self.tok)
+            nxt = self.tok.tolist()
+            for i in list(live):
+                outs[i].append(nxt[i])
+                made[i] += 1
+                if nxt[i] in eos or made[i] >= max_new_tokens or self._host_pos[i] >= self.cache_len:
+                    self.release(i)
+                    live.remove(i)
+            if live:
+                self.step()
+        return outs
