@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 302 /* 0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 303 /* 0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -729,6 +729,18 @@ int mq_calib_rope(const float* q_in, const float* k_in, float* q_out, float* k_o
  * v_in and (v_out: both NULL or both given -- v_out holds v_in's values).  */
 int mq_calib_rope_qkv(const float* q_in, const float* k_in, const float* v_in, float* q_out, float* k_out, float* v_out, int64_t batch, int64_t seq, int heads,
                       int kv_heads, int head_dim, int rot_dim, const float* cos, const float* sin, float* const* stats, mq_stream_t stream);
+
+/* ---- token scoring: the fp32 lm_head fused with its log-softmax ----------------------------------------------- */
+/* Per row m of y [M][y_stride] (the final norm's output, K used columns) against the lm_head W [V][K] (nn.Linear layout) and an optional
+ * bias [V]: lse[m] = log sum_v exp(l_mv), logprob[m] = l_m,t - lse[m] for t = targets[m] (targets NULL, or t outside [0, V): logprob 0),
+ * argmax[m] = the lowest index among the maximal logits (NaN ranks highest: torch.argmax's rule).  l_mv = sum_k y_mk w_vk (+ b_v) in
+ * fp32 MFMA; the logits are never written to memory: per 128-entry vocabulary tile a row is reduced to (max, sum exp, first argmax) in
+ * `scratch` (>= mq_score_head_scratch_bytes(M, V) bytes, 256-byte aligned, owned by the caller for the duration of the call on
+ * `stream`), and a second launch merges the tiles in a fixed order -- no atomics: bit-reproducible, and every row's result depends on
+ * that row alone.  Error bound: csrc/mq_score.hip's header.  K % 4 == 0, y_stride % 4 == 0, y and w 16-byte aligned; M = 0 is a no-op. */
+int64_t mq_score_head_scratch_bytes(int64_t M, int64_t V);
+int mq_score_head(const float* y, int64_t y_stride, const float* w, const float* bias, const int64_t* targets, int64_t M, int64_t K,
+                  int64_t V, void* scratch, int64_t scratch_bytes, float* logprob, float* lse, int64_t* argmax, mq_stream_t stream);
 
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes

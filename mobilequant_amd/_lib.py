@@ -156,6 +156,8 @@ _SIGNATURES = {
     "mq_decode_attention_batch": (c_int, [POINTER(MqDecodeAttentionBatchArgs), _P]),
     "mq_decode_head_batch": (c_int, [POINTER(MqDecodeHeadBatchArgs), _P]),
     "mq_attention_quant": (c_int, [POINTER(MqAttentionArgs), _P]),
+    "mq_score_head_scratch_bytes": (c_int64, [c_int64, c_int64]),
+    "mq_score_head": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

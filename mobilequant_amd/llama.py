@@ -591,6 +591,31 @@ class LlamaForCausalLM(nn.Module):
         """ids [B, S] token ids.  cache: list (one per layer) of (k, v) static buffers [B, KV, T, D], see Attention.forward.
         last_logits_only: final norm + lm_head on the LAST position only (logits [B, 1, vocab]) -- a context encoding that feeds
         generation needs no other row, and at TinyLlama's size the fp32 lm_head over 2 048 positions is 2.6 of the forward's 6.8 ms."""
+        x, pend = self._trunk(ids, cache, pos)
+        if pend is not None:
+            calib = self.__dict__.get("_mq_calib_layer")            # (collector, ("norm",)): the final norm takes the last add like a layer's
+            if (calib is not None and calib[0] is pend[2] and not last_logits_only and calib[0].can_fuse_layer(x)
+                    and calib[0].norm_is_plain(self.norm)):
+                _, y = calib[0].norm_pass(calib[1][0], self.norm, x, pend[0], pend[1])
+                return self.lm_head(y)
+            pend[2]._update(pend[1][0], pend[1][1], pend[0])
+            x = x + pend[0]
+        if last_logits_only:
+            from .quantization import qmodule as Q
+            x = Q._materialize(x)[:, -1:].contiguous()
+        return self.lm_head(self.norm(x))
+
+    def hidden_states(self, ids, cache=None, pos: int = 0):
+        """The residual stream after the last decoder layer, in front of the final norm ([B, S, hidden]): forward() without its
+        norm and lm_head (scoring.token_logprobs runs the head itself)."""
+        x, pend = self._trunk(ids, cache, pos)
+        if pend is not None:
+            pend[2]._update(pend[1][0], pend[1][1], pend[0])
+            x = x + pend[0]
+        return x
+
+    def _trunk(self, ids, cache=None, pos: int = 0):
+        """Embedding and decoder layers: (x, pend) -- pend is a calibration pass's deferred last residual add (None otherwise)."""
         B, S = ids.shape
         x = self.embed_tokens(ids)
         if self.shape.embed_scale:
@@ -612,18 +637,7 @@ class LlamaForCausalLM(nn.Module):
                     pend[2]._update(pend[1][0], pend[1][1], pend[0])
                     x, pend = x + pend[0], None
                 x = layer(x, cos, sin, mask, c, pos)
-        if pend is not None:
-            calib = self.__dict__.get("_mq_calib_layer")            # (collector, ("norm",)): the final norm takes the last add like a layer's
-            if (calib is not None and calib[0] is pend[2] and not last_logits_only and calib[0].can_fuse_layer(x)
-                    and calib[0].norm_is_plain(self.norm)):
-                _, y = calib[0].norm_pass(calib[1][0], self.norm, x, pend[0], pend[1])
-                return self.lm_head(y)
-            pend[2]._update(pend[1][0], pend[1][1], pend[0])
-            x = x + pend[0]
-        if last_logits_only:
-            from .quantization import qmodule as Q
-            x = Q._materialize(x)[:, -1:].contiguous()
-        return self.lm_head(self.norm(x))
+        return x, pend
 
     def new_image_cache(self, batch: int, length: int, device=None):
         """Cache for CHUNKED prefill through the fused attention (llama.fuse_attention / fuse_decoder_layer): per layer and sequence the

@@ -972,3 +972,49 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     if out is None:
         return None
     return out if S_real == S else out[..., :S_real, :].contiguous()
+
+
+# ---- token scoring: the fp32 lm_head fused with its log-softmax ------------------------------------------------------------------
+def score_head(y: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], targets: Optional[torch.Tensor]):
+    """Per row of y [M, K] (fp32, unit column stride): (logprob [M] fp32, lse [M] fp32, argmax [M] int64) of the logits
+    y @ weight.T (+ bias) without writing them (mq_score_head).  weight [V, K] fp32 is nn.Linear's layout.  targets [M] int64: a
+    row's target index, < 0 = ignored (logprob 0); every target must be < V (checked here, on the host)."""
+    _dev(y, "score_head y")
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise RuntimeError("mobilequant_amd: score_head y must be fp32 [M, K]")
+    M, K = y.shape
+    if y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:
+        y = y.contiguous()
+    w = _f32(weight, "score_head weight")
+    V = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != K:
+        raise RuntimeError(f"mobilequant_amd: score_head weight must be [V, {K}], got {tuple(w.shape)}")
+    if K % 4:
+        raise RuntimeError(f"mobilequant_amd: score_head needs K % 4 == 0 (K = {K})")
+    b = None
+    if bias is not None:
+        b = _f32(bias, "score_head bias")
+        if b.shape != (V,):
+            raise RuntimeError(f"mobilequant_amd: score_head bias must be [{V}]")
+    t = None
+    if targets is not None:
+        _dev(targets, "score_head targets")
+        if targets.shape != (M,):
+            raise RuntimeError(f"mobilequant_amd: score_head targets must be [{M}]")
+        t = targets.to(torch.int64).contiguous()
+        if M and int(t.max()) >= V:
+            raise RuntimeError(f"mobilequant_amd: score_head target {int(t.max())} outside the vocabulary [0, {V})")
+    dev = y.device
+    logprob = torch.empty(M, dtype=torch.float32, device=dev)
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    amax = torch.empty(M, dtype=torch.int64, device=dev)
+    if M == 0:
+        return logprob, lse, amax
+    lib = _lib.load()
+    nbytes = int(lib.mq_score_head_scratch_bytes(M, V))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # the caching allocator hands out 512-byte aligned blocks
+    with _on(y, w, b, t):
+        _lib.call("mq_score_head", y.data_ptr(), y.stride(0), w.data_ptr(), b.data_ptr() if b is not None else None,
+                  t.data_ptr() if t is not None else None, M, K, V, scratch.data_ptr(), nbytes, logprob.data_ptr(), lse.data_ptr(),
+                  amax.data_ptr(), _stream())
+    return logprob, lse, amax
