@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + the last timed step's output as DIR/qlinear_out.npy
+    python bench.py --gpus N --steps K --warmup W --full                # + every other leg below (minutes, not seconds)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,15 +12,18 @@ One STEP = one pass of the hot path over one batch of synthetic activations alre
     8-bit output quantizer)-->  output indices [2048, 5632]                     (BASELINE.json configs[1])
 metric = 2*M*K*N int8 ops per step / step time, summed over ranks (replicas: the quantized forward has no
 exchange step -- DESIGN.md "Multi-GPU"; the data-parallel calibration path with its single all-reduce is
-exercised by `--workload calibration`).
+exercised by `--workload calibration` and by the calibration legs of `--full`).
 
-The JSON line also carries
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line
+(`roofline`, `cpu_baseline` and `decode` are null there, `variants` is empty).  With --full the JSON line also carries
   roofline     : the dominant kernel (the int8 GEMM) against the dense int8 MFMA peak, from HIP-event timing
                  of that kernel alone on the stream it is launched on;
   cpu_baseline : the torch-CPU restatement of the reference's simulated QLinear (oracle/mq_oracle_torch.py, "port": the
                  reference's op sequence on torch CPU kernels, bit-checked against the numpy oracle) timed on this box's
                  physical host cores on the same shape -- a reported baseline, not a target;
-  variants     : the same step with fp16 / fp32 outputs, and the drop-in nn.Module forward (fp32 in/out).
+  decode       : the full decode step of three model families (decode_block);
+  variants     : the data-parallel calibration legs, BASELINE.json configs[2] / [3] GEMMs; with --variants also the same
+                 step with fp16 / fp32 outputs, the drop-in nn.Module forward (fp32 in/out) and the legs of bench_variants.py.
 """
 from __future__ import annotations
 
@@ -55,11 +59,15 @@ def parse():
     p.add_argument("--calib-stub-gemm", action="store_true",
                    help="--workload calibration: every Linear / FMatMul returns a resident tensor of its output shape instead of running the "
                         "fp32 library GEMM, so the timed region is the hot path (hooked reductions + the collective), not rocBLAS")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beyond the headline: roofline leg, calibration legs, full decode step, configs[2] / [3] "
+                        "GEMMs, CPU baseline (minutes, not seconds); without it a run sets up, warms up, times the steps and prints")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-graph", action="store_true")
-    p.add_argument("--headline-only", action="store_true", help="only the timed steps and the roofline leg (profiler passes)")
+    p.add_argument("--headline-only", action="store_true",
+                   help="only the timed steps and the roofline leg (profiler passes); implies --full")
     p.add_argument("--variants", action="store_true", help="also run the non-headline legs (bench_variants.py: layers at prefill, training step, "
-                                                           "model prefill, ...): minutes, not seconds")
+                                                           "model prefill, ...): minutes, not seconds; implies --full")
     p.add_argument("--row-major-activations", action="store_true",
                    help="A/B: quantise row-major and run the C++ ping-pong GEMM loop instead of the fragment-blocked layout")
     p.add_argument("--overlap", action="store_true",
@@ -71,6 +79,7 @@ def parse():
     args = p.parse_args()
     if args.steps < 1:
         p.error("--steps must be at least 1")
+    args.full = args.full or args.headline_only or args.variants       # both choose among the legs of --full
     return args
 
 
@@ -689,9 +698,16 @@ def bench_calibration(args, rank, world, dev):
         rows = [np.asarray(r["act"][m][f], dtype=np.float32).reshape(2, -1) for m, f in keys]
         dump_outputs(args.dump_outputs, {"act_range_min": np.concatenate([x[0] for x in rows]),
                                          "act_range_max": np.concatenate([x[1] for x in rows])})
-    mm = bench_minmax(dev, args.calib_seq)
-    cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    cpu = roof = None
+    key = "minmax_cols" if args.per_channel else "minmax_tensor"
+    if args.full:
+        mm = bench_minmax(dev, args.calib_seq)
+        big = mm["qk_bmm.output [1,32,S,S]"]
+        achieved = big["bytes"] / (big[key + "_us"] * 1e-6) / 1e9
+        roof = {"bound": "hbm", "kernel": f"mq::{key}_kernel on the [32*S, S] attention scores (the largest hooked tensor)",
+                "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4),
+                "algorithmic_bytes_per_launch": big["bytes"], "traffic": None, "per_tensor_shapes": mm}
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # the oracle's running min / max (oracle/mq_oracle.py: compute_min_max_from_tensor + update_act_range) over a bounded sample of
         # the hooked bytes; samples/s = rate / hooked bytes per sample
         from oracle import mq_oracle as O
@@ -706,9 +722,6 @@ def bench_calibration(args, rank, world, dev):
                "GBps": round(rate / 1e9, 2),
                "sample": f"{n} ActRangeOracle.update calls (oracle/mq_oracle.py, numpy) over a [{4 * args.calib_seq}, {args.calib_seq}] fp32 tensor (~10 s); "
                          "samples/s = bytes/s / hooked bytes per sample (reductions only, no model forward)"}
-    big = mm["qk_bmm.output [1,32,S,S]"]
-    key = "minmax_cols" if args.per_channel else "minmax_tensor"
-    achieved = big["bytes"] / (big[key + "_us"] * 1e-6) / 1e9
     info = None
     try:
         import mobilequant_amd._lib as L
@@ -726,9 +739,7 @@ def bench_calibration(args, rank, world, dev):
                                + " running [min, max], round-robin shards", "parallelism": f"dp{world}", "collectives": r["collectives"],
                    "tensors_tracked": r["tensors"], "device": info,
                    "gemms": "stubbed (resident output tensors; --calib-stub-gemm)" if args.calib_stub_gemm else "fp32 library GEMMs (rocBLAS)"},
-        "roofline": {"bound": "hbm", "kernel": f"mq::{key}_kernel on the [32*S, S] attention scores (the largest hooked tensor)",
-                     "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4),
-                     "algorithmic_bytes_per_launch": big["bytes"], "traffic": None, "per_tensor_shapes": mm},
+        "roofline": roof,
         "breakdown": {"hooked_bytes_per_sample": int(r["hooked_bytes_per_sample"]),
                       "model_ms_per_sample (fp32 library GEMMs, softmax: not the hot path)": round(1e3 * r["model_seconds_per_sample"], 3),
                       "reduction_ms_per_sample": round(1e3 * r["reduction_seconds_per_sample"], 3),
@@ -771,9 +782,10 @@ def main():
 
         extras = {}
         roof = cpu = decode = None
+        # everything below is --full only: a plain run prints the headline right after the timed steps
         # the data-parallel half of the hot path, bounded: 8 samples per rank through 2 TinyLlama-shaped layers + the single
-        # all-reduce -- so every multi-GPU run of this file also drives the RCCL path (full configs[4]: --workload calibration)
-        if not args.headline_only:
+        # all-reduce -- so every multi-GPU --full run of this file also drives the RCCL path (full configs[4]: --workload calibration)
+        if args.full and not args.headline_only:
             cal = calibration_run(dev, rank, world, layers=2, n_samples=8 * world, seq=2048, per_channel=False)
             extras["calibration_dp"] = {"samples_per_s": round(cal["samples_per_s"], 2), "n_gpus": world, "samples": 8 * world, "layers": 2,
                                         "seq": 2048, "collectives": cal["collectives"], "scaling": "weak (8 samples per rank)"}
@@ -790,7 +802,7 @@ def main():
                 "reduction_ms_per_sample": round(1e3 * cal["reduction_seconds_per_sample"], 3),
                 "reduction_GBps_per_gpu": round(cal["hooked_bytes_per_sample"] / max(cal["reduction_seconds_per_sample"], 1e-9) / 1e9, 1)}
             torch.cuda.empty_cache()
-        if rank == 0:
+        if args.full and rank == 0:
             # dominant kernel alone, HIP events on its stream
             t_gemm = event_time(step.gemm, 50)
             t_quant = event_time(lambda: step.quantize(0), 50)

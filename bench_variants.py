@@ -3,10 +3,10 @@
 busy): module forward, FFN pair GEMM, whole decoder layers at prefill (three families, W8 / W4), one e2equant training step, the 22-layer
 model prefill, the calibration reductions, linears-only decode, BASELINE.json configs[2] / [3] GEMMs.
 
-    python bench_variants.py [bench.py flags]      ==      python bench.py --variants [flags]
+    python bench_variants.py [bench.py flags]      ==      python bench.py --variants [flags]      (--variants implies --full)
 
-prints bench.py's JSON line with every leg inside `variants`.  bench.py itself imports bench_other_configs from here (configs[2] / [3]
-belong to the headline line); the rest runs only on request.  Shared helpers (Step, event_time, calibration_run, ...) live in bench.py."""
+prints bench.py's JSON line with every leg inside `variants`.  bench.py --full imports bench_other_configs from here (configs[2] / [3]
+belong to the --full line); the rest runs only on request.  Shared helpers (Step, event_time, calibration_run, ...) live in bench.py."""
 from __future__ import annotations
 
 import os

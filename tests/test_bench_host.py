@@ -69,6 +69,14 @@ def test_dump_outputs_flag_and_steps_bound(monkeypatch):
         b.parse()
 
 
+def test_full_flag_is_off_by_default_and_implied_by_the_legs_it_holds(monkeypatch):
+    b = _bench()
+    for argv, full in ((["--steps", "20", "--warmup", "5"], False), (["--full"], True), (["--headline-only"], True), (["--variants"], True),
+                       (["--workload", "calibration"], False), (["--workload", "calibration", "--full"], True)):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        assert b.parse().full is full, argv
+
+
 def test_dump_outputs_writes_float_npy_within_the_size_limit(tmp_path):
     b = _bench()
     y = np.arange(12, dtype=np.float32).reshape(3, 4)

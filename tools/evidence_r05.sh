@@ -6,8 +6,8 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/evidence_r05; mkdir -p $OUT; cd $R
 timeout 1800 python -m pytest tests -m gpu -q > $OUT/gpu_tests_full.log 2>&1; grep -E "passed|failed" $OUT/gpu_tests_full.log > $OUT/gpu_tests.log; cat $OUT/gpu_tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 # 2. the bench line at the driver's settings and at 10 x the steps
-timeout 1500 python bench.py --steps 20 --warmup 5 2> $OUT/bench_final.err | grep '^{"metric"' > $OUT/bench_final.json
-timeout 600 python bench.py --steps 200 --warmup 20 --headline-only --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $OUT/bench_steps200.json
+timeout 1500 python bench.py --steps 20 --warmup 5 --full 2> $OUT/bench_final.err | grep '^{"metric"' > $OUT/bench_final.json
+timeout 600 python bench.py --steps 200 --warmup 20 --full --headline-only --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $OUT/bench_steps200.json
 python - <<'PY'
 import json, os
 o = os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out", "evidence_r05")

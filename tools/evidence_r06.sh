@@ -2,7 +2,7 @@
 # Regenerates the round-6 evidence under gpurun_out/evidence_r06/ on an MI355X (run through gpurun; ~12 min).  profiles/r06/ keeps copies.
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/evidence_r06; mkdir -p $OUT; cd $R
 # 1. the bench line at the driver's settings (headline + decode + configs[2] / [3] + cpu baseline; the other legs: bench_variants.py)
-T0=$(date +%s); timeout 1200 python bench.py --steps 20 --warmup 5 2> $OUT/bench_final.err | grep '^{"metric"' > $OUT/bench_final.json; echo "bench.py wall $(( $(date +%s) - T0 )) s" | tee $OUT/bench_wall.log
+T0=$(date +%s); timeout 1200 python bench.py --steps 20 --warmup 5 --full 2> $OUT/bench_final.err | grep '^{"metric"' > $OUT/bench_final.json; echo "bench.py wall $(( $(date +%s) - T0 )) s" | tee $OUT/bench_wall.log
 python - <<'PY'
 import json, os
 o = os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out", "evidence_r06")

@@ -3,10 +3,10 @@
 # databases are tens of MB).  usage: prof_bench.sh <tag> [pmc]     (run through gpurun)
 TAG=${1:-r04}; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof_bench_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline"
+CMD="python $R/bench.py --steps 100 --warmup 10 --full --no-cpu-baseline"
 # PMC passes profile the headline legs only (timed steps + the GEMM / quantize kernels alone): counter collection over the
 # whole variant suite (library GEMMs of the calibration leg, graph replays of the decode engine) crashed rocprofv3 on this pool
-PMC_CMD="python $R/bench.py --steps 100 --warmup 10 --headline-only"
+PMC_CMD="python $R/bench.py --steps 100 --warmup 10 --full --headline-only"
 pass() {  # name, rocprofv3 args...
   local name=$1; shift
   local cmd=$CMD; case $name in pmc_*) cmd=$PMC_CMD;; esac

@@ -8,7 +8,7 @@ timeout 900 python tools/stable_depth_diag.py 2>&1 | grep -v amdgpu.ids > $OUT/s
 hipcc --offload-arch=gfx950 -O3 tools/mfma_energy_probe.cpp -o /tmp/mfma_energy_probe 2> $OUT/probe_build.log && timeout 300 /tmp/mfma_energy_probe 256 200 > $OUT/mfma_energy_probe.log 2>&1 && timeout 120 /tmp/mfma_energy_probe 32 400 > $OUT/mfma_energy_probe_k32.log 2>&1
 grep "4 waves\|W from LDS gauss" $OUT/mfma_energy_probe.log $OUT/mfma_energy_probe_k32.log
 for mode in "" "--calib-stub-gemm"; do
-  timeout 600 python bench.py --workload calibration --calib-samples 64 $mode 2>/dev/null | grep '^{"metric"' > $OUT/calibration64$mode.json
+  timeout 600 python bench.py --workload calibration --calib-samples 64 --full $mode 2>/dev/null | grep '^{"metric"' > $OUT/calibration64$mode.json
   python -c "
 import json,sys
 d=json.load(open('$OUT/calibration64$mode.json')); print('calibration $mode', d['value'], 'samples/s', d['breakdown'])"
