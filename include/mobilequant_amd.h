@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 303 /* 0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4: + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -582,6 +582,25 @@ typedef struct mq_decode_head_batch_args {
   int cache_len;
 } mq_decode_head_batch_args;
 int mq_decode_head_batch(const mq_decode_head_batch_args* args, mq_stream_t stream);
+
+/* mq_decode_gemv_batch with PER-GROUP weight grids (QuantConfig group_size; the recipe of mq_w8a8_linear_grouped) for 1 ..
+ * MQ_DECODE_MAX_BATCH rows.  b is the batched launch's argument block, read as for mq_decode_gemv_batch (prologues, strides,
+ * consts, output grids, gate, residual) except that b.g.alpha / w_zp / col_term are not used: the contraction takes the [G, N]
+ * group vectors below (G = K / group_size, group-major; gate mode: columns 2i / 2i+1 = w1 / w3 row i, as the rows of b.g.w).
+ * Per row and output n, with the stored image bytes a' = ia - 128 and the stored weights w' (index - 128 for int8 rows; the unsigned
+ * nibble for packed 4-bit rows, b.g.w4 = 1), every group's bracket P_g + cw[g, n] A_g + t[g, n] (P_g = sum a' w', A_g = sum a' over
+ * the group) is an exact int32, folded in ascending g as acc = fmaf((float)bracket, alpha[g, n], acc) from acc = 0, then acc +
+ * bias[n] (bias nullable): the value in front of the output grid equals mq_w8a8_linear_grouped's on the same image, bit for bit.
+ * group_size: a power of two >= 64 dividing K (others: MQ_EUNSUPPORTED); batch * K <= 131072 (MQ_EINVAL).  alpha / cw / t
+ * 16-byte aligned. */
+typedef struct mq_decode_gemv_grouped_args {
+  mq_decode_gemv_batch_args b;
+  int group_size;
+  const float* alpha;  /* [G, N] s_a * s_w[n, g] */
+  const int32_t* cw;   /* [G, N] sh_w - o_w[n, g] (sh_w: the weight storage shift) */
+  const int32_t* t;    /* [G, N] c_a W_g[n] + group_size c_a cw[g, n], c_a = 128 - z_a, W_g = sum of the group's stored weights */
+} mq_decode_gemv_grouped_args;
+int mq_decode_gemv_grouped(const mq_decode_gemv_grouped_args* args, mq_stream_t stream);
 
 /* ---- a10: quantized causal attention at prefill (hf_model.py:486-534 with the two QMatMuls of qmodule.py:453-466) ------------ */
 /* One sequence.  q [seq, heads*D], k / v [seq, kv_heads*D] fp32 = the q / k / v projection outputs BEFORE RoPE; cos / sin [seq, D]

@@ -63,6 +63,10 @@ class MqDecodeGemvBatchArgs(ctypes.Structure):
     _fields_ = [("g", MqDecodeGemvArgs), ("batch", c_int), ("x_stride", c_int64), ("y_stride", c_int64), ("gate_stride", c_int64)]
 
 
+class MqDecodeGemvGroupedArgs(ctypes.Structure):
+    _fields_ = [("b", MqDecodeGemvBatchArgs), ("group_size", c_int), ("alpha", c_void_p), ("cw", c_void_p), ("t", c_void_p)]
+
+
 class MqDecodeAttentionBatchArgs(ctypes.Structure):
     _fields_ = [("a", MqDecodeAttentionArgs), ("batch", c_int), ("split_from", c_int), ("qkv_stride", c_int64)]
 
@@ -154,6 +158,7 @@ _SIGNATURES = {
     "mq_decode_head": (c_int, [_P, _P, _P, c_int, c_float, _P, _P, c_int64, c_int64, _P, _P]),
     "mq_decode_gemv_batch": (c_int, [POINTER(MqDecodeGemvBatchArgs), _P]),
     "mq_decode_attention_batch": (c_int, [POINTER(MqDecodeAttentionBatchArgs), _P]),
+    "mq_decode_gemv_grouped": (c_int, [POINTER(MqDecodeGemvGroupedArgs), _P]),
     "mq_decode_head_batch": (c_int, [POINTER(MqDecodeHeadBatchArgs), _P]),
     "mq_attention_quant": (c_int, [POINTER(MqAttentionArgs), _P]),
     "mq_score_head_scratch_bytes": (c_int64, [c_int64, c_int64]),

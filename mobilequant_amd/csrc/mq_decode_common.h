@@ -1,5 +1,6 @@
-// Device helpers shared by the single-sequence decode kernels (mq_decode.hip) and the batched ones (mq_decode_batch.hip): quantizer
-// arithmetic, DPP wave reductions, the launch-constants line and the layout constants both families agree on.
+// Device helpers shared by the single-sequence decode kernels (mq_decode.hip), the batched ones (mq_decode_batch.hip) and the grouped
+// GEMV (mq_decode_grouped.hip): quantizer arithmetic, DPP wave reductions, the launch-constants line, the layout constants the
+// families agree on and the batched GEMV's prologue and epilogue.
 #pragma once
 #include "mq_common.h"
 
@@ -121,6 +122,308 @@ __device__ __forceinline__ int quad_sum(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);                 // quad_perm [1,0,3,2]
   if (N == 4) v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);     // quad_perm [2,3,0,1]
   return v;
+}
+
+// ---- the five-launch GEMV over B activation rows: pieces shared by decode_gemv_batch_kernel (mq_decode_batch.hip) and
+// decode_gemv_grouped_kernel (mq_decode_grouped.hip), which differ only in how a weight row is contracted with the images ----------
+constexpr int DB_MAXB = MQ_DECODE_MAX_BATCH;
+constexpr int DB_XH = 1;             // float4 per row and thread the prologue holds between its passes (K <= 2048); beyond that it re-reads
+
+// PROLOGUE role (waves 0 .. DG_PRO-1): the B rows' int8 images (index - 128) into smem [B][K] and the per-wave partials of their
+// image sums into s_redi[b][wave].  Per row b the prologue is thread p's walk over float4 p + 512 u, the per-thread partial in that
+// order, wave_sum_f, then the DG_PRO wave partials added in wave order -- decode_gemv_kernel's arithmetic (mq_decode.hip); the rows'
+// chains interleave, the barriers are shared (the STREAM waves mirror them with gemv_batch_stream_barriers).  Beyond DB_XH float4 per
+// row the prologue re-reads x (and the norm weights) instead of holding them: the same values, so the same bits.  Ends on the
+// barrier after which the images and the sums are complete.
+template <int XMODE, int NB>
+__device__ __forceinline__ void gemv_batch_prologue(const mq_decode_gemv_batch_args& ba, char* smem, float (*s_red)[DG_PRO], float (*s_red2)[DG_PRO],
+                                                    int (*s_redi)[DG_PRO], const float cv, const int lane, const int wave) {
+  const mq_decode_gemv_args& g = ba.g;
+  const int B = ba.batch;
+  const int K = g.K;
+  const int p = threadIdx.x;                                     // 0 .. 511
+  int my_sum[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) my_sum[b] = 0;
+  if constexpr (XMODE == XM_I8) {                                // ready int8 images: copy + row sums
+    const int nq = K >> 4;
+    for (int i = p; i < nq; i += DG_PRO * 64) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if (b < B) {
+          const v4i v = reinterpret_cast<const v4i*>(g.xq + (size_t)b * ba.x_stride)[i];
+          reinterpret_cast<v4i*>(smem + (size_t)b * K)[i] = v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) my_sum[b] = __builtin_amdgcn_sdot4(v[e], 0x01010101, my_sum[b], false);
+        }
+      }
+    }
+  } else {
+    const int nvec = K >> 2;
+    constexpr bool ANYNORM = XMODE == XM_NORM || XMODE == XM_LNORM;
+    const Grid ag = const_grid(cv, CG_A, g.a_grid);
+    const Grid ng = const_grid(cv, CG_NORM_IN, g.norm_in);
+    float4 xv[NB][DB_XH], nw[DB_XH], nb[DB_XH];
+    auto xrow = [&](int b, int ic) { return reinterpret_cast<const float4*>(g.x + (size_t)b * ba.x_stride)[ic]; };
+    auto fqv = [&](float4 v) {                                   // the norm's input quantizer, two elements per instruction
+      const v2f lo2 = ng.fq2((v2f){v.x, v.y}), hi2 = ng.fq2((v2f){v.z, v.w});
+      return make_float4(lo2.x, lo2.y, hi2.x, hi2.y);
+    };
+#pragma unroll
+    for (int u = 0; u < DB_XH; ++u) {
+      if (u * DG_PRO * 64 < nvec) {                              // wave-uniform
+        const int i = p + u * DG_PRO * 64;
+        const int ic = i < nvec ? i : nvec - 1;
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+          if (b < B) xv[b][u] = xrow(b, ic);
+        if constexpr (ANYNORM) nw[u] = reinterpret_cast<const float4*>(g.norm_w)[ic];
+        if constexpr (XMODE == XM_LNORM)
+          nb[u] = g.norm_bias ? reinterpret_cast<const float4*>(g.norm_bias)[ic] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    // row b's (normalised-input) float4 u: held, or re-read and re-quantised (fq: the norm modes' input quantizer applied)
+    auto xval = [&](int b, int u, int ic, bool fq) {
+      if (u < DB_XH) return xv[b][u < DB_XH ? u : 0];
+      const float4 v = xrow(b, ic);
+      return fq ? fqv(v) : v;
+    };
+    float r[NB], shiftv[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) r[b] = 1.f, shiftv[b] = 0.f;
+    if constexpr (XMODE == XM_LNORM) {                           // QLayerNorm.forward, decode_gemv_kernel's arithmetic
+      float s1[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) s1[b] = 0.f;
+#pragma unroll
+      for (int u = 0; u < DG_XPRE; ++u) {
+        if (u * DG_PRO * 64 < nvec) {
+          const int i = p + u * DG_PRO * 64, ic = i < nvec ? i : nvec - 1;
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            if (b < B) {
+              float4 v;
+              if (u < DB_XH) v = xv[b][u < DB_XH ? u : 0] = fqv(xv[b][u < DB_XH ? u : 0]);
+              else v = fqv(xrow(b, ic));
+              if (i < nvec) s1[b] += (v.x + v.y) + (v.z + v.w);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if (b < B) {
+          const float t = wave_sum_f(s1[b]);
+          if (lane == 0) s_red[b][wave] = t;
+        }
+      }
+      __syncthreads();                                           // barrier 1 of 3
+      float mu[NB], s2[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float tot = 0.f;
+#pragma unroll
+        for (int w = 0; w < DG_PRO; ++w) tot += s_red[b][w];
+        mu[b] = __fdiv_rn(tot, (float)K);
+        s2[b] = 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < DG_XPRE; ++u) {
+        if (u * DG_PRO * 64 < nvec && p + u * DG_PRO * 64 < nvec) {
+          const int ic = p + u * DG_PRO * 64;
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            if (b < B) {
+              const float4 v = xval(b, u, ic, true);
+              const float d0 = v.x - mu[b], d1 = v.y - mu[b], d2 = v.z - mu[b], d3 = v.w - mu[b];
+              s2[b] += d0 * d0;
+              s2[b] += d1 * d1;
+              s2[b] += d2 * d2;
+              s2[b] += d3 * d3;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if (b < B) {
+          const float t = wave_sum_f(s2[b]);
+          if (lane == 0) s_red2[b][wave] = t;
+        }
+      }
+      __syncthreads();                                           // barrier 2 of 3
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float tot2 = 0.f;
+#pragma unroll
+        for (int w = 0; w < DG_PRO; ++w) tot2 += s_red2[b][w];
+        const float var = __fdiv_rn(tot2, (float)K);
+        r[b] = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, g.eps)));
+        shiftv[b] = __fmul_rn(-r[b], mu[b]);
+      }
+    }
+    if constexpr (XMODE == XM_NORM) {                            // QRMSNorm.forward, decode_gemv_kernel's arithmetic
+      float ss[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) ss[b] = 0.f;
+#pragma unroll
+      for (int u = 0; u < DG_XPRE; ++u) {
+        if (u * DG_PRO * 64 < nvec) {
+          const int i = p + u * DG_PRO * 64, ic = i < nvec ? i : nvec - 1;
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            if (b < B) {
+              float4 v;
+              if (u < DB_XH) v = xv[b][u < DB_XH ? u : 0] = fqv(xv[b][u < DB_XH ? u : 0]);
+              else v = fqv(xrow(b, ic));
+              if (i < nvec) {
+                const v2f lo2 = (v2f){v.x, v.y}, hi2 = (v2f){v.z, v.w};
+                const v2f sl = lo2 * lo2, sh = hi2 * hi2;
+                ss[b] += sl.x;
+                ss[b] += sl.y;
+                ss[b] += sh.x;
+                ss[b] += sh.y;
+              }
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if (b < B) {
+          const float t = wave_sum_f(ss[b]);
+          if (lane == 0) s_red[b][wave] = t;
+        }
+      }
+      __syncthreads();                                           // barrier 1 of 2
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float tot = 0.f;
+#pragma unroll
+        for (int w = 0; w < DG_PRO; ++w) tot += s_red[b][w];
+        const float mean = __fdiv_rn(tot, (float)K);
+        r[b] = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(mean, g.eps)));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < DG_XPRE; ++u) {
+      if (u * DG_PRO * 64 < nvec) {
+        const int i = p + u * DG_PRO * 64, ic = i < nvec ? i : nvec - 1;
+        float4 w = make_float4(0.f, 0.f, 0.f, 0.f), bb = w;
+        if constexpr (ANYNORM) w = u < DB_XH ? nw[u < DB_XH ? u : 0] : reinterpret_cast<const float4*>(g.norm_w)[ic];
+        if constexpr (XMODE == XM_LNORM)
+          bb = u < DB_XH ? nb[u < DB_XH ? u : 0] : (g.norm_bias ? reinterpret_cast<const float4*>(g.norm_bias)[ic] : make_float4(0.f, 0.f, 0.f, 0.f));
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          if (b < B) {
+            float4 v = xval(b, u, ic, ANYNORM);
+            if constexpr (XMODE == XM_NORM) {
+              const v2f a2 = (v2f){w.x, w.y} * ((v2f){v.x, v.y} * splat2(r[b])), b2 = (v2f){w.z, w.w} * ((v2f){v.z, v.w} * splat2(r[b]));
+              v = make_float4(a2.x, a2.y, b2.x, b2.y);
+            }
+            if constexpr (XMODE == XM_LNORM) {
+              v.x = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.x, r[b]), shiftv[b]), w.x), bb.x);
+              v.y = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.y, r[b]), shiftv[b]), w.y), bb.y);
+              v.z = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.z, r[b]), shiftv[b]), w.z), bb.z);
+              v.w = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(v.w, r[b]), shiftv[b]), w.w), bb.w);
+            }
+            const v2f u01 = image_u8f2((v2f){v.x, v.y}, ag.s, ag.inv_s, ag.o, ag.qmin, ag.qmax, 0.f);
+            const v2f u23 = image_u8f2((v2f){v.z, v.w}, ag.s, ag.inv_s, ag.o, ag.qmin, ag.qmax, 0.f);
+            uint32_t usum = 0;
+            const uint32_t pk = image_pack4(u01.x, u01.y, u23.x, u23.y, usum);
+            if (i < nvec) {
+              my_sum[b] += (int)usum - 512;
+              reinterpret_cast<unsigned*>(smem + (size_t)b * K)[i] = pk;
+            }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    if (b < B) {
+      const int part = wave_sum_dpp(my_sum[b]);
+      if (lane == 0) s_redi[b][wave] = part;
+    }
+  }
+  __syncthreads();                                               // the images and the row sums are complete
+}
+
+// the STREAM waves' side of the prologue's barriers: the norm reductions, then the one after which the images are complete
+template <int XMODE>
+__device__ __forceinline__ void gemv_batch_stream_barriers() {
+  if constexpr (XMODE == XM_LNORM) {                               // the prologue waves' mean and variance reductions
+    __syncthreads();
+    __syncthreads();
+  }
+  if constexpr (XMODE == XM_NORM) __syncthreads();                 // barrier 1 of 2: the prologue waves' sums of squares
+  __syncthreads();                                                 // the images and the row sums are complete
+}
+
+// Epilogue of one output row of one activation row, from the fp32 value(s) in front of the output grid(s): out_grid by q|k|v segment
+// (+ residual), or the gate (QSiLU / QGELU, the product, w2's input quantizer written as int8).
+struct GemvBatchEpilogue {
+  Grid og0, og1, og2, gmid, gact, gout;
+  __device__ __forceinline__ GemvBatchEpilogue(const float cv, const mq_decode_gemv_args& g)
+      : og0(const_grid(cv, CG_OUT0, g.out_grid[0])), og1(const_grid(cv, CG_OUT1, g.out_grid[1])), og2(const_grid(cv, CG_OUT2, g.out_grid[2])),
+        gmid(const_grid(cv, CG_GATE_MID, g.gate_mid)), gact(const_grid(cv, CG_GATE_ACTOUT, g.gate_actout)), gout(const_grid(cv, CG_GATE_OUT, g.gate_out)) {}
+  // output quantizer as the GEMM / GEMV epilogues evaluate it (reciprocal multiply)
+  __device__ __forceinline__ static float out_q(const Grid& q, float f) {
+    if (!q.on) return f;
+    float v = rintf(f * q.inv_s) + q.o;
+    v = fminf(fmaxf(v, q.qmin), q.qmax);
+    return __fmul_rn(__fsub_rn(v, q.o), q.s);
+  }
+  template <bool GATE>
+  __device__ __forceinline__ void store(const mq_decode_gemv_batch_args& ba, const int b, const int row, const float e0, const float e1, const float res) const {
+    const mq_decode_gemv_args& g = ba.g;
+    if constexpr (GATE) {
+      const float fa = out_q(og0, e0), fb = out_q(og1, e1);
+      float rr;
+      if (g.gate_act == 0) {                                       // QSiLU (qmodule.py:739-753)
+        const float gate = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-fa)));
+        rr = __fmul_rn(fa, gmid.fq(gate));
+      } else {                                                     // QGELU (qmodule.py:790-798), erf form
+        rr = __fmul_rn(__fmul_rn(0.5f, fa), __fadd_rn(1.0f, erff(__fmul_rn(fa, 0.70710678118654752440f))));
+      }
+      const float prod = __fmul_rn(gact.fq(rr), fb);
+      const float qi = dq_index(prod, gout.s, gout.inv_s, gout.o, gout.qmin, gout.qmax);
+      g.gate_q[(size_t)b * ba.gate_stride + row] = (int8_t)((qi != qi ? (int)gout.qmin : (int)qi) - 128);
+      if (g.y) g.y[(size_t)b * ba.y_stride + row] = prod;
+    } else {
+      float v = row < g.seg_end[0] ? out_q(og0, e0) : (row < g.seg_end[1] ? out_q(og1, e0) : out_q(og2, e0));
+      if (g.resid) v = __fadd_rn(res, v);
+      g.y[(size_t)b * ba.y_stride + row] = v;
+    }
+  }
+};
+
+// ---- host side of the batched GEMV launches (mq_decode_batch.hip, mq_decode_grouped.hip) ----------------------------------------
+// rows per workgroup and grid: the logical rows spread over the device's CUs, at most DG_STR * 64 per workgroup
+inline int batch_gemv_geometry(int NL, int* rows_per_wg, unsigned* grid) {
+  static std::atomic<int> cus_of[kMaxDevices];
+  const int dev = current_device();
+  int cus = cus_of[dev].load(std::memory_order_relaxed);
+  if (!cus) {
+    hipDeviceProp_t prop;
+    cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    cus_of[dev].store(cus, std::memory_order_relaxed);
+  }
+  int rpw = (NL + cus - 1) / cus;
+  if (rpw > DG_STR * 64) rpw = DG_STR * 64;
+  *rows_per_wg = rpw;
+  *grid = (unsigned)((NL + rpw - 1) / rpw);
+  return NL;
+}
+
+// raise a kernel's dynamic-LDS ceiling once per device (above the default 64 KiB)
+inline int set_lds(const void* fn, std::atomic<size_t>* cache, size_t lds, const char* name) {
+  if (lds > 32768 && cache[current_device()].load(std::memory_order_relaxed) < lds) {
+    MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess, "%s: %zu bytes of dynamic LDS rejected", name, lds);
+    cache[current_device()].store(lds, std::memory_order_relaxed);
+  }
+  return MQ_OK;
 }
 
 }  // namespace mq

@@ -23,7 +23,8 @@ from typing import List, Optional
 import torch
 
 from . import _lib, ops
-from ._lib import MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqGrid
+from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs, MqDecodeGemvGroupedArgs,
+                   MqGrid)
 from .quantization import qmodule as Q
 
 
@@ -65,8 +66,6 @@ class _Linear:
             raise RuntimeError(f"DecodeEngine: {name}.int8_mode == 'off' asks for the simulated path")
         if wq is None or wq.bypassed() or wq.qcfg.bitwidth > 8 or wq.qcfg.is_dynamic or wq.lwc:
             raise RuntimeError("DecodeEngine: weight quantizers must be static, <= 8 bit and not in LWC mode (run the PTQ to its end first)")
-        if wq.qcfg.is_per_channel and wq.qcfg.group_size != -1:
-            raise RuntimeError("DecodeEngine: grouped per-channel weight quantizers are not served by the integer kernels")
         if lin.use_temporary_parameter or getattr(lin, "temp_weight", None) is not None:
             raise RuntimeError("DecodeEngine: fold the LET parameters first (smooth_lm_inplace): temp_weight / use_temporary_parameter is set")
         if lin.input_chan_scale is not None:
@@ -84,6 +83,16 @@ class _Linear:
         if len(bits) != 1 or not bits <= {4, 8}:
             raise RuntimeError("DecodeEngine: the linears of one phase need the same 8- or 4-bit weight quantizer width")
         self.w4 = bits == {4}
+        kinds = {_Linear.is_grouped(lin) for lin in linears}
+        if len(kinds) != 1:
+            raise RuntimeError("DecodeEngine: the linears of one phase mix per-group and per-channel weight grids (one launch contracts them "
+                               "alike)")
+        self.grouped = kinds == {True}
+        self.group_size = None
+        cat = (lambda ts: torch.stack(ts, dim=1).reshape(-1, *ts[0].shape[1:])) if interleave else (lambda ts: torch.cat(ts, dim=0))
+        if self.grouped:
+            self._init_grouped(linears, a_grid, cat)
+            return
         for lin in linears:
             K = lin.weight.shape[1]
             if self.w4 and K % 64:
@@ -92,9 +101,70 @@ class _Linear:
             ws.append(Q.QLinear._decode_weights(plan)[0]); alphas.append(plan["alpha"].clone()); zps.append(plan["w_zp"].clone()); cts.append(plan["col_term"].clone())
             biases.append(lin.bias.detach().float() if lin.bias is not None else None)
             plan["epi_key"] = None                      # the prefill path re-derives its vectors for its own grid object
-        cat = (lambda ts: torch.stack(ts, dim=1).reshape(-1, *ts[0].shape[1:])) if interleave else (lambda ts: torch.cat(ts, dim=0))
         self.w = cat(ws).contiguous()
         self.alpha, self.w_zp, self.col_term = cat(alphas).contiguous(), cat(zps).contiguous(), cat(cts).contiguous()
+        self._finish(linears, biases, cat)
+
+    @staticmethod
+    def is_grouped(lin: Q.QLinear) -> bool:
+        qc = lin.weight_quantizer.qcfg
+        return bool(qc.is_per_channel and qc.group_size != -1)
+
+    def _init_grouped(self, linears: List[Q.QLinear], a_grid: Q.Quantizer, cat):
+        """Per-group weight grids (mq_decode_gemv_grouped): the weight stream and the [G, N] vectors alpha / cw / t of the bracket
+        P_g + cw A_g + t, from the quantities QLinear._grouped_plan and _forward_int8_grouped use at prefill (the same stored
+        weights, cw = sh_w - o_w, t from the activation grid's c_a, alpha = s_a s_w).  Packed 4-bit rows carry unsigned nibbles
+        (index - qmin), so their cw and t are taken in that domain.  Refuses where the prefill path would leave the integer kernel."""
+        sizes = {int(lin.weight_quantizer.qcfg.group_size) for lin in linears}
+        if len(sizes) != 1:
+            raise RuntimeError(f"DecodeEngine: the linears of one phase mix group sizes {sorted(sizes)} (one launch folds one group size)")
+        gs = sizes.pop()
+        if not Q._static_per_tensor(a_grid, 8) or a_grid.qmin != 0 or a_grid.qmax != 255:
+            raise RuntimeError("DecodeEngine: per-group weight grid: the input needs a static 8-bit unsigned per-tensor grid")
+        s_a = a_grid.scale.detach().reshape(()).float()
+        c_a = (128 - a_grid.offset.detach().reshape(())).round().to(torch.int64)
+        ws, alphas, cws, ts, biases = [], [], [], [], []
+        for lin in linears:
+            N, K = lin.weight.shape
+            if gs < 64 or gs & (gs - 1) or K % gs:
+                raise RuntimeError(f"DecodeEngine: per-group weight grid: group_size {gs} with K {K} is outside the grouped decode launch "
+                                   f"(a power of two >= 64 that divides K)")
+            plan = lin._grouped_plan(lin.weight)
+            if not plan["fold_ok"]:
+                raise RuntimeError("DecodeEngine: per-group weight grid: a group's offset exceeds the kernel's 24-bit fold (narrow range far "
+                                   "from zero)")
+            wq, G = lin.weight_quantizer, plan["G"]
+            q = plan["w"].view(N, K)                                   # stored weights: index - shift
+            shift = 128 if wq.qmax > 127 else 0
+            if self.w4:
+                nib = (q.to(torch.int32) + (shift - int(wq.qmin))).to(torch.uint8)         # the unsigned nibble, 0 .. 15
+                ws.append(ops.pack_w4(nib))
+                wsum = nib.view(N, G, gs).sum(-1, dtype=torch.int64)
+                cw = (int(wq.qmin) - wq.offset.detach().reshape(N, G)).round().to(torch.int64)
+            else:
+                ws.append(q)
+                wsum = plan["wsum_t"].t().to(torch.int64)
+                cw = plan["cw_t"].t().to(torch.int64)
+            t64 = c_a * wsum + (gs * c_a) * cw
+            cw_max = int(cw.abs().max())
+            # the int32 bracket: |P_g| <= 128 * 128 gs, |cw A_g| <= cw_max 128 gs, |t|; the 24-bit multiply needs |cw| < 2^23.  One
+            # host read per lowering (static grids): where it does not fit the prefill path's alpha turns NaN, here the engine refuses
+            if cw_max >= 2 ** 23 or int(t64.abs().max()) + (cw_max + 128) * 128 * gs >= 2 ** 31:
+                raise RuntimeError("DecodeEngine: per-group weight grid: the int32 bracket of the fold does not fit for this activation grid "
+                                   "(an input grid far from zero)")
+            ws[-1] = ws[-1].view(torch.int8)
+            cws.append(cw.to(torch.int32))
+            ts.append(t64.to(torch.int32))
+            alphas.append(s_a * wq.scale.detach().reshape(N, G).float())
+            biases.append(lin.bias.detach().float() if lin.bias is not None else None)
+        self.group_size = gs
+        self.w = cat(ws).contiguous()
+        self.alpha = self.w_zp = self.col_term = None
+        # [G, N] group-major, columns concatenated (q|k|v) or interleaved (w1|w3) as the rows of the stream
+        self.g_alpha, self.g_cw, self.g_t = (cat(v).t().contiguous() for v in (alphas, cws, ts))
+        self._finish(linears, biases, cat)
+
+    def _finish(self, linears, biases, cat):
         self.bias = None
         if any(b is not None for b in biases):
             self.bias = cat([b if b is not None else torch.zeros(l.weight.shape[0], device=l.weight.device)
@@ -119,6 +189,17 @@ class _Linear:
             else:
                 outs.append(plan["w"].view(torch.int8).reshape(lin.weight.shape))
         return torch.cat(outs, dim=0).contiguous()
+
+
+def _grouped_args(lin: _Linear, a: MqDecodeGemvArgs, batch: int, x_stride: int, y_stride: int, gate_stride: int) -> MqDecodeGemvGroupedArgs:
+    """mq_decode_gemv_grouped's argument block: the batched launch's block around `a` plus the group size and the [G, N] vectors."""
+    b = MqDecodeGemvBatchArgs()
+    b.g, b.batch, b.x_stride, b.y_stride, b.gate_stride = a, batch, x_stride, y_stride, gate_stride
+    ga = MqDecodeGemvGroupedArgs()
+    ga.b, ga.group_size = b, lin.group_size
+    ga.alpha, ga.cw, ga.t = lin.g_alpha.data_ptr(), lin.g_cw.data_ptr(), lin.g_t.data_ptr()
+    ga._mq_bytes = a._mq_bytes + 12 * lin.g_alpha.numel()          # + alpha / cw / t, 4 bytes each per group and row
+    return ga
 
 
 class DecodeEngine:
@@ -147,7 +228,8 @@ class DecodeEngine:
                  launches: int = 4, long_from: Optional[int] = None):
         """launches: 4 (round 6, default) = per layer {norm + q|k|v, RoPE / cache append / attention + o_proj's contraction, o_proj's
         epilogue + norm + w1|w3 + gate, w2}; 5 = round 2-5's chain with o_proj as a launch of its own.  A geometry the 4-launch kernels
-        do not serve -- incl. a cache_len above max_cache_len(4, head_dim) -- falls back to 5 (self.launches says which); a cache_len
+        do not serve -- incl. a cache_len above max_cache_len(4, head_dim) and a model with per-group weight grids (QuantConfig
+        group_size: mq_decode_gemv_grouped) -- falls back to 5 (self.launches says which); a cache_len
         above max_cache_len(5, head_dim) raises RuntimeError.  The 4-launch chain keeps the VALUE cache transposed in 16-position chunks
         ([kv_heads, cache_len / 16, head_dim, 16]: its p.v sweep is v_dot4 work on coalesced KiB requests); use cached_values() / load_cached_values() to read / write it in
         the logical [kv_heads, positions, head_dim] layout."""
@@ -160,7 +242,9 @@ class DecodeEngine:
         self.dev, self.cache_len = dev, int(cache_len)
         self._prefetch = (prefetch, prefetch_delay_us)           # (delay None: by chain, once self.launches is known)
         self.cos, self.sin = model.cos.contiguous(), model.sin.contiguous()
-        self.oproj_geom = self._chain_geometry(s, self.cos.shape[1], self.cache_len, launches)
+        # per-group weight grids: the five-launch chain (o_proj's contraction inside the four-launch attention launch has no per-group fold)
+        self.grouped = any(isinstance(m, Q.QLinear) and m.weight_quantizer is not None and _Linear.is_grouped(m) for m in model.modules())
+        self.oproj_geom = self._chain_geometry(s, self.cos.shape[1], self.cache_len, 5 if self.grouped else launches)
         self.launches = 4 if self.oproj_geom is not None else 5
         self.v_transposed = self.launches == 4
         self.long_from = self.LONG4_FROM if long_from is None else int(long_from)      # (four launches) first position of the long-cache graph
@@ -260,8 +344,10 @@ class DecodeEngine:
         # 256): share 0 / 0.5 / 0.7 / 1.0 -> 0.678 / 0.656 / 0.665 / 0.690 ms per token: the attention's own dependent loads queue
         # behind the prefetch stream, so half of it, started 1.5 us into the launch, is the optimum.
         if prefetch:
-            pairs = [(self.phases[i][1], self.phases[i + (1 if self.launches == 4 else 2)][1]) for i in range(1, len(self.phases), self.launches)]
-            for at, gate in pairs:
+            pairs = [(self.phases[i][1], self.phases[i + (1 if self.launches == 4 else 2)]) for i in range(1, len(self.phases), self.launches)]
+            for at, (kind, gate) in pairs:
+                if kind != "gemv":        # the grouped launch spreads its rows differently: its workgroups would not meet these bytes
+                    continue
                 n, per, tot = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
                 _lib.call("mq_decode_gemv_geometry", ctypes.byref(gate), ctypes.byref(n), ctypes.byref(per), ctypes.byref(tot))
                 at.prefetch, at.prefetch_stride, at.prefetch_total, at.prefetch_wgs = gate.w, per.value, tot.value, n.value
@@ -319,7 +405,9 @@ class DecodeEngine:
     def _gemv(self, lin: _Linear, **fields) -> MqDecodeGemvArgs:
         a = MqDecodeGemvArgs()
         a.K, a.N = lin.K, lin.N
-        a.w, a.alpha, a.w_zp, a.col_term = lin.w.data_ptr(), lin.alpha.data_ptr(), lin.w_zp.data_ptr(), lin.col_term.data_ptr()
+        a.w = lin.w.data_ptr()
+        if not lin.grouped:                                  # (grouped: the [G, N] vectors travel in _grouped_args' block)
+            a.alpha, a.w_zp, a.col_term = lin.alpha.data_ptr(), lin.w_zp.data_ptr(), lin.col_term.data_ptr()
         a.bias = lin.bias.data_ptr() if lin.bias is not None else None
         a.seg_end[0] = a.seg_end[1] = lin.N
         for k, v in fields.items():
@@ -342,6 +430,10 @@ class DecodeEngine:
     def _finish_gemv(self, a: MqDecodeGemvArgs) -> MqDecodeGemvArgs:
         a.consts = self._pack([a.norm_in, a.a_grid, a.out_grid[0], a.out_grid[1], a.out_grid[2], a.gate_mid, a.gate_actout, a.gate_out, a.o_out])
         return a
+
+    def _gemv_phase(self, lin: _Linear, a: MqDecodeGemvArgs):
+        """(kind, launch record) of a five-launch GEMV phase: mq_decode_gemv, or mq_decode_gemv_grouped at batch 1 for per-group weight grids."""
+        return ("gemv_grouped", _grouped_args(lin, a, 1, 0, 0, 0)) if lin.grouped else ("gemv", a)
 
     def _attention_grids(self, attn, at, keep):
         qk, pv = attn.qk_bmm, attn.pv_bmm
@@ -438,7 +530,7 @@ class DecodeEngine:
         p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
         for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
             p1.out_grid[k] = _grid(lin.output_quantizer, keep)
-        phases.append(("gemv", self._finish_gemv(p1)))
+        phases.append(self._gemv_phase(qkv, self._finish_gemv(p1)))
         # (2) attention core
         at = MqDecodeAttentionArgs()
         at.qkv, at.k_cache, at.v_cache = self.qkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
@@ -452,7 +544,7 @@ class DecodeEngine:
         op = _Linear([attn.o_proj], g_o)
         p3 = self._gemv(op, xq=self.attn_q.data_ptr(), a_grid=_grid(g_o, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
         p3.out_grid[0] = _grid(attn.o_proj.output_quantizer, keep)
-        phases.append(("gemv", self._finish_gemv(p3)))
+        phases.append(self._gemv_phase(op, self._finish_gemv(p3)))
         # (4) post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
         a2 = MqDecodeGemvArgs()
         g_ffn = self._norm_args(layer.post_attention_layernorm, a2)
@@ -469,15 +561,15 @@ class DecodeEngine:
                         gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
                         gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep))
         p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
-        phases.append(("gemv", self._finish_gemv(p4)))
+        phases.append(self._gemv_phase(w13, self._finish_gemv(p4)))
         # (5) w2 from the int8 image + residual
         w2 = _Linear([mlp.w2], iq2)
         p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
         p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
-        phases.append(("gemv", self._finish_gemv(p5)))
+        phases.append(self._gemv_phase(w2, self._finish_gemv(p5)))
 
     # -- running -------------------------------------------------------------------------------------------------------------
-    _ENTRY = {"gemv": "mq_decode_gemv", "attn": "mq_decode_attention", "attn_oproj": "mq_decode_attention_oproj"}
+    _ENTRY = {"gemv": "mq_decode_gemv", "gemv_grouped": "mq_decode_gemv_grouped", "attn": "mq_decode_attention", "attn_oproj": "mq_decode_attention_oproj"}
 
     def _launch(self, phases=None):
         """embedding gather + 4 (or 5) launches per layer + norm / lm_head, on the current stream; reads self.tok / self.pos."""

@@ -4,7 +4,8 @@ int8 KV cache (csrc/mq_decode_batch.hip).
 ``DecodeEngine`` streams the whole model for one token per step.  ``BatchDecodeEngine`` lowers every decoder layer to the same five
 launches (norm + q|k|v, attention, o_proj + residual, norm + w1|w3 + gate, w2 + residual) but each launch serves B activation rows:
 the weights are read once per step for all slots.  The contract is per sequence: slot b of a batched step computes exactly -- bit for
-bit -- what ``DecodeEngine`` computes for that sequence alone.
+bit -- what ``DecodeEngine`` computes for that sequence alone.  A phase whose linears carry per-group weight grids
+(QuantConfig group_size) runs ``mq_decode_gemv_grouped``, the launch the single engine runs for it at B = 1.
 
 Positions live in device memory (``pos [B]``), so ONE captured hipGraph serves every mix of slot positions: the attention launch
 chooses each sequence's split count on the device, and a slot whose position is the ``cache_len`` sentinel is idle -- its cache and
@@ -19,7 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs, MqDecodeHeadBatchArgs
-from .decode import DecodeEngine, _grid, _Keep, _Linear
+from .decode import DecodeEngine, _grid, _grouped_args, _Keep, _Linear
 from .quantization import qmodule as Q
 
 MAX_BATCH = 8
@@ -110,11 +111,14 @@ class BatchDecodeEngine:
         self.weight_bytes = sum(p[1]._mq_bytes for p in self.phases if hasattr(p[1], "_mq_bytes"))
         self.head_bytes = self.lm_w.numel() * 4
 
-    def _batched(self, a: MqDecodeGemvArgs, x_stride: int, y_stride: int, gate_stride: int = 0) -> MqDecodeGemvBatchArgs:
+    def _batched(self, lin: _Linear, a: MqDecodeGemvArgs, x_stride: int, y_stride: int, gate_stride: int = 0):
+        """(kind, launch record) over the B slot rows: mq_decode_gemv_batch, or mq_decode_gemv_grouped for per-group weight grids."""
+        if lin.grouped:
+            return "gemv_grouped", _grouped_args(lin, a, self.batch, x_stride, y_stride, gate_stride)
         b = MqDecodeGemvBatchArgs()
         b.g, b.batch, b.x_stride, b.y_stride, b.gate_stride = a, self.batch, x_stride, y_stride, gate_stride
         b._mq_bytes = a._mq_bytes
-        return b
+        return "gemv", b
 
     def _lower_layer(self, li, layer):
         """The five launches of DecodeEngine._lower_layer, each over the B rows of the slot buffers."""
@@ -133,7 +137,7 @@ class BatchDecodeEngine:
         p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
         for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
             p1.out_grid[k] = _grid(lin.output_quantizer, keep)
-        self.phases.append(("gemv", self._batched(self._finish_gemv(p1), s.hidden, self.qkv.shape[1])))
+        self.phases.append(self._batched(qkv, self._finish_gemv(p1), s.hidden, self.qkv.shape[1]))
         # (2) attention core, per sequence
         at = MqDecodeAttentionArgs()
         at.qkv, at.k_cache, at.v_cache = self.qkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
@@ -149,7 +153,7 @@ class BatchDecodeEngine:
         op = _Linear([attn.o_proj], g_o)
         p3 = self._gemv(op, xq=self.attn_q.data_ptr(), a_grid=_grid(g_o, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
         p3.out_grid[0] = _grid(attn.o_proj.output_quantizer, keep)
-        self.phases.append(("gemv", self._batched(self._finish_gemv(p3), H * D, s.hidden)))
+        self.phases.append(self._batched(op, self._finish_gemv(p3), H * D, s.hidden))
         # (4) post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
         a2 = MqDecodeGemvArgs()
         g_ffn = self._norm_args(layer.post_attention_layernorm, a2)
@@ -166,12 +170,12 @@ class BatchDecodeEngine:
                         gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
                         gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep))
         p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
-        self.phases.append(("gemv", self._batched(self._finish_gemv(p4), s.hidden, 0, s.ffn)))
+        self.phases.append(self._batched(w13, self._finish_gemv(p4), s.hidden, 0, s.ffn))
         # (5) w2 from the int8 image + residual
         w2 = _Linear([mlp.w2], iq2)
         p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
         p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
-        self.phases.append(("gemv", self._batched(self._finish_gemv(p5), s.ffn, s.hidden)))
+        self.phases.append(self._batched(w2, self._finish_gemv(p5), s.ffn, s.hidden))
 
     def grids_stale(self) -> bool:
         return self._keep.stale()
@@ -190,7 +194,7 @@ class BatchDecodeEngine:
             self.refresh_grids()
 
     # -- running -------------------------------------------------------------------------------------------------------------
-    _ENTRY = {"gemv": "mq_decode_gemv_batch", "attn": "mq_decode_attention_batch"}
+    _ENTRY = {"gemv": "mq_decode_gemv_batch", "gemv_grouped": "mq_decode_gemv_grouped", "attn": "mq_decode_attention_batch"}
 
     def _launch(self):
         """embedding gather + 5 launches per layer + norm / lm_head for all slots, on the current stream; reads self.tok / self.pos."""

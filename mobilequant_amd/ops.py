@@ -481,6 +481,12 @@ def int8_linear_grouped(a_q: torch.Tensor, w_q: torch.Tensor, group_size: int, a
     return out
 
 
+def decode_gemv_grouped(args: "_lib.MqDecodeGemvGroupedArgs") -> None:
+    """mq_decode_gemv_grouped on the current stream: the five-launch decode GEMV with per-group weight grids for 1 .. 8 activation rows.
+    args is a filled _lib.MqDecodeGemvGroupedArgs (include/mobilequant_amd.h); the tensors it points into stay alive until it has run."""
+    _lib.call("mq_decode_gemv_grouped", ctypes.byref(args), _stream())
+
+
 def int8_linear_segmented(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: torch.Tensor, alpha: torch.Tensor, w_zp: torch.Tensor,
                           col_term: torch.Tensor, bias: Optional[torch.Tensor], seg_ends, grids, w4: bool = False,
                           a_tiled_rows: Optional[int] = None) -> torch.Tensor:
