@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4: + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4: + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -601,6 +601,31 @@ typedef struct mq_decode_gemv_grouped_args {
   const int32_t* t;    /* [G, N] c_a W_g[n] + group_size c_a cw[g, n], c_a = 128 - z_a, W_g = sum of the group's stored weights */
 } mq_decode_gemv_grouped_args;
 int mq_decode_gemv_grouped(const mq_decode_gemv_grouped_args* args, mq_stream_t stream);
+
+/* ---- several consecutive positions of ONE sequence per launch (multi-token decode step, speculative verification) -- */
+/* mq_decode_attention for `rows` consecutive tokens of one sequence: grid (heads, a.nsplit, rows).  p = *a.pos (one int); row j is the
+ * token at position p + j.  Row j reads qkv + j * qkv_stride floats, writes out / out_q + j * heads * head_dim, and uses the split
+ * scratch part + j * nsplit * heads * head_dim and ticket + j * heads.  A row with p + j >= cache_len does nothing.
+ * Contract:
+ *   - row j's outputs equal, bit for bit, what mq_decode_attention_batch at batch 1 computes for position p + j over a cache that
+ *     already holds rows 0 .. j-1's appended keys and values (the same fp32 softmax expressions and reduction orders at T = p + j + 1,
+ *     the split count chosen on the device from split_from; the p.v sums are exact integers);
+ *   - after the launch, positions p .. p + rows - 1 of both caches hold exactly the bytes `rows` sequential single-position launches
+ *     would have written; no other cache byte changes.
+ * No row reads a cached position >= p (those are written by this very launch): every workgroup forms the RoPE'd, quantised keys and
+ * values of rows 0 .. j itself, in LDS.  Cached bytes past the sequence are never read either.
+ * v_chunked = 0: value cache [kv_heads][cache_len][head_dim] (mq_decode_attention); 1: [kv_heads][cache_len / 16][head_dim][16]
+ * (mq_decode_attention_oproj; cache_len % 16 == 0).  The key cache is [kv_heads][cache_len][head_dim] in both.
+ * Limits (MQ_EINVAL with a message, before any HIP call): rows 1 .. MQ_DECODE_MAX_BATCH, cache_len <= 32768 (4 bytes of LDS per
+ * cached position plus <= 13 KiB static), nsplit > 1 needs part and ticket, no prefetch rows, and mq_decode_attention_batch's grids. */
+typedef struct mq_decode_attention_multi_args {
+  mq_decode_attention_args a;
+  int rows; /* 1 .. MQ_DECODE_MAX_BATCH */
+  int split_from;
+  int64_t qkv_stride;
+  int v_chunked;
+} mq_decode_attention_multi_args;
+int mq_decode_attention_multi(const mq_decode_attention_multi_args* args, mq_stream_t stream);
 
 /* ---- a10: quantized causal attention at prefill (hf_model.py:486-534 with the two QMatMuls of qmodule.py:453-466) ------------ */
 /* One sequence.  q [seq, heads*D], k / v [seq, kv_heads*D] fp32 = the q / k / v projection outputs BEFORE RoPE; cos / sin [seq, D]

@@ -115,6 +115,28 @@ constexpr int DG_PRO = 8, DG_STR = DG_WAVES - DG_PRO, DG_XPRE = 4;      // 512 p
 
 enum { AG_QK_A = 0, AG_QK_B = 1, AG_QK_OUT = 2, AG_PV_A = 3, AG_PV_B = 4, AG_PV_OUT = 5, AG_O_IN = 6, AG_COUNT = 7 };
 
+// One element d of a new token's q / k / v row on its 8-bit attention input grid, as stored (index - 128): RoPE (rotate-half over the
+// first rot dimensions: x * cos + rot(x) * sin) then the grid -- the expressions of decode_attention_batch_kernel, for the
+// attention launches that build new rows themselves (mq_decode_multi.hip).  par: the element's RoPE partner; rot = 0: no rotation (v).
+__device__ __forceinline__ int8_t attn_new_elem(float raw, float par, float cs, float sn, int d, int rot, const Grid& g) {
+  float x = raw;
+  if (d < rot) {
+    const float sg = d < (rot >> 1) ? -1.f : 1.f;                  // (-x) * sin == -(x * sin) exactly
+    x = __fadd_rn(__fmul_rn(raw, cs), __fmul_rn(sg * par, sn));
+  }
+  const float i = dq_index(x, g.s, g.inv_s, g.o, g.qmin, g.qmax);
+  return (int8_t)((i != i ? 0 : (int)i) - 128);
+}
+// The score of one position from its exact integer dot (q index . k index) and key byte sum: qk_bmm's output grid, then / sqrt(D)
+// (hf_model.py:513) -- decode_attention_batch_kernel's expression.
+template <int D>
+__device__ __forceinline__ float attn_score(int dot, int ks, int zq, int qconst, float alpha_qk, const Grid& qo) {
+  constexpr bool pow2 = (D == 64 || D == 256);
+  const int ti = dot - zq * ks + qconst;
+  const float qv = qo.fq(__fmul_rn((float)ti, alpha_qk));
+  return pow2 ? __fmul_rn(qv, 1.0f / (D == 64 ? 8.0f : 16.0f)) : __fdiv_rn(qv, __fsqrt_rn((float)D));
+}
+
 // sum over aligned groups of N = 2 / 4 adjacent lanes: DPP quad permutes (a __shfl_xor is an LDS round trip, ~100 cycles each)
 template <int N>
 __device__ __forceinline__ int quad_sum(int v) {

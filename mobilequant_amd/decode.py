@@ -18,13 +18,13 @@ qk_bmm output, pv_bmm input).
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _lib, ops
-from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs, MqDecodeGemvGroupedArgs,
-                   MqGrid)
+from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
+                   MqDecodeGemvGroupedArgs, MqDecodeHeadBatchArgs, MqGrid)
 from .quantization import qmodule as Q
 
 
@@ -202,7 +202,52 @@ def _grouped_args(lin: _Linear, a: MqDecodeGemvArgs, batch: int, x_stride: int, 
     return ga
 
 
+def spec_accept(argmax_rows: Sequence[int], proposals: Sequence[int], eos=(), budget: Optional[int] = None,
+                room: Optional[int] = None) -> Tuple[List[int], int, bool]:
+    """Bookkeeping of one greedy speculative round (DecodeEngine.generate with a draft), host only.  The target ran the rows
+    [t, d1 .. dk] (t: the last token, not yet cached; d: the proposals); argmax_rows[i] is row i's greedy token, i.e. plain greedy's token
+    after t, d1 .. di.  Tokens are taken in order: row i's token is kept; it continues the round only while it equals d(i+1) (accepted).
+    The first disagreeing row or the bonus row k ends the round with its own token.  The round also ends at an EOS token, once `budget`
+    tokens are kept (new tokens still allowed) or once `room` are (cache positions left behind the last cached one: the position plain
+    generate would stop at).  Returns (kept tokens, accepted proposals among them, stop).  The kept tokens are plain greedy's next
+    tokens, and the target's cache is valid for exactly len(kept) positions from t's on."""
+    eos = set(eos or ())
+    k = len(proposals)
+    if len(argmax_rows) < k + 1:
+        raise ValueError(f"spec_accept: {len(argmax_rows)} rows for {k} proposals (needs k + 1)")
+    out, acc = [], 0
+    for i, g in enumerate(argmax_rows[:k + 1]):
+        g = int(g)
+        out.append(g)
+        hit = i < k and g == int(proposals[i])
+        acc += int(hit)
+        if g in eos or (budget is not None and len(out) >= budget) or (room is not None and len(out) >= room):
+            return out, acc, True
+        if not hit:
+            break
+    return out, acc, False
+
+
+def prompt_lookup_draft(ngram: int = 3) -> Callable[[List[int], int], List[int]]:
+    """A draft without a model (prompt lookup): draft(ids, k) proposes up to k tokens that followed the latest EARLIER occurrence of
+    the last `ngram` tokens of ids, or none."""
+    n = int(ngram)
+    if n < 1:
+        raise ValueError(f"prompt_lookup_draft: ngram={ngram} must be >= 1")
+
+    def draft(ids: List[int], k: int) -> List[int]:
+        if k <= 0 or len(ids) <= n:
+            return []
+        tail = list(ids[-n:])
+        for i in range(len(ids) - n - 1, -1, -1):
+            if list(ids[i:i + n]) == tail:
+                return [int(t) for t in ids[i + n:i + n + k]]
+        return []
+    return draft
+
+
 class DecodeEngine:
+    MAX_ROWS = 8                         # step_tokens: tokens per multi-token step (MQ_DECODE_MAX_BATCH), lowered by the shape (max_rows)
     LONG_FROM, LONG_SPLITS = 768, 4      # five launches: the split attention launch from LONG_FROM cached positions on
     LONG4_FROM = 1024                    # four launches: the 1024-thread attention + o_proj launch from here on (mq_decode_attention_oproj_args.threads):
                                          # 256 / 1024 threads at 256 | 512 | 1024 | 2048 positions: 1768 | 1701 | 1555 | 1331 against 1669 | 1646 | 1595 | 1482 tok/s
@@ -212,6 +257,7 @@ class DecodeEngine:
     # 32768 binds); four launches 2240 / 2368 / 2624 / 3136 at 256 threads, 8528 / 8656 / 8912 / 9424 at 1024 threads.
     LDS_BYTES = 160 * 1024
     ATTN_MAX_CACHE = 32768
+    ROW_IMAGE_BYTES, ROW_HEAD_FLOATS = 128 * 1024, 32768      # mq_decode_gemv_batch / mq_decode_head_batch limits (rows * K, rows * hidden)
     AO_STATIC_LDS = {256: {32: 2240, 64: 2368, 128: 2624, 256: 3136}, 1024: {32: 8528, 64: 8656, 128: 8912, 256: 9424}}
 
     @classmethod
@@ -280,6 +326,10 @@ class DecodeEngine:
         self.v_cache = [torch.zeros(vshape, dtype=torch.int8, device=dev) for _ in model.layers]
         self._host_pos = 0                                   # mirror of self.pos for the cache-overflow guard (no device read-back)
         assert self.cos.shape[0] >= self.cache_len, "rope tables shorter than the cache"
+        # step_tokens: rows per multi-token step -- T * K int8 images in the batched GEMV launches' LDS, T * hidden floats in the head's
+        big = max(s.hidden, s.ffn, s.heads * s.head_dim)
+        self.max_rows = max(1, min(self.MAX_ROWS, self.ROW_IMAGE_BYTES // big, self.ROW_HEAD_FLOATS // s.hidden))
+        self.spec_stats = None
         self.graph = None
         self.graph_long = None
         self._lower()
@@ -319,6 +369,9 @@ class DecodeEngine:
         prefetch, prefetch_delay_us = self._prefetch
         self._keep = _Keep()
         self.phases = []          # (kind, ctypes struct) in launch order
+        self._layer_lins = []     # per layer (q|k|v, o_proj, w1|w3, w2): the weight images the T-row phases share (_lower_rows)
+        self._rows = None         # T-row phases of step_tokens: lowered on first use, from the images above
+        self._row_graphs = {}
         # embedding table, final norm and lm_head (fp32, unquantised: qmodule.py:843) are snapshots like every weight image: re-derived
         # here and tracked for grids_stale()
         self.embed = model.embed_tokens.weight.detach()
@@ -513,6 +566,7 @@ class DecodeEngine:
         p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x_mid.data_ptr(), y=self.x.data_ptr())
         p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
         self.phases.append(("gemv", self._finish_gemv(p5)))
+        self._layer_lins.append((qkv, op, w13, w2))
 
     def _lower_layer(self, li, layer):
         phases = self.phases
@@ -567,8 +621,184 @@ class DecodeEngine:
         p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
         p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
         phases.append(self._gemv_phase(w2, self._finish_gemv(p5)))
+        self._layer_lins.append((qkv, op, w13, w2))
+
+    # -- T-row phases (step_tokens) -----------------------------------------------------------------------------------------
+    def _lower_rows(self):
+        """The launch records of a multi-token step: per layer the batched five-launch chain (mq_decode_gemv_batch / _grouped over T
+        rows, mq_decode_attention_multi over the engine's own caches in its value layout) on the weight images the single chain already
+        holds (self._layer_lins: the same _Linear objects, incl. o_proj's row image `op` that the four-launch chain keeps next to its
+        head-sliced copy), plus mq_decode_head_batch.  Row buffers of their own; the row count T is set per launch (_set_rows)."""
+        model, s, dev, keep, R = self.model, self.shape, self.dev, self._keep, self.max_rows
+        H, D = s.heads, s.head_dim
+        qkv_n = self.qkv.shape[0]
+        self.rx = torch.zeros(R, s.hidden, device=dev)
+        self.rqkv = torch.zeros(R, qkv_n, device=dev)
+        self.rattn_q = torch.zeros(R, H * D, dtype=torch.int8, device=dev)
+        self.rpart = torch.zeros(R, self.LONG_SPLITS, H * D, dtype=torch.int64, device=dev)
+        self.rticket = torch.zeros(R, H, dtype=torch.int32, device=dev)
+        self.rgate = torch.zeros(R, s.ffn, dtype=torch.int8, device=dev)
+        self.rlogits = torch.zeros(R, s.vocab, device=dev)
+        self.rtok = torch.zeros(R, dtype=torch.int64, device=dev)
+
+        def rows(lin: _Linear, a: MqDecodeGemvArgs, x_stride: int, y_stride: int, gate_stride: int = 0):
+            if lin.grouped:
+                return "gemv_grouped", _grouped_args(lin, a, R, x_stride, y_stride, gate_stride)
+            b = MqDecodeGemvBatchArgs()
+            b.g, b.batch, b.x_stride, b.y_stride, b.gate_stride = a, R, x_stride, y_stride, gate_stride
+            return "gemv", b
+
+        phases = []
+        with torch.no_grad():
+            for li, (layer, (qkv, op, w13, w2)) in enumerate(zip(model.layers, self._layer_lins)):
+                attn, mlp = layer.self_attn, layer.mlp
+                # (1) input_layernorm + q|k|v
+                a = MqDecodeGemvArgs()
+                self._norm_args(layer.input_layernorm, a)
+                p1 = self._gemv(qkv, x=self.rx.data_ptr(), norm_w=a.norm_w, norm_bias=a.norm_bias, layernorm=a.layernorm, norm_in=a.norm_in,
+                                eps=a.eps, a_grid=a.a_grid, y=self.rqkv.data_ptr())
+                p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
+                for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
+                    p1.out_grid[k] = _grid(lin.output_quantizer, keep)
+                phases.append(rows(qkv, self._finish_gemv(p1), s.hidden, qkv_n))
+                # (2) attention of the T consecutive positions, appending to the engine's caches
+                at = MqDecodeAttentionArgs()
+                at.qkv, at.k_cache, at.v_cache = self.rqkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
+                at.cos, at.sin, at.pos = self.cos.data_ptr(), self.sin.data_ptr(), self.pos.data_ptr()
+                at.heads, at.kv_heads, at.head_dim, at.cache_len = H, s.kv_heads, D, self.cache_len
+                at.rot_dim, at.nsplit = self.cos.shape[1], self.LONG_SPLITS
+                g_o = self._attention_grids(attn, at, keep)
+                at.out_q, at.part, at.ticket = self.rattn_q.data_ptr(), self.rpart.data_ptr(), self.rticket.data_ptr()
+                ma = MqDecodeAttentionMultiArgs()
+                ma.a, ma.rows, ma.split_from, ma.qkv_stride, ma.v_chunked = at, R, self.LONG_FROM, qkv_n, int(self.v_transposed)
+                phases.append(("attn_multi", ma))
+                # (3) o_proj + residual from the int8 image
+                p3 = self._gemv(op, xq=self.rattn_q.data_ptr(), a_grid=_grid(g_o, keep), resid=self.rx.data_ptr(), y=self.rx.data_ptr())
+                p3.out_grid[0] = _grid(attn.o_proj.output_quantizer, keep)
+                phases.append(rows(op, self._finish_gemv(p3), H * D, s.hidden))
+                # (4) post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
+                a2 = MqDecodeGemvArgs()
+                self._norm_args(layer.post_attention_layernorm, a2)
+                act, iq2 = mlp.act_fn, mlp.w2.input_quantizer
+                p4 = self._gemv(w13, x=self.rx.data_ptr(), norm_w=a2.norm_w, norm_bias=a2.norm_bias, layernorm=a2.layernorm, norm_in=a2.norm_in,
+                                eps=a2.eps, a_grid=a2.a_grid,
+                                gate_q=self.rgate.data_ptr(), gate_act=0 if isinstance(act, Q.QSiLU) else 1,
+                                gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
+                                gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep))
+                p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
+                phases.append(rows(w13, self._finish_gemv(p4), s.hidden, 0, s.ffn))
+                # (5) w2 from the int8 image + residual
+                p5 = self._gemv(w2, xq=self.rgate.data_ptr(), a_grid=_grid(iq2, keep), resid=self.rx.data_ptr(), y=self.rx.data_ptr())
+                p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
+                phases.append(rows(w2, self._finish_gemv(p5), s.ffn, s.hidden))
+        hb = MqDecodeHeadBatchArgs()
+        hb.x, hb.x_stride = self.rx.data_ptr(), s.hidden
+        hb.norm_weight, hb.norm_bias = self.norm_w.data_ptr(), (self.norm_b.data_ptr() if self.norm_b is not None else None)
+        hb.layernorm, hb.eps = int(self.norm_ln), float(model.norm.eps)
+        hb.w, hb.bias = self.lm_w.data_ptr(), (self.lm_b.data_ptr() if self.lm_b is not None else None)
+        hb.K, hb.V, hb.batch = s.hidden, s.vocab, R
+        hb.logits, hb.logits_stride = self.rlogits.data_ptr(), s.vocab
+        self._rows = (phases, hb)
+        self._row_graphs = {}
+
+    def _set_rows(self, T: int):
+        phases, hb = self._rows
+        for kind, a in phases:
+            if kind == "gemv":
+                a.batch = T
+            elif kind == "gemv_grouped":
+                a.b.batch = T
+            else:
+                a.rows = T
+        hb.batch = T
+
+    def _launch_rows(self, T: int):
+        """Embedding rows + 5 launches per layer over T rows + norm / lm_head for T rows, on the current stream (reads rtok / pos)."""
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        phases, hb = self._rows
+        torch.index_select(self.embed, 0, self.rtok[:T], out=self.rx[:T])
+        for kind, a in phases:
+            _lib.call(self._ENTRY_ROWS[kind], ctypes.byref(a), st)
+        _lib.call("mq_decode_head_batch", ctypes.byref(hb), st)
+
+    def _finish_rows(self, T: int):
+        self.logits.copy_(self.rlogits[T - 1])
+        self.pos.add_(T)
+
+    def _capture_rows(self, T: int):
+        """Record the T-row step (incl. self.logits <- its last row and the position advance) as a hipGraph.  The warm-up launch outside
+        the capture runs with the position at the cache_len sentinel: every attention row is idle, no cache byte changes."""
+        self._set_rows(T)
+        pos0 = self.pos.clone()
+        self.pos.fill_(self.cache_len)
+        with torch.cuda.device(self.dev):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._launch_rows(T)              # (sets the launches' LDS ceilings outside the capture)
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launch_rows(T)
+                self._finish_rows(T)
+        self.pos.copy_(pos0)
+        self._row_graphs[T] = g
+        return g
+
+    @torch.no_grad()
+    def step_tokens(self, tokens: Sequence[int]) -> torch.Tensor:
+        """T = len(tokens) <= max_rows tokens of this sequence in ONE step: appended at positions p .. p + T - 1 (p = position()).
+        Returns logits [T, vocab] (a device tensor, overwritten by the next call): row j is, bit for bit, what step(tokens[j]) returns
+        after the earlier tokens, and the caches end as those T steps leave them.  The position advances by T; self.logits holds the
+        last row.  After capture() a graph per row count is recorded on first use and replayed; the uncaptured launches give the same
+        bits.  Raises if p + T > cache_len."""
+        t = [int(v) for v in tokens]
+        T = len(t)
+        if not 1 <= T <= self.max_rows:
+            raise ValueError(f"DecodeEngine.step_tokens: {T} tokens outside 1..{self.max_rows} (max_rows)")
+        if self._host_pos + T > self.cache_len:
+            raise RuntimeError(f"DecodeEngine.step_tokens: {T} tokens at position {self._host_pos} overflow the KV cache ({self.cache_len} positions)")
+        if self._rows is None:
+            self._lower_rows()
+        self.rtok[:T].copy_(torch.tensor(t, dtype=torch.int64), non_blocking=False)
+        if self.graph is not None:
+            (self._row_graphs.get(T) or self._capture_rows(T)).replay()
+        else:
+            self._set_rows(T)
+            with torch.cuda.device(self.dev):
+                self._launch_rows(T)
+            self._finish_rows(T)
+        self._host_pos += T
+        return self.rlogits[:T]
+
+    @torch.no_grad()
+    def extend(self, tokens: Sequence[int]) -> torch.Tensor:
+        """Append any number of tokens to the live sequence (no reset), max_rows per step: the same logits and caches as that many
+        step() calls.  Returns self.logits (the last token's row)."""
+        t = [int(v) for v in tokens]
+        if self._host_pos + len(t) > self.cache_len:
+            raise RuntimeError(f"DecodeEngine.extend: {len(t)} tokens at position {self._host_pos} overflow the KV cache ({self.cache_len} positions)")
+        for i in range(0, len(t), self.max_rows):
+            self.step_tokens(t[i:i + self.max_rows])
+        return self.logits
+
+    def rewind(self, n: int):
+        """Drop the positions >= n (n <= position()): later steps compute what an engine that never saw them computes.  Only the
+        position moves: no launch reads a cached byte at or past the position (the attention launches mask the keys, the values, the
+        16-position chunk tail of the four-launch layout and the split blocks by it), so the dropped bytes are never read before they
+        are overwritten.  self.logits is left as it is."""
+        n = int(n)
+        if not 0 <= n <= self._host_pos:
+            raise ValueError(f"DecodeEngine.rewind: n={n} outside 0..{self._host_pos} (the current position)")
+        self.set_position(n)
+        return self
+
+    def position(self) -> int:
+        """Cached positions of the sequence (where the next token is appended)."""
+        return self._host_pos
 
     # -- running -------------------------------------------------------------------------------------------------------------
+    _ENTRY_ROWS = {"gemv": "mq_decode_gemv_batch", "gemv_grouped": "mq_decode_gemv_grouped", "attn_multi": "mq_decode_attention_multi"}
     _ENTRY = {"gemv": "mq_decode_gemv", "gemv_grouped": "mq_decode_gemv_grouped", "attn": "mq_decode_attention", "attn_oproj": "mq_decode_attention_oproj"}
 
     def _launch(self, phases=None):
@@ -617,6 +847,7 @@ class DecodeEngine:
         Quantizers changed since the engine was built (recalibration, scale.copy_) are picked up here, in reset() and in prefill()."""
         if self._keep.stale():
             self._lower()
+        self._row_graphs = {}                                    # (multi-token steps: one graph per row count, recorded on first use)
         tok0, pos0, hp0 = self.tok.clone(), self.pos.clone(), self._host_pos
         graphs = []
         for phases, splits in self._variants():
@@ -726,11 +957,19 @@ class DecodeEngine:
 
     @torch.no_grad()
     def generate(self, context_ids, max_new_tokens: int, eos_token_id=None, prefill: bool = True, do_sample: bool = False,
-                 temperature: float = 0.5, generator: Optional[torch.Generator] = None):
+                 temperature: float = 0.5, generator: Optional[torch.Generator] = None,
+                 draft: Union[None, "DecodeEngine", Callable[[List[int], int], List[int]]] = None, num_draft: int = 4):
         """SimModel.generate (mobilellm/model/sim_model.py:160-221): context encoding in one prefill forward (prefill=False: token by
         token through the step kernels), then per new token: next = argmax(logits) or, with do_sample, multinomial(softmax(logits /
         temperature)) (:198-201) -- on the device, into self.tok --, append it, stop if it is an EOS (:202-204), else run the step.
-        The host reads one token id per step only to test for EOS and to return the ids."""
+        The host reads one token id per step only to test for EOS and to return the ids.
+        draft (greedy only): speculative generation -- another DecodeEngine over a model of the same vocabulary size, or a callable
+        draft(ids, k) -> at most k proposals (prompt_lookup_draft) -- verified num_draft tokens at a time with step_tokens.  The
+        returned ids equal the plain greedy ones token for token; self.spec_stats counts the rounds (_generate_speculative)."""
+        if draft is not None:
+            if do_sample:
+                raise ValueError("DecodeEngine.generate: a draft is for greedy decoding only (do_sample=True with a draft)")
+            return self._generate_speculative(context_ids, max_new_tokens, eos_token_id, prefill, draft, num_draft)
         ids = [int(t) for t in context_ids]
         assert len(ids) + max_new_tokens <= self.cache_len
         self.reset()
@@ -755,3 +994,77 @@ class DecodeEngine:
                 break
             self.step()
         return out
+
+    def _start_sequence(self, ids: List[int], prefill: bool):
+        self.reset()
+        if prefill and len(ids) > 1:
+            self.prefill(ids)
+        else:
+            for t in ids:
+                self.step(t)
+
+    @torch.no_grad()
+    def _generate_speculative(self, context_ids, max_new_tokens: int, eos_token_id, prefill: bool, draft, num_draft: int):
+        """Greedy speculative decoding.  The sequence starts as in plain generate; the first new token is the argmax of the context's
+        logits.  Then per round, with t the last token (not yet cached) and P the position: k = min(num_draft, max_rows - 1, tokens still
+        allowed - 1, cache room - 1) proposals d1..dk from the draft, ONE step_tokens([t, d1..dk]), spec_accept on the rows' argmaxes,
+        and rewind to P + the kept tokens.  Every kept token is plain greedy's (row i holds the logits after t, d1..di, bit for bit), and
+        the stops are plain generate's: EOS, max_new_tokens, the cache end.  An engine draft catches up on the kept tokens with extend
+        and drops the rejected ones with rewind."""
+        ids = [int(t) for t in context_ids]
+        assert len(ids) + max_new_tokens <= self.cache_len
+        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        d_eng = draft if isinstance(draft, DecodeEngine) else None
+        if d_eng is self:
+            raise ValueError("DecodeEngine.generate: the draft must be another engine (it keeps its own cache)")
+        if d_eng is not None and d_eng.shape.vocab != self.shape.vocab:
+            raise ValueError(f"DecodeEngine.generate: draft vocabulary {d_eng.shape.vocab} != target vocabulary {self.shape.vocab}")
+        if d_eng is None and not callable(draft):
+            raise TypeError("DecodeEngine.generate: draft must be a DecodeEngine or a callable draft(ids, k) -> list of token ids")
+        if int(num_draft) < 0:
+            raise ValueError(f"DecodeEngine.generate: num_draft={num_draft} must be >= 0")
+        stats = self.spec_stats = {"rounds": 0, "proposed": 0, "accepted": 0, "target_steps": 0}
+        self._start_sequence(ids, prefill)
+        out = list(ids)
+        if max_new_tokens <= 0:
+            return out
+        d_pos = 0                                                  # the draft engine's cache holds out[:d_pos]
+        if d_eng is not None:
+            d_eng._start_sequence(ids, prefill)
+            d_pos = len(ids)
+        nxt = int(torch.argmax(self.logits))
+        out.append(nxt)
+        made = 1
+        if nxt in eos or made >= max_new_tokens or self._host_pos >= self.cache_len:
+            return out
+        while True:
+            P = self._host_pos
+            k = max(0, min(int(num_draft), self.max_rows - 1, max_new_tokens - made - 1, self.cache_len - P - 1))
+            props: List[int] = []
+            if k > 0 and d_eng is not None:
+                kd = min(k, d_eng.cache_len - len(out) + 1)
+                if kd > 0:
+                    d_eng.extend(out[d_pos:])
+                    props = [int(torch.argmax(d_eng.logits))]
+                    for _ in range(kd - 1):
+                        d_eng.step(props[-1])
+                        props.append(int(torch.argmax(d_eng.logits)))
+                    d_pos = len(out) + kd - 1                      # out + props[:-1]
+            elif k > 0:
+                props = [int(v) for v in draft(list(out), k)][:k]
+            rows = self.step_tokens([out[-1]] + props)
+            new, acc, stop = spec_accept(torch.argmax(rows, dim=-1).tolist(), props, eos, budget=max_new_tokens - made,
+                                         room=self.cache_len - P)
+            stats["rounds"] += 1
+            stats["target_steps"] += 1
+            stats["proposed"] += len(props)
+            stats["accepted"] += acc
+            self.rewind(P + len(new))                              # t and the accepted proposals stay cached
+            self.logits.copy_(rows[len(new) - 1])
+            if d_eng is not None and d_pos > len(out):             # the draft keeps out + the accepted proposals it had cached
+                d_pos = min(d_pos, len(out) + acc)
+                d_eng.rewind(d_pos)
+            out += new
+            made += len(new)
+            if stop:
+                return out

@@ -487,6 +487,13 @@ def decode_gemv_grouped(args: "_lib.MqDecodeGemvGroupedArgs") -> None:
     _lib.call("mq_decode_gemv_grouped", ctypes.byref(args), _stream())
 
 
+def decode_attention_multi(args: "_lib.MqDecodeAttentionMultiArgs") -> None:
+    """mq_decode_attention_multi on the current stream: the decode attention of args.rows consecutive positions of one sequence (from
+    *args.a.pos on) in one launch, appending them to its caches.  args is a filled _lib.MqDecodeAttentionMultiArgs
+    (include/mobilequant_amd.h); the tensors it points into stay alive until it has run."""
+    _lib.call("mq_decode_attention_multi", ctypes.byref(args), _stream())
+
+
 def int8_linear_segmented(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: torch.Tensor, alpha: torch.Tensor, w_zp: torch.Tensor,
                           col_term: torch.Tensor, bias: Optional[torch.Tensor], seg_ends, grids, w4: bool = False,
                           a_tiled_rows: Optional[int] = None) -> torch.Tensor:
