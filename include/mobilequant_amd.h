@@ -786,6 +786,48 @@ int64_t mq_score_head_scratch_bytes(int64_t M, int64_t V);
 int mq_score_head(const float* y, int64_t y_stride, const float* w, const float* bias, const int64_t* targets, int64_t M, int64_t K,
                   int64_t V, void* scratch, int64_t scratch_bytes, float* logprob, float* lse, int64_t* argmax, mq_stream_t stream);
 
+/* ---- seeded token selection on the device: greedy, temperature, top-k, top-p, min-p ------------------------- */
+/* One row's request.  temperature >= 0 (0 = greedy), top_k >= 0 (0 = off), top_p in (0, 1] (1 = off), min_p in [0, 1) (0 = off); seed
+ * and stream select the random numbers: token n of a sequence draws from philox4x32_10(counter {n, i / 4, stream}, key seed) for
+ * vocabulary entry i, so a draw depends on (seed, stream, n) and the row's logits alone.  A row outside these ranges is served as
+ * greedy.  Device data: a slot changes its request without a new graph. */
+typedef struct mq_sample_row {
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  float min_p;
+  uint64_t seed;
+  uint64_t stream;
+} mq_sample_row;
+
+#define MQ_SAMPLE_SCRATCH_BYTES 8192
+
+/* For row r < rows (1 .. MQ_DECODE_MAX_BATCH): n = pos[r] is read on the device; a row with n outside [0, cache_len) is idle (tok, kept
+ * and logprob keep their bytes: the batched launches' sentinel).  Otherwise tok[r] = the token the selection rule in
+ * csrc/mq_sample.hip's header draws from logits[r * logits_stride .. + V) under params[r]; kept[r] (nullable) = the size of the
+ * candidate set, logprob[r] (nullable) = the drawn token's log-probability in it (tolerance: that header; 0 for a greedy row).  The
+ * token is a function of the row's logits, params[r] and n only -- bit for bit the same at any rows, in any slot, captured or not.
+ * V % 4 == 0, 4 <= V <= 2^20; logits_stride >= V and % 4 == 0; logits, params, scratch 16-byte aligned; scratch >=
+ * MQ_SAMPLE_SCRATCH_BYTES, owned by the call on `stream`.  Two launches, no host synchronisation: capturable. */
+typedef struct mq_sample_args {
+  const float* logits;
+  int64_t logits_stride;
+  int64_t V;
+  int rows; /* 1 .. MQ_DECODE_MAX_BATCH */
+  const int* pos;
+  int cache_len;
+  const mq_sample_row* params;
+  int64_t* tok;
+  int* kept;
+  float* logprob;
+  void* scratch;
+  int64_t scratch_bytes;
+} mq_sample_args;
+int mq_sample(const mq_sample_args* args, mq_stream_t stream);
+/* out[j] = the uniform u_i of the rule for vocabulary entry i = first + j, j < count, at (seed, stream_id, n): the generator alone,
+ * for tests (bit-exact against a host philox4x32_10). */
+int mq_sample_uniforms(uint64_t seed, uint64_t stream_id, uint32_t n, int64_t first, int64_t count, float* out, mq_stream_t stream);
+
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes
  * per operand, an fp32 library bmm and two more passes over the product in the reference -- by ONE launch: both fp32 operands are

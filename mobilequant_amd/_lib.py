@@ -81,6 +81,20 @@ class MqDecodeHeadBatchArgs(ctypes.Structure):
                 ("logits", c_void_p), ("logits_stride", c_int64), ("pos", c_void_p), ("cache_len", c_int)]
 
 
+class MqSampleRow(ctypes.Structure):
+    _fields_ = [("temperature", c_float), ("top_k", ctypes.c_int32), ("top_p", c_float), ("min_p", c_float), ("seed", ctypes.c_uint64),
+                ("stream", ctypes.c_uint64)]
+
+
+class MqSampleArgs(ctypes.Structure):
+    _fields_ = [("logits", c_void_p), ("logits_stride", c_int64), ("V", c_int64), ("rows", c_int), ("pos", c_void_p), ("cache_len", c_int),
+                ("params", c_void_p), ("tok", c_void_p), ("kept", c_void_p), ("logprob", c_void_p), ("scratch", c_void_p),
+                ("scratch_bytes", c_int64)]
+
+
+MQ_SAMPLE_SCRATCH_BYTES = 8192
+
+
 class MqAttentionArgs(ctypes.Structure):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("seq", c_int),
                 ("heads", c_int), ("kv_heads", c_int), ("head_dim", c_int), ("inv_sqrt_d", c_float), ("qk_a", MqGrid),
@@ -168,6 +182,8 @@ _SIGNATURES = {
     "mq_attention_quant": (c_int, [POINTER(MqAttentionArgs), _P]),
     "mq_score_head_scratch_bytes": (c_int64, [c_int64, c_int64]),
     "mq_score_head": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P]),
+    "mq_sample": (c_int, [POINTER(MqSampleArgs), _P]),
+    "mq_sample_uniforms": (c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_int64, c_int64, _P, _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

@@ -1,0 +1,475 @@
+// Seeded token selection on the device (mq_sample): greedy, temperature, top-k, top-p (nucleus) and min-p for 1 .. 8 logits rows.
+//
+// THE RULE (normative).  Per row: fp32 logits l[0..V), temperature >= 0, top_k (0 = off), top_p in (0, 1] (1 = off),
+// min_p in [0, 1) (0 = off), seed and stream (u64), n = pos[row] = the number of tokens already in the sequence.
+//   1. z_i = l_i / temperature (fp32, correctly rounded divide; -0 counts as +0).  A NaN logit is -inf.  If every logit is -inf or
+//      NaN the token is 0.
+//   2. Order: z descending, ties by index ascending.  "Prefix" = a prefix in this order.
+//   3. K = the first top_k tokens (all if top_k is 0 or >= V).
+//   4. w_i = (u64) floor(expf(z_i - z_max) * 2^32): sums of w are exact integers in any order (V <= 2^20: below 2^53).  W_K = sum over
+//      K.  P = the shortest prefix of K whose sum is >= ceil((double)top_p * (double)W_K); never empty; top_p == 1: P = K.
+//   5. C = the tokens of P with z_i - z_max >= logf(min_p) (fp32); the top token always passes; min_p == 0: C = P.
+//   6. (r0..r3) = philox4x32_10(counter {lo32(n), i / 4, lo32(stream), hi32(stream)}, key {lo32(seed), hi32(seed)}),
+//      u_i = ((r_(i % 4) >> 9) + 0.5) * 2^-23 (23 random bits: k + 0.5 has at most 24 significant bits, so u_i is exact in fp32 and
+//      strictly inside (0, 1); with 24 bits the largest k + 0.5 would round up to u = 1 and g = +inf), g_i = -logf(-logf(u_i)),
+//      token = argmax over C of z_i + g_i (one fp32 add), ties to the lowest index: a draw from softmax(z) restricted to C.
+//   7. temperature == 0: the lowest index of the maximal logit; no random numbers.  A row whose parameters are out of range
+//      (temperature < 0 or not finite, top_k < 0, top_p outside (0, 1], min_p outside [0, 1)) is served as greedy.
+// Nothing above depends on an evaluation order: the masses are integers, every random number is a function of (seed, stream, n, i)
+// and every maximum is taken under a total order.  So a row's token depends on that row alone, not on its slot or on the launch.
+//
+// THE KERNELS.  Launch 1 (sample_scan_kernel, grid slices x rows, 256 threads): rows without a filter (and greedy rows) -- each
+// workgroup takes a slice of the row, keeps the running best (z + g, index) and writes its partial to scratch.  Launch 2
+// (sample_select_kernel, one workgroup of 1024 threads per row): merges the partials of an unfiltered row in slice order; a filtered
+// row is selected here by radix, without a sort.  Every token gets the 52-bit key (monotone u32 of z) << 20 | (2^20 - 1 - i): keys
+// are distinct and their descending order is the rule's order, so K and P are "key >= cut" and no tie needs a case of its own.  A cut
+// is found digit by digit (11 / 11 / 10 / 10 / 10 bits): per level one pass over the row builds (count, u64 mass) per digit in LDS
+// with integer atomics among the tokens that share the digits found so far, a block scan from the top digit finds the digit where the
+// count reaches top_k (K) or the mass reaches the threshold (P), and the descent goes on inside it; once the digit holds one token a
+// single pass reads its key.  The last pass is the Gumbel argmax over key >= cut with the min-p test.  A row of at most 32 768 entries
+// is read from memory once and held in LDS as z; longer rows are re-read (from the L2) per pass.
+// Optional outputs: kept[row] = |C|; logprob[row] = (z_tok - z_max) - log(W_C 2^-32) with W_C the integer mass of C, evaluated in
+// double from fp32 z.  Against the exact restricted log-softmax of z: |error| <= 2^-23 (2 + log V) + V / W_C + ulp_fp32(logprob) --
+// each w carries expf's error (1 ulp ASSUMED) and the rounding of z_i - z_max, |d_i| 2^-24 relative, whose p-weighted mean is at
+// most 2^-24 log V; flooring drops less than one unit of 2^-32 per token; one rounding of z_tok - z_max and one of the result.  Not
+// part of the bit contract.  All results leave through ordinary vector stores.
+#include "mq_common.h"
+
+#include <limits.h>
+
+namespace mq {
+namespace {
+
+constexpr int SM_SCAN_THREADS = 256;
+constexpr int SM_SLICE = 4096;                 // entries per slice of launch 1 (at most SM_MAX_SLICES slices: longer slices above 2^18 entries)
+constexpr int SM_MAX_SLICES = 64;
+constexpr int SM_THREADS = 1024;               // launch 2: one workgroup per row
+constexpr int SM_WAVES = SM_THREADS / 64;
+constexpr int SM_BINS = 2048;
+constexpr int SM_LDS_ROW = 32768;              // entries of a row held in LDS (128 KiB of the 160)
+constexpr int SM_LEVELS = 5;
+constexpr unsigned long long SM_IDX_MASK = (1ull << 20) - 1;
+
+struct Best {
+  float v;
+  int i;
+};
+
+// (a, ia) ranks above (b, ib): the larger value, then the lower index.  No NaN reaches here.  A total order.
+__device__ __forceinline__ bool better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned r[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+__device__ __forceinline__ float uniform_of(unsigned r) { return ((float)(r >> 9) + 0.5f) * 0x1p-23f; }
+__device__ __forceinline__ float gumbel_of(unsigned r) { return -logf(-logf(uniform_of(r))); }
+
+struct RowCfg {
+  float t, top_p, min_p;
+  int top_k;
+  unsigned s0, s1, k0, k1, n;
+  bool greedy, filtered;
+};
+
+__device__ __forceinline__ RowCfg row_cfg(const mq_sample_row& p, int n, int V) {
+  RowCfg c;
+  c.t = p.temperature; c.top_p = p.top_p; c.min_p = p.min_p; c.top_k = p.top_k;
+  c.s0 = (unsigned)p.stream; c.s1 = (unsigned)(p.stream >> 32); c.k0 = (unsigned)p.seed; c.k1 = (unsigned)(p.seed >> 32);
+  c.n = (unsigned)n;
+  const bool valid = c.t >= 0.f && c.t < __builtin_inff() && c.top_k >= 0 && c.top_p > 0.f && c.top_p <= 1.f && c.min_p >= 0.f && c.min_p < 1.f;
+  c.greedy = !valid || c.t == 0.f;
+  c.filtered = !c.greedy && ((c.top_k > 0 && c.top_k < V) || c.top_p < 1.f || c.min_p > 0.f);
+  return c;
+}
+
+// z of rule 1 (greedy rows: the logit itself)
+__device__ __forceinline__ float z_of(float l, const RowCfg& c) {
+  if (l != l) return -__builtin_inff();
+  return (c.greedy ? l : l / c.t) + 0.f;
+}
+
+// running best of z + g (greedy: z) over entries [lo, hi) of the row, 4 per thread and step; lo, hi multiples of 4
+__device__ __forceinline__ Best scan_range(const float* __restrict__ row, int lo, int hi, const RowCfg& c, int tid, int nthreads) {
+  Best b{-__builtin_inff(), INT_MAX};
+  for (int i = lo + 4 * tid; i < hi; i += 4 * nthreads) {
+    const float4 l = *reinterpret_cast<const float4*>(row + i);
+    const float lv[4] = {l.x, l.y, l.z, l.w};
+    unsigned r[4] = {0, 0, 0, 0};
+    if (!c.greedy) philox4x32_10(c.n, (unsigned)(i >> 2), c.s0, c.s1, c.k0, c.k1, r);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float s = z_of(lv[e], c);
+      if (!c.greedy) s = s + gumbel_of(r[e]);
+      if (better(s, i + e, b.v, b.i)) { b.v = s; b.i = i + e; }
+    }
+  }
+  return b;
+}
+
+__device__ __forceinline__ Best wave_best(Best b) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ov = __shfl_xor(b.v, o);
+    const int oi = __shfl_xor(b.i, o);
+    if (better(ov, oi, b.v, b.i)) { b.v = ov; b.i = oi; }
+  }
+  return b;
+}
+
+// every thread gets the workgroup's best; red: 2 * waves words of LDS
+__device__ __forceinline__ Best block_best(Best b, float* red_v, int* red_i, int tid, int waves) {
+  b = wave_best(b);
+  __syncthreads();
+  if ((tid & 63) == 0) { red_v[tid >> 6] = b.v; red_i[tid >> 6] = b.i; }
+  __syncthreads();
+  Best o{red_v[0], red_i[0]};
+  for (int w = 1; w < waves; ++w)
+    if (better(red_v[w], red_i[w], o.v, o.i)) { o.v = red_v[w]; o.i = red_i[w]; }
+  return o;
+}
+
+__device__ __forceinline__ bool row_idle(const int* pos, int row, int cache_len, int* n) {
+  *n = pos[row];
+  return *n < 0 || *n >= cache_len;
+}
+
+__device__ __forceinline__ void slice_bounds(int V, int S, int s, int* lo, int* hi) {
+  const int len = ((V / 4 + S - 1) / S) * 4;
+  *lo = min(V, s * len);
+  *hi = min(V, *lo + len);
+}
+
+__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_kernel(const float* __restrict__ logits, long long stride, int V, const int* __restrict__ pos,
+                                                                      int cache_len, const mq_sample_row* __restrict__ params, Best* __restrict__ part) {
+  __shared__ float red_v[SM_SCAN_THREADS / 64];
+  __shared__ int red_i[SM_SCAN_THREADS / 64];
+  const int row = blockIdx.y, s = blockIdx.x, S = gridDim.x, tid = threadIdx.x;
+  int n;
+  if (row_idle(pos, row, cache_len, &n)) return;                      // workgroup-uniform
+  const RowCfg c = row_cfg(params[row], n, V);
+  if (c.filtered) return;
+  int lo, hi;
+  slice_bounds(V, S, s, &lo, &hi);
+  const Best b = block_best(scan_range(logits + (long long)row * stride, lo, hi, c, tid, SM_SCAN_THREADS), red_v, red_i, tid, SM_SCAN_THREADS / 64);
+  if (tid == 0) part[row * SM_MAX_SLICES + s] = b;
+}
+
+// ---- launch 2 ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long key_of(float z, int i) {
+  const unsigned u = __float_as_uint(z);
+  const unsigned k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)k << 20) | (SM_IDX_MASK - (unsigned long long)i);
+}
+
+__device__ __forceinline__ unsigned long long mass_of(float z, float zmax) {
+  const float e = expf(z - zmax) * 0x1p32f;
+  return e >= 0.f ? (unsigned long long)floorf(e) : 0ull;            // (a NaN, from z = z_max = +inf, carries no mass)
+}
+
+struct Lds {
+  float* z;                       // the row as z (rows of at most SM_LDS_ROW entries), else unused
+  unsigned long long* hm;         // [SM_BINS] mass per digit
+  unsigned* hc;                   // [SM_BINS] count per digit
+  unsigned long long* wt;         // [2][SM_WAVES] wave totals of the two scans
+  unsigned long long* found;      // [6] digit, count before, mass before, count in, mass in, key
+  float* red_v;                   // [SM_WAVES]
+  int* red_i;                     // [SM_WAVES]
+};
+
+struct RowSrc {
+  const float* g;                 // logits row in memory
+  const float* z;                 // LDS copy (z), or nullptr
+};
+
+__device__ __forceinline__ float4 load_z4(const RowSrc& r, int i, const RowCfg& c) {
+  if (r.z) return *reinterpret_cast<const float4*>(r.z + i);
+  const float4 l = *reinterpret_cast<const float4*>(r.g + i);
+  return make_float4(z_of(l.x, c), z_of(l.y, c), z_of(l.z, c), z_of(l.w, c));
+}
+
+__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, const Lds& L, int tid) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the last shuffle has landed: nothing of this wave is in flight at the barrier
+  __syncthreads();                                                 // (L.wt may still be read by the previous reduction)
+  if ((tid & 63) == 0) L.wt[tid >> 6] = v;
+  __syncthreads();
+  unsigned long long s = 0;
+  for (int w = 0; w < SM_WAVES; ++w) s += L.wt[w];
+  return s;
+}
+
+// The cut of the shortest prefix (among tokens with key >= lb) whose count (by_mass = false) or mass (true) reaches `need` (>= 1, at most
+// the total).  Returns the cut key; *cnt / *mass = the prefix's count and mass (the cut token included).
+__device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c, float zmax, unsigned long long lb, bool by_mass,
+                                         unsigned long long need, const Lds& L, int tid, unsigned long long* cnt, unsigned long long* mass) {
+  const int SH[SM_LEVELS] = {41, 30, 20, 10, 0}, WD[SM_LEVELS] = {11, 11, 10, 10, 10};
+  unsigned long long prefix = 0, acc_c = 0, acc_m = 0;
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int level = 0; level < SM_LEVELS; ++level) {
+    const int sh = SH[level], up = SH[level] + WD[level];
+    const unsigned dmask = (1u << WD[level]) - 1u;
+    __syncthreads();
+    for (int b = tid; b < SM_BINS; b += SM_THREADS) { L.hc[b] = 0u; L.hm[b] = 0ull; }
+    if (tid == 0) { L.found[0] = 0; L.found[1] = 0; L.found[2] = 0; L.found[3] = 0; L.found[4] = 0; }
+    __syncthreads();
+    for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
+      const float4 z4 = load_z4(r, i, c);
+      const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const unsigned long long k = key_of(zv[e], i + e);
+        if (k >= lb && (level == 0 || (k >> up) == (prefix >> up))) {
+          const unsigned d = (unsigned)(k >> sh) & dmask;
+          atomicAdd(&L.hc[d], 1u);
+          atomicAdd(&L.hm[d], mass_of(zv[e], zmax));
+        }
+      }
+    }
+    __syncthreads();
+    // thread t owns digits 2047 - 2t (first in the order) and 2046 - 2t; exclusive scans of count and mass in that order
+    const int bh = SM_BINS - 1 - 2 * tid, bl = bh - 1;
+    const unsigned long long ch = L.hc[bh], cl = L.hc[bl], mh = L.hm[bh], ml = L.hm[bl];
+    unsigned long long sc = ch + cl, sm = mh + ml;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned long long uc = __shfl_up(sc, o), um = __shfl_up(sm, o);
+      if (lane >= o) { sc += uc; sm += um; }
+    }
+    if (lane == 63) { L.wt[wave] = sc; L.wt[SM_WAVES + wave] = sm; }
+    __syncthreads();
+    unsigned long long oc = 0, om = 0;
+    for (int w = 0; w < wave; ++w) { oc += L.wt[w]; om += L.wt[SM_WAVES + w]; }
+    const unsigned long long ec = sc - (ch + cl) + oc, em = sm - (mh + ml) + om;        // before digit bh
+    const unsigned long long before = by_mass ? em : ec, vh = by_mass ? mh : ch, vl = by_mass ? ml : cl;
+    if (before < need && need <= before + vh) {
+      L.found[0] = (unsigned long long)bh; L.found[1] = ec; L.found[2] = em; L.found[3] = ch; L.found[4] = mh;
+    } else if (before + vh < need && need <= before + vh + vl) {
+      L.found[0] = (unsigned long long)bl; L.found[1] = ec + ch; L.found[2] = em + mh; L.found[3] = cl; L.found[4] = ml;
+    }
+    __syncthreads();
+    const unsigned long long d = L.found[0], in_c = L.found[3], in_m = L.found[4];
+    acc_c += L.found[1];
+    acc_m += L.found[2];
+    need -= by_mass ? L.found[2] : L.found[1];
+    prefix |= d << sh;
+    if (level == SM_LEVELS - 1 || in_c <= 1) {
+      acc_c += in_c;
+      acc_m += in_m;
+      if (level < SM_LEVELS - 1 && in_c == 1) {                  // the digit holds one token: read its key instead of descending
+        __syncthreads();
+        for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
+          const float4 z4 = load_z4(r, i, c);
+          const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const unsigned long long k = key_of(zv[e], i + e);
+            if (k >= lb && (k >> sh) == (prefix >> sh)) L.found[5] = k;
+          }
+        }
+        __syncthreads();
+        prefix = L.found[5];
+      }
+      break;
+    }
+  }
+  *cnt = acc_c;
+  *mass = acc_m;
+  return prefix;
+}
+
+__global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
+                                                                   const int* __restrict__ pos, int cache_len,
+                                                                   const mq_sample_row* __restrict__ params, const Best* __restrict__ part,
+                                                                   long long* __restrict__ tok, int* __restrict__ kept, float* __restrict__ logprob) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  int n;
+  if (row_idle(pos, row, cache_len, &n)) return;                      // workgroup-uniform: an idle row keeps its token
+  const RowCfg c = row_cfg(params[row], n, V);
+  Lds L;
+  L.z = reinterpret_cast<float*>(smem);
+  L.hm = reinterpret_cast<unsigned long long*>(smem + (size_t)lds_row * 4);
+  L.found = L.hm + SM_BINS;
+  L.wt = L.found + 8;
+  L.hc = reinterpret_cast<unsigned*>(L.wt + 2 * SM_WAVES);
+  L.red_v = reinterpret_cast<float*>(L.hc + SM_BINS);
+  L.red_i = reinterpret_cast<int*>(L.red_v + SM_WAVES);
+  RowSrc r{logits + (long long)row * stride, nullptr};
+  const float NEG_INF = -__builtin_inff();
+  const bool want_mass = logprob != nullptr;
+
+  if (!c.filtered && !want_mass) {                                  // merge launch 1's partials in slice order (one slice: scan here)
+    Best b{NEG_INF, INT_MAX};
+    if (S > 1) {
+      if (tid < S) b = part[row * SM_MAX_SLICES + tid];
+      b = block_best(b, L.red_v, L.red_i, tid, SM_WAVES);
+    } else {
+      b = block_best(scan_range(r.g, 0, V, c, tid, SM_THREADS), L.red_v, L.red_i, tid, SM_WAVES);
+    }
+    if (tid == 0) {
+      tok[row] = b.i == INT_MAX ? 0 : b.i;
+      if (kept) kept[row] = c.greedy ? 1 : V;
+    }
+    return;
+  }
+
+  // stage the row as z; its maximum
+  Best zb{NEG_INF, INT_MAX};
+  for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
+    const float4 z4 = load_z4(r, i, c);
+    if (lds_row) *reinterpret_cast<float4*>(L.z + i) = z4;
+    const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (better(zv[e], i + e, zb.v, zb.i)) { zb.v = zv[e]; zb.i = i + e; }
+  }
+  if (lds_row) r.z = L.z;
+  zb = block_best(zb, L.red_v, L.red_i, tid, SM_WAVES);
+  const float zmax = zb.v;
+  if (zmax == NEG_INF || c.greedy) {                                  // nothing to draw from (token 0), or greedy with a log-probability asked for
+    if (tid == 0) {
+      tok[row] = zmax == NEG_INF ? 0 : zb.i;
+      if (kept) kept[row] = zmax == NEG_INF ? 0 : 1;
+      if (logprob) logprob[row] = 0.f;
+    }
+    return;
+  }
+
+  unsigned long long cut = 0, cnt = (unsigned long long)V, wk = 0;
+  const bool use_k = c.top_k > 0 && c.top_k < V;
+  if (use_k) {
+    cut = select_cut(r, V, c, zmax, 0ull, false, (unsigned long long)c.top_k, L, tid, &cnt, &wk);
+  } else if (c.top_p < 1.f) {
+    unsigned long long m = 0;
+    for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
+      const float4 z4 = load_z4(r, i, c);
+      m += mass_of(z4.x, zmax) + mass_of(z4.y, zmax) + mass_of(z4.z, zmax) + mass_of(z4.w, zmax);
+    }
+    wk = block_sum_u64(m, L, tid);
+  }
+  if (c.top_p < 1.f) {
+    unsigned long long need = (unsigned long long)ceil((double)c.top_p * (double)wk);
+    need = need < 1ull ? 1ull : (need > wk ? wk : need);
+    unsigned long long pm;
+    cut = select_cut(r, V, c, zmax, cut, true, need, L, tid, &cnt, &pm);
+  }
+
+  // the draw: argmax of z + g over key >= cut with the min-p test; |C| and its mass on the way
+  const float lmin = c.min_p > 0.f ? logf(c.min_p) : NEG_INF;
+  Best b{NEG_INF, INT_MAX};
+  unsigned long long nkept = 0, wc = 0;
+  for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
+    const float4 z4 = load_z4(r, i, c);
+    const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
+    bool in[4], any = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      in[e] = key_of(zv[e], i + e) >= cut && (zv[e] - zmax >= lmin || i + e == zb.i);
+      any = any || in[e];
+    }
+    if (!any) continue;
+    unsigned rr[4];
+    philox4x32_10(c.n, (unsigned)(i >> 2), c.s0, c.s1, c.k0, c.k1, rr);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (in[e]) {
+        const float s = zv[e] + gumbel_of(rr[e]);
+        if (better(s, i + e, b.v, b.i)) { b.v = s; b.i = i + e; }
+        nkept += 1;
+        if (want_mass) wc += mass_of(zv[e], zmax);
+      }
+  }
+  b = block_best(b, L.red_v, L.red_i, tid, SM_WAVES);
+  if (kept) nkept = block_sum_u64(nkept, L, tid);
+  if (want_mass) wc = block_sum_u64(wc, L, tid);
+  if (tid == 0) {
+    const int t = b.i == INT_MAX ? zb.i : b.i;
+    tok[row] = t;
+    if (kept) kept[row] = (int)nkept;
+    if (logprob) {
+      const float zt = r.z ? r.z[t] : z_of(r.g[t], c);
+      logprob[row] = (float)((double)(zt - zmax) - (log((double)wc) - 32.0 * 0.693147180559945309417));
+    }
+  }
+}
+
+__global__ void sample_uniforms_kernel(unsigned long long seed, unsigned long long stream, unsigned n, long long first, long long count,
+                                       float* __restrict__ out) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  const long long i = first + j;
+  unsigned r[4];
+  philox4x32_10(n, (unsigned)(i >> 2), (unsigned)stream, (unsigned)(stream >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+  out[j] = uniform_of(r[i & 3]);
+}
+
+size_t select_lds_bytes(int lds_row) {
+  return (size_t)lds_row * 4 + (size_t)SM_BINS * 8 + 8 * 8 + 2 * SM_WAVES * 8 + (size_t)SM_BINS * 4 + 2 * SM_WAVES * 4;
+}
+
+PerDeviceOnce g_lds_set;
+
+}  // namespace
+}  // namespace mq
+
+using namespace mq;
+
+extern "C" {
+
+int mq_sample(const mq_sample_args* a, mq_stream_t stream) {
+  MQ_REQUIRE(a != nullptr, "mq_sample: null argument block");
+  MQ_REQUIRE(a->logits && a->pos && a->params && a->tok && a->scratch,
+             "mq_sample: null pointer (logits, pos, params, tok and scratch are required; kept and logprob are optional)");
+  MQ_REQUIRE(a->rows >= 1 && a->rows <= MQ_DECODE_MAX_BATCH, "mq_sample: rows=%d outside 1..%d", a->rows, MQ_DECODE_MAX_BATCH);
+  MQ_REQUIRE(a->V >= 4 && a->V % 4 == 0 && a->V <= (1 << 20), "mq_sample: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)a->V);
+  MQ_REQUIRE(a->logits_stride >= a->V && a->logits_stride % 4 == 0, "mq_sample: logits_stride=%lld must be >= V and a multiple of 4",
+             (long long)a->logits_stride);
+  MQ_REQUIRE(a->cache_len >= 1, "mq_sample: cache_len=%d must be >= 1 (a row with pos outside [0, cache_len) is idle)", a->cache_len);
+  MQ_REQUIRE(aligned(a->logits, 16) && aligned(a->params, 16) && aligned(a->scratch, 16), "mq_sample: logits, params and scratch must be 16-byte aligned");
+  MQ_REQUIRE(aligned(a->tok, 8) && aligned(a->pos, 4) && aligned(a->kept, 4) && aligned(a->logprob, 4), "mq_sample: tok must be 8-byte, pos / kept / logprob 4-byte aligned");
+  MQ_REQUIRE(a->scratch_bytes >= MQ_SAMPLE_SCRATCH_BYTES, "mq_sample: scratch_bytes=%lld below MQ_SAMPLE_SCRATCH_BYTES", (long long)a->scratch_bytes);
+  static_assert(MQ_SAMPLE_SCRATCH_BYTES >= MQ_DECODE_MAX_BATCH * SM_MAX_SLICES * sizeof(Best), "scratch holds every row's partials");
+  static_assert(sizeof(mq_sample_row) == 32, "mq_sample_row is 32 bytes");
+  const int V = (int)a->V;
+  const int S = min(SM_MAX_SLICES, (V + SM_SLICE - 1) / SM_SLICE);
+  const int lds_row = V <= SM_LDS_ROW ? V : 0;
+  const size_t lds = select_lds_bytes(lds_row);
+  const int dev = current_device();
+  if (!g_lds_set.done(dev)) {
+    MQ_REQUIRE(hipFuncSetAttribute((const void*)sample_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_LDS_ROW)) == hipSuccess,
+               "mq_sample: hipFuncSetAttribute(%zu B LDS) failed", select_lds_bytes(SM_LDS_ROW));
+    g_lds_set.mark(dev);
+  }
+  hipStream_t st = as_stream(stream);
+  Best* part = static_cast<Best*>(a->scratch);
+  if (S > 1) {
+    sample_scan_kernel<<<dim3((unsigned)S, (unsigned)a->rows), SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len,
+                                                                                        a->params, part);
+    MQ_LAUNCH_CHECK("mq_sample");
+  }
+  sample_select_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len, a->params,
+                                                                  part, reinterpret_cast<long long*>(a->tok), a->kept, a->logprob);
+  MQ_LAUNCH_CHECK("mq_sample");
+  return MQ_OK;
+}
+
+int mq_sample_uniforms(uint64_t seed, uint64_t stream_id, uint32_t n, int64_t first, int64_t count, float* out, mq_stream_t stream) {
+  MQ_REQUIRE(out != nullptr, "mq_sample_uniforms: null pointer");
+  MQ_REQUIRE(first >= 0 && count >= 1 && count <= (1 << 24) && first + count <= ((int64_t)1 << 34), "mq_sample_uniforms: first=%lld count=%lld outside first >= 0, 1 <= count <= 2^24, first + count <= 2^34",
+             (long long)first, (long long)count);
+  sample_uniforms_kernel<<<(unsigned)((count + 255) / 256), 256, 0, as_stream(stream)>>>(seed, stream_id, n, (long long)first, (long long)count, out);
+  MQ_LAUNCH_CHECK("mq_sample_uniforms");
+  return MQ_OK;
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@ from . import _lib, ops
 from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
                    MqDecodeGemvGroupedArgs, MqDecodeHeadBatchArgs, MqGrid)
 from .quantization import qmodule as Q
+from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
 
 
 def _grid(q: Optional[Q.Quantizer], keep: list) -> MqGrid:
@@ -332,6 +333,8 @@ class DecodeEngine:
         self.spec_stats = None
         self.graph = None
         self.graph_long = None
+        self._sampler = None                                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
+        self._sample_graphs = {}                             # step variant -> the captured sample + step graph, recorded on first use
         self._lower()
 
     @classmethod
@@ -848,6 +851,7 @@ class DecodeEngine:
         if self._keep.stale():
             self._lower()
         self._row_graphs = {}                                    # (multi-token steps: one graph per row count, recorded on first use)
+        self._sample_graphs = {}                                 # (sample + step: one graph per step variant, recorded on first use)
         tok0, pos0, hp0 = self.tok.clone(), self.pos.clone(), self._host_pos
         graphs = []
         for phases, splits in self._variants():
@@ -935,6 +939,66 @@ class DecodeEngine:
         self._host_pos += 1
         return self.logits
 
+    # -- seeded token selection on the device (csrc/mq_sample.hip) ---------------------------------------------
+    def set_sampling(self, sampling: SamplingParams, stream: int = 0):
+        """The request sample() serves from now on: rewritten in device memory, the captured graphs stay valid."""
+        if not isinstance(sampling, SamplingParams):
+            raise TypeError(f"DecodeEngine.set_sampling: expected SamplingParams, got {type(sampling).__name__}")
+        if self._sampler is None:
+            self._sampler = SampleLaunch(self.logits, self.pos, self.tok, self.cache_len)
+        self._sampler.set_rows([sampling], [check_stream(stream)])
+        return self
+
+    @torch.no_grad()
+    def sample(self) -> torch.Tensor:
+        """mq_sample on self.logits into self.tok (a device tensor; no host read): token n = position() of the sequence under the
+        request of set_sampling (greedy until one is set).  step() with no argument then consumes it."""
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        with torch.cuda.device(self.dev):
+            self._sampler.launch()
+        return self.tok
+
+    def _capture_sample_step(self, variant: int):
+        """Record mq_sample followed by the step (and the position advance) as one graph: the embedding launch reads the token the
+        sample launch of the same replay wrote, and the sample launch reads the position in front of the step.  The launch outside
+        the capture (the kernel's LDS ceiling) runs with the position at the cache_len sentinel: the row is idle, the token stays."""
+        phases, splits = self._variants()[variant]
+        self._set_splits(phases, splits)
+        pos0 = self.pos.clone()
+        self.pos.fill_(self.cache_len)
+        with torch.cuda.device(self.dev):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._sampler.launch()
+            torch.cuda.current_stream().wait_stream(side)
+            self.pos.copy_(pos0)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._sampler.launch()
+                self._launch(phases)
+                self.pos.add_(1)
+        self._set_splits(*self._variants()[0])
+        self._sample_graphs[variant] = g
+        return g
+
+    @torch.no_grad()
+    def sample_step(self) -> torch.Tensor:
+        """sample() and step() on the drawn token.  After capture(): ONE graph replay (recorded on first use, per step variant); the
+        uncaptured launches give the same token and the same logits.  self.tok holds the drawn token, self.logits the next row."""
+        if self._host_pos >= self.cache_len:
+            raise RuntimeError(f"DecodeEngine.sample_step: the KV cache is full ({self.cache_len} positions); reset() or build a longer cache")
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        if self.graph is None:
+            self.sample()
+            return self.step()
+        v = self._variant_at(self._host_pos)
+        (self._sample_graphs.get(v) or self._capture_sample_step(v)).replay()
+        self._host_pos += 1
+        return self.logits
+
     @torch.no_grad()
     def prefill(self, context_ids) -> torch.Tensor:
         """Context encoding in ONE forward over the whole context (sim_model.py:176-193) instead of len(context) steps: the module
@@ -958,14 +1022,22 @@ class DecodeEngine:
     @torch.no_grad()
     def generate(self, context_ids, max_new_tokens: int, eos_token_id=None, prefill: bool = True, do_sample: bool = False,
                  temperature: float = 0.5, generator: Optional[torch.Generator] = None,
-                 draft: Union[None, "DecodeEngine", Callable[[List[int], int], List[int]]] = None, num_draft: int = 4):
+                 draft: Union[None, "DecodeEngine", Callable[[List[int], int], List[int]]] = None, num_draft: int = 4,
+                 sampling: Optional[SamplingParams] = None, stream: int = 0):
         """SimModel.generate (mobilellm/model/sim_model.py:160-221): context encoding in one prefill forward (prefill=False: token by
         token through the step kernels), then per new token: next = argmax(logits) or, with do_sample, multinomial(softmax(logits /
         temperature)) (:198-201) -- on the device, into self.tok --, append it, stop if it is an EOS (:202-204), else run the step.
         The host reads one token id per step only to test for EOS and to return the ids.
         draft (greedy only): speculative generation -- another DecodeEngine over a model of the same vocabulary size, or a callable
         draft(ids, k) -> at most k proposals (prompt_lookup_draft) -- verified num_draft tokens at a time with step_tokens.  The
-        returned ids equal the plain greedy ones token for token; self.spec_stats counts the rounds (_generate_speculative)."""
+        returned ids equal the plain greedy ones token for token; self.spec_stats counts the rounds (_generate_speculative).
+        sampling (with stream, the sequence's identity): seeded selection on the device by mq_sample's rule (temperature, top-k, top-p,
+        min-p) -- the ids depend on (context, sampling, stream) only: BatchDecodeEngine.generate returns the same ids
+        for this sequence in any batch and slot.  After capture() a token costs one graph replay (sample + step) and one token
+        read-back; a sequence that ends on an EOS has then cached that token too (position() is one past the returned ids)."""
+        if sampling is not None:
+            validate_generate_args("DecodeEngine.generate", sampling, do_sample, draft)
+            return self._generate_sampled(context_ids, max_new_tokens, eos_token_id, prefill, sampling, stream)
         if draft is not None:
             if do_sample:
                 raise ValueError("DecodeEngine.generate: a draft is for greedy decoding only (do_sample=True with a draft)")
@@ -993,6 +1065,24 @@ class DecodeEngine:
             if self._host_pos >= self.cache_len:
                 break
             self.step()
+        return out
+
+    def _generate_sampled(self, context_ids, max_new_tokens: int, eos_token_id, prefill: bool, sampling: SamplingParams, stream: int):
+        ids = [int(t) for t in context_ids]
+        assert len(ids) + max_new_tokens <= self.cache_len
+        self.set_sampling(sampling, stream)
+        self._start_sequence(ids, prefill)
+        out = list(ids)
+        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        for made in range(1, max_new_tokens + 1):
+            if made < max_new_tokens:
+                self.sample_step()                                 # token n from the logits of n - 1, and the step on it
+            else:
+                self.sample()                                      # the last token needs no step
+            nxt = int(self.tok.item())
+            out.append(nxt)
+            if nxt in eos:
+                break
         return out
 
     def _start_sequence(self, ids: List[int], prefill: bool):

@@ -22,6 +22,7 @@ from . import _lib
 from ._lib import MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs, MqDecodeHeadBatchArgs
 from .decode import DecodeEngine, _grid, _grouped_args, _Keep, _Linear
 from .quantization import qmodule as Q
+from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
 
 MAX_BATCH = 8
 
@@ -74,6 +75,8 @@ class BatchDecodeEngine:
         self._host_pos = [self.cache_len] * B
         self._active = [False] * B
         self.graph = None
+        self._sampler = None                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
+        self._sample_graph = None            # the captured sample + step graph, recorded on first use after capture()
         self._lower()
 
     # -- lowering ----------------------------------------------------------------------------------------------------------
@@ -226,7 +229,68 @@ class BatchDecodeEngine:
                 self._advance()
         self.pos.copy_(pos0)
         self.graph = g
+        self._sample_graph = None
         return self
+
+    # -- seeded token selection on the device (csrc/mq_sample.hip) ---------------------------------------------
+    def set_sampling(self, sampling, streams: Optional[Sequence[int]] = None):
+        """Per-slot requests for sample(): one SamplingParams for every slot or one per slot; streams (the sequences' identities)
+        default to the slot numbers.  Rewritten in device memory: the captured graphs stay valid."""
+        rows = [sampling] * self.batch if isinstance(sampling, SamplingParams) else list(sampling)
+        st = list(range(self.batch)) if streams is None else [check_stream(v) for v in streams]
+        if len(rows) != self.batch or len(st) != self.batch:
+            raise ValueError(f"BatchDecodeEngine.set_sampling: {len(rows)} requests / {len(st)} streams for {self.batch} slots")
+        if self._sampler is None:
+            self._sampler = SampleLaunch(self.logits, self.pos, self.tok, self.cache_len)
+        self._sampler.set_rows(rows, st)
+        return self
+
+    @torch.no_grad()
+    def sample(self) -> torch.Tensor:
+        """mq_sample on the logits rows into tok [B] (device; no host read).  An idle slot keeps its token.  Slot b's token is what
+        DecodeEngine.sample draws for that sequence alone under the same request and stream."""
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        with torch.cuda.device(self.dev):
+            self._sampler.launch()
+        return self.tok
+
+    def _capture_sample_step(self):
+        """mq_sample + the step for all slots + the position advance as one graph (BatchDecodeEngine.capture's recipe: the launch
+        outside the capture runs with every slot idle)."""
+        pos0 = self.pos.clone()
+        self.pos.fill_(self.cache_len)
+        with torch.cuda.device(self.dev):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._sampler.launch()
+            torch.cuda.current_stream().wait_stream(side)
+            self.pos.copy_(pos0)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._sampler.launch()
+                self._launch()
+                self._advance()
+        self._sample_graph = g
+        return g
+
+    @torch.no_grad()
+    def sample_step(self) -> torch.Tensor:
+        """sample() and step() on the drawn tokens; after capture() ONE graph replay (recorded on first use)."""
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        if self.graph is None:
+            self.sample()
+            return self.step()
+        for b in range(self.batch):
+            if self._active[b] and self._host_pos[b] >= self.cache_len:
+                raise RuntimeError(f"BatchDecodeEngine.sample_step: slot {b}'s KV cache is full ({self.cache_len} positions); release() it first")
+        (self._sample_graph or self._capture_sample_step()).replay()
+        for b in range(self.batch):
+            if self._active[b]:
+                self._host_pos[b] += 1
+        return self.logits
 
     def position(self, slot: int) -> int:
         """Cached positions of the slot's sequence (what the next step appends at); cache_len for an idle slot."""
@@ -326,14 +390,31 @@ class BatchDecodeEngine:
 
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_token_id=None, do_sample: bool = False,
-                 temperature: float = 0.5, generator: Optional[torch.Generator] = None) -> List[List[int]]:
+                 temperature: float = 0.5, generator: Optional[torch.Generator] = None, sampling=None,
+                 streams: Optional[Sequence[int]] = None) -> List[List[int]]:
         """DecodeEngine.generate for up to `batch` prompts at once, each in its own slot: prompt i's list is what DecodeEngine.generate
         returns for it alone (context + new tokens).  Per step the next tokens are chosen on the device (argmax, or multinomial of
         softmax(logits / temperature) per row); the host reads the B token ids.  A sequence stops at its own EOS, after max_new_tokens
-        or at the cache end, and its slot is released."""
+        or at the cache end, and its slot is released.
+        sampling (one SamplingParams, or one per prompt) with streams (default: the prompt's index in `prompts`): seeded selection by
+        mq_sample's rule.  Prompt i's list is then what DecodeEngine.generate(prompts[i], sampling=..., stream=
+        streams[i]) returns, bit for bit, whatever the batch, the slot and the other prompts are.  After capture() a step costs one
+        graph replay (sample + step) and one read-back of the B tokens."""
         n = len(prompts)
         if not 0 < n <= self.batch:
             raise ValueError(f"BatchDecodeEngine.generate: {n} prompts for {self.batch} slots")
+        if sampling is not None:
+            validate_generate_args("BatchDecodeEngine.generate", sampling, do_sample)
+            rows = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
+            st = list(range(n)) if streams is None else [check_stream(v) for v in streams]
+            if len(rows) != n or len(st) != n:
+                raise ValueError(f"BatchDecodeEngine.generate: {len(rows)} SamplingParams / {len(st)} streams for {n} prompts")
+            if any(not isinstance(r, SamplingParams) for r in rows):
+                raise TypeError("BatchDecodeEngine.generate: sampling must be SamplingParams or a sequence of them")
+            if any(len(p) + max_new_tokens > self.cache_len for p in prompts):
+                raise ValueError(f"BatchDecodeEngine.generate: a prompt plus {max_new_tokens} new tokens exceeds the cache ({self.cache_len} positions)")
+        elif streams is not None:
+            raise ValueError("BatchDecodeEngine.generate: streams= belongs to sampling=")
         prompts = [[int(t) for t in p] for p in prompts]
         assert all(len(p) > 0 for p in prompts)
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
@@ -353,6 +434,22 @@ class BatchDecodeEngine:
         outs = [list(p) for p in prompts]
         made = [0] * n
         live = list(range(n))
+        if sampling is not None:
+            idle = SamplingParams(temperature=0.0)
+            self.set_sampling(rows + [idle] * (self.batch - n), st + [0] * (self.batch - n))
+            while live:
+                if all(made[i] + 1 >= max_new_tokens for i in live):
+                    self.sample()                                  # the last tokens need no step
+                else:
+                    self.sample_step()
+                nxt = self.tok.tolist()
+                for i in list(live):
+                    outs[i].append(nxt[i])
+                    made[i] += 1
+                    if nxt[i] in eos or made[i] >= max_new_tokens:
+                        self.release(i)
+                        live.remove(i)
+            return outs
         while live:
             if do_sample:
                 probs = torch.softmax(self.logits / temperature, dim=-1)

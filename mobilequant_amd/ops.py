@@ -1031,3 +1031,7 @@ def score_head(y: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
                   t.data_ptr() if t is not None else None, M, K, V, scratch.data_ptr(), nbytes, logprob.data_ptr(), lse.data_ptr(),
                   amax.data_ptr(), _stream())
     return logprob, lse, amax
+
+
+# ---- seeded token selection on the device (mq_sample): the binding lives with SamplingParams -------------------------
+from .sampling import sample, sample_uniforms  # noqa: E402,F401
