@@ -14,16 +14,22 @@ the module graph computes for that position: each logit within the tolerance the
 id and the position live in device memory: ``capture()`` records ONE hipGraph that serves every step of a generation.
 W8A8 (8-bit weights); 8-bit unsigned activation grids; 16-bit grids where the recipe puts them (norm inputs, o_proj / w2 outputs,
 qk_bmm output, pv_bmm input).
+
+The layer is lowered in one place, ``_DecodeBase``: ``_layer_images`` validates a layer and builds its norms and weight images once,
+``_lower_chain`` (five launches) and ``DecodeEngine._lower_chain4`` (four) turn them into launch records through the same per-launch
+helpers.  An engine asks for a chain with a ``_Target``: the buffers, the row count and how the attention record is wrapped.  The
+single-row chain, the T-row chain of ``step_tokens`` and ``BatchDecodeEngine``'s B-row chain are three such calls; every hipGraph is
+recorded by ``_DecodeBase._record``.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Callable, List, Optional, Sequence, Tuple, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _lib, ops
-from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
+from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
                    MqDecodeGemvGroupedArgs, MqDecodeHeadBatchArgs, MqGrid)
 from .quantization import qmodule as Q
 from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
@@ -247,9 +253,308 @@ def prompt_lookup_draft(ngram: int = 3) -> Callable[[List[int], int], List[int]]
     return draft
 
 
-class DecodeEngine:
-    MAX_ROWS = 8                         # step_tokens: tokens per multi-token step (MQ_DECODE_MAX_BATCH), lowered by the shape (max_rows)
+def _eos_set(eos_token_id) -> set:
+    """generate's eos_token_id (None, one id or several) as a set."""
+    return set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+
+
+class _Images(NamedTuple):
+    """One decoder layer as every chain over it reads it: the record fields of its two fused norms (_norm_args), o_proj's input grid and
+    the weight images (o_w: o_proj once more, sliced by head for the four-launch attention launch, else None).  Built and validated once
+    per layer and lowering (_layer_images)."""
+    layer: torch.nn.Module
+    norm1: dict
+    qkv: _Linear
+    g_o: Q.Quantizer
+    op: _Linear
+    o_w: Optional[torch.Tensor]
+    norm2: dict
+    w13: _Linear
+    w2: _Linear
+
+
+class _Target(NamedTuple):
+    """Where a layer's chain reads and writes: data, not the engine that asks.  rows None: one row, bare records; else every record is
+    wrapped for `rows` rows of these buffers (mq_decode_gemv_batch / _grouped).  attn: how the attention record is wrapped -- None
+    (bare), "batch" (a sequence per row, mq_decode_attention_batch) or "multi" (consecutive positions of one sequence,
+    mq_decode_attention_multi; v_chunked: the four-launch value layout)."""
+    x: torch.Tensor
+    qkv: torch.Tensor
+    attn_q: torch.Tensor
+    attn_part: torch.Tensor
+    attn_ticket: torch.Tensor
+    gate_q: torch.Tensor
+    k_cache: List[torch.Tensor]
+    v_cache: List[torch.Tensor]
+    nsplit: int
+    rows: Optional[int] = None
+    attn: Optional[str] = None
+    v_chunked: bool = False
+
+
+class _Chain(NamedTuple):
+    """One layer's (kind, record) launches by role, in launch order; o_proj is None where the attention launch contracts it (four launches)."""
+    qkv: tuple
+    attn: tuple
+    o_proj: Optional[tuple]
+    gate: tuple
+    w2: tuple
+
+
+class _DecodeBase:
+    """What DecodeEngine and BatchDecodeEngine both are: snapshots of one model (_lower_model), the lowering of a decoder layer to launch
+    records on a _Target (_lower_chain and its per-launch helpers) and the hipGraph recorder (_record).  The engine supplies model / shape /
+    dev / cache_len / cos / sin / pos / graph, _lower() and capture()."""
+
     LONG_FROM, LONG_SPLITS = 768, 4      # five launches: the split attention launch from LONG_FROM cached positions on
+    # mq_decode_gemv_batch / mq_decode_head_batch limits: rows * K int8 images in the GEMV launches' LDS, rows * hidden normalised floats in the head's
+    MAX_IMAGE_BYTES, MAX_HEAD_FLOATS = 128 * 1024, 32768
+
+    def _lower_model(self):
+        """What every lowering starts from, built from the model as it is now: weight images, epilogue vectors and one constants line per
+        launch (_pack) are SNAPSHOTS of the quantizers -- the kernels do not read through the module's scale / offset tensors."""
+        model, s = self.model, self.shape
+        self._keep = _Keep()
+        self.phases = []          # (kind, ctypes struct) in launch order
+        # embedding table, final norm and lm_head (fp32, unquantised: qmodule.py:843) are snapshots like every weight image: re-derived
+        # here and tracked for grids_stale()
+        self.embed = model.embed_tokens.weight.detach()
+        if s.embed_scale:                                    # normalize_embed (Gemma; hf_model.py:1555-1556): x = embed * hidden ** 0.5
+            self.embed = self.embed * (s.hidden ** 0.5)      # the same fp32 product the module graph forms per token
+        self.norm_ln = isinstance(model.norm, torch.nn.LayerNorm)
+        self.norm_w = model.norm.weight.detach().float().contiguous()
+        self.norm_b = model.norm.bias.detach().float().contiguous() if getattr(model.norm, "bias", None) is not None else None
+        self.lm_w = model.lm_head.weight.detach().float().contiguous()
+        self.lm_b = model.lm_head.bias.detach().float().contiguous() if model.lm_head.bias is not None else None
+        for w in (model.embed_tokens.weight, model.norm.weight, getattr(model.norm, "bias", None), model.lm_head.weight, model.lm_head.bias):
+            if w is not None:
+                self._keep.weights.append((w, Q._ver(w)))
+        for q in model.modules():                 # grids set from act_dict.json sit on the host until a forward moves them
+            if isinstance(q, Q.Quantizer) and q._has_grid() and q.scale.device != self.dev:
+                q.scale.data, q.offset.data = q.scale.to(self.dev), q.offset.to(self.dev)
+        self._images = []         # per layer, filled as the engine lowers it (_layer_images); the T-row chain reuses them (_lower_rows)
+
+    @property
+    def weight_bytes(self) -> int:
+        return sum(p[1]._mq_bytes for p in self.phases if hasattr(p[1], "_mq_bytes"))
+
+    @property
+    def head_bytes(self) -> int:
+        return self.lm_w.numel() * 4
+
+    def grids_stale(self) -> bool:
+        """True when a quantizer grid or a weight the engine snapshotted has been changed since (in place or replaced)."""
+        return self._keep.stale()
+
+    def refresh_grids(self):
+        """Re-derive every weight image, epilogue vector and constants line from the model's current quantizers and re-record the
+        graph(s) if there were any.  The cached keys / values stay as they are: they are indices on the OLD qk_bmm / pv_bmm input
+        grids, so after a recalibration start the sequence again (reset() / prefill())."""
+        had_graph = self.graph is not None
+        self.graph = None
+        self._lower()
+        if had_graph:
+            self.capture()
+        return self
+
+    def _sync_grids(self):
+        # checked where a sequence starts (capture / reset / prefill), not per step(): a token is 0.65 ms, the walk over ~500 grids
+        # is about as long.  A grid changed in the middle of a sequence is the caller's to announce with refresh_grids().
+        if self._keep.stale():
+            self.refresh_grids()
+
+    def _record(self, launch, append, before_capture=None):
+        """launch() followed by append() as ONE hipGraph on one stream.  launch() first runs once on a side stream outside the capture:
+        it sets the launches' LDS ceilings, which must not happen while capturing.  What that warm-up may touch (pos parked at the
+        cache_len sentinel or not, tickets, tok) and what is restored afterwards is the caller's; before_capture() runs between the
+        warm-up and the capture."""
+        with torch.cuda.device(self.dev):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                launch()
+            torch.cuda.current_stream().wait_stream(side)
+            if before_capture is not None:
+                before_capture()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                launch()
+                append()
+        return g
+
+    # -- lowering ----------------------------------------------------------------------------------------------------------
+    def _norm_args(self, norm) -> Tuple[dict, Q.Quantizer]:
+        """QRMSNorm (qmodule.py:469-530) or QLayerNorm (qmodule.py:579-640; StableLM-2) fused in front of a weight stream: the GEMV record's
+        norm fields and the grid the stream's input sits on."""
+        me = type(self).__name__
+        ln = isinstance(norm, Q.QLayerNorm)
+        if ln:
+            if norm.use_temporary_parameter or norm.weight is None:
+                raise RuntimeError(f"{me}: QLayerNorm needs its affine weight and no temporary (LET) parameters")
+        elif not isinstance(norm, Q.QRMSNorm) or norm.l2norm_as_rmsnorm or norm.bias is not None:
+            raise RuntimeError(f"{me}: QRMSNorm (plain RMS form, no bias) or QLayerNorm layers only")
+        wfq = Q._apply(norm.weight_quantizer, norm.weight.detach()).float().contiguous()
+        self._keep.append(wfq)
+        self._keep.weights.append((norm.weight, Q._ver(norm.weight)))
+        if norm.weight_quantizer is not None and norm.weight_quantizer._has_grid():
+            self._keep.sources.append((norm.weight_quantizer, norm.weight_quantizer.grid_token()))
+        f = dict(norm_w=wfq.data_ptr(), norm_in=_grid(norm.input_quantizer, self._keep), eps=float(norm.eps), layernorm=int(ln))
+        if ln and norm.bias is not None:
+            nb = norm.bias.detach().float().contiguous()
+            self._keep.append(nb)
+            f["norm_bias"] = nb.data_ptr()
+        f["a_grid"] = _grid(norm.output_quantizer, self._keep)
+        if norm.output_quantizer is None or norm.output_quantizer.qmax != 255:
+            raise RuntimeError(f"{me}: the norm feeding a linear needs an 8-bit unsigned output grid")
+        return f, norm.output_quantizer
+
+    def _layer_images(self, layer, head_sliced: bool = False) -> _Images:
+        """The layer's norms and weight images, with every check the chains rely on; appended to self._images."""
+        me, s = type(self).__name__, self.shape
+        attn, mlp = layer.self_attn, layer.mlp
+        for m in (attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj, mlp.w1, mlp.w2, mlp.w3):
+            if not isinstance(m, Q.QLinear):
+                raise RuntimeError(f"{me}: run create_sim_qmodel first")
+        norm1, g_in = self._norm_args(layer.input_layernorm)
+        qkv = _Linear([attn.q_proj, attn.k_proj, attn.v_proj], g_in)
+        # o_proj's input sits on pv_bmm's output grid (the live producer), else on its declared / own grid: the attention launch
+        # writes pv_bmm's output straight as o_proj's int8 image on that grid
+        pv_out = attn.pv_bmm.output_quantizer
+        g_o = attn.o_proj.input_quantizer if attn.o_proj.input_quantizer is not None else (
+            pv_out if Q._static_per_tensor(pv_out, 8) else attn.o_proj._input_grid)
+        if g_o is None or g_o.qmax != 255:
+            raise RuntimeError(f"{me}: o_proj needs an 8-bit unsigned input grid (pv_bmm output)")
+        op = _Linear([attn.o_proj], g_o)
+        if op.K != s.heads * s.head_dim or op.N != s.hidden:
+            raise RuntimeError(f"{me}: o_proj must map heads * head_dim -> hidden")
+        # [heads][N][D]: a head's K-slice of every row, one byte per weight whatever the stream format
+        o_w = op.byte_rows().view(op.N, s.heads, s.head_dim).permute(1, 0, 2).contiguous() if head_sliced else None
+        norm2, g_ffn = self._norm_args(layer.post_attention_layernorm)
+        w13 = _Linear([mlp.w1, mlp.w3], g_ffn, interleave=True)
+        act = mlp.act_fn
+        if not isinstance(act, (Q.QSiLU, Q.QGELU)) or (act.input_quantizer is not None and not act.input_quantizer.bypassed()):
+            raise RuntimeError(f"{me}: act_fn must be QSiLU / QGELU without an input quantizer (the reference's surgery)")
+        iq2 = mlp.w2.input_quantizer
+        if iq2 is None or iq2.qmax != 255:
+            raise RuntimeError(f"{me}: w2 needs its own 8-bit unsigned input quantizer")
+        self._images.append(_Images(layer, norm1, qkv, g_o, op, o_w, norm2, w13, _Linear([mlp.w2], iq2)))
+        return self._images[-1]
+
+    def _gemv(self, lin: _Linear, **fields) -> MqDecodeGemvArgs:
+        a = MqDecodeGemvArgs()
+        a.K, a.N = lin.K, lin.N
+        a.w = lin.w.data_ptr()
+        if not lin.grouped:                                  # (grouped: the [G, N] vectors travel in _grouped_args' block)
+            a.alpha, a.w_zp, a.col_term = lin.alpha.data_ptr(), lin.w_zp.data_ptr(), lin.col_term.data_ptr()
+        a.bias = lin.bias.data_ptr() if lin.bias is not None else None
+        a.seg_end[0] = a.seg_end[1] = lin.N
+        for k, v in fields.items():
+            setattr(a, k, v)
+        a.w4 = int(lin.w4)
+        a._mq_bytes = lin.N * lin.K // (2 if lin.w4 else 1)
+        self._keep.append(lin)
+        self._keep.sources += lin.sources
+        self._keep.weights += lin.weights
+        return a
+
+    def _pack(self, grids) -> int:
+        """mq_decode_pack_grids: the launch's static grids -> one constants line on the device (no host read-back)."""
+        arr = (MqGrid * len(grids))(*grids)
+        out = torch.zeros(64, device=self.dev)                 # one 256-byte line: every wave reads all 64 floats
+        _lib.call("mq_decode_pack_grids", arr, len(grids), out.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream)
+        self._keep.append(out)
+        return out.data_ptr()
+
+    def _finish_gemv(self, t: _Target, lin: _Linear, a: MqDecodeGemvArgs, x_stride: int, y_stride: int, gate_stride: int = 0):
+        """Pack the record's constants line and wrap it for the target: (kind, launch record).  One row: mq_decode_gemv, or
+        mq_decode_gemv_grouped at batch 1 for per-group weight grids; t.rows rows: mq_decode_gemv_batch / _grouped with the row strides."""
+        a.consts = self._pack([a.norm_in, a.a_grid, a.out_grid[0], a.out_grid[1], a.out_grid[2], a.gate_mid, a.gate_actout, a.gate_out, a.o_out])
+        if lin.grouped:
+            return "gemv_grouped", (_grouped_args(lin, a, 1, 0, 0, 0) if t.rows is None else
+                                    _grouped_args(lin, a, t.rows, x_stride, y_stride, gate_stride))
+        if t.rows is None:
+            return "gemv", a
+        b = MqDecodeGemvBatchArgs()
+        b.g, b.batch, b.x_stride, b.y_stride, b.gate_stride = a, t.rows, x_stride, y_stride, gate_stride
+        b._mq_bytes = a._mq_bytes
+        return "gemv", b
+
+    def _attention_grids(self, attn, at, g_o):
+        keep = self._keep
+        qk, pv = attn.qk_bmm, attn.pv_bmm
+        at.qk_a, at.qk_b, at.qk_out = (_grid(q, keep) for q in (qk.input_quantizer, qk.input2_quantizer, qk.output_quantizer))
+        at.pv_a, at.pv_b, at.pv_out = (_grid(q, keep) for q in (pv.input_quantizer, pv.input2_quantizer, pv.output_quantizer))
+        at.o_in = _grid(g_o, keep)
+        at.consts = self._pack([at.qk_a, at.qk_b, at.qk_out, at.pv_a, at.pv_b, at.pv_out, at.o_in])
+
+    def _qkv_launch(self, im: _Images, t: _Target, **extra):
+        """input_layernorm + q|k|v stream."""
+        attn = im.layer.self_attn
+        p = self._gemv(im.qkv, **im.norm1, x=t.x.data_ptr(), y=t.qkv.data_ptr(), **extra)
+        p.seg_end[0], p.seg_end[1] = im.qkv.rows[0], im.qkv.rows[0] + im.qkv.rows[1]
+        for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
+            p.out_grid[k] = _grid(lin.output_quantizer, self._keep)
+        return self._finish_gemv(t, im.qkv, p, self.shape.hidden, t.qkv.shape[-1])
+
+    def _attn_launches(self, li: int, im: _Images, t: _Target):
+        """RoPE / cache append / attention core into o_proj's int8 image, then o_proj + residual from that image."""
+        s, attn, qkv_n = self.shape, im.layer.self_attn, t.qkv.shape[-1]
+        at = MqDecodeAttentionArgs()
+        at.qkv, at.k_cache, at.v_cache = t.qkv.data_ptr(), t.k_cache[li].data_ptr(), t.v_cache[li].data_ptr()
+        at.cos, at.sin, at.pos = self.cos.data_ptr(), self.sin.data_ptr(), self.pos.data_ptr()
+        at.heads, at.kv_heads, at.head_dim, at.cache_len = s.heads, s.kv_heads, s.head_dim, self.cache_len
+        at.rot_dim, at.nsplit = self.cos.shape[1], t.nsplit
+        self._attention_grids(attn, at, im.g_o)
+        at.out_q, at.part, at.ticket = t.attn_q.data_ptr(), t.attn_part.data_ptr(), t.attn_ticket.data_ptr()
+        if t.attn == "batch":
+            w = MqDecodeAttentionBatchArgs()
+            w.a, w.batch, w.split_from, w.qkv_stride = at, t.rows, self.LONG_FROM, qkv_n
+        elif t.attn == "multi":
+            w = MqDecodeAttentionMultiArgs()
+            w.a, w.rows, w.split_from, w.qkv_stride, w.v_chunked = at, t.rows, self.LONG_FROM, qkv_n, int(t.v_chunked)
+        else:
+            w = at
+        p = self._gemv(im.op, xq=t.attn_q.data_ptr(), a_grid=_grid(im.g_o, self._keep), resid=t.x.data_ptr(), y=t.x.data_ptr())
+        p.out_grid[0] = _grid(attn.o_proj.output_quantizer, self._keep)
+        return ("attn_multi" if t.attn == "multi" else "attn", w), self._finish_gemv(t, im.op, p, s.heads * s.head_dim, s.hidden)
+
+    def _ffn_launches(self, im: _Images, t: _Target, resid: torch.Tensor, **extra):
+        """post_attention_layernorm + interleaved w1|w3 stream + gated activation + w2's input quantizer, then w2 from that int8 image +
+        the residual `resid`.  extra: more fields of the w1|w3 record (four launches: o_proj's epilogue in front of the norm)."""
+        s, keep, mlp = self.shape, self._keep, im.layer.mlp
+        act, iq2 = mlp.act_fn, mlp.w2.input_quantizer
+        p = self._gemv(im.w13, **im.norm2, x=t.x.data_ptr(), gate_q=t.gate_q.data_ptr(), gate_act=0 if isinstance(act, Q.QSiLU) else 1,
+                       gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
+                       gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep), **extra)
+        p.out_grid[0], p.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
+        gate = self._finish_gemv(t, im.w13, p, s.hidden, 0, s.ffn)
+        p = self._gemv(im.w2, xq=t.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=resid.data_ptr(), y=t.x.data_ptr())
+        p.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
+        return gate, self._finish_gemv(t, im.w2, p, s.ffn, s.hidden)
+
+    def _lower_chain(self, li: int, im: _Images, t: _Target) -> _Chain:
+        """Layer li as the five-launch chain on target t."""
+        qkv = self._qkv_launch(im, t)
+        at, o_proj = self._attn_launches(li, im, t)
+        return _Chain(qkv, at, o_proj, *self._ffn_launches(im, t, t.x))
+
+    def _head_batch(self, x: torch.Tensor, logits: torch.Tensor, rows: int, pos: Optional[torch.Tensor] = None) -> MqDecodeHeadBatchArgs:
+        """mq_decode_head_batch's record: final norm + lm_head over `rows` rows of x into logits.  pos (one per row): a row whose
+        position is the cache_len sentinel keeps its logits."""
+        s, hb = self.shape, MqDecodeHeadBatchArgs()
+        hb.x, hb.x_stride = x.data_ptr(), s.hidden
+        hb.norm_weight, hb.norm_bias = self.norm_w.data_ptr(), (self.norm_b.data_ptr() if self.norm_b is not None else None)
+        hb.layernorm, hb.eps = int(self.norm_ln), float(self.model.norm.eps)
+        hb.w, hb.bias = self.lm_w.data_ptr(), (self.lm_b.data_ptr() if self.lm_b is not None else None)
+        hb.K, hb.V, hb.batch = s.hidden, s.vocab, rows
+        hb.logits, hb.logits_stride = logits.data_ptr(), s.vocab
+        if pos is not None:
+            hb.pos, hb.cache_len = pos.data_ptr(), self.cache_len
+        return hb
+
+
+class DecodeEngine(_DecodeBase):
+    MAX_ROWS = 8                         # step_tokens: tokens per multi-token step (MQ_DECODE_MAX_BATCH), lowered by the shape (max_rows)
     LONG4_FROM = 1024                    # four launches: the 1024-thread attention + o_proj launch from here on (mq_decode_attention_oproj_args.threads):
                                          # 256 / 1024 threads at 256 | 512 | 1024 | 2048 positions: 1768 | 1701 | 1555 | 1331 against 1669 | 1646 | 1595 | 1482 tok/s
     # The largest cache_len each attention launch serves (csrc/mq_decode.hip, ao_max_cache / kAttnMaxCache): 160 KiB of LDS per workgroup
@@ -258,7 +563,7 @@ class DecodeEngine:
     # 32768 binds); four launches 2240 / 2368 / 2624 / 3136 at 256 threads, 8528 / 8656 / 8912 / 9424 at 1024 threads.
     LDS_BYTES = 160 * 1024
     ATTN_MAX_CACHE = 32768
-    ROW_IMAGE_BYTES, ROW_HEAD_FLOATS = 128 * 1024, 32768      # mq_decode_gemv_batch / mq_decode_head_batch limits (rows * K, rows * hidden)
+    ROW_IMAGE_BYTES, ROW_HEAD_FLOATS = _DecodeBase.MAX_IMAGE_BYTES, _DecodeBase.MAX_HEAD_FLOATS      # (the same limits, for the T rows of step_tokens)
     AO_STATIC_LDS = {256: {32: 2240, 64: 2368, 128: 2624, 256: 3136}, 1024: {32: 8528, 64: 8656, 128: 8912, 256: 9424}}
 
     @classmethod
@@ -366,173 +671,52 @@ class DecodeEngine:
         return None
 
     def _lower(self):
-        """Build the launch records from the model as it is now: weight images, epilogue vectors and one constants line per launch
-        (_pack) are SNAPSHOTS of the quantizers -- the kernels do not read through the module's scale / offset tensors."""
-        model, dev, s = self.model, self.dev, self.shape
+        """Build the launch records from the model as it is now (_lower_model): per layer the four- or five-launch chain over the engine's
+        own single-row buffers."""
         prefetch, prefetch_delay_us = self._prefetch
-        self._keep = _Keep()
-        self.phases = []          # (kind, ctypes struct) in launch order
-        self._layer_lins = []     # per layer (q|k|v, o_proj, w1|w3, w2): the weight images the T-row phases share (_lower_rows)
-        self._rows = None         # T-row phases of step_tokens: lowered on first use, from the images above
+        self._rows = None         # T-row phases of step_tokens: lowered on first use, from the layers' images (_lower_rows)
         self._row_graphs = {}
-        # embedding table, final norm and lm_head (fp32, unquantised: qmodule.py:843) are snapshots like every weight image: re-derived
-        # here and tracked for grids_stale()
-        self.embed = model.embed_tokens.weight.detach()
-        if s.embed_scale:                                    # normalize_embed (Gemma; hf_model.py:1555-1556): x = embed * hidden ** 0.5
-            self.embed = self.embed * (s.hidden ** 0.5)      # the same fp32 product the module graph forms per token
-        self.norm_ln = isinstance(model.norm, torch.nn.LayerNorm)
-        self.norm_w = model.norm.weight.detach().float().contiguous()
-        self.norm_b = model.norm.bias.detach().float().contiguous() if getattr(model.norm, "bias", None) is not None else None
-        self.lm_w = model.lm_head.weight.detach().float().contiguous()
-        self.lm_b = model.lm_head.bias.detach().float().contiguous() if model.lm_head.bias is not None else None
-        for w in (model.embed_tokens.weight, model.norm.weight, getattr(model.norm, "bias", None), model.lm_head.weight, model.lm_head.bias):
-            if w is not None:
-                self._keep.weights.append((w, Q._ver(w)))
-        for q in model.modules():                 # grids set from act_dict.json sit on the host until a forward moves them
-            if isinstance(q, Q.Quantizer) and q._has_grid() and q.scale.device != dev:
-                q.scale.data, q.offset.data = q.scale.to(dev), q.offset.to(dev)
         self.oproj_images = []
+        self._lower_model()
+        t = _Target(self.x, self.qkv, self.attn_q, self.attn_part, self.attn_ticket, self.gate_q, self.k_cache, self.v_cache, nsplit=self.attn_splits)
         with torch.no_grad():
-            for li, layer in enumerate(model.layers):
-                (self._lower_layer4 if self.launches == 4 else self._lower_layer)(li, layer)
-        # The attention launch of layer L pulls (a share of) layer L's w1|w3 stream into the L2s with extra workgroups: it keeps 32 of
-        # 256 CUs busy and leaves the memory fabric idle, while w1|w3 is the step's biggest stream.  Measured (TinyLlama shape, context
-        # 256): share 0 / 0.5 / 0.7 / 1.0 -> 0.678 / 0.656 / 0.665 / 0.690 ms per token: the attention's own dependent loads queue
-        # behind the prefetch stream, so half of it, started 1.5 us into the launch, is the optimum.
-        if prefetch:
-            pairs = [(self.phases[i][1], self.phases[i + (1 if self.launches == 4 else 2)]) for i in range(1, len(self.phases), self.launches)]
-            for at, (kind, gate) in pairs:
-                if kind != "gemv":        # the grouped launch spreads its rows differently: its workgroups would not meet these bytes
-                    continue
-                n, per, tot = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-                _lib.call("mq_decode_gemv_geometry", ctypes.byref(gate), ctypes.byref(n), ctypes.byref(per), ctypes.byref(tot))
-                at.prefetch, at.prefetch_stride, at.prefetch_total, at.prefetch_wgs = gate.w, per.value, tot.value, n.value
-                at.prefetch_bytes_per_wg = min(per.value, int(per.value * float(prefetch)) // 1024 * 1024)
-                at.prefetch_delay = int(prefetch_delay_us * 100)
-        self.weight_bytes = sum(p[1]._mq_bytes for p in self.phases if hasattr(p[1], "_mq_bytes"))
-        self.head_bytes = self.lm_w.numel() * 4
+            for li, layer in enumerate(self.model.layers):
+                im = self._layer_images(layer, head_sliced=self.launches == 4)
+                chain = self._lower_chain4(li, im, t) if self.launches == 4 else self._lower_chain(li, im, t)
+                self.phases += [p for p in chain if p is not None]
+                # The attention launch of layer L pulls (a share of) layer L's w1|w3 stream into the L2s with extra workgroups: it keeps 32 of
+                # 256 CUs busy and leaves the memory fabric idle, while w1|w3 is the step's biggest stream.  Measured (TinyLlama shape, context
+                # 256): share 0 / 0.5 / 0.7 / 1.0 -> 0.678 / 0.656 / 0.665 / 0.690 ms per token: the attention's own dependent loads queue
+                # behind the prefetch stream, so half of it, started 1.5 us into the launch, is the optimum.
+                at, (kind, gate) = chain.attn[1], chain.gate
+                if prefetch and kind == "gemv":           # the grouped launch spreads its rows differently: its workgroups would not meet these bytes
+                    n, per, tot = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+                    _lib.call("mq_decode_gemv_geometry", ctypes.byref(gate), ctypes.byref(n), ctypes.byref(per), ctypes.byref(tot))
+                    at.prefetch, at.prefetch_stride, at.prefetch_total, at.prefetch_wgs = gate.w, per.value, tot.value, n.value
+                    at.prefetch_bytes_per_wg = min(per.value, int(per.value * float(prefetch)) // 1024 * 1024)
+                    at.prefetch_delay = int(prefetch_delay_us * 100)
 
-    def grids_stale(self) -> bool:
-        """True when a quantizer grid or a weight the engine snapshotted has been changed since (in place or replaced)."""
-        return self._keep.stale()
+    def _lower_chain4(self, li: int, im: _Images, t: _Target) -> _Chain:
+        """Layer li as four launches (csrc/mq_decode.hip: decode_attention_oproj_kernel, OPRE): the q|k|v launch also clears o_proj's sums,
+        the attention launch contracts o_proj (split-K over the heads, exact integer atomics), the w1|w3 launch starts with o_proj's
+        epilogue + residual into x_mid, and w2 adds that stream behind the attention block."""
+        s, op = self.shape, im.op
+        qkv = self._qkv_launch(im, t, zero_acc=self.o_acc.data_ptr(), zero_n=s.hidden)
+        at = self._attention_oproj(li, im)
+        gate, w2 = self._ffn_launches(im, t, self.x_mid, o_acc=self.o_acc.data_ptr(), o_alpha=op.alpha.data_ptr(), o_ct=op.col_term.data_ptr(),
+                                      o_bias=op.bias.data_ptr() if op.bias is not None else None,
+                                      o_out=_grid(im.layer.self_attn.o_proj.output_quantizer, self._keep), x_mid=self.x_mid.data_ptr())
+        return _Chain(qkv, ("attn_oproj", at), None, gate, w2)
 
-    def refresh_grids(self):
-        """Re-derive every weight image, epilogue vector and constants line from the model's current quantizers and re-record the
-        graph(s) if there were any.  The cached keys / values stay as they are: they are indices on the OLD qk_bmm / pv_bmm input
-        grids, so after a recalibration start the sequence again (reset() / prefill())."""
-        had_graph = self.graph is not None
-        self.graph = self.graph_long = None
-        self._lower()
-        if had_graph:
-            self.capture()
-        return self
-
-    def _sync_grids(self):
-        # checked where a sequence starts (capture / reset / prefill), not per step(): a token is 0.65 ms, the walk over ~500 grids
-        # is about as long.  A grid changed in the middle of a sequence is the caller's to announce with refresh_grids().
-        if self._keep.stale():
-            self.refresh_grids()
-
-    # -- lowering ----------------------------------------------------------------------------------------------------------
-    def _norm_args(self, norm, a: MqDecodeGemvArgs):
-        """QRMSNorm (qmodule.py:469-530) or QLayerNorm (qmodule.py:579-640; StableLM-2) fused in front of the weight stream."""
-        ln = isinstance(norm, Q.QLayerNorm)
-        if ln:
-            if norm.use_temporary_parameter or norm.weight is None:
-                raise RuntimeError("DecodeEngine: QLayerNorm needs its affine weight and no temporary (LET) parameters")
-        elif not isinstance(norm, Q.QRMSNorm) or norm.l2norm_as_rmsnorm or norm.bias is not None:
-            raise RuntimeError("DecodeEngine: QRMSNorm (plain RMS form, no bias) or QLayerNorm layers only")
-        wfq = Q._apply(norm.weight_quantizer, norm.weight.detach()).float().contiguous()
-        self._keep.append(wfq)
-        self._keep.weights.append((norm.weight, Q._ver(norm.weight)))
-        if norm.weight_quantizer is not None and norm.weight_quantizer._has_grid():
-            self._keep.sources.append((norm.weight_quantizer, norm.weight_quantizer.grid_token()))
-        a.norm_w, a.norm_in, a.eps = wfq.data_ptr(), _grid(norm.input_quantizer, self._keep), float(norm.eps)
-        a.layernorm = int(ln)
-        if ln and norm.bias is not None:
-            nb = norm.bias.detach().float().contiguous()
-            self._keep.append(nb)
-            a.norm_bias = nb.data_ptr()
-        a.a_grid = _grid(norm.output_quantizer, self._keep)
-        if norm.output_quantizer is None or norm.output_quantizer.qmax != 255:
-            raise RuntimeError("DecodeEngine: the norm feeding a linear needs an 8-bit unsigned output grid")
-        return norm.output_quantizer
-
-    def _gemv(self, lin: _Linear, **fields) -> MqDecodeGemvArgs:
-        a = MqDecodeGemvArgs()
-        a.K, a.N = lin.K, lin.N
-        a.w = lin.w.data_ptr()
-        if not lin.grouped:                                  # (grouped: the [G, N] vectors travel in _grouped_args' block)
-            a.alpha, a.w_zp, a.col_term = lin.alpha.data_ptr(), lin.w_zp.data_ptr(), lin.col_term.data_ptr()
-        a.bias = lin.bias.data_ptr() if lin.bias is not None else None
-        a.seg_end[0] = a.seg_end[1] = lin.N
-        for k, v in fields.items():
-            setattr(a, k, v)
-        a.w4 = int(lin.w4)
-        a._mq_bytes = lin.N * lin.K // (2 if lin.w4 else 1)
-        self._keep.append(lin)
-        self._keep.sources += lin.sources
-        self._keep.weights += lin.weights
-        return a
-
-    def _pack(self, grids) -> int:
-        """mq_decode_pack_grids: the launch's static grids -> one constants line on the device (no host read-back)."""
-        arr = (MqGrid * len(grids))(*grids)
-        out = torch.zeros(64, device=self.dev)                 # one 256-byte line: every wave reads all 64 floats
-        _lib.call("mq_decode_pack_grids", arr, len(grids), out.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream)
-        self._keep.append(out)
-        return out.data_ptr()
-
-    def _finish_gemv(self, a: MqDecodeGemvArgs) -> MqDecodeGemvArgs:
-        a.consts = self._pack([a.norm_in, a.a_grid, a.out_grid[0], a.out_grid[1], a.out_grid[2], a.gate_mid, a.gate_actout, a.gate_out, a.o_out])
-        return a
-
-    def _gemv_phase(self, lin: _Linear, a: MqDecodeGemvArgs):
-        """(kind, launch record) of a five-launch GEMV phase: mq_decode_gemv, or mq_decode_gemv_grouped at batch 1 for per-group weight grids."""
-        return ("gemv_grouped", _grouped_args(lin, a, 1, 0, 0, 0)) if lin.grouped else ("gemv", a)
-
-    def _attention_grids(self, attn, at, keep):
-        qk, pv = attn.qk_bmm, attn.pv_bmm
-        at.qk_a, at.qk_b, at.qk_out = (_grid(q, keep) for q in (qk.input_quantizer, qk.input2_quantizer, qk.output_quantizer))
-        at.pv_a, at.pv_b, at.pv_out = (_grid(q, keep) for q in (pv.input_quantizer, pv.input2_quantizer, pv.output_quantizer))
-        # o_proj's input sits on pv_bmm's output grid (the live producer), else on its declared / own grid: the attention launch
-        # writes pv_bmm's output straight as o_proj's int8 image on that grid
-        g_o = attn.o_proj.input_quantizer if attn.o_proj.input_quantizer is not None else (
-            pv.output_quantizer if Q._static_per_tensor(pv.output_quantizer, 8) else attn.o_proj._input_grid)
-        if g_o is None or g_o.qmax != 255:
-            raise RuntimeError("DecodeEngine: o_proj needs an 8-bit unsigned input grid (pv_bmm output)")
-        at.o_in = _grid(g_o, keep)
-        at.consts = self._pack([at.qk_a, at.qk_b, at.qk_out, at.pv_a, at.pv_b, at.pv_out, at.o_in])
-        return g_o
-
-    def _lower_layer4(self, li, layer):
-        """Round 6: four launches per layer (csrc/mq_decode.hip: decode_attention_oproj_kernel, OPRE)."""
-        s, keep = self.shape, self._keep
-        attn, mlp = layer.self_attn, layer.mlp
-        for m in (attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj, mlp.w1, mlp.w2, mlp.w3):
-            if not isinstance(m, Q.QLinear):
-                raise RuntimeError("DecodeEngine: run create_sim_qmodel first")
+    def _attention_oproj(self, li: int, im: _Images) -> MqDecodeAttentionOprojArgs:
+        """The four-launch chain's RoPE / cache append / attention + o_proj's contraction launch."""
+        s, keep, op, o_w = self.shape, self._keep, im.op, im.o_w
         slices, tpr = self.oproj_geom
-        # (1) input_layernorm + q|k|v stream (the five-launch chain's launch); also clears o_proj's sums
-        a = MqDecodeGemvArgs()
-        g_in = self._norm_args(layer.input_layernorm, a)
-        qkv = _Linear([attn.q_proj, attn.k_proj, attn.v_proj], g_in)
-        p1 = self._gemv(qkv, x=self.x.data_ptr(), norm_w=a.norm_w, norm_bias=a.norm_bias, layernorm=a.layernorm, norm_in=a.norm_in, eps=a.eps,
-                        a_grid=a.a_grid, y=self.qkv.data_ptr(), zero_acc=self.o_acc.data_ptr(), zero_n=s.hidden)
-        p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
-        for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
-            p1.out_grid[k] = _grid(lin.output_quantizer, keep)
-        self.phases.append(("gemv", self._finish_gemv(p1)))
-        # (2) RoPE / cache append / attention + o_proj's contraction (split-K over the heads, exact integer atomics)
         at = MqDecodeAttentionOprojArgs()
         at.qkv, at.k_cache, at.v_cache = self.qkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
         at.rope_row, at.pos = self.rope_row.data_ptr(), self.pos.data_ptr()
         at.heads, at.kv_heads, at.head_dim, at.cache_len, at.rot_dim = s.heads, s.kv_heads, s.head_dim, self.cache_len, self.cos.shape[1]
-        g_o = self._attention_grids(attn, at, keep)
-        op = _Linear([attn.o_proj], g_o)
-        if op.K != s.heads * s.head_dim or op.N != s.hidden:
-            raise RuntimeError("DecodeEngine: o_proj must map heads * head_dim -> hidden")
-        o_w = op.byte_rows().view(op.N, s.heads, s.head_dim).permute(1, 0, 2).contiguous()          # [heads][N][D]: a head's K-slice of every row
+        self._attention_grids(im.layer.self_attn, at, im.g_o)
         keep += [o_w, op]
         self.oproj_images.append((o_w, op))                   # (per layer; tests read them)
         keep.sources += op.sources
@@ -543,165 +727,29 @@ class DecodeEngine:
         ok = None not in (lgs, lgg, lgk) and (lgk > 3 or lgs + lgg >= 3 - lgk)
         at.lg_slices, at.lg_group, at.lg_kv = (lgs, lgg, lgk) if ok else (-1, 0, 0)
         at._mq_bytes = o_w.numel()
-        self.phases.append(("attn_oproj", at))
-        # (3) o_proj's epilogue + residual -> post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
-        a2 = MqDecodeGemvArgs()
-        g_ffn = self._norm_args(layer.post_attention_layernorm, a2)
-        w13 = _Linear([mlp.w1, mlp.w3], g_ffn, interleave=True)
-        act = mlp.act_fn
-        if not isinstance(act, (Q.QSiLU, Q.QGELU)) or (act.input_quantizer is not None and not act.input_quantizer.bypassed()):
-            raise RuntimeError("DecodeEngine: act_fn must be QSiLU / QGELU without an input quantizer (the reference's surgery)")
-        iq2 = mlp.w2.input_quantizer
-        if iq2 is None or iq2.qmax != 255:
-            raise RuntimeError("DecodeEngine: w2 needs its own 8-bit unsigned input quantizer")
-        p4 = self._gemv(w13, x=self.x.data_ptr(), norm_w=a2.norm_w, norm_bias=a2.norm_bias, layernorm=a2.layernorm, norm_in=a2.norm_in,
-                        eps=a2.eps, a_grid=a2.a_grid,
-                        gate_q=self.gate_q.data_ptr(), gate_act=0 if isinstance(act, Q.QSiLU) else 1,
-                        gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
-                        gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep),
-                        o_acc=self.o_acc.data_ptr(), o_alpha=op.alpha.data_ptr(), o_ct=op.col_term.data_ptr(),
-                        o_bias=op.bias.data_ptr() if op.bias is not None else None, o_out=_grid(attn.o_proj.output_quantizer, keep),
-                        x_mid=self.x_mid.data_ptr())
-        p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
-        self.phases.append(("gemv", self._finish_gemv(p4)))
-        # (4) w2 from the int8 image + residual (the stream behind the attention block)
-        w2 = _Linear([mlp.w2], iq2)
-        p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x_mid.data_ptr(), y=self.x.data_ptr())
-        p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
-        self.phases.append(("gemv", self._finish_gemv(p5)))
-        self._layer_lins.append((qkv, op, w13, w2))
-
-    def _lower_layer(self, li, layer):
-        phases = self.phases
-        s, keep = self.shape, self._keep
-        attn, mlp = layer.self_attn, layer.mlp
-        for m in (attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj, mlp.w1, mlp.w2, mlp.w3):
-            if not isinstance(m, Q.QLinear):
-                raise RuntimeError("DecodeEngine: run create_sim_qmodel first")
-        # (1) input_layernorm + q|k|v
-        a = MqDecodeGemvArgs()
-        g_in = self._norm_args(layer.input_layernorm, a)
-        qkv = _Linear([attn.q_proj, attn.k_proj, attn.v_proj], g_in)
-        p1 = self._gemv(qkv, x=self.x.data_ptr(), norm_w=a.norm_w, norm_bias=a.norm_bias, layernorm=a.layernorm, norm_in=a.norm_in, eps=a.eps,
-                        a_grid=a.a_grid, y=self.qkv.data_ptr())
-        p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
-        for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
-            p1.out_grid[k] = _grid(lin.output_quantizer, keep)
-        phases.append(self._gemv_phase(qkv, self._finish_gemv(p1)))
-        # (2) attention core
-        at = MqDecodeAttentionArgs()
-        at.qkv, at.k_cache, at.v_cache = self.qkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
-        at.cos, at.sin, at.pos = self.cos.data_ptr(), self.sin.data_ptr(), self.pos.data_ptr()
-        at.heads, at.kv_heads, at.head_dim, at.cache_len = s.heads, s.kv_heads, s.head_dim, self.cache_len
-        at.rot_dim, at.nsplit = self.cos.shape[1], self.attn_splits
-        g_o = self._attention_grids(attn, at, keep)
-        at.out_q, at.part, at.ticket = self.attn_q.data_ptr(), self.attn_part.data_ptr(), self.attn_ticket.data_ptr()
-        phases.append(("attn", at))
-        # (3) o_proj + residual from the int8 image
-        op = _Linear([attn.o_proj], g_o)
-        p3 = self._gemv(op, xq=self.attn_q.data_ptr(), a_grid=_grid(g_o, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
-        p3.out_grid[0] = _grid(attn.o_proj.output_quantizer, keep)
-        phases.append(self._gemv_phase(op, self._finish_gemv(p3)))
-        # (4) post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
-        a2 = MqDecodeGemvArgs()
-        g_ffn = self._norm_args(layer.post_attention_layernorm, a2)
-        w13 = _Linear([mlp.w1, mlp.w3], g_ffn, interleave=True)
-        act = mlp.act_fn
-        if not isinstance(act, (Q.QSiLU, Q.QGELU)) or (act.input_quantizer is not None and not act.input_quantizer.bypassed()):
-            raise RuntimeError("DecodeEngine: act_fn must be QSiLU / QGELU without an input quantizer (the reference's surgery)")
-        iq2 = mlp.w2.input_quantizer
-        if iq2 is None or iq2.qmax != 255:
-            raise RuntimeError("DecodeEngine: w2 needs its own 8-bit unsigned input quantizer")
-        p4 = self._gemv(w13, x=self.x.data_ptr(), norm_w=a2.norm_w, norm_bias=a2.norm_bias, layernorm=a2.layernorm, norm_in=a2.norm_in,
-                        eps=a2.eps, a_grid=a2.a_grid,
-                        gate_q=self.gate_q.data_ptr(), gate_act=0 if isinstance(act, Q.QSiLU) else 1,
-                        gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
-                        gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep))
-        p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
-        phases.append(self._gemv_phase(w13, self._finish_gemv(p4)))
-        # (5) w2 from the int8 image + residual
-        w2 = _Linear([mlp.w2], iq2)
-        p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
-        p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
-        phases.append(self._gemv_phase(w2, self._finish_gemv(p5)))
-        self._layer_lins.append((qkv, op, w13, w2))
+        return at
 
     # -- T-row phases (step_tokens) -----------------------------------------------------------------------------------------
     def _lower_rows(self):
-        """The launch records of a multi-token step: per layer the batched five-launch chain (mq_decode_gemv_batch / _grouped over T
-        rows, mq_decode_attention_multi over the engine's own caches in its value layout) on the weight images the single chain already
-        holds (self._layer_lins: the same _Linear objects, incl. o_proj's row image `op` that the four-launch chain keeps next to its
-        head-sliced copy), plus mq_decode_head_batch.  Row buffers of their own; the row count T is set per launch (_set_rows)."""
-        model, s, dev, keep, R = self.model, self.shape, self.dev, self._keep, self.max_rows
+        """The launch records of a multi-token step: per layer the five-launch chain over T rows (mq_decode_gemv_batch / _grouped,
+        mq_decode_attention_multi over the engine's own caches in its value layout) on the norms and weight images the single chain already
+        holds (self._images, incl. o_proj's row image `op` that the four-launch chain keeps next to its head-sliced copy), plus
+        mq_decode_head_batch.  Row buffers of their own; the row count T is set per launch (_set_rows)."""
+        s, dev, R = self.shape, self.dev, self.max_rows
         H, D = s.heads, s.head_dim
-        qkv_n = self.qkv.shape[0]
         self.rx = torch.zeros(R, s.hidden, device=dev)
-        self.rqkv = torch.zeros(R, qkv_n, device=dev)
+        self.rqkv = torch.zeros(R, self.qkv.shape[0], device=dev)
         self.rattn_q = torch.zeros(R, H * D, dtype=torch.int8, device=dev)
         self.rpart = torch.zeros(R, self.LONG_SPLITS, H * D, dtype=torch.int64, device=dev)
         self.rticket = torch.zeros(R, H, dtype=torch.int32, device=dev)
         self.rgate = torch.zeros(R, s.ffn, dtype=torch.int8, device=dev)
         self.rlogits = torch.zeros(R, s.vocab, device=dev)
         self.rtok = torch.zeros(R, dtype=torch.int64, device=dev)
-
-        def rows(lin: _Linear, a: MqDecodeGemvArgs, x_stride: int, y_stride: int, gate_stride: int = 0):
-            if lin.grouped:
-                return "gemv_grouped", _grouped_args(lin, a, R, x_stride, y_stride, gate_stride)
-            b = MqDecodeGemvBatchArgs()
-            b.g, b.batch, b.x_stride, b.y_stride, b.gate_stride = a, R, x_stride, y_stride, gate_stride
-            return "gemv", b
-
-        phases = []
+        t = _Target(self.rx, self.rqkv, self.rattn_q, self.rpart, self.rticket, self.rgate, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
+                    rows=R, attn="multi", v_chunked=self.v_transposed)
         with torch.no_grad():
-            for li, (layer, (qkv, op, w13, w2)) in enumerate(zip(model.layers, self._layer_lins)):
-                attn, mlp = layer.self_attn, layer.mlp
-                # (1) input_layernorm + q|k|v
-                a = MqDecodeGemvArgs()
-                self._norm_args(layer.input_layernorm, a)
-                p1 = self._gemv(qkv, x=self.rx.data_ptr(), norm_w=a.norm_w, norm_bias=a.norm_bias, layernorm=a.layernorm, norm_in=a.norm_in,
-                                eps=a.eps, a_grid=a.a_grid, y=self.rqkv.data_ptr())
-                p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
-                for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
-                    p1.out_grid[k] = _grid(lin.output_quantizer, keep)
-                phases.append(rows(qkv, self._finish_gemv(p1), s.hidden, qkv_n))
-                # (2) attention of the T consecutive positions, appending to the engine's caches
-                at = MqDecodeAttentionArgs()
-                at.qkv, at.k_cache, at.v_cache = self.rqkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
-                at.cos, at.sin, at.pos = self.cos.data_ptr(), self.sin.data_ptr(), self.pos.data_ptr()
-                at.heads, at.kv_heads, at.head_dim, at.cache_len = H, s.kv_heads, D, self.cache_len
-                at.rot_dim, at.nsplit = self.cos.shape[1], self.LONG_SPLITS
-                g_o = self._attention_grids(attn, at, keep)
-                at.out_q, at.part, at.ticket = self.rattn_q.data_ptr(), self.rpart.data_ptr(), self.rticket.data_ptr()
-                ma = MqDecodeAttentionMultiArgs()
-                ma.a, ma.rows, ma.split_from, ma.qkv_stride, ma.v_chunked = at, R, self.LONG_FROM, qkv_n, int(self.v_transposed)
-                phases.append(("attn_multi", ma))
-                # (3) o_proj + residual from the int8 image
-                p3 = self._gemv(op, xq=self.rattn_q.data_ptr(), a_grid=_grid(g_o, keep), resid=self.rx.data_ptr(), y=self.rx.data_ptr())
-                p3.out_grid[0] = _grid(attn.o_proj.output_quantizer, keep)
-                phases.append(rows(op, self._finish_gemv(p3), H * D, s.hidden))
-                # (4) post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
-                a2 = MqDecodeGemvArgs()
-                self._norm_args(layer.post_attention_layernorm, a2)
-                act, iq2 = mlp.act_fn, mlp.w2.input_quantizer
-                p4 = self._gemv(w13, x=self.rx.data_ptr(), norm_w=a2.norm_w, norm_bias=a2.norm_bias, layernorm=a2.layernorm, norm_in=a2.norm_in,
-                                eps=a2.eps, a_grid=a2.a_grid,
-                                gate_q=self.rgate.data_ptr(), gate_act=0 if isinstance(act, Q.QSiLU) else 1,
-                                gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
-                                gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep))
-                p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
-                phases.append(rows(w13, self._finish_gemv(p4), s.hidden, 0, s.ffn))
-                # (5) w2 from the int8 image + residual
-                p5 = self._gemv(w2, xq=self.rgate.data_ptr(), a_grid=_grid(iq2, keep), resid=self.rx.data_ptr(), y=self.rx.data_ptr())
-                p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
-                phases.append(rows(w2, self._finish_gemv(p5), s.ffn, s.hidden))
-        hb = MqDecodeHeadBatchArgs()
-        hb.x, hb.x_stride = self.rx.data_ptr(), s.hidden
-        hb.norm_weight, hb.norm_bias = self.norm_w.data_ptr(), (self.norm_b.data_ptr() if self.norm_b is not None else None)
-        hb.layernorm, hb.eps = int(self.norm_ln), float(model.norm.eps)
-        hb.w, hb.bias = self.lm_w.data_ptr(), (self.lm_b.data_ptr() if self.lm_b is not None else None)
-        hb.K, hb.V, hb.batch = s.hidden, s.vocab, R
-        hb.logits, hb.logits_stride = self.rlogits.data_ptr(), s.vocab
-        self._rows = (phases, hb)
+            phases = [p for li, im in enumerate(self._images) for p in self._lower_chain(li, im, t)]
+        self._rows = (phases, self._head_batch(self.rx, self.rlogits, R))
         self._row_graphs = {}
 
     def _set_rows(self, T: int):
@@ -734,18 +782,8 @@ class DecodeEngine:
         self._set_rows(T)
         pos0 = self.pos.clone()
         self.pos.fill_(self.cache_len)
-        with torch.cuda.device(self.dev):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._launch_rows(T)              # (sets the launches' LDS ceilings outside the capture)
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launch_rows(T)
-                self._finish_rows(T)
+        g = self._row_graphs[T] = self._record(lambda: self._launch_rows(T), lambda: self._finish_rows(T))
         self.pos.copy_(pos0)
-        self._row_graphs[T] = g
         return g
 
     @torch.no_grad()
@@ -857,17 +895,7 @@ class DecodeEngine:
         for phases, splits in self._variants():
             self._set_splits(phases, splits)
             self.attn_ticket.zero_()
-            with torch.cuda.device(self.dev):
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self._launch(phases)
-                torch.cuda.current_stream().wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._launch(phases)
-                    self.pos.add_(1)
-            graphs.append(g)
+            graphs.append(self._record(lambda: self._launch(phases), lambda: self.pos.add_(1)))
             self.tok.copy_(tok0); self.pos.copy_(pos0)
         self._set_splits(*self._variants()[0])                  # a direct launch after capture() runs the base variant again
         self._host_pos = hp0
@@ -967,20 +995,12 @@ class DecodeEngine:
         self._set_splits(phases, splits)
         pos0 = self.pos.clone()
         self.pos.fill_(self.cache_len)
-        with torch.cuda.device(self.dev):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._sampler.launch()
-            torch.cuda.current_stream().wait_stream(side)
-            self.pos.copy_(pos0)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._sampler.launch()
-                self._launch(phases)
-                self.pos.add_(1)
+
+        def step():
+            self._launch(phases)
+            self.pos.add_(1)
+        g = self._sample_graphs[variant] = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
         self._set_splits(*self._variants()[0])
-        self._sample_graphs[variant] = g
         return g
 
     @torch.no_grad()
@@ -1044,14 +1064,9 @@ class DecodeEngine:
             return self._generate_speculative(context_ids, max_new_tokens, eos_token_id, prefill, draft, num_draft)
         ids = [int(t) for t in context_ids]
         assert len(ids) + max_new_tokens <= self.cache_len
-        self.reset()
-        if prefill and len(ids) > 1:
-            self.prefill(ids)
-        else:
-            for t in ids:
-                self.step(t)
+        self._start_sequence(ids, prefill)
         out = list(ids)
-        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        eos = _eos_set(eos_token_id)
         for _ in range(max_new_tokens):
             if do_sample:
                 probs = torch.softmax(self.logits / temperature, dim=-1)
@@ -1073,7 +1088,7 @@ class DecodeEngine:
         self.set_sampling(sampling, stream)
         self._start_sequence(ids, prefill)
         out = list(ids)
-        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        eos = _eos_set(eos_token_id)
         for made in range(1, max_new_tokens + 1):
             if made < max_new_tokens:
                 self.sample_step()                                 # token n from the logits of n - 1, and the step on it
@@ -1103,7 +1118,7 @@ class DecodeEngine:
         and drops the rejected ones with rewind."""
         ids = [int(t) for t in context_ids]
         assert len(ids) + max_new_tokens <= self.cache_len
-        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        eos = _eos_set(eos_token_id)
         d_eng = draft if isinstance(draft, DecodeEngine) else None
         if d_eng is self:
             raise ValueError("DecodeEngine.generate: the draft must be another engine (it keeps its own cache)")

@@ -6,6 +6,7 @@ launches (norm + q|k|v, attention, o_proj + residual, norm + w1|w3 + gate, w2 + 
 the weights are read once per step for all slots.  The contract is per sequence: slot b of a batched step computes exactly -- bit for
 bit -- what ``DecodeEngine`` computes for that sequence alone.  A phase whose linears carry per-group weight grids
 (QuantConfig group_size) runs ``mq_decode_gemv_grouped``, the launch the single engine runs for it at B = 1.
+The layer is lowered by the code the single engine uses (``decode._DecodeBase._lower_chain``); this engine only says where the B rows live.
 
 Positions live in device memory (``pos [B]``), so ONE captured hipGraph serves every mix of slot positions: the attention launch
 chooses each sequence's split count on the device, and a slot whose position is the ``cache_len`` sentinel is idle -- its cache and
@@ -19,28 +20,17 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs, MqDecodeHeadBatchArgs
-from .decode import DecodeEngine, _grid, _grouped_args, _Keep, _Linear
-from .quantization import qmodule as Q
+from .decode import DecodeEngine, _DecodeBase, _eos_set, _Target
 from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
 
 MAX_BATCH = 8
 
 
-class BatchDecodeEngine:
+class BatchDecodeEngine(_DecodeBase):
     """B single-token decode streams over one model.  Slots are filled with prefill(slot, ids), emptied with release(slot) and all
     active slots advance together with step()."""
 
-    LONG_FROM, LONG_SPLITS = DecodeEngine.LONG_FROM, DecodeEngine.LONG_SPLITS      # per sequence, on the device
-    MAX_IMAGE_BYTES = 128 * 1024                                                   # B * K int8 images in the GEMV launches' LDS
-    MAX_HEAD_FLOATS = 32768                                                        # B * hidden normalised floats in the head's LDS
-
-    # the lowering helpers of the single-sequence engine, shared as they are (they only touch self._keep / self.dev)
-    _norm_args = DecodeEngine._norm_args
-    _gemv = DecodeEngine._gemv
-    _pack = DecodeEngine._pack
-    _finish_gemv = DecodeEngine._finish_gemv
-    _attention_grids = DecodeEngine._attention_grids
+    # LONG_FROM / LONG_SPLITS (the base's) apply per sequence, on the device; MAX_IMAGE_BYTES / MAX_HEAD_FLOATS bound B * K and B * hidden
 
     def __init__(self, model, batch: int, cache_len: int = 2048):
         from .llama import LlamaForCausalLM
@@ -79,122 +69,16 @@ class BatchDecodeEngine:
         self._sample_graph = None            # the captured sample + step graph, recorded on first use after capture()
         self._lower()
 
-    # -- lowering ----------------------------------------------------------------------------------------------------------
     def _lower(self):
-        """Launch records from the model as it is now (snapshots, as DecodeEngine._lower)."""
-        model, s = self.model, self.shape
-        self._keep = _Keep()
-        self.phases = []
-        self.embed = model.embed_tokens.weight.detach()
-        if s.embed_scale:
-            self.embed = self.embed * (s.hidden ** 0.5)
-        self.norm_ln = isinstance(model.norm, torch.nn.LayerNorm)
-        self.norm_w = model.norm.weight.detach().float().contiguous()
-        self.norm_b = model.norm.bias.detach().float().contiguous() if getattr(model.norm, "bias", None) is not None else None
-        self.lm_w = model.lm_head.weight.detach().float().contiguous()
-        self.lm_b = model.lm_head.bias.detach().float().contiguous() if model.lm_head.bias is not None else None
-        for w in (model.embed_tokens.weight, model.norm.weight, getattr(model.norm, "bias", None), model.lm_head.weight, model.lm_head.bias):
-            if w is not None:
-                self._keep.weights.append((w, Q._ver(w)))
-        for q in model.modules():
-            if isinstance(q, Q.Quantizer) and q._has_grid() and q.scale.device != self.dev:
-                q.scale.data, q.offset.data = q.scale.to(self.dev), q.offset.to(self.dev)
+        """Launch records from the model as it is now (_lower_model): per layer the five-launch chain over the B rows of the slot buffers,
+        a sequence per row."""
+        self._lower_model()
+        t = _Target(self.x, self.qkv, self.attn_q, self.attn_part, self.attn_ticket, self.gate_q, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
+                    rows=self.batch, attn="batch")
         with torch.no_grad():
-            for li, layer in enumerate(model.layers):
-                self._lower_layer(li, layer)
-        hb = MqDecodeHeadBatchArgs()
-        hb.x, hb.x_stride = self.x.data_ptr(), s.hidden
-        hb.norm_weight, hb.norm_bias = self.norm_w.data_ptr(), (self.norm_b.data_ptr() if self.norm_b is not None else None)
-        hb.layernorm, hb.eps = int(self.norm_ln), float(model.norm.eps)
-        hb.w, hb.bias = self.lm_w.data_ptr(), (self.lm_b.data_ptr() if self.lm_b is not None else None)
-        hb.K, hb.V, hb.batch = s.hidden, s.vocab, self.batch
-        hb.logits, hb.logits_stride = self.logits.data_ptr(), s.vocab
-        hb.pos, hb.cache_len = self.pos.data_ptr(), self.cache_len
-        self.head = hb
-        self.weight_bytes = sum(p[1]._mq_bytes for p in self.phases if hasattr(p[1], "_mq_bytes"))
-        self.head_bytes = self.lm_w.numel() * 4
-
-    def _batched(self, lin: _Linear, a: MqDecodeGemvArgs, x_stride: int, y_stride: int, gate_stride: int = 0):
-        """(kind, launch record) over the B slot rows: mq_decode_gemv_batch, or mq_decode_gemv_grouped for per-group weight grids."""
-        if lin.grouped:
-            return "gemv_grouped", _grouped_args(lin, a, self.batch, x_stride, y_stride, gate_stride)
-        b = MqDecodeGemvBatchArgs()
-        b.g, b.batch, b.x_stride, b.y_stride, b.gate_stride = a, self.batch, x_stride, y_stride, gate_stride
-        b._mq_bytes = a._mq_bytes
-        return "gemv", b
-
-    def _lower_layer(self, li, layer):
-        """The five launches of DecodeEngine._lower_layer, each over the B rows of the slot buffers."""
-        s, keep = self.shape, self._keep
-        attn, mlp = layer.self_attn, layer.mlp
-        for m in (attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj, mlp.w1, mlp.w2, mlp.w3):
-            if not isinstance(m, Q.QLinear):
-                raise RuntimeError("BatchDecodeEngine: run create_sim_qmodel first")
-        H, D = s.heads, s.head_dim
-        # (1) input_layernorm + q|k|v
-        a = MqDecodeGemvArgs()
-        g_in = self._norm_args(layer.input_layernorm, a)
-        qkv = _Linear([attn.q_proj, attn.k_proj, attn.v_proj], g_in)
-        p1 = self._gemv(qkv, x=self.x.data_ptr(), norm_w=a.norm_w, norm_bias=a.norm_bias, layernorm=a.layernorm, norm_in=a.norm_in, eps=a.eps,
-                        a_grid=a.a_grid, y=self.qkv.data_ptr())
-        p1.seg_end[0], p1.seg_end[1] = qkv.rows[0], qkv.rows[0] + qkv.rows[1]
-        for k, lin in enumerate((attn.q_proj, attn.k_proj, attn.v_proj)):
-            p1.out_grid[k] = _grid(lin.output_quantizer, keep)
-        self.phases.append(self._batched(qkv, self._finish_gemv(p1), s.hidden, self.qkv.shape[1]))
-        # (2) attention core, per sequence
-        at = MqDecodeAttentionArgs()
-        at.qkv, at.k_cache, at.v_cache = self.qkv.data_ptr(), self.k_cache[li].data_ptr(), self.v_cache[li].data_ptr()
-        at.cos, at.sin, at.pos = self.cos.data_ptr(), self.sin.data_ptr(), self.pos.data_ptr()
-        at.heads, at.kv_heads, at.head_dim, at.cache_len = H, s.kv_heads, D, self.cache_len
-        at.rot_dim, at.nsplit = self.cos.shape[1], self.LONG_SPLITS
-        g_o = self._attention_grids(attn, at, keep)
-        at.out_q, at.part, at.ticket = self.attn_q.data_ptr(), self.attn_part.data_ptr(), self.attn_ticket.data_ptr()
-        ab = MqDecodeAttentionBatchArgs()
-        ab.a, ab.batch, ab.split_from, ab.qkv_stride = at, self.batch, self.LONG_FROM, self.qkv.shape[1]
-        self.phases.append(("attn", ab))
-        # (3) o_proj + residual from the int8 image
-        op = _Linear([attn.o_proj], g_o)
-        p3 = self._gemv(op, xq=self.attn_q.data_ptr(), a_grid=_grid(g_o, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
-        p3.out_grid[0] = _grid(attn.o_proj.output_quantizer, keep)
-        self.phases.append(self._batched(op, self._finish_gemv(p3), H * D, s.hidden))
-        # (4) post_attention_layernorm + interleaved w1|w3 + gated activation + w2's input quantizer
-        a2 = MqDecodeGemvArgs()
-        g_ffn = self._norm_args(layer.post_attention_layernorm, a2)
-        w13 = _Linear([mlp.w1, mlp.w3], g_ffn, interleave=True)
-        act = mlp.act_fn
-        if not isinstance(act, (Q.QSiLU, Q.QGELU)) or (act.input_quantizer is not None and not act.input_quantizer.bypassed()):
-            raise RuntimeError("BatchDecodeEngine: act_fn must be QSiLU / QGELU without an input quantizer (the reference's surgery)")
-        iq2 = mlp.w2.input_quantizer
-        if iq2 is None or iq2.qmax != 255:
-            raise RuntimeError("BatchDecodeEngine: w2 needs its own 8-bit unsigned input quantizer")
-        p4 = self._gemv(w13, x=self.x.data_ptr(), norm_w=a2.norm_w, norm_bias=a2.norm_bias, layernorm=a2.layernorm, norm_in=a2.norm_in,
-                        eps=a2.eps, a_grid=a2.a_grid,
-                        gate_q=self.gate_q.data_ptr(), gate_act=0 if isinstance(act, Q.QSiLU) else 1,
-                        gate_mid=_grid(act.input2_quantizer if isinstance(act, Q.QSiLU) else None, keep),
-                        gate_actout=_grid(act.output_quantizer, keep), gate_out=_grid(iq2, keep))
-        p4.out_grid[0], p4.out_grid[1] = _grid(mlp.w1.output_quantizer, keep), _grid(mlp.w3.output_quantizer, keep)
-        self.phases.append(self._batched(w13, self._finish_gemv(p4), s.hidden, 0, s.ffn))
-        # (5) w2 from the int8 image + residual
-        w2 = _Linear([mlp.w2], iq2)
-        p5 = self._gemv(w2, xq=self.gate_q.data_ptr(), a_grid=_grid(iq2, keep), resid=self.x.data_ptr(), y=self.x.data_ptr())
-        p5.out_grid[0] = _grid(mlp.w2.output_quantizer, keep)
-        self.phases.append(self._batched(w2, self._finish_gemv(p5), s.ffn, s.hidden))
-
-    def grids_stale(self) -> bool:
-        return self._keep.stale()
-
-    def refresh_grids(self):
-        """Re-derive every launch record from the model's current quantizers (DecodeEngine.refresh_grids); re-records the graph."""
-        had_graph = self.graph is not None
-        self.graph = None
-        self._lower()
-        if had_graph:
-            self.capture()
-        return self
-
-    def _sync_grids(self):
-        if self._keep.stale():
-            self.refresh_grids()
+            for li, layer in enumerate(self.model.layers):
+                self.phases += self._lower_chain(li, self._layer_images(layer), t)
+        self.head = self._head_batch(self.x, self.logits, self.batch, pos=self.pos)
 
     # -- running -------------------------------------------------------------------------------------------------------------
     _ENTRY = {"gemv": "mq_decode_gemv_batch", "gemv_grouped": "mq_decode_gemv_grouped", "attn": "mq_decode_attention_batch"}
@@ -217,18 +101,8 @@ class BatchDecodeEngine:
         pos0 = self.pos.clone()
         self.pos.fill_(self.cache_len)            # the warm-up below runs with every slot idle: no cache or logits row changes
         self.attn_ticket.zero_()
-        with torch.cuda.device(self.dev):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._launch()                    # (sets the launches' LDS ceilings outside the capture)
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launch()
-                self._advance()
+        self.graph = self._record(self._launch, self._advance)
         self.pos.copy_(pos0)
-        self.graph = g
         self._sample_graph = None
         return self
 
@@ -260,20 +134,12 @@ class BatchDecodeEngine:
         outside the capture runs with every slot idle)."""
         pos0 = self.pos.clone()
         self.pos.fill_(self.cache_len)
-        with torch.cuda.device(self.dev):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._sampler.launch()
-            torch.cuda.current_stream().wait_stream(side)
-            self.pos.copy_(pos0)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._sampler.launch()
-                self._launch()
-                self._advance()
-        self._sample_graph = g
-        return g
+
+        def step():
+            self._launch()
+            self._advance()
+        self._sample_graph = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
+        return self._sample_graph
 
     @torch.no_grad()
     def sample_step(self) -> torch.Tensor:
@@ -417,7 +283,7 @@ class BatchDecodeEngine:
             raise ValueError("BatchDecodeEngine.generate: streams= belongs to sampling=")
         prompts = [[int(t) for t in p] for p in prompts]
         assert all(len(p) > 0 for p in prompts)
-        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        eos = _eos_set(eos_token_id)
         if max_new_tokens <= 0:
             return prompts
         for b in range(self.batch):
