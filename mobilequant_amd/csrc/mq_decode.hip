@@ -15,7 +15,7 @@
 // kernel of mq_gemv.hip (one 1024-thread workgroup per CU, all weight loads of a wave issued before anything else, DPP reductions);
 // the arithmetic of every quantizer is op for op that of the prefill kernels (mq_norm.hip, mq_elementwise.hip, mq_gemm.hip).
 // The token position is read from device memory, so one captured hipGraph serves every step of a generation.
-#include "mq_decode_common.h"
+#include "mq_decode_attention.h"
 
 namespace mq {
 
@@ -444,21 +444,14 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
 // ...).  nsplit == 1: the workgroup finishes the head.  nsplit > 1: exact int64 partial sums go to `part` with write-through
 // stores, a per-head ticket counts the splits, the last one adds the partials (integers: any order is THE sum) and finishes.
 
-// D = head_dim (compile time: every index below is a shift).  Scores: LPP lanes per cached position (4; 2 at D = 32), each with CH
-// 16-byte chunks of the key row (LPP * CH * 16 = D); 256 / LPP positions per pass, KB passes in flight.  p.v: a thread owns one dword (4 dims) of the
-// value rows of G = 1024 / D position groups; a 64-position block gives each thread PPB = D / 16 positions.
+// The phases are the MQ_ATTN_* texts of mq_decode_attention.h, shared with the batched and the multi-token launch.  This kernel's own:
+// the prefetch rows, the stamps between the phases, and its order of requests -- the q | k | v loads do not depend on the position and
+// are issued BEFORE the position's early return (request order at the top of a decode launch is not cosmetic: see
+// decode_attention_oproj_kernel's header below).
 template <int D>
 __global__ void __launch_bounds__(256) decode_attention_kernel(const mq_decode_attention_args a, unsigned long long* stamps) {
-  constexpr int LPP = D >= 64 ? 4 : 2, CH = D >= 64 ? D / 64 : 1, PPP = 256 / LPP, KB = 8 / CH;
-  constexpr int DQ = D / 4, G = 256 / DQ, PPB = 64 / G, VB = 16;
-  static_assert(PPB * G == 64 && VB % PPB == 0, "block mapping");
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* s_sc = reinterpret_cast<float*>(smem_raw);              // [cache_len] scores -> exp -> (p index - zp) as int
-  __shared__ __attribute__((aligned(16))) int8_t s_q8[D], s_k8[D], s_v8[D];
-  __shared__ float s_redf[4];
-  __shared__ int s_redq[4];
-  __shared__ long long s_acc[1024];                              // [G][D] partial p.v sums
-  __shared__ unsigned s_ticket;
+  MQ_ATTN_GEOMETRY(D);
+  MQ_ATTN_LDS(s_q8[D], s_k8[D], s_v8[D]);
   const int H = a.heads, rot = a.rot_dim, nsplit = a.nsplit;
   if ((int)blockIdx.y >= nsplit) {
     // ---- L2 prefetch role (grid rows behind the attention's): this launch keeps 32 .. 128 of 256 CUs busy and moves a few hundred
@@ -508,200 +501,34 @@ __global__ void __launch_bounds__(256) decode_attention_kernel(const mq_decode_a
   const float cs = a.cos[(size_t)pos * rot + dr], sn = a.sin[(size_t)pos * rot + dr];
   const int8_t* kc = a.k_cache + (size_t)kvh * a.cache_len * D;
   const int8_t* vc = a.v_cache + (size_t)kvh * a.cache_len * D;
-  // ---- key loads of the first batch ------------------------------------------------------------------------------------------------
-  const int sub = tid & (LPP - 1), slot = tid / LPP;
-  v4i kbuf[KB][CH];
-  auto load_keys = [&](int t0) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u) {
-      const int t = t0 + u * PPP + slot;
-      const int tc = (t < T && t != pos) ? t : 0;                   // position 0 stands in (always valid memory); masked below
-#pragma unroll
-      for (int ch = 0; ch < CH; ++ch) kbuf[u][ch] = *reinterpret_cast<const v4i*>(kc + (size_t)tc * D + (sub * CH + ch) * 16);
-    }
-  };
-  load_keys(0);
-  // ---- the value loads of this split's first blocks: thread (dq = dword of 4 dims, grp): positions 64 b + grp + G j ------------
-  const int dq = tid & (DQ - 1), grp = tid / DQ;
-  int vbuf[VB];
-  auto item_pos = [&](int i) { return 64 * (c + nsplit * (i / PPB)) + grp + G * (i % PPB); };   // PPB: a power of two (shifts)
-  auto load_values = [&](int i0) {                                   // cached positions t < pos only: the new one stays in registers
-#pragma unroll
-    for (int u = 0; u < VB; ++u) {
-      const int t = item_pos(i0 + u);
-      vbuf[u] = *reinterpret_cast<const int*>(vc + (size_t)(t < pos ? t : 0) * D + dq * 4);
-    }
-  };
+  MQ_ATTN_KEY_LOADER(t < T && t != pos);
+  MQ_ATTN_VALUE_LOADER(pos);                                       // cached positions t < pos only: the new one stays in registers
   load_values(0);
-  // ---- RoPE + the three input quantizers of the new token ---------------------------------------------------------------------------
-  const Grid qa = const_grid(cv, AG_QK_A, a.qk_a), qb = const_grid(cv, AG_QK_B, a.qk_b), qo = const_grid(cv, AG_QK_OUT, a.qk_out);
-  const Grid pa = const_grid(cv, AG_PV_A, a.pv_a), pb = const_grid(cv, AG_PV_B, a.pv_b), po = const_grid(cv, AG_PV_OUT, a.pv_out);
-  const Grid oi = const_grid(cv, AG_O_IN, a.o_in);
-  int qsum_part = 0;
-  if (tid < D) {
-    float qv = q_raw, kv = k_raw;
-    if (tid < rot) {                                               // x * cos + rot(x) * sin, rot(x)[d] = d < rot/2 ? -x[d + rot/2] : x[d - rot/2]
-      const float sg = tid < half ? -1.f : 1.f;                    // (-x) * sin == -(x * sin) exactly
-      qv = __fadd_rn(__fmul_rn(q_raw, cs), __fmul_rn(sg * q_par, sn));
-      kv = __fadd_rn(__fmul_rn(k_raw, cs), __fmul_rn(sg * k_par, sn));
-    }
-    const float iq = dq_index(qv, qa.s, qa.inv_s, qa.o, qa.qmin, qa.qmax), ik = dq_index(kv, qb.s, qb.inv_s, qb.o, qb.qmin, qb.qmax);
-    const float iv = dq_index(v_raw, pb.s, pb.inv_s, pb.o, pb.qmin, pb.qmax);
-    const int sq = (iq != iq ? 0 : (int)iq) - 128, sk = (ik != ik ? 0 : (int)ik) - 128, sv = (iv != iv ? 0 : (int)iv) - 128;
-    s_q8[tid] = (int8_t)sq;
-    s_k8[tid] = (int8_t)sk;
-    s_v8[tid] = (int8_t)sv;
-    qsum_part = sq;
-    if (c == 0 && h % (H / a.kv_heads) == 0) {                     // the group's first head appends to the cache
-      a.k_cache[((size_t)kvh * a.cache_len + pos) * D + tid] = (int8_t)sk;
-      a.v_cache[((size_t)kvh * a.cache_len + pos) * D + tid] = (int8_t)sv;
-    }
-  }
-  {
-    const int w = wave_sum_dpp(qsum_part);
-    if (lane == 0) s_redq[wv] = w;
-  }
-  __syncthreads();
+  MQ_ATTN_GRIDS;
+  MQ_ATTN_NEW_TOKEN(a.k_cache, a.v_cache)
+  MQ_ATTN_QSUM_REDUCE;
   DG_STAMP(1);
-  const int qsum = (s_redq[0] + s_redq[1]) + (s_redq[2] + s_redq[3]);
-  const int zq = (int)qa.o - 128, zk = (int)qb.o - 128, zv = (int)pb.o - 128, zp = (int)pa.o;
-  const float alpha_qk = __fmul_rn(qa.s, qb.s), alpha_pv = __fmul_rn(pa.s, pb.s);
-  const int qconst = D * zq * zk - zk * qsum;                      // sum (iq - zq)(ik - zk) = sum sq sk - zk sum sq - zq sum sk + D zq zk
-  constexpr bool pow2 = (D == 64 || D == 256);                     // sqrt(D) a power of two: the divide is an exact multiply
-  const float sqrt_d = __fsqrt_rn((float)D), inv_sqrt_d = 1.0f / (D == 64 ? 8.0f : 16.0f);
+  MQ_ATTN_CONSTS;
   v4i qf[CH], kn[CH];                                              // this lane's share of the query / of the NEW key (never via memory)
 #pragma unroll
   for (int ch = 0; ch < CH; ++ch) {
-    qf[ch] = *reinterpret_cast<const v4i*>(s_q8 + (sub * CH + ch) * 16);
-    kn[ch] = *reinterpret_cast<const v4i*>(s_k8 + (sub * CH + ch) * 16);
+    qf[ch] = MQ_ATTN_LDS_FRAG(s_q8, ch);
+    kn[ch] = MQ_ATTN_LDS_FRAG(s_k8, ch);
   }
-  const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
-  // ---- scores ----------------------------------------------------------------------------------------------------------------------
-  float lmax = -INFINITY;
-  for (int t0 = 0; t0 < T; t0 += KB * PPP) {
-    if (t0 > 0) load_keys(t0);
-#pragma unroll
-    for (int u = 0; u < KB; ++u) {
-      if (t0 + u * PPP >= T) break;                                // (uniform) the rest of the batch lies beyond the sequence
-      const int t = t0 + u * PPP + slot;
-      int dot = 0, ks = 0;
-#pragma unroll
-      for (int ch = 0; ch < CH; ++ch) {
-        const v4i kf = t == pos ? kn[ch] : kbuf[u][ch];
-        dot = dot16(kf, qf[ch], dot);
-        ks = dot16(kf, ones, ks);
-      }
-      dot = quad_sum<LPP>(dot);
-      ks = quad_sum<LPP>(ks);
-      if (t < T && sub == 0) {
-        const int ti = dot - zq * ks + qconst;
-        const float val = __fmul_rn((float)ti, alpha_qk);
-        const float qv = qo.fq(val);
-        const float sc = pow2 ? __fmul_rn(qv, inv_sqrt_d) : __fdiv_rn(qv, sqrt_d);     // qk_bmm(...) / sqrt(head_dim)  (hf_model.py:513)
-        s_sc[t] = sc;
-        lmax = fmaxf(lmax, sc);
-      }
-    }
-  }
-  lmax = wave_max_f(lmax);
-  if (lane == 0) s_redf[wv] = lmax;
-  __syncthreads();
+  MQ_ATTN_SCORES(t == pos ? kn[ch] : kbuf[u][ch]);
   DG_STAMP(2);
-  const float mx = fmaxf(fmaxf(s_redf[0], s_redf[1]), fmaxf(s_redf[2], s_redf[3]));
-  __syncthreads();
-  float lsum = 0.f;
-  for (int t = tid; t < T; t += 256) {
-    const float e = expf(s_sc[t] - mx);
-    s_sc[t] = e;
-    lsum += e;
-  }
-  lsum = wave_sum_f(lsum);
-  if (lane == 0) s_redf[wv] = lsum;
-  __syncthreads();
-  const float tot_e = (s_redf[0] + s_redf[1]) + (s_redf[2] + s_redf[3]);
-  // pv_bmm's input quantizer, once per position of THIS split's blocks: (index - zp) as int
-  int* s_pi = reinterpret_cast<int*>(s_sc);
-  for (int t = tid; t < T; t += 256) {
-    if (nsplit == 1 || ((t >> 6) % nsplit) == c) {
-      const float p = __fdiv_rn(s_sc[t], tot_e);
-      const float ip = dq_index(p, pa.s, pa.inv_s, pa.o, pa.qmin, pa.qmax);
-      s_pi[t] = (ip != ip ? 0 : (int)ip) - zp;
-    }
-  }
-  __syncthreads();
+  MQ_ATTN_SOFTMAX;
   DG_STAMP(3);
-  // ---- p.v over this split's blocks: exact integers ------------------------------------------------------------------------------
-  // sum_t pi[t] (vs[t][d] - zv) = sum_t pi[t] vs[t][d] - zv sum_t pi[t]: v_bfe_i32 + v_mad_i32_i24 per element, one add per position
   long long acc[4] = {0, 0, 0, 0};
   long long psum = 0;
-  const int nblk = (pos + 63) >> 6;                                  // blocks of CACHED positions 0 .. pos - 1
-  const int my_blocks = c < nblk ? (nblk - 1 - c) / nsplit + 1 : 0;
+  MQ_ATTN_SPLIT_BLOCKS(pos);
   const int items = my_blocks * PPB;
-  for (int i0 = 0; i0 < items; i0 += VB) {
-    if (i0 > 0) load_values(i0);
-    int a32[4] = {0, 0, 0, 0}, p32 = 0;                              // <= 16 positions x 65535 x 128 < 2^31
-#pragma unroll
-    for (int u = 0; u < VB; ++u) {
-      const int t = item_pos(i0 + u);
-      const bool ok = i0 + u < items && t < pos;
-      const int pi = s_pi[ok ? t : 0];
-      const int pim = ok ? pi : 0;
-      p32 += pim;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) a32[e] += (int)__builtin_amdgcn_sbfe(vbuf[u], 8 * e, 8) * pim;      // (the builtin returns unsigned)
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += a32[e];
-    psum += p32;
-  }
-  if (grp == 0 && ((pos >> 6) % nsplit) == c) {                      // the new position: its split's group 0 adds it from registers
-    const int sv4 = *reinterpret_cast<const int*>(s_v8 + dq * 4);
-    const int pi = s_pi[pos];
-    psum += pi;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += (long long)((int)__builtin_amdgcn_sbfe(sv4, 8 * e, 8) * pi);
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) acc[e] -= (long long)zv * psum;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) s_acc[grp * D + dq * 4 + e] = acc[e];
+  MQ_ATTN_PV_FLAT(pos)
+  if (grp == 0 && ((pos >> 6) % nsplit) == c) MQ_ATTN_PV_ADD_NEW(s_v8, s_pi[pos])   // the new position
+  MQ_ATTN_FOLD_GROUPS;
   __syncthreads();
   DG_STAMP(4);
-  long long tot = 0;
-  if (tid < D) {
-#pragma unroll
-    for (int gq = 0; gq < G; ++gq) tot += s_acc[gq * D + tid];
-  }
-  if (nsplit > 1) {
-    // publish this split's exact partial sums write-through, count the head's splits; the last one adds them (cdna guide G16 R1)
-    if (tid < D) __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.part) + ((size_t)c * H + h) * D + tid, (unsigned long long)tot,
-                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    // RELEASE at agent scope: the partials above are already write-through (8-byte agent atomics, drained by the vmcnt wait
-    // and ordered for the whole workgroup by the barrier), which is what makes this correct on gfx950; the release gives the formal
-    // release -> acquire edge to the last split's fence below as well.  One L2 write-back per split workgroup, on the long-context path only.
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(a.ticket + h, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_ticket != (unsigned)(nsplit - 1)) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (tid == 0) __hip_atomic_store(a.ticket + h, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-    if (tid < D) {
-      tot = 0;
-      for (int cc = 0; cc < nsplit; ++cc)
-        tot += (long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(a.part) + ((size_t)cc * H + h) * D + tid, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (tid < D) {
-    const float pre = (float)((double)tot * (double)alpha_pv);     // one rounding of the exact sum (as mq_attention.hip)
-    const float y = po.fq(pre);
-    if (a.out) a.out[(size_t)h * D + tid] = y;
-    if (a.out_q) {
-      const float qi = dq_index(y, oi.s, oi.inv_s, oi.o, oi.qmin, oi.qmax);
-      a.out_q[(size_t)h * D + tid] = (int8_t)((qi != qi ? (int)oi.qmin : (int)qi) - 128);
-    }
-  }
+  MQ_ATTN_FINISH(G, , reinterpret_cast<unsigned long long*>(a.part), a.ticket, , (size_t)h * D + tid)
 #ifdef MQ_DECODE_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   DG_STAMP(5);
@@ -1311,28 +1138,11 @@ int mq_decode_pack_grids(const mq_grid* grids, int n, float* consts, mq_stream_t
   return MQ_OK;
 }
 
-static int decode_gemv_geometry(const mq_decode_gemv_args& g, int* rows_per_wg, unsigned* grid) {
-  static std::atomic<int> cus_of[kMaxDevices];
-  const int dev = current_device();
-  int cus = cus_of[dev].load(std::memory_order_relaxed);
-  if (!cus) {
-    hipDeviceProp_t prop;
-    cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    cus_of[dev].store(cus, std::memory_order_relaxed);
-  }
-  const int NL = g.gate_q ? g.N / 2 : g.N;
-  int rpw = (NL + cus - 1) / cus;
-  if (rpw > DG_STR * 64) rpw = DG_STR * 64;
-  *rows_per_wg = rpw;
-  *grid = (unsigned)((NL + rpw - 1) / rpw);
-  return NL;
-}
-
 int mq_decode_gemv_geometry(const mq_decode_gemv_args* args, int64_t* workgroups, int64_t* bytes_per_workgroup, int64_t* total_bytes) {
   MQ_REQUIRE(args && workgroups && bytes_per_workgroup && total_bytes && args->K > 0 && args->N > 0, "mq_decode_gemv_geometry: null / empty argument");
   int rpw;
   unsigned grid;
-  decode_gemv_geometry(*args, &rpw, &grid);
+  gemv_row_geometry(args->gate_q ? args->N / 2 : args->N, &rpw, &grid);
   const int64_t row = (int64_t)(args->gate_q ? 2 : 1) * (args->w4 ? args->K / 2 : args->K);
   *workgroups = grid;
   *bytes_per_workgroup = rpw * row;
@@ -1362,7 +1172,7 @@ int mq_decode_gemv(const mq_decode_gemv_args* args, mq_stream_t stream) {
              "mq_decode_gemv: o_acc (o_proj's epilogue as prologue) is served for the gate launch, K <= 4096, with o_alpha / o_ct / x_mid, 16-byte aligned");
   int rows_per_wg;
   unsigned grid;
-  decode_gemv_geometry(g, &rows_per_wg, &grid);
+  gemv_row_geometry(gate ? g.N / 2 : g.N, &rows_per_wg, &grid);
   const size_t lds = (size_t)g.K + 64;
   hipStream_t st = as_stream(stream);
   unsigned long long* stamps = STAMP_SLOT(gate ? 1 : (g.norm_w ? 0 : (g.xq ? 3 : 2)), grid);
@@ -1396,16 +1206,15 @@ int mq_decode_gemv(const mq_decode_gemv_args* args, mq_stream_t stream) {
   return MQ_OK;
 }
 
-// ---- the largest cache_len each attention launch serves: LDS per workgroup on gfx950 (160 KiB) = static + dynamic LDS ------------------
+// ---- the largest cache_len the four-launch attention serves: LDS per workgroup on gfx950 (160 KiB) = static + dynamic LDS ------------
 // Static LDS in bytes (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage on this file), head_dim 32 / 64 / 128 / 256:
 //   decode_attention_kernel<D>                      8336 / 8432 / 8624 / 9008   + 4 B per cached position (scores)
 //   decode_attention_oproj_kernel<D, 256>           2240 / 2368 / 2624 / 3136   + 7 B per cached position (scores + 3 digit planes)
 //   decode_attention_oproj_kernel<D, 1024>          8528 / 8656 / 8912 / 9424
-// five launches: 4 x 32768 + 9008 fits at every head_dim, so the entry's own 32768 is the bound; four launches: the largest multiple of
-// 16 with 7 cache_len + static <= 163840 -- 23072 / 23056 / 23024 / 22944 (256 threads), 22176 / 22160 / 22128 / 22048 (1024 threads).
-// mobilequant_amd/decode.py (DecodeEngine.max_cache_len) mirrors these numbers to choose the chain.
+// five launches: 4 x 32768 + 9008 fits at every head_dim, so kAttnMaxCache (mq_decode_attention.h) is the bound; four launches: the
+// largest multiple of 16 with 7 cache_len + static <= 163840 -- 23072 / 23056 / 23024 / 22944 (256 threads), 22176 / 22160 / 22128 /
+// 22048 (1024 threads).  mobilequant_amd/decode.py (DecodeEngine.max_cache_len) mirrors these numbers to choose the chain.
 constexpr int kLdsPerWorkgroup = 160 * 1024;
-constexpr int kAttnMaxCache = 32768;
 static int ao_max_cache(int head_dim, bool lng) {
   const int ki = head_dim == 32 ? 0 : head_dim == 64 ? 1 : head_dim == 128 ? 2 : 3;
   static const int static_lds[2][4] = {{2240, 2368, 2624, 3136}, {8528, 8656, 8912, 9424}};
@@ -1415,29 +1224,16 @@ static int ao_max_cache(int head_dim, bool lng) {
 int mq_decode_attention(const mq_decode_attention_args* args, mq_stream_t stream) {
   MQ_REQUIRE(args != nullptr, "mq_decode_attention: null argument block");
   const mq_decode_attention_args& a = *args;
-  MQ_REQUIRE(a.qkv && a.k_cache && a.v_cache && a.cos && a.sin && a.pos && a.consts && (a.out || a.out_q), "mq_decode_attention: null pointer");
-  MQ_REQUIRE(a.heads > 0 && a.kv_heads > 0 && a.heads % a.kv_heads == 0 && (a.head_dim == 32 || a.head_dim == 64 || a.head_dim == 128 || a.head_dim == 256) &&
-                 a.cache_len > 0 && a.cache_len <= kAttnMaxCache && a.rot_dim > 0 && a.rot_dim <= a.head_dim && a.rot_dim % 2 == 0,
-             "mq_decode_attention: heads=%d kv_heads=%d head_dim=%d (32 / 64 / 128 / 256) cache_len=%d (<= %d) rot_dim=%d", a.heads, a.kv_heads, a.head_dim,
-             a.cache_len, kAttnMaxCache, a.rot_dim);
-  MQ_REQUIRE(a.nsplit >= 1 && a.nsplit <= 16 && (a.nsplit == 1 || (a.part && a.ticket)), "mq_decode_attention: nsplit=%d (1..16; > 1 needs part and ticket)", a.nsplit);
-  MQ_REQUIRE(a.qk_a.scale && a.qk_b.scale && a.pv_a.scale && a.pv_b.scale && a.qk_a.qmin == 0.f && a.qk_a.qmax == 255.f && a.qk_b.qmin == 0.f &&
-                 a.qk_b.qmax == 255.f && a.pv_b.qmin == 0.f && a.pv_b.qmax == 255.f && a.pv_a.qmin == 0.f && a.pv_a.qmax <= 65535.f,
-             "mq_decode_attention: q / k / v need 8-bit unsigned grids, the probabilities an unsigned grid of at most 16 bits");
-  MQ_REQUIRE(!a.out_q || (a.o_in.scale && a.o_in.qmin == 0.f && a.o_in.qmax == 255.f), "mq_decode_attention: the int8 output image needs the consumer's 8-bit unsigned grid (o_in)");
-  MQ_REQUIRE(aligned(a.k_cache, 16) && aligned(a.v_cache, 16) && aligned(a.consts, 16) && aligned(a.qkv, 4), "mq_decode_attention: caches / consts must be 16-byte aligned");
+  int rc = check_five_launch_attention("mq_decode_attention", a);
+  if (rc != MQ_OK) return rc;
   const size_t lds = (size_t)a.cache_len * sizeof(float);
   const void* fn = a.head_dim == 32 ? reinterpret_cast<const void*>(decode_attention_kernel<32>)
                    : a.head_dim == 64 ? reinterpret_cast<const void*>(decode_attention_kernel<64>)
                    : a.head_dim == 128 ? reinterpret_cast<const void*>(decode_attention_kernel<128>)
                                        : reinterpret_cast<const void*>(decode_attention_kernel<256>);
-  static std::atomic<size_t> lds_set[kMaxDevices][4];
-  const int dev = current_device(), ki = a.head_dim == 32 ? 0 : a.head_dim == 64 ? 1 : a.head_dim == 128 ? 2 : 3;
-  if (lds > 32768 && lds_set[dev][ki].load(std::memory_order_relaxed) < lds) {
-    MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-               "mq_decode_attention: %zu bytes of dynamic LDS rejected", lds);
-    lds_set[dev][ki].store(lds, std::memory_order_relaxed);
-  }
+  static std::atomic<size_t> lds_set[4][kMaxDevices];
+  rc = set_lds(fn, lds_set[a.head_dim == 32 ? 0 : a.head_dim == 64 ? 1 : a.head_dim == 128 ? 2 : 3], lds, "mq_decode_attention");
+  if (rc != MQ_OK) return rc;
   MQ_REQUIRE(a.prefetch_wgs == 0 || (a.prefetch && aligned(a.prefetch, 16) && a.prefetch_bytes_per_wg % 16 == 0 && a.prefetch_wgs > 0 && a.prefetch_wgs <= 4096),
              "mq_decode_attention: prefetch needs a 16-byte aligned range and 1..4096 workgroups");
   MQ_REQUIRE(a.prefetch_wgs == 0 || (a.prefetch_stride >= a.prefetch_bytes_per_wg && a.prefetch_stride % 16 == 0 && a.prefetch_delay >= 0 && a.prefetch_delay <= 100000),

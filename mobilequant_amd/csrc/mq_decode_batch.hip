@@ -5,9 +5,10 @@
 // in the same reduction orders (integer sums are exact in any order).
 //   mq_decode_gemv_batch      : decode_gemv_kernel (five-launch subset) for B rows: B prologues interleaved over shared barriers, the
 //                               B int8 images side by side in LDS, every 16-byte weight chunk contracted with all of them
-//   mq_decode_attention_batch : decode_attention_kernel<D> on a (heads, nsplit, B) grid, per-sequence positions, caches and scratch
+//   mq_decode_attention_batch : decode_attention_kernel<D>'s phases (mq_decode_attention.h) on a (heads, nsplit, B) grid, per-sequence
+//                               positions, caches and scratch
 //   mq_decode_head_batch      : decode_head_kernel's final norm for B rows, then the fp32 lm_head streamed once for all of them
-#include "mq_decode_common.h"
+#include "mq_decode_attention.h"
 
 namespace mq {
 
@@ -170,19 +171,12 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_batch_kernel(const mq_
 // that sequence's position, q | k | v row, caches, output row and split scratch.  The split count is chosen here from the position
 // (nsplit from split_from cached positions on, else 1; the other workgroups exit): the scores and the softmax are computed whole by
 // every split and the p.v partials are exact integers, so the result bits do not depend on it.  No prefetch rows.
+// The phases are the MQ_ATTN_* texts of mq_decode_attention.h; this kernel's own are the per-sequence offsets and split_from.
 template <int D>
 __global__ void __launch_bounds__(256) decode_attention_batch_kernel(const mq_decode_attention_batch_args ba) {
   const mq_decode_attention_args& a = ba.a;
-  constexpr int LPP = D >= 64 ? 4 : 2, CH = D >= 64 ? D / 64 : 1, PPP = 256 / LPP, KB = 8 / CH;
-  constexpr int DQ = D / 4, G = 256 / DQ, PPB = 64 / G, VB = 16;
-  static_assert(PPB * G == 64 && VB % PPB == 0, "block mapping");
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* s_sc = reinterpret_cast<float*>(smem_raw);              // [cache_len] scores -> exp -> (p index - zp) as int
-  __shared__ __attribute__((aligned(16))) int8_t s_q8[D], s_k8[D], s_v8[D];
-  __shared__ float s_redf[4];
-  __shared__ int s_redq[4];
-  __shared__ long long s_acc[1024];                              // [G][D] partial p.v sums
-  __shared__ unsigned s_ticket;
+  MQ_ATTN_GEOMETRY(D);
+  MQ_ATTN_LDS(s_q8[D], s_k8[D], s_v8[D]);
   const int H = a.heads, rot = a.rot_dim, sb = blockIdx.z;
   const int pos = a.pos[sb];
   if (pos < 0 || pos >= a.cache_len) return;                       // an idle slot (or a step past the cache): nothing is read or written
@@ -207,190 +201,34 @@ __global__ void __launch_bounds__(256) decode_attention_batch_kernel(const mq_de
   const float cs = a.cos[(size_t)pos * rot + dr], sn = a.sin[(size_t)pos * rot + dr];
   const int8_t* kc = k_cache + (size_t)kvh * a.cache_len * D;
   const int8_t* vc = v_cache + (size_t)kvh * a.cache_len * D;
-  const int sub = tid & (LPP - 1), slot = tid / LPP;
-  v4i kbuf[KB][CH];
-  auto load_keys = [&](int t0) {
-#pragma unroll
-    for (int u = 0; u < KB; ++u) {
-      const int t = t0 + u * PPP + slot;
-      const int tc = (t < T && t != pos) ? t : 0;                   // position 0 stands in (always valid memory); masked below
-#pragma unroll
-      for (int ch = 0; ch < CH; ++ch) kbuf[u][ch] = *reinterpret_cast<const v4i*>(kc + (size_t)tc * D + (sub * CH + ch) * 16);
-    }
-  };
-  load_keys(0);
-  const int dq = tid & (DQ - 1), grp = tid / DQ;
-  int vbuf[VB];
-  auto item_pos = [&](int i) { return 64 * (c + nsplit * (i / PPB)) + grp + G * (i % PPB); };
-  auto load_values = [&](int i0) {
-#pragma unroll
-    for (int u = 0; u < VB; ++u) {
-      const int t = item_pos(i0 + u);
-      vbuf[u] = *reinterpret_cast<const int*>(vc + (size_t)(t < pos ? t : 0) * D + dq * 4);
-    }
-  };
+  MQ_ATTN_KEY_LOADER(t < T && t != pos);
+  MQ_ATTN_VALUE_LOADER(pos);
   load_values(0);
-  // ---- RoPE + the three input quantizers of the new token ---------------------------------------------------------------------------
-  const Grid qa = const_grid(cv, AG_QK_A, a.qk_a), qb = const_grid(cv, AG_QK_B, a.qk_b), qo = const_grid(cv, AG_QK_OUT, a.qk_out);
-  const Grid pa = const_grid(cv, AG_PV_A, a.pv_a), pb = const_grid(cv, AG_PV_B, a.pv_b), po = const_grid(cv, AG_PV_OUT, a.pv_out);
-  const Grid oi = const_grid(cv, AG_O_IN, a.o_in);
-  int qsum_part = 0;
-  if (tid < D) {
-    float qv = q_raw, kv = k_raw;
-    if (tid < rot) {
-      const float sg = tid < half ? -1.f : 1.f;
-      qv = __fadd_rn(__fmul_rn(q_raw, cs), __fmul_rn(sg * q_par, sn));
-      kv = __fadd_rn(__fmul_rn(k_raw, cs), __fmul_rn(sg * k_par, sn));
-    }
-    const float iq = dq_index(qv, qa.s, qa.inv_s, qa.o, qa.qmin, qa.qmax), ik = dq_index(kv, qb.s, qb.inv_s, qb.o, qb.qmin, qb.qmax);
-    const float iv = dq_index(v_raw, pb.s, pb.inv_s, pb.o, pb.qmin, pb.qmax);
-    const int sq = (iq != iq ? 0 : (int)iq) - 128, sk = (ik != ik ? 0 : (int)ik) - 128, sv = (iv != iv ? 0 : (int)iv) - 128;
-    s_q8[tid] = (int8_t)sq;
-    s_k8[tid] = (int8_t)sk;
-    s_v8[tid] = (int8_t)sv;
-    qsum_part = sq;
-    if (c == 0 && h % (H / a.kv_heads) == 0) {                     // the group's first head appends to this sequence's cache
-      k_cache[((size_t)kvh * a.cache_len + pos) * D + tid] = (int8_t)sk;
-      v_cache[((size_t)kvh * a.cache_len + pos) * D + tid] = (int8_t)sv;
-    }
-  }
-  {
-    const int w = wave_sum_dpp(qsum_part);
-    if (lane == 0) s_redq[wv] = w;
-  }
-  __syncthreads();
-  const int qsum = (s_redq[0] + s_redq[1]) + (s_redq[2] + s_redq[3]);
-  const int zq = (int)qa.o - 128, zk = (int)qb.o - 128, zv = (int)pb.o - 128, zp = (int)pa.o;
-  const float alpha_qk = __fmul_rn(qa.s, qb.s), alpha_pv = __fmul_rn(pa.s, pb.s);
-  const int qconst = D * zq * zk - zk * qsum;
-  constexpr bool pow2 = (D == 64 || D == 256);
-  const float sqrt_d = __fsqrt_rn((float)D), inv_sqrt_d = 1.0f / (D == 64 ? 8.0f : 16.0f);
-  v4i qf[CH], kn[CH];
+  MQ_ATTN_GRIDS;
+  MQ_ATTN_NEW_TOKEN(k_cache, v_cache)                              // (appends to this sequence's cache)
+  MQ_ATTN_QSUM_REDUCE;
+  MQ_ATTN_CONSTS;
+  v4i qf[CH], kn[CH];                                              // this lane's share of the query / of the NEW key (never via memory)
 #pragma unroll
   for (int ch = 0; ch < CH; ++ch) {
-    qf[ch] = *reinterpret_cast<const v4i*>(s_q8 + (sub * CH + ch) * 16);
-    kn[ch] = *reinterpret_cast<const v4i*>(s_k8 + (sub * CH + ch) * 16);
+    qf[ch] = MQ_ATTN_LDS_FRAG(s_q8, ch);
+    kn[ch] = MQ_ATTN_LDS_FRAG(s_k8, ch);
   }
-  const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
-  // ---- scores ----------------------------------------------------------------------------------------------------------------------
-  float lmax = -INFINITY;
-  for (int t0 = 0; t0 < T; t0 += KB * PPP) {
-    if (t0 > 0) load_keys(t0);
-#pragma unroll
-    for (int u = 0; u < KB; ++u) {
-      if (t0 + u * PPP >= T) break;
-      const int t = t0 + u * PPP + slot;
-      int dot = 0, ks = 0;
-#pragma unroll
-      for (int ch = 0; ch < CH; ++ch) {
-        const v4i kf = t == pos ? kn[ch] : kbuf[u][ch];
-        dot = dot16(kf, qf[ch], dot);
-        ks = dot16(kf, ones, ks);
-      }
-      dot = quad_sum<LPP>(dot);
-      ks = quad_sum<LPP>(ks);
-      if (t < T && sub == 0) {
-        const int ti = dot - zq * ks + qconst;
-        const float val = __fmul_rn((float)ti, alpha_qk);
-        const float qv = qo.fq(val);
-        const float sc = pow2 ? __fmul_rn(qv, inv_sqrt_d) : __fdiv_rn(qv, sqrt_d);
-        s_sc[t] = sc;
-        lmax = fmaxf(lmax, sc);
-      }
-    }
-  }
-  lmax = wave_max_f(lmax);
-  if (lane == 0) s_redf[wv] = lmax;
-  __syncthreads();
-  const float mx = fmaxf(fmaxf(s_redf[0], s_redf[1]), fmaxf(s_redf[2], s_redf[3]));
-  __syncthreads();
-  float lsum = 0.f;
-  for (int t = tid; t < T; t += 256) {
-    const float e = expf(s_sc[t] - mx);
-    s_sc[t] = e;
-    lsum += e;
-  }
-  lsum = wave_sum_f(lsum);
-  if (lane == 0) s_redf[wv] = lsum;
-  __syncthreads();
-  const float tot_e = (s_redf[0] + s_redf[1]) + (s_redf[2] + s_redf[3]);
-  int* s_pi = reinterpret_cast<int*>(s_sc);
-  for (int t = tid; t < T; t += 256) {
-    if (nsplit == 1 || ((t >> 6) % nsplit) == c) {
-      const float p = __fdiv_rn(s_sc[t], tot_e);
-      const float ip = dq_index(p, pa.s, pa.inv_s, pa.o, pa.qmin, pa.qmax);
-      s_pi[t] = (ip != ip ? 0 : (int)ip) - zp;
-    }
-  }
-  __syncthreads();
-  // ---- p.v over this split's blocks: exact integers ------------------------------------------------------------------------------
+  MQ_ATTN_SCORES(t == pos ? kn[ch] : kbuf[u][ch]);
+  MQ_ATTN_SOFTMAX;
   long long acc[4] = {0, 0, 0, 0};
   long long psum = 0;
-  const int nblk = (pos + 63) >> 6;
-  const int my_blocks = c < nblk ? (nblk - 1 - c) / nsplit + 1 : 0;
+  MQ_ATTN_SPLIT_BLOCKS(pos);
   const int items = my_blocks * PPB;
-  for (int i0 = 0; i0 < items; i0 += VB) {
-    if (i0 > 0) load_values(i0);
-    int a32[4] = {0, 0, 0, 0}, p32 = 0;
-#pragma unroll
-    for (int u = 0; u < VB; ++u) {
-      const int t = item_pos(i0 + u);
-      const bool ok = i0 + u < items && t < pos;
-      const int pi = s_pi[ok ? t : 0];
-      const int pim = ok ? pi : 0;
-      p32 += pim;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) a32[e] += (int)__builtin_amdgcn_sbfe(vbuf[u], 8 * e, 8) * pim;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += a32[e];
-    psum += p32;
-  }
-  if (grp == 0 && ((pos >> 6) % nsplit) == c) {
-    const int sv4 = *reinterpret_cast<const int*>(s_v8 + dq * 4);
-    const int pi = s_pi[pos];
-    psum += pi;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += (long long)((int)__builtin_amdgcn_sbfe(sv4, 8 * e, 8) * pi);
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) acc[e] -= (long long)zv * psum;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) s_acc[grp * D + dq * 4 + e] = acc[e];
+  MQ_ATTN_PV_FLAT(pos)
+  if (grp == 0 && ((pos >> 6) % nsplit) == c) MQ_ATTN_PV_ADD_NEW(s_v8, s_pi[pos])
+  MQ_ATTN_FOLD_GROUPS;
   __syncthreads();
-  long long tot = 0;
-  if (tid < D) {
-#pragma unroll
-    for (int gq = 0; gq < G; ++gq) tot += s_acc[gq * D + tid];
-  }
-  if (nsplit > 1) {
-    // this sequence's split scratch and tickets; the protocol of decode_attention_kernel
-    unsigned long long* part = reinterpret_cast<unsigned long long*>(a.part) + (size_t)sb * a.nsplit * H * D;
-    unsigned* ticket = a.ticket + (size_t)sb * H;
-    if (tid < D) __hip_atomic_store(part + ((size_t)c * H + h) * D + tid, (unsigned long long)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(ticket + h, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_ticket != (unsigned)(nsplit - 1)) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (tid == 0) __hip_atomic_store(ticket + h, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < D) {
-      tot = 0;
-      for (int cc = 0; cc < nsplit; ++cc)
-        tot += (long long)__hip_atomic_load(part + ((size_t)cc * H + h) * D + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (tid < D) {
-    const size_t o = ((size_t)sb * H + h) * D + tid;
-    const float pre = (float)((double)tot * (double)alpha_pv);
-    const float y = po.fq(pre);
-    if (a.out) a.out[o] = y;
-    if (a.out_q) {
-      const float qi = dq_index(y, oi.s, oi.inv_s, oi.o, oi.qmin, oi.qmax);
-      a.out_q[o] = (int8_t)((qi != qi ? (int)oi.qmin : (int)qi) - 128);
-    }
-  }
+  // this sequence's split scratch, tickets and output row
+  MQ_ATTN_FINISH(G,
+                 unsigned long long* part = reinterpret_cast<unsigned long long*>(a.part) + (size_t)sb * a.nsplit * H * D;
+                 unsigned* ticket = a.ticket + (size_t)sb * H;, part, ticket,
+                 const size_t o = ((size_t)sb * H + h) * D + tid;, o)
 }
 
 // ---- final norm for B rows + the fp32 lm_head streamed once -----------------------------------------------------------------------
@@ -575,7 +413,7 @@ int mq_decode_gemv_batch(const mq_decode_gemv_batch_args* args, mq_stream_t stre
   MQ_REQUIRE(!g.norm_bias || (g.layernorm && aligned(g.norm_bias, 16)), "mq_decode_gemv_batch: norm_bias belongs to the LayerNorm prologue (layernorm = 1), 16-byte aligned");
   int rows_per_wg;
   unsigned grid;
-  batch_gemv_geometry(NLr, &rows_per_wg, &grid);
+  gemv_row_geometry(NLr, &rows_per_wg, &grid);
   const size_t lds = (size_t)B * g.K;
   hipStream_t st = as_stream(stream);
   const int xmode = g.xq ? XM_I8 : (g.norm_w ? (g.layernorm ? XM_LNORM : XM_NORM) : XM_F32);
@@ -611,25 +449,13 @@ int mq_decode_gemv_batch(const mq_decode_gemv_batch_args* args, mq_stream_t stre
   return MQ_OK;
 }
 
-// the five-launch attention's bound (mq_decode.hip kAttnMaxCache): 4 bytes of LDS per cached position plus <= 9 KB static
-constexpr int kBatchAttnMaxCache = 32768;
-
 int mq_decode_attention_batch(const mq_decode_attention_batch_args* args, mq_stream_t stream) {
   MQ_REQUIRE(args != nullptr, "mq_decode_attention_batch: null argument block");
   const mq_decode_attention_args& a = args->a;
   const int B = args->batch;
   MQ_REQUIRE(B >= 1 && B <= MQ_DECODE_MAX_BATCH, "mq_decode_attention_batch: batch=%d outside 1..%d", B, MQ_DECODE_MAX_BATCH);
-  MQ_REQUIRE(a.qkv && a.k_cache && a.v_cache && a.cos && a.sin && a.pos && a.consts && (a.out || a.out_q), "mq_decode_attention_batch: null pointer");
-  MQ_REQUIRE(a.heads > 0 && a.kv_heads > 0 && a.heads % a.kv_heads == 0 && (a.head_dim == 32 || a.head_dim == 64 || a.head_dim == 128 || a.head_dim == 256) &&
-                 a.cache_len > 0 && a.cache_len <= kBatchAttnMaxCache && a.rot_dim > 0 && a.rot_dim <= a.head_dim && a.rot_dim % 2 == 0,
-             "mq_decode_attention_batch: heads=%d kv_heads=%d head_dim=%d (32 / 64 / 128 / 256) cache_len=%d (<= %d) rot_dim=%d", a.heads, a.kv_heads,
-             a.head_dim, a.cache_len, kBatchAttnMaxCache, a.rot_dim);
-  MQ_REQUIRE(a.nsplit >= 1 && a.nsplit <= 16 && (a.nsplit == 1 || (a.part && a.ticket)), "mq_decode_attention_batch: nsplit=%d (1..16; > 1 needs part and ticket)", a.nsplit);
-  MQ_REQUIRE(a.qk_a.scale && a.qk_b.scale && a.pv_a.scale && a.pv_b.scale && a.qk_a.qmin == 0.f && a.qk_a.qmax == 255.f && a.qk_b.qmin == 0.f &&
-                 a.qk_b.qmax == 255.f && a.pv_b.qmin == 0.f && a.pv_b.qmax == 255.f && a.pv_a.qmin == 0.f && a.pv_a.qmax <= 65535.f,
-             "mq_decode_attention_batch: q / k / v need 8-bit unsigned grids, the probabilities an unsigned grid of at most 16 bits");
-  MQ_REQUIRE(!a.out_q || (a.o_in.scale && a.o_in.qmin == 0.f && a.o_in.qmax == 255.f), "mq_decode_attention_batch: the int8 output image needs the consumer's 8-bit unsigned grid (o_in)");
-  MQ_REQUIRE(aligned(a.k_cache, 16) && aligned(a.v_cache, 16) && aligned(a.consts, 16) && aligned(a.qkv, 4), "mq_decode_attention_batch: caches / consts must be 16-byte aligned");
+  int rc = check_five_launch_attention("mq_decode_attention_batch", a);
+  if (rc != MQ_OK) return rc;
   MQ_REQUIRE(a.prefetch_wgs == 0, "mq_decode_attention_batch: no prefetch rows (prefetch_wgs must be 0)");
   MQ_REQUIRE(B == 1 || args->qkv_stride >= (int64_t)(a.heads + 2 * a.kv_heads) * a.head_dim, "mq_decode_attention_batch: qkv_stride must cover a q | k | v row");
   const size_t lds = (size_t)a.cache_len * sizeof(float);
@@ -638,7 +464,7 @@ int mq_decode_attention_batch(const mq_decode_attention_batch_args* args, mq_str
                    : a.head_dim == 128 ? reinterpret_cast<const void*>(decode_attention_batch_kernel<128>)
                                        : reinterpret_cast<const void*>(decode_attention_batch_kernel<256>);
   static std::atomic<size_t> lds_set[4][kMaxDevices];
-  const int rc = set_lds(fn, lds_set[a.head_dim == 32 ? 0 : a.head_dim == 64 ? 1 : a.head_dim == 128 ? 2 : 3], lds, "mq_decode_attention_batch");
+  rc = set_lds(fn, lds_set[a.head_dim == 32 ? 0 : a.head_dim == 64 ? 1 : a.head_dim == 128 ? 2 : 3], lds, "mq_decode_attention_batch");
   if (rc != MQ_OK) return rc;
   const dim3 grid((unsigned)a.heads, (unsigned)a.nsplit, (unsigned)B);
   hipStream_t st = as_stream(stream);

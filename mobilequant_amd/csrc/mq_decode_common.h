@@ -1,6 +1,7 @@
-// Device helpers shared by the single-sequence decode kernels (mq_decode.hip), the batched ones (mq_decode_batch.hip) and the grouped
-// GEMV (mq_decode_grouped.hip): quantizer arithmetic, DPP wave reductions, the launch-constants line, the layout constants the
-// families agree on and the batched GEMV's prologue and epilogue.
+// Device helpers shared by the single-sequence decode kernels (mq_decode.hip), the batched ones (mq_decode_batch.hip), the grouped
+// GEMV (mq_decode_grouped.hip) and the multi-token attention (mq_decode_multi.hip): quantizer arithmetic, DPP wave reductions, the
+// launch-constants line, the layout constants the families agree on, the batched GEMV's prologue and epilogue and the GEMV launches'
+// row geometry.  The five-launch attention's phases build on this header in mq_decode_attention.h.
 #pragma once
 #include "mq_common.h"
 
@@ -114,28 +115,6 @@ enum { XM_NORM = 0, XM_F32 = 1, XM_I8 = 2, XM_LNORM = 3 };
 constexpr int DG_PRO = 8, DG_STR = DG_WAVES - DG_PRO, DG_XPRE = 4;      // 512 prologue threads x 4 float4 -> K <= 8192 (fp32)
 
 enum { AG_QK_A = 0, AG_QK_B = 1, AG_QK_OUT = 2, AG_PV_A = 3, AG_PV_B = 4, AG_PV_OUT = 5, AG_O_IN = 6, AG_COUNT = 7 };
-
-// One element d of a new token's q / k / v row on its 8-bit attention input grid, as stored (index - 128): RoPE (rotate-half over the
-// first rot dimensions: x * cos + rot(x) * sin) then the grid -- the expressions of decode_attention_batch_kernel, for the
-// attention launches that build new rows themselves (mq_decode_multi.hip).  par: the element's RoPE partner; rot = 0: no rotation (v).
-__device__ __forceinline__ int8_t attn_new_elem(float raw, float par, float cs, float sn, int d, int rot, const Grid& g) {
-  float x = raw;
-  if (d < rot) {
-    const float sg = d < (rot >> 1) ? -1.f : 1.f;                  // (-x) * sin == -(x * sin) exactly
-    x = __fadd_rn(__fmul_rn(raw, cs), __fmul_rn(sg * par, sn));
-  }
-  const float i = dq_index(x, g.s, g.inv_s, g.o, g.qmin, g.qmax);
-  return (int8_t)((i != i ? 0 : (int)i) - 128);
-}
-// The score of one position from its exact integer dot (q index . k index) and key byte sum: qk_bmm's output grid, then / sqrt(D)
-// (hf_model.py:513) -- decode_attention_batch_kernel's expression.
-template <int D>
-__device__ __forceinline__ float attn_score(int dot, int ks, int zq, int qconst, float alpha_qk, const Grid& qo) {
-  constexpr bool pow2 = (D == 64 || D == 256);
-  const int ti = dot - zq * ks + qconst;
-  const float qv = qo.fq(__fmul_rn((float)ti, alpha_qk));
-  return pow2 ? __fmul_rn(qv, 1.0f / (D == 64 ? 8.0f : 16.0f)) : __fdiv_rn(qv, __fsqrt_rn((float)D));
-}
 
 // sum over aligned groups of N = 2 / 4 adjacent lanes: DPP quad permutes (a __shfl_xor is an LDS round trip, ~100 cycles each)
 template <int N>
@@ -421,9 +400,10 @@ struct GemvBatchEpilogue {
   }
 };
 
-// ---- host side of the batched GEMV launches (mq_decode_batch.hip, mq_decode_grouped.hip) ----------------------------------------
-// rows per workgroup and grid: the logical rows spread over the device's CUs, at most DG_STR * 64 per workgroup
-inline int batch_gemv_geometry(int NL, int* rows_per_wg, unsigned* grid) {
+// ---- host side of the decode GEMV launches (mq_decode.hip, mq_decode_batch.hip, mq_decode_grouped.hip) -------------------------
+// rows per workgroup and grid: the NL logical rows (a gate launch's w1 | w3 pair is one) spread over the device's CUs, at most
+// DG_STR * 64 per workgroup
+inline int gemv_row_geometry(int NL, int* rows_per_wg, unsigned* grid) {
   static std::atomic<int> cus_of[kMaxDevices];
   const int dev = current_device();
   int cus = cus_of[dev].load(std::memory_order_relaxed);

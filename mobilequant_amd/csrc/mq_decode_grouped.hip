@@ -249,7 +249,7 @@ int mq_decode_gemv_grouped(const mq_decode_gemv_grouped_args* args, mq_stream_t 
   MQ_REQUIRE(!g.norm_bias || (g.layernorm && aligned(g.norm_bias, 16)), "mq_decode_gemv_grouped: norm_bias belongs to the LayerNorm prologue (layernorm = 1), 16-byte aligned");
   int rows_per_wg;
   unsigned grid;
-  batch_gemv_geometry(NLr, &rows_per_wg, &grid);
+  gemv_row_geometry(NLr, &rows_per_wg, &grid);
   const size_t lds = (size_t)B * g.K;
   hipStream_t st = as_stream(stream);
   const int xmode = g.xq ? XM_I8 : (g.norm_w ? (g.layernorm ? XM_LNORM : XM_NORM) : XM_F32);
