@@ -764,63 +764,194 @@ __global__ void __launch_bounds__(64 * WM * WN)
 }
 
 
-// ---- free-running generated kernel (tools/gen_fr_asm.py -> mq_gemm_fr_asm.inc) ---------------------------------------
-// The whole workgroup program (prologue, software-pipelined main loop, epilogue) is generated gfx950 ISA; C++ only forms
-// the per-lane addresses and the scalar arguments.  256 x 176 tile, fragment-blocked activations, int8 weights, 8-bit
-// UNSIGNED output grid (u8 storage, or i8 storage = index - 128), K % 256 == 0, K >= 768.
+// ---- one launch path ------------------------------------------------------------------------------------------------------------------
+// The dynamic-LDS attribute once per device and kernel (KFN is a template argument: one PerDeviceOnce per kernel instantiation), the
+// launch, the check.
+template <auto KFN, typename Args>
+static int launch_kernel(const Args& args, int blocks, int threads, int lds, hipStream_t st) {
+  static PerDeviceOnce attr_set;
+  const int dev = current_device();
+  if (!attr_set.done(dev)) {
+    hipError_t e = hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) {
+      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
+      return MQ_EHIP;
+    }
+    attr_set.mark(dev);
+  }
+  KFN<<<blocks, threads, lds, st>>>(args);
+  MQ_LAUNCH_CHECK("mq_gemm");
+  return MQ_OK;
+}
+
+// What every kernel here expects of the host: absent row sums / bias replaced by valid dummy pointers (row sums: element 0 only -- M may
+// exceed N -- and multiplied by w_zp == 0, which the caller guarantees; bias: masked by has_bias), and the grid of bm x bn tiles.
+static void prepare_tiles(GemmArgs& a, int bm, int bn) {
+  a.has_rowsum = a.a_rowsum != nullptr;
+  if (a.a_rowsum == nullptr) a.a_rowsum = a.col_term;
+  if (a.bias == nullptr) a.bias = a.alpha;
+  a.grid_m = (a.M + bm - 1) / bm;
+  a.grid_n = (a.N + bn - 1) / bn;
+}
+
+// ---- free-running generated kernels (tools/gen_fr_asm.py -> mq_gemm_fr*_asm.inc) ------------------------------------------------------
+// The whole workgroup program (prologue, software-pipelined main loop, epilogue) is generated gfx950 ISA; C++ only forms the tile, the
+// per-lane addresses and the scalar arguments and hands them to one asm statement.  That shim is written once, as the phases below; a
+// kernel is its choice of phases, the operands of its own epilogue, and the asm statement.  Two rules hold for every one of them:
+//  * Nothing in front of the generated program may wait for memory beyond the kernel arguments: the first LDS-DMA requests leave as soon
+//    as the tile's addresses are formed (the output grid is loaded and inverted INSIDE the program, behind them; the row-sum zeroing of
+//    the gated pair's first launch follows the program).
+//  * Every scalar operand goes through readfirstlane: an "s" constraint alone does not stop hipcc from handing over a VGPR.
+// The phases are statement macros, not functions: hipcc simplifies an inline function on its own before it inlines it, and the code in
+// front of the program then differs from kernel to kernel in instruction count and register names (measured: all 14 kernels, +-1..8
+// instructions); expanded in place, in the order tile, W pieces, rows, pointers, scalars (the epilogue's own pointers where its kernels have always formed them), it is the same for every kernel as if written
+// out.  They declare the locals the operand lists below name, for a `const GemmArgs& args` in scope.
+
+// lane, wave and the tile of block BID of NBLK (BMT = 32 x waves, stacked along M); problem shape; K stages.  SPLITK (FR128RS): blocks
+// [0, NBLK) take the first half of K (role 0), blocks [NBLK, 2 NBLK) the second (dispatched after every first-half workgroup: the
+// partner a wave waits for is always resident or finished).
+#define MQ_FR_TILE(BMT, BNT, SPLITK, BID, NBLK, GROUP_M)                                                                           \
+  const int lane = threadIdx.x & 63;                                                                                               \
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                                               \
+  int tm, tn;                                                                                                                      \
+  const int ntiles = (NBLK);                                                                                                       \
+  const int role = (SPLITK) ? __builtin_amdgcn_readfirstlane((BID) >= ntiles ? 1 : 0) : 0;                                         \
+  const int tile = (BID) - role * ntiles;                                                                                          \
+  tile_of_block(tile, ntiles, args.grid_m, args.grid_n, tm, tn, GROUP_M);                                                          \
+  const int m0 = tm * (BMT), n0 = tn * (BNT);                                                                                      \
+  const int M = args.M, N = args.N, K = args.K;                                                                                    \
+  const int KT = ((SPLITK) ? K / 2 : K) / BK
+
+// LDS-DMA source offsets sw[0 .. PCS) of this wave's W pieces, int8 weights: 8 rows x 128 B each, piece wave + NWV i, XOR-swizzled like
+// the other variants (16-byte chunk c of row r comes from chunk c ^ (r & 7))
+#define MQ_FR_W_PIECES(PCS, NWV)                                                                                                   \
+  _Pragma("unroll") for (int i = 0; i < (PCS); ++i) {                                                                              \
+    int row = n0 + (wave + i * (NWV)) * 8 + (lane >> 3);                                                                           \
+    row = row < N ? row : N - 1;                                                                                                   \
+    sw[i] = (unsigned)row * (unsigned)K + (unsigned)(((lane & 7) ^ (lane >> 3)) << 4);                                             \
+  }
+
+// ... packed 4-bit weights (mq_pack_w4): 16 rows x 64 packed bytes each.  CLAMP: the tile has fewer pieces (FNT) than PCS rounds of
+// waves, the waves beyond load the last one again.  IMAGE (frw4 / frw4_128): the pieces go through the LDS as they are, chunks swizzled
+// {0, 3, 2, 1}[(r >> 2) & 3]; otherwise they are loaded into registers and there is no LDS image.
+#define MQ_FR_W4_PIECES(PCS, NWV, FNT, CLAMP, IMAGE)                                                                               \
+  _Pragma("unroll") for (int i = 0; i < (PCS); ++i) {                                                                              \
+    const int r = lane >> 2; /* row of the piece */                                                                                \
+    int piece = wave + i * (NWV);                                                                                                  \
+    if (CLAMP) piece = piece < (FNT) ? piece : (FNT) - 1;                                                                          \
+    int row = n0 + piece * 16 + r;                                                                                                 \
+    row = row < N ? row : N - 1;                                                                                                   \
+    const int g = (IMAGE) ? (4 - ((r >> 2) & 3)) & 3 : 0;                                                                          \
+    sw[i] = (unsigned)row * (unsigned)(K >> 1) + (unsigned)((((lane & 3) ^ g)) << 4);                                              \
+  }
+
+// The wave's 32 rows.  Fragment-blocked A (mq_quantize_tiled): row block rb (clamped to the last one), k block kb at
+// ((rb * K/64) + kb) KiB, lane-linear inside.
+#define MQ_FR_ROW_BLOCKS                                                                                                           \
+  const int m0w = m0 + wave * 32;                                                                                                  \
+  const unsigned rb_max = (unsigned)((M + 15) >> 4) - 1;                                                                           \
+  unsigned rb0 = (unsigned)(m0w >> 4), rb1 = rb0 + 1;                                                                              \
+  rb0 = rb0 < rb_max ? rb0 : rb_max;                                                                                               \
+  rb1 = rb1 < rb_max ? rb1 : rb_max
+// offsets of the wave's two activation fragments (LOFS: the lane's offset inside a row block's 1-KiB k block) and of their row sums
+#define MQ_FR_FRAGMENTS(LOFS)                                                                                                      \
+  const unsigned av0 = (rb0 * (unsigned)(K >> 6)) * 1024u + (LOFS);                                                                \
+  const unsigned av1 = (rb1 * (unsigned)(K >> 6)) * 1024u + (LOFS);                                                                \
+  unsigned rsofs[2];                                                                                                               \
+  _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                                  \
+    int m = m0w + i * 16 + (lane & 15);                                                                                            \
+    m = args.has_rowsum ? (m < M ? m : M - 1) : 0;                                                                                 \
+    rsofs[i] = (unsigned)m * 4u;                                                                                                   \
+  }
+#define MQ_FR_LANE_LINEAR ((unsigned)lane << 4)
+
+// operand and parameter pointers, the per-n vectors at the tile's first column.  Split-K role 1: k blocks K / 128 .. of the
+// fragment-blocked image (1 KiB each), byte K / 2 of every weight row.
+#define MQ_FR_POINTERS                                                                                                             \
+  const int8_t* a_ptr = args.a + (size_t)role * (size_t)(K >> 7) * 1024u;                                                          \
+  const int8_t* w_ptr = reinterpret_cast<const int8_t*>(args.w) + (size_t)role * (size_t)(K >> 1);                                 \
+  const float* alpha_p = args.alpha + n0;                                                                                          \
+  const float* bias_p = args.bias + n0;                                                                                            \
+  const int32_t* wzp_p = args.w_zp + n0;                                                                                           \
+  const int32_t* ct_p = args.col_term + n0;                                                                                        \
+  const int32_t* rs_p = args.a_rowsum
+
+// scalar operands; cg0, mb0: the tile's first 16-column group and the wave's first 16-row block (gate epilogue).  XORV: MQ_FR_XORV in
+// the kernels that have always formed xorv here (fr, frw4*), empty otherwise (fr128 / fr160 form it behind the column grid): hipcc's
+// code in front of the program follows the position.
+#define MQ_FR_SCALARS(BNT, XORV)                                                                                                       \
+  const int mrem = __builtin_amdgcn_readfirstlane(M - m0w);                                                                        \
+  const int flags = __builtin_amdgcn_readfirstlane((args.has_bias ? 1 : 0) | (args.has_rowsum ? 2 : 0) | (role ? 4 : 0));          \
+  XORV                                                                                                                             \
+  const int ldn = __builtin_amdgcn_readfirstlane(N), kt = __builtin_amdgcn_readfirstlane(KT);                                      \
+  const int cg0 = __builtin_amdgcn_readfirstlane(tn * ((BNT) / 16)), mb0 = __builtin_amdgcn_readfirstlane(m0w >> 4);               \
+  const unsigned tid = threadIdx.x
+
+// this thread's column (tid < BNT) and its output grid (invc, ooc): segment 0 = out_scale / out_offset, later segments their own
+#define MQ_FR_COLUMN_GRID(BNT)                                                                                                     \
+  const int n = n0 + (int)(tid < (unsigned)(BNT) ? tid : (unsigned)(BNT) - 1u);                                                    \
+  float sc = args.out_scale[0], ooc = args.out_offset[0];                                                                          \
+  if (args.seg_scale[0] != nullptr) {                                                                                              \
+    const int sg = (n >= args.seg_end[0]) + (args.seg_scale[1] != nullptr && n >= args.seg_end[1]);                                \
+    if (sg > 0) {                                                                                                                  \
+      sc = args.seg_scale[sg - 1][0];                                                                                              \
+      ooc = args.seg_offset[sg - 1][0];                                                                                            \
+    }                                                                                                                              \
+  }                                                                                                                                \
+  const float invc = __fdiv_rn(1.0f, sc)
+
+// the 8-bit index epilogue (fr / fr128 / fr160 / frw4*): u8 storage, or i8 storage = index - 128
+#define MQ_FR_INDEX_OUT uint8_t* outw = reinterpret_cast<uint8_t*>(args.out) + (size_t)m0w * N + n0
+#define MQ_FR_XORV const int xorv = __builtin_amdgcn_readfirstlane(args.out_dtype == MQ_I8 ? (int)0x80808080u : 0);
+
+// the residual epilogue (fr128r / fr128r8 / fr128rs / frw4x_128r): fp32 out = resid + Q16(linear), the 16-bit grid's clamp as scalars
+#define MQ_FR_RESIDUAL                                                                                                             \
+  const int qmin_bits = __builtin_amdgcn_readfirstlane(__float_as_int(args.out_qmin));                                             \
+  const int qmax_bits = __builtin_amdgcn_readfirstlane(__float_as_int(args.out_qmax));                                             \
+  float* outw = reinterpret_cast<float*>(args.out) + (size_t)m0w * N + n0;                                                         \
+  const float* resid = args.resid + (size_t)m0w * N + n0
+
+// the gate epilogue (frg / frg128 / frgw4x / frgw4x_128): w1's indices of the tile, the row sums of w2's input image
+#define MQ_FR_GATE                                                                                                                 \
+  const uint8_t* aidx = args.gate_aidx + (size_t)m0w * N + n0;                                                                     \
+  int32_t* rsout = args.gate_rowsum + m0w
+
+// behind the program: the first launch of a gated pair zeroes the row sums the second one accumulates into (THREADS ints per workgroup)
+#define MQ_FR_ZERO_TAIL(BID, THREADS)                                                                                              \
+  if (args.zero_buf != nullptr) {                                                                                                  \
+    const int zi = (BID) * (THREADS) + (int)threadIdx.x;                                                                           \
+    if (zi < args.zero_count) args.zero_buf[zi] = 0;                                                                               \
+  }
+
+// The operands every program takes (names: the generator's); a variant appends the operands of its own epilogue and its W pieces.
+#define MQ_FR_BASE_OPERANDS                                                                                                        \
+  [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [alpha] "s"(alpha_p), [bias] "s"(bias_p), [wzp] "s"(wzp_p), \
+      [ct] "s"(ct_p), [rsptr] "s"(rs_p), [ldn] "s"(ldn), [mrem] "s"(mrem), [flags] "s"(flags), [av0] "v"(av0), [av1] "v"(av1),    \
+      [tid] "v"(tid), [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1])
+// one output grid, loaded and inverted inside the program
+#define MQ_FR_GRID_OPERANDS [soptr] "s"(args.out_scale), [ooptr] "s"(args.out_offset)
+#define MQ_FR_INDEX_OPERANDS MQ_FR_BASE_OPERANDS, [outw] "s"(outw), [xorv] "s"(xorv)
+#define MQ_FR_RESIDUAL_OPERANDS \
+  MQ_FR_BASE_OPERANDS, MQ_FR_GRID_OPERANDS, [outw] "s"(outw), [resid] "s"(resid), [qmin] "s"(qmin_bits), [qmax] "s"(qmax_bits)
+#define MQ_FR_GATE_OPERANDS                                                                                                        \
+  MQ_FR_BASE_OPERANDS, MQ_FR_GRID_OPERANDS, [aidx] "s"(aidx), [table] "s"(args.gate_table), [qout] "s"(args.gate_q),               \
+      [rsout] "s"(rsout), [cg0] "s"(cg0), [mb0] "s"(mb0)
+
+// fr: 256 x 176 tile, fragment-blocked activations, int8 weights, 8-bit UNSIGNED output grid (u8 storage, or i8 storage = index - 128),
+// K % 256 == 0, K >= 768.
 __device__ __forceinline__ void gemm_i8_fr_body(const GemmArgs& args, int bid, int nblk) {
-  // Nothing in front of the generated program may wait for memory beyond the kernel arguments: the first LDS-DMA requests leave as soon
-  // as the tile's addresses are formed (the output grid is loaded and inverted INSIDE the program, behind them; the row-sum zeroing of
-  // the gated pair's first launch follows the program).
 #if MQ_FR_ASM_STAMP
   const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
 #endif
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int tm, tn;
-  tile_of_block(bid, nblk, args.grid_m, args.grid_n, tm, tn);
-  const int m0 = tm * 256, n0 = tn * 176;
-  const int M = args.M, N = args.N, K = args.K;
-  const int KT = K / BK;
-  // LDS-DMA source offsets of this wave's W pieces (8 rows x 128 B each; piece wave + 8 i), XOR-swizzled like the other variants
+  constexpr int BNT = 176;
+  MQ_FR_TILE(256, BNT, false, bid, nblk, 0);
   unsigned sw[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    int row = n0 + (wave + i * 8) * 8 + (lane >> 3);
-    row = row < N ? row : N - 1;
-    sw[i] = (unsigned)row * (unsigned)K + (unsigned)(((lane & 7) ^ (lane >> 3)) << 4);
-  }
-  // fragment-blocked A (mq_quantize_tiled): row block rb, k block kb at ((rb * K/64) + kb) KiB, lane-linear inside
-  const int m0w = m0 + wave * 32;
-  const unsigned rb_max = (unsigned)((M + 15) >> 4) - 1;
-  unsigned rb0 = (unsigned)(m0w >> 4), rb1 = rb0 + 1;
-  rb0 = rb0 < rb_max ? rb0 : rb_max;
-  rb1 = rb1 < rb_max ? rb1 : rb_max;
-  const unsigned av0 = (rb0 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  const unsigned av1 = (rb1 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  unsigned rsofs[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0w + i * 16 + (lane & 15);
-    m = args.has_rowsum ? (m < M ? m : M - 1) : 0;
-    rsofs[i] = (unsigned)m * 4u;
-  }
-  const float* so_ptr = args.out_scale;
-  const float* oo_ptr = args.out_offset;
-  const int8_t* a_ptr = args.a;
-  const int8_t* w_ptr = reinterpret_cast<const int8_t*>(args.w);
-  const float* alpha_p = args.alpha + n0;
-  const float* bias_p = args.bias + n0;
-  const int32_t* wzp_p = args.w_zp + n0;
-  const int32_t* ct_p = args.col_term + n0;
-  const int32_t* rs_p = args.a_rowsum;
-  uint8_t* outw = reinterpret_cast<uint8_t*>(args.out) + (size_t)m0w * N + n0;
-  // (explicit readfirstlane: an "s" constraint alone does not stop hipcc from handing over a VGPR)
-  const int mrem = __builtin_amdgcn_readfirstlane(M - m0w);
-  const int flags = __builtin_amdgcn_readfirstlane((args.has_bias ? 1 : 0) | (args.has_rowsum ? 2 : 0));
-  const int xorv = __builtin_amdgcn_readfirstlane(args.out_dtype == MQ_I8 ? (int)0x80808080u : 0);
-  const int ldn = __builtin_amdgcn_readfirstlane(N), kt = __builtin_amdgcn_readfirstlane(KT);
-  const unsigned tid = threadIdx.x;
+  MQ_FR_W_PIECES(3, 8)
+  MQ_FR_ROW_BLOCKS;
+  MQ_FR_FRAGMENTS(MQ_FR_LANE_LINEAR)
+  MQ_FR_POINTERS;
+  MQ_FR_INDEX_OUT;
+  MQ_FR_SCALARS(BNT, MQ_FR_XORV);
 #if MQ_FR_ASM_PROBE
   // clock probe (mq_gemm_set_clock_probe): 8 bytes per wave = [shader cycles, 100-MHz real-time ticks] of the generated program
   unsigned long long* dbg = args.dbg_ts ? args.dbg_ts + ((size_t)bid * 8 + wave) : nullptr;
@@ -831,22 +962,16 @@ __device__ __forceinline__ void gemm_i8_fr_body(const GemmArgs& args, int bid, i
 #endif
   asm volatile(MQ_FR_ASM_BODY
                :
-               : [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [outw] "s"(outw), [alpha] "s"(alpha_p),
-                 [bias] "s"(bias_p), [wzp] "s"(wzp_p), [ct] "s"(ct_p), [rsptr] "s"(rs_p), [soptr] "s"(so_ptr), [ooptr] "s"(oo_ptr),
-                 [ldn] "s"(ldn), [mrem] "s"(mrem), [flags] "s"(flags), [xorv] "s"(xorv),
+               : MQ_FR_INDEX_OPERANDS, MQ_FR_GRID_OPERANDS,
 #if MQ_FR_ASM_STAMP
                  [dbg] "s"(dbg), [tentry_lo] "s"(te_lo), [tentry_hi] "s"(te_hi),
 #endif
 #if MQ_FR_ASM_PROBE
                  [dbg] "s"(dbg),
 #endif
-                 [sw0] "v"(sw[0]), [sw1] "v"(sw[1]), [sw2] "v"(sw[2]), [av0] "v"(av0), [av1] "v"(av1), [tid] "v"(tid),
-                 [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1])
+                 [sw0] "v"(sw[0]), [sw1] "v"(sw[1]), [sw2] "v"(sw[2])
                : MQ_FR_ASM_CLOBBERS);
-  if (args.zero_buf != nullptr) {                                   // (gated pair, first launch: 512 ints per workgroup)
-    const int zi = bid * 512 + (int)threadIdx.x;
-    if (zi < args.zero_count) args.zero_buf[zi] = 0;
-  }
+  MQ_FR_ZERO_TAIL(bid, 512)
 }
 
 __global__ void __launch_bounds__(512) gemm_i8_fr_kernel(const GemmArgs args) { gemm_i8_fr_body(args, blockIdx.x, args.grid_m * args.grid_n); }
@@ -858,75 +983,31 @@ __global__ void __launch_bounds__(512) gemm_i8_fr_kernel(const GemmArgs args) { 
 // FR160: 128 x 160 tiles, four waves, per-column 8-bit grids: q | k | v at M = 2048 is 16 x 16 = 256 tiles, one per CU (256 x 128 tiles: 160).
 enum { FR128 = 1, FR128R = 2, FR128R8 = 3, FR160 = 4, FR128RS = 5 };   // FR128RS: FR128R8's tile with the K loop split over two workgroups
 template <int VAR>
+struct Fr128 {
+  static constexpr int NW = (VAR == FR128R || VAR == FR160) ? 4 : 8;
+  static constexpr int BMT = 32 * NW;
+  static constexpr int BNT = VAR == FR160 ? 160 : 128;
+  static constexpr int LDS = VAR == FR128 ? MQ_FR128_LDS_BYTES
+                                          : (VAR == FR128R ? MQ_FR128R_LDS_BYTES
+                                                           : (VAR == FR160 ? MQ_FR160_LDS_BYTES : (VAR == FR128RS ? MQ_FR128RS_LDS_BYTES : MQ_FR128R8_LDS_BYTES)));
+};
+
+template <int VAR>
 __device__ __forceinline__ void gemm_i8_fr128_body(const GemmArgs& args) {
-  constexpr int NWV = (VAR == FR128R || VAR == FR160) ? 4 : 8;
-  constexpr int BMT = 32 * NWV;
-  constexpr int BNT = VAR == FR160 ? 160 : 128;
-  constexpr int PCS = BNT / 8 / NWV;            // W LDS-DMA pieces (8 rows x 128 B) per wave and stage
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int tm, tn;
-  const int ntiles = args.grid_m * args.grid_n;
-  // split-K (FR128RS): blocks [0, tiles) take the first half of K, blocks [tiles, 2 tiles) the second (dispatched after every first-half
-  // workgroup: the partner a wave waits for is always resident or finished)
-  const int role = VAR == FR128RS ? __builtin_amdgcn_readfirstlane((int)blockIdx.x >= ntiles ? 1 : 0) : 0;
-  const int tile = (int)blockIdx.x - role * ntiles;
-  tile_of_block(tile, ntiles, args.grid_m, args.grid_n, tm, tn, args.group_m);
-  const int m0 = tm * BMT, n0 = tn * BNT;
-  const int M = args.M, N = args.N, K = args.K;
-  const int KT = (VAR == FR128RS ? K / 2 : K) / BK;
+  constexpr int NW = Fr128<VAR>::NW, BNT = Fr128<VAR>::BNT;
+  constexpr int PCS = BNT / 8 / NW;             // W LDS-DMA pieces (8 rows x 128 B) per wave and stage
+  MQ_FR_TILE(32 * NW, BNT, VAR == FR128RS, (int)blockIdx.x, args.grid_m * args.grid_n, args.group_m);
   unsigned sw[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-  for (int i = 0; i < PCS; ++i) {
-    int row = n0 + (wave + i * NWV) * 8 + (lane >> 3);
-    row = row < N ? row : N - 1;
-    sw[i] = (unsigned)row * (unsigned)K + (unsigned)(((lane & 7) ^ (lane >> 3)) << 4);
-  }
-  const int m0w = m0 + wave * 32;
-  const unsigned rb_max = (unsigned)((M + 15) >> 4) - 1;
-  unsigned rb0 = (unsigned)(m0w >> 4), rb1 = rb0 + 1;
-  rb0 = rb0 < rb_max ? rb0 : rb_max;
-  rb1 = rb1 < rb_max ? rb1 : rb_max;
-  const unsigned av0 = (rb0 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  const unsigned av1 = (rb1 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  unsigned rsofs[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0w + i * 16 + (lane & 15);
-    m = args.has_rowsum ? (m < M ? m : M - 1) : 0;
-    rsofs[i] = (unsigned)m * 4u;
-  }
-  // second K half: k blocks K / 128 .. of the fragment-blocked image (1 KiB each), byte K / 2 of every weight row
-  const int8_t* a_ptr = args.a + (size_t)role * (size_t)(K >> 7) * 1024u;
-  const int8_t* w_ptr = reinterpret_cast<const int8_t*>(args.w) + (size_t)role * (size_t)(K >> 1);
-  const float* alpha_p = args.alpha + n0;
-  const float* bias_p = args.bias + n0;
-  const int32_t* wzp_p = args.w_zp + n0;
-  const int32_t* ct_p = args.col_term + n0;
-  const int32_t* rs_p = args.a_rowsum;
-  const int mrem = __builtin_amdgcn_readfirstlane(M - m0w);
-  const int flags = __builtin_amdgcn_readfirstlane((args.has_bias ? 1 : 0) | (args.has_rowsum ? 2 : 0) | (role ? 4 : 0));
-  const int ldn = __builtin_amdgcn_readfirstlane(N), kt = __builtin_amdgcn_readfirstlane(KT);
-  const unsigned tid = threadIdx.x;
+  MQ_FR_W_PIECES(PCS, NW)
+  MQ_FR_ROW_BLOCKS;
+  MQ_FR_FRAGMENTS(MQ_FR_LANE_LINEAR)
+  MQ_FR_POINTERS;
+  MQ_FR_SCALARS(BNT, );
   if constexpr (VAR == FR128 || VAR == FR160) {
-    // this thread's column (tid < BNT) and its output grid: segment 0 = out_scale / out_offset, later segments their own
-    const int n = n0 + (int)(tid < (unsigned)BNT ? tid : (unsigned)BNT - 1u);
-    float sc = args.out_scale[0], ooc = args.out_offset[0];
-    if (args.seg_scale[0] != nullptr) {
-      const int sg = (n >= args.seg_end[0]) + (args.seg_scale[1] != nullptr && n >= args.seg_end[1]);
-      if (sg > 0) {
-        sc = args.seg_scale[sg - 1][0];
-        ooc = args.seg_offset[sg - 1][0];
-      }
-    }
-    const float invc = __fdiv_rn(1.0f, sc);
-    uint8_t* outw = reinterpret_cast<uint8_t*>(args.out) + (size_t)m0w * N + n0;
-    const int xorv = __builtin_amdgcn_readfirstlane(args.out_dtype == MQ_I8 ? (int)0x80808080u : 0);
-#define MQ_FR128U_OPERANDS                                                                                                        \
-    [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [outw] "s"(outw), [alpha] "s"(alpha_p),                  \
-        [bias] "s"(bias_p), [wzp] "s"(wzp_p), [ct] "s"(ct_p), [rsptr] "s"(rs_p), [ldn] "s"(ldn), [mrem] "s"(mrem),                 \
-        [flags] "s"(flags), [xorv] "s"(xorv), [sw0] "v"(sw[0]), [sw1] "v"(sw[1]), [av0] "v"(av0), [av1] "v"(av1),                  \
-        [tid] "v"(tid), [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1]), [invc] "v"(invc), [ooc] "v"(ooc)
+    MQ_FR_COLUMN_GRID(BNT);
+    MQ_FR_INDEX_OUT;
+    MQ_FR_XORV
+#define MQ_FR128U_OPERANDS MQ_FR_INDEX_OPERANDS, [invc] "v"(invc), [ooc] "v"(ooc), [sw0] "v"(sw[0]), [sw1] "v"(sw[1])
     if constexpr (VAR == FR128) {
       asm volatile(MQ_FR128_ASM_BODY : : MQ_FR128U_OPERANDS : MQ_FR128_ASM_CLOBBERS);
     } else {
@@ -934,39 +1015,31 @@ __device__ __forceinline__ void gemm_i8_fr128_body(const GemmArgs& args) {
     }
 #undef MQ_FR128U_OPERANDS
   } else {
-    const float* so_ptr = args.out_scale;
-    const float* oo_ptr = args.out_offset;
-    const int qmin_bits = __builtin_amdgcn_readfirstlane(__float_as_int(args.out_qmin));
-    const int qmax_bits = __builtin_amdgcn_readfirstlane(__float_as_int(args.out_qmax));
-    float* outw = reinterpret_cast<float*>(args.out) + (size_t)m0w * N + n0;
-    const float* resid = args.resid + (size_t)m0w * N + n0;
-#define MQ_FR128R_OPERANDS                                                                                                          \
-    [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [outw] "s"(outw), [resid] "s"(resid), [alpha] "s"(alpha_p), \
-        [bias] "s"(bias_p), [wzp] "s"(wzp_p), [ct] "s"(ct_p), [rsptr] "s"(rs_p), [soptr] "s"(so_ptr), [ooptr] "s"(oo_ptr),       \
-        [qmin] "s"(qmin_bits), [qmax] "s"(qmax_bits), [ldn] "s"(ldn), [mrem] "s"(mrem), [flags] "s"(flags),      \
-        [av0] "v"(av0), [av1] "v"(av1), [tid] "v"(tid), [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1]), [sw0] "v"(sw[0]), [sw1] "v"(sw[1])
+    MQ_FR_RESIDUAL;
     if constexpr (VAR == FR128R) {
-      asm volatile(MQ_FR128R_ASM_BODY : : MQ_FR128R_OPERANDS, [sw2] "v"(sw[2]), [sw3] "v"(sw[3]) : MQ_FR128R_ASM_CLOBBERS);
+      asm volatile(MQ_FR128R_ASM_BODY
+                   :
+                   : MQ_FR_RESIDUAL_OPERANDS, [sw0] "v"(sw[0]), [sw1] "v"(sw[1]), [sw2] "v"(sw[2]), [sw3] "v"(sw[3])
+                   : MQ_FR128R_ASM_CLOBBERS);
 #ifdef MQ_BUILD_EXPERIMENTS
     } else if constexpr (VAR == FR128RS) {
       // the tile's exchange area: 2 x 8 x 8 KiB of partial sums, 2 x 8 flags (gemm_splitk_scratch)
       const char* xch = reinterpret_cast<const char*>(args.gate_q) + (size_t)tile * 131072u;
       const int* xfl = reinterpret_cast<const int*>(args.gate_rowsum) + (size_t)tile * 16u;
-      asm volatile(MQ_FR128RS_ASM_BODY : : MQ_FR128R_OPERANDS, [xch] "s"(xch), [xfl] "s"(xfl) : MQ_FR128RS_ASM_CLOBBERS);
+      asm volatile(MQ_FR128RS_ASM_BODY
+                   :
+                   : MQ_FR_RESIDUAL_OPERANDS, [sw0] "v"(sw[0]), [sw1] "v"(sw[1]), [xch] "s"(xch), [xfl] "s"(xfl)
+                   : MQ_FR128RS_ASM_CLOBBERS);
 #endif
     } else {
-      asm volatile(MQ_FR128R8_ASM_BODY : : MQ_FR128R_OPERANDS : MQ_FR128R8_ASM_CLOBBERS);
+      asm volatile(MQ_FR128R8_ASM_BODY : : MQ_FR_RESIDUAL_OPERANDS, [sw0] "v"(sw[0]), [sw1] "v"(sw[1]) : MQ_FR128R8_ASM_CLOBBERS);
     }
-#undef MQ_FR128R_OPERANDS
   }
-  if (args.zero_buf != nullptr) {               // (gated pair, first launch)
-    const int zi = (int)blockIdx.x * (64 * NWV) + (int)threadIdx.x;
-    if (zi < args.zero_count) args.zero_buf[zi] = 0;
-  }
+  MQ_FR_ZERO_TAIL((int)blockIdx.x, 64 * NW)      // (gated pair, first launch)
 }
 
 template <int VAR>
-__global__ void __launch_bounds__((VAR == FR128R || VAR == FR160) ? 256 : 512) gemm_i8_fr128_kernel(const GemmArgs args) { gemm_i8_fr128_body<VAR>(args); }
+__global__ void __launch_bounds__(64 * Fr128<VAR>::NW) gemm_i8_fr128_kernel(const GemmArgs args) { gemm_i8_fr128_body<VAR>(args); }
 
 // shapes the 128-column generated kernels serve (fragment-blocked activations, int8 weights)
 static bool gemm_fr128_shape(int64_t M, int64_t N, int64_t K) { return M > 0 && N % 128 == 0 && K % 256 == 0 && K >= 768; }
@@ -1010,232 +1083,87 @@ static int gemm_splitk_scratch(int tiles, char** xch, int** xfl) {
 
 template <int VAR>
 static int launch_fr128(GemmArgs a, hipStream_t st) {
-  constexpr int LDS = VAR == FR128 ? MQ_FR128_LDS_BYTES
-                                   : (VAR == FR128R ? MQ_FR128R_LDS_BYTES
-                                                    : (VAR == FR160 ? MQ_FR160_LDS_BYTES : (VAR == FR128RS ? MQ_FR128RS_LDS_BYTES : MQ_FR128R8_LDS_BYTES)));
-  constexpr int BMT = (VAR == FR128R || VAR == FR160) ? 128 : 256;
-  constexpr int BNT = VAR == FR160 ? 160 : 128;
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_fr128_kernel<VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
-  a.has_rowsum = a.a_rowsum != nullptr;
-  if (a.a_rowsum == nullptr) a.a_rowsum = a.col_term;
-  if (a.bias == nullptr) a.bias = a.alpha;
-  a.grid_m = (a.M + BMT - 1) / BMT;
-  a.grid_n = a.N / BNT;
+  prepare_tiles(a, Fr128<VAR>::BMT, Fr128<VAR>::BNT);
   a.group_m = g_group_m.load();
+  int blocks = a.grid_m * a.grid_n;
   if constexpr (VAR == FR128RS) {
     char* xch = nullptr;
     int* xfl = nullptr;
-    const int rc = gemm_splitk_scratch(a.grid_m * a.grid_n, &xch, &xfl);
+    const int rc = gemm_splitk_scratch(blocks, &xch, &xfl);
     if (rc != MQ_OK) return rc;
     a.gate_q = reinterpret_cast<int8_t*>(xch);            // (fields of the gated pair, unused by the residual GEMMs)
     a.gate_rowsum = reinterpret_cast<int32_t*>(xfl);
-    gemm_i8_fr128_kernel<VAR><<<2 * a.grid_m * a.grid_n, 512, LDS, st>>>(a);
-    MQ_LAUNCH_CHECK("mq_gemm");
-    return MQ_OK;
+    blocks *= 2;
   }
-  gemm_i8_fr128_kernel<VAR><<<a.grid_m * a.grid_n, (VAR == FR128R || VAR == FR160) ? 256 : 512, LDS, st>>>(a);
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+  return launch_kernel<gemm_i8_fr128_kernel<VAR>>(a, blocks, 64 * Fr128<VAR>::NW, Fr128<VAR>::LDS, st);
 }
 
 // ---- packed 4-bit weights on the free-running program (tools/gen_fr_asm.py variants frw4 / frw4_128, round 4) --------------------------
 // mq_pack_w4's image (two unsigned nibbles per byte; 16 bytes = 32 consecutive k, element p low / p + 16 high in byte p) goes through the
 // LDS ring as it is (LDS-DMA pieces of 16 rows x 64 B); a lane's single ds_read_b128 per 16 columns and stage holds both of its MFMA
-// operands of that stage, split in registers.  The activation fragments are gathered to match (type A = k 32 q + 0..15, type B = + 16..31
-// of the stage: per-lane offsets below).  256 x BNT tiles, eight waves, 8-bit unsigned output grid (BNT = 176: one grid; 128: per column).
+// operands of that stage, split in registers.  The activation fragments are gathered to match (lofs below).  256 x BNT tiles, eight
+// waves, 8-bit unsigned output grid (BNT = 176: one grid; 128: per column).
 // X (frw4x / frw4x_128): the packed pieces go wave-privately through registers, are expanded ONCE per workgroup into the int8 W ring, and
 // the loop is the int8 kernel's (standard activation fragments); !X (frw4 / frw4_128): every wave unpacks its own fragments.
 template <int BNT, bool X>
 __global__ void __launch_bounds__(512) gemm_i8_frw4_kernel(const GemmArgs args) {
   constexpr int FNT = BNT / 16;
   constexpr int PCS = (FNT + 7) / 8;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int tm, tn;
-  tile_of_block(blockIdx.x, args.grid_m * args.grid_n, args.grid_m, args.grid_n, tm, tn);
-  const int m0 = tm * 256, n0 = tn * BNT;
-  const int M = args.M, N = args.N, K = args.K;
-  const int KT = K / BK;
+  MQ_FR_TILE(256, BNT, false, (int)blockIdx.x, args.grid_m * args.grid_n, 0);
   unsigned sw[3] = {0, 0, 0};
-#pragma unroll
-  for (int i = 0; i < PCS; ++i) {
-    const int r = lane >> 2;                                   // row of the piece (16 rows x 64 B)
-    int piece = wave + i * 8;
-    piece = piece < FNT ? piece : FNT - 1;
-    int row = n0 + piece * 16 + r;
-    row = row < N ? row : N - 1;
-    const int g = X ? 0 : (4 - ((r >> 2) & 3)) & 3;            // LDS image of the packed rows: {0, 3, 2, 1}[(r >> 2) & 3]; X: no LDS image
-    sw[i] = (unsigned)row * (unsigned)(K >> 1) + (unsigned)((((lane & 3) ^ g)) << 4);
-  }
-  const int m0w = m0 + wave * 32;
-  const unsigned rb_max = (unsigned)((M + 15) >> 4) - 1;
-  unsigned rb0 = (unsigned)(m0w >> 4), rb1 = rb0 + 1;
-  rb0 = rb0 < rb_max ? rb0 : rb_max;
-  rb1 = rb1 < rb_max ? rb1 : rb_max;
-  // type-A fragment of lane (frow, kq): x[row, 128 s + 32 kq + 0..15] = k block 2 s + (kq >> 1), quarter 2 (kq & 1); type B: + 256 bytes
+  MQ_FR_W4_PIECES(PCS, 8, FNT, true, !X)
+  MQ_FR_ROW_BLOCKS;
+  // !X: the fragments are gathered to match the packed nibbles -- type-A fragment of lane (frow, kq): x[row, 128 s + 32 kq + 0..15] =
+  // k block 2 s + (kq >> 1), quarter 2 (kq & 1); type B: + 256 bytes
   const unsigned frow = (unsigned)lane & 15u, kq = (unsigned)lane >> 4;
-  const unsigned lofs = X ? ((unsigned)lane << 4) : (kq >> 1) * 1024u + ((2u * (kq & 1u)) * 16u + frow) * 16u;
-  const unsigned av0 = (rb0 * (unsigned)(K >> 6)) * 1024u + lofs;
-  const unsigned av1 = (rb1 * (unsigned)(K >> 6)) * 1024u + lofs;
-  unsigned rsofs[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0w + i * 16 + (lane & 15);
-    m = args.has_rowsum ? (m < M ? m : M - 1) : 0;
-    rsofs[i] = (unsigned)m * 4u;
-  }
-  const int8_t* a_ptr = args.a;
-  const int8_t* w_ptr = reinterpret_cast<const int8_t*>(args.w);
-  const float* alpha_p = args.alpha + n0;
-  const float* bias_p = args.bias + n0;
-  const int32_t* wzp_p = args.w_zp + n0;
-  const int32_t* ct_p = args.col_term + n0;
-  const int32_t* rs_p = args.a_rowsum;
-  uint8_t* outw = reinterpret_cast<uint8_t*>(args.out) + (size_t)m0w * N + n0;
-  const int mrem = __builtin_amdgcn_readfirstlane(M - m0w);
-  const int flags = __builtin_amdgcn_readfirstlane((args.has_bias ? 1 : 0) | (args.has_rowsum ? 2 : 0));
-  const int xorv = __builtin_amdgcn_readfirstlane(args.out_dtype == MQ_I8 ? (int)0x80808080u : 0);
-  const int ldn = __builtin_amdgcn_readfirstlane(N), kt = __builtin_amdgcn_readfirstlane(KT);
-  const unsigned tid = threadIdx.x;
-#define MQ_FRW4_OPERANDS                                                                                                          \
-  [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [outw] "s"(outw), [alpha] "s"(alpha_p), [bias] "s"(bias_p),  \
-      [wzp] "s"(wzp_p), [ct] "s"(ct_p), [rsptr] "s"(rs_p), [ldn] "s"(ldn), [mrem] "s"(mrem), [flags] "s"(flags), [xorv] "s"(xorv),   \
-      [av0] "v"(av0), [av1] "v"(av1), [tid] "v"(tid), [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1])
+  const unsigned lofs = X ? MQ_FR_LANE_LINEAR : (kq >> 1) * 1024u + ((2u * (kq & 1u)) * 16u + frow) * 16u;
+  MQ_FR_FRAGMENTS(lofs)
+  MQ_FR_POINTERS;
+  MQ_FR_INDEX_OUT;
+  MQ_FR_SCALARS(BNT, MQ_FR_XORV);
+#define MQ_FRW4_PIECES [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]), [sw2] "+v"(sw[2])
   if constexpr (BNT == 176) {
-    const float* so_ptr = args.out_scale;
-    const float* oo_ptr = args.out_offset;
     if constexpr (X) {
-      asm volatile(MQ_FRW4X_ASM_BODY
-                   : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]), [sw2] "+v"(sw[2])
-                   : MQ_FRW4_OPERANDS, [soptr] "s"(so_ptr), [ooptr] "s"(oo_ptr)
-                   : MQ_FRW4X_ASM_CLOBBERS);
+      asm volatile(MQ_FRW4X_ASM_BODY : MQ_FRW4_PIECES : MQ_FR_INDEX_OPERANDS, MQ_FR_GRID_OPERANDS : MQ_FRW4X_ASM_CLOBBERS);
     } else {
 #ifdef MQ_BUILD_EXPERIMENTS
-      asm volatile(MQ_FRW4_ASM_BODY
-                   : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]), [sw2] "+v"(sw[2])
-                   : MQ_FRW4_OPERANDS, [soptr] "s"(so_ptr), [ooptr] "s"(oo_ptr)
-                   : MQ_FRW4_ASM_CLOBBERS);
+      asm volatile(MQ_FRW4_ASM_BODY : MQ_FRW4_PIECES : MQ_FR_INDEX_OPERANDS, MQ_FR_GRID_OPERANDS : MQ_FRW4_ASM_CLOBBERS);
 #endif
     }
   } else {
-    const int n = n0 + (int)(tid < (unsigned)BNT ? tid : (unsigned)BNT - 1u);
-    float sc = args.out_scale[0], ooc = args.out_offset[0];
-    if (args.seg_scale[0] != nullptr) {
-      const int sg = (n >= args.seg_end[0]) + (args.seg_scale[1] != nullptr && n >= args.seg_end[1]);
-      if (sg > 0) {
-        sc = args.seg_scale[sg - 1][0];
-        ooc = args.seg_offset[sg - 1][0];
-      }
-    }
-    const float invc = __fdiv_rn(1.0f, sc);
+    MQ_FR_COLUMN_GRID(BNT);
     if constexpr (X) {
-      asm volatile(MQ_FRW4X_128_ASM_BODY
-                   : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]), [sw2] "+v"(sw[2])
-                   : MQ_FRW4_OPERANDS, [invc] "v"(invc), [ooc] "v"(ooc)
-                   : MQ_FRW4X_128_ASM_CLOBBERS);
+      asm volatile(MQ_FRW4X_128_ASM_BODY : MQ_FRW4_PIECES : MQ_FR_INDEX_OPERANDS, [invc] "v"(invc), [ooc] "v"(ooc) : MQ_FRW4X_128_ASM_CLOBBERS);
     } else {
 #ifdef MQ_BUILD_EXPERIMENTS
-      asm volatile(MQ_FRW4_128_ASM_BODY
-                   : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]), [sw2] "+v"(sw[2])
-                   : MQ_FRW4_OPERANDS, [invc] "v"(invc), [ooc] "v"(ooc)
-                   : MQ_FRW4_128_ASM_CLOBBERS);
+      asm volatile(MQ_FRW4_128_ASM_BODY : MQ_FRW4_PIECES : MQ_FR_INDEX_OPERANDS, [invc] "v"(invc), [ooc] "v"(ooc) : MQ_FRW4_128_ASM_CLOBBERS);
 #endif
     }
   }
-#undef MQ_FRW4_OPERANDS
-  if (args.zero_buf != nullptr) {               // (packed gated pair, first launch: 512 ints per workgroup)
-    const int zi = (int)blockIdx.x * 512 + (int)threadIdx.x;
-    if (zi < args.zero_count) args.zero_buf[zi] = 0;
-  }
+#undef MQ_FRW4_PIECES
+  MQ_FR_ZERO_TAIL((int)blockIdx.x, 512)          // (packed gated pair, first launch)
 }
 
 // Packed 4-bit weights in front of the RESIDUAL epilogue (tools/gen_fr_asm.py variant frw4x_128r): o_proj / w2 from the mq_pack_w4 image
 // on 128 x 128 tiles, four waves -- fr128r's program with the W pieces (16 rows x 64 B, two per wave and stage) loaded into registers,
 // split and written into the int8 ring once per workgroup.  fp32 out = resid + Q16(linear).
 __global__ void __launch_bounds__(256) gemm_i8_frw4r_kernel(const GemmArgs args) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int tm, tn;
-  tile_of_block(blockIdx.x, args.grid_m * args.grid_n, args.grid_m, args.grid_n, tm, tn, args.group_m);
-  const int m0 = tm * 128, n0 = tn * 128;
-  const int M = args.M, N = args.N, K = args.K;
-  const int KT = K / BK;
+  constexpr int BNT = 128;
+  MQ_FR_TILE(128, BNT, false, (int)blockIdx.x, args.grid_m * args.grid_n, args.group_m);
   unsigned sw[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row = n0 + (wave + i * 4) * 16 + (lane >> 2);          // piece wave + 4 i: 16 rows x 64 packed bytes per stage
-    row = row < N ? row : N - 1;
-    sw[i] = (unsigned)row * (unsigned)(K >> 1) + (unsigned)((lane & 3) << 4);
-  }
-  const int m0w = m0 + wave * 32;
-  const unsigned rb_max = (unsigned)((M + 15) >> 4) - 1;
-  unsigned rb0 = (unsigned)(m0w >> 4), rb1 = rb0 + 1;
-  rb0 = rb0 < rb_max ? rb0 : rb_max;
-  rb1 = rb1 < rb_max ? rb1 : rb_max;
-  const unsigned av0 = (rb0 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  const unsigned av1 = (rb1 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  unsigned rsofs[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0w + i * 16 + (lane & 15);
-    m = args.has_rowsum ? (m < M ? m : M - 1) : 0;
-    rsofs[i] = (unsigned)m * 4u;
-  }
-  const int8_t* a_ptr = args.a;
-  const int8_t* w_ptr = reinterpret_cast<const int8_t*>(args.w);
-  const float* alpha_p = args.alpha + n0;
-  const float* bias_p = args.bias + n0;
-  const int32_t* wzp_p = args.w_zp + n0;
-  const int32_t* ct_p = args.col_term + n0;
-  const int32_t* rs_p = args.a_rowsum;
-  const float* so_ptr = args.out_scale;
-  const float* oo_ptr = args.out_offset;
-  const int qmin_bits = __builtin_amdgcn_readfirstlane(__float_as_int(args.out_qmin));
-  const int qmax_bits = __builtin_amdgcn_readfirstlane(__float_as_int(args.out_qmax));
-  float* outw = reinterpret_cast<float*>(args.out) + (size_t)m0w * N + n0;
-  const float* resid = args.resid + (size_t)m0w * N + n0;
-  const int mrem = __builtin_amdgcn_readfirstlane(M - m0w);
-  const int flags = __builtin_amdgcn_readfirstlane((args.has_bias ? 1 : 0) | (args.has_rowsum ? 2 : 0));
-  const int ldn = __builtin_amdgcn_readfirstlane(N), kt = __builtin_amdgcn_readfirstlane(KT);
-  const unsigned tid = threadIdx.x;
-  asm volatile(MQ_FRW4X_128R_ASM_BODY
-               : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1])
-               : [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [outw] "s"(outw), [resid] "s"(resid), [alpha] "s"(alpha_p),
-                 [bias] "s"(bias_p), [wzp] "s"(wzp_p), [ct] "s"(ct_p), [rsptr] "s"(rs_p), [soptr] "s"(so_ptr), [ooptr] "s"(oo_ptr),
-                 [qmin] "s"(qmin_bits), [qmax] "s"(qmax_bits), [ldn] "s"(ldn), [mrem] "s"(mrem), [flags] "s"(flags), [av0] "v"(av0), [av1] "v"(av1),
-                 [tid] "v"(tid), [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1])
-               : MQ_FRW4X_128R_ASM_CLOBBERS);
+  MQ_FR_W4_PIECES(2, 4, 8, false, false)
+  MQ_FR_ROW_BLOCKS;
+  MQ_FR_FRAGMENTS(MQ_FR_LANE_LINEAR)
+  MQ_FR_POINTERS;
+  MQ_FR_RESIDUAL;
+  MQ_FR_SCALARS(BNT, );
+  asm volatile(MQ_FRW4X_128R_ASM_BODY : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]) : MQ_FR_RESIDUAL_OPERANDS : MQ_FRW4X_128R_ASM_CLOBBERS);
 }
 
 static int launch_frw4r(GemmArgs a, hipStream_t st) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_frw4r_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MQ_FRW4X_128R_LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", MQ_FRW4X_128R_LDS_BYTES, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
-  a.has_rowsum = a.a_rowsum != nullptr;
-  if (a.a_rowsum == nullptr) a.a_rowsum = a.col_term;
-  if (a.bias == nullptr) a.bias = a.alpha;
-  a.grid_m = (a.M + 127) / 128;
-  a.grid_n = a.N / 128;
+  prepare_tiles(a, 128, 128);
   a.group_m = g_group_m.load();
-  gemm_i8_frw4r_kernel<<<a.grid_m * a.grid_n, 256, MQ_FRW4X_128R_LDS_BYTES, st>>>(a);
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+  return launch_kernel<gemm_i8_frw4r_kernel>(a, a.grid_m * a.grid_n, 256, MQ_FRW4X_128R_LDS_BYTES, st);
 }
 
 static bool gemm_frw4_shape(int64_t M, int64_t N, int64_t K) { return M > 0 && (N % 176 == 0 || N % 128 == 0) && K % 256 == 0 && K >= 768; }
@@ -1245,191 +1173,59 @@ static std::atomic<int> g_w4_mode{1};           // mobilequant_amd_tuning.h: 1 =
 template <int BNT, bool X>
 static int launch_frw4(GemmArgs a, hipStream_t st) {
   constexpr int LDS = X ? (BNT == 176 ? MQ_FRW4X_LDS_BYTES : MQ_FRW4X_128_LDS_BYTES) : (BNT == 176 ? MQ_FRW4_LDS_BYTES : MQ_FRW4_128_LDS_BYTES);
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_frw4_kernel<BNT, X>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
-  a.has_rowsum = a.a_rowsum != nullptr;
-  if (a.a_rowsum == nullptr) a.a_rowsum = a.col_term;
-  if (a.bias == nullptr) a.bias = a.alpha;
-  a.grid_m = (a.M + 255) / 256;
-  a.grid_n = a.N / BNT;
-  gemm_i8_frw4_kernel<BNT, X><<<a.grid_m * a.grid_n, 512, LDS, st>>>(a);
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+  prepare_tiles(a, 256, BNT);
+  return launch_kernel<gemm_i8_frw4_kernel<BNT, X>>(a, a.grid_m * a.grid_n, 512, LDS, st);
 }
 
-// ---- w3 of a gated FFN with the gate in its epilogue (tools/gen_fr_asm.py variant frg) ------------------------------------------------
-// The free-running 256 x 176 program; its epilogue turns the tile's 8-bit output indices and w1's (gate_aidx, written by the launch
+// ---- w3 of a gated FFN with the gate in its epilogue (tools/gen_fr_asm.py variants frg / frg128) ---------------------------------------
+// The free-running 256 x BNT program; its epilogue turns the tile's 8-bit output indices and w1's (gate_aidx, written by the launch
 // before) into w2's int8 input image through the LDS-resident 64-KiB gated table: no index tensor of w3, no lookup launch.
 template <int BNT>
 __global__ void __launch_bounds__(512) gemm_i8_frg_kernel(const GemmArgs args) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int tm, tn;
-  tile_of_block(blockIdx.x, args.grid_m * args.grid_n, args.grid_m, args.grid_n, tm, tn);
-  const int m0 = tm * 256, n0 = tn * BNT;
-  const int M = args.M, N = args.N, K = args.K;
-  const int KT = K / BK;
+  MQ_FR_TILE(256, BNT, false, (int)blockIdx.x, args.grid_m * args.grid_n, 0);
   unsigned sw[3] = {0, 0, 0};
-#pragma unroll
-  for (int i = 0; i < (BNT == 176 ? 3 : 2); ++i) {
-    int row = n0 + (wave + i * 8) * 8 + (lane >> 3);
-    row = row < N ? row : N - 1;
-    sw[i] = (unsigned)row * (unsigned)K + (unsigned)(((lane & 7) ^ (lane >> 3)) << 4);
-  }
-  const int m0w = m0 + wave * 32;
-  const unsigned rb_max = (unsigned)((M + 15) >> 4) - 1;
-  unsigned rb0 = (unsigned)(m0w >> 4), rb1 = rb0 + 1;
-  rb0 = rb0 < rb_max ? rb0 : rb_max;
-  rb1 = rb1 < rb_max ? rb1 : rb_max;
-  const unsigned av0 = (rb0 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  const unsigned av1 = (rb1 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  unsigned rsofs[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0w + i * 16 + (lane & 15);
-    m = args.has_rowsum ? (m < M ? m : M - 1) : 0;
-    rsofs[i] = (unsigned)m * 4u;
-  }
-  const float* so_ptr = args.out_scale;
-  const float* oo_ptr = args.out_offset;
-  const int8_t* a_ptr = args.a;
-  const int8_t* w_ptr = reinterpret_cast<const int8_t*>(args.w);
-  const float* alpha_p = args.alpha + n0;
-  const float* bias_p = args.bias + n0;
-  const int32_t* wzp_p = args.w_zp + n0;
-  const int32_t* ct_p = args.col_term + n0;
-  const int32_t* rs_p = args.a_rowsum;
-  const uint8_t* aidx = args.gate_aidx + (size_t)m0w * N + n0;
-  const int8_t* table = args.gate_table;
-  int8_t* qout = args.gate_q;
-  int32_t* rsout = args.gate_rowsum + m0w;
-  const int mrem = __builtin_amdgcn_readfirstlane(M - m0w);
-  const int flags = __builtin_amdgcn_readfirstlane((args.has_bias ? 1 : 0) | (args.has_rowsum ? 2 : 0));
-  const int ldn = __builtin_amdgcn_readfirstlane(N), kt = __builtin_amdgcn_readfirstlane(KT);
-  const int cg0 = __builtin_amdgcn_readfirstlane(tn * (BNT / 16)), mb0 = __builtin_amdgcn_readfirstlane(m0w >> 4);
-  const unsigned tid = threadIdx.x;
-#define MQ_FRG_OPERANDS                                                                                                            \
-  [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [aidx] "s"(aidx), [alpha] "s"(alpha_p),                    \
-      [bias] "s"(bias_p), [wzp] "s"(wzp_p), [ct] "s"(ct_p), [rsptr] "s"(rs_p), [soptr] "s"(so_ptr), [ooptr] "s"(oo_ptr),       \
-      [ldn] "s"(ldn), [mrem] "s"(mrem), [flags] "s"(flags), [table] "s"(table), [qout] "s"(qout), [rsout] "s"(rsout),              \
-      [cg0] "s"(cg0), [mb0] "s"(mb0), [sw0] "v"(sw[0]), [sw1] "v"(sw[1]), [av0] "v"(av0), [av1] "v"(av1),                          \
-      [tid] "v"(tid), [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1])
+  MQ_FR_W_PIECES(BNT == 176 ? 3 : 2, 8)
+  MQ_FR_ROW_BLOCKS;
+  MQ_FR_FRAGMENTS(MQ_FR_LANE_LINEAR)
+  MQ_FR_POINTERS;
+  MQ_FR_GATE;
+  MQ_FR_SCALARS(BNT, );
   if constexpr (BNT == 176) {
-    asm volatile(MQ_FRG_ASM_BODY : : MQ_FRG_OPERANDS, [sw2] "v"(sw[2]) : MQ_FRG_ASM_CLOBBERS);
+    asm volatile(MQ_FRG_ASM_BODY : : MQ_FR_GATE_OPERANDS, [sw0] "v"(sw[0]), [sw1] "v"(sw[1]), [sw2] "v"(sw[2]) : MQ_FRG_ASM_CLOBBERS);
   } else {
-    asm volatile(MQ_FRG128_ASM_BODY : : MQ_FRG_OPERANDS : MQ_FRG128_ASM_CLOBBERS);
+    asm volatile(MQ_FRG128_ASM_BODY : : MQ_FR_GATE_OPERANDS, [sw0] "v"(sw[0]), [sw1] "v"(sw[1]) : MQ_FRG128_ASM_CLOBBERS);
   }
-#undef MQ_FRG_OPERANDS
 }
 
 template <int BNT>
-static int launch_frg(const GemmArgs& a, hipStream_t st) {
-  constexpr int LDS = BNT == 176 ? MQ_FRG_LDS_BYTES : MQ_FRG128_LDS_BYTES;
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_frg_kernel<BNT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
-  gemm_i8_frg_kernel<BNT><<<a.grid_m * a.grid_n, 512, LDS, st>>>(a);
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+static int launch_frg(GemmArgs a, hipStream_t st) {
+  prepare_tiles(a, 256, BNT);
+  return launch_kernel<gemm_i8_frg_kernel<BNT>>(a, a.grid_m * a.grid_n, 512, BNT == 176 ? MQ_FRG_LDS_BYTES : MQ_FRG128_LDS_BYTES, st);
 }
 
 // w3 of a gated FFN from PACKED 4-bit weights with the gate in its epilogue (tools/gen_fr_asm.py variants frgw4x / frgw4x_128): frg's
 // program with the W pieces (16 rows x 64 packed bytes) loaded into registers and expanded once per workgroup into the int8 ring.
 template <int BNT>
 __global__ void __launch_bounds__(512) gemm_i8_frgw4_kernel(const GemmArgs args) {
-  constexpr int FNT = BNT / 16;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int tm, tn;
-  tile_of_block(blockIdx.x, args.grid_m * args.grid_n, args.grid_m, args.grid_n, tm, tn);
-  const int m0 = tm * 256, n0 = tn * BNT;
-  const int M = args.M, N = args.N, K = args.K;
-  const int KT = K / BK;
+  MQ_FR_TILE(256, BNT, false, (int)blockIdx.x, args.grid_m * args.grid_n, 0);
   unsigned sw[2] = {0, 0};
-#pragma unroll
-  for (int i = 0; i < (BNT == 176 ? 2 : 1); ++i) {
-    int piece = wave + i * 8;
-    piece = piece < FNT ? piece : FNT - 1;
-    int row = n0 + piece * 16 + (lane >> 2);
-    row = row < N ? row : N - 1;
-    sw[i] = (unsigned)row * (unsigned)(K >> 1) + (unsigned)((lane & 3) << 4);
-  }
-  const int m0w = m0 + wave * 32;
-  const unsigned rb_max = (unsigned)((M + 15) >> 4) - 1;
-  unsigned rb0 = (unsigned)(m0w >> 4), rb1 = rb0 + 1;
-  rb0 = rb0 < rb_max ? rb0 : rb_max;
-  rb1 = rb1 < rb_max ? rb1 : rb_max;
-  const unsigned av0 = (rb0 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  const unsigned av1 = (rb1 * (unsigned)(K >> 6)) * 1024u + ((unsigned)lane << 4);
-  unsigned rsofs[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int m = m0w + i * 16 + (lane & 15);
-    m = args.has_rowsum ? (m < M ? m : M - 1) : 0;
-    rsofs[i] = (unsigned)m * 4u;
-  }
-  const float* so_ptr = args.out_scale;
-  const float* oo_ptr = args.out_offset;
-  const int8_t* a_ptr = args.a;
-  const int8_t* w_ptr = reinterpret_cast<const int8_t*>(args.w);
-  const float* alpha_p = args.alpha + n0;
-  const float* bias_p = args.bias + n0;
-  const int32_t* wzp_p = args.w_zp + n0;
-  const int32_t* ct_p = args.col_term + n0;
-  const int32_t* rs_p = args.a_rowsum;
-  const uint8_t* aidx = args.gate_aidx + (size_t)m0w * N + n0;
-  const int8_t* table = args.gate_table;
-  int8_t* qout = args.gate_q;
-  int32_t* rsout = args.gate_rowsum + m0w;
-  const int mrem = __builtin_amdgcn_readfirstlane(M - m0w);
-  const int flags = __builtin_amdgcn_readfirstlane((args.has_bias ? 1 : 0) | (args.has_rowsum ? 2 : 0));
-  const int ldn = __builtin_amdgcn_readfirstlane(N), kt = __builtin_amdgcn_readfirstlane(KT);
-  const int cg0 = __builtin_amdgcn_readfirstlane(tn * (BNT / 16)), mb0 = __builtin_amdgcn_readfirstlane(m0w >> 4);
-  const unsigned tid = threadIdx.x;
-#define MQ_FRGW4_OPERANDS                                                                                                          \
-  [kt] "s"(kt), [wave] "s"(wave), [aptr] "s"(a_ptr), [wptr] "s"(w_ptr), [aidx] "s"(aidx), [alpha] "s"(alpha_p),                    \
-      [bias] "s"(bias_p), [wzp] "s"(wzp_p), [ct] "s"(ct_p), [rsptr] "s"(rs_p), [soptr] "s"(so_ptr), [ooptr] "s"(oo_ptr),       \
-      [ldn] "s"(ldn), [mrem] "s"(mrem), [flags] "s"(flags), [table] "s"(table), [qout] "s"(qout), [rsout] "s"(rsout),              \
-      [cg0] "s"(cg0), [mb0] "s"(mb0), [av0] "v"(av0), [av1] "v"(av1), [tid] "v"(tid), [rsofs0] "v"(rsofs[0]), [rsofs1] "v"(rsofs[1])
+  MQ_FR_W4_PIECES(BNT == 176 ? 2 : 1, 8, BNT / 16, true, false)
+  MQ_FR_ROW_BLOCKS;
+  MQ_FR_FRAGMENTS(MQ_FR_LANE_LINEAR)
+  MQ_FR_POINTERS;
+  MQ_FR_GATE;
+  MQ_FR_SCALARS(BNT, );
   if constexpr (BNT == 176) {
-    asm volatile(MQ_FRGW4X_ASM_BODY : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]) : MQ_FRGW4_OPERANDS : MQ_FRGW4X_ASM_CLOBBERS);
+    asm volatile(MQ_FRGW4X_ASM_BODY : [sw0] "+v"(sw[0]), [sw1] "+v"(sw[1]) : MQ_FR_GATE_OPERANDS : MQ_FRGW4X_ASM_CLOBBERS);
   } else {
-    asm volatile(MQ_FRGW4X_128_ASM_BODY : [sw0] "+v"(sw[0]) : MQ_FRGW4_OPERANDS : MQ_FRGW4X_128_ASM_CLOBBERS);
+    asm volatile(MQ_FRGW4X_128_ASM_BODY : [sw0] "+v"(sw[0]) : MQ_FR_GATE_OPERANDS : MQ_FRGW4X_128_ASM_CLOBBERS);
   }
-#undef MQ_FRGW4_OPERANDS
 }
 
 template <int BNT>
-static int launch_frgw4(const GemmArgs& a, hipStream_t st) {
-  constexpr int LDS = BNT == 176 ? MQ_FRGW4X_LDS_BYTES : MQ_FRGW4X_128_LDS_BYTES;
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_frgw4_kernel<BNT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
-  gemm_i8_frgw4_kernel<BNT><<<a.grid_m * a.grid_n, 512, LDS, st>>>(a);
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+static int launch_frgw4(GemmArgs a, hipStream_t st) {
+  prepare_tiles(a, 256, BNT);
+  return launch_kernel<gemm_i8_frgw4_kernel<BNT>>(a, a.grid_m * a.grid_n, 512, BNT == 176 ? MQ_FRGW4X_LDS_BYTES : MQ_FRGW4X_128_LDS_BYTES, st);
 }
 
 // Two QLinears that consume the SAME activation (w1 / w3 of an FFN: hf_model.py:1057) in ONE launch: workgroups
@@ -1465,51 +1261,18 @@ static bool gemm_fr_supported(const GemmArgs& a) {
 }
 
 static int launch_fr_pair(const GemmArgs& a0, const GemmArgs& a1, hipStream_t st) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_fr_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MQ_FR_LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", MQ_FR_LDS_BYTES, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
   GemmPairArgs pa;
   pa.p[0] = a0;
   pa.p[1] = a1;
-  if (g_pair_mode.load() == 1) {
-    static PerDeviceOnce attr_set_p;
-    if (!attr_set_p.done(dev)) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_fr_pair_persistent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MQ_FR_LDS_BYTES);
-      if (e != hipSuccess) {
-        set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", MQ_FR_LDS_BYTES, hipGetErrorString(e));
-        return MQ_EHIP;
-      }
-      attr_set_p.mark(dev);
-    }
-    gemm_i8_fr_pair_persistent_kernel<<<a0.grid_m * a0.grid_n, 512, MQ_FR_LDS_BYTES, st>>>(pa);
-  } else {
-    gemm_i8_fr_pair_kernel<<<2 * a0.grid_m * a0.grid_n, 512, MQ_FR_LDS_BYTES, st>>>(pa);
-  }
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+  for (GemmArgs& a : pa.p) prepare_tiles(a, 256, 176);
+  const int nblk = pa.p[0].grid_m * pa.p[0].grid_n;
+  if (g_pair_mode.load() == 1) return launch_kernel<gemm_i8_fr_pair_persistent_kernel>(pa, nblk, 512, MQ_FR_LDS_BYTES, st);
+  return launch_kernel<gemm_i8_fr_pair_kernel>(pa, 2 * nblk, 512, MQ_FR_LDS_BYTES, st);
 }
 
-static int launch_fr(const GemmArgs& a, hipStream_t st) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_fr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MQ_FR_LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", MQ_FR_LDS_BYTES, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
-  gemm_i8_fr_kernel<<<a.grid_m * a.grid_n, 512, MQ_FR_LDS_BYTES, st>>>(a);
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+static int launch_fr(GemmArgs a, hipStream_t st) {
+  prepare_tiles(a, 256, 176);
+  return launch_kernel<gemm_i8_fr_kernel>(a, a.grid_m * a.grid_n, 512, MQ_FR_LDS_BYTES, st);
 }
 
 // ---- variants & dispatch --------------------------------------------------------------------------
@@ -1539,20 +1302,7 @@ static unsigned long long* g_dbg_ts = nullptr;
 
 template <int BM, int BN, int WM, int WN, int OUT, bool OQ, bool W4, int ABL, int PP>
 static int launch_one(const GemmArgs& a, int lds, hipStream_t st) {
-  auto kfn = gemm_i8_kernel<BM, BN, WM, WN, OUT, OQ, W4, ABL, PP>;
-  static PerDeviceOnce attr_set;   // per instantiation and per device
-  const int dev = current_device();
-  if (!attr_set.done(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      set_error("mq_gemm: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-      return MQ_EHIP;
-    }
-    attr_set.mark(dev);
-  }
-  kfn<<<a.grid_m * a.grid_n, 64 * WM * WN, lds, st>>>(a);
-  MQ_LAUNCH_CHECK("mq_gemm");
-  return MQ_OK;
+  return launch_kernel<gemm_i8_kernel<BM, BN, WM, WN, OUT, OQ, W4, ABL, PP>>(a, a.grid_m * a.grid_n, 64 * WM * WN, lds, st);
 }
 
 template <int BM, int BN, int WM, int WN, int OUT, bool OQ, bool W4, int PP>
@@ -1645,9 +1395,6 @@ static int run_gemm(GemmArgs a, hipStream_t st) {
     return launch_fr128<FR128>(a, st);      // 8-bit unsigned index outputs on 256 x 128 tiles (Gemma's w1 / w3: N = 16384)
   }
   const bool outq = a.out_scale != nullptr;
-  a.has_rowsum = a.a_rowsum != nullptr;
-  if (a.a_rowsum == nullptr) a.a_rowsum = a.col_term;                 // element 0 only (M may exceed N); multiplied by w_zp == 0
-  if (a.bias == nullptr) a.bias = a.alpha;                            // masked by has_bias
   int v = pick_variant(a.M, a.N, W4);
   if (a.a_tiled) {
     if (W4 || !gemm_tiled_supported(a.M, a.N, a.K)) {
@@ -1661,8 +1408,7 @@ static int run_gemm(GemmArgs a, hipStream_t st) {
   } else if (v == 9 || v == 11) {
     v = 7;                                  // variants 9 and 11 read fragment-blocked activations only
   }
-  a.grid_m = (a.M + kVariants[v].bm - 1) / kVariants[v].bm;
-  a.grid_n = (a.N + kVariants[v].bn - 1) / kVariants[v].bn;
+  if (v != 11) prepare_tiles(a, kVariants[v].bm, kVariants[v].bn);      // (launch_fr prepares its own)
   switch (v) {
     case 0: return launch_cfg<256, 176, 4, 1, W4>(a, outq, st);
     case 1: return launch_cfg<256, 176, 8, 1, W4>(a, outq, st);
@@ -1698,6 +1444,64 @@ static int check_common(const char* fn, const void* a, const void* w, int64_t M,
   MQ_REQUIRE((out_scale == nullptr) == (out_offset == nullptr), "%s: out_scale/out_offset must both be set or NULL", fn);
   (void)a_rowsum;
   return MQ_OK;
+}
+
+// Column segments with their own output grids: every grid 8-bit unsigned; the ends increasing multiples of 4 up to N (check_ends: a
+// single segment may come without ends).
+static int check_segments(const char* fn, int n_segments, const int64_t* seg_end, const mq_grid* grids, int64_t N, bool check_ends) {
+  int64_t prev = 0;
+  for (int i = 0; i < n_segments; ++i) {
+    MQ_REQUIRE(grids[i].scale && grids[i].offset && grids[i].qmin == 0.f && grids[i].qmax == 255.f,
+               "%s: segment %d needs an 8-bit unsigned output grid", fn, i);
+    if (check_ends) {
+      MQ_REQUIRE(seg_end[i] > prev && seg_end[i] <= N && seg_end[i] % 4 == 0, "%s: segment ends must increase, be multiples of 4, <= N", fn);
+      prev = seg_end[i];
+    }
+  }
+  MQ_REQUIRE(!check_ends || prev == N, "%s: the last segment must end at N", fn);
+  return MQ_OK;
+}
+
+// The launch arguments of one linear, as the entry points receive them; has_bias from the caller's bias, the clock-probe buffer, and
+// nothing else set (grid, dummy pointers: prepare_tiles).
+static GemmArgs gemm_args(const int8_t* a, const void* w, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum, const float* alpha,
+                          const int32_t* w_zp, const int32_t* col_term, const float* bias, const float* out_scale, const float* out_offset,
+                          float out_qmin, float out_qmax, void* out, int out_dtype, bool a_tiled, const float* resid = nullptr) {
+  GemmArgs g{};
+  g.a = a;
+  g.w = w;
+  g.M = (int)M;
+  g.N = (int)N;
+  g.K = (int)K;
+  g.a_rowsum = a_rowsum;
+  g.alpha = alpha;
+  g.w_zp = w_zp;
+  g.col_term = col_term;
+  g.bias = bias;
+  g.out_scale = out_scale;
+  g.out_offset = out_offset;
+  g.out_qmin = out_qmin;
+  g.out_qmax = out_qmax;
+  g.out = out;
+  g.out_dtype = out_dtype;
+  g.has_bias = bias != nullptr;
+  g.a_tiled = a_tiled;
+  g.dbg_ts = g_dbg_ts;
+  g.resid = resid;
+  return g;
+}
+
+// ... with 8-bit unsigned output grids per column segment: columns below seg_end[0] use grids[0], the later segments their own
+static GemmArgs gemm_args(const int8_t* a, const void* w, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum, const float* alpha,
+                          const int32_t* w_zp, const int32_t* col_term, const float* bias, int n_segments, const int64_t* seg_end,
+                          const mq_grid* grids, void* out, int out_dtype, bool a_tiled) {
+  GemmArgs g = gemm_args(a, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, grids[0].scale, grids[0].offset, 0.f, 255.f, out, out_dtype, a_tiled);
+  for (int i = 1; i < n_segments; ++i) {
+    g.seg_end[i - 1] = (int)seg_end[i - 1];
+    g.seg_scale[i - 1] = grids[i].scale;
+    g.seg_offset[i - 1] = grids[i].offset;
+  }
+  return g;
 }
 
 }  // namespace mq
@@ -1806,9 +1610,8 @@ int mq_w8a8_linear(const int8_t* a, const int8_t* w, int64_t M, int64_t N, int64
                out_qmin, out_qmax, out, out_dtype, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0};
     return run_gemv(v, as_stream(stream));
   }
-  GemmArgs g{a, w, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset,
-             out_qmin, out_qmax, out, out_dtype, 0, 0, bias != nullptr, 0, 0, g_dbg_ts};
-  return run_gemm<false>(g, as_stream(stream));
+  return run_gemm<false>(gemm_args(a, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out_qmin, out_qmax, out, out_dtype, false),
+                         as_stream(stream));
 }
 
 int mq_w8a8_linear_residual(const int8_t* a, const int8_t* w, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
@@ -1818,9 +1621,8 @@ int mq_w8a8_linear_residual(const int8_t* a, const int8_t* w, int64_t M, int64_t
   int rc = check_common("mq_w8a8_linear_residual", a, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out, 1);
   if (rc != MQ_OK) return rc;
   MQ_REQUIRE(resid != nullptr && aligned(resid, 16) && M > 8, "mq_w8a8_linear_residual: resid must be non-null and 16-byte aligned; M > 8");
-  GemmArgs g{a, w, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset,
-             out_qmin, out_qmax, out, MQ_F32, 0, 0, bias != nullptr, 0, 0, g_dbg_ts, resid};
-  return run_gemm<false>(g, as_stream(stream));
+  return run_gemm<false>(gemm_args(a, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out_qmin, out_qmax, out, MQ_F32, false, resid),
+                         as_stream(stream));
 }
 
 static int linear_segmented(const char* fn, bool w4, const int8_t* a, const void* w, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
@@ -1831,21 +1633,9 @@ static int linear_segmented(const char* fn, bool w4, const int8_t* a, const void
   if (rc != MQ_OK) return rc;
   MQ_REQUIRE(M > 8, "%s: M > 8 (decode shapes: mq_decode_gemv)", fn);
   MQ_REQUIRE(!w4 || K % 64 == 0, "%s: packed 4-bit weights need K %% 64 == 0", fn);
-  int64_t prev = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    MQ_REQUIRE(grids[i].scale && grids[i].offset && grids[i].qmin == 0.f && grids[i].qmax == 255.f,
-               "%s: segment %d needs an 8-bit unsigned output grid", fn, i);
-    MQ_REQUIRE(seg_end[i] > prev && seg_end[i] <= N && seg_end[i] % 4 == 0, "%s: segment ends must increase, be multiples of 4, <= N", fn);
-    prev = seg_end[i];
-  }
-  MQ_REQUIRE(prev == N, "%s: the last segment must end at N", fn);
-  GemmArgs g{a, w, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, grids[0].scale, grids[0].offset,
-             0.f, 255.f, out, MQ_U8, 0, 0, bias != nullptr, 0, 0, g_dbg_ts, nullptr, {0, 0}, {nullptr, nullptr}, {nullptr, nullptr}};
-  for (int i = 1; i < n_segments; ++i) {
-    g.seg_end[i - 1] = (int)seg_end[i - 1];
-    g.seg_scale[i - 1] = grids[i].scale;
-    g.seg_offset[i - 1] = grids[i].offset;
-  }
+  rc = check_segments(fn, n_segments, seg_end, grids, N, true);
+  if (rc != MQ_OK) return rc;
+  const GemmArgs g = gemm_args(a, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, n_segments, seg_end, grids, out, MQ_U8, false);
   return w4 ? run_gemm<true>(g, as_stream(stream)) : run_gemm<false>(g, as_stream(stream));
 }
 
@@ -1873,9 +1663,8 @@ int mq_w8a8_linear_tiled(const int8_t* a_tiled, const int8_t* w, int64_t M, int6
                         out_offset, out, 1);
   if (rc != MQ_OK) return rc;
   MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32), "mq_w8a8_linear_tiled: activation too large");
-  GemmArgs g{a_tiled, w, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset,
-             out_qmin, out_qmax, out, out_dtype, 0, 0, bias != nullptr, 1, 0, g_dbg_ts};
-  return run_gemm<false>(g, as_stream(stream));
+  return run_gemm<false>(gemm_args(a_tiled, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out_qmin, out_qmax, out, out_dtype, true),
+                         as_stream(stream));
 }
 
 int mq_gemm_tiled_w4_supported(int64_t M, int64_t N, int64_t K) { return gemm_frw4_shape(M, N, K) ? 1 : 0; }
@@ -1889,28 +1678,14 @@ int mq_w4a8_linear_tiled(const int8_t* a_tiled, const uint8_t* w_packed, int64_t
   if (rc != MQ_OK) return rc;
   MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32), "%s: activation too large", fn);
   MQ_REQUIRE(out_dtype == MQ_U8 || out_dtype == MQ_I8, "%s: u8 (indices) or i8 (index - 128) output", fn);
-  int64_t prev = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    MQ_REQUIRE(grids[i].scale && grids[i].offset && grids[i].qmin == 0.f && grids[i].qmax == 255.f,
-               "%s: segment %d needs an 8-bit unsigned output grid", fn, i);
-    if (n_segments > 1) {
-      MQ_REQUIRE(seg_end[i] > prev && seg_end[i] <= N && seg_end[i] % 4 == 0, "%s: segment ends must increase, be multiples of 4, <= N", fn);
-      prev = seg_end[i];
-    }
-  }
-  MQ_REQUIRE(n_segments == 1 || prev == N, "%s: the last segment must end at N", fn);
+  rc = check_segments(fn, n_segments, seg_end, grids, N, n_segments > 1);
+  if (rc != MQ_OK) return rc;
   if (!gemm_frw4_shape(M, N, K) || (n_segments > 1 && N % 128 != 0)) {
     set_error("%s: shape %lldx%lldx%lld is not served (mq_gemm_tiled_w4_supported: N %% 176 == 0 or N %% 128 == 0 (segments: 128), K %% 256 == 0, "
               "K >= 768)", fn, (long long)M, (long long)N, (long long)K);
     return MQ_EUNSUPPORTED;
   }
-  GemmArgs g{a_tiled, w_packed, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, grids[0].scale, grids[0].offset,
-             0.f, 255.f, out, out_dtype, 0, 0, bias != nullptr, 1, 0, g_dbg_ts, nullptr, {0, 0}, {nullptr, nullptr}, {nullptr, nullptr}};
-  for (int i = 1; i < n_segments; ++i) {
-    g.seg_end[i - 1] = (int)seg_end[i - 1];
-    g.seg_scale[i - 1] = grids[i].scale;
-    g.seg_offset[i - 1] = grids[i].offset;
-  }
+  const GemmArgs g = gemm_args(a_tiled, w_packed, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, n_segments, seg_end, grids, out, out_dtype, true);
 #ifdef MQ_BUILD_EXPERIMENTS
   const bool x = g_w4_mode.load() != 0;
   if (n_segments == 1 && N % 176 == 0) return x ? launch_frw4<176, true>(g, as_stream(stream)) : launch_frw4<176, false>(g, as_stream(stream));
@@ -1935,21 +1710,12 @@ int mq_w8a8_linear_tiled_pair(const int8_t* a_tiled, int64_t M, int64_t N, int64
   MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32), "%s: activation too large", fn);
   MQ_REQUIRE(out_scale0 && out_scale1 && (out_dtype == MQ_U8 || out_dtype == MQ_I8),
              "%s: both outputs carry an 8-bit unsigned output grid (u8 / i8 storage)", fn);
-  GemmArgs g0{a_tiled, w0, (int)M, (int)N, (int)K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0,
-              0.f, 255.f, out0, out_dtype, 0, 0, bias0 != nullptr, 1, 0, g_dbg_ts};
-  GemmArgs g1{a_tiled, w1, (int)M, (int)N, (int)K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1,
-              0.f, 255.f, out1, out_dtype, 0, 0, bias1 != nullptr, 1, 0, g_dbg_ts};
+  const GemmArgs g0 = gemm_args(a_tiled, w0, M, N, K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0, 0.f, 255.f, out0, out_dtype, true);
+  const GemmArgs g1 = gemm_args(a_tiled, w1, M, N, K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1, 0.f, 255.f, out1, out_dtype, true);
   if (!gemm_tiled_supported(M, N, K) || !gemm_fr_supported(g0)) {
     set_error("%s: shape %lldx%lldx%lld is not served (mq_gemm_tiled_supported, K %% 256 == 0, K >= 768)", fn, (long long)M, (long long)N,
               (long long)K);
     return MQ_EUNSUPPORTED;
-  }
-  for (GemmArgs* g : {&g0, &g1}) {
-    g->has_rowsum = g->a_rowsum != nullptr;
-    if (g->a_rowsum == nullptr) g->a_rowsum = g->col_term;
-    if (g->bias == nullptr) g->bias = g->alpha;
-    g->grid_m = (g->M + 255) / 256;
-    g->grid_n = (g->N + 175) / 176;
   }
   return launch_fr_pair(g0, g1, as_stream(stream));
 }
@@ -1973,23 +1739,26 @@ int mq_gemm_set_residual_tile(int rows) {
 #endif
 }
 
-int mq_w8a8_linear_tiled_residual(const int8_t* a_tiled, const int8_t* w, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
-                                  const float* alpha, const int32_t* w_zp, const int32_t* col_term, const float* bias,
-                                  const float* out_scale, const float* out_offset, float out_qmin, float out_qmax,
-                                  const float* resid, float* out, mq_stream_t stream) {
-  const char* fn = "mq_w8a8_linear_tiled_residual";
-  int rc = check_common(fn, a_tiled, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out, 1);
+// o_proj / w2 on fragment-blocked activations: fp32 out = resid + Q16(linear).  int8 weights: the fr128r family by shape (or as forced);
+// packed 4-bit weights: frw4x_128r.
+static int linear_tiled_residual(const char* fn, bool w4, const int8_t* a_tiled, const void* w, int64_t M, int64_t N, int64_t K,
+                                 const int32_t* a_rowsum, const float* alpha, const int32_t* w_zp, const int32_t* col_term, const float* bias,
+                                 const float* out_scale, const float* out_offset, float out_qmin, float out_qmax, const float* resid,
+                                 float* out, mq_stream_t stream) {
+  int rc = check_common(fn, a_tiled, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out, w4 ? 2 : 1);
   if (rc != MQ_OK) return rc;
   MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32) && M * N * 4 < (1ll << 32), "%s: operand too large", fn);
   MQ_REQUIRE(resid != nullptr && aligned(resid, 16), "%s: resid must be non-null and 16-byte aligned", fn);
-  MQ_REQUIRE(out_scale != nullptr && out_qmax - out_qmin > 255.0f, "%s: a 16-bit output grid is required (8-bit grids: mq_w8a8_linear_residual)", fn);
+  MQ_REQUIRE(out_scale != nullptr && out_qmax - out_qmin > 255.0f, "%s: a 16-bit output grid is required%s", fn,
+             w4 ? "" : " (8-bit grids: mq_w8a8_linear_residual)");
   if (!gemm_fr128_shape(M, N, K)) {
     set_error("%s: shape %lldx%lldx%lld is not served (mq_gemm_tiled128_supported: N %% 128 == 0, K %% 256 == 0, K >= 768)", fn, (long long)M,
               (long long)N, (long long)K);
     return MQ_EUNSUPPORTED;
   }
-  GemmArgs g{a_tiled, w, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset,
-             out_qmin, out_qmax, out, MQ_F32, 0, 0, bias != nullptr, 1, 0, g_dbg_ts, resid};
+  const GemmArgs g = gemm_args(a_tiled, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out_qmin, out_qmax, out, MQ_F32,
+                               true, resid);
+  if (w4) return launch_frw4r(g, as_stream(stream));
   // 128-row tiles while they give every CU at most ~two rounds of work; taller tiles (twice the MFMAs per W fragment) beyond
   const int forced = g_fr128r_tile.load();
   const int64_t tiles128 = ((M + 127) / 128) * (N / 128);
@@ -2006,24 +1775,20 @@ int mq_w8a8_linear_tiled_residual(const int8_t* a_tiled, const int8_t* w, int64_
   return tall ? launch_fr128<FR128R8>(g, as_stream(stream)) : launch_fr128<FR128R>(g, as_stream(stream));
 }
 
+int mq_w8a8_linear_tiled_residual(const int8_t* a_tiled, const int8_t* w, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
+                                  const float* alpha, const int32_t* w_zp, const int32_t* col_term, const float* bias,
+                                  const float* out_scale, const float* out_offset, float out_qmin, float out_qmax,
+                                  const float* resid, float* out, mq_stream_t stream) {
+  return linear_tiled_residual("mq_w8a8_linear_tiled_residual", false, a_tiled, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale,
+                               out_offset, out_qmin, out_qmax, resid, out, stream);
+}
+
 int mq_w4a8_linear_tiled_residual(const int8_t* a_tiled, const uint8_t* w_packed, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
                                   const float* alpha, const int32_t* w_zp, const int32_t* col_term, const float* bias,
                                   const float* out_scale, const float* out_offset, float out_qmin, float out_qmax,
                                   const float* resid, float* out, mq_stream_t stream) {
-  const char* fn = "mq_w4a8_linear_tiled_residual";
-  int rc = check_common(fn, a_tiled, w_packed, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out, 2);
-  if (rc != MQ_OK) return rc;
-  MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32) && M * N * 4 < (1ll << 32), "%s: operand too large", fn);
-  MQ_REQUIRE(resid != nullptr && aligned(resid, 16), "%s: resid must be non-null and 16-byte aligned", fn);
-  MQ_REQUIRE(out_scale != nullptr && out_qmax - out_qmin > 255.0f, "%s: a 16-bit output grid is required", fn);
-  if (!gemm_fr128_shape(M, N, K)) {
-    set_error("%s: shape %lldx%lldx%lld is not served (mq_gemm_tiled128_supported: N %% 128 == 0, K %% 256 == 0, K >= 768)", fn, (long long)M,
-              (long long)N, (long long)K);
-    return MQ_EUNSUPPORTED;
-  }
-  GemmArgs g{a_tiled, w_packed, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset,
-             out_qmin, out_qmax, out, MQ_F32, 0, 0, bias != nullptr, 1, 0, g_dbg_ts, resid};
-  return launch_frw4r(g, as_stream(stream));
+  return linear_tiled_residual("mq_w4a8_linear_tiled_residual", true, a_tiled, w_packed, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale,
+                               out_offset, out_qmin, out_qmax, resid, out, stream);
 }
 
 int mq_w8a8_linear_tiled_segmented(const int8_t* a_tiled, const int8_t* w, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
@@ -2034,29 +1799,57 @@ int mq_w8a8_linear_tiled_segmented(const int8_t* a_tiled, const int8_t* w, int64
   int rc = check_common(fn, a_tiled, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, grids[0].scale, grids[0].offset, out, 1);
   if (rc != MQ_OK) return rc;
   MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32), "%s: activation too large", fn);
-  int64_t prev = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    MQ_REQUIRE(grids[i].scale && grids[i].offset && grids[i].qmin == 0.f && grids[i].qmax == 255.f,
-               "%s: segment %d needs an 8-bit unsigned output grid", fn, i);
-    MQ_REQUIRE(seg_end[i] > prev && seg_end[i] <= N && seg_end[i] % 4 == 0, "%s: segment ends must increase, be multiples of 4, <= N", fn);
-    prev = seg_end[i];
-  }
-  MQ_REQUIRE(prev == N, "%s: the last segment must end at N", fn);
+  rc = check_segments(fn, n_segments, seg_end, grids, N, true);
+  if (rc != MQ_OK) return rc;
   if (!gemm_fr128_shape(M, N, K)) {
     set_error("%s: shape %lldx%lldx%lld is not served (mq_gemm_tiled128_supported: N %% 128 == 0, K %% 256 == 0, K >= 768)", fn, (long long)M,
               (long long)N, (long long)K);
     return MQ_EUNSUPPORTED;
   }
-  GemmArgs g{a_tiled, w, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, grids[0].scale, grids[0].offset,
-             0.f, 255.f, out, MQ_U8, 0, 0, bias != nullptr, 1, 0, g_dbg_ts, nullptr, {0, 0}, {nullptr, nullptr}, {nullptr, nullptr}};
-  for (int i = 1; i < n_segments; ++i) {
-    g.seg_end[i - 1] = (int)seg_end[i - 1];
-    g.seg_scale[i - 1] = grids[i].scale;
-    g.seg_offset[i - 1] = grids[i].offset;
-  }
+  const GemmArgs g = gemm_args(a_tiled, w, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, n_segments, seg_end, grids, out, MQ_U8, true);
   // 128 x 160 tiles when they give every CU exactly (at most) one tile -- q | k | v at M = 2048: 256 tiles against 160 of 256 x 128
   if (N % 160 == 0 && ((M + 127) / 128) * (N / 160) <= 256 && g_seg_tile.load() != 128) return launch_fr128<FR160>(g, as_stream(stream));
   return launch_fr128<FR128>(g, as_stream(stream));
+}
+
+// w1 / w3 of a gated FFN in two launches: w1's 8-bit indices (and the zeroed row sums), then w3 with the gate in its epilogue.  Wide:
+// 256 x 176 tiles; narrow: 256 x 128 tiles (Gemma: N = 16384).
+static int linear_tiled_gated(const char* fn, bool w4, const int8_t* a_tiled, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
+                              const void* w0, const float* alpha0, const int32_t* w_zp0, const int32_t* col_term0, const float* bias0,
+                              const float* out_scale0, const float* out_offset0, const void* w1, const float* alpha1, const int32_t* w_zp1,
+                              const int32_t* col_term1, const float* bias1, const float* out_scale1, const float* out_offset1,
+                              const int8_t* table, uint8_t* idx_scratch, int8_t* q_tiled, int32_t* row_sum, mq_stream_t stream) {
+  int rc = check_common(fn, a_tiled, w0, M, N, K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0, idx_scratch, w4 ? 2 : 1);
+  if (rc != MQ_OK) return rc;
+  rc = check_common(fn, a_tiled, w1, M, N, K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1, q_tiled, w4 ? 2 : 1);
+  if (rc != MQ_OK) return rc;
+  MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32) && ((M + 15) / 16) * 16 * N < (1ll << 32), "%s: operand too large", fn);
+  MQ_REQUIRE(out_scale0 && out_scale1 && table && row_sum && aligned(table, 16) && aligned(idx_scratch, 16) && aligned(q_tiled, 16),
+             "%s: both linears carry an 8-bit unsigned output grid; table / scratch / image must be non-null and 16-byte aligned", fn);
+  GemmArgs g0 = gemm_args(a_tiled, w0, M, N, K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0, 0.f, 255.f, idx_scratch, MQ_U8, true);
+  GemmArgs g1 = gemm_args(a_tiled, w1, M, N, K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1, 0.f, 255.f, q_tiled, MQ_U8, true);
+  const bool wide = gemm_tiled_supported(M, N, K) && N % 64 == 0 &&
+                    (w4 ? N % 176 == 0 && K % 256 == 0 && K >= 768 : gemm_fr_supported(g0));                     // 256 x 176 tiles
+  const bool narrow = !wide && gemm_fr128_shape(M, N, K) && ((M + 255) / 256) * (N / 128) >= 192;              // 256 x 128 tiles
+  if (!(wide || narrow) || M > 256 * 512) {
+    if (w4) set_error("%s: shape %lldx%lldx%lld is not served (as mq_w8a8_linear_tiled_gated)", fn, (long long)M, (long long)N, (long long)K);
+    else
+      set_error("%s: shape %lldx%lldx%lld is not served (mq_gemm_tiled_supported or N %% 128 == 0 with >= 192 tiles; K %% 256 == 0, K >= 768)",
+                fn, (long long)M, (long long)N, (long long)K);
+    return MQ_EUNSUPPORTED;
+  }
+  g0.zero_buf = row_sum;
+  g0.zero_count = (int)M;
+  g1.gate_aidx = idx_scratch;
+  g1.gate_table = table;
+  g1.gate_q = q_tiled;
+  g1.gate_rowsum = row_sum;
+  hipStream_t st = as_stream(stream);
+  if (w4) rc = wide ? launch_frw4<176, true>(g0, st) : launch_frw4<128, true>(g0, st);
+  else rc = wide ? launch_fr(g0, st) : launch_fr128<FR128>(g0, st);
+  if (rc != MQ_OK) return rc;
+  if (w4) return wide ? launch_frgw4<176>(g1, st) : launch_frgw4<128>(g1, st);
+  return wide ? launch_frg<176>(g1, st) : launch_frg<128>(g1, st);
 }
 
 int mq_w8a8_linear_tiled_gated(const int8_t* a_tiled, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
@@ -2065,51 +1858,8 @@ int mq_w8a8_linear_tiled_gated(const int8_t* a_tiled, int64_t M, int64_t N, int6
                                const int8_t* w1, const float* alpha1, const int32_t* w_zp1, const int32_t* col_term1,
                                const float* bias1, const float* out_scale1, const float* out_offset1,
                                const int8_t* table, uint8_t* idx_scratch, int8_t* q_tiled, int32_t* row_sum, mq_stream_t stream) {
-  const char* fn = "mq_w8a8_linear_tiled_gated";
-  int rc = check_common(fn, a_tiled, w0, M, N, K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0, idx_scratch, 1);
-  if (rc != MQ_OK) return rc;
-  rc = check_common(fn, a_tiled, w1, M, N, K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1, q_tiled, 1);
-  if (rc != MQ_OK) return rc;
-  MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32) && ((M + 15) / 16) * 16 * N < (1ll << 32), "%s: operand too large", fn);
-  MQ_REQUIRE(out_scale0 && out_scale1 && table && row_sum && aligned(table, 16) && aligned(idx_scratch, 16) && aligned(q_tiled, 16),
-             "%s: both linears carry an 8-bit unsigned output grid; table / scratch / image must be non-null and 16-byte aligned", fn);
-  GemmArgs g0{a_tiled, w0, (int)M, (int)N, (int)K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0,
-              0.f, 255.f, idx_scratch, MQ_U8, 0, 0, bias0 != nullptr, 1, 0, g_dbg_ts};
-  GemmArgs g1{a_tiled, w1, (int)M, (int)N, (int)K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1,
-              0.f, 255.f, q_tiled, MQ_U8, 0, 0, bias1 != nullptr, 1, 0, g_dbg_ts};
-  const bool wide = gemm_tiled_supported(M, N, K) && gemm_fr_supported(g0) && N % 64 == 0;         // 256 x 176 tiles
-  const bool narrow = !wide && gemm_fr128_shape(M, N, K) && ((M + 255) / 256) * (N / 128) >= 192;  // 256 x 128 tiles (Gemma: N = 16384)
-  if (!(wide || narrow) || M > 256 * 512) {
-    set_error("%s: shape %lldx%lldx%lld is not served (mq_gemm_tiled_supported or N %% 128 == 0 with >= 192 tiles; K %% 256 == 0, K >= 768)",
-              fn, (long long)M, (long long)N, (long long)K);
-    return MQ_EUNSUPPORTED;
-  }
-  g0.zero_buf = row_sum;
-  g0.zero_count = (int)M;
-  g1.gate_aidx = idx_scratch;
-  g1.gate_table = table;
-  g1.gate_q = q_tiled;
-  g1.gate_rowsum = row_sum;
-  if (narrow) {
-    rc = launch_fr128<FR128>(g0, as_stream(stream));
-    if (rc != MQ_OK) return rc;
-    g1.has_rowsum = g1.a_rowsum != nullptr;
-    if (g1.a_rowsum == nullptr) g1.a_rowsum = g1.col_term;
-    if (g1.bias == nullptr) g1.bias = g1.alpha;
-    g1.grid_m = (g1.M + 255) / 256;
-    g1.grid_n = g1.N / 128;
-    return launch_frg<128>(g1, as_stream(stream));
-  }
-  for (GemmArgs* g : {&g0, &g1}) {
-    g->has_rowsum = g->a_rowsum != nullptr;
-    if (g->a_rowsum == nullptr) g->a_rowsum = g->col_term;
-    if (g->bias == nullptr) g->bias = g->alpha;
-    g->grid_m = (g->M + 255) / 256;
-    g->grid_n = (g->N + 175) / 176;
-  }
-  rc = launch_fr(g0, as_stream(stream));
-  if (rc != MQ_OK) return rc;
-  return launch_frg<176>(g1, as_stream(stream));
+  return linear_tiled_gated("mq_w8a8_linear_tiled_gated", false, a_tiled, M, N, K, a_rowsum, w0, alpha0, w_zp0, col_term0, bias0, out_scale0,
+                            out_offset0, w1, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1, table, idx_scratch, q_tiled, row_sum, stream);
 }
 
 int mq_w4a8_linear_tiled_gated(const int8_t* a_tiled, int64_t M, int64_t N, int64_t K, const int32_t* a_rowsum,
@@ -2118,38 +1868,8 @@ int mq_w4a8_linear_tiled_gated(const int8_t* a_tiled, int64_t M, int64_t N, int6
                                const uint8_t* w1, const float* alpha1, const int32_t* w_zp1, const int32_t* col_term1,
                                const float* bias1, const float* out_scale1, const float* out_offset1,
                                const int8_t* table, uint8_t* idx_scratch, int8_t* q_tiled, int32_t* row_sum, mq_stream_t stream) {
-  const char* fn = "mq_w4a8_linear_tiled_gated";
-  int rc = check_common(fn, a_tiled, w0, M, N, K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0, idx_scratch, 2);
-  if (rc != MQ_OK) return rc;
-  rc = check_common(fn, a_tiled, w1, M, N, K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1, q_tiled, 2);
-  if (rc != MQ_OK) return rc;
-  MQ_REQUIRE(((M + 15) / 16) * 16 * K < (1ll << 32) && ((M + 15) / 16) * 16 * N < (1ll << 32), "%s: operand too large", fn);
-  MQ_REQUIRE(out_scale0 && out_scale1 && table && row_sum && aligned(table, 16) && aligned(idx_scratch, 16) && aligned(q_tiled, 16),
-             "%s: both linears carry an 8-bit unsigned output grid; table / scratch / image must be non-null and 16-byte aligned", fn);
-  GemmArgs g0{a_tiled, w0, (int)M, (int)N, (int)K, a_rowsum, alpha0, w_zp0, col_term0, bias0, out_scale0, out_offset0,
-              0.f, 255.f, idx_scratch, MQ_U8, 0, 0, bias0 != nullptr, 1, 0, g_dbg_ts};
-  GemmArgs g1{a_tiled, w1, (int)M, (int)N, (int)K, a_rowsum, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1,
-              0.f, 255.f, q_tiled, MQ_U8, 0, 0, bias1 != nullptr, 1, 0, g_dbg_ts};
-  const bool wide = gemm_tiled_supported(M, N, K) && N % 176 == 0 && N % 64 == 0 && K % 256 == 0 && K >= 768;   // 256 x 176 tiles
-  const bool narrow = !wide && gemm_fr128_shape(M, N, K) && ((M + 255) / 256) * (N / 128) >= 192;                 // 256 x 128 tiles
-  if (!(wide || narrow) || M > 256 * 512) {
-    set_error("%s: shape %lldx%lldx%lld is not served (as mq_w8a8_linear_tiled_gated)", fn, (long long)M, (long long)N, (long long)K);
-    return MQ_EUNSUPPORTED;
-  }
-  g0.zero_buf = row_sum;
-  g0.zero_count = (int)M;
-  g1.gate_aidx = idx_scratch;
-  g1.gate_table = table;
-  g1.gate_q = q_tiled;
-  g1.gate_rowsum = row_sum;
-  rc = wide ? launch_frw4<176, true>(g0, as_stream(stream)) : launch_frw4<128, true>(g0, as_stream(stream));
-  if (rc != MQ_OK) return rc;
-  g1.has_rowsum = g1.a_rowsum != nullptr;
-  if (g1.a_rowsum == nullptr) g1.a_rowsum = g1.col_term;
-  if (g1.bias == nullptr) g1.bias = g1.alpha;
-  g1.grid_m = (g1.M + 255) / 256;
-  g1.grid_n = wide ? g1.N / 176 : g1.N / 128;
-  return wide ? launch_frgw4<176>(g1, as_stream(stream)) : launch_frgw4<128>(g1, as_stream(stream));
+  return linear_tiled_gated("mq_w4a8_linear_tiled_gated", true, a_tiled, M, N, K, a_rowsum, w0, alpha0, w_zp0, col_term0, bias0, out_scale0,
+                            out_offset0, w1, alpha1, w_zp1, col_term1, bias1, out_scale1, out_offset1, table, idx_scratch, q_tiled, row_sum, stream);
 }
 
 static int linear_f32in(const char* fn, int w4, const float* x, const float* a_scale, const float* a_offset, float a_qmin,
@@ -2207,9 +1927,8 @@ int mq_w4a8_linear(const int8_t* a, const uint8_t* w_packed, int64_t M, int64_t 
                out_offset, out_qmin, out_qmax, out, out_dtype, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 1};
     return run_gemv(v, as_stream(stream));
   }
-  GemmArgs g{a, w_packed, (int)M, (int)N, (int)K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset,
-             out_qmin, out_qmax, out, out_dtype, 0, 0, bias != nullptr, 0, 0, g_dbg_ts};
-  return run_gemm<true>(g, as_stream(stream));
+  return run_gemm<true>(gemm_args(a, w_packed, M, N, K, a_rowsum, alpha, w_zp, col_term, bias, out_scale, out_offset, out_qmin, out_qmax, out, out_dtype, false),
+                        as_stream(stream));
 }
 
 }  // extern "C"

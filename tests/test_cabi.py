@@ -175,3 +175,64 @@ def test_no_barrier_with_lds_traffic_in_flight(tmp_path):
         assert p.returncode == 0, out[-2000:]
         rep = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "barrier_audit.py"), asm], stdout=subprocess.PIPE, text=True).stdout
         assert "PENDING" not in rep and "possibly in flight 0" in rep, rep
+
+
+def test_tiled_gemm_refusals_keep_their_text():
+    """The residual pair, the gated pair and the three segmented entry points share one body / one segment check each (mq_gemm.hip): every
+    refusal keeps its return code and the text it had when each entry point carried its own copy.  No HIP call is reached."""
+    import ctypes
+    from mobilequant_amd import _lib as L
+    lib = L.load()
+    p = ctypes.c_void_p(0x10000)
+
+    def grids(qmax=(255.0, 255.0, 255.0)):
+        g = (L.MqGrid * 3)()
+        for i in range(3):
+            g[i].scale, g[i].offset, g[i].qmin, g[i].qmax = 0x10000, 0x10000, 0.0, qmax[i]
+        return g
+
+    def ends(*v):
+        return (ctypes.c_int64 * 3)(*v)
+
+    def err():
+        return lib.mq_last_error().decode()
+
+    seg = {"mq_w8a8_linear_segmented": lambda n, e, g, N=2560: lib.mq_w8a8_linear_segmented(p, p, 2048, N, 2048, None, p, p, p, None, n, e, g, p, None),
+           "mq_w4a8_linear_segmented": lambda n, e, g, N=2560: lib.mq_w4a8_linear_segmented(p, p, 2048, N, 2048, None, p, p, p, None, n, e, g, p, None),
+           "mq_w8a8_linear_tiled_segmented": lambda n, e, g, N=2560: lib.mq_w8a8_linear_tiled_segmented(p, p, 2048, N, 2048, None, p, p, p, None, n, e, g, p, None),
+           "mq_w4a8_linear_tiled": lambda n, e, g, N=2560: lib.mq_w4a8_linear_tiled(p, p, 2048, N, 2048, None, p, p, p, None, n, e, g, p, L.MQ_U8, None)}
+    for fn, call in seg.items():
+        assert call(0, ends(2560), grids()) == 1 and err() == fn + ": 1..3 segments"
+        assert call(3, ends(2048, 2304, 2560), grids((255.0, 65535.0, 255.0))) == 1 and err() == fn + ": segment 1 needs an 8-bit unsigned output grid"
+        assert call(3, ends(2048, 2048, 2560), grids()) == 1 and err() == fn + ": segment ends must increase, be multiples of 4, <= N"
+        assert call(3, ends(2048, 2304, 2432), grids()) == 1 and err() == fn + ": the last segment must end at N"
+    # a single segment of the packed tiled entry point comes without ends; the others insist on them
+    assert lib.mq_w4a8_linear_tiled(p, p, 2048, 2000, 2048, None, p, p, p, None, 1, None, grids(), p, L.MQ_U8, None) == 3
+    assert err() == ("mq_w4a8_linear_tiled: shape 2048x2000x2048 is not served (mq_gemm_tiled_w4_supported: N % 176 == 0 or N % 128 == 0 "
+                     "(segments: 128), K % 256 == 0, K >= 768)")
+    assert seg["mq_w8a8_linear_tiled_segmented"](1, None, grids()) == 1 and err() == "mq_w8a8_linear_tiled_segmented: 1..3 segments"
+    assert seg["mq_w8a8_linear_tiled_segmented"](1, ends(2000), grids(), 2000) == 3
+    assert err() == "mq_w8a8_linear_tiled_segmented: shape 2048x2000x2048 is not served (mq_gemm_tiled128_supported: N % 128 == 0, K % 256 == 0, K >= 768)"
+
+    # residual pair: one body, the 8-bit hint in the int8 entry point's message only
+    for fn, hint in (("mq_w8a8_linear_tiled_residual", " (8-bit grids: mq_w8a8_linear_residual)"), ("mq_w4a8_linear_tiled_residual", "")):
+        f = getattr(lib, fn)
+        assert f(p, p, 2048, 2048, 2048, None, p, p, p, None, p, p, 0.0, 65535.0, None, p, None) == 1
+        assert err() == fn + ": resid must be non-null and 16-byte aligned"
+        assert f(p, p, 2048, 2048, 2048, None, p, p, p, None, p, p, 0.0, 255.0, p, p, None) == 1
+        assert err() == fn + ": a 16-bit output grid is required" + hint
+        assert f(p, p, 2048, 2000, 2048, None, p, p, p, None, p, p, 0.0, 65535.0, p, p, None) == 3
+        assert err() == fn + ": shape 2048x2000x2048 is not served (mq_gemm_tiled128_supported: N % 128 == 0, K % 256 == 0, K >= 768)"
+
+    # gated pair: one body, each entry point's own "not served" text
+    served = {"mq_w8a8_linear_tiled_gated": "mq_gemm_tiled_supported or N % 128 == 0 with >= 192 tiles; K % 256 == 0, K >= 768",
+              "mq_w4a8_linear_tiled_gated": "as mq_w8a8_linear_tiled_gated"}
+    for fn, why in served.items():
+        f = getattr(lib, fn)
+        assert f(p, 2048, 5632, 2048, None, p, p, p, p, None, p, p, p, p, p, p, None, p, p, None, p, p, p, None) == 1
+        assert err() == fn + ": both linears carry an 8-bit unsigned output grid; table / scratch / image must be non-null and 16-byte aligned"
+        assert f(p, 2048, 2000, 2048, None, p, p, p, p, None, p, p, p, p, p, p, None, p, p, p, p, p, p, None) == 3
+        assert err() == fn + ": shape 2048x2000x2048 is not served (" + why + ")"
+    # the pair launch of the same family
+    assert lib.mq_w8a8_linear_tiled_pair(p, 2048, 2048, 2048, None, p, p, p, p, None, p, p, p, p, p, p, p, None, p, p, p, L.MQ_U8, None) == 3
+    assert err() == "mq_w8a8_linear_tiled_pair: shape 2048x2048x2048 is not served (mq_gemm_tiled_supported, K % 256 == 0, K >= 768)"
