@@ -828,6 +828,42 @@ int mq_sample(const mq_sample_args* args, mq_stream_t stream);
  * for tests (bit-exact against a host philox4x32_10). */
 int mq_sample_uniforms(uint64_t seed, uint64_t stream_id, uint32_t n, int64_t first, int64_t count, float* out, mq_stream_t stream);
 
+/* Repetition / presence / frequency penalties and a logit bias in front of the selection rule (step 0 of the rule in
+ * csrc/mq_sample.hip's header).  A row's history h[0..V) of uint32 is the sequence's own past: bit 31 = the token occurs in the prompt,
+ * bits 0..15 = c_i, the times token i was generated (saturating at 65 535); seen_i = (h_i != 0).  Per entry, in fp32, one correctly
+ * rounded operation each and no fused multiply-add:
+ *   l1 = seen_i ? (l_i > 0 ? l_i / repetition : l_i * repetition) : l_i      (prompt and generated tokens)
+ *   t  = frequency * (float)c_i;  t = t + (c_i > 0 ? presence : 0);  l2 = l1 - t      (generated tokens only)
+ *   l3 = bias ? l2 + bias_i : l2
+ * and l3 stands for l_i in the rule (NaN -> -inf and the greedy argmax included).  repetition 1, presence 0, frequency 0 and no bias is
+ * the identity on the bits of l_i: such a row draws what mq_sample draws.  A repetition that is not finite and > 0 is served as 1.
+ * Device data, like mq_sample_row. */
+typedef struct mq_sample_penalty_row {
+  float repetition;
+  float presence;
+  float frequency;
+  int32_t reserved;
+} mq_sample_penalty_row;
+
+/* mq_sample (s: every field and limit as there) with step 0 applied as the kernels read the logits: the logits buffer is not written and
+ * no launch is added.  penalty [rows]; history [rows][history_stride], history_stride >= V and % 4 == 0, both 16-byte aligned; bias:
+ * NULL, or [rows] device pointers in device memory, each NULL (no bias for the row) or a 16-byte aligned dense fp32 [V] (-inf bans a
+ * token).  observe = 1: after a drawing row's token is written, its count in the row's history rises by one (saturating); an idle row
+ * keeps its history.  Each row owns its history: rows must not share one.  Two launches, no host synchronisation: capturable. */
+typedef struct mq_sample_penalized_args {
+  mq_sample_args s;
+  const mq_sample_penalty_row* penalty;
+  uint32_t* history;
+  int64_t history_stride;
+  const float* const* bias;
+  int observe;
+} mq_sample_penalized_args;
+int mq_sample_penalized(const mq_sample_penalized_args* args, mq_stream_t stream);
+/* One row's history [V] (V % 4 == 0, 4 <= V <= 2^20, 16-byte aligned): clear = 1 zeroes it first; then bit 31 is set for each of the n
+ * ids (n >= 0; ids may repeat).  ids is DEVICE memory, so no id is checked on the host: an id outside [0, V) is ignored by the kernel.
+ * At most two launches, capturable. */
+int mq_sample_history_prompt(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int clear, mq_stream_t stream);
+
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes
  * per operand, an fp32 library bmm and two more passes over the product in the reference -- by ONE launch: both fp32 operands are

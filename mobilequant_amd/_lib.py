@@ -95,6 +95,15 @@ class MqSampleArgs(ctypes.Structure):
 MQ_SAMPLE_SCRATCH_BYTES = 8192
 
 
+class MqSamplePenaltyRow(ctypes.Structure):
+    _fields_ = [("repetition", c_float), ("presence", c_float), ("frequency", c_float), ("reserved", ctypes.c_int32)]
+
+
+class MqSamplePenalizedArgs(ctypes.Structure):
+    _fields_ = [("s", MqSampleArgs), ("penalty", c_void_p), ("history", c_void_p), ("history_stride", c_int64), ("bias", c_void_p),
+                ("observe", c_int)]
+
+
 class MqAttentionArgs(ctypes.Structure):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("seq", c_int),
                 ("heads", c_int), ("kv_heads", c_int), ("head_dim", c_int), ("inv_sqrt_d", c_float), ("qk_a", MqGrid),
@@ -184,6 +193,8 @@ _SIGNATURES = {
     "mq_score_head": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P]),
     "mq_sample": (c_int, [POINTER(MqSampleArgs), _P]),
     "mq_sample_uniforms": (c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_int64, c_int64, _P, _P]),
+    "mq_sample_penalized": (c_int, [POINTER(MqSamplePenalizedArgs), _P]),
+    "mq_sample_history_prompt": (c_int, [_P, c_int64, _P, c_int64, c_int, _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

@@ -2,6 +2,11 @@
 //
 // THE RULE (normative).  Per row: fp32 logits l[0..V), temperature >= 0, top_k (0 = off), top_p in (0, 1] (1 = off),
 // min_p in [0, 1) (0 = off), seed and stream (u64), n = pos[row] = the number of tokens already in the sequence.
+//   0. (mq_sample_penalized only.)  With the row's history h[0..V) (bit 31: in the prompt; bits 0..15: c_i, times generated, saturating),
+//      seen_i = (h_i != 0), repetition r, presence a, frequency f and an optional dense bias, each line one correctly rounded fp32
+//      operation, no fused multiply-add:  l1 = seen_i ? (l_i > 0 ? l_i / r : l_i * r) : l_i;  t = f * (float)c_i;
+//      t = t + (c_i > 0 ? a : 0);  l2 = l1 - t;  l3 = bias ? l2 + bias_i : l2.  l3 stands for l_i below.  A neutral row (r = 1, a = f = 0,
+//      no bias) skips the step: the bits of l_i are kept.  r not finite and > 0 is served as 1.
 //   1. z_i = l_i / temperature (fp32, correctly rounded divide; -0 counts as +0).  A NaN logit is -inf.  If every logit is -inf or
 //      NaN the token is 0.
 //   2. Order: z descending, ties by index ascending.  "Prefix" = a prefix in this order.
@@ -33,6 +38,10 @@
 // each w carries expf's error (1 ulp ASSUMED) and the rounding of z_i - z_max, |d_i| 2^-24 relative, whose p-weighted mean is at
 // most 2^-24 log V; flooring drops less than one unit of 2^-32 per token; one rounding of z_tok - z_max and one of the result.  Not
 // part of the bit contract.  All results leave through ordinary vector stores.
+// mq_sample_penalized runs the same two kernels instantiated with the Penalty load policy (sample_scan_penalized_kernel,
+// sample_select_penalized_kernel): step 0 is applied wherever a logit is loaded -- once for a row held in LDS, on every re-read of a longer
+// one -- reading 4 more bytes of history (8 with a bias) per entry; the history is never staged in LDS.  The thread that writes a row's
+// token then counts it in the row's history (observe).
 #include "mq_common.h"
 
 #include <limits.h>
@@ -97,11 +106,73 @@ __device__ __forceinline__ float z_of(float l, const RowCfg& c) {
   return (c.greedy ? l : l / c.t) + 0.f;
 }
 
+// ---- step 0 of the rule: how a kernel reads a logit -------------------------------------------------------------------------------
+// A policy loads entries of a logits row.  NoPenalty is the plain read of mq_sample; Penalty applies step 0 on the way in (mq_sample_penalized),
+// so no kernel writes the logits and none makes a pass of its own for it.
+struct NoArgs {};
+
+struct NoPenalty {
+  __device__ __forceinline__ NoPenalty(const NoArgs&, int) {}
+  __device__ __forceinline__ float4 load4(const float* __restrict__ row, int i) const { return *reinterpret_cast<const float4*>(row + i); }
+  __device__ __forceinline__ float load1(const float* __restrict__ row, int i) const { return row[i]; }
+  __device__ __forceinline__ void observe(int) const {}
+};
+
+struct PenArgs {
+  const mq_sample_penalty_row* pen;
+  unsigned* hist;
+  long long hstride;
+  const float* const* bias;
+  int observe;
+};
+
+struct Penalty {
+  unsigned* h;                    // the row's history: bit 31 = in the prompt, bits 0..15 = times generated
+  const float* b;                 // the row's dense bias, or nullptr
+  float r, a, f;
+  bool active, count;
+  __device__ __forceinline__ Penalty(const PenArgs& pa, int row) {
+    const mq_sample_penalty_row p = pa.pen[row];
+    h = pa.hist + (long long)row * pa.hstride;
+    b = pa.bias ? pa.bias[row] : nullptr;
+    r = (p.repetition > 0.f && p.repetition < __builtin_inff()) ? p.repetition : 1.f;
+    a = p.presence; f = p.frequency;
+    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral row keeps the bits of its logits (-0 stays -0)
+    count = pa.observe != 0;
+  }
+  // one correctly rounded fp32 operation per line (the build has no contraction: -ffp-contract=off)
+  __device__ __forceinline__ float one(float l, unsigned hv, float bv) const {
+    const unsigned c = hv & 0xFFFFu;
+    const float l1 = hv != 0u ? (l > 0.f ? l / r : l * r) : l;
+    float t = f * (float)c;
+    t = t + (c > 0u ? a : 0.f);
+    const float l2 = l1 - t;
+    return b ? l2 + bv : l2;
+  }
+  __device__ __forceinline__ float4 load4(const float* __restrict__ row, int i) const {
+    const float4 l = *reinterpret_cast<const float4*>(row + i);
+    if (!active) return l;                                          // workgroup-uniform
+    const uint4 hv = *reinterpret_cast<const uint4*>(h + i);
+    const float4 bv = b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    return make_float4(one(l.x, hv.x, bv.x), one(l.y, hv.y, bv.y), one(l.z, hv.z, bv.z), one(l.w, hv.w, bv.w));
+  }
+  __device__ __forceinline__ float load1(const float* __restrict__ row, int i) const {
+    return active ? one(row[i], h[i], b ? b[i] : 0.f) : row[i];
+  }
+  // the drawn token's count, saturating at 65 535: one thread, after every read of the row's history in this launch
+  __device__ __forceinline__ void observe(int t) const {
+    if (!count) return;
+    const unsigned v = h[t];
+    if ((v & 0xFFFFu) != 0xFFFFu) h[t] = v + 1u;
+  }
+};
+
 // running best of z + g (greedy: z) over entries [lo, hi) of the row, 4 per thread and step; lo, hi multiples of 4
-__device__ __forceinline__ Best scan_range(const float* __restrict__ row, int lo, int hi, const RowCfg& c, int tid, int nthreads) {
+template <class Pol>
+__device__ __forceinline__ Best scan_range(const float* __restrict__ row, int lo, int hi, const RowCfg& c, const Pol& p, int tid, int nthreads) {
   Best b{-__builtin_inff(), INT_MAX};
   for (int i = lo + 4 * tid; i < hi; i += 4 * nthreads) {
-    const float4 l = *reinterpret_cast<const float4*>(row + i);
+    const float4 l = p.load4(row, i);
     const float lv[4] = {l.x, l.y, l.z, l.w};
     unsigned r[4] = {0, 0, 0, 0};
     if (!c.greedy) philox4x32_10(c.n, (unsigned)(i >> 2), c.s0, c.s1, c.k0, c.k1, r);
@@ -148,8 +219,9 @@ __device__ __forceinline__ void slice_bounds(int V, int S, int s, int* lo, int* 
   *hi = min(V, *lo + len);
 }
 
-__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_kernel(const float* __restrict__ logits, long long stride, int V, const int* __restrict__ pos,
-                                                                      int cache_len, const mq_sample_row* __restrict__ params, Best* __restrict__ part) {
+template <class Pol, class PolArgs>
+__device__ __forceinline__ void sample_scan(const float* __restrict__ logits, long long stride, int V, const int* __restrict__ pos, int cache_len,
+                                            const mq_sample_row* __restrict__ params, Best* __restrict__ part, const PolArgs& pa) {
   __shared__ float red_v[SM_SCAN_THREADS / 64];
   __shared__ int red_i[SM_SCAN_THREADS / 64];
   const int row = blockIdx.y, s = blockIdx.x, S = gridDim.x, tid = threadIdx.x;
@@ -157,10 +229,23 @@ __global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_kernel(const floa
   if (row_idle(pos, row, cache_len, &n)) return;                      // workgroup-uniform
   const RowCfg c = row_cfg(params[row], n, V);
   if (c.filtered) return;
+  const Pol p(pa, row);
   int lo, hi;
   slice_bounds(V, S, s, &lo, &hi);
-  const Best b = block_best(scan_range(logits + (long long)row * stride, lo, hi, c, tid, SM_SCAN_THREADS), red_v, red_i, tid, SM_SCAN_THREADS / 64);
+  const Best b = block_best(scan_range(logits + (long long)row * stride, lo, hi, c, p, tid, SM_SCAN_THREADS), red_v, red_i, tid, SM_SCAN_THREADS / 64);
   if (tid == 0) part[row * SM_MAX_SLICES + s] = b;
+}
+
+__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_kernel(const float* __restrict__ logits, long long stride, int V, const int* __restrict__ pos,
+                                                                      int cache_len, const mq_sample_row* __restrict__ params, Best* __restrict__ part) {
+  sample_scan<NoPenalty>(logits, stride, V, pos, cache_len, params, part, NoArgs{});
+}
+
+__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_penalized_kernel(const float* __restrict__ logits, long long stride, int V,
+                                                                                const int* __restrict__ pos, int cache_len,
+                                                                                const mq_sample_row* __restrict__ params, Best* __restrict__ part,
+                                                                                PenArgs pa) {
+  sample_scan<Penalty>(logits, stride, V, pos, cache_len, params, part, pa);
 }
 
 // ---- launch 2 ------------------------------------------------------------------------------------------------------------------
@@ -190,9 +275,10 @@ struct RowSrc {
   const float* z;                 // LDS copy (z), or nullptr
 };
 
-__device__ __forceinline__ float4 load_z4(const RowSrc& r, int i, const RowCfg& c) {
+template <class Pol>
+__device__ __forceinline__ float4 load_z4(const RowSrc& r, int i, const RowCfg& c, const Pol& p) {
   if (r.z) return *reinterpret_cast<const float4*>(r.z + i);
-  const float4 l = *reinterpret_cast<const float4*>(r.g + i);
+  const float4 l = p.load4(r.g, i);
   return make_float4(z_of(l.x, c), z_of(l.y, c), z_of(l.z, c), z_of(l.w, c));
 }
 
@@ -210,7 +296,8 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
 
 // The cut of the shortest prefix (among tokens with key >= lb) whose count (by_mass = false) or mass (true) reaches `need` (>= 1, at most
 // the total).  Returns the cut key; *cnt / *mass = the prefix's count and mass (the cut token included).
-__device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c, float zmax, unsigned long long lb, bool by_mass,
+template <class Pol>
+__device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c, const Pol& p, float zmax, unsigned long long lb, bool by_mass,
                                          unsigned long long need, const Lds& L, int tid, unsigned long long* cnt, unsigned long long* mass) {
   const int SH[SM_LEVELS] = {41, 30, 20, 10, 0}, WD[SM_LEVELS] = {11, 11, 10, 10, 10};
   unsigned long long prefix = 0, acc_c = 0, acc_m = 0;
@@ -223,7 +310,7 @@ __device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c
     if (tid == 0) { L.found[0] = 0; L.found[1] = 0; L.found[2] = 0; L.found[3] = 0; L.found[4] = 0; }
     __syncthreads();
     for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
-      const float4 z4 = load_z4(r, i, c);
+      const float4 z4 = load_z4(r, i, c, p);
       const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -268,7 +355,7 @@ __device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c
       if (level < SM_LEVELS - 1 && in_c == 1) {                  // the digit holds one token: read its key instead of descending
         __syncthreads();
         for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
-          const float4 z4 = load_z4(r, i, c);
+          const float4 z4 = load_z4(r, i, c, p);
           const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -287,15 +374,16 @@ __device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c
   return prefix;
 }
 
-__global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
-                                                                   const int* __restrict__ pos, int cache_len,
-                                                                   const mq_sample_row* __restrict__ params, const Best* __restrict__ part,
-                                                                   long long* __restrict__ tok, int* __restrict__ kept, float* __restrict__ logprob) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+template <class Pol, class PolArgs>
+__device__ __forceinline__ void sample_select(unsigned char* smem, const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
+                                              const int* __restrict__ pos, int cache_len, const mq_sample_row* __restrict__ params,
+                                              const Best* __restrict__ part, long long* __restrict__ tok, int* __restrict__ kept,
+                                              float* __restrict__ logprob, const PolArgs& pa) {
   const int row = blockIdx.x, tid = threadIdx.x;
   int n;
-  if (row_idle(pos, row, cache_len, &n)) return;                      // workgroup-uniform: an idle row keeps its token
+  if (row_idle(pos, row, cache_len, &n)) return;                      // workgroup-uniform: an idle row keeps its token and its history
   const RowCfg c = row_cfg(params[row], n, V);
+  const Pol p(pa, row);
   Lds L;
   L.z = reinterpret_cast<float*>(smem);
   L.hm = reinterpret_cast<unsigned long long*>(smem + (size_t)lds_row * 4);
@@ -314,11 +402,13 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* 
       if (tid < S) b = part[row * SM_MAX_SLICES + tid];
       b = block_best(b, L.red_v, L.red_i, tid, SM_WAVES);
     } else {
-      b = block_best(scan_range(r.g, 0, V, c, tid, SM_THREADS), L.red_v, L.red_i, tid, SM_WAVES);
+      b = block_best(scan_range(r.g, 0, V, c, p, tid, SM_THREADS), L.red_v, L.red_i, tid, SM_WAVES);
     }
     if (tid == 0) {
-      tok[row] = b.i == INT_MAX ? 0 : b.i;
+      const int t = b.i == INT_MAX ? 0 : b.i;
+      tok[row] = t;
       if (kept) kept[row] = c.greedy ? 1 : V;
+      p.observe(t);
     }
     return;
   }
@@ -326,7 +416,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* 
   // stage the row as z; its maximum
   Best zb{NEG_INF, INT_MAX};
   for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
-    const float4 z4 = load_z4(r, i, c);
+    const float4 z4 = load_z4(r, i, c, p);
     if (lds_row) *reinterpret_cast<float4*>(L.z + i) = z4;
     const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
 #pragma unroll
@@ -338,9 +428,11 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* 
   const float zmax = zb.v;
   if (zmax == NEG_INF || c.greedy) {                                  // nothing to draw from (token 0), or greedy with a log-probability asked for
     if (tid == 0) {
-      tok[row] = zmax == NEG_INF ? 0 : zb.i;
+      const int t = zmax == NEG_INF ? 0 : zb.i;
+      tok[row] = t;
       if (kept) kept[row] = zmax == NEG_INF ? 0 : 1;
       if (logprob) logprob[row] = 0.f;
+      p.observe(t);
     }
     return;
   }
@@ -348,11 +440,11 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* 
   unsigned long long cut = 0, cnt = (unsigned long long)V, wk = 0;
   const bool use_k = c.top_k > 0 && c.top_k < V;
   if (use_k) {
-    cut = select_cut(r, V, c, zmax, 0ull, false, (unsigned long long)c.top_k, L, tid, &cnt, &wk);
+    cut = select_cut(r, V, c, p, zmax, 0ull, false, (unsigned long long)c.top_k, L, tid, &cnt, &wk);
   } else if (c.top_p < 1.f) {
     unsigned long long m = 0;
     for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
-      const float4 z4 = load_z4(r, i, c);
+      const float4 z4 = load_z4(r, i, c, p);
       m += mass_of(z4.x, zmax) + mass_of(z4.y, zmax) + mass_of(z4.z, zmax) + mass_of(z4.w, zmax);
     }
     wk = block_sum_u64(m, L, tid);
@@ -361,7 +453,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* 
     unsigned long long need = (unsigned long long)ceil((double)c.top_p * (double)wk);
     need = need < 1ull ? 1ull : (need > wk ? wk : need);
     unsigned long long pm;
-    cut = select_cut(r, V, c, zmax, cut, true, need, L, tid, &cnt, &pm);
+    cut = select_cut(r, V, c, p, zmax, cut, true, need, L, tid, &cnt, &pm);
   }
 
   // the draw: argmax of z + g over key >= cut with the min-p test; |C| and its mass on the way
@@ -369,7 +461,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* 
   Best b{NEG_INF, INT_MAX};
   unsigned long long nkept = 0, wc = 0;
   for (int i = 4 * tid; i < V; i += 4 * SM_THREADS) {
-    const float4 z4 = load_z4(r, i, c);
+    const float4 z4 = load_z4(r, i, c, p);
     const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
     bool in[4], any = false;
 #pragma unroll
@@ -397,10 +489,42 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* 
     tok[row] = t;
     if (kept) kept[row] = (int)nkept;
     if (logprob) {
-      const float zt = r.z ? r.z[t] : z_of(r.g[t], c);
+      const float zt = r.z ? r.z[t] : z_of(p.load1(r.g, t), c);
       logprob[row] = (float)((double)(zt - zmax) - (log((double)wc) - 32.0 * 0.693147180559945309417));
     }
+    p.observe(t);
   }
+}
+
+__global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
+                                                                   const int* __restrict__ pos, int cache_len,
+                                                                   const mq_sample_row* __restrict__ params, const Best* __restrict__ part,
+                                                                   long long* __restrict__ tok, int* __restrict__ kept, float* __restrict__ logprob) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  sample_select<NoPenalty>(smem, logits, stride, V, S, lds_row, pos, cache_len, params, part, tok, kept, logprob, NoArgs{});
+}
+
+// mq_sample_penalized: the same selection with step 0 applied as a row is read; the drawn token is counted in the row's history at the tail
+__global__ __launch_bounds__(SM_THREADS) void sample_select_penalized_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
+                                                                             const int* __restrict__ pos, int cache_len,
+                                                                             const mq_sample_row* __restrict__ params, const Best* __restrict__ part,
+                                                                             long long* __restrict__ tok, int* __restrict__ kept,
+                                                                             float* __restrict__ logprob, PenArgs pa) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  sample_select<Penalty>(smem, logits, stride, V, S, lds_row, pos, cache_len, params, part, tok, kept, logprob, pa);
+}
+
+__global__ void history_clear_kernel(uint4* __restrict__ h, int n4) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n4) h[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// ids repeat: the OR is idempotent.  An id outside [0, V) is ignored.
+__global__ void history_mark_kernel(unsigned* __restrict__ h, int V, const long long* __restrict__ ids, long long n) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const long long t = ids[j];
+  if (t >= 0 && t < V) atomicOr(&h[t], 0x80000000u);
 }
 
 __global__ void sample_uniforms_kernel(unsigned long long seed, unsigned long long stream, unsigned n, long long first, long long count,
@@ -417,7 +541,59 @@ size_t select_lds_bytes(int lds_row) {
   return (size_t)lds_row * 4 + (size_t)SM_BINS * 8 + 8 * 8 + 2 * SM_WAVES * 8 + (size_t)SM_BINS * 4 + 2 * SM_WAVES * 4;
 }
 
-PerDeviceOnce g_lds_set;
+PerDeviceOnce g_lds_set, g_lds_set_pen;
+
+int check_sample_args(const mq_sample_args* a, const char* who) {
+  MQ_REQUIRE(a->logits && a->pos && a->params && a->tok && a->scratch,
+             "%s: null pointer (logits, pos, params, tok and scratch are required; kept and logprob are optional)", who);
+  MQ_REQUIRE(a->rows >= 1 && a->rows <= MQ_DECODE_MAX_BATCH, "%s: rows=%d outside 1..%d", who, a->rows, MQ_DECODE_MAX_BATCH);
+  MQ_REQUIRE(a->V >= 4 && a->V % 4 == 0 && a->V <= (1 << 20), "%s: V=%lld must be a multiple of 4 in [4, 2^20]", who, (long long)a->V);
+  MQ_REQUIRE(a->logits_stride >= a->V && a->logits_stride % 4 == 0, "%s: logits_stride=%lld must be >= V and a multiple of 4", who,
+             (long long)a->logits_stride);
+  MQ_REQUIRE(a->cache_len >= 1, "%s: cache_len=%d must be >= 1 (a row with pos outside [0, cache_len) is idle)", who, a->cache_len);
+  MQ_REQUIRE(aligned(a->logits, 16) && aligned(a->params, 16) && aligned(a->scratch, 16), "%s: logits, params and scratch must be 16-byte aligned", who);
+  MQ_REQUIRE(aligned(a->tok, 8) && aligned(a->pos, 4) && aligned(a->kept, 4) && aligned(a->logprob, 4), "%s: tok must be 8-byte, pos / kept / logprob 4-byte aligned", who);
+  MQ_REQUIRE(a->scratch_bytes >= MQ_SAMPLE_SCRATCH_BYTES, "%s: scratch_bytes=%lld below MQ_SAMPLE_SCRATCH_BYTES", who, (long long)a->scratch_bytes);
+  static_assert(MQ_SAMPLE_SCRATCH_BYTES >= MQ_DECODE_MAX_BATCH * SM_MAX_SLICES * sizeof(Best), "scratch holds every row's partials");
+  static_assert(sizeof(mq_sample_row) == 32, "mq_sample_row is 32 bytes");
+  static_assert(sizeof(mq_sample_penalty_row) == 16, "mq_sample_penalty_row is 16 bytes");
+  return MQ_OK;
+}
+
+// the two launches of mq_sample (pa == nullptr) and of mq_sample_penalized
+int launch_sample(const mq_sample_args* a, const PenArgs* pa, const char* who, mq_stream_t stream) {
+  const int V = (int)a->V;
+  const int S = min(SM_MAX_SLICES, (V + SM_SLICE - 1) / SM_SLICE);
+  const int lds_row = V <= SM_LDS_ROW ? V : 0;
+  const size_t lds = select_lds_bytes(lds_row);
+  const int dev = current_device();
+  PerDeviceOnce& once = pa ? g_lds_set_pen : g_lds_set;
+  if (!once.done(dev)) {
+    const void* fn = pa ? (const void*)sample_select_penalized_kernel : (const void*)sample_select_kernel;
+    MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_LDS_ROW)) == hipSuccess,
+               "%s: hipFuncSetAttribute(%zu B LDS) failed", who, select_lds_bytes(SM_LDS_ROW));
+    once.mark(dev);
+  }
+  hipStream_t st = as_stream(stream);
+  Best* part = static_cast<Best*>(a->scratch);
+  long long* tok = reinterpret_cast<long long*>(a->tok);
+  if (S > 1) {
+    const dim3 grid((unsigned)S, (unsigned)a->rows);
+    if (pa)
+      sample_scan_penalized_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part, *pa);
+    else
+      sample_scan_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part);
+    MQ_LAUNCH_CHECK(who);
+  }
+  if (pa)
+    sample_select_penalized_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len,
+                                                                              a->params, part, tok, a->kept, a->logprob, *pa);
+  else
+    sample_select_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len, a->params,
+                                                                    part, tok, a->kept, a->logprob);
+  MQ_LAUNCH_CHECK(who);
+  return MQ_OK;
+}
 
 }  // namespace
 }  // namespace mq
@@ -428,38 +604,39 @@ extern "C" {
 
 int mq_sample(const mq_sample_args* a, mq_stream_t stream) {
   MQ_REQUIRE(a != nullptr, "mq_sample: null argument block");
-  MQ_REQUIRE(a->logits && a->pos && a->params && a->tok && a->scratch,
-             "mq_sample: null pointer (logits, pos, params, tok and scratch are required; kept and logprob are optional)");
-  MQ_REQUIRE(a->rows >= 1 && a->rows <= MQ_DECODE_MAX_BATCH, "mq_sample: rows=%d outside 1..%d", a->rows, MQ_DECODE_MAX_BATCH);
-  MQ_REQUIRE(a->V >= 4 && a->V % 4 == 0 && a->V <= (1 << 20), "mq_sample: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)a->V);
-  MQ_REQUIRE(a->logits_stride >= a->V && a->logits_stride % 4 == 0, "mq_sample: logits_stride=%lld must be >= V and a multiple of 4",
-             (long long)a->logits_stride);
-  MQ_REQUIRE(a->cache_len >= 1, "mq_sample: cache_len=%d must be >= 1 (a row with pos outside [0, cache_len) is idle)", a->cache_len);
-  MQ_REQUIRE(aligned(a->logits, 16) && aligned(a->params, 16) && aligned(a->scratch, 16), "mq_sample: logits, params and scratch must be 16-byte aligned");
-  MQ_REQUIRE(aligned(a->tok, 8) && aligned(a->pos, 4) && aligned(a->kept, 4) && aligned(a->logprob, 4), "mq_sample: tok must be 8-byte, pos / kept / logprob 4-byte aligned");
-  MQ_REQUIRE(a->scratch_bytes >= MQ_SAMPLE_SCRATCH_BYTES, "mq_sample: scratch_bytes=%lld below MQ_SAMPLE_SCRATCH_BYTES", (long long)a->scratch_bytes);
-  static_assert(MQ_SAMPLE_SCRATCH_BYTES >= MQ_DECODE_MAX_BATCH * SM_MAX_SLICES * sizeof(Best), "scratch holds every row's partials");
-  static_assert(sizeof(mq_sample_row) == 32, "mq_sample_row is 32 bytes");
-  const int V = (int)a->V;
-  const int S = min(SM_MAX_SLICES, (V + SM_SLICE - 1) / SM_SLICE);
-  const int lds_row = V <= SM_LDS_ROW ? V : 0;
-  const size_t lds = select_lds_bytes(lds_row);
-  const int dev = current_device();
-  if (!g_lds_set.done(dev)) {
-    MQ_REQUIRE(hipFuncSetAttribute((const void*)sample_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_LDS_ROW)) == hipSuccess,
-               "mq_sample: hipFuncSetAttribute(%zu B LDS) failed", select_lds_bytes(SM_LDS_ROW));
-    g_lds_set.mark(dev);
-  }
+  if (const int rc = check_sample_args(a, "mq_sample")) return rc;
+  return launch_sample(a, nullptr, "mq_sample", stream);
+}
+
+int mq_sample_penalized(const mq_sample_penalized_args* a, mq_stream_t stream) {
+  MQ_REQUIRE(a != nullptr, "mq_sample_penalized: null argument block");
+  if (const int rc = check_sample_args(&a->s, "mq_sample_penalized")) return rc;
+  MQ_REQUIRE(a->penalty != nullptr && a->history != nullptr, "mq_sample_penalized: null pointer (penalty and history are required; bias is optional)");
+  MQ_REQUIRE(aligned(a->penalty, 16) && aligned(a->history, 16) && aligned(a->bias, 8),
+             "mq_sample_penalized: penalty and history must be 16-byte aligned, bias 8-byte aligned");
+  MQ_REQUIRE(a->history_stride >= a->s.V && a->history_stride % 4 == 0, "mq_sample_penalized: history_stride=%lld must be >= V and a multiple of 4",
+             (long long)a->history_stride);
+  MQ_REQUIRE(a->observe == 0 || a->observe == 1, "mq_sample_penalized: observe=%d must be 0 or 1", a->observe);
+  const PenArgs pa{a->penalty, a->history, (long long)a->history_stride, a->bias, a->observe};
+  return launch_sample(&a->s, &pa, "mq_sample_penalized", stream);
+}
+
+int mq_sample_history_prompt(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int clear, mq_stream_t stream) {
+  MQ_REQUIRE(history != nullptr && aligned(history, 16), "mq_sample_history_prompt: history must be a 16-byte aligned pointer");
+  MQ_REQUIRE(V >= 4 && V % 4 == 0 && V <= (1 << 20), "mq_sample_history_prompt: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)V);
+  MQ_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "mq_sample_history_prompt: n=%lld outside [0, 2^31]", (long long)n);
+  MQ_REQUIRE(n == 0 || (ids != nullptr && aligned(ids, 8)), "mq_sample_history_prompt: ids must be an 8-byte aligned pointer when n > 0");
+  MQ_REQUIRE(clear == 0 || clear == 1, "mq_sample_history_prompt: clear=%d must be 0 or 1", clear);
   hipStream_t st = as_stream(stream);
-  Best* part = static_cast<Best*>(a->scratch);
-  if (S > 1) {
-    sample_scan_kernel<<<dim3((unsigned)S, (unsigned)a->rows), SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len,
-                                                                                        a->params, part);
-    MQ_LAUNCH_CHECK("mq_sample");
+  if (clear) {
+    const int n4 = (int)(V / 4);
+    history_clear_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(reinterpret_cast<uint4*>(history), n4);
+    MQ_LAUNCH_CHECK("mq_sample_history_prompt");
   }
-  sample_select_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len, a->params,
-                                                                  part, reinterpret_cast<long long*>(a->tok), a->kept, a->logprob);
-  MQ_LAUNCH_CHECK("mq_sample");
+  if (n > 0) {
+    history_mark_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(history, (int)V, reinterpret_cast<const long long*>(ids), (long long)n);
+    MQ_LAUNCH_CHECK("mq_sample_history_prompt");
+  }
   return MQ_OK;
 }
 

@@ -639,7 +639,7 @@ class DecodeEngine(_DecodeBase):
         self.graph = None
         self.graph_long = None
         self._sampler = None                                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
-        self._sample_graphs = {}                             # step variant -> the captured sample + step graph, recorded on first use
+        self._sample_graphs = {}                             # (step variant, penalised) -> the captured sample + step graph, recorded on first use
         self._lower()
 
     @classmethod
@@ -889,7 +889,7 @@ class DecodeEngine(_DecodeBase):
         if self._keep.stale():
             self._lower()
         self._row_graphs = {}                                    # (multi-token steps: one graph per row count, recorded on first use)
-        self._sample_graphs = {}                                 # (sample + step: one graph per step variant, recorded on first use)
+        self._sample_graphs = {}                                 # (sample + step: one graph per step variant and selection entry, recorded on first use)
         tok0, pos0, hp0 = self.tok.clone(), self.pos.clone(), self._host_pos
         graphs = []
         for phases, splits in self._variants():
@@ -969,12 +969,25 @@ class DecodeEngine(_DecodeBase):
 
     # -- seeded token selection on the device (csrc/mq_sample.hip) ---------------------------------------------
     def set_sampling(self, sampling: SamplingParams, stream: int = 0):
-        """The request sample() serves from now on: rewritten in device memory, the captured graphs stay valid."""
+        """The request sample() serves from now on: rewritten in device memory, the captured graphs stay valid.  A request with a
+        penalty or a logit bias (sampling.penalized) is served by mq_sample_penalized from the sequence's token history: generate()
+        rebuilds that history itself; a caller who drives sample_step() gives it with observe_history(ids).  rewind() and
+        set_position() do not touch it."""
         if not isinstance(sampling, SamplingParams):
             raise TypeError(f"DecodeEngine.set_sampling: expected SamplingParams, got {type(sampling).__name__}")
         if self._sampler is None:
             self._sampler = SampleLaunch(self.logits, self.pos, self.tok, self.cache_len)
         self._sampler.set_rows([sampling], [check_stream(stream)])
+        return self
+
+    def observe_history(self, ids):
+        """Make `ids` the token history the penalties see: the history is cleared and every id is marked as a prompt token (the
+        repetition penalty covers it; presence and frequency count generated tokens only).  Every token drawn afterwards by sample() /
+        sample_step() under a penalised request is counted on the device.  After rewind() or set_position() the history is stale: call
+        this again with the tokens the sequence now holds.  Without a penalised request since the engine was built it does nothing."""
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        self._sampler.observe_prompt(0, ids, clear=True)
         return self
 
     @torch.no_grad()
@@ -987,8 +1000,8 @@ class DecodeEngine(_DecodeBase):
             self._sampler.launch()
         return self.tok
 
-    def _capture_sample_step(self, variant: int):
-        """Record mq_sample followed by the step (and the position advance) as one graph: the embedding launch reads the token the
+    def _capture_sample_step(self, variant: int, penalized: bool):
+        """Record mq_sample (penalized: mq_sample_penalized) followed by the step (and the position advance) as one graph: the embedding launch reads the token the
         sample launch of the same replay wrote, and the sample launch reads the position in front of the step.  The launch outside
         the capture (the kernel's LDS ceiling) runs with the position at the cache_len sentinel: the row is idle, the token stays."""
         phases, splits = self._variants()[variant]
@@ -999,7 +1012,7 @@ class DecodeEngine(_DecodeBase):
         def step():
             self._launch(phases)
             self.pos.add_(1)
-        g = self._sample_graphs[variant] = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
+        g = self._sample_graphs[(variant, penalized)] = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
         self._set_splits(*self._variants()[0])
         return g
 
@@ -1014,8 +1027,8 @@ class DecodeEngine(_DecodeBase):
         if self.graph is None:
             self.sample()
             return self.step()
-        v = self._variant_at(self._host_pos)
-        (self._sample_graphs.get(v) or self._capture_sample_step(v)).replay()
+        key = (self._variant_at(self._host_pos), self._sampler.penalized)      # a request of the other kind records a graph of its own
+        (self._sample_graphs.get(key) or self._capture_sample_step(*key)).replay()
         self._host_pos += 1
         return self.logits
 
@@ -1052,7 +1065,7 @@ class DecodeEngine(_DecodeBase):
         draft(ids, k) -> at most k proposals (prompt_lookup_draft) -- verified num_draft tokens at a time with step_tokens.  The
         returned ids equal the plain greedy ones token for token; self.spec_stats counts the rounds (_generate_speculative).
         sampling (with stream, the sequence's identity): seeded selection on the device by mq_sample's rule (temperature, top-k, top-p,
-        min-p) -- the ids depend on (context, sampling, stream) only: BatchDecodeEngine.generate returns the same ids
+        min-p, behind the repetition / presence / frequency penalties and the logit bias of the sequence's own tokens) -- the ids depend on (context, sampling, stream) only: BatchDecodeEngine.generate returns the same ids
         for this sequence in any batch and slot.  After capture() a token costs one graph replay (sample + step) and one token
         read-back; a sequence that ends on an EOS has then cached that token too (position() is one past the returned ids)."""
         if sampling is not None:
@@ -1087,6 +1100,8 @@ class DecodeEngine(_DecodeBase):
         assert len(ids) + max_new_tokens <= self.cache_len
         self.set_sampling(sampling, stream)
         self._start_sequence(ids, prefill)
+        if self._sampler.penalized:
+            self._sampler.observe_prompt(0, ids)                   # the history is rebuilt for every sequence
         out = list(ids)
         eos = _eos_set(eos_token_id)
         for made in range(1, max_new_tokens + 1):

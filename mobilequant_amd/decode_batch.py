@@ -66,7 +66,7 @@ class BatchDecodeEngine(_DecodeBase):
         self._active = [False] * B
         self.graph = None
         self._sampler = None                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
-        self._sample_graph = None            # the captured sample + step graph, recorded on first use after capture()
+        self._sample_graphs = {}             # penalised -> the captured sample + step graph, recorded on first use after capture()
         self._lower()
 
     def _lower(self):
@@ -103,13 +103,14 @@ class BatchDecodeEngine(_DecodeBase):
         self.attn_ticket.zero_()
         self.graph = self._record(self._launch, self._advance)
         self.pos.copy_(pos0)
-        self._sample_graph = None
+        self._sample_graphs = {}
         return self
 
     # -- seeded token selection on the device (csrc/mq_sample.hip) ---------------------------------------------
     def set_sampling(self, sampling, streams: Optional[Sequence[int]] = None):
         """Per-slot requests for sample(): one SamplingParams for every slot or one per slot; streams (the sequences' identities)
-        default to the slot numbers.  Rewritten in device memory: the captured graphs stay valid."""
+        default to the slot numbers.  Rewritten in device memory: the captured graphs stay valid.  Penalised and neutral requests
+        may mix; a penalised slot reads its own token history (observe_history(slot, ids); generate() keeps it itself)."""
         rows = [sampling] * self.batch if isinstance(sampling, SamplingParams) else list(sampling)
         st = list(range(self.batch)) if streams is None else [check_stream(v) for v in streams]
         if len(rows) != self.batch or len(st) != self.batch:
@@ -117,6 +118,15 @@ class BatchDecodeEngine(_DecodeBase):
         if self._sampler is None:
             self._sampler = SampleLaunch(self.logits, self.pos, self.tok, self.cache_len)
         self._sampler.set_rows(rows, st)
+        return self
+
+    def observe_history(self, slot: int, ids):
+        """DecodeEngine.observe_history for one slot: its history is cleared and `ids` are marked as its prompt tokens.  release(slot)
+        clears it; set_position(slot, ...) leaves it as it is."""
+        self._check_slot(slot)
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        self._sampler.observe_prompt(slot, ids, clear=True)
         return self
 
     @torch.no_grad()
@@ -138,8 +148,8 @@ class BatchDecodeEngine(_DecodeBase):
         def step():
             self._launch()
             self._advance()
-        self._sample_graph = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
-        return self._sample_graph
+        g = self._sample_graphs[self._sampler.penalized] = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
+        return g
 
     @torch.no_grad()
     def sample_step(self) -> torch.Tensor:
@@ -152,7 +162,7 @@ class BatchDecodeEngine(_DecodeBase):
         for b in range(self.batch):
             if self._active[b] and self._host_pos[b] >= self.cache_len:
                 raise RuntimeError(f"BatchDecodeEngine.sample_step: slot {b}'s KV cache is full ({self.cache_len} positions); release() it first")
-        (self._sample_graph or self._capture_sample_step()).replay()
+        (self._sample_graphs.get(self._sampler.penalized) or self._capture_sample_step()).replay()
         for b in range(self.batch):
             if self._active[b]:
                 self._host_pos[b] += 1
@@ -193,6 +203,8 @@ class BatchDecodeEngine(_DecodeBase):
         self.pos[slot] = self.cache_len
         self._host_pos[slot] = self.cache_len
         self._active[slot] = False
+        if self._sampler is not None:
+            self._sampler.clear_history(slot)                  # (a no-op until a penalised request has allocated the histories)
 
     def fill_cache_random(self, slot: int, n: int, seed: int = 0):
         """Benchmark helper: n positions of random cached indices in one slot, which becomes active at position n."""
@@ -303,6 +315,9 @@ class BatchDecodeEngine(_DecodeBase):
         if sampling is not None:
             idle = SamplingParams(temperature=0.0)
             self.set_sampling(rows + [idle] * (self.batch - n), st + [0] * (self.batch - n))
+            if self._sampler.penalized:
+                for i, p in enumerate(prompts):
+                    self._sampler.observe_prompt(i, p)             # slot i's history: cleared, then its prompt
             while live:
                 if all(made[i] + 1 >= max_new_tokens for i in live):
                     self.sample()                                  # the last tokens need no step

@@ -5,30 +5,47 @@ from __future__ import annotations
 import ctypes
 import math
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MQ_SAMPLE_SCRATCH_BYTES, MqSampleArgs
+from ._lib import MQ_SAMPLE_SCRATCH_BYTES, MqSampleArgs, MqSamplePenalizedArgs
 
 MAX_ROWS = 8
 MAX_VOCAB = 1 << 20
 ROW_DTYPE = np.dtype([("temperature", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"), ("min_p", "<f4"), ("seed", "<u8"), ("stream", "<u8")])
 assert ROW_DTYPE.itemsize == ctypes.sizeof(_lib.MqSampleRow) == 32
+PENALTY_DTYPE = np.dtype([("repetition", "<f4"), ("presence", "<f4"), ("frequency", "<f4"), ("reserved", "<i4")])
+assert PENALTY_DTYPE.itemsize == ctypes.sizeof(_lib.MqSamplePenaltyRow) == 16
+HISTORY_PROMPT_BIT = 1 << 31                      # a history entry: bit 31 = in the prompt, bits 0..15 = times generated (saturating)
+
+
+def _f32(v) -> np.float32:
+    with np.errstate(over="ignore"):
+        return np.float32(v)
 
 
 @dataclass(frozen=True)
 class SamplingParams:
     """temperature >= 0 (0 = greedy), top_k >= 0 (0 = off), top_p in (0, 1] (1 = off), min_p in [0, 1) (0 = off), seed in [0, 2^64).
     Filters compose in the usual order: temperature, top-k, top-p, min-p.  With a seed, a stream (the sequence's identity) and the
-    position, the drawn token is a property of the sequence: the same in any batch, in any slot, captured or not."""
+    position, the drawn token is a property of the sequence: the same in any batch, in any slot, captured or not.
+    In front of them (step 0 of the rule), from the sequence's own tokens: repetition_penalty > 0 (1 = off; a positive
+    logit of a token of the prompt or of the generated text is divided by it, a negative one multiplied: transformers'
+    RepetitionPenaltyLogitsProcessor), presence_penalty and frequency_penalty (0 = off; subtracted once, and once per occurrence, for
+    tokens generated so far: the OpenAI / vLLM definition) and logit_bias {token id: added value} (-inf bans a token; stored as a sorted
+    tuple of pairs, so the request stays hashable)."""
     temperature: float = 1.0
     top_k: int = 0
     top_p: float = 1.0
     min_p: float = 0.0
     seed: int = 0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Optional[Mapping[int, float]] = None
 
     def __post_init__(self):
         t, k, p, m, s = self.temperature, self.top_k, self.top_p, self.min_p, self.seed
@@ -44,6 +61,34 @@ class SamplingParams:
             raise ValueError(f"SamplingParams: seed={s!r} must be an int in [0, 2^64)")
         if np.float32(p) <= 0 or np.float32(m) >= 1:
             raise ValueError("SamplingParams: top_p / min_p leave their range when rounded to fp32")
+        r, a, f, lb = self.repetition_penalty, self.presence_penalty, self.frequency_penalty, self.logit_bias
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not (math.isfinite(r) and r > 0) or not 0 < _f32(r) < np.inf:
+            raise ValueError(f"SamplingParams: repetition_penalty={r!r} must be a finite number > 0 in fp32 (1 = off)")
+        for name, v in (("presence_penalty", a), ("frequency_penalty", f)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not np.isfinite(_f32(v)):
+                raise ValueError(f"SamplingParams: {name}={v!r} must be a finite number in fp32 (0 = off)")
+        if lb is not None:
+            items = lb.items() if isinstance(lb, Mapping) else lb
+            pairs = []
+            try:
+                for t, v in items:
+                    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or int(t) < 0:
+                        raise ValueError(f"SamplingParams: logit_bias token id {t!r} must be an int >= 0")
+                    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or math.isnan(v) or v == math.inf:
+                        raise ValueError(f"SamplingParams: logit_bias[{t}]={v!r} must be a number below +inf (-inf bans the token)")
+                    pairs.append((int(t), float(v)))
+            except TypeError:
+                raise ValueError(f"SamplingParams: logit_bias={lb!r} must map token ids to numbers") from None
+            pairs.sort()
+            if any(p[0] == q[0] for p, q in zip(pairs, pairs[1:])):
+                raise ValueError("SamplingParams: logit_bias names a token id twice")
+            object.__setattr__(self, "logit_bias", tuple(pairs) or None)
+
+    @property
+    def penalized(self) -> bool:
+        """Any of repetition_penalty, presence_penalty, frequency_penalty, logit_bias is active (step 0 of the rule runs)."""
+        return np.float32(self.repetition_penalty) != 1 or np.float32(self.presence_penalty) != 0 or np.float32(self.frequency_penalty) != 0 \
+            or self.logit_bias is not None
 
 
 def check_stream(stream) -> int:
@@ -64,9 +109,40 @@ def pack_rows(params: Sequence[SamplingParams], streams: Sequence[int]) -> np.nd
     return rows
 
 
+def pack_penalty_rows(params: Sequence) -> np.ndarray:
+    """The mq_sample_penalty_row array (host side): SamplingParams or (repetition, presence, frequency) per row."""
+    rows = np.zeros(len(params), dtype=PENALTY_DTYPE)
+    for r, p in enumerate(params):
+        rows[r] = (p.repetition_penalty, p.presence_penalty, p.frequency_penalty, 0) if isinstance(p, SamplingParams) else (*p, 0)
+    return rows
+
+
+def _check_ids(ids, V: int) -> torch.Tensor:
+    t = torch.as_tensor([int(i) for i in ids], dtype=torch.int64)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= V):
+        raise ValueError(f"sampling: a token id outside [0, {V}) in the history")
+    return t
+
+
+def history_prompt(history_row: torch.Tensor, ids, clear: bool = True):
+    """mq_sample_history_prompt on one row's history ([V] int32 device tensor holding the uint32 entries): clear it, then mark the ids
+    as prompt tokens (bit 31).  The ids are checked here, on the host: one outside [0, V) raises ValueError."""
+    V = history_row.numel()
+    if history_row.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not history_row.is_contiguous():
+        raise RuntimeError("mobilequant_amd: a history row must be a contiguous int32 (uint32 bits) tensor")
+    dev = history_row.device
+    t = _check_ids(ids, V).to(dev)
+    with torch.cuda.device(dev):
+        _lib.call("mq_sample_history_prompt", history_row.data_ptr(), V, t.data_ptr() if t.numel() else None, t.numel(), int(bool(clear)),
+                  torch.cuda.current_stream(dev).cuda_stream)
+
+
 class SampleLaunch:
     """mq_sample over an engine's own buffers: logits [rows, V] -> tok [rows] at the positions in pos [rows].  The per-row requests
-    live in a device array that set_rows() rewrites in place, so a captured launch serves any request."""
+    live in a device array that set_rows() rewrites in place, so a captured launch serves any request.
+    The first request with a penalty or a bias allocates the rows' histories [rows, V], penalty rows and dense bias rows; from then on,
+    while any row's request is penalised, launch() is mq_sample_penalized (which also counts every drawn token in its row's history),
+    and while every row is neutral it is mq_sample, as before.  `penalized` says which: a captured graph holds one of the two."""
 
     def __init__(self, logits: torch.Tensor, pos: torch.Tensor, tok: torch.Tensor, cache_len: int):
         lg = logits.view(-1, logits.shape[-1])
@@ -82,6 +158,9 @@ class SampleLaunch:
         a.scratch, a.scratch_bytes = self.scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
         self.args = a
         self._keep = (lg, pos, tok)
+        self.V = V
+        self.penalized = False
+        self.pargs = None                                       # mq_sample_penalized's block and buffers: allocated on first need
         self.set_rows([SamplingParams(temperature=0.0)] * rows, list(range(rows)))
 
     def set_rows(self, params: Sequence[SamplingParams], streams: Sequence[int]):
@@ -89,10 +168,55 @@ class SampleLaunch:
         if len(host) != self.rows:
             raise ValueError(f"sampling: {len(host)} requests for {self.rows} rows")
         self.params.copy_(torch.from_numpy(host.view(np.uint8).reshape(-1)))
+        self.penalized = any(p.penalized for p in params)
+        if self.penalized or self.pargs is not None:
+            self._set_penalty_rows(params)
+
+    def _allocate_penalty(self):
+        rows, V, dev = self.rows, self.V, self.dev
+        self.history = torch.zeros(rows, V, dtype=torch.int32, device=dev)              # uint32 entries
+        self.penalty = torch.zeros(rows * PENALTY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.bias = torch.zeros(rows, V, dtype=torch.float32, device=dev)
+        self.bias_ptr = torch.zeros(rows, dtype=torch.int64, device=dev)                # per row: its bias row, or NULL
+        self._bias_of = [None] * rows
+        p = MqSamplePenalizedArgs()
+        ctypes.memmove(ctypes.byref(p.s), ctypes.byref(self.args), ctypes.sizeof(MqSampleArgs))
+        p.penalty, p.history, p.history_stride = self.penalty.data_ptr(), self.history.data_ptr(), self.history.stride(0)
+        p.bias, p.observe = self.bias_ptr.data_ptr(), 1
+        self.pargs = p
+
+    def _set_penalty_rows(self, params: Sequence[SamplingParams]):
+        if self.pargs is None:
+            self._allocate_penalty()
+        self.penalty.copy_(torch.from_numpy(pack_penalty_rows(params).view(np.uint8).reshape(-1)))
+        ptrs = []
+        for r, p in enumerate(params):
+            lb = p.logit_bias
+            if lb != self._bias_of[r]:
+                self.bias[r].zero_()
+                if lb is not None:
+                    ids = _check_ids([t for t, _ in lb], self.V).to(self.dev)
+                    self.bias[r].index_copy_(0, ids, torch.tensor([v for _, v in lb], dtype=torch.float32, device=self.dev))
+                self._bias_of[r] = lb
+            ptrs.append(self.bias[r].data_ptr() if lb is not None else 0)
+        self.bias_ptr.copy_(torch.tensor(ptrs, dtype=torch.int64))
+
+    def observe_prompt(self, row: int, ids, clear: bool = True):
+        """Mark ids as prompt tokens of the row's sequence (clear: forget the row's history first).  Only a penalised launch reads the
+        histories, so this does nothing until the first penalised request has allocated them."""
+        if self.pargs is not None:
+            history_prompt(self.history[row], ids, clear)
+
+    def clear_history(self, row: int):
+        self.observe_prompt(row, (), clear=True)
 
     def launch(self):
         """On the current stream (capturable: two kernel launches, nothing else)."""
-        _lib.call("mq_sample", ctypes.byref(self.args), torch.cuda.current_stream(self.dev).cuda_stream)
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        if self.penalized:
+            _lib.call("mq_sample_penalized", ctypes.byref(self.pargs), st)
+        else:
+            _lib.call("mq_sample", ctypes.byref(self.args), st)
 
 
 def validate_generate_args(who: str, sampling, do_sample: bool, draft=None):
@@ -103,10 +227,16 @@ def validate_generate_args(who: str, sampling, do_sample: bool, draft=None):
 
 
 def sample(logits: torch.Tensor, pos: torch.Tensor, params_rows, tok: torch.Tensor, *, cache_len: int = 2 ** 31 - 1,
-           kept: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None) -> torch.Tensor:
+           kept: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None, penalties=None,
+           history: Optional[torch.Tensor] = None, bias=None, observe: bool = False) -> torch.Tensor:
     """mq_sample: logits [rows, V] fp32 (row stride >= V), pos [rows] int32, tok [rows] int64 (written in place, returned).
     params_rows: a uint8 device tensor holding the mq_sample_row array, or (list of SamplingParams, list of streams).  A row whose
-    pos is outside [0, cache_len) keeps its token.  kept [rows] int32 / logprob [rows] fp32: optional outputs."""
+    pos is outside [0, cache_len) keeps its token.  kept [rows] int32 / logprob [rows] fp32: optional outputs.
+    With any of penalties / history / bias / observe the call is mq_sample_penalized (step 0 of the rule in front): history [rows, >= V]
+    int32 (the uint32 entries: bit 31 = in the prompt, bits 0..15 = times generated) is required; penalties: a uint8 device tensor
+    holding the mq_sample_penalty_row array, or per row a SamplingParams or (repetition, presence, frequency) (default: the
+    SamplingParams of params_rows, else neutral); bias: None, or per row None or a dense fp32 [V] device tensor; observe: count each
+    drawn token in its row's history.  The logits are not written."""
     from .ops import _dev, _on, _stream
     _dev(logits, "sample logits")
     if logits.dim() == 1:
@@ -138,8 +268,44 @@ def sample(logits: torch.Tensor, pos: torch.Tensor, params_rows, tok: torch.Tens
     a.kept = kept.data_ptr() if kept is not None else None
     a.logprob = logprob.data_ptr() if logprob is not None else None
     a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+    if penalties is None and history is None and bias is None and not observe:
+        with _on(logits, pos, pr, tok):
+            _lib.call("mq_sample", ctypes.byref(a), _stream())
+        return tok
+    if history is None:
+        raise RuntimeError("mobilequant_amd: sample with penalties=, bias= or observe= needs history=")
+    _dev(history, "sample history")
+    if history.dim() == 1:
+        history = history.view(1, -1)
+    if history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 2 or history.shape[0] != rows \
+            or history.shape[1] < V or history.stride(1) != 1:
+        raise RuntimeError(f"mobilequant_amd: sample history must be int32 (uint32 bits) [{rows}, >= {V}] with unit column stride")
+    if penalties is None:
+        penalties = params_rows[0] if not isinstance(params_rows, torch.Tensor) else [(1.0, 0.0, 0.0)] * rows
+    if isinstance(penalties, torch.Tensor):
+        pen = _dev(penalties, "sample penalties")
+        if pen.dtype != torch.uint8 or pen.numel() != rows * PENALTY_DTYPE.itemsize or not pen.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: sample penalties must be {rows * PENALTY_DTYPE.itemsize} contiguous uint8 bytes")
+    else:
+        host = pack_penalty_rows(list(penalties))
+        if len(host) != rows:
+            raise RuntimeError(f"mobilequant_amd: sample got {len(host)} penalty rows for {rows} rows")
+        pen = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(logits.device)
+    bias_ptr = None
+    if bias is not None:
+        brows = list(bias)
+        if len(brows) != rows:
+            raise RuntimeError(f"mobilequant_amd: sample got {len(brows)} bias rows for {rows} rows")
+        for b in brows:
+            if b is not None and (_dev(b, "sample bias").dtype != torch.float32 or b.dim() != 1 or b.numel() < V or not b.is_contiguous()):
+                raise RuntimeError(f"mobilequant_amd: a sample bias row must be a contiguous fp32 [{V}] tensor")
+        bias_ptr = torch.tensor([0 if b is None else b.data_ptr() for b in brows], dtype=torch.int64).to(logits.device)
+    p = MqSamplePenalizedArgs()
+    p.s = a
+    p.penalty, p.history, p.history_stride = pen.data_ptr(), history.data_ptr(), history.stride(0) if rows > 1 else max(V, history.stride(0))
+    p.bias, p.observe = (bias_ptr.data_ptr() if bias_ptr is not None else None), int(bool(observe))
     with _on(logits, pos, pr, tok):
-        _lib.call("mq_sample", ctypes.byref(a), _stream())
+        _lib.call("mq_sample_penalized", ctypes.byref(p), _stream())
     return tok
 
 

@@ -2,6 +2,7 @@
 of generate() with and without it, in one process.
 
     python tools/bench_sample.py [--calls 200] [--vocabs 32000,100352,256000] [--rows 1,8] [--new-tokens 128] [--context 256] [--no-generate]
+                                 [--penalties]
 
 kernel: per (V, rows, mode) HIP events around `calls` back-to-back eager calls, best of 3, microseconds per call.
   mode temp     : mq_sample, temperature 0.7                      vs  multinomial(softmax(logits / T))          (generate(do_sample=True)'s rule)
@@ -11,6 +12,9 @@ generate: the TinyLlama-1.1B shape (random weights, the reference's surgery), W8
   engine captured; wall clock around generate() (it reads one token id per step), best of 3, tokens/s:
   greedy (argmax + .item() + step graph), do_sample (softmax + multinomial + .item() + step graph) -- the two legacy paths, whose code
   this feature does not touch -- and sampling= with top_k 40 / top_p 0.9 (one sample + step graph replay + one token read-back).
+--penalties: per cell also mq_sample_penalized (repetition 1.3, presence 0.2, frequency 0.1 and a logit bias, all active, on a history
+  with 5 % of its entries seen, observe on) as mq_sample_penalized_us and x_plain = penalised / plain; generate also runs the same
+  top_k 40 / top_p 0.9 request with the penalties.
 Prints ONE JSON line."""
 from __future__ import annotations
 
@@ -39,7 +43,10 @@ def _events(fn, calls):
     return best * 1e3                                       # us per call
 
 
-def kernel_table(vocabs, rows_list, calls, dev):
+PENALTIES = dict(repetition_penalty=1.3, presence_penalty=0.2, frequency_penalty=0.1, logit_bias={5: -1.0, 11: float("-inf")})
+
+
+def kernel_table(vocabs, rows_list, calls, dev, penalties=False):
     from mobilequant_amd import SamplingParams
     from mobilequant_amd.sampling import SampleLaunch
     out = {}
@@ -72,12 +79,22 @@ def kernel_table(vocabs, rows_list, calls, dev):
                     ref()
                 torch.cuda.synchronize()
                 k_us, t_us = _events(sl.launch, calls), _events(ref, calls)
-                out[f"V{V}_rows{rows}_{mode}"] = {"mq_sample_us": round(k_us, 2), "torch_us": round(t_us, 2), "x_torch": round(k_us / t_us, 3),
-                                                  "miss": bool(k_us >= t_us)}
+                cell = out[f"V{V}_rows{rows}_{mode}"] = {"mq_sample_us": round(k_us, 2), "torch_us": round(t_us, 2), "x_torch": round(k_us / t_us, 3),
+                                                         "miss": bool(k_us >= t_us)}
+                if penalties:
+                    import dataclasses
+                    sl.set_rows([dataclasses.replace(sp, **PENALTIES)] * rows, list(range(rows)))
+                    seen = torch.rand(rows, V, generator=g, device=dev) < 0.05          # 5 % of the entries seen: prompt bit or a count
+                    sl.history.copy_(torch.where(seen, torch.randint(1, 6, (rows, V), generator=g, device=dev, dtype=torch.int32), 0))
+                    for _ in range(5):
+                        sl.launch()
+                    torch.cuda.synchronize()
+                    p_us = _events(sl.launch, calls)
+                    cell["mq_sample_penalized_us"], cell["x_plain"] = round(p_us, 2), round(p_us / k_us, 3)
     return out
 
 
-def generate_table(context, new_tokens, dev):
+def generate_table(context, new_tokens, dev, penalties=False):
     from bench_decode_batch import _model
     from mobilequant_amd import SamplingParams
     from mobilequant_amd.decode import DecodeEngine
@@ -91,6 +108,9 @@ def generate_table(context, new_tokens, dev):
              "do_sample": lambda: eng.generate(prompt, new_tokens, do_sample=True, temperature=0.7, generator=torch.Generator(device=dev).manual_seed(3)),
              "sampling_topk40_topp0.9": lambda: eng.generate(prompt, new_tokens, sampling=sp, stream=0),
              "sampling_temperature_only": lambda: eng.generate(prompt, new_tokens, sampling=SamplingParams(temperature=0.7, seed=3), stream=0)}
+    if penalties:
+        spp = SamplingParams(temperature=0.7, top_k=40, top_p=0.9, seed=3, **PENALTIES)
+        paths["sampling_topk40_topp0.9_penalized"] = lambda: eng.generate(prompt, new_tokens, sampling=spp, stream=0)
     # the prefill forward is the same in every path: time it once and take it off
     def prefill_only():
         eng.reset()
@@ -128,13 +148,14 @@ def main():
     ap.add_argument("--context", type=int, default=256)
     ap.add_argument("--new-tokens", type=int, default=128)
     ap.add_argument("--no-generate", action="store_true")
+    ap.add_argument("--penalties", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sample.py needs an MI355X: there is no CPU path")
     dev = torch.device("cuda:0")
-    res = {"kernel": kernel_table([int(v) for v in a.vocabs.split(",")], [int(v) for v in a.rows.split(",")], a.calls, dev)}
+    res = {"kernel": kernel_table([int(v) for v in a.vocabs.split(",")], [int(v) for v in a.rows.split(",")], a.calls, dev, a.penalties)}
     if not a.no_generate:
-        res["generate"] = generate_table(a.context, a.new_tokens, dev)
+        res["generate"] = generate_table(a.context, a.new_tokens, dev, a.penalties)
     print(json.dumps(res))
 
 
