@@ -119,22 +119,8 @@ __device__ __forceinline__ void tie16(float (&x)[16]) {   // an ordering point f
                "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]));
 }
 
-struct AGrid {
-  float s, o, qmin, qmax, inv_s;
-  bool on;
-};
-__device__ __forceinline__ AGrid a_load_grid(const mq_grid& g) {
-  AGrid r;
-  r.on = g.scale != nullptr;
-  r.s = r.on ? g.scale[0] : 1.f;
-  r.o = r.on ? g.offset[0] : 0.f;
-  r.qmin = g.qmin;
-  r.qmax = g.qmax;
-  r.inv_s = __fdiv_rn(1.0f, r.s);
-  return r;
-}
 // reciprocal-multiply form, used inside the attention kernel
-__device__ __forceinline__ float a_index_fast(float x, const AGrid& g) {
+__device__ __forceinline__ float a_index_fast(float x, const Grid& g) {
   return fminf(fmaxf(rintf(x * g.inv_s) + g.o, g.qmin), g.qmax);
 }
 
@@ -199,14 +185,14 @@ __global__ void __launch_bounds__(256) attention_prep_kernel(const mq_attention_
   };
   // index input: the uint8 output indices of the fused q|k|v GEMM, dequantised as that linear's fp32 output would read
   const uint8_t* isrc = idx_in ? idx_in + ((size_t)s * (H + 2 * KV) + part) * D : nullptr;
-  const AGrid gin = a_load_grid(is_q ? a.q_in : (is_k ? a.k_in : a.v_in));
+  const Grid gin = load_grid(is_q ? a.q_in : (is_k ? a.k_in : a.v_in));
   auto load16_idx = [&](const uint8_t* p, float (&d)[16]) {
     const uint4 t = *reinterpret_cast<const uint4*>(p);
     const unsigned w4[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
     for (int i = 0; i < 16; ++i) d[i] = __fmul_rn(__fsub_rn((float)((w4[i >> 2] >> (8 * (i & 3))) & 0xffu), gin.o), gin.s);
   };
-  const AGrid g = a_load_grid(is_q ? a.qk_a : (is_k ? a.qk_b : a.pv_b));
+  const Grid g = load_grid(is_q ? a.qk_a : (is_k ? a.qk_b : a.pv_b));
   const int rot = a.rot_dim > 0 ? a.rot_dim : D;
   uint32_t usum = 0;                                 // sum of the stored bytes + 128 each (image_pack4, mq_common.h)
 #pragma unroll 1
@@ -252,7 +238,7 @@ __global__ void __launch_bounds__(256) attention_prep_kernel(const mq_attention_
   unsigned w[4];
   float qi[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) qi[i] = image_idxf(y16[i], g.s, g.inv_s, g.o, g.qmin, g.qmax);
+  for (int i = 0; i < 16; ++i) qi[i] = index_image_nan2qmin(y16[i], g.s, g.inv_s, g.o, g.qmin, g.qmax);
 #pragma unroll
   for (int d4 = 0; d4 < 4; ++d4) w[d4] = image_pack4(qi[4 * d4], qi[4 * d4 + 1], qi[4 * d4 + 2], qi[4 * d4 + 3], usum);
   if constexpr (D == 64) {
@@ -294,7 +280,7 @@ __global__ void __launch_bounds__(256) attention_prep_kernel(const mq_attention_
       sum += __shfl_xor(sum, 1, 64);
       sum += __shfl_xor(sum, 2, 64);
       // the zero-point terms of sum_d (qi - zq)(ki - zk) = sum qs ks - zq' rowsum(ks) - zk' rowsum(qs) + D zq' zk'  (primes: - 128)
-      const int zq = (int)a_load_grid(a.qk_a).o - 128, zk = (int)a_load_grid(a.qk_b).o - 128;
+      const int zq = (int)load_grid(a.qk_a).o - 128, zk = (int)load_grid(a.qk_b).o - 128;
       if (c == 0) {
         if (is_q) q_rs[(size_t)head * S + s] = D * zq * zk - zk * sum;
         else k_rs[(size_t)head * CS + P0 + s] = -zq * sum;
@@ -428,8 +414,8 @@ __global__ void __launch_bounds__(PAIR ? 512 : 256) __attribute__((amdgpu_waves_
   const int qb = S / 64 - 1 - (int)blockIdx.x / (PAIR ? H / 2 : H);
   const int srow = lane & 15, tq = lane >> 4;
   const int s_abs = qb * 64 + wave * 16 + srow;                     // this lane's query row
-  const AGrid gqa = a_load_grid(a.qk_a), gqb = a_load_grid(a.qk_b), gqo = a_load_grid(a.qk_out);
-  const AGrid gpa = a_load_grid(a.pv_a), gpb = a_load_grid(a.pv_b), gpo = a_load_grid(a.pv_out);
+  const Grid gqa = load_grid(a.qk_a), gqb = load_grid(a.qk_b), gqo = load_grid(a.qk_out);
+  const Grid gpa = load_grid(a.pv_a), gpb = load_grid(a.pv_b), gpo = load_grid(a.pv_out);
   const int zv = (int)gpb.o - 128, zp = (int)gpa.o;
   const float alpha_qk = __fmul_rn(gqa.s, gqb.s);
   // scores: QK_OUT: f = magic + index on the 16-bit grid; value = (index - o) * s / 8.   else: f = ti * alpha / 8 (the value itself)
@@ -506,7 +492,7 @@ __global__ void __launch_bounds__(PAIR ? 512 : 256) __attribute__((amdgpu_waves_
       }
     }
     if (a.qkv_idx) {                                                // ... dequantised as that linear's fp32 output would read
-      const AGrid gin = a_load_grid(a.q_in);
+      const Grid gin = load_grid(a.q_in);
       const unsigned w0[4] = {t0.x, t0.y, t0.z, t0.w}, w1[4] = {t1.x, t1.y, t1.z, t1.w};
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -534,7 +520,7 @@ __global__ void __launch_bounds__(PAIR ? 512 : 256) __attribute__((amdgpu_waves_
     for (int d4 = 0; d4 < 4; ++d4) {
       float qi[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) qi[e] = image_idxf(ya[4 * d4 + e], gqa.s, gqa.inv_s, gqa.o, gqa.qmin, gqa.qmax);
+      for (int e = 0; e < 4; ++e) qi[e] = index_image_nan2qmin(ya[4 * d4 + e], gqa.s, gqa.inv_s, gqa.o, gqa.qmin, gqa.qmax);
       if constexpr (F16) {
         hw[2 * d4] = pack_h2(__fsub_rn(qi[0], gqa.o), __fsub_rn(qi[1], gqa.o));
         hw[2 * d4 + 1] = pack_h2(__fsub_rn(qi[2], gqa.o), __fsub_rn(qi[3], gqa.o));

@@ -1,6 +1,7 @@
 // Shared helpers for the libmobilequant_amd translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
 #include <atomic>
 #include <stdarg.h>
 #include <stdint.h>
@@ -10,7 +11,7 @@
 
 namespace mq {
 
-// Thread-local error text behind mq_last_error(); defined in mq_elementwise.hip.
+// Thread-local error text behind mq_last_error(); defined in mq_quantize.hip.
 void set_error(const char* fmt, ...);
 
 inline hipStream_t as_stream(mq_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
@@ -77,43 +78,13 @@ __device__ __forceinline__ float div_by_scale_guarded(float x, float s, float in
   return fast ? div_by_scale(x, s, inv_s) : __fdiv_rn(x, s);
 }
 
-// Four activations -> the dword of their int8 image bytes (index - shift), for the image-only kernels.  index = clamp(rint(x / s) + o):
-// (rint(t) - t) + t, the reference's round_ste, IS rint(t) in fp32 for every t (|t| >= 0.5: rint(t) and t are within a factor of two,
-// the difference is exact and adding t back lands on the representable rint(t); |t| < 0.5: (0 - t) + t = 0; x = +-inf / NaN: t is
-// already NaN, div_by_scale).  The clamp is one v_med3_f32, which returns min3 when an operand is a (quiet) NaN: NaN -> qmin, the
-// integer image's convention.  u = index + (128 - shift) lies in [0, 255] (the host checks that index - shift fits int8), so
-// v_cvt_pk_u8_f32 converts AND packs in one instruction; the int8 bytes are u ^ 0x80 and sum(index - shift) = sum(u) - 128 n with
-// sum(u) from one v_sad_u8 per dword (`usum` accumulates it).  ~8.5 VALU instructions per element instead of ~16.
-__device__ __forceinline__ float image_idxf(float x, float s, float inv_s, float o, float qmin, float qmax) {
-  const float t = div_by_scale(x, s, inv_s);
-  return __builtin_amdgcn_fmed3f(__fadd_rn(rintf(t), o), qmin, qmax);
-}
-__device__ __forceinline__ float image_u8f(float x, float s, float inv_s, float o, float qmin, float qmax, float bias) {
-  return __fadd_rn(image_idxf(x, s, inv_s, o, qmin, qmax), bias);
-}
 // Two elements per instruction: v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32 are IEEE fp32 operations on register pairs (full rate on
-// CDNA3 / 4), so the packed forms below return the bits of the scalar ones; rint, med3 and the u8 conversion have no packed form.
+// CDNA3 / 4), so the packed forms return the bits of the scalar ones; rint, med3 and the u8 conversion have no packed form.
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f splat2(float v) { return (v2f)(v); }
 __device__ __forceinline__ v2f div_by_scale2(v2f x, float s, float inv_s) {
   const v2f q0 = x * splat2(inv_s);
   return __builtin_elementwise_fma(__builtin_elementwise_fma(-q0, splat2(s), x), splat2(inv_s), q0);
-}
-__device__ __forceinline__ v2f image_u8f2(v2f x, float s, float inv_s, float o, float qmin, float qmax, float bias) {
-  const v2f t = div_by_scale2(x, s, inv_s);
-  v2f r = {rintf(t.x), rintf(t.y)};
-  r = r + splat2(o);
-  r.x = __builtin_amdgcn_fmed3f(r.x, qmin, qmax);
-  r.y = __builtin_amdgcn_fmed3f(r.y, qmin, qmax);
-  return r + splat2(bias);
-}
-__device__ __forceinline__ uint32_t image_pack4(float u0, float u1, float u2, float u3, uint32_t& usum) {
-  uint32_t pk = __builtin_amdgcn_cvt_pk_u8_f32(u0, 0u, 0u);
-  pk = __builtin_amdgcn_cvt_pk_u8_f32(u1, 1u, pk);
-  pk = __builtin_amdgcn_cvt_pk_u8_f32(u2, 2u, pk);
-  pk = __builtin_amdgcn_cvt_pk_u8_f32(u3, 3u, pk);
-  usum = __builtin_amdgcn_sad_u8(pk, 0u, usum);
-  return pk ^ 0x80808080u;
 }
 
 // 64-lane wave reductions on DPP moves (wave = 64 on gfx950): quad permutes, row_half_mirror, row_mirror leave every lane of a
@@ -140,7 +111,10 @@ __device__ __forceinline__ float wave_min(float v) {
 __device__ __forceinline__ float wave_max(float v) {
   return wave_reduce_f(v, [](float a, float b) { return fmaxf(a, b); });
 }
-__device__ __forceinline__ float wave_sum_f32_dpp(float v) {
+// The two float wave sums run the same four steps inside a 16-lane row and differ in how the four row totals r0 .. r3 meet.  They are
+// kept apart so that no kernel's instruction stream or summation order changes by accident.
+// rows met through v_readlane: (r0 + r1) + (r2 + r3).  The prefill kernels (norms, fake-quant backward, training softmax, reductions).
+__device__ __forceinline__ float wave_sum_f_readlane(float v) {
   return wave_reduce_f(v, [](float a, float b) { return a + b; });
 }
 __device__ __forceinline__ int wave_sum(int v) {
@@ -149,6 +123,50 @@ __device__ __forceinline__ int wave_sum(int v) {
   v += dpp_mov_i<0x141>(v);
   v += dpp_mov_i<0x140>(v);
   return (__builtin_amdgcn_readlane(v, 15) + __builtin_amdgcn_readlane(v, 31)) + (__builtin_amdgcn_readlane(v, 47) + __builtin_amdgcn_readlane(v, 63));
+}
+// The decode kernels' forms (six DPP adds, the result read from lane 63): rows met through row broadcasts.
+template <int CTRL, int ROW_MASK, bool BOUND>
+__device__ __forceinline__ float dpp_f(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
+}
+__device__ __forceinline__ int wave_sum_dpp(int v) {               // all lanes active
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
+  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);   // row_half_mirror
+  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);   // row_mirror: every lane = its row-of-16 total
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+  return __builtin_amdgcn_readlane(v, 63);
+}
+// rows met through row broadcasts: (r3 + r2) + (r1 + r0), the value of lane 63
+__device__ __forceinline__ float wave_sum_f_rowbcast(float v) {
+  v += dpp_f<0xB1, 0xf, true>(v);
+  v += dpp_f<0x4E, 0xf, true>(v);
+  v += dpp_f<0x141, 0xf, true>(v);
+  v += dpp_f<0x140, 0xf, true>(v);
+  v += dpp_f<0x142, 0xa, false>(v);                                 // row_bcast15 into rows 1 and 3 (0 elsewhere: x + 0 = x)
+  v += dpp_f<0x143, 0xc, false>(v);                                 // row_bcast31 into rows 2 and 3
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+__device__ __forceinline__ float wave_max_f(float v) {              // inputs are finite or -inf, never NaN
+  v = fmaxf(v, dpp_f<0xB1, 0xf, true>(v));
+  v = fmaxf(v, dpp_f<0x4E, 0xf, true>(v));
+  v = fmaxf(v, dpp_f<0x141, 0xf, true>(v));
+  v = fmaxf(v, dpp_f<0x140, 0xf, true>(v));
+  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 15));
+  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 31));
+  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 47));
+  const float r4 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+  return fmaxf(fmaxf(r1, r2), fmaxf(r3, r4));
+}
+
+// Sum of the four waves' (wave-uniform) values of a 256-thread group, for every thread: wave `wave` leaves v in slots[wave], one
+// barrier, (0 + 1) + (2 + 3).  Float or int.  The slots may be rewritten after the next barrier.
+template <typename T>
+__device__ __forceinline__ T block_sum4(T v, T* slots, int wave) {
+  if ((threadIdx.x & 63) == 0) slots[wave] = v;
+  __syncthreads();
+  return (slots[0] + slots[1]) + (slots[2] + slots[3]);
 }
 
 // Exact float atomic min/max on the IEEE bit pattern (no CAS loop): non-negative floats order as
@@ -162,4 +180,61 @@ __device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
   else atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
+// Byte offset of element (row, k) in the fragment-blocked ("tiled") int8 image of a [rows, cols] activation -- the layout
+// include/mobilequant_amd.h describes at mq_quantize_tiled: 1-KiB blocks of 16 rows x 64 k ordered [row block][k block]; inside a block
+// lane (row & 15) + 16 * ((k >> 4) & 3) owns the 16 bytes k & 15.
+__device__ __forceinline__ int64_t tiled_block_base(int64_t row_block, int64_t k_block, int64_t cols) { return (row_block * (cols >> 6) + k_block) << 10; }
+__device__ __forceinline__ int64_t tiled_image_offset(int64_t row, int64_t k, int64_t cols) {
+  return tiled_block_base(row >> 4, k >> 6, cols) + ((((int)row & 15) + 16 * (((int)k >> 4) & 3)) << 4) + ((int)k & 15);
+}
+// Copy-out of the staged tiled kernels (norm_tiled8_kernel, quantize_tiled8_kernel): the LDS tile holds RW rows (row0 .. row0 + RW - 1,
+// inside one row block) as 16-byte units p = RW * piece + r, piece = k >> 4; unit p goes to block (row0 >> 4, piece >> 2), byte
+// 256 (piece & 3) + 16 ((row0 & 15) + r) -- RW x 16 B contiguous per piece: whole cache lines of a fragment block.  PAD: the rows
+// past `rows` (padding of the image's last row block) are written like the others; otherwise they stay untouched.
+template <int RW, int THREADS, bool PAD>
+__device__ __forceinline__ void staged_copy_out(const int8_t* stage, int8_t* q_tiled, int64_t row0, int64_t rows, int64_t cols) {
+  const int units = (int)(cols >> 4) * RW;
+  const int64_t rb = row0 >> 4;
+  const int half = (int)(row0 & 15);
+  for (int p = threadIdx.x; p < units; p += THREADS) {
+    const int piece = p / RW, r = p % RW;
+    if (PAD || row0 + r < rows)
+      *reinterpret_cast<uint4*>(q_tiled + tiled_block_base(rb, piece >> 2, cols) + ((piece & 3) << 8) + ((half + r) << 4)) =
+          *reinterpret_cast<const uint4*>(stage + (p << 4));
+  }
+}
+
+// ---- 16 bytes of fp32 / fp16 elements per lane (the element-wise kernels of mq_fake_quant.hip and mq_quantize.hip) ---------------
+template <typename T>
+struct Vec16;
+template <>
+struct Vec16<float> {
+  static constexpr int N = 4;
+  float v[4];
+  __device__ static float get(const Vec16& a, int i) { return a.v[i]; }
+  __device__ static void set(Vec16& a, int i, float f) { a.v[i] = f; }
+};
+template <>
+struct Vec16<__half> {
+  static constexpr int N = 8;
+  __half v[8];
+  __device__ static float get(const Vec16& a, int i) { return __half2float(a.v[i]); }
+  __device__ static void set(Vec16& a, int i, float f) { a.v[i] = __float2half_rn(f); }
+};
+
+template <typename T>
+__device__ __forceinline__ float ld(const T* p, int64_t i);
+template <>
+__device__ __forceinline__ float ld<float>(const float* p, int64_t i) { return p[i]; }
+template <>
+__device__ __forceinline__ float ld<__half>(const __half* p, int64_t i) { return __half2float(p[i]); }
+template <typename T>
+__device__ __forceinline__ void st(T* p, int64_t i, float v);
+template <>
+__device__ __forceinline__ void st<float>(float* p, int64_t i, float v) { p[i] = v; }
+template <>
+__device__ __forceinline__ void st<__half>(__half* p, int64_t i, float v) { p[i] = __float2half_rn(v); }
+
 }  // namespace mq
+
+#include "mq_quant.h"

@@ -13,7 +13,7 @@
 // and mq_decode_head: final HFRMSNorm (floating point, not quantised: qmodule.py:843) fused in front of the fp32 lm_head stream.
 // Every weight byte is read once per token; the activations (<= 22 KiB) live in LDS per CU.  The GEMV body is the fat-workgroup
 // kernel of mq_gemv.hip (one 1024-thread workgroup per CU, all weight loads of a wave issued before anything else, DPP reductions);
-// the arithmetic of every quantizer is op for op that of the prefill kernels (mq_norm.hip, mq_elementwise.hip, mq_gemm.hip).
+// the arithmetic of every quantizer is op for op that of the prefill kernels (mq_norm.hip, mq_activation.hip, mq_quantize.hip, mq_gemm.hip; the forms: mq_quant.h).
 // The token position is read from device memory, so one captured hipGraph serves every step of a generation.
 #include "mq_decode_attention.h"
 
@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
             if (p + u * DG_PRO * 64 < nvec) s1 += (v.x + v.y) + (v.z + v.w);
           }
         }
-        s1 = wave_sum_f(s1);
+        s1 = wave_sum_f_rowbcast(s1);
         if (lane == 0) s_red[wave] = s1;
         __syncthreads();                                           // barrier 1 of 3
         float tot = 0.f;
@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
             s2 += d3 * d3;
           }
         }
-        s2 = wave_sum_f(s2);
+        s2 = wave_sum_f_rowbcast(s2);
         if (lane == 0) s_red2[wave] = s2;
         __syncthreads();                                           // barrier 2 of 3
         float tot2 = 0.f;
@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
           }
         }
         DG_STAMP_ARRIVED(8, 0, ss);
-        ss = wave_sum_f(ss);
+        ss = wave_sum_f_rowbcast(ss);
         if (lane == 0) s_red[wave] = ss;
         DG_STAMP_ARRIVED(9, 0, ss);
         __syncthreads();                                           // barrier 1 of 2 (the stream waves pass it right after their requests)
@@ -409,7 +409,7 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
         rr = __fmul_rn(__fmul_rn(0.5f, fa), __fadd_rn(1.0f, erff(__fmul_rn(fa, 0.70710678118654752440f))));
       }
       const float prod = __fmul_rn(gact.fq(rr), fb);
-      const float qi = dq_index(prod, gout.s, gout.inv_s, gout.o, gout.qmin, gout.qmax);
+      const float qi = index_decode_keepnan(prod, gout.s, gout.inv_s, gout.o, gout.qmin, gout.qmax);
       g.gate_q[row] = (int8_t)((qi != qi ? (int)gout.qmin : (int)qi) - 128);
       if (g.y) g.y[row] = prod;
     } else {
@@ -718,8 +718,8 @@ __global__ void __launch_bounds__(NT_) decode_attention_oproj_kernel(const mq_de
       qv = __fadd_rn(__fmul_rn(q_raw, cs), __fmul_rn(sg * q_par, sn));
       kv = __fadd_rn(__fmul_rn(k_raw, cs), __fmul_rn(sg * k_par, sn));
     }
-    const float iq = dq_index(qv, qa.s, qa.inv_s, qa.o, qa.qmin, qa.qmax), ik = dq_index(kv, qb.s, qb.inv_s, qb.o, qb.qmin, qb.qmax);
-    const float iv = dq_index(v_raw, pb.s, pb.inv_s, pb.o, pb.qmin, pb.qmax);
+    const float iq = index_decode_keepnan(qv, qa.s, qa.inv_s, qa.o, qa.qmin, qa.qmax), ik = index_decode_keepnan(kv, qb.s, qb.inv_s, qb.o, qb.qmin, qb.qmax);
+    const float iv = index_decode_keepnan(v_raw, pb.s, pb.inv_s, pb.o, pb.qmin, pb.qmax);
     const int sq = (iq != iq ? 0 : (int)iq) - 128, sk = (ik != ik ? 0 : (int)ik) - 128, sv = (iv != iv ? 0 : (int)iv) - 128;
     s_q8[tid] = (int8_t)sq;
     s_k8[tid] = (int8_t)sk;
@@ -855,7 +855,7 @@ __global__ void __launch_bounds__(NT_) decode_attention_oproj_kernel(const mq_de
       s_sc[t] = e;
       lsum += e;
     }
-    lsum = wave_sum_f(lsum);
+    lsum = wave_sum_f_rowbcast(lsum);
     if (lane == 0) s_redf[wv] = lsum;
   } else {
     for (int t = tid; t < T; t += NT) s_sc[t] = expf(s_sc[t] - mx);
@@ -863,7 +863,7 @@ __global__ void __launch_bounds__(NT_) decode_attention_oproj_kernel(const mq_de
     if (wv < 4) {
       float lsum = 0.f;
       for (int t = tid; t < T; t += 256) lsum += s_sc[t];
-      lsum = wave_sum_f(lsum);
+      lsum = wave_sum_f_rowbcast(lsum);
       if (lane == 0) s_redf[wv] = lsum;
     }
   }
@@ -881,7 +881,7 @@ __global__ void __launch_bounds__(NT_) decode_attention_oproj_kernel(const mq_de
     int bh = 0, bl = 0, bm = 0;
     if (t < T) {
       const float p = __fdiv_rn(s_sc[t], tot_e);
-      const float ipf = dq_index(p, pa.s, pa.inv_s, pa.o, pa.qmin, pa.qmax);
+      const float ipf = index_decode_keepnan(p, pa.s, pa.inv_s, pa.o, pa.qmin, pa.qmax);
       const int ip = ipf != ipf ? 0 : (int)ipf;
       my_p += ip - zp;
       if (t == pos) s_pnew = ip - zp;
@@ -939,7 +939,7 @@ __global__ void __launch_bounds__(NT_) decode_attention_oproj_kernel(const mq_de
     tot -= (long long)zv * psum;
     const float pre = (float)((double)tot * (double)alpha_pv);     // one rounding of the exact sum (as mq_attention.hip)
     const float y = po.fq(pre);
-    const float qi = dq_index(y, oi.s, oi.inv_s, oi.o, oi.qmin, oi.qmax);
+    const float qi = index_decode_keepnan(y, oi.s, oi.inv_s, oi.o, oi.qmin, oi.qmax);
     a_byte = (qi != qi ? (int)oi.qmin : (int)qi) - 128;
     s_a8[tid] = (int8_t)a_byte;
     if (a.out_q && c == 0 && live) a.out_q[(size_t)h * D + tid] = (int8_t)a_byte;
@@ -1005,7 +1005,7 @@ __global__ void __launch_bounds__(256) decode_head_kernel(const float* __restric
   if (layernorm) {                                                 // final nn.LayerNorm (StableLM-2: hf_model.py:1440-1441), fp32, torch's expression
     float s1 = 0.f;
     for (int i = tid; i < K; i += 256) s1 += x[i];
-    s1 = wave_sum_f(s1);
+    s1 = wave_sum_f_rowbcast(s1);
     if (lane == 0) s_red[wv] = s1;
     __syncthreads();
     const float mu = __fdiv_rn((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]), (float)K);
@@ -1015,7 +1015,7 @@ __global__ void __launch_bounds__(256) decode_head_kernel(const float* __restric
       const float d = x[i] - mu;
       s2 += d * d;
     }
-    s2 = wave_sum_f(s2);
+    s2 = wave_sum_f_rowbcast(s2);
     if (lane == 0) s_red[wv] = s2;
     __syncthreads();
     const float var = __fdiv_rn((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]), (float)K);
@@ -1029,7 +1029,7 @@ __global__ void __launch_bounds__(256) decode_head_kernel(const float* __restric
   } else {
     float ss = 0.f;
     for (int i = tid; i < K; i += 256) ss += x[i] * x[i];
-    ss = wave_sum_f(ss);
+    ss = wave_sum_f_rowbcast(ss);
     if (lane == 0) s_red[wv] = ss;
     __syncthreads();
     const float mean = __fdiv_rn((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]), (float)K);
@@ -1066,7 +1066,7 @@ __global__ void __launch_bounds__(256) decode_head_kernel(const float* __restric
           acc += buf[j][3] * b.w;
         }
       }
-      acc = wave_sum_f(acc);
+      acc = wave_sum_f_rowbcast(acc);
       if (lane == 0 && r < V) logits[r] = bias ? acc + bias[r] : acc;
     };
     fetch(cur, row);
@@ -1088,7 +1088,7 @@ __global__ void __launch_bounds__(256) decode_head_kernel(const float* __restric
         acc += a[2] * b.z;
         acc += a[3] * b.w;
       }
-      acc = wave_sum_f(acc);
+      acc = wave_sum_f_rowbcast(acc);
       if (lane == 0) logits[row] = bias ? acc + bias[row] : acc;
     }
   }

@@ -34,7 +34,7 @@ __device__ __forceinline__ int8_t attn_new_elem(float raw, float par, float cs, 
     const float sg = d < (rot >> 1) ? -1.f : 1.f;                  // (-x) * sin == -(x * sin) exactly
     x = __fadd_rn(__fmul_rn(raw, cs), __fmul_rn(sg * par, sn));
   }
-  const float i = dq_index(x, g.s, g.inv_s, g.o, g.qmin, g.qmax);
+  const float i = index_decode_keepnan(x, g.s, g.inv_s, g.o, g.qmin, g.qmax);
   return (int8_t)((i != i ? 0 : (int)i) - 128);
 }
 // The score of one position from its exact integer dot (q index . k index) and key byte sum: qk_bmm's output grid, then / sqrt(D)
@@ -116,8 +116,8 @@ __device__ __forceinline__ float attn_score(int dot, int ks, int zq, int qconst,
       qv = __fadd_rn(__fmul_rn(q_raw, cs), __fmul_rn(sg * q_par, sn));                                                                    \
       kv = __fadd_rn(__fmul_rn(k_raw, cs), __fmul_rn(sg * k_par, sn));                                                                    \
     }                                                                                                                                     \
-    const float iq = dq_index(qv, qa.s, qa.inv_s, qa.o, qa.qmin, qa.qmax), ik = dq_index(kv, qb.s, qb.inv_s, qb.o, qb.qmin, qb.qmax);     \
-    const float iv = dq_index(v_raw, pb.s, pb.inv_s, pb.o, pb.qmin, pb.qmax);                                                             \
+    const float iq = index_decode_keepnan(qv, qa.s, qa.inv_s, qa.o, qa.qmin, qa.qmax), ik = index_decode_keepnan(kv, qb.s, qb.inv_s, qb.o, qb.qmin, qb.qmax);     \
+    const float iv = index_decode_keepnan(v_raw, pb.s, pb.inv_s, pb.o, pb.qmin, pb.qmax);                                                             \
     const int sq = (iq != iq ? 0 : (int)iq) - 128, sk = (ik != ik ? 0 : (int)ik) - 128, sv = (iv != iv ? 0 : (int)iv) - 128;              \
     s_q8[tid] = (int8_t)sq;                                                                                                               \
     s_k8[tid] = (int8_t)sk;                                                                                                               \
@@ -186,7 +186,7 @@ __device__ __forceinline__ float attn_score(int dot, int ks, int zq, int qconst,
     s_sc[t] = e;                                                                                   \
     lsum += e;                                                                                     \
   }                                                                                                \
-  lsum = wave_sum_f(lsum);                                                                         \
+  lsum = wave_sum_f_rowbcast(lsum);                                                                         \
   if (lane == 0) s_redf[wv] = lsum;                                                                \
   __syncthreads();                                                                                 \
   const float tot_e = (s_redf[0] + s_redf[1]) + (s_redf[2] + s_redf[3]);                           \
@@ -194,7 +194,7 @@ __device__ __forceinline__ float attn_score(int dot, int ks, int zq, int qconst,
   for (int t = tid; t < T; t += 256) {                                                             \
     if (nsplit == 1 || ((t >> 6) % nsplit) == c) {                                                 \
       const float pr = __fdiv_rn(s_sc[t], tot_e);                                                  \
-      const float ip = dq_index(pr, pa.s, pa.inv_s, pa.o, pa.qmin, pa.qmax);                       \
+      const float ip = index_decode_keepnan(pr, pa.s, pa.inv_s, pa.o, pa.qmin, pa.qmax);                       \
       s_pi[t] = (ip != ip ? 0 : (int)ip) - zp;                                                     \
     }                                                                                              \
   }                                                                                                \
@@ -276,7 +276,7 @@ __device__ __forceinline__ float attn_score(int dot, int ks, int zq, int qconst,
     const float y = po.fq(pre);                                                                                                            \
     if (a.out) a.out[OUT] = y;                                                                                                               \
     if (a.out_q) {                                                                                                                         \
-      const float qi = dq_index(y, oi.s, oi.inv_s, oi.o, oi.qmin, oi.qmax);                                                                \
+      const float qi = index_decode_keepnan(y, oi.s, oi.inv_s, oi.o, oi.qmin, oi.qmax);                                                                \
       a.out_q[OUT] = (int8_t)((qi != qi ? (int)oi.qmin : (int)qi) - 128);                                                                    \
     }                                                                                                                                      \
   }

@@ -20,7 +20,7 @@ constexpr int DB_MAX_IMAGE = 128 * 1024;
 // ---- weight stream x B activation rows ---------------------------------------------------------------------------------------------
 // Roles, barriers, geometry and epilogue as decode_gemv_kernel (mq_decode.hip): PROLOGUE waves 0 .. DG_PRO-1 build the images, STREAM
 // waves request weights and epilogue parameters first.  Per row b the prologue is thread p's walk over float4 p + 512 u, the per-thread
-// partial in that order, wave_sum_f, then the DG_PRO wave partials added in wave order -- the rows' chains interleave, the barriers are
+// partial in that order, wave_sum_f_rowbcast, then the DG_PRO wave partials added in wave order -- the rows' chains interleave, the barriers are
 // shared.  Beyond DB_XH float4 per row the prologue re-reads x (and the norm weights) instead of holding them: the same values, so the
 // same bits.
 template <int XMODE, bool GATE, bool W4>
@@ -232,9 +232,9 @@ __global__ void __launch_bounds__(256) decode_attention_batch_kernel(const mq_de
 }
 
 // ---- final norm for B rows + the fp32 lm_head streamed once -----------------------------------------------------------------------
-// decode_head_kernel's arithmetic per row: the norm's reductions over 256 threads (i = tid, tid + 256, ...), wave_sum_f, the four wave
+// decode_head_kernel's arithmetic per row: the norm's reductions over 256 threads (i = tid, tid + 256, ...), wave_sum_f_rowbcast, the four wave
 // partials as (w0 + w1) + (w2 + w3); a vocabulary row per wave, lane l summing float4 chunks l, l + 64, ... ascending with four adds
-// each, then wave_sum_f.  Each lane holds B accumulators against one weight request.
+// each, then wave_sum_f_rowbcast.  Each lane holds B accumulators against one weight request.
 __global__ void __launch_bounds__(256) decode_head_batch_kernel(const mq_decode_head_batch_args hb) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* s_x = reinterpret_cast<float*>(smem_raw);               // [B][K] normalised rows
@@ -263,7 +263,7 @@ __global__ void __launch_bounds__(256) decode_head_batch_kernel(const mq_decode_
 #pragma unroll
     for (int b = 0; b < DB_MAXB; ++b) {
       if (act[b]) {
-        const float t = wave_sum_f(s1[b]);
+        const float t = wave_sum_f_rowbcast(s1[b]);
         if (lane == 0) s_red[b][wv] = t;
       }
     }
@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(256) decode_head_batch_kernel(const mq_decode_
 #pragma unroll
     for (int b = 0; b < DB_MAXB; ++b) {
       if (act[b]) {
-        const float t = wave_sum_f(s2[b]);
+        const float t = wave_sum_f_rowbcast(s2[b]);
         if (lane == 0) s_red2[b][wv] = t;
       }
     }
@@ -320,7 +320,7 @@ __global__ void __launch_bounds__(256) decode_head_batch_kernel(const mq_decode_
 #pragma unroll
     for (int b = 0; b < DB_MAXB; ++b) {
       if (act[b]) {
-        const float t = wave_sum_f(ss[b]);
+        const float t = wave_sum_f_rowbcast(ss[b]);
         if (lane == 0) s_red[b][wv] = t;
       }
     }
@@ -372,7 +372,7 @@ __global__ void __launch_bounds__(256) decode_head_batch_kernel(const mq_decode_
 #pragma unroll
     for (int b = 0; b < DB_MAXB; ++b) {
       if (act[b]) {
-        const float s = wave_sum_f(acc[b]);
+        const float s = wave_sum_f_rowbcast(acc[b]);
         if (lane == 0) hb.logits[(size_t)b * hb.logits_stride + row] = hb.bias ? s + hb.bias[row] : s;
       }
     }

@@ -1,5 +1,5 @@
 // Device helpers shared by the single-sequence decode kernels (mq_decode.hip), the batched ones (mq_decode_batch.hip), the grouped
-// GEMV (mq_decode_grouped.hip) and the multi-token attention (mq_decode_multi.hip): quantizer arithmetic, DPP wave reductions, the
+// GEMV (mq_decode_grouped.hip) and the multi-token attention (mq_decode_multi.hip): the
 // launch-constants line, the layout constants the families agree on, the batched GEMV's prologue and epilogue and the GEMV launches'
 // row geometry.  The five-launch attention's phases build on this header in mq_decode_attention.h.
 #pragma once
@@ -11,87 +11,10 @@ namespace mq {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-// torch.clamp propagates NaN; so do v_maximum3_f32 / v_minimum3_f32 (gfx950) -- two instructions where fmaxf / fminf + a NaN select
-// cost five (round 5: every quantizer of the decode step sits on a launch's critical path)
-__device__ __forceinline__ float dq_clamp_nan(float q, float lo, float hi) {
-  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(q, lo), hi);
-}
-// (x / s: div_by_scale of mq_common.h -- at M = 1 every CU quantises the whole activation row, and that arithmetic is on the
-// launch's critical path)
-// qmodule.py:286-290.  round_ste = (round(t) - t) + t IS rint(t) in fp32 for every t div_by_scale returns (finite or NaN, never inf:
-// mq_common.h image_idxf has the argument) -- two instructions fewer on the M = 1 critical path
-__device__ __forceinline__ float dq_index(float x, float s, float inv_s, float o, float qmin, float qmax) {
-  const float t = div_by_scale(x, s, inv_s);
-  return dq_clamp_nan(__fadd_rn(rintf(t), o), qmin, qmax);
-}
-__device__ __forceinline__ float dq_dequant(float q, float s, float o) { return __fmul_rn(__fsub_rn(q, o), s); }
-
-struct Grid {          // device view of mq_grid
-  float s, o, qmin, qmax, inv_s;
-  bool on;
-  __device__ __forceinline__ float fq(float v) const { return on ? dq_dequant(dq_index(v, s, inv_s, o, qmin, qmax), s, o) : v; }
-  // two elements per instruction where a packed form exists (v_pk_mul / v_pk_fma / v_pk_add are IEEE fp32 on register pairs: the same
-  // bits as fq on each half; rint and the clamp stay scalar).  q - o == q + (-o) exactly.
-  __device__ __forceinline__ v2f fq2(v2f v) const {
-    if (!on) return v;
-    const v2f t = div_by_scale2(v, s, inv_s);
-    v2f r = {rintf(t.x), rintf(t.y)};
-    r = r + splat2(o);
-    r.x = dq_clamp_nan(r.x, qmin, qmax);
-    r.y = dq_clamp_nan(r.y, qmin, qmax);
-    return (r + splat2(-o)) * splat2(s);
-  }
-};
-__device__ __forceinline__ Grid load_grid(const mq_grid& g) {
-  Grid r;
-  r.on = g.scale != nullptr;
-  r.s = r.on ? g.scale[0] : 1.f;
-  r.o = r.on ? g.offset[0] : 0.f;
-  r.qmin = g.qmin;
-  r.qmax = g.qmax;
-  r.inv_s = __fdiv_rn(1.0f, r.s);
-  return r;
-}
-
 __device__ __forceinline__ int dot16(const v4i a, const v4i b, int c) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_sdot4(a[e], b[e], c, false);
   return c;
-}
-__device__ __forceinline__ int wave_sum_dpp(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// float wave reductions on DPP moves (a __shfl_xor is an LDS round trip of ~100 cycles; six of them in a row cost ~0.25 us of
-// a kernel that lasts 3): same lane pattern as wave_sum_dpp; the result is the value of lane 63, broadcast
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-  v += dpp_f<0xB1, 0xf, true>(v);
-  v += dpp_f<0x4E, 0xf, true>(v);
-  v += dpp_f<0x141, 0xf, true>(v);
-  v += dpp_f<0x140, 0xf, true>(v);
-  v += dpp_f<0x142, 0xa, false>(v);                                 // row_bcast15 into rows 1 and 3 (0 elsewhere: x + 0 = x)
-  v += dpp_f<0x143, 0xc, false>(v);                                 // row_bcast31 into rows 2 and 3
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ float wave_max_f(float v) {              // inputs are finite or -inf, never NaN
-  v = fmaxf(v, dpp_f<0xB1, 0xf, true>(v));
-  v = fmaxf(v, dpp_f<0x4E, 0xf, true>(v));
-  v = fmaxf(v, dpp_f<0x141, 0xf, true>(v));
-  v = fmaxf(v, dpp_f<0x140, 0xf, true>(v));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 15));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 31));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 47));
-  const float r4 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-  return fmaxf(fmaxf(r1, r2), fmaxf(r3, r4));
 }
 
 constexpr int DG_THREADS = 1024, DG_WAVES = 16, DG_INFLIGHT = 12;   // 12: the w1|w3 launch (22 row pairs per CU over 8 stream waves: 3 x 4 chunks per lane) has every load in flight at once
@@ -132,7 +55,7 @@ constexpr int DB_XH = 1;             // float4 per row and thread the prologue h
 
 // PROLOGUE role (waves 0 .. DG_PRO-1): the B rows' int8 images (index - 128) into smem [B][K] and the per-wave partials of their
 // image sums into s_redi[b][wave].  Per row b the prologue is thread p's walk over float4 p + 512 u, the per-thread partial in that
-// order, wave_sum_f, then the DG_PRO wave partials added in wave order -- decode_gemv_kernel's arithmetic (mq_decode.hip); the rows'
+// order, wave_sum_f_rowbcast, then the DG_PRO wave partials added in wave order -- decode_gemv_kernel's arithmetic (mq_decode.hip); the rows'
 // chains interleave, the barriers are shared (the STREAM waves mirror them with gemv_batch_stream_barriers).  Beyond DB_XH float4 per
 // row the prologue re-reads x (and the norm weights) instead of holding them: the same values, so the same bits.  Ends on the
 // barrier after which the images and the sums are complete.
@@ -214,7 +137,7 @@ __device__ __forceinline__ void gemv_batch_prologue(const mq_decode_gemv_batch_a
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         if (b < B) {
-          const float t = wave_sum_f(s1[b]);
+          const float t = wave_sum_f_rowbcast(s1[b]);
           if (lane == 0) s_red[b][wave] = t;
         }
       }
@@ -248,7 +171,7 @@ __device__ __forceinline__ void gemv_batch_prologue(const mq_decode_gemv_batch_a
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         if (b < B) {
-          const float t = wave_sum_f(s2[b]);
+          const float t = wave_sum_f_rowbcast(s2[b]);
           if (lane == 0) s_red2[b][wave] = t;
         }
       }
@@ -292,7 +215,7 @@ __device__ __forceinline__ void gemv_batch_prologue(const mq_decode_gemv_batch_a
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         if (b < B) {
-          const float t = wave_sum_f(ss[b]);
+          const float t = wave_sum_f_rowbcast(ss[b]);
           if (lane == 0) s_red[b][wave] = t;
         }
       }
@@ -389,7 +312,7 @@ struct GemvBatchEpilogue {
         rr = __fmul_rn(__fmul_rn(0.5f, fa), __fadd_rn(1.0f, erff(__fmul_rn(fa, 0.70710678118654752440f))));
       }
       const float prod = __fmul_rn(gact.fq(rr), fb);
-      const float qi = dq_index(prod, gout.s, gout.inv_s, gout.o, gout.qmin, gout.qmax);
+      const float qi = index_decode_keepnan(prod, gout.s, gout.inv_s, gout.o, gout.qmin, gout.qmax);
       g.gate_q[(size_t)b * ba.gate_stride + row] = (int8_t)((qi != qi ? (int)gout.qmin : (int)qi) - 128);
       if (g.y) g.y[(size_t)b * ba.y_stride + row] = prod;
     } else {

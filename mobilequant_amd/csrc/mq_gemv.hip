@@ -33,22 +33,6 @@ __device__ __forceinline__ int dot16(const v4i a, const v4i b, int c) {
 }
 
 #pragma clang fp contract(off)
-// qmodule.py:286-287, the same expression tree as mq_elementwise.hip (bit-exact indices)
-__device__ __forceinline__ int q_index_i(float x, float s, float inv_s, float o, float qmin, float qmax) {
-  float q = __fadd_rn(rintf(div_by_scale(x, s, inv_s)), o);
-  return (int)fminf(fmaxf(q, qmin), qmax);
-}
-
-// 64-lane integer sum with DPP row operations (6 VALU adds instead of 6 LDS-crossbar bpermutes); all lanes active
-__device__ __forceinline__ int wave_sum_dpp(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);   // row_half_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);   // row_mirror: every lane = its row-of-16 total
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
-  return __builtin_amdgcn_readlane(v, 63);
-}
 
 constexpr int GV2_THREADS = 1024, GV2_WAVES = 16, GV2_INFLIGHT = 8;
 
@@ -108,8 +92,9 @@ __global__ void __launch_bounds__(GV2_THREADS) gemv_i8_fat_kernel(const GemvArgs
     const float inv_s = __fdiv_rn(1.0f, s);
     for (int i = threadIdx.x; i < M * (K >> 2); i += GV2_THREADS) {
       const float4 v = reinterpret_cast<const float4*>(g.x_f32)[i];
-      const int q0 = q_index_i(v.x, s, inv_s, o, g.xq_qmin, g.xq_qmax) - g.xq_shift, q1 = q_index_i(v.y, s, inv_s, o, g.xq_qmin, g.xq_qmax) - g.xq_shift;
-      const int q2 = q_index_i(v.z, s, inv_s, o, g.xq_qmin, g.xq_qmax) - g.xq_shift, q3 = q_index_i(v.w, s, inv_s, o, g.xq_qmin, g.xq_qmax) - g.xq_shift;
+      // storage form (mq_quant.h): the indices of mq_quantize, bit for bit
+      auto qs = [&](float x) { return (int)index_storage_nan2qmin(x, s, inv_s, o, g.xq_qmin, g.xq_qmax) - g.xq_shift; };
+      const int q0 = qs(v.x), q1 = qs(v.y), q2 = qs(v.z), q3 = qs(v.w);
       reinterpret_cast<unsigned*>(smem)[i] = (q0 & 0xff) | ((q1 & 0xff) << 8) | ((q2 & 0xff) << 16) | ((unsigned)(q3 & 0xff) << 24);
       // K % 256 == 0 (host check): a wave's 64 float4s never straddle a row and the trip count is a multiple of
       // 64, so every wave is fully active here

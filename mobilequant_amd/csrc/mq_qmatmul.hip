@@ -5,7 +5,7 @@
 // The reference fake-quantises both operands (two elementwise passes each), multiplies them in fp32 (rocBLAS here) and fake-quantises
 // the product (another two passes): for the attention block's qk_bmm / pv_bmm that is six passes over the [heads, S, T] tensor.  Here a
 // workgroup owns a 64 x 64 output tile and walks K in 64-wide chunks: both operand chunks are loaded as fp32, quantised in registers
-// with the reference's exact index arithmetic (mq_common.h: image_idxf = clamp(rint(x / s) + o)), stored as int8 (index - shift) in
+// with the reference's exact index arithmetic (mq_quant.h: index_image_nan2qmin = clamp(rint(x / s) + o)), stored as int8 (index - shift) in
 // the LDS -- a 9 ... 16-bit first operand (pv_bmm's probabilities: ptq/mobilequant.py:198) as a high and a low byte plane -- and
 // contracted with v_mfma_i32_16x16x64_i8.  Row sums of the stored A bytes and column sums of the stored B bytes come from two more
 // MFMAs against an all-ones fragment, so the zero-point correction

@@ -438,7 +438,7 @@ __global__ void __launch_bounds__(256) calib_probs_kernel(const float* raw, floa
         }
       }
     }
-    l = wave_sum_f32_dpp(l);
+    l = wave_sum_f_readlane(l);
     float4* orow = reinterpret_cast<float4*>(out + row * cols);
     // ex / l through RN(1 / l) and one fma correction (mq_common.h: div_by_scale, 3 instructions for the ~10 of the IEEE sequence -- this
     // pass is VALU-bound once the masked stores are gone): l in [1, cols] is normal and its reciprocal correctly rounded, so the
@@ -528,7 +528,7 @@ __global__ void __launch_bounds__(256) calib_norm_kernel(const float* __restrict
       }
     }
     auto block_sum = [&](float v, int slot) {
-      v = wave_sum_f32_dpp(v);
+      v = wave_sum_f_readlane(v);
       if (lane == 0) s_red[slot][wv] = v;
       __syncthreads();
       return (s_red[slot][0] + s_red[slot][1]) + (s_red[slot][2] + s_red[slot][3]);

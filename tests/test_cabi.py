@@ -161,12 +161,12 @@ def test_no_barrier_with_lds_traffic_in_flight(tmp_path):
     landed (tests/fuzz_qmatmul.py case 85, one run in five).  The kernel now waits explicitly; tools/barrier_audit.py walks every
     s_barrier of a compiled file backwards through the control-flow graph and must find no path with an LDS operation in flight.
     Audited here: every source whose barriers are the compiler's (mq_gemm.hip and mq_attention.hip place theirs, and the waits in front
-    of them, by hand in inline assembly; mq_elementwise.hip -- block reductions only -- is left to the tool by hand: 80 s to compile)."""
+    of them, by hand in inline assembly; mq_fake_quant.hip and mq_quantize.hip -- block reductions only -- are left to the tool by hand: 80 s to compile)."""
     import sys
     from mobilequant_amd import build
     flags = [f for f in build.FLAGS if f != "-fPIC"]
     procs = []
-    for src in ("mq_qmatmul.hip", "mq_decode.hip", "mq_norm.hip", "mq_gemv.hip", "mq_reduce.hip", "mq_gemm_grouped.hip"):
+    for src in ("mq_qmatmul.hip", "mq_decode.hip", "mq_norm.hip", "mq_activation.hip", "mq_gemv.hip", "mq_reduce.hip", "mq_gemm_grouped.hip"):
         asm = str(tmp_path / src.replace(".hip", ".s"))
         cmd = [build.HIPCC, *flags, *build.PER_FILE_FLAGS.get(src, ()), "-w", "--cuda-device-only", "-S", os.path.join(ROOT, "mobilequant_amd", "csrc", src), "-o", asm]
         procs.append((asm, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

@@ -9,7 +9,7 @@ for cfg in "frs:" "frs_noa:MQ_FR_NO_A=1" "frs_now:MQ_FR_NO_W=1" "frs_nord:MQ_FR_
   mkdir -p $L/$tag
   env MQ_FR_STAMP=1 $envs python tools/gen_fr_asm.py > /dev/null || exit 1
   /opt/rocm/bin/hipcc $FLAGS -c mobilequant_amd/csrc/mq_gemm.hip -o $L/$tag/mq_gemm.o || exit 1
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $L/mq_elementwise.o $L/mq_reduce.o $L/$tag/mq_gemm.o $L/mq_gemv.o $L/mq_norm.o -o $L/$tag/libmobilequant_amd.so || exit 1
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $L/mq_fake_quant.o $L/mq_quantize.o $L/mq_reduce.o $L/$tag/mq_gemm.o $L/mq_gemv.o $L/mq_norm.o $L/mq_activation.o -o $L/$tag/libmobilequant_amd.so || exit 1
   python -c "from mobilequant_amd import build as b; b.build_probe('$tag')" || exit 1
   echo "built $tag ($envs)"
 done
