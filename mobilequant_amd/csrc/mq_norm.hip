@@ -13,8 +13,11 @@
 // Numerics: every elementwise op is the reference's (IEEE divide, round-half-even, separate mul/add; 1/sqrt with
 // correctly rounded sqrt and divide, which is what the CPU reference computes).  The sum of squares is reduced in
 // a different order than torch's (lane-strided partial sums, then a butterfly), so r can differ in the last bit
-// and an output that sits within ~1e-7 relative of a rounding boundary can land on the neighbouring grid point:
-// tests allow 1 LSB on < 0.1 % of the elements.
+// and an output that sits within ~1e-7 relative of a rounding boundary can land on the neighbouring grid point.
+// What the tests hold (tests/test_gpu_prefill_elementwise.py): given the row scalar -- some fp32 r within the
+// derived bound of the float64 one -- every RMSNorm output is the fp32 replay of `emit` bit for bit; a LayerNorm element equals the
+// float64 oracle's index unless its pre-rounding value is within the derived fp32 bound of a boundary (< 0.1 % of the elements of an
+// 8-bit grid), and is one step away at most there.  Against the reference's frozen outputs: 1 LSB on < 0.1 % of the elements.
 #include <hip/hip_fp16.h>
 
 #include "mq_common.h"

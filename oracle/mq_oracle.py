@@ -834,6 +834,8 @@ def decode_gemv_epilogue(sums, rs, alpha, w_zp, col_term, bias=None, seg_end=Non
 
 
 def _gate_chain(fa, fb, act, g_mid, g_act, g_out):
+    """The gate chain of decode_gemv_epilogue (see there): Qact(act(fa)) * fb -> index on g_out, with `tie` over the three quantizers.
+    g_out None: the activation alone (prefill_act) -- prod is Qact(act(fa)) * fb, no product grid, q and t_out None."""
     tol = 2.0 ** -17
 
     def near(t):
@@ -862,6 +864,8 @@ def _gate_chain(fa, fb, act, g_mid, g_act, g_out):
     else:
         a64 = rr64
     prod = (_fq_div(rr, g_act) * fb).astype(F32)
+    if g_out is None:                              # the activation alone (prefill_act): no product grid behind it
+        return dict(q=None, prod=prod, t_mid=t_mid, t_act=t_act, t_out=None, tie=tie)
     t_out = a64 * fb.astype(np.float64) / np.float64(F32(g_out.scale))
     tie |= near(t_out)
     qi = quantize_index(prod, g_out.scale, g_out.offset, g_out.qmin, g_out.qmax)
@@ -1097,3 +1101,124 @@ def prefill_envelope(r, qk: tuple, pv: tuple, exp2_ulp: int = EXP2_ULP):
     lay = lambda z: z.transpose(1, 0, 2).reshape(R, H * D)                          # noqa: E731
     return dict(p_lo=p_lo, p_hi=p_hi, acc_lo=acc_lo, acc_hi=acc_hi, lo=lay(lo), hi=lay(hi), n_amb_score=n_amb_score,
                 n_amb_p=int(((p_hi != p_lo) & live).sum()))
+
+
+# ----------------------------------------------------------------------------------------------
+# a10 (prefill, element-wise)  mq_rmsnorm_quant / mq_layernorm_quant, mq_act_quant and the gated-activation routes
+# ----------------------------------------------------------------------------------------------
+def prefill_norm_n_red(cols):
+    """Adds on the longest path of the float reductions of mq_norm.hip's launch for rows of `cols` floats, branch by branch
+    (launch_norm).  A thread owns the float4 vectors lane, lane + TPR, ... of its row and adds their four squares one after the other
+    into one accumulator: 4 ceil(nvec / TPR) sequential adds, nvec = cols / 4 (a slot past the row's end is skipped, so this is at
+    most 4 V for the register forms and 4 ceil(nvec / 256) on the re-read path; LayerNorm's sum of (x + y) + (z + w) per vector and
+    its four squared deviations per vector are no longer).  Then the six levels of wave_sum_f_readlane (four DPP steps inside a
+    16-lane row, then (r0 + r1) + (r2 + r3)), then block_sum4's (s0 + s1) + (s2 + s3) where a workgroup owns the row:
+      cols < 1024            V = 4, TPR = 64 (a wave per row)     4 ceil(nvec / 64) + 6       <= 22
+      cols <= 1024           V = 1, TPR = 256                     4 + 6 + 2                   =  12
+      cols <= 2048           V = 2                                8 + 6 + 2                   =  16
+      cols <= 4096           V = 4                                16 + 6 + 2                  =  24
+      cols <= 8192           V = 8                                32 + 6 + 2                  =  40
+      beyond (re-read)       V = 0                                4 ceil(nvec / 256) + 6 + 2     (12288: 56)
+    norm_tiled8_kernel<V, LN, GRPS> (1024 <= cols <= 4096) runs the arithmetic of the TPR = 256 form of its V in either GRPS."""
+    nvec = int(cols) // 4
+    tpr = 64 if cols < 1024 else 256
+    return 4 * ((nvec + tpr - 1) // tpr) + 6 + (0 if tpr == 64 else 2)
+
+
+def f32_between(lo, hi):
+    """Every fp32 value in [lo, hi] (0 < lo <= hi finite, float64), ascending: consecutive bit patterns."""
+    a, b = F32(lo), F32(hi)
+    if np.float64(a) < lo:
+        a = np.nextafter(a, F32(np.inf))
+    if np.float64(b) > hi:
+        b = np.nextafter(b, F32(-np.inf))
+    ia, ib = int(a.view(np.uint32)), int(b.view(np.uint32))
+    return np.arange(ia, ib + 1, dtype=np.uint32).view(F32)
+
+
+def prefill_norm_rows(x, weight, bias, eps, layernorm, in_q, out_q, q_shift, n_red):
+    """mq_rmsnorm_quant / mq_layernorm_quant row by row in float64: x [rows, cols] fp32, weight the (already fake-quantised) vector the
+    kernel is given, bias or None, in_q / out_q QuantizerOracles or None.  The input quantizer is the reference's division form in fp32
+    (bit-exact: it is element-wise); the norm of each row is _norm64 with the reduction depth n_red (prefill_norm_n_red(cols): the
+    derivation is there), so `err` bounds the fp32 kernel's |value - v64| element by element.
+    Returns a dict ([rows, cols] unless noted; the index fields are None without an output grid):
+      xi      fp32     the input-quantised row the kernel normalises
+      v64     float64  the norm value;  err  float64  the fp32 error bound on it
+      t64     float64  v64 / scale: the pre-rounding value on the output grid
+      idx     float64  clip(rint(t64) + offset, qmin, qmax)  (NaN where v64 is)
+      q8      int8     idx - q_shift, NaN -> qmin - q_shift (the kernel's integer image);  rs [rows] int64 its row sums
+      tie     bool     _tie_dist(t64) within (err + u |v64|) / scale: the kernel's fp32 value may round to the neighbouring index (the
+                       quotient's own rounding is the u |v64| term: div_by_scale is the IEEE quotient)
+      r64 [rows] float64   (RMS) 1 / sqrt(mean(xi^2) + eps);  r_err [rows]: bound of |r - r64| for the kernel's fp32
+                       r = fl(1 / fl(sqrt(fl(fl(ss / cols) + eps)))): ss carries gamma(n_red + 1) (the squares' rounding and the adds; all terms
+                       positive), / cols and + eps one u each -> gamma(n_red + 3) under the root, which halves it (to first order; the
+                       factor 1.001 covers the second), + u for the root and + u for the reciprocal."""
+    x = np.asarray(x, F32)
+    rows, cols = x.shape
+    with np.errstate(all="ignore"):
+        xi = _fq_div(x, in_q).astype(F32)
+        w = np.asarray(weight, F32).astype(np.float64)
+        b = np.asarray(bias, F32).astype(np.float64) if bias is not None else None
+        e = float(F32(eps))
+        v64, err = np.empty((rows, cols)), np.empty((rows, cols))
+        for i in range(rows):
+            v64[i], err[i] = _norm64(xi[i].astype(np.float64), w, b, bool(layernorm), e, n_red)
+        out = dict(xi=xi, v64=v64, err=err, t64=None, idx=None, q8=None, rs=None, tie=None, r64=None, r_err=None)
+        if not layernorm:
+            x64 = xi.astype(np.float64)
+            r64 = 1.0 / np.sqrt((x64 * x64).sum(axis=1) / cols + e)
+            out.update(r64=r64, r_err=r64 * (_gamma(n_red + 3) / 2 + 2 * U32) * 1.001)
+        if out_q is None:
+            return out
+        s, o = np.float64(F32(out_q.scale)), np.float64(F32(out_q.offset))
+        t64 = v64 / s
+        idx = np.clip(np.rint(t64) + o, out_q.qmin, out_q.qmax)
+        bound = (err + U32 * np.abs(v64)) / s * (1.0 + 1e-6) + 1e-300
+        tie = _tie_dist(t64) <= bound
+        st = np.where(np.isnan(idx), np.float64(out_q.qmin), idx) - q_shift
+    q8 = st.astype(np.int64).astype(np.int8)
+    out.update(t64=t64, idx=idx, q8=q8, rs=q8.astype(np.int64).sum(axis=1), tie=tie)
+    return out
+
+
+def prefill_norm_replay(xi, r, shift, weight, bias, layernorm, out_q, q_shift):
+    """The `emit` of mq_norm.hip in fp32, op for op, given the row scalars: xi [..., cols] fp32 (prefill_norm_rows' xi), r and shift
+    fp32 (scalars, or [..., 1]).  RMS: fl(w fl(xi r)); LayerNorm: fl(fl(fl(xi r) + shift) w); + bias; then the value-form index
+    (quantize_index: NaN stays NaN), y = dequant(index), and the integer image index - q_shift with NaN -> qmin.  No approximation:
+    every operation is one IEEE fp32 operation in the kernel's order.  Returns dict(y fp32, idx fp32 | None, q8 int8 | None,
+    rs int64 [...] | None); without an output grid y is the norm value itself."""
+    xi, r, w = np.asarray(xi, F32), np.asarray(r, F32), np.asarray(weight, F32)
+    with np.errstate(all="ignore"):
+        z = (xi * r).astype(F32)
+        if layernorm:
+            y = ((z + np.asarray(shift, F32)).astype(F32) * w).astype(F32)
+        else:
+            y = (w * z).astype(F32)
+        if bias is not None:
+            y = (y + np.asarray(bias, F32)).astype(F32)
+        if out_q is None:
+            return dict(y=y, idx=None, q8=None, rs=None)
+        idx = quantize_index(y, out_q.scale, out_q.offset, out_q.qmin, out_q.qmax)
+        yq = dequantize_index(idx, out_q.scale, out_q.offset)
+    q8 = (np.where(np.isnan(idx), F32(out_q.qmin), idx).astype(np.int64) - int(q_shift)).astype(np.int8)
+    return dict(y=yq, idx=idx, q8=q8, rs=q8.astype(np.int64).sum(axis=-1))
+
+
+def prefill_act(x, act, in_q, mid_q, out_q):
+    """mq_act_quant (QSiLU act 0 / QGELU act 1): xi = Qin(x), then _gate_chain's activation with b = 1 and no product grid.  Returns
+    dict(y fp32, xi, t_mid, t_act (float64 pre-rounding values, None where the grid is off), tie)."""
+    with np.errstate(all="ignore"):
+        xi = _fq_div(np.asarray(x, F32), in_q).astype(F32)
+        c = _gate_chain(xi, np.ones_like(xi), int(act), mid_q, out_q, None)
+    return dict(y=c["prod"], xi=xi, t_mid=c["t_mid"], t_act=c["t_act"], tie=c["tie"])
+
+
+def prefill_gate(y1, vb, out_q, q_shift):
+    """The gated FFN's product behind an OBSERVED activation value: prod = fl(y1 vb) (ElementwiseMul is not quantised), w2's input
+    index in the division form and its integer image index - q_shift, NaN -> qmin (mq_activation.hip gated_store).  Broadcasts.
+    Returns dict(prod fp32, idx fp32 (NaN kept), q8 int8)."""
+    with np.errstate(all="ignore"):
+        prod = (np.asarray(y1, F32) * np.asarray(vb, F32)).astype(F32)
+        idx = quantize_index(prod, out_q.scale, out_q.offset, out_q.qmin, out_q.qmax)
+    q8 = (np.where(np.isnan(idx), F32(out_q.qmin), idx).astype(np.int64) - int(q_shift)).astype(np.int8)
+    return dict(prod=prod, idx=idx, q8=q8)
