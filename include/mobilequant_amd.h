@@ -724,6 +724,38 @@ typedef struct mq_attention_args {
 } mq_attention_args;
 int mq_attention_quant(const mq_attention_args* args, mq_stream_t stream);
 
+/* ---- the bridge between a decode engine's int8 KV caches and the image caches of mq_attention_quant ------------- */
+/* The decode kernels keep one sequence's keys as k [kv_heads][cache_len][head_dim] int8 (index - 128) and its values either in the same
+ * layout (v_chunked = 0) or transposed in 16-position chunks, [kv_heads][cache_len / 16][head_dim][16] (v_chunked = 1: the layout of
+ * mq_decode_attention_oproj; cache_len % 16 == 0).  Head h starts k_head_stride / v_head_stride BYTES behind head h - 1 (multiples of 16,
+ * >= cache_len * head_dim), so a slot of a batched engine's caches is served in place.  The images are the caches of mq_attention_args
+ * laid out for cache_seq rows (cache_seq % 64 == 0, <= 65536), by the formulas stated there; both sides hold the same indices.
+ * mq_attention_cache_import: positions 0 .. n - 1 (p0 = 0, n % 64 == 0, n <= cache_seq, n <= cache_len) of the decode caches -> k_i8,
+ *   k_rowsum (zq = *qk_a.offset, read by the kernel at launch), vt_i8, v_prefix (required at head_dim 128 / 256, NULL at 64) and, when
+ *   k_f16 != NULL (head_dim 64), the fragment-blocked fp16 image of index - zk (zk = *qk_b.offset).  With zk outside [-256, 511] the
+ *   k_f16 image is filled with NaN, exactly as mq_attention_quant's own preparation poisons it: the caller must then keep this cache
+ *   on the int8 score contraction (k_f16 = NULL in mq_attention_args).  Image rows >= n are not written.  Only the offsets of qk_a / qk_b are read.
+ * mq_attention_cache_export: rows p0 .. p0 + n - 1 of k_i8 / vt_i8 (any p0 >= 0, n > 0, p0 + n <= cache_seq, p0 + n <= cache_len) ->
+ *   the decode caches.  No byte outside those positions is written: in the chunked layout the other positions of a shared 16-position
+ *   chunk keep their values.  k_rowsum, v_prefix, k_f16 and the grids are ignored.
+ * One launch each, no host synchronisation (capturable).  Pointers 16-byte aligned.  Validation comes before any HIP call. */
+typedef struct mq_attention_cache_args {
+  int8_t* k;
+  int8_t* v;
+  int64_t k_head_stride, v_head_stride;
+  int v_chunked;
+  int kv_heads, head_dim, cache_len;
+  int p0, n, cache_seq;
+  int8_t* k_i8;
+  int8_t* vt_i8;
+  int32_t* k_rowsum;
+  int32_t* v_prefix;
+  uint16_t* k_f16;
+  mq_grid qk_a, qk_b;
+} mq_attention_cache_args;
+int mq_attention_cache_import(const mq_attention_cache_args* args, mq_stream_t stream);
+int mq_attention_cache_export(const mq_attention_cache_args* args, mq_stream_t stream);
+
 /* ---- calibration: the score chain of an attention block with its two statistics ------------------ */
 /* ptq/generate_act_range.py:55-69 hooks qk_bmm's output (raw scores) and pv_bmm's input (probabilities); the graph between them is
  * hf_model.py:513-530: att / sqrt(head_dim) [+ mask] -> softmax(dim = -1, fp32).  One pass per row: running [min, max] of the raw scores,

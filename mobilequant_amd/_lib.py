@@ -114,6 +114,13 @@ class MqAttentionArgs(ctypes.Structure):
                 ("rot_dim", c_int), ("v_prefix", c_void_p), ("pos0", c_int), ("cache_seq", c_int), ("q_f16", c_void_p), ("k_f16", c_void_p), ("batch", c_int)]
 
 
+class MqAttentionCacheArgs(ctypes.Structure):
+    _fields_ = [("k", c_void_p), ("v", c_void_p), ("k_head_stride", c_int64), ("v_head_stride", c_int64), ("v_chunked", c_int),
+                ("kv_heads", c_int), ("head_dim", c_int), ("cache_len", c_int), ("p0", c_int), ("n", c_int), ("cache_seq", c_int),
+                ("k_i8", c_void_p), ("vt_i8", c_void_p), ("k_rowsum", c_void_p), ("v_prefix", c_void_p), ("k_f16", c_void_p),
+                ("qk_a", MqGrid), ("qk_b", MqGrid)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "mq_version": (c_int, []),
@@ -189,6 +196,8 @@ _SIGNATURES = {
     "mq_decode_head_batch": (c_int, [POINTER(MqDecodeHeadBatchArgs), _P]),
     "mq_decode_attention_multi": (c_int, [POINTER(MqDecodeAttentionMultiArgs), _P]),
     "mq_attention_quant": (c_int, [POINTER(MqAttentionArgs), _P]),
+    "mq_attention_cache_import": (c_int, [POINTER(MqAttentionCacheArgs), _P]),
+    "mq_attention_cache_export": (c_int, [POINTER(MqAttentionCacheArgs), _P]),
     "mq_score_head_scratch_bytes": (c_int64, [c_int64, c_int64]),
     "mq_score_head": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P]),
     "mq_sample": (c_int, [POINTER(MqSampleArgs), _P]),

@@ -363,6 +363,55 @@ class _DecodeBase:
         if self._keep.stale():
             self.refresh_grids()
 
+    # -- continuing a live sequence with a prefill forward over its cache -----------------------------------------
+    # prefill(append=True) steps fewer tokens than this behind the 64-boundary instead of importing the cache for them.  NOT MEASURED
+    # yet: 16 is a placeholder until tools/bench_append.py has been run on the device (the crossover against extend(), rounded up to
+    # a multiple of 8, belongs here).
+    APPEND_MIN_TOKENS = 16
+
+    def _append_split(self, P: int, n: int) -> Tuple[int, Optional[str]]:
+        """How an append of n tokens at position P is served: (tokens to step first, reason).  The first (-P) % 64 tokens are stepped
+        to the next multiple of 64 -- the only positions the chunk-continuing attention starts at -- and the rest goes through the
+        model's chunked forward, unless too few remain or the model's attention cannot continue an image cache: then every token is
+        stepped and `reason` says why."""
+        from .llama import image_cache_unsupported
+        head = min((-P) % 64, n)
+        rest = n - head
+        if rest < max(2, self.APPEND_MIN_TOKENS):
+            return n, (None if rest == 0 else f"{rest} token(s) behind position {P + head}: fewer than APPEND_MIN_TOKENS = {max(2, self.APPEND_MIN_TOKENS)}")
+        why = image_cache_unsupported(self.model)
+        if why is not None:
+            return n, why
+        return head, None
+
+    def _append_chunk(self, chunk: Sequence[int], P1: int, caches, v_chunked: bool) -> Optional[torch.Tensor]:
+        """The fused part of an append: per layer import positions [0, P1) of caches(li) = (k, v) into that layer's ImageCache
+        (allocated on first use and kept: cache_len rounded up to 64 rows), run the model's chunked forward at pos = P1 and export
+        rows [P1, P1 + len(chunk)) back.  Returns the logits row of the last token, or None when the model refused the image cache
+        after all (nothing of the engine has been written then)."""
+        from . import ops
+        from .llama import _f16_scores_ok
+        if getattr(self, "_append_images", None) is None:
+            self._append_images = self.model.new_image_cache(1, self.cache_len, device=self.dev)
+        images = self._append_images
+        for li, layer in enumerate(self.model.layers):
+            qk = layer.self_attn.qk_bmm
+            grids = {name: (q.scale.detach(), q.offset.detach(), q.qmin, q.qmax) for name, q in (("qk_a", qk.input_quantizer), ("qk_b", qk.input2_quantizer))}
+            k, v = caches(li)
+            ops.attention_cache_import(images[li].per_sequence[0], k, v, P1, grids, v_chunked=v_chunked, k_f16_exact=_f16_scores_ok(qk.input2_quantizer))
+            images[li].filled = P1
+        ids = torch.as_tensor([int(t) for t in chunk], dtype=torch.long, device=self.dev).view(1, -1)
+        try:
+            logits = self.model(ids, cache=images, pos=P1, last_logits_only=True)
+        except RuntimeError as e:
+            if "image cache" not in str(e):
+                raise
+            return None
+        for li in range(len(self.model.layers)):
+            k, v = caches(li)
+            ops.attention_cache_export(images[li].per_sequence[0], k, v, P1, len(chunk), v_chunked=v_chunked)
+        return logits[0, -1]
+
     def _record(self, launch, append, before_capture=None):
         """launch() followed by append() as ONE hipGraph on one stream.  launch() first runs once on a side stream outside the capture:
         it sets the launches' LDS ceilings, which must not happen while capturing.  What that warm-up may touch (pos parked at the
@@ -636,6 +685,8 @@ class DecodeEngine(_DecodeBase):
         big = max(s.hidden, s.ffn, s.heads * s.head_dim)
         self.max_rows = max(1, min(self.MAX_ROWS, self.ROW_IMAGE_BYTES // big, self.ROW_HEAD_FLOATS // s.hidden))
         self.spec_stats = None
+        self.append_stats = None                             # what the last prefill(append=True) did
+        self._append_images = None                           # per layer ImageCache of prefill(append=True), allocated on first use
         self.graph = None
         self.graph_long = None
         self._sampler = None                                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
@@ -1033,11 +1084,22 @@ class DecodeEngine(_DecodeBase):
         return self.logits
 
     @torch.no_grad()
-    def prefill(self, context_ids) -> torch.Tensor:
+    def prefill(self, context_ids, append: bool = False) -> torch.Tensor:
         """Context encoding in ONE forward over the whole context (sim_model.py:176-193) instead of len(context) steps: the module
         graph's prefill (with llama.fuse_decoder_layer: 9 launches per layer) runs with a KV cache attached, the cached keys /
         values are put on their QMatMul input grids (what the step kernels keep in the cache) and the position is set behind the
-        context.  Returns the logits of the last context position (self.logits)."""
+        context.  Returns the logits of the last context position (self.logits).
+        append=True: the tokens CONTINUE the live sequence at P = position().  P + len(ids) > cache_len raises
+        RuntimeError before anything runs; P == 0 is the path above.  Otherwise the first (-P) % 64 tokens are stepped (extend():
+        the bits of step()) up to a multiple of 64, P'; the rest -- if at least APPEND_MIN_TOKENS (and 2) tokens -- is ONE chunked
+        forward of the model over image caches imported from the engine's caches (ops.attention_cache_import), whose new rows are
+        exported back (ops.attention_cache_export); fewer tokens, a model whose attention is not the fused one, or grids / a head_dim
+        the fused attention does not serve are stepped instead.  self.append_stats = {"stepped", "prefilled", "reason"} says what ran.
+        Contract: the stepped tokens carry step()'s bits; the prefilled chunk carries the bits of the model's own chunked forward
+        (model(chunk, cache=image_cache, pos=P')) over an image cache that holds the engine's cached indices.  The two paths agree
+        with each other only within the bound that holds between prefill() and the steps behind it; no bitwise claim between them."""
+        if append:
+            return self._prefill_append(context_ids)
         ids = torch.as_tensor([int(t) for t in context_ids], dtype=torch.long, device=self.dev).view(1, -1)
         S = ids.shape[1]
         assert 0 < S <= self.cache_len
@@ -1050,6 +1112,33 @@ class DecodeEngine(_DecodeBase):
             self.load_cached_values(li, att.pv_bmm.input2_quantizer.quantize_to_int(raw[li][1][0].contiguous())[0])
         self.set_position(S)
         self.logits.copy_(logits[0, -1])
+        return self.logits
+
+    @torch.no_grad()
+    def _prefill_append(self, context_ids) -> torch.Tensor:
+        t = [int(v) for v in context_ids]
+        P = self._host_pos
+        if not t:
+            raise ValueError("DecodeEngine.prefill: no tokens to append")
+        if P + len(t) > self.cache_len:
+            raise RuntimeError(f"DecodeEngine.prefill: {len(t)} tokens appended at position {P} overflow the KV cache ({self.cache_len} positions)")
+        if P == 0:
+            self.append_stats = {"stepped": 0, "prefilled": len(t), "reason": None}
+            return self.prefill(t)
+        self._sync_grids()
+        head, reason = self._append_split(P, len(t))
+        if head:
+            self.extend(t[:head])
+        if head < len(t):
+            row = self._append_chunk(t[head:], P + head, lambda li: (self.k_cache[li], self.v_cache[li]), self.v_transposed)
+            if row is None:
+                reason = "the model's attention refused the image cache"
+                self.extend(t[head:])
+                head = len(t)
+            else:
+                self.set_position(P + len(t))
+                self.logits.copy_(row)
+        self.append_stats = {"stepped": head, "prefilled": len(t) - head, "reason": reason}
         return self.logits
 
     @torch.no_grad()

@@ -65,6 +65,8 @@ class BatchDecodeEngine(_DecodeBase):
         self._host_pos = [self.cache_len] * B
         self._active = [False] * B
         self.graph = None
+        self.append_stats = None             # what the last prefill(slot, ids, append=True) did
+        self._append_images = None           # per layer ImageCache of prefill(append=True), allocated on first use
         self._sampler = None                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
         self._sample_graphs = {}             # penalised -> the captured sample + step graph, recorded on first use after capture()
         self._lower()
@@ -215,11 +217,64 @@ class BatchDecodeEngine(_DecodeBase):
         self.set_position(slot, n)
 
     @torch.no_grad()
-    def prefill(self, slot: int, context_ids) -> torch.Tensor:
+    def _step_slot(self, slot: int, tokens: Sequence[int]):
+        """step() for ONE slot, token by token: the other active slots are parked at the cache_len sentinel for the duration (an idle
+        slot's cache and logits row do not change) and get their positions back afterwards."""
+        others = [b for b in range(self.batch) if b != slot and self._active[b]]
+        saved = self.pos.clone()
+        try:
+            for b in others:
+                self._active[b] = False
+                self.pos[b] = self.cache_len
+            for tok in tokens:
+                self.tok[slot] = int(tok)
+                self.step()
+        finally:
+            for b in others:
+                self._active[b] = True
+                self.pos[b] = saved[b]
+
+    @torch.no_grad()
+    def _prefill_append(self, slot: int, context_ids) -> torch.Tensor:
+        t = [int(v) for v in context_ids]
+        if not self._active[slot]:
+            raise RuntimeError(f"BatchDecodeEngine.prefill: slot {slot} is idle: append continues a live sequence (prefill() or start() it first)")
+        P = self._host_pos[slot]
+        if not t:
+            raise ValueError("BatchDecodeEngine.prefill: no tokens to append")
+        if P + len(t) > self.cache_len:
+            raise RuntimeError(f"BatchDecodeEngine.prefill: {len(t)} tokens appended at position {P} overflow slot {slot}'s KV cache "
+                               f"({self.cache_len} positions)")
+        if P == 0:
+            self.append_stats = {"stepped": 0, "prefilled": len(t), "reason": None}
+            return self.prefill(slot, t)
+        self._sync_grids()
+        head, reason = self._append_split(P, len(t))
+        if head:
+            self._step_slot(slot, t[:head])
+        if head < len(t):
+            row = self._append_chunk(t[head:], P + head, lambda li: (self.k_cache[li][slot], self.v_cache[li][slot]), False)
+            if row is None:
+                reason = "the model's attention refused the image cache"
+                self._step_slot(slot, t[head:])
+                head = len(t)
+            else:
+                self.set_position(slot, P + len(t))
+                self.logits[slot].copy_(row)
+        self.append_stats = {"stepped": head, "prefilled": len(t) - head, "reason": reason}
+        return self.logits[slot]
+
+    @torch.no_grad()
+    def prefill(self, slot: int, context_ids, append: bool = False) -> torch.Tensor:
         """DecodeEngine.prefill for one slot: one module-graph forward over the context, its keys / values on their QMatMul input
         grids into the slot's caches, the slot's position behind the context.  The other slots are untouched.  Returns the logits row
-        of the last context position."""
+        of the last context position.
+        append=True: DecodeEngine.prefill(append=True) on this slot's live sequence (same split, same contract, self.append_stats);
+        the slot's caches are imported and written in place through their head strides.  The stepped tokens run as single-slot steps
+        with the other slots parked; their caches, positions and logits rows do not change."""
         self._check_slot(slot)
+        if append:
+            return self._prefill_append(slot, context_ids)
         ids = torch.as_tensor([int(t) for t in context_ids], dtype=torch.long, device=self.dev).view(1, -1)
         S = ids.shape[1]
         assert 0 < S <= self.cache_len

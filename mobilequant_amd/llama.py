@@ -295,6 +295,36 @@ def _fused_attention_forward(self, x, cos, sin, mask, cache=None, pos: int = 0, 
     return out if resid is None else resid + out
 
 
+def image_cache_unsupported(model) -> Optional[str]:
+    """None when every attention block of `model` continues an ImageCache through _fused_attention_forward, else the first reason it
+    would take the module chain instead (the conditions of that forward that do not depend on the chunk: fused at all, head_dim, the
+    QMatMuls and their static per-tensor grids, fp32 parameters on a device).  DecodeEngine.prefill(append=True) asks before it feeds a chunk."""
+    from .quantization import qmodule as Q
+    s = model.shape
+    if s.head_dim not in (64, 128, 256):
+        return f"head_dim {s.head_dim} is not served by the fused attention (64, 128, 256)"
+    w = model.embed_tokens.weight
+    if not w.is_cuda or w.dtype != torch.float32:
+        return "the model is not an fp32 model on a ROCm device"
+    for i, layer in enumerate(model.layers):
+        att = layer.self_attn
+        if not hasattr(att, "_mq_plain_forward"):
+            return f"layers.{i}.self_attn is not the fused attention (llama.fuse_attention / fuse_decoder_layer)"
+        if getattr(att, "fused_mode", "auto") == "off":
+            return f"layers.{i}.self_attn.fused_mode is off"
+        qk, pv = att.qk_bmm, att.pv_bmm
+        if not isinstance(qk, Q.QMatMul) or not isinstance(pv, Q.QMatMul):
+            return f"layers.{i}.self_attn's matmuls are not QMatMuls"
+        if Q._needs_grad(*att.parameters()):
+            return f"layers.{i}.self_attn has parameters that require gradients"
+        if not (Q._u8_grid(qk.input_quantizer) and Q._u8_grid(qk.input2_quantizer) and Q._u8_grid(pv.input2_quantizer)
+                and Q._static_per_tensor(pv.input_quantizer, 16) and pv.input_quantizer.qmin == 0):
+            return f"layers.{i}.self_attn needs static per-tensor 8-bit unsigned q / k / v grids and an unsigned probability grid of at most 16 bits"
+        if Q.QRMSNorm._grid_or_none(qk.output_quantizer) is False or Q.QRMSNorm._grid_or_none(pv.output_quantizer) is False:
+            return f"layers.{i}.self_attn's output grids are not static per-tensor grids"
+    return None
+
+
 def _f16_scores_ok(*quantizers) -> bool:
     """Whether the q / k grids' offsets let ops.attention_quant contract the scores in fp16 (ops.F16_OFFSETS).  The offsets are read on
     the host once per grid version and kept on the quantizer; while a graph is being captured an unread grid takes the int8

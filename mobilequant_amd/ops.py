@@ -987,6 +987,74 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     return out if S_real == S else out[..., :S_real, :].contiguous()
 
 
+def _cache_bridge_args(fn: str, cache: dict, k: torch.Tensor, v: torch.Tensor, p0: int, n: int, v_chunked: bool):
+    """Host-side checks (before any device is touched) and the argument block shared by attention_cache_import / _export."""
+    D, KV, rows = int(cache["head_dim"]), int(cache["kv_heads"]), int(cache["rows"])
+    if D not in (64, 128, 256):
+        raise RuntimeError(f"mobilequant_amd: {fn} serves head_dim 64, 128 and 256 (got {D})")
+    p0, n = int(p0), int(n)
+    if n <= 0 or p0 < 0 or p0 + n > rows:
+        raise RuntimeError(f"mobilequant_amd: {fn} positions {p0} .. {p0 + n - 1} outside the image cache's {rows} rows")
+    if not isinstance(k, torch.Tensor) or not isinstance(v, torch.Tensor) or k.dtype != torch.int8 or v.dtype != torch.int8:
+        raise RuntimeError(f"mobilequant_amd: {fn} takes int8 decode caches")
+    L = k.shape[1] if k.dim() == 3 else -1
+    v_shape = (KV, L // 16, D, 16) if v_chunked else (KV, L, D)
+    if (k.dim() != 3 or tuple(k.shape) != (KV, L, D) or tuple(v.shape) != v_shape or (v_chunked and L % 16) or p0 + n > L
+            or k.stride()[1:] != (D, 1) or v.stride()[1:] != ((16 * D, 16, 1) if v_chunked else (D, 1))):
+        raise RuntimeError(f"mobilequant_amd: {fn} shape mismatch: k must be [{KV}, cache_len, {D}], v the same or (v_chunked) "
+                           f"[{KV}, cache_len / 16, {D}, 16], dense behind the head dimension, with at least {p0 + n} positions "
+                           f"(got k {tuple(k.shape)}, v {tuple(v.shape)})")
+    _dev(k, "k"), _dev(v, "v")
+    if cache["k_i8"].device != k.device or v.device != k.device:
+        raise RuntimeError(f"mobilequant_amd: {fn} image cache and decode caches live on different devices")
+    a = _lib.MqAttentionCacheArgs()
+    a.k, a.v, a.k_head_stride, a.v_head_stride, a.v_chunked = k.data_ptr(), v.data_ptr(), int(k.stride(0)), int(v.stride(0)), int(bool(v_chunked))
+    a.kv_heads, a.head_dim, a.cache_len, a.p0, a.n, a.cache_seq = KV, D, L, p0, n, rows
+    a.k_i8, a.vt_i8 = cache["k_i8"].data_ptr(), cache["vt_i8"].data_ptr()
+    return a
+
+
+def attention_cache_import(cache: dict, k: torch.Tensor, v: torch.Tensor, n: int, grids: dict, v_chunked: bool = False,
+                           k_f16_exact: Optional[bool] = None) -> None:
+    """Build the images of `cache` (attention_image_cache) for positions 0 .. n - 1 from a decode engine's caches
+    (mq_attention_cache_import, one launch): k [kv_heads, cache_len, D] int8, v the same or -- v_chunked -- the four-launch chain's
+    [kv_heads, cache_len / 16, D, 16]; a view with its own head stride (a slot of the batched engine's caches) is read in place.
+    n % 64 == 0.  grids: qk_a and qk_b as (scale, offset, qmin, qmax) -- the kernel reads their OFFSETS by pointer at launch (the zero
+    points of k_rowsum and k_f16).  Rows >= n of the images are left as they are.
+    k_f16 (head_dim 64) holds fp16(index - zk) exactly only for zk inside F16_OFFSETS; outside, the kernel poisons it with NaN as the
+    prefill's own preparation does, and cache["k_f16_valid"] is set False so that attention_quant keeps this cache on the int8 score
+    contraction.  k_f16_exact: the caller's knowledge of that (llama._f16_scores_ok); None reads qk_b's offset on the host (False while
+    a graph is being captured: no device read there)."""
+    if int(n) % 64:
+        raise RuntimeError(f"mobilequant_amd: attention_cache_import needs n % 64 == 0 (got n={n}): the attention continues an image cache at multiples of 64")
+    a = _cache_bridge_args("attention_cache_import", cache, k, v, 0, n, v_chunked)
+    keep = []
+    for name in ("qk_a", "qk_b"):
+        g = grids[name]
+        s, o = _f32(g[0], "scale"), _f32(g[1], "offset")
+        keep += [s, o]
+        setattr(a, name, _lib.MqGrid(s.data_ptr(), o.data_ptr(), float(g[2]), float(g[3])))
+    a.k_rowsum = cache["k_rs"].data_ptr()
+    if cache.get("v_pre") is not None:
+        a.v_prefix = cache["v_pre"].data_ptr()
+    if cache.get("k_f16") is not None:
+        a.k_f16 = cache["k_f16"].data_ptr()
+        if k_f16_exact is None:
+            k_f16_exact = not torch.cuda.is_current_stream_capturing() and attention_f16_offsets_ok(float(grids["qk_b"][1].detach().reshape(-1)[0]))
+    with _on(k, v, *keep):
+        _lib.call("mq_attention_cache_import", ctypes.byref(a), _stream())
+    cache["k_f16_valid"] = bool(k_f16_exact) and cache.get("k_f16") is not None
+
+
+def attention_cache_export(cache: dict, k: torch.Tensor, v: torch.Tensor, p0: int, n: int, v_chunked: bool = False) -> None:
+    """The inverse for rows p0 .. p0 + n - 1 of the images (mq_attention_cache_export, one launch): the keys are copied, the values
+    un-permuted into either decode layout.  n is any positive count -- the REAL rows of a ragged final chunk, not its pad rows.  No
+    byte outside those positions is written (the other positions of a shared 16-position chunk keep their values)."""
+    a = _cache_bridge_args("attention_cache_export", cache, k, v, p0, n, v_chunked)
+    with _on(k, v):
+        _lib.call("mq_attention_cache_export", ctypes.byref(a), _stream())
+
+
 # ---- token scoring: the fp32 lm_head fused with its log-softmax ------------------------------------------------------------------
 def score_head(y: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], targets: Optional[torch.Tensor]):
     """Per row of y [M, K] (fp32, unit column stride): (logprob [M] fp32, lse [M] fp32, argmax [M] int64) of the logits
