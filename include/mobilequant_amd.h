@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4: + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -895,6 +895,41 @@ int mq_sample_penalized(const mq_sample_penalized_args* args, mq_stream_t stream
  * ids (n >= 0; ids may repeat).  ids is DEVICE memory, so no id is checked on the host: an id outside [0, V) is ignored by the kernel.
  * At most two launches, capturable. */
 int mq_sample_history_prompt(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int clear, mq_stream_t stream);
+
+/* rows (1 .. MQ_DECODE_MAX_BATCH) logits rows of ONE sequence -- the rows of a multi-token step over [t, d_1 .. d_(rows-1)] -- drawn under
+ * one request (params: one mq_sample_row), one optional penalty row, one optional dense bias row [V] and one optional history [V], all
+ * shared by the rows (the rule's extension in csrc/mq_sample.hip's header).  Row j is drawn at n_j = *n_base + n_offset + j
+ * (n_base: device memory; n_offset in [-2^30, 2^30]).  With a penalised request, row j sees the history with the proposals in front of it
+ * counted: c_i(j) = min(65535, c_i + #{m < j : proposals[m] == i}), seen_i(j) = (h_i != 0) or (c_i(j) > 0); proposals: rows - 1 ids in
+ * device memory (NULL when rows == 1); an id outside [0, V) matches no entry; history NULL = all zeros.  tok[j] (kept[j], logprob[j]: as in
+ * mq_sample, nullable) is, bit for bit, what mq_sample draws for that row alone at n_j, and under a penalised request what
+ * mq_sample_penalized draws there from a history on which proposals[0 .. j-1] were counted one after the other.  A neutral request (penalty
+ * NULL or neutral, bias NULL) keeps the bits of its logits, history or not.  Every row draws: there is no idle-row sentinel.  Nothing but
+ * tok / kept / logprob / scratch is written.  Limits and alignments of mq_sample; penalty, history, bias 16-byte, proposals 8-byte aligned.
+ * Two launches (one while V <= 4096), no host synchronisation: capturable. */
+typedef struct mq_sample_rows_args {
+  const float* logits;
+  int64_t logits_stride;
+  int64_t V;
+  int rows; /* 1 .. MQ_DECODE_MAX_BATCH */
+  const int* n_base;
+  int n_offset;
+  const mq_sample_row* params;
+  const mq_sample_penalty_row* penalty;
+  const float* bias;
+  const uint32_t* history;
+  const int64_t* proposals;
+  int64_t* tok;
+  int* kept;
+  float* logprob;
+  void* scratch;
+  int64_t scratch_bytes;
+} mq_sample_rows_args;
+int mq_sample_rows(const mq_sample_rows_args* args, mq_stream_t stream);
+/* One row's history [V] (as mq_sample_history_prompt): for each of the n ids in DEVICE memory the count in bits 0..15 moves by delta (+1 or
+ * -1), saturating at 65 535 and at 0; bit 31 is kept; an id outside [0, V) is ignored; repeated ids count repeatedly -- the result of
+ * applying them one by one.  One launch, capturable. */
+int mq_sample_history_count(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int delta, mq_stream_t stream);
 
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes

@@ -3,7 +3,7 @@
 Layout: csrc/ (HIP kernels + C ABI), _lib.py (ctypes binding), ops.py (tensor wrappers),
 quantization/ (the reference's qmodule API), calibration.py (generate_act_range counterpart).
 """
-from . import _lib, ops, scoring  # noqa: F401
+from . import _lib, ops, sampling, scoring  # noqa: F401
 from .decode import DecodeEngine, prompt_lookup_draft, spec_accept  # noqa: F401
 from .decode_batch import BatchDecodeEngine  # noqa: F401
 from .quantization import *  # noqa: F401,F403

@@ -104,6 +104,12 @@ class MqSamplePenalizedArgs(ctypes.Structure):
                 ("observe", c_int)]
 
 
+class MqSampleRowsArgs(ctypes.Structure):
+    _fields_ = [("logits", c_void_p), ("logits_stride", c_int64), ("V", c_int64), ("rows", c_int), ("n_base", c_void_p), ("n_offset", c_int),
+                ("params", c_void_p), ("penalty", c_void_p), ("bias", c_void_p), ("history", c_void_p), ("proposals", c_void_p),
+                ("tok", c_void_p), ("kept", c_void_p), ("logprob", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_int64)]
+
+
 class MqAttentionArgs(ctypes.Structure):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("seq", c_int),
                 ("heads", c_int), ("kv_heads", c_int), ("head_dim", c_int), ("inv_sqrt_d", c_float), ("qk_a", MqGrid),
@@ -204,6 +210,8 @@ _SIGNATURES = {
     "mq_sample_uniforms": (c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_int64, c_int64, _P, _P]),
     "mq_sample_penalized": (c_int, [POINTER(MqSamplePenalizedArgs), _P]),
     "mq_sample_history_prompt": (c_int, [_P, c_int64, _P, c_int64, c_int, _P]),
+    "mq_sample_rows": (c_int, [POINTER(MqSampleRowsArgs), _P]),
+    "mq_sample_history_count": (c_int, [_P, c_int64, _P, c_int64, c_int, _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

@@ -42,6 +42,21 @@
 // sample_select_penalized_kernel): step 0 is applied wherever a logit is loaded -- once for a row held in LDS, on every re-read of a longer
 // one -- reading 4 more bytes of history (8 with a bias) per entry; the history is never staged in LDS.  The thread that writes a row's
 // token then counts it in the row's history (observe).
+//
+// SEVERAL ROWS OF ONE SEQUENCE (mq_sample_rows).  T <= 8 logits rows of ONE sequence -- the rows of a multi-token step over
+// [t, d_1 .. d_(T-1)] -- under one request, one optional penalty row, one optional dense bias row and one optional history h[0..V); the
+// proposals d[0..T-2] (int64) and a base index are read from device memory.  Row j (0-based) is drawn at n_j = *n_base + n_offset + j.
+// Step 0 uses for row j the entry
+//      c_i(j) = min(65535, c_i + #{m < j : d[m] == i})   (bits 0..15)      seen_i(j) = (h_i != 0) or (c_i(j) > 0)      (bit 31 untouched)
+// i.e. the history on which d[0..j-1] were counted one after the other; an absent history is all zeros; a proposal outside [0, V) matches
+// no entry.  Everything else is the rule above, unchanged; there is no idle row: every row draws.  The history and the logits are not
+// written.  So tok[j] is what mq_sample draws for that row alone at n_j (a neutral request, with or without a history, keeps the bits of
+// its logits) and what mq_sample_penalized draws there from a history that has counted d[0..j-1].
+// The same two kernels with a third load policy, Rows (sample_scan_rows_kernel, sample_select_rows_kernel): a workgroup reads the at most
+// seven proposals in front of its row once, wave-uniform, and compares them with the 4-entry block index as the entries are loaded --
+// nothing more is staged in LDS and no pass over V is added.
+// mq_sample_history_count moves the counts of n ids by +1 or -1 (saturating at 65 535 and at 0, bit 31 kept, ids outside [0, V) ignored)
+// with one compare-and-swap loop per id: the result of applying them one by one, in any order.
 #include "mq_common.h"
 
 #include <limits.h>
@@ -167,6 +182,81 @@ struct Penalty {
   }
 };
 
+// mq_sample_rows: T rows of ONE sequence.  One request, penalty row, bias row and history for all rows; row j adds the proposals in front
+// of it to the history's counts as it reads them.
+struct RowsArgs {
+  const mq_sample_penalty_row* pen;   // one row, or nullptr (neutral)
+  const unsigned* hist;               // the sequence's history, or nullptr (all zeros)
+  const float* bias;                  // one dense row, or nullptr
+  const long long* prop;              // rows - 1 proposals
+  int V;
+  int n_offset;
+};
+
+constexpr int SM_MAX_PROPOSALS = MQ_DECODE_MAX_BATCH - 1;
+
+struct Rows {
+  const unsigned* h;
+  const float* b;
+  float r, a, f;
+  bool active;
+  int d[SM_MAX_PROPOSALS];        // the proposals in front of this row (wave-uniform), -1: none
+  __device__ __forceinline__ Rows(const RowsArgs& ra, int row) {
+    r = 1.f; a = 0.f; f = 0.f;
+    if (ra.pen) {
+      const mq_sample_penalty_row p = ra.pen[0];
+      r = (p.repetition > 0.f && p.repetition < __builtin_inff()) ? p.repetition : 1.f;
+      a = p.presence; f = p.frequency;
+    }
+    h = ra.hist;
+    b = ra.bias;
+    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral request keeps the bits of its logits, history or not
+#pragma unroll
+    for (int m = 0; m < SM_MAX_PROPOSALS; ++m) {
+      d[m] = -1;
+      if (active && m < row) {
+        const long long t = ra.prop[m];
+        if (t >= 0 && t < (long long)ra.V) d[m] = (int)t;
+      }
+    }
+  }
+  // Penalty::one on the entry (hv with `extra` in-flight occurrences added to its count)
+  __device__ __forceinline__ float one(float l, unsigned hv, unsigned extra, float bv) const {
+    const unsigned c = min(0xFFFFu, (hv & 0xFFFFu) + extra);
+    const float l1 = (hv != 0u || extra != 0u) ? (l > 0.f ? l / r : l * r) : l;
+    float t = f * (float)c;
+    t = t + (c > 0u ? a : 0.f);
+    const float l2 = l1 - t;
+    return b ? l2 + bv : l2;
+  }
+  __device__ __forceinline__ float4 load4(const float* __restrict__ row, int i) const {
+    const float4 l = *reinterpret_cast<const float4*>(row + i);
+    if (!active) return l;                                          // workgroup-uniform
+    const uint4 hv = h ? *reinterpret_cast<const uint4*>(h + i) : make_uint4(0u, 0u, 0u, 0u);
+    const float4 bv = b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    unsigned e0 = 0u, e1 = 0u, e2 = 0u, e3 = 0u;
+    const int blk = i >> 2;
+    bool hit = false;
+#pragma unroll
+    for (int m = 0; m < SM_MAX_PROPOSALS; ++m) hit = hit || (d[m] >> 2) == blk;      // (-1 >> 2 = -1: no block)
+    if (hit) {
+#pragma unroll
+      for (int m = 0; m < SM_MAX_PROPOSALS; ++m) {
+        e0 += d[m] == i ? 1u : 0u; e1 += d[m] == i + 1 ? 1u : 0u; e2 += d[m] == i + 2 ? 1u : 0u; e3 += d[m] == i + 3 ? 1u : 0u;
+      }
+    }
+    return make_float4(one(l.x, hv.x, e0, bv.x), one(l.y, hv.y, e1, bv.y), one(l.z, hv.z, e2, bv.z), one(l.w, hv.w, e3, bv.w));
+  }
+  __device__ __forceinline__ float load1(const float* __restrict__ row, int i) const {
+    if (!active) return row[i];
+    unsigned e = 0u;
+#pragma unroll
+    for (int m = 0; m < SM_MAX_PROPOSALS; ++m) e += d[m] == i ? 1u : 0u;
+    return one(row[i], h ? h[i] : 0u, e, b ? b[i] : 0.f);
+  }
+  __device__ __forceinline__ void observe(int) const {}               // the caller counts what it keeps (mq_sample_history_count)
+};
+
 // running best of z + g (greedy: z) over entries [lo, hi) of the row, 4 per thread and step; lo, hi multiples of 4
 template <class Pol>
 __device__ __forceinline__ Best scan_range(const float* __restrict__ row, int lo, int hi, const RowCfg& c, const Pol& p, int tid, int nthreads) {
@@ -213,6 +303,18 @@ __device__ __forceinline__ bool row_idle(const int* pos, int row, int cache_len,
   return *n < 0 || *n >= cache_len;
 }
 
+// Which index a row draws at and which request it reads.  mq_sample / mq_sample_penalized: pos[row] with the idle sentinel, params[row].
+// mq_sample_rows: *pos + n_offset + row, never idle, the one request.
+template <class PolArgs>
+__device__ __forceinline__ bool row_index(const PolArgs&, const int* pos, int row, int cache_len, int* n) { return row_idle(pos, row, cache_len, n); }
+__device__ __forceinline__ bool row_index(const RowsArgs& ra, const int* pos, int row, int, int* n) {
+  *n = pos[0] + ra.n_offset + row;
+  return false;
+}
+template <class PolArgs>
+__device__ __forceinline__ int request_of(const PolArgs&, int row) { return row; }
+__device__ __forceinline__ int request_of(const RowsArgs&, int) { return 0; }
+
 __device__ __forceinline__ void slice_bounds(int V, int S, int s, int* lo, int* hi) {
   const int len = ((V / 4 + S - 1) / S) * 4;
   *lo = min(V, s * len);
@@ -226,8 +328,8 @@ __device__ __forceinline__ void sample_scan(const float* __restrict__ logits, lo
   __shared__ int red_i[SM_SCAN_THREADS / 64];
   const int row = blockIdx.y, s = blockIdx.x, S = gridDim.x, tid = threadIdx.x;
   int n;
-  if (row_idle(pos, row, cache_len, &n)) return;                      // workgroup-uniform
-  const RowCfg c = row_cfg(params[row], n, V);
+  if (row_index(pa, pos, row, cache_len, &n)) return;                 // workgroup-uniform
+  const RowCfg c = row_cfg(params[request_of(pa, row)], n, V);
   if (c.filtered) return;
   const Pol p(pa, row);
   int lo, hi;
@@ -246,6 +348,12 @@ __global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_penalized_kernel(
                                                                                 const mq_sample_row* __restrict__ params, Best* __restrict__ part,
                                                                                 PenArgs pa) {
   sample_scan<Penalty>(logits, stride, V, pos, cache_len, params, part, pa);
+}
+
+__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_rows_kernel(const float* __restrict__ logits, long long stride, int V,
+                                                                           const int* __restrict__ n_base, const mq_sample_row* __restrict__ params,
+                                                                           Best* __restrict__ part, RowsArgs ra) {
+  sample_scan<Rows>(logits, stride, V, n_base, 0, params, part, ra);
 }
 
 // ---- launch 2 ------------------------------------------------------------------------------------------------------------------
@@ -381,8 +489,8 @@ __device__ __forceinline__ void sample_select(unsigned char* smem, const float* 
                                               float* __restrict__ logprob, const PolArgs& pa) {
   const int row = blockIdx.x, tid = threadIdx.x;
   int n;
-  if (row_idle(pos, row, cache_len, &n)) return;                      // workgroup-uniform: an idle row keeps its token and its history
-  const RowCfg c = row_cfg(params[row], n, V);
+  if (row_index(pa, pos, row, cache_len, &n)) return;                 // workgroup-uniform: an idle row keeps its token and its history
+  const RowCfg c = row_cfg(params[request_of(pa, row)], n, V);
   const Pol p(pa, row);
   Lds L;
   L.z = reinterpret_cast<float*>(smem);
@@ -514,6 +622,15 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_penalized_kernel(con
   sample_select<Penalty>(smem, logits, stride, V, S, lds_row, pos, cache_len, params, part, tok, kept, logprob, pa);
 }
 
+// mq_sample_rows: the rows of one sequence, each with the proposals in front of it counted as its entries are read
+__global__ __launch_bounds__(SM_THREADS) void sample_select_rows_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
+                                                                        const int* __restrict__ n_base, const mq_sample_row* __restrict__ params,
+                                                                        const Best* __restrict__ part, long long* __restrict__ tok, int* __restrict__ kept,
+                                                                        float* __restrict__ logprob, RowsArgs ra) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  sample_select<Rows>(smem, logits, stride, V, S, lds_row, n_base, 0, params, part, tok, kept, logprob, ra);
+}
+
 __global__ void history_clear_kernel(uint4* __restrict__ h, int n4) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n4) h[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -525,6 +642,23 @@ __global__ void history_mark_kernel(unsigned* __restrict__ h, int V, const long 
   if (j >= n) return;
   const long long t = ids[j];
   if (t >= 0 && t < V) atomicOr(&h[t], 0x80000000u);
+}
+
+// The count (bits 0..15) of every id moves by delta = +1 / -1, saturating at 65 535 / at 0; bit 31 stays.  One compare-and-swap loop per
+// id: repeated ids count repeatedly, and since every id moves its entry the same way the result is that of applying them one by one.
+__global__ void history_count_kernel(unsigned* __restrict__ h, int V, const long long* __restrict__ ids, long long n, int delta) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const long long t = ids[j];
+  if (t < 0 || t >= V) return;
+  unsigned old = h[t];
+  for (;;) {
+    const unsigned c = old & 0xFFFFu;
+    if (delta > 0 ? c == 0xFFFFu : c == 0u) return;
+    const unsigned seen = atomicCAS(&h[t], old, delta > 0 ? old + 1u : old - 1u);
+    if (seen == old) return;
+    old = seen;
+  }
 }
 
 __global__ void sample_uniforms_kernel(unsigned long long seed, unsigned long long stream, unsigned n, long long first, long long count,
@@ -541,7 +675,7 @@ size_t select_lds_bytes(int lds_row) {
   return (size_t)lds_row * 4 + (size_t)SM_BINS * 8 + 8 * 8 + 2 * SM_WAVES * 8 + (size_t)SM_BINS * 4 + 2 * SM_WAVES * 4;
 }
 
-PerDeviceOnce g_lds_set, g_lds_set_pen;
+PerDeviceOnce g_lds_set, g_lds_set_pen, g_lds_set_rows;
 
 int check_sample_args(const mq_sample_args* a, const char* who) {
   MQ_REQUIRE(a->logits && a->pos && a->params && a->tok && a->scratch,
@@ -560,16 +694,16 @@ int check_sample_args(const mq_sample_args* a, const char* who) {
   return MQ_OK;
 }
 
-// the two launches of mq_sample (pa == nullptr) and of mq_sample_penalized
-int launch_sample(const mq_sample_args* a, const PenArgs* pa, const char* who, mq_stream_t stream) {
+// the two launches of mq_sample (pa == ra == nullptr), of mq_sample_penalized (pa) and of mq_sample_rows (ra; a->pos is n_base)
+int launch_sample(const mq_sample_args* a, const PenArgs* pa, const RowsArgs* ra, const char* who, mq_stream_t stream) {
   const int V = (int)a->V;
   const int S = min(SM_MAX_SLICES, (V + SM_SLICE - 1) / SM_SLICE);
   const int lds_row = V <= SM_LDS_ROW ? V : 0;
   const size_t lds = select_lds_bytes(lds_row);
   const int dev = current_device();
-  PerDeviceOnce& once = pa ? g_lds_set_pen : g_lds_set;
+  PerDeviceOnce& once = ra ? g_lds_set_rows : pa ? g_lds_set_pen : g_lds_set;
   if (!once.done(dev)) {
-    const void* fn = pa ? (const void*)sample_select_penalized_kernel : (const void*)sample_select_kernel;
+    const void* fn = ra ? (const void*)sample_select_rows_kernel : pa ? (const void*)sample_select_penalized_kernel : (const void*)sample_select_kernel;
     MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_LDS_ROW)) == hipSuccess,
                "%s: hipFuncSetAttribute(%zu B LDS) failed", who, select_lds_bytes(SM_LDS_ROW));
     once.mark(dev);
@@ -579,13 +713,18 @@ int launch_sample(const mq_sample_args* a, const PenArgs* pa, const char* who, m
   long long* tok = reinterpret_cast<long long*>(a->tok);
   if (S > 1) {
     const dim3 grid((unsigned)S, (unsigned)a->rows);
-    if (pa)
+    if (ra)
+      sample_scan_rows_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->params, part, *ra);
+    else if (pa)
       sample_scan_penalized_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part, *pa);
     else
       sample_scan_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part);
     MQ_LAUNCH_CHECK(who);
   }
-  if (pa)
+  if (ra)
+    sample_select_rows_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->params, part, tok,
+                                                                         a->kept, a->logprob, *ra);
+  else if (pa)
     sample_select_penalized_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len,
                                                                               a->params, part, tok, a->kept, a->logprob, *pa);
   else
@@ -605,7 +744,7 @@ extern "C" {
 int mq_sample(const mq_sample_args* a, mq_stream_t stream) {
   MQ_REQUIRE(a != nullptr, "mq_sample: null argument block");
   if (const int rc = check_sample_args(a, "mq_sample")) return rc;
-  return launch_sample(a, nullptr, "mq_sample", stream);
+  return launch_sample(a, nullptr, nullptr, "mq_sample", stream);
 }
 
 int mq_sample_penalized(const mq_sample_penalized_args* a, mq_stream_t stream) {
@@ -618,7 +757,7 @@ int mq_sample_penalized(const mq_sample_penalized_args* a, mq_stream_t stream) {
              (long long)a->history_stride);
   MQ_REQUIRE(a->observe == 0 || a->observe == 1, "mq_sample_penalized: observe=%d must be 0 or 1", a->observe);
   const PenArgs pa{a->penalty, a->history, (long long)a->history_stride, a->bias, a->observe};
-  return launch_sample(&a->s, &pa, "mq_sample_penalized", stream);
+  return launch_sample(&a->s, &pa, nullptr, "mq_sample_penalized", stream);
 }
 
 int mq_sample_history_prompt(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int clear, mq_stream_t stream) {
@@ -636,6 +775,36 @@ int mq_sample_history_prompt(uint32_t* history, int64_t V, const int64_t* ids, i
   if (n > 0) {
     history_mark_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(history, (int)V, reinterpret_cast<const long long*>(ids), (long long)n);
     MQ_LAUNCH_CHECK("mq_sample_history_prompt");
+  }
+  return MQ_OK;
+}
+
+int mq_sample_rows(const mq_sample_rows_args* a, mq_stream_t stream) {
+  MQ_REQUIRE(a != nullptr, "mq_sample_rows: null argument block");
+  MQ_REQUIRE(a->n_base != nullptr, "mq_sample_rows: null pointer (n_base is required)");
+  // mq_sample's block over the same rows: its limits and alignments are this entry's (pos = n_base; no row is idle, cache_len is unused)
+  mq_sample_args s;
+  s.logits = a->logits; s.logits_stride = a->logits_stride; s.V = a->V; s.rows = a->rows;
+  s.pos = a->n_base; s.cache_len = 1; s.params = a->params; s.tok = a->tok; s.kept = a->kept; s.logprob = a->logprob;
+  s.scratch = a->scratch; s.scratch_bytes = a->scratch_bytes;
+  if (const int rc = check_sample_args(&s, "mq_sample_rows")) return rc;
+  MQ_REQUIRE(a->n_offset >= -(1 << 30) && a->n_offset <= (1 << 30), "mq_sample_rows: n_offset=%d outside [-2^30, 2^30]", a->n_offset);
+  MQ_REQUIRE(a->rows == 1 || a->proposals != nullptr, "mq_sample_rows: null pointer (proposals holds rows - 1 ids when rows > 1)");
+  MQ_REQUIRE(aligned(a->penalty, 16) && aligned(a->history, 16) && aligned(a->bias, 16) && aligned(a->proposals, 8),
+             "mq_sample_rows: penalty, history and bias must be 16-byte aligned, proposals 8-byte aligned");
+  const RowsArgs ra{a->penalty, a->history, a->bias, reinterpret_cast<const long long*>(a->proposals), (int)a->V, a->n_offset};
+  return launch_sample(&s, nullptr, &ra, "mq_sample_rows", stream);
+}
+
+int mq_sample_history_count(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int delta, mq_stream_t stream) {
+  MQ_REQUIRE(history != nullptr && aligned(history, 16), "mq_sample_history_count: history must be a 16-byte aligned pointer");
+  MQ_REQUIRE(V >= 4 && V % 4 == 0 && V <= (1 << 20), "mq_sample_history_count: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)V);
+  MQ_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "mq_sample_history_count: n=%lld outside [0, 2^31]", (long long)n);
+  MQ_REQUIRE(n == 0 || (ids != nullptr && aligned(ids, 8)), "mq_sample_history_count: ids must be an 8-byte aligned pointer when n > 0");
+  MQ_REQUIRE(delta == 1 || delta == -1, "mq_sample_history_count: delta=%d must be +1 or -1", delta);
+  if (n > 0) {
+    history_count_kernel<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(history, (int)V, reinterpret_cast<const long long*>(ids), (long long)n, delta);
+    MQ_LAUNCH_CHECK("mq_sample_history_count");
   }
   return MQ_OK;
 }

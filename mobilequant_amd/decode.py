@@ -32,7 +32,7 @@ from . import _lib, ops
 from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
                    MqDecodeGemvGroupedArgs, MqDecodeHeadBatchArgs, MqGrid)
 from .quantization import qmodule as Q
-from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
+from .sampling import RowsLaunch, SampleLaunch, SamplingParams, check_stream, history_count, validate_generate_args
 
 
 def _grid(q: Optional[Q.Quantizer], keep: list) -> MqGrid:
@@ -691,6 +691,7 @@ class DecodeEngine(_DecodeBase):
         self.graph_long = None
         self._sampler = None                                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
         self._sample_graphs = {}                             # (step variant, penalised) -> the captured sample + step graph, recorded on first use
+        self._rows_at = None                                 # (T, position behind it) of the last step_tokens call: what sample_rows may draw
         self._lower()
 
     @classmethod
@@ -727,6 +728,8 @@ class DecodeEngine(_DecodeBase):
         prefetch, prefetch_delay_us = self._prefetch
         self._rows = None         # T-row phases of step_tokens: lowered on first use, from the layers' images (_lower_rows)
         self._row_graphs = {}
+        self._row_sel = None      # mq_sample_rows over the T-row buffers (sample_rows): built on first use
+        self._row_sample_graphs = {}                         # (T, penalised) -> the captured rows step + selection graph
         self.oproj_images = []
         self._lower_model()
         t = _Target(self.x, self.qkv, self.attn_q, self.attn_part, self.attn_ticket, self.gate_q, self.k_cache, self.v_cache, nsplit=self.attn_splits)
@@ -796,6 +799,8 @@ class DecodeEngine(_DecodeBase):
         self.rgate = torch.zeros(R, s.ffn, dtype=torch.int8, device=dev)
         self.rlogits = torch.zeros(R, s.vocab, device=dev)
         self.rtok = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.rsel = torch.zeros(R, dtype=torch.int64, device=dev)                     # sample_rows: row j's drawn token
+        self._row_sel, self._row_sample_graphs = None, {}
         t = _Target(self.rx, self.rqkv, self.rattn_q, self.rpart, self.rticket, self.rgate, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
                     rows=R, attn="multi", v_chunked=self.v_transposed)
         with torch.no_grad():
@@ -827,13 +832,23 @@ class DecodeEngine(_DecodeBase):
         self.logits.copy_(self.rlogits[T - 1])
         self.pos.add_(T)
 
-    def _capture_rows(self, T: int):
-        """Record the T-row step (incl. self.logits <- its last row and the position advance) as a hipGraph.  The warm-up launch outside
-        the capture runs with the position at the cache_len sentinel: every attention row is idle, no cache byte changes."""
+    def _capture_rows(self, T: int, sel: Optional[RowsLaunch] = None):
+        """Record the T-row step (incl. self.logits <- its last row and the position advance) as a hipGraph; with sel, mq_sample_rows
+        over the rows behind it, in the same graph.  The warm-up launch outside the capture runs with the position at the cache_len
+        sentinel: every attention row is idle, no cache byte changes (the selection's own warm-up writes rsel only)."""
         self._set_rows(T)
         pos0 = self.pos.clone()
         self.pos.fill_(self.cache_len)
-        g = self._row_graphs[T] = self._record(lambda: self._launch_rows(T), lambda: self._finish_rows(T))
+        if sel is None:
+            g = self._row_graphs[T] = self._record(lambda: self._launch_rows(T), lambda: self._finish_rows(T))
+        else:
+            with torch.cuda.device(self.dev):
+                sel.launch(T)                                  # outside the capture: the select kernel's LDS ceiling
+
+            def finish():
+                self._finish_rows(T)
+                sel.launch(T)
+            g = self._row_sample_graphs[(T, self._sampler.penalized)] = self._record(lambda: self._launch_rows(T), finish)
         self.pos.copy_(pos0)
         return g
 
@@ -844,24 +859,66 @@ class DecodeEngine(_DecodeBase):
         after the earlier tokens, and the caches end as those T steps leave them.  The position advances by T; self.logits holds the
         last row.  After capture() a graph per row count is recorded on first use and replayed; the uncaptured launches give the same
         bits.  Raises if p + T > cache_len."""
+        return self._step_rows(tokens, False, "step_tokens")
+
+    def _step_rows(self, tokens: Sequence[int], select: bool, who: str) -> torch.Tensor:
         t = [int(v) for v in tokens]
         T = len(t)
         if not 1 <= T <= self.max_rows:
-            raise ValueError(f"DecodeEngine.step_tokens: {T} tokens outside 1..{self.max_rows} (max_rows)")
+            raise ValueError(f"DecodeEngine.{who}: {T} tokens outside 1..{self.max_rows} (max_rows)")
         if self._host_pos + T > self.cache_len:
-            raise RuntimeError(f"DecodeEngine.step_tokens: {T} tokens at position {self._host_pos} overflow the KV cache ({self.cache_len} positions)")
+            raise RuntimeError(f"DecodeEngine.{who}: {T} tokens at position {self._host_pos} overflow the KV cache ({self.cache_len} positions)")
         if self._rows is None:
             self._lower_rows()
+        sel = self._row_launch() if select else None
         self.rtok[:T].copy_(torch.tensor(t, dtype=torch.int64), non_blocking=False)
         if self.graph is not None:
-            (self._row_graphs.get(T) or self._capture_rows(T)).replay()
+            if select:
+                (self._row_sample_graphs.get((T, self._sampler.penalized)) or self._capture_rows(T, sel)).replay()
+            else:
+                (self._row_graphs.get(T) or self._capture_rows(T)).replay()
         else:
             self._set_rows(T)
             with torch.cuda.device(self.dev):
                 self._launch_rows(T)
-            self._finish_rows(T)
+                self._finish_rows(T)
+                if select:
+                    sel.launch(T)
         self._host_pos += T
-        return self.rlogits[:T]
+        self._rows_at = (T, self._host_pos)
+        return self.rsel[:T] if select else self.rlogits[:T]
+
+    def _row_launch(self) -> RowsLaunch:
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        if self._rows is None:
+            self._lower_rows()
+        if self._row_sel is None:
+            self._row_sel = RowsLaunch(self._sampler, self.rlogits, self.pos, self.rtok[1:], self.rsel)
+        return self._row_sel
+
+    @torch.no_grad()
+    def sample_rows(self, T: int) -> torch.Tensor:
+        """mq_sample_rows on the T rows of the last step_tokens call, under the request of set_sampling (greedy until
+        one is set): returns a device tensor [T] (overwritten by the next call; no host read) whose entry j is the token plain sampling
+        draws at index position() - T + 1 + j from row j -- the token that follows tokens[:j + 1] of that call.  Under a penalised
+        request row j sees the sequence's history plus tokens[1:j + 1], the proposals in front of it (read from the engine's own
+        row-token buffer); the history is not written: count what is kept with sampling.history_count.  T must be that call's row
+        count, with the position still behind it."""
+        T = int(T)
+        if self._rows_at != (T, self._host_pos):
+            raise RuntimeError(f"DecodeEngine.sample_rows: T={T} is not the row count of a step_tokens call that the position ({self._host_pos}) "
+                               f"still stands behind")
+        with torch.cuda.device(self.dev):
+            self._row_launch().launch(T)
+        return self.rsel[:T]
+
+    @torch.no_grad()
+    def step_sample_tokens(self, tokens: Sequence[int]) -> torch.Tensor:
+        """step_tokens(tokens) and sample_rows(len(tokens)): returns the drawn tokens [T] (device).  After capture() the rows step and
+        the selection are ONE graph per (T, penalised), recorded on first use like the sample + step graphs; the uncaptured launches
+        give the same bits.  step_tokens' logits rows are in self.rlogits[:T]."""
+        return self._step_rows(tokens, True, "step_sample_tokens")
 
     @torch.no_grad()
     def extend(self, tokens: Sequence[int]) -> torch.Tensor:
@@ -940,6 +997,7 @@ class DecodeEngine(_DecodeBase):
         if self._keep.stale():
             self._lower()
         self._row_graphs = {}                                    # (multi-token steps: one graph per row count, recorded on first use)
+        self._row_sample_graphs = {}                             # (rows step + mq_sample_rows: one graph per row count and selection kind)
         self._sample_graphs = {}                                 # (sample + step: one graph per step variant and selection entry, recorded on first use)
         tok0, pos0, hp0 = self.tok.clone(), self.pos.clone(), self._host_pos
         graphs = []
@@ -958,6 +1016,7 @@ class DecodeEngine(_DecodeBase):
         assert 0 <= int(pos) <= self.cache_len
         self.pos.fill_(int(pos))
         self._host_pos = int(pos)
+        self._rows_at = None
 
     def cached_values(self, li: int, n: Optional[int] = None) -> torch.Tensor:
         """Layer li's cached values as [kv_heads, n positions, head_dim] int8 indices (index - 128), whatever the engine's layout."""
@@ -1016,6 +1075,7 @@ class DecodeEngine(_DecodeBase):
                 self._launch(phases)
             self.pos.add_(1)
         self._host_pos += 1
+        self._rows_at = None
         return self.logits
 
     # -- seeded token selection on the device (csrc/mq_sample.hip) ---------------------------------------------
@@ -1081,6 +1141,7 @@ class DecodeEngine(_DecodeBase):
         key = (self._variant_at(self._host_pos), self._sampler.penalized)      # a request of the other kind records a graph of its own
         (self._sample_graphs.get(key) or self._capture_sample_step(*key)).replay()
         self._host_pos += 1
+        self._rows_at = None
         return self.logits
 
     @torch.no_grad()
@@ -1273,6 +1334,105 @@ class DecodeEngine(_DecodeBase):
             if d_eng is not None and d_pos > len(out):             # the draft keeps out + the accepted proposals it had cached
                 d_pos = min(d_pos, len(out) + acc)
                 d_eng.rewind(d_pos)
+            out += new
+            made += len(new)
+            if stop:
+                return out
+
+    @torch.no_grad()
+    def generate_speculative(self, context_ids, max_new_tokens: int, draft, *, sampling: SamplingParams, stream: int = 0, num_draft: int = 4,
+                             eos_token_id=None, prefill: bool = True):
+        """Speculative decoding under seeded sampling: returns, token for token, the ids of
+        generate(context_ids, max_new_tokens, sampling=sampling, stream=stream, ...).  Token n of a sequence is a function of its logits,
+        the request, the stream and n alone, so no rejection scheme is needed: the first token comes from sample(); then per round, with t
+        the last token (not yet cached) and P the position, k proposals (k bounded as in the greedy path), ONE step_tokens([t, d1..dk])
+        with mq_sample_rows drawing every row at its own index (one graph after capture()), one read-back of the T tokens, spec_accept
+        on them and rewind to P + the kept tokens; under a penalised request row j sees the history plus d1..dj, and the kept tokens are
+        then counted with history_count(+1).  draft: another DecodeEngine of the same vocabulary size, or a callable draft(ids, k).  An
+        engine draft is set to the SAME sampling and stream and proposes with its own sample_step() / sample(): it shares the Gumbel
+        noise with the target, so it is accepted wherever its logits are close (a self-draft: always); its history is brought back to
+        the sequence's with history_count (-1 for the rejected proposals, +1 for the token that replaced them and for the first token),
+        its cache with extend / rewind.  self.spec_stats counts the rounds.  Afterwards the caches hold out[:position()]."""
+        if not isinstance(sampling, SamplingParams):
+            raise TypeError(f"DecodeEngine.generate_speculative: sampling must be SamplingParams, got {type(sampling).__name__}")
+        stream = check_stream(stream)
+        d_eng = draft if isinstance(draft, DecodeEngine) else None
+        if d_eng is self:
+            raise ValueError("DecodeEngine.generate_speculative: the draft must be another engine (it keeps its own cache)")
+        if d_eng is None and not callable(draft):
+            raise TypeError("DecodeEngine.generate_speculative: draft must be a DecodeEngine or a callable draft(ids, k) -> list of token ids")
+        if isinstance(num_draft, bool) or int(num_draft) < 0:
+            raise ValueError(f"DecodeEngine.generate_speculative: num_draft={num_draft} must be >= 0")
+        if d_eng is not None and d_eng.shape.vocab != self.shape.vocab:
+            raise ValueError(f"DecodeEngine.generate_speculative: draft vocabulary {d_eng.shape.vocab} != target vocabulary {self.shape.vocab}")
+        ids = [int(t) for t in context_ids]
+        assert len(ids) + max_new_tokens <= self.cache_len
+        eos = _eos_set(eos_token_id)
+        stats = self.spec_stats = {"rounds": 0, "proposed": 0, "accepted": 0, "target_steps": 0}
+        self.set_sampling(sampling, stream)
+        self._start_sequence(ids, prefill)
+        penalized = self._sampler.penalized
+        if penalized:
+            self._sampler.observe_prompt(0, ids)                   # the history is rebuilt for every sequence
+        out = list(ids)
+        if max_new_tokens <= 0:
+            return out
+        dev_ids = lambda v: torch.tensor(v, dtype=torch.int64, device=self.dev)      # noqa: E731
+        d_pos = 0                                                  # the draft engine's cache holds out[:d_pos]
+        if d_eng is not None:
+            d_eng.set_sampling(sampling, stream)
+            d_eng._start_sequence(ids, prefill)
+            d_pos = len(ids)
+            if penalized:
+                d_eng._sampler.observe_prompt(0, ids)
+            d_buf = torch.zeros(self.max_rows, dtype=torch.int64, device=d_eng.dev)
+        self.sample()                                              # token len(ids), counted in the history by the launch itself
+        nxt = int(self.tok.item())
+        out.append(nxt)
+        made = 1
+        if d_eng is not None and penalized:
+            history_count(d_eng._sampler.history[0], dev_ids([nxt]).to(d_eng.dev), 1)
+        if nxt in eos or made >= max_new_tokens or self._host_pos >= self.cache_len:
+            return out
+        while True:
+            P = self._host_pos
+            k = max(0, min(int(num_draft), self.max_rows - 1, max_new_tokens - made - 1, self.cache_len - P - 1))
+            props: List[int] = []
+            if k > 0 and d_eng is not None:
+                kd = min(k, d_eng.cache_len - len(out))             # (its last draw, at index len(out) + kd - 1, must not be an idle row)
+                if kd > 0:
+                    d_eng.extend(out[d_pos:])                      # its logits: behind out, the row token len(out) is drawn from
+                    for i in range(kd):                            # d(i+1) at index len(out) + i, counted in the draft's own history
+                        if i < kd - 1:
+                            d_eng.sample_step()
+                        else:
+                            d_eng.sample()
+                        d_buf[i:i + 1].copy_(d_eng.tok)
+                    props = d_buf[:kd].tolist()
+                    d_pos = len(out) + kd - 1                      # out + props[:-1]
+            elif k > 0:
+                props = [int(v) for v in draft(list(out), k)][:k]
+            T = 1 + len(props)
+            drawn = self.step_sample_tokens([out[-1]] + props).tolist()      # ONE read-back of the T tokens
+            new, acc, stop = spec_accept(drawn, props, eos, budget=max_new_tokens - made, room=self.cache_len - P)
+            stats["rounds"] += 1
+            stats["target_steps"] += 1
+            stats["proposed"] += len(props)
+            stats["accepted"] += acc
+            self.rewind(P + len(new))                              # t and the accepted proposals stay cached
+            self.logits.copy_(self.rlogits[len(new) - 1])
+            if penalized:
+                history_count(self._sampler.history[0], dev_ids(new), 1)
+            if d_eng is not None:
+                if penalized:                                      # the draft counted every proposal: back to the sequence's truth, out + new
+                    h = d_eng._sampler.history[0]
+                    if props[acc:]:
+                        history_count(h, dev_ids(props[acc:]).to(d_eng.dev), -1)
+                    if new[acc:]:
+                        history_count(h, dev_ids(new[acc:]).to(d_eng.dev), 1)
+                if d_pos > len(out):                               # the draft keeps out + the accepted proposals it had cached
+                    d_pos = min(d_pos, len(out) + acc)
+                    d_eng.rewind(d_pos)
             out += new
             made += len(new)
             if stop:

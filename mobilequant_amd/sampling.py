@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MQ_SAMPLE_SCRATCH_BYTES, MqSampleArgs, MqSamplePenalizedArgs
+from ._lib import MQ_SAMPLE_SCRATCH_BYTES, MqSampleArgs, MqSamplePenalizedArgs, MqSampleRowsArgs
 
 MAX_ROWS = 8
 MAX_VOCAB = 1 << 20
@@ -137,6 +137,32 @@ def history_prompt(history_row: torch.Tensor, ids, clear: bool = True):
                   torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _history_row(history_row, who: str) -> torch.Tensor:
+    if not isinstance(history_row, torch.Tensor) or history_row.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
+            or history_row.dim() != 1 or not history_row.is_contiguous():
+        raise RuntimeError(f"mobilequant_amd: {who} history must be one contiguous int32 (uint32 bits) row [V]")
+    if not history_row.is_cuda:
+        raise RuntimeError(f"mobilequant_amd: {who} history must be a ROCm device tensor; there is no CPU path")
+    return history_row
+
+
+def history_count(history_row: torch.Tensor, ids: torch.Tensor, delta: int):
+    """mq_sample_history_count on one row's history ([V] int32 device tensor holding the uint32 entries): the count (bits 0..15) of every
+    id in `ids` (an int64 device tensor, any number; ids repeat) moves by delta = +1 or -1, saturating at 65 535 and at 0.  Bit 31 is kept
+    and an id outside [0, V) is ignored on the device: no id is read on the host.  One launch, capturable."""
+    if isinstance(delta, bool) or delta not in (1, -1):
+        raise ValueError(f"mobilequant_amd: history_count delta={delta!r} must be +1 or -1")
+    h = _history_row(history_row, "history_count")
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous():
+        raise RuntimeError("mobilequant_amd: history_count ids must be a contiguous int64 [n] tensor")
+    if ids.device != h.device:
+        raise RuntimeError("mobilequant_amd: history_count ids must be a ROCm device tensor on the history's device")
+    with torch.cuda.device(h.device):
+        _lib.call("mq_sample_history_count", h.data_ptr(), h.numel(), ids.data_ptr() if ids.numel() else None, ids.numel(), int(delta),
+                  torch.cuda.current_stream(h.device).cuda_stream)
+    return history_row
+
+
 class SampleLaunch:
     """mq_sample over an engine's own buffers: logits [rows, V] -> tok [rows] at the positions in pos [rows].  The per-row requests
     live in a device array that set_rows() rewrites in place, so a captured launch serves any request.
@@ -217,6 +243,41 @@ class SampleLaunch:
             _lib.call("mq_sample_penalized", ctypes.byref(self.pargs), st)
         else:
             _lib.call("mq_sample", ctypes.byref(self.args), st)
+
+
+class RowsLaunch:
+    """mq_sample_rows over an engine's multi-token step: rows logits [R, V] of ONE sequence -> out [R], row j drawn at
+    *pos + n_offset + j under the single request of `sampler` (a one-row SampleLaunch: its device request, penalty row, bias row and
+    history are read in place, so a captured launch serves any request of the same kind).  proposals: the int64 device ids in front of
+    rows 1 .. R - 1.  One argument block per (row count, penalised): a penalised block names the sampler's penalty row, its history and
+    its dense bias row (zeros without a logit_bias: adding +0 leaves every z of the rule as it is)."""
+
+    def __init__(self, sampler: "SampleLaunch", logits: torch.Tensor, pos: torch.Tensor, proposals: torch.Tensor, out: torch.Tensor):
+        if sampler.rows != 1:
+            raise ValueError("sampling: RowsLaunch serves one sequence (a one-row SampleLaunch)")
+        self.sampler, self.logits, self.pos, self.proposals, self.out = sampler, logits, pos, proposals, out
+        self.scratch = torch.zeros(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=logits.device)
+        self._args = {}
+
+    def args(self, T: int, penalized: bool) -> MqSampleRowsArgs:
+        a = self._args.get((T, penalized))
+        if a is None:
+            s, lg = self.sampler, self.logits
+            a = MqSampleRowsArgs()
+            a.logits, a.logits_stride, a.V, a.rows = lg.data_ptr(), lg.stride(0), lg.shape[1], T
+            a.n_base, a.n_offset, a.params = self.pos.data_ptr(), 1 - T, s.params.data_ptr()
+            a.proposals = self.proposals.data_ptr() if T > 1 else None
+            a.tok, a.kept, a.logprob = self.out.data_ptr(), None, None
+            a.scratch, a.scratch_bytes = self.scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+            if penalized:
+                a.penalty, a.history, a.bias = s.penalty.data_ptr(), s.history[0].data_ptr(), s.bias[0].data_ptr()
+            self._args[(T, penalized)] = a
+        return a
+
+    def launch(self, T: int):
+        """On the current stream (capturable).  Reads the position BEHIND the T-row step: row j draws at pos - T + 1 + j."""
+        a = self.args(T, self.sampler.penalized)
+        _lib.call("mq_sample_rows", ctypes.byref(a), torch.cuda.current_stream(self.logits.device).cuda_stream)
 
 
 def validate_generate_args(who: str, sampling, do_sample: bool, draft=None):
@@ -306,6 +367,66 @@ def sample(logits: torch.Tensor, pos: torch.Tensor, params_rows, tok: torch.Tens
     p.bias, p.observe = (bias_ptr.data_ptr() if bias_ptr is not None else None), int(bool(observe))
     with _on(logits, pos, pr, tok):
         _lib.call("mq_sample_penalized", ctypes.byref(p), _stream())
+    return tok
+
+
+def sample_rows(logits: torch.Tensor, n_base: torch.Tensor, n_offset: int, params: SamplingParams, stream: int, tok: torch.Tensor, *,
+                proposals: Optional[torch.Tensor] = None, history: Optional[torch.Tensor] = None, penalties=None,
+                bias: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mq_sample_rows: logits [rows, V] fp32 (row stride >= V), the rows of ONE sequence, under the single request
+    (params, stream).  Row j is drawn at n_base[0] + n_offset + j (n_base: an int32 device tensor of one entry) into tok [rows] int64
+    (written in place, returned); kept [rows] int32 / logprob [rows] fp32: optional outputs.  proposals: int64 device tensor of the
+    rows - 1 ids in front of rows 1 .. rows - 1 (required when rows > 1).  history: None or one int32 (uint32 bits) row [>= V] shared by
+    the rows; penalties: None (params' own), a SamplingParams or (repetition, presence, frequency); bias: None or a dense fp32 [>= V]
+    device row.  Row j sees the history with proposals[:j] counted; nothing but the outputs is written."""
+    from .ops import _dev, _on, _stream
+    if isinstance(logits, torch.Tensor) and logits.dim() == 1:
+        logits = logits.view(1, -1)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise RuntimeError("mobilequant_amd: sample_rows logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    if not 1 <= rows <= MAX_ROWS:
+        raise RuntimeError(f"mobilequant_amd: sample_rows rows={rows} outside 1..{MAX_ROWS}")
+    if not isinstance(params, SamplingParams):
+        raise TypeError(f"mobilequant_amd: sample_rows expected SamplingParams, got {type(params).__name__}")
+    if isinstance(n_offset, bool) or not isinstance(n_offset, (int, np.integer)) or not -2 ** 30 <= int(n_offset) <= 2 ** 30:
+        raise ValueError(f"mobilequant_amd: sample_rows n_offset={n_offset!r} must be an int in [-2^30, 2^30]")
+    host = pack_rows([params], [stream])
+    _dev(logits, "sample_rows logits")
+    pr = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(logits.device)
+    for t, dt, n, what in ((n_base, torch.int32, 1, "n_base"), (tok, torch.int64, rows, "tok"), (kept, torch.int32, rows, "kept"),
+                           (logprob, torch.float32, rows, "logprob"), (proposals, torch.int64, rows - 1, "proposals")):
+        if t is None:
+            if what in ("n_base", "tok") or (what == "proposals" and rows > 1):
+                raise RuntimeError(f"mobilequant_amd: sample_rows needs {what} ({dt} [{n}])")
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: sample_rows {what} must be contiguous {dt} [{n}]")
+        _dev(t, "sample_rows " + what)
+    if history is not None:
+        if not isinstance(history, torch.Tensor) or history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 1 or history.numel() < V \
+                or not history.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: sample_rows history must be one contiguous int32 (uint32 bits) row [>= {V}]")
+        _dev(history, "sample_rows history")
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() < V or not bias.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: sample_rows bias must be a contiguous fp32 [>= {V}] tensor")
+        _dev(bias, "sample_rows bias")
+    pen_src = params if penalties is None else penalties
+    pen = torch.from_numpy(pack_penalty_rows([pen_src]).view(np.uint8).reshape(-1)).to(logits.device)
+    a = MqSampleRowsArgs()
+    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=logits.device)
+    a.logits, a.logits_stride, a.V, a.rows = logits.data_ptr(), logits.stride(0) if rows > 1 else max(V, logits.stride(0)), V, rows
+    a.n_base, a.n_offset, a.params, a.penalty = n_base.data_ptr(), int(n_offset), pr.data_ptr(), pen.data_ptr()
+    a.bias = bias.data_ptr() if bias is not None else None
+    a.history = history.data_ptr() if history is not None else None
+    a.proposals = proposals.data_ptr() if proposals is not None and rows > 1 else None
+    a.tok = tok.data_ptr()
+    a.kept = kept.data_ptr() if kept is not None else None
+    a.logprob = logprob.data_ptr() if logprob is not None else None
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+    with _on(logits, n_base, pr, tok):
+        _lib.call("mq_sample_rows", ctypes.byref(a), _stream())
     return tok
 
 
