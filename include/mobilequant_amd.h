@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -626,6 +626,38 @@ typedef struct mq_decode_attention_multi_args {
   int v_chunked;
 } mq_decode_attention_multi_args;
 int mq_decode_attention_multi(const mq_decode_attention_multi_args* args, mq_stream_t stream);
+
+/* ---- ragged rows: each attention row a (sequence, position) of a batch of caches, consecutive rows of one sequence seeing each other
+ * (multi-token steps per slot of the batched engine, batched speculative verification) --------------------------------- */
+/* mq_decode_attention for `rows` table rows over `batch` caches: grid (heads, a.nsplit, rows).  row_seq / row_pos are DEVICE arrays of
+ * `rows` ints; a.pos is not read.  The caches are [batch][kv_heads][cache_len][head_dim] as for mq_decode_attention_batch (flat value
+ * layout).  Row r reads qkv + r * qkv_stride floats, writes out / out_q + r * heads * head_dim, and uses the split scratch part + r *
+ * nsplit * heads * head_dim and ticket + r * heads.
+ * Runs: a run is a maximal stretch of consecutive rows with equal row_seq whose row_pos rise by exactly one.  The kernel derives on
+ * the device the distance j of row r from its run's first row; with p = row_pos[r] - j it forms the keys and values of rows r - j .. r in
+ * LDS, reads no position >= p from memory, appends row r's own position, and adds the run's positions to p.v through the split that
+ * owns their 64-position block (mq_decode_attention_multi at that sequence's cache, position p, row j).
+ * Idle rows: a row with row_seq[r] outside [0, batch) or row_pos[r] outside [0, cache_len) reads and writes nothing, and ends a run.
+ * The table is device data and cannot be validated by this entry: the kernel stays inside its buffers whatever the table holds.
+ * CALLER'S CONTRACT: a sequence appears in at most ONE run per launch (two runs on one sequence would race on its cache).
+ * Contract:
+ *   - row r's out / out_q equal, bit for bit, what mq_decode_attention_batch at batch 1 computes at row_pos[r] over that sequence's
+ *     cache once it holds the run's earlier rows (the split count chosen on the device from split_from; exact integer p.v sums);
+ *   - after the launch every named position holds exactly the bytes sequential single-position launches would have written;
+ *   - no other byte of any cache changes -- sequences the table does not name included.
+ * Limits (MQ_EINVAL with a message, before any HIP call): a null block, rows / batch outside 1 .. MQ_DECODE_MAX_BATCH, null tables,
+ * mq_decode_attention_batch's shape and grids, no prefetch rows, qkv_stride covers a q | k | v row, nsplit > 1 needs part and
+ * ticket, cache_len <= 32768 (4 bytes of LDS per cached position plus <= 13 KiB static, as mq_decode_attention_multi). */
+typedef struct mq_decode_attention_ragged_args {
+  mq_decode_attention_args a;
+  int rows;  /* 1 .. MQ_DECODE_MAX_BATCH */
+  int batch; /* sequences in the caches, 1 .. MQ_DECODE_MAX_BATCH */
+  int split_from;
+  int64_t qkv_stride;
+  const int* row_seq; /* [rows], device */
+  const int* row_pos; /* [rows], device */
+} mq_decode_attention_ragged_args;
+int mq_decode_attention_ragged(const mq_decode_attention_ragged_args* args, mq_stream_t stream);
 
 /* ---- a10: quantized causal attention at prefill (hf_model.py:486-534 with the two QMatMuls of qmodule.py:453-466) ------------ */
 /* One sequence.  q [seq, heads*D], k / v [seq, kv_heads*D] fp32 = the q / k / v projection outputs BEFORE RoPE; cos / sin [seq, D]

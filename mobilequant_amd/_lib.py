@@ -75,6 +75,11 @@ class MqDecodeAttentionMultiArgs(ctypes.Structure):
     _fields_ = [("a", MqDecodeAttentionArgs), ("rows", c_int), ("split_from", c_int), ("qkv_stride", c_int64), ("v_chunked", c_int)]
 
 
+class MqDecodeAttentionRaggedArgs(ctypes.Structure):
+    _fields_ = [("a", MqDecodeAttentionArgs), ("rows", c_int), ("batch", c_int), ("split_from", c_int), ("qkv_stride", c_int64),
+                ("row_seq", c_void_p), ("row_pos", c_void_p)]
+
+
 class MqDecodeHeadBatchArgs(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("x_stride", c_int64), ("norm_weight", c_void_p), ("norm_bias", c_void_p), ("layernorm", c_int),
                 ("eps", c_float), ("w", c_void_p), ("bias", c_void_p), ("K", c_int64), ("V", c_int64), ("batch", c_int),
@@ -201,6 +206,7 @@ _SIGNATURES = {
     "mq_decode_gemv_grouped": (c_int, [POINTER(MqDecodeGemvGroupedArgs), _P]),
     "mq_decode_head_batch": (c_int, [POINTER(MqDecodeHeadBatchArgs), _P]),
     "mq_decode_attention_multi": (c_int, [POINTER(MqDecodeAttentionMultiArgs), _P]),
+    "mq_decode_attention_ragged": (c_int, [POINTER(MqDecodeAttentionRaggedArgs), _P]),
     "mq_attention_quant": (c_int, [POINTER(MqAttentionArgs), _P]),
     "mq_attention_cache_import": (c_int, [POINTER(MqAttentionCacheArgs), _P]),
     "mq_attention_cache_export": (c_int, [POINTER(MqAttentionCacheArgs), _P]),

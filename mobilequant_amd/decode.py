@@ -24,12 +24,12 @@ recorded by ``_DecodeBase._record``.
 from __future__ import annotations
 
 import ctypes
-from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _lib, ops
-from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
+from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeAttentionRaggedArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
                    MqDecodeGemvGroupedArgs, MqDecodeHeadBatchArgs, MqGrid)
 from .quantization import qmodule as Q
 from .sampling import RowsLaunch, SampleLaunch, SamplingParams, check_stream, history_count, validate_generate_args
@@ -253,6 +253,63 @@ def prompt_lookup_draft(ngram: int = 3) -> Callable[[List[int], int], List[int]]
     return draft
 
 
+class RowPlan(NamedTuple):
+    """A ragged step as the launches read it (plan_rows): row r is token row_tok[r] of slot row_seq[r] at position row_pos[r]; spans[slot]
+    = (first row, row count) of the slot's run."""
+    row_seq: List[int]
+    row_pos: List[int]
+    row_tok: List[int]
+    spans: Dict[int, Tuple[int, int]]
+
+
+def plan_rows(tokens: Mapping[int, Sequence[int]], positions: Sequence[Optional[int]], max_rows: int, cache_len: int,
+              who: str = "BatchDecodeEngine.step_tokens") -> RowPlan:
+    """The row table of one ragged step (BatchDecodeEngine.step_tokens), host only.  tokens: slot -> its tokens; positions[slot]: the
+    slot's cached positions, None for an idle slot.  Rows are laid out in ascending slot order, a slot's rows contiguous at consecutive
+    positions from its own: each slot is ONE run of mq_decode_attention_ragged, which is what that launch asks of its caller.
+    ValueError: a slot outside 0 .. len(positions) - 1, an empty token list, a total outside 1 .. max_rows.  RuntimeError: an idle
+    slot, or tokens that would overflow the slot's cache."""
+    B = len(positions)
+    plan = {}
+    for slot, toks in tokens.items():
+        if isinstance(slot, bool) or int(slot) != slot or not 0 <= int(slot) < B:
+            raise ValueError(f"{who}: slot {slot!r} outside 0..{B - 1}")
+        if int(slot) in plan:
+            raise ValueError(f"{who}: slot {int(slot)} is named twice")
+        plan[int(slot)] = [int(v) for v in toks]
+        if not plan[int(slot)]:
+            raise ValueError(f"{who}: slot {int(slot)} has no tokens (leave a slot that does not move out of the mapping)")
+    total = sum(len(t) for t in plan.values())
+    if not 1 <= total <= max_rows:
+        raise ValueError(f"{who}: {total} rows outside 1..{max_rows} (max_rows)")
+    out = RowPlan([], [], [], {})
+    for slot in sorted(plan):
+        t, P = plan[slot], positions[slot]
+        if P is None:
+            raise RuntimeError(f"{who}: slot {slot} is idle (prefill() or start() it first)")
+        if P + len(t) > cache_len:
+            raise RuntimeError(f"{who}: {len(t)} tokens at position {P} overflow slot {slot}'s KV cache ({cache_len} positions)")
+        out.spans[slot] = (len(out.row_tok), len(t))
+        out.row_seq.extend([slot] * len(t))
+        out.row_pos.extend(range(P, P + len(t)))
+        out.row_tok.extend(t)
+    return out
+
+
+def spec_row_budget(num_draft: int, max_rows: int, allowed: Sequence[int], room: Sequence[int]) -> List[int]:
+    """Proposals per live slot of one batched speculative round (BatchDecodeEngine.generate with a draft), host only.  The L = len(allowed)
+    live slots share the step's max_rows rows evenly, one of each share being the slot's last token: k_i = min(num_draft, max_rows // L
+    - 1, allowed[i] - 1, room[i] - 1), at least 0, where allowed[i] is the new tokens slot i may still return and room[i] the cache
+    positions behind its last cached one (spec_accept's budget and room).  With max_rows // L <= 1 (eight live slots of eight rows)
+    every k_i is 0: plain steps.  While L <= max_rows the rows L + sum(k) never exceed max_rows."""
+    L = len(allowed)
+    if len(room) != L:
+        raise ValueError(f"spec_row_budget: {L} budgets for {len(room)} cache rooms")
+    if int(num_draft) < 0:
+        raise ValueError(f"spec_row_budget: num_draft={num_draft} must be >= 0")
+    return [max(0, min(int(num_draft), int(max_rows) // L - 1, int(a) - 1, int(r) - 1)) for a, r in zip(allowed, room)]
+
+
 def _eos_set(eos_token_id) -> set:
     """generate's eos_token_id (None, one id or several) as a set."""
     return set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
@@ -276,8 +333,9 @@ class _Images(NamedTuple):
 class _Target(NamedTuple):
     """Where a layer's chain reads and writes: data, not the engine that asks.  rows None: one row, bare records; else every record is
     wrapped for `rows` rows of these buffers (mq_decode_gemv_batch / _grouped).  attn: how the attention record is wrapped -- None
-    (bare), "batch" (a sequence per row, mq_decode_attention_batch) or "multi" (consecutive positions of one sequence,
-    mq_decode_attention_multi; v_chunked: the four-launch value layout)."""
+    (bare), "batch" (a sequence per row, mq_decode_attention_batch), "multi" (consecutive positions of one sequence,
+    mq_decode_attention_multi; v_chunked: the four-launch value layout) or "ragged" (row r the position row_pos[r] of sequence
+    row_seq[r] of the `batch` sequences in the caches, mq_decode_attention_ragged)."""
     x: torch.Tensor
     qkv: torch.Tensor
     attn_q: torch.Tensor
@@ -290,6 +348,9 @@ class _Target(NamedTuple):
     rows: Optional[int] = None
     attn: Optional[str] = None
     v_chunked: bool = False
+    batch: Optional[int] = None
+    row_seq: Optional[torch.Tensor] = None
+    row_pos: Optional[torch.Tensor] = None
 
 
 class _Chain(NamedTuple):
@@ -561,11 +622,15 @@ class _DecodeBase:
         elif t.attn == "multi":
             w = MqDecodeAttentionMultiArgs()
             w.a, w.rows, w.split_from, w.qkv_stride, w.v_chunked = at, t.rows, self.LONG_FROM, qkv_n, int(t.v_chunked)
+        elif t.attn == "ragged":
+            w = MqDecodeAttentionRaggedArgs()
+            w.a, w.rows, w.batch, w.split_from, w.qkv_stride = at, t.rows, t.batch, self.LONG_FROM, qkv_n
+            w.row_seq, w.row_pos = t.row_seq.data_ptr(), t.row_pos.data_ptr()
         else:
             w = at
         p = self._gemv(im.op, xq=t.attn_q.data_ptr(), a_grid=_grid(im.g_o, self._keep), resid=t.x.data_ptr(), y=t.x.data_ptr())
         p.out_grid[0] = _grid(attn.o_proj.output_quantizer, self._keep)
-        return ("attn_multi" if t.attn == "multi" else "attn", w), self._finish_gemv(t, im.op, p, s.heads * s.head_dim, s.hidden)
+        return ({"multi": "attn_multi", "ragged": "attn_ragged"}.get(t.attn, "attn"), w), self._finish_gemv(t, im.op, p, s.heads * s.head_dim, s.hidden)
 
     def _ffn_launches(self, im: _Images, t: _Target, resid: torch.Tensor, **extra):
         """post_attention_layernorm + interleaved w1|w3 stream + gated activation + w2's input quantizer, then w2 from that int8 image +

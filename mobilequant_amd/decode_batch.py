@@ -11,16 +11,22 @@ The layer is lowered by the code the single engine uses (``decode._DecodeBase._l
 Positions live in device memory (``pos [B]``), so ONE captured hipGraph serves every mix of slot positions: the attention launch
 chooses each sequence's split count on the device, and a slot whose position is the ``cache_len`` sentinel is idle -- its cache and
 its logits row do not change.
+
+Ragged steps: ``step_tokens`` / ``extend`` move chosen slots by several tokens in ONE step while the others stand
+still, ``rewind`` drops a slot's last positions, and ``generate(draft=...)`` is greedy speculative decoding across the batch.  Their
+rows run the same weight launches over row buffers of their own and ``mq_decode_attention_ragged`` (csrc/mq_decode_ragged.hip), whose
+row table -- like the tokens and the position advance -- is device data: one hipGraph per total row count serves every plan.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence
+from typing import Dict, List, Mapping, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
-from .decode import DecodeEngine, _DecodeBase, _eos_set, _Target
+from .decode import DecodeEngine, _DecodeBase, _eos_set, _Target, plan_rows, spec_accept, spec_row_budget
 from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
 
 MAX_BATCH = 8
@@ -32,7 +38,11 @@ class BatchDecodeEngine(_DecodeBase):
 
     # LONG_FROM / LONG_SPLITS (the base's) apply per sequence, on the device; MAX_IMAGE_BYTES / MAX_HEAD_FLOATS bound B * K and B * hidden
 
-    def __init__(self, model, batch: int, cache_len: int = 2048):
+    MAX_ROWS = MAX_BATCH                 # step_tokens: rows per ragged step (MQ_DECODE_MAX_BATCH), lowered by the shape (max_rows)
+
+    def __init__(self, model, batch: int, cache_len: int = 2048, max_rows: int = 8):
+        """max_rows: the rows of a ragged step (step_tokens), lowered as DecodeEngine.max_rows is: R * K int8 images in the GEMV launches'
+        LDS (128 KiB), R * hidden normalised floats in the head's (32 768)."""
         from .llama import LlamaForCausalLM
         assert isinstance(model, LlamaForCausalLM)
         B = int(batch)
@@ -56,7 +66,9 @@ class BatchDecodeEngine(_DecodeBase):
         self.attn_part = torch.zeros(B, self.LONG_SPLITS, s.heads * s.head_dim, dtype=torch.int64, device=dev)
         self.attn_ticket = torch.zeros(B, s.heads, dtype=torch.int32, device=dev)
         self.gate_q = torch.zeros(B, s.ffn, dtype=torch.int8, device=dev)
-        self.logits = torch.zeros(B, s.vocab, device=dev)
+        # (row B of the allocation, outside self.logits: where a ragged step's finish drops the rows that are no slot's last)
+        self._logits_rows = torch.zeros(B + 1, s.vocab, device=dev)
+        self.logits = self._logits_rows[:B]
         self.pos = torch.full((B,), self.cache_len, dtype=torch.int32, device=dev)       # every slot idle
         self.tok = torch.zeros(B, dtype=torch.int64, device=dev)
         # [B][kv_heads][cache_len][head_dim] int8 indices (index - 128) on qk_bmm.input2 / pv_bmm.input2's grids
@@ -64,6 +76,10 @@ class BatchDecodeEngine(_DecodeBase):
         self.v_cache = [torch.zeros(B, s.kv_heads, self.cache_len, s.head_dim, dtype=torch.int8, device=dev) for _ in model.layers]
         self._host_pos = [self.cache_len] * B
         self._active = [False] * B
+        if isinstance(max_rows, bool) or int(max_rows) < 1:
+            raise ValueError(f"BatchDecodeEngine: max_rows={max_rows} must be >= 1")
+        self.max_rows = max(1, min(int(max_rows), self.MAX_ROWS, self.MAX_IMAGE_BYTES // big, self.MAX_HEAD_FLOATS // s.hidden))
+        self.spec_stats = None               # what the last generate(draft=...) did
         self.graph = None
         self.append_stats = None             # what the last prefill(slot, ids, append=True) did
         self._append_images = None           # per layer ImageCache of prefill(append=True), allocated on first use
@@ -74,6 +90,8 @@ class BatchDecodeEngine(_DecodeBase):
     def _lower(self):
         """Launch records from the model as it is now (_lower_model): per layer the five-launch chain over the B rows of the slot buffers,
         a sequence per row."""
+        self._rows = None         # row phases of step_tokens: lowered on first use, from the layers' images (_lower_rows)
+        self._row_graphs = {}     # total row count -> the captured ragged step, recorded on first use after capture()
         self._lower_model()
         t = _Target(self.x, self.qkv, self.attn_q, self.attn_part, self.attn_ticket, self.gate_q, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
                     rows=self.batch, attn="batch")
@@ -106,6 +124,160 @@ class BatchDecodeEngine(_DecodeBase):
         self.graph = self._record(self._launch, self._advance)
         self.pos.copy_(pos0)
         self._sample_graphs = {}
+        self._row_graphs = {}                     # (ragged steps: one graph per total row count, recorded on first use)
+        return self
+
+    # -- ragged steps: several tokens per slot (csrc/mq_decode_ragged.hip) ----------------------------------------
+    _ENTRY_ROWS = {"gemv": "mq_decode_gemv_batch", "gemv_grouped": "mq_decode_gemv_grouped", "attn_ragged": "mq_decode_attention_ragged"}
+
+    def _lower_rows(self):
+        """The launch records of a ragged step: per layer the five-launch chain over max_rows rows (mq_decode_gemv_batch / _grouped,
+        mq_decode_attention_ragged over the engine's own caches) on the norms and weight images the slot chain already holds
+        (self._images: no weight is stored twice), plus mq_decode_head_batch.  Row buffers of their own; the row count is set per
+        launch (_set_rows).  The plan of a step -- tokens, row table, where each row's logits go, the slots' position advance -- is
+        ONE packed int32 buffer (rplan), written by one host -> device copy; rtok / row_dst (int64) and row_seq / row_pos / radv
+        (int32) are views of it."""
+        s, dev, R, B = self.shape, self.dev, self.max_rows, self.batch
+        H, D = s.heads, s.head_dim
+        self.rx = torch.zeros(R, s.hidden, device=dev)
+        self.rqkv = torch.zeros(R, self.qkv.shape[1], device=dev)
+        self.rattn_q = torch.zeros(R, H * D, dtype=torch.int8, device=dev)
+        self.rpart = torch.zeros(R, self.LONG_SPLITS, H * D, dtype=torch.int64, device=dev)
+        self.rticket = torch.zeros(R, H, dtype=torch.int32, device=dev)
+        self.rgate = torch.zeros(R, s.ffn, dtype=torch.int8, device=dev)
+        self.rlogits = torch.zeros(R, s.vocab, device=dev)
+        self.rplan = torch.zeros(6 * R + B, dtype=torch.int32, device=dev)
+        self.rtok, self.row_dst = self.rplan[:2 * R].view(torch.int64), self.rplan[2 * R:4 * R].view(torch.int64)
+        self.row_seq, self.row_pos, self.radv = self.rplan[4 * R:5 * R], self.rplan[5 * R:6 * R], self.rplan[6 * R:]
+        self._upload_plan(None)
+        t = _Target(self.rx, self.rqkv, self.rattn_q, self.rpart, self.rticket, self.rgate, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
+                    rows=R, attn="ragged", batch=B, row_seq=self.row_seq, row_pos=self.row_pos)
+        with torch.no_grad():
+            phases = [p for li, im in enumerate(self._images) for p in self._lower_chain(li, im, t)]
+        self._rows = (phases, self._head_batch(self.rx, self.rlogits, R, pos=self.row_pos))
+        self._row_graphs = {}
+
+    def _upload_plan(self, plan):
+        """A plan_rows plan (None: every row idle, no slot advances) into rplan: one host -> device copy.  An idle row names
+        sequence -1 at the cache_len sentinel; a row that is not its slot's last sends its logits to the spare row behind self.logits."""
+        R, B = self.max_rows, self.batch
+        h = np.zeros(6 * R + B, dtype=np.int32)
+        tok, dst = h[:2 * R].view(np.int64), h[2 * R:4 * R].view(np.int64)
+        dst[:] = B
+        h[4 * R:5 * R], h[5 * R:6 * R] = -1, self.cache_len
+        if plan is not None:
+            n = len(plan.row_tok)
+            tok[:n], h[4 * R:4 * R + n], h[5 * R:5 * R + n] = plan.row_tok, plan.row_seq, plan.row_pos
+            for slot, (r0, cnt) in plan.spans.items():
+                dst[r0 + cnt - 1] = slot
+                h[6 * R + slot] = cnt
+        self.rplan.copy_(torch.from_numpy(h), non_blocking=False)
+
+    def _set_rows(self, R: int):
+        phases, hb = self._rows
+        for kind, a in phases:
+            if kind == "gemv":
+                a.batch = R
+            elif kind == "gemv_grouped":
+                a.b.batch = R
+            else:
+                a.rows = R
+        hb.batch = R
+
+    def _launch_rows(self, R: int):
+        """Embedding rows + 5 launches per layer over R rows + norm / lm_head for R rows, on the current stream (reads rplan)."""
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        phases, hb = self._rows
+        torch.index_select(self.embed, 0, self.rtok[:R], out=self.rx[:R])
+        for kind, a in phases:
+            _lib.call(self._ENTRY_ROWS[kind], ctypes.byref(a), st)
+        _lib.call("mq_decode_head_batch", ctypes.byref(hb), st)
+
+    def _finish_rows(self, R: int):
+        """logits[slot] <- the slot's last row (the others, idle ones included, land in the spare row) and the slots' position advance:
+        fixed-shape device ops over the plan, so any assignment of R rows to slots replays the same graph."""
+        self._logits_rows.index_copy_(0, self.row_dst[:R], self.rlogits[:R])
+        self.pos.add_(self.radv)
+
+    def _capture_rows(self, R: int, plan):
+        """Record the R-row ragged step (incl. the logits rows and the position advance) as a hipGraph.  The warm-up launch outside
+        the capture runs with every row idle: no cache byte, logits row or position changes."""
+        self._set_rows(R)
+        self._upload_plan(None)
+        self.rticket.zero_()
+        g = self._row_graphs[R] = self._record(lambda: self._launch_rows(R), lambda: self._finish_rows(R))
+        self._upload_plan(plan)
+        return g
+
+    @torch.no_grad()
+    def step_tokens(self, tokens: Mapping[int, Sequence[int]]) -> Dict[int, torch.Tensor]:
+        """A ragged step: every named slot (active, at least one token) appends its tokens at its own position, all in ONE step of at
+        most max_rows rows in total (rows in ascending slot order, a slot's rows contiguous).  Returns slot -> logits [T_slot, vocab],
+        views of the row buffer that the next call overwrites: row j is, bit for bit, what DecodeEngine.step(tokens[j]) returns for
+        that sequence alone after the earlier tokens, and the slot's caches end as those steps leave them.  Its position advances by
+        T_slot and self.logits[slot] holds its last row: sample() and generate continue from there.  Slots NOT named do not move
+        (unlike step(), which advances every active slot): their caches, positions and logits rows keep their bytes.
+        ValueError: total rows outside 1..max_rows, an empty token list, a slot out of range; RuntimeError: an idle slot, tokens
+        that would overflow the slot's cache.  After capture(): one hipGraph per TOTAL row count, recorded on first use; the row
+        table, the tokens, the position advance and the logits[slot] update are device data and device ops inside it."""
+        plan = plan_rows(tokens, [p if a else None for p, a in zip(self._host_pos, self._active)], self.max_rows, self.cache_len)
+        R = len(plan.row_tok)
+        if self._rows is None:
+            self._lower_rows()
+        if self.graph is not None:
+            g = self._row_graphs.get(R)
+            if g is None:
+                g = self._capture_rows(R, plan)
+            else:
+                self._upload_plan(plan)
+            g.replay()
+        else:
+            self._upload_plan(plan)
+            self._set_rows(R)
+            with torch.cuda.device(self.dev):
+                self._launch_rows(R)
+                self._finish_rows(R)
+        for slot, (_, cnt) in plan.spans.items():
+            self._host_pos[slot] += cnt
+        return {slot: self.rlogits[r0:r0 + cnt] for slot, (r0, cnt) in plan.spans.items()}
+
+    @torch.no_grad()
+    def extend(self, tokens: Mapping[int, Sequence[int]]) -> torch.Tensor:
+        """Append any number of tokens per named slot (active; no reset), packed into step_tokens calls of at most max_rows rows:
+        the logits and caches of that many single steps per slot.  Returns self.logits (each named slot's row: its last token's)."""
+        rest = {int(slot): [int(v) for v in t] for slot, t in tokens.items()}
+        plan_rows({b: t[:1] for b, t in rest.items()}, [p if a else None for p, a in zip(self._host_pos, self._active)], max(self.max_rows, len(rest)),
+                  self.cache_len, "BatchDecodeEngine.extend")                # slots in range, active, no empty list
+        for b, t in rest.items():
+            if self._host_pos[b] + len(t) > self.cache_len:
+                raise RuntimeError(f"BatchDecodeEngine.extend: {len(t)} tokens at position {self._host_pos[b]} overflow slot {b}'s KV cache "
+                                   f"({self.cache_len} positions)")
+        while rest:
+            room, call = self.max_rows, {}
+            for b in sorted(rest):
+                if room == 0:
+                    break
+                call[b], rest[b] = rest[b][:room], rest[b][room:]
+                room -= len(call[b])
+                if not rest[b]:
+                    del rest[b]
+            self.step_tokens(call)
+        return self.logits
+
+    def rewind(self, slot: int, n: int):
+        """Drop the slot's positions >= n (n <= position(slot)): its later steps compute what an engine that never saw them computes.
+        Only the slot's position moves, on host and device: no batched launch reads a cached byte at or past a slot's position (the
+        attention launches mask the keys, the values and the split blocks by it), so the dropped bytes are never read before they are
+        overwritten.  The other slots and self.logits are untouched.  The sampler's token history of the slot is left STALE, as in
+        DecodeEngine.rewind: call observe_history(slot, ids) with the tokens the sequence now holds before a penalised draw."""
+        self._check_slot(slot)
+        n = int(n)
+        if not self._active[slot]:
+            raise RuntimeError(f"BatchDecodeEngine.rewind: slot {slot} is idle")
+        if not 0 <= n <= self._host_pos[slot]:
+            raise ValueError(f"BatchDecodeEngine.rewind: n={n} outside 0..{self._host_pos[slot]} (slot {slot}'s position)")
+        self.pos[slot] = n
+        self._host_pos[slot] = n
         return self
 
     # -- seeded token selection on the device (csrc/mq_sample.hip, DESIGN.md 4.3e) ---------------------------------------------
@@ -324,7 +496,7 @@ class BatchDecodeEngine(_DecodeBase):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_token_id=None, do_sample: bool = False,
                  temperature: float = 0.5, generator: Optional[torch.Generator] = None, sampling=None,
-                 streams: Optional[Sequence[int]] = None) -> List[List[int]]:
+                 streams: Optional[Sequence[int]] = None, draft=None, num_draft: int = 4) -> List[List[int]]:
         """DecodeEngine.generate for up to `batch` prompts at once, each in its own slot: prompt i's list is what DecodeEngine.generate
         returns for it alone (context + new tokens).  Per step the next tokens are chosen on the device (argmax, or multinomial of
         softmax(logits / temperature) per row); the host reads the B token ids.  A sequence stops at its own EOS, after max_new_tokens
@@ -332,10 +504,30 @@ class BatchDecodeEngine(_DecodeBase):
         sampling (one SamplingParams, or one per prompt) with streams (default: the prompt's index in `prompts`): seeded selection by
         mq_sample's rule.  Prompt i's list is then what DecodeEngine.generate(prompts[i], sampling=..., stream=
         streams[i]) returns, bit for bit, whatever the batch, the slot and the other prompts are.  After capture() a step costs one
-        graph replay (sample + step) and one read-back of the B tokens."""
+        graph replay (sample + step) and one read-back of the B tokens.
+        draft (greedy only; a callable draft(ids, k) -> at most k proposals such as prompt_lookup_draft(), or one callable per prompt):
+        greedy speculative decoding for every prompt at once (_generate_speculative).  Prompt i's list equals the plain greedy one
+        token for token; self.spec_stats counts the rounds."""
         n = len(prompts)
         if not 0 < n <= self.batch:
             raise ValueError(f"BatchDecodeEngine.generate: {n} prompts for {self.batch} slots")
+        drafts = None
+        if draft is not None:
+            if sampling is not None:
+                validate_generate_args("BatchDecodeEngine.generate", sampling, do_sample, draft)
+            if do_sample:
+                raise ValueError("BatchDecodeEngine.generate: a draft is for greedy decoding only (do_sample=True with a draft)")
+            drafts = [draft] * n if callable(draft) and not isinstance(draft, _DecodeBase) else draft
+            if isinstance(drafts, _DecodeBase) or (isinstance(drafts, (list, tuple)) and any(isinstance(d, _DecodeBase) for d in drafts)):
+                raise TypeError("BatchDecodeEngine.generate: an engine cannot draft for a batch: pass callable drafts, draft(ids, k) -> list of "
+                                "token ids (one for all prompts or one per prompt)")
+            if not isinstance(drafts, (list, tuple)) or any(not callable(d) for d in drafts):
+                raise TypeError("BatchDecodeEngine.generate: draft must be a callable draft(ids, k) -> list of token ids, or a sequence of "
+                                "such callable drafts, one per prompt")
+            if len(drafts) != n:
+                raise ValueError(f"BatchDecodeEngine.generate: {len(drafts)} drafts for {n} prompts")
+            if isinstance(num_draft, bool) or int(num_draft) < 0:
+                raise ValueError(f"BatchDecodeEngine.generate: num_draft={num_draft} must be >= 0")
         if sampling is not None:
             validate_generate_args("BatchDecodeEngine.generate", sampling, do_sample)
             rows = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
@@ -367,6 +559,8 @@ class BatchDecodeEngine(_DecodeBase):
         outs = [list(p) for p in prompts]
         made = [0] * n
         live = list(range(n))
+        if drafts is not None:
+            return self._generate_speculative(outs, max_new_tokens, eos, drafts, int(num_draft))
         if sampling is not None:
             idle = SamplingParams(temperature=0.0)
             self.set_sampling(rows + [idle] * (self.batch - n), st + [0] * (self.batch - n))
@@ -401,4 +595,55 @@ class BatchDecodeEngine(_DecodeBase):
                     live.remove(i)
             if live:
                 self.step()
+        return outs
+
+    def _generate_speculative(self, outs: List[List[int]], max_new_tokens: int, eos: set, drafts, num_draft: int) -> List[List[int]]:
+        """Greedy speculative decoding across the batch; slot i holds outs[i] (its prompt, cached).  The first new token of every prompt
+        is the argmax of its context's logits.  Then per round, with t_i slot i's last token (not yet cached) and P_i its position: the
+        live slots share the step's rows (spec_row_budget), slot i's draft proposes k_i tokens, ONE step_tokens call runs [t_i, d1 ..
+        dk_i] for every live slot, one read-back brings the rows' argmax, and per slot spec_accept keeps plain greedy's next tokens and
+        rewind(slot, P_i + kept) drops the rest.  The stops are plain generate's: EOS, max_new_tokens, the cache end.  More live slots
+        than max_rows (an engine whose shape lowered max_rows below its batch) take a plain step() instead."""
+        n = len(outs)
+        stats = self.spec_stats = {"rounds": 0, "proposed": 0, "accepted": 0, "target_steps": 0}
+        made, live = [0] * n, []
+        first = torch.argmax(self.logits, dim=-1).tolist()
+        for i in range(n):
+            outs[i].append(first[i])
+            made[i] = 1
+            if first[i] in eos or made[i] >= max_new_tokens or self._host_pos[i] >= self.cache_len:
+                self.release(i)
+            else:
+                live.append(i)
+        while live:
+            P = {i: self._host_pos[i] for i in live}
+            stats["rounds"] += 1
+            stats["target_steps"] += 1
+            if len(live) > self.max_rows:
+                self.step([outs[i][-1] if i in P else 0 for i in range(self.batch)])
+                arg = torch.argmax(self.logits, dim=-1).tolist()
+                props = {i: [] for i in live}
+                rows = {i: [arg[i]] for i in live}
+                views = None
+            else:
+                ks = spec_row_budget(num_draft, self.max_rows, [max_new_tokens - made[i] for i in live], [self.cache_len - P[i] for i in live])
+                props = {i: ([int(v) for v in drafts[i](list(outs[i]), k)][:k] if k > 0 else []) for i, k in zip(live, ks)}
+                views = self.step_tokens({i: [outs[i][-1]] + props[i] for i in live})
+                arg = torch.argmax(self.rlogits[:sum(1 + len(props[i]) for i in live)], dim=-1).tolist()      # ONE read-back for all slots
+                rows, r0 = {}, 0
+                for i in live:                                     # (ascending slots: the rows' order)
+                    rows[i] = arg[r0:r0 + 1 + len(props[i])]
+                    r0 += 1 + len(props[i])
+            for i in list(live):
+                new, acc, stop = spec_accept(rows[i], props[i], eos, budget=max_new_tokens - made[i], room=self.cache_len - P[i])
+                stats["proposed"] += len(props[i])
+                stats["accepted"] += acc
+                if views is not None:
+                    self.rewind(i, P[i] + len(new))                # t and the accepted proposals stay cached
+                    self.logits[i].copy_(views[i][len(new) - 1])
+                outs[i] += new
+                made[i] += len(new)
+                if stop:
+                    self.release(i)
+                    live.remove(i)
         return outs

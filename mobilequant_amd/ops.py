@@ -494,6 +494,14 @@ def decode_attention_multi(args: "_lib.MqDecodeAttentionMultiArgs") -> None:
     _lib.call("mq_decode_attention_multi", ctypes.byref(args), _stream())
 
 
+def decode_attention_ragged(args: "_lib.MqDecodeAttentionRaggedArgs") -> None:
+    """mq_decode_attention_ragged on the current stream: the decode attention of args.rows table rows -- row r the position
+    row_pos[r] of sequence row_seq[r] (device arrays), consecutive rows of one sequence at consecutive positions seeing each other --
+    over args.batch caches in one launch, appending the named positions.  A sequence may appear in at most one run per launch.  args is
+    a filled _lib.MqDecodeAttentionRaggedArgs (include/mobilequant_amd.h); the tensors it points into stay alive until it has run."""
+    _lib.call("mq_decode_attention_ragged", ctypes.byref(args), _stream())
+
+
 def int8_linear_segmented(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: torch.Tensor, alpha: torch.Tensor, w_zp: torch.Tensor,
                           col_term: torch.Tensor, bias: Optional[torch.Tensor], seg_ends, grids, w4: bool = False,
                           a_tiled_rows: Optional[int] = None) -> torch.Tensor:
