@@ -310,9 +310,138 @@ def spec_row_budget(num_draft: int, max_rows: int, allowed: Sequence[int], room:
     return [max(0, min(int(num_draft), int(max_rows) // L - 1, int(a) - 1, int(r) - 1)) for a, r in zip(allowed, room)]
 
 
+def _spec_stats() -> Dict[str, int]:
+    """self.spec_stats of a speculative generation: rows steps of the target (rounds, target_steps), tokens proposed and accepted."""
+    return {"rounds": 0, "proposed": 0, "accepted": 0, "target_steps": 0}
+
+
 def _eos_set(eos_token_id) -> set:
     """generate's eos_token_id (None, one id or several) as a set."""
     return set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+
+
+def _check_draft(who: str, target, draft, num_draft, engine: tuple, what: str = "a DecodeEngine or a callable draft(ids, k) -> list of token ids"):
+    """The refusals every speculative entry point shares, before anything runs: the draft is another engine (an instance of the
+    classes `engine`; none: no engine may draft) of the target's vocabulary size or a callable, and num_draft >= 0.  Returns the
+    draft engine, or None for a callable."""
+    d_eng = draft if isinstance(draft, engine) else None
+    if d_eng is target:
+        raise ValueError(f"{who}: the draft must be another engine (it keeps its own cache)")
+    if d_eng is None and not callable(draft):
+        raise TypeError(f"{who}: draft must be {what}")
+    if isinstance(num_draft, bool) or int(num_draft) < 0:
+        raise ValueError(f"{who}: num_draft={num_draft} must be >= 0")
+    if d_eng is not None and d_eng.shape.vocab != target.shape.vocab:
+        raise ValueError(f"{who}: draft vocabulary {d_eng.shape.vocab} != target vocabulary {target.shape.vocab}")
+    return d_eng
+
+
+class _Greedy:
+    """How DecodeEngine._speculate chooses tokens, on the target and on an engine draft alike.  This one is plain generate's
+    torch.argmax (ties break as they do there)."""
+    draft_room = 1                       # an engine draft reads its last proposal from its logits: kd <= cache_len - len(out) + 1
+
+    def start(self, eng, ids, prefill):
+        eng._start_sequence(ids, prefill)
+
+    def first(self, eng) -> int:
+        """The token behind eng's cached sequence, from eng.logits."""
+        return int(torch.argmax(eng.logits))
+
+    def chain(self, eng, n: int) -> List[int]:
+        """n tokens behind eng's cached sequence, each stepped before the next is chosen; the last one is not cached."""
+        toks = [self.first(eng)]
+        for _ in range(n - 1):
+            eng.step(toks[-1])
+            toks.append(self.first(eng))
+        return toks
+
+    def rows(self, eng, tokens) -> List[int]:
+        """ONE rows step of eng over `tokens`: the token behind every row."""
+        return torch.argmax(eng.step_tokens(tokens), dim=-1).tolist()
+
+    def recount(self, eng, dropped, kept):
+        pass
+
+
+class _Sampled:
+    """_Greedy's counterpart for generate(sampling=...): the selection under one request and stream: sample() / sample_step() and, behind a rows step,
+    mq_sample_rows (one graph after capture(), ONE read-back of the T tokens).  An engine draft shares the noise with the target.
+    Under a penalised request start() rebuilds eng's history from the context and every launch counts what it draws; recount() brings
+    the history back to the sequence's truth: -1 for drawn tokens that were dropped, +1 for kept ones no launch has counted."""
+    draft_room = 0                       # (its last draw, at index len(out) + kd - 1, must not be an idle row)
+
+    def __init__(self, sampling, stream):
+        self.request = (sampling, stream)
+
+    def start(self, eng, ids, prefill):
+        eng.set_sampling(*self.request)
+        eng._start_sequence(ids, prefill)
+        if eng._sampler.penalized:
+            eng._sampler.observe_prompt(0, ids)                    # the history is rebuilt for every sequence
+
+    def first(self, eng) -> int:
+        eng.sample()
+        return int(eng.tok.item())
+
+    def chain(self, eng, n: int) -> List[int]:
+        buf = torch.empty(n, dtype=torch.int64, device=eng.tok.device)
+        for i in range(n):                                         # token i at index position() + i, counted in eng's own history
+            (eng.sample_step if i < n - 1 else eng.sample)()
+            buf[i:i + 1].copy_(eng.tok)
+        return buf.tolist()
+
+    def rows(self, eng, tokens) -> List[int]:
+        return eng.step_sample_tokens(tokens).tolist()
+
+    def recount(self, eng, dropped, kept):
+        if eng._sampler.penalized:
+            for ids, delta in ((dropped, -1), (kept, 1)):
+                if ids:
+                    history_count(eng._sampler.history[0], torch.tensor(ids, dtype=torch.int64, device=eng.dev), delta)
+
+
+class _CallableDraft:
+    """A draft of DecodeEngine._speculate: propose(out, k) -> at most k tokens to follow out; settle(out, new, acc, props) once the
+    target kept `new` behind out, `acc` of them from `props`.  This one is draft(ids, k), which keeps nothing."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def start(self, ids, prefill):
+        pass
+
+    def propose(self, out, k):
+        return [int(v) for v in self.fn(list(out), k)][:k]
+
+    def settle(self, out, new, acc, props):
+        pass
+
+
+class _EngineDraft:
+    """Another DecodeEngine drafting by the target's own selection.  Its cache holds out[:pos]: propose catches up on the kept tokens
+    with extend, settle drops the rejected proposals with rewind (and from a penalised history)."""
+
+    def __init__(self, eng, select):
+        self.eng, self.select, self.pos = eng, select, 0
+
+    def start(self, ids, prefill):
+        self.select.start(self.eng, ids, prefill)
+        self.pos = len(ids)
+
+    def propose(self, out, k):
+        kd = min(k, self.eng.cache_len - len(out) + self.select.draft_room)
+        if kd <= 0:
+            return []
+        self.eng.extend(out[self.pos:])                            # its logits: behind out, the row token len(out) is chosen from
+        self.pos = len(out) + kd - 1                               # out + props[:-1]
+        return self.select.chain(self.eng, kd)
+
+    def settle(self, out, new, acc, props):
+        self.select.recount(self.eng, props[acc:], new[acc:])
+        if self.pos > len(out):                                    # the draft keeps out + the accepted proposals it had cached
+            self.pos = min(self.pos, len(out) + acc)
+            self.eng.rewind(self.pos)
 
 
 class _Images(NamedTuple):
@@ -364,8 +493,12 @@ class _Chain(NamedTuple):
 
 class _DecodeBase:
     """What DecodeEngine and BatchDecodeEngine both are: snapshots of one model (_lower_model), the lowering of a decoder layer to launch
-    records on a _Target (_lower_chain and its per-launch helpers) and the hipGraph recorder (_record).  The engine supplies model / shape /
-    dev / cache_len / cos / sin / pos / graph, _lower() and capture()."""
+    records on a _Target (_lower_chain and its per-launch helpers), the hipGraph recorder (_record), the rows step behind step_tokens
+    (_lower_row_chain, _set_rows, _launch_rows) and, written over ONE sequence, prefill (_prefill_fill, _prefill_append) and a
+    sequence's share of a speculative round (_spec_keep).  The engine supplies model / shape / dev / cache_len / cos / sin / pos / graph
+    / max_rows, _lower() and capture(), its _lower_rows / _finish_rows / _capture_rows and, for the code over one sequence, position /
+    set_position / rewind plus _seq_caches / _store_values / _step_seq / _logits_row.  Those take the sequence as trailing arguments
+    `*seq`: nothing in DecodeEngine, the slot in BatchDecodeEngine."""
 
     LONG_FROM, LONG_SPLITS = 768, 4      # five launches: the split attention launch from LONG_FROM cached positions on
     # mq_decode_gemv_batch / mq_decode_head_batch limits: rows * K int8 images in the GEMV launches' LDS, rows * hidden normalised floats in the head's
@@ -472,6 +605,58 @@ class _DecodeBase:
             k, v = caches(li)
             ops.attention_cache_export(images[li].per_sequence[0], k, v, P1, len(chunk), v_chunked=v_chunked)
         return logits[0, -1]
+
+    v_transposed = False                 # the value layout _append_chunk finds in _seq_caches (DecodeEngine's four-launch chain: chunked)
+
+    @torch.no_grad()
+    def _prefill_append(self, context_ids, *seq) -> torch.Tensor:
+        """prefill(append=True) for the sequence `seq` (DecodeEngine.prefill has the contract)."""
+        me, t = type(self).__name__, [int(v) for v in context_ids]
+        P = self.position(*seq)
+        if not t:
+            raise ValueError(f"{me}.prefill: no tokens to append")
+        if P + len(t) > self.cache_len:
+            where = f"slot {seq[0]}'s KV cache" if seq else "the KV cache"
+            raise RuntimeError(f"{me}.prefill: {len(t)} tokens appended at position {P} overflow {where} ({self.cache_len} positions)")
+        if P == 0:
+            self.append_stats = {"stepped": 0, "prefilled": len(t), "reason": None}
+            return self.prefill(*seq, t)
+        self._sync_grids()
+        head, reason = self._append_split(P, len(t))
+        if head:
+            self._step_seq(t[:head], *seq)
+        if head < len(t):
+            row = self._append_chunk(t[head:], P + head, lambda li: self._seq_caches(li, *seq), self.v_transposed)
+            if row is None:
+                reason = "the model's attention refused the image cache"
+                self._step_seq(t[head:], *seq)
+                head = len(t)
+            else:
+                self.set_position(*seq, P + len(t))
+                self._logits_row(*seq).copy_(row)
+        self.append_stats = {"stepped": head, "prefilled": len(t) - head, "reason": reason}
+        return self._logits_row(*seq)
+
+    @torch.no_grad()
+    def _prefill_fill(self, context_ids, zero: bool, *seq) -> torch.Tensor:
+        """Context encoding for the sequence `seq` in ONE forward of the module graph with a KV cache attached: the cached keys /
+        values go on their QMatMul input grids into the sequence's caches (zero: cleared first), its position behind the context, the
+        last position's logits into its row."""
+        ids = torch.as_tensor([int(t) for t in context_ids], dtype=torch.long, device=self.dev).view(1, -1)
+        S = ids.shape[1]
+        assert 0 < S <= self.cache_len
+        self._sync_grids()
+        raw = self.model.new_cache(1, S, device=self.dev)
+        logits = self.model(ids, cache=raw, last_logits_only=True)      # [1, 1, vocab]: only the last position feeds the first new token
+        for li, layer in enumerate(self.model.layers):
+            att, (k, v) = layer.self_attn, self._seq_caches(li, *seq)
+            if zero:
+                k.zero_()
+                v.zero_()
+            k[:, :S] = att.qk_bmm.input2_quantizer.quantize_to_int(raw[li][0][0].contiguous())[0]
+            self._store_values(li, att.pv_bmm.input2_quantizer.quantize_to_int(raw[li][1][0].contiguous())[0], *seq)
+        self.set_position(*seq, S)
+        return self._logits_row(*seq).copy_(logits[0, -1])
 
     def _record(self, launch, append, before_capture=None):
         """launch() followed by append() as ONE hipGraph on one stream.  launch() first runs once on a side stream outside the capture:
@@ -666,6 +851,67 @@ class _DecodeBase:
             hb.pos, hb.cache_len = pos.data_ptr(), self.cache_len
         return hb
 
+    # -- the rows step (step_tokens) ------------------------------------------------------------------------------------------
+    _ENTRY_ROWS = {"gemv": "mq_decode_gemv_batch", "gemv_grouped": "mq_decode_gemv_grouped", "attn_multi": "mq_decode_attention_multi",
+                   "attn_ragged": "mq_decode_attention_ragged"}
+
+    def _lower_row_chain(self, head_pos: Optional[torch.Tensor] = None, **attn):
+        """The launch records of a rows step, self._rows = (phases, head): per layer the five-launch chain over max_rows rows
+        (mq_decode_gemv_batch / _grouped and the attention launch that `attn`, the _Target's attention fields, names) over the
+        engine's own caches, on the norms and weight images the engine's chain already holds (self._images: no weight is stored
+        twice), plus mq_decode_head_batch (head_pos: its per-row positions).  Row buffers of their own; the row count is set per
+        launch (_set_rows)."""
+        s, dev, R = self.shape, self.dev, self.max_rows
+        H, D = s.heads, s.head_dim
+        self.rx = torch.zeros(R, s.hidden, device=dev)
+        self.rqkv = torch.zeros(R, self.qkv.shape[-1], device=dev)
+        self.rattn_q = torch.zeros(R, H * D, dtype=torch.int8, device=dev)
+        self.rpart = torch.zeros(R, self.LONG_SPLITS, H * D, dtype=torch.int64, device=dev)
+        self.rticket = torch.zeros(R, H, dtype=torch.int32, device=dev)
+        self.rgate = torch.zeros(R, s.ffn, dtype=torch.int8, device=dev)
+        self.rlogits = torch.zeros(R, s.vocab, device=dev)
+        t = _Target(self.rx, self.rqkv, self.rattn_q, self.rpart, self.rticket, self.rgate, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
+                    rows=R, **attn)
+        with torch.no_grad():
+            phases = [p for li, im in enumerate(self._images) for p in self._lower_chain(li, im, t)]
+        self._rows = (phases, self._head_batch(self.rx, self.rlogits, R, pos=head_pos))
+        self._row_graphs = {}
+
+    def _set_rows(self, T: int):
+        phases, hb = self._rows
+        for kind, a in phases:
+            if kind == "gemv":
+                a.batch = T
+            elif kind == "gemv_grouped":
+                a.b.batch = T
+            else:
+                a.rows = T
+        hb.batch = T
+
+    def _launch_rows(self, T: int):
+        """Embedding rows + 5 launches per layer over T rows + norm / lm_head for T rows, on the current stream (reads rtok and the
+        positions the attention records point at)."""
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        phases, hb = self._rows
+        torch.index_select(self.embed, 0, self.rtok[:T], out=self.rx[:T])
+        for kind, a in phases:
+            _lib.call(self._ENTRY_ROWS[kind], ctypes.byref(a), st)
+        _lib.call("mq_decode_head_batch", ctypes.byref(hb), st)
+
+    def _spec_keep(self, drawn: Sequence[int], props: Sequence[int], eos: set, budget: int, rows: Optional[torch.Tensor], *seq):
+        """The sequence `seq`'s share of a speculative round, behind the step that ran [t, d1 .. dk] for it: spec_accept on the tokens
+        `drawn` from its rows, the round's counts in self.spec_stats, and -- rows: its logits rows of that step; None after a plain
+        step, which leaves nothing to drop -- rewind to the kept tokens (t and the accepted proposals stay cached) with the last kept
+        row as the sequence's logits.  Returns spec_accept's (kept tokens, accepted, stop)."""
+        P = self.position(*seq) - len(drawn)
+        new, acc, stop = spec_accept(drawn, props, eos, budget=budget, room=self.cache_len - P)
+        self.spec_stats["proposed"] += len(props)
+        self.spec_stats["accepted"] += acc
+        if rows is not None:
+            self.rewind(*seq, P + len(new))
+            self._logits_row(*seq).copy_(rows[len(new) - 1])
+        return new, acc, stop
+
 
 class DecodeEngine(_DecodeBase):
     MAX_ROWS = 8                         # step_tokens: tokens per multi-token step (MQ_DECODE_MAX_BATCH), lowered by the shape (max_rows)
@@ -850,48 +1096,13 @@ class DecodeEngine(_DecodeBase):
 
     # -- T-row phases (step_tokens) -----------------------------------------------------------------------------------------
     def _lower_rows(self):
-        """The launch records of a multi-token step: per layer the five-launch chain over T rows (mq_decode_gemv_batch / _grouped,
-        mq_decode_attention_multi over the engine's own caches in its value layout) on the norms and weight images the single chain already
-        holds (self._images, incl. o_proj's row image `op` that the four-launch chain keeps next to its head-sliced copy), plus
-        mq_decode_head_batch.  Row buffers of their own; the row count T is set per launch (_set_rows)."""
-        s, dev, R = self.shape, self.dev, self.max_rows
-        H, D = s.heads, s.head_dim
-        self.rx = torch.zeros(R, s.hidden, device=dev)
-        self.rqkv = torch.zeros(R, self.qkv.shape[0], device=dev)
-        self.rattn_q = torch.zeros(R, H * D, dtype=torch.int8, device=dev)
-        self.rpart = torch.zeros(R, self.LONG_SPLITS, H * D, dtype=torch.int64, device=dev)
-        self.rticket = torch.zeros(R, H, dtype=torch.int32, device=dev)
-        self.rgate = torch.zeros(R, s.ffn, dtype=torch.int8, device=dev)
-        self.rlogits = torch.zeros(R, s.vocab, device=dev)
-        self.rtok = torch.zeros(R, dtype=torch.int64, device=dev)
-        self.rsel = torch.zeros(R, dtype=torch.int64, device=dev)                     # sample_rows: row j's drawn token
+        """The launch records of a multi-token step (_lower_row_chain): mq_decode_attention_multi over the engine's own caches in its
+        value layout, on the images the single chain holds (incl. o_proj's row image `op` that the four-launch chain keeps next to its
+        head-sliced copy).  The rows' tokens (rtok) and what sample_rows draws from them (rsel) are buffers of their own."""
+        self.rtok = torch.zeros(self.max_rows, dtype=torch.int64, device=self.dev)
+        self.rsel = torch.zeros(self.max_rows, dtype=torch.int64, device=self.dev)      # sample_rows: row j's drawn token
         self._row_sel, self._row_sample_graphs = None, {}
-        t = _Target(self.rx, self.rqkv, self.rattn_q, self.rpart, self.rticket, self.rgate, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
-                    rows=R, attn="multi", v_chunked=self.v_transposed)
-        with torch.no_grad():
-            phases = [p for li, im in enumerate(self._images) for p in self._lower_chain(li, im, t)]
-        self._rows = (phases, self._head_batch(self.rx, self.rlogits, R))
-        self._row_graphs = {}
-
-    def _set_rows(self, T: int):
-        phases, hb = self._rows
-        for kind, a in phases:
-            if kind == "gemv":
-                a.batch = T
-            elif kind == "gemv_grouped":
-                a.b.batch = T
-            else:
-                a.rows = T
-        hb.batch = T
-
-    def _launch_rows(self, T: int):
-        """Embedding rows + 5 launches per layer over T rows + norm / lm_head for T rows, on the current stream (reads rtok / pos)."""
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        phases, hb = self._rows
-        torch.index_select(self.embed, 0, self.rtok[:T], out=self.rx[:T])
-        for kind, a in phases:
-            _lib.call(self._ENTRY_ROWS[kind], ctypes.byref(a), st)
-        _lib.call("mq_decode_head_batch", ctypes.byref(hb), st)
+        self._lower_row_chain(attn="multi", v_chunked=self.v_transposed)
 
     def _finish_rows(self, T: int):
         self.logits.copy_(self.rlogits[T - 1])
@@ -1012,7 +1223,6 @@ class DecodeEngine(_DecodeBase):
         return self._host_pos
 
     # -- running -------------------------------------------------------------------------------------------------------------
-    _ENTRY_ROWS = {"gemv": "mq_decode_gemv_batch", "gemv_grouped": "mq_decode_gemv_grouped", "attn_multi": "mq_decode_attention_multi"}
     _ENTRY = {"gemv": "mq_decode_gemv", "gemv_grouped": "mq_decode_gemv_grouped", "attn": "mq_decode_attention", "attn_oproj": "mq_decode_attention_oproj"}
 
     def _launch(self, phases=None):
@@ -1224,47 +1434,19 @@ class DecodeEngine(_DecodeBase):
         Contract: the stepped tokens carry step()'s bits; the prefilled chunk carries the bits of the model's own chunked forward
         (model(chunk, cache=image_cache, pos=P')) over an image cache that holds the engine's cached indices.  The two paths agree
         with each other only within the bound that holds between prefill() and the steps behind it; no bitwise claim between them."""
-        if append:
-            return self._prefill_append(context_ids)
-        ids = torch.as_tensor([int(t) for t in context_ids], dtype=torch.long, device=self.dev).view(1, -1)
-        S = ids.shape[1]
-        assert 0 < S <= self.cache_len
-        self._sync_grids()
-        raw = self.model.new_cache(1, S, device=self.dev)
-        logits = self.model(ids, cache=raw, last_logits_only=True)      # [1, 1, vocab]: only the last position feeds the first new token
-        for li, layer in enumerate(self.model.layers):
-            att = layer.self_attn
-            self.k_cache[li][:, :S] = att.qk_bmm.input2_quantizer.quantize_to_int(raw[li][0][0].contiguous())[0]
-            self.load_cached_values(li, att.pv_bmm.input2_quantizer.quantize_to_int(raw[li][1][0].contiguous())[0])
-        self.set_position(S)
-        self.logits.copy_(logits[0, -1])
-        return self.logits
+        return self._prefill_append(context_ids) if append else self._prefill_fill(context_ids, False)
 
-    @torch.no_grad()
-    def _prefill_append(self, context_ids) -> torch.Tensor:
-        t = [int(v) for v in context_ids]
-        P = self._host_pos
-        if not t:
-            raise ValueError("DecodeEngine.prefill: no tokens to append")
-        if P + len(t) > self.cache_len:
-            raise RuntimeError(f"DecodeEngine.prefill: {len(t)} tokens appended at position {P} overflow the KV cache ({self.cache_len} positions)")
-        if P == 0:
-            self.append_stats = {"stepped": 0, "prefilled": len(t), "reason": None}
-            return self.prefill(t)
-        self._sync_grids()
-        head, reason = self._append_split(P, len(t))
-        if head:
-            self.extend(t[:head])
-        if head < len(t):
-            row = self._append_chunk(t[head:], P + head, lambda li: (self.k_cache[li], self.v_cache[li]), self.v_transposed)
-            if row is None:
-                reason = "the model's attention refused the image cache"
-                self.extend(t[head:])
-                head = len(t)
-            else:
-                self.set_position(P + len(t))
-                self.logits.copy_(row)
-        self.append_stats = {"stepped": head, "prefilled": len(t) - head, "reason": reason}
+    # the one sequence as _DecodeBase's prefill and speculative bodies see it
+    def _store_values(self, li: int, values: torch.Tensor):
+        self.load_cached_values(li, values)
+
+    def _step_seq(self, tokens: Sequence[int]):
+        self.extend(tokens)
+
+    def _seq_caches(self, li: int):
+        return self.k_cache[li], self.v_cache[li]
+
+    def _logits_row(self) -> torch.Tensor:
         return self.logits
 
     @torch.no_grad()
@@ -1278,18 +1460,19 @@ class DecodeEngine(_DecodeBase):
         The host reads one token id per step only to test for EOS and to return the ids.
         draft (greedy only): speculative generation -- another DecodeEngine over a model of the same vocabulary size, or a callable
         draft(ids, k) -> at most k proposals (prompt_lookup_draft) -- verified num_draft tokens at a time with step_tokens.  The
-        returned ids equal the plain greedy ones token for token; self.spec_stats counts the rounds (_generate_speculative).
+        returned ids equal the plain greedy ones token for token; self.spec_stats counts the rounds (_speculate).
         sampling (with stream, the sequence's identity): seeded selection on the device by mq_sample's rule (temperature, top-k, top-p,
-        min-p, behind the repetition / presence / frequency penalties and the logit bias of the sequence's own tokens) -- the ids depend on (context, sampling, stream) only: BatchDecodeEngine.generate returns the same ids
-        for this sequence in any batch and slot.  After capture() a token costs one graph replay (sample + step) and one token
-        read-back; a sequence that ends on an EOS has then cached that token too (position() is one past the returned ids)."""
+        min-p, behind the repetition / presence / frequency penalties and the logit bias of the sequence's own tokens; DESIGN.md
+        4.3e) -- the ids depend on (context, sampling, stream) only: BatchDecodeEngine.generate returns the same ids for this sequence
+        in any batch and slot.  After capture() a token costs one graph replay (sample + step) and one token read-back; a sequence
+        that ends on an EOS has then cached that token too (position() is one past the returned ids)."""
         if sampling is not None:
             validate_generate_args("DecodeEngine.generate", sampling, do_sample, draft)
             return self._generate_sampled(context_ids, max_new_tokens, eos_token_id, prefill, sampling, stream)
         if draft is not None:
             if do_sample:
                 raise ValueError("DecodeEngine.generate: a draft is for greedy decoding only (do_sample=True with a draft)")
-            return self._generate_speculative(context_ids, max_new_tokens, eos_token_id, prefill, draft, num_draft)
+            return self._speculate("DecodeEngine.generate", context_ids, max_new_tokens, eos_token_id, prefill, _Greedy(), draft, num_draft)
         ids = [int(t) for t in context_ids]
         assert len(ids) + max_new_tokens <= self.cache_len
         self._start_sequence(ids, prefill)
@@ -1339,66 +1522,40 @@ class DecodeEngine(_DecodeBase):
                 self.step(t)
 
     @torch.no_grad()
-    def _generate_speculative(self, context_ids, max_new_tokens: int, eos_token_id, prefill: bool, draft, num_draft: int):
-        """Greedy speculative decoding.  The sequence starts as in plain generate; the first new token is the argmax of the context's
-        logits.  Then per round, with t the last token (not yet cached) and P the position: k = min(num_draft, max_rows - 1, tokens still
-        allowed - 1, cache room - 1) proposals d1..dk from the draft, ONE step_tokens([t, d1..dk]), spec_accept on the rows' argmaxes,
-        and rewind to P + the kept tokens.  Every kept token is plain greedy's (row i holds the logits after t, d1..di, bit for bit), and
-        the stops are plain generate's: EOS, max_new_tokens, the cache end.  An engine draft catches up on the kept tokens with extend
-        and drops the rejected ones with rewind."""
+    def _speculate(self, who: str, context_ids, max_new_tokens: int, eos_token_id, prefill: bool, select, draft, num_draft: int):
+        """Speculative decoding, for generate(draft=...) (select: _Greedy) and generate_speculative (_Sampled).  The sequence starts as
+        in the plain loop and the first new token is chosen from the context's logits.  Then per round, with t the last token (not yet
+        cached) and P the position: k = min(num_draft, max_rows - 1, tokens still allowed - 1, cache room - 1) proposals d1..dk from
+        the draft, ONE rows step over [t, d1..dk] whose tokens `select` chooses, spec_accept on them and rewind to P + the kept tokens
+        (_spec_keep).  Every kept token is the plain loop's: row i holds the logits after t, d1..di, bit for bit, and a token depends
+        on its row (greedy) or on its row and its index (sampling) alone.  The stops are plain generate's: EOS, max_new_tokens, the
+        cache end.  Afterwards the caches hold out[:position()]."""
+        d_eng = _check_draft(who, self, draft, num_draft, (DecodeEngine,))
+        draft = _CallableDraft(draft) if d_eng is None else _EngineDraft(d_eng, select)
         ids = [int(t) for t in context_ids]
         assert len(ids) + max_new_tokens <= self.cache_len
         eos = _eos_set(eos_token_id)
-        d_eng = draft if isinstance(draft, DecodeEngine) else None
-        if d_eng is self:
-            raise ValueError("DecodeEngine.generate: the draft must be another engine (it keeps its own cache)")
-        if d_eng is not None and d_eng.shape.vocab != self.shape.vocab:
-            raise ValueError(f"DecodeEngine.generate: draft vocabulary {d_eng.shape.vocab} != target vocabulary {self.shape.vocab}")
-        if d_eng is None and not callable(draft):
-            raise TypeError("DecodeEngine.generate: draft must be a DecodeEngine or a callable draft(ids, k) -> list of token ids")
-        if int(num_draft) < 0:
-            raise ValueError(f"DecodeEngine.generate: num_draft={num_draft} must be >= 0")
-        stats = self.spec_stats = {"rounds": 0, "proposed": 0, "accepted": 0, "target_steps": 0}
-        self._start_sequence(ids, prefill)
+        stats = self.spec_stats = _spec_stats()
+        select.start(self, ids, prefill)
         out = list(ids)
         if max_new_tokens <= 0:
             return out
-        d_pos = 0                                                  # the draft engine's cache holds out[:d_pos]
-        if d_eng is not None:
-            d_eng._start_sequence(ids, prefill)
-            d_pos = len(ids)
-        nxt = int(torch.argmax(self.logits))
-        out.append(nxt)
+        draft.start(ids, prefill)
+        new = [select.first(self)]                                 # (under a penalised request its own launch has counted it)
+        draft.settle(out, new, 0, [])
+        out += new
         made = 1
-        if nxt in eos or made >= max_new_tokens or self._host_pos >= self.cache_len:
+        if new[0] in eos or made >= max_new_tokens or self._host_pos >= self.cache_len:
             return out
         while True:
-            P = self._host_pos
-            k = max(0, min(int(num_draft), self.max_rows - 1, max_new_tokens - made - 1, self.cache_len - P - 1))
-            props: List[int] = []
-            if k > 0 and d_eng is not None:
-                kd = min(k, d_eng.cache_len - len(out) + 1)
-                if kd > 0:
-                    d_eng.extend(out[d_pos:])
-                    props = [int(torch.argmax(d_eng.logits))]
-                    for _ in range(kd - 1):
-                        d_eng.step(props[-1])
-                        props.append(int(torch.argmax(d_eng.logits)))
-                    d_pos = len(out) + kd - 1                      # out + props[:-1]
-            elif k > 0:
-                props = [int(v) for v in draft(list(out), k)][:k]
-            rows = self.step_tokens([out[-1]] + props)
-            new, acc, stop = spec_accept(torch.argmax(rows, dim=-1).tolist(), props, eos, budget=max_new_tokens - made,
-                                         room=self.cache_len - P)
+            k = max(0, min(int(num_draft), self.max_rows - 1, max_new_tokens - made - 1, self.cache_len - self._host_pos - 1))
+            props = draft.propose(out, k) if k > 0 else []
+            drawn = select.rows(self, [out[-1]] + props)
             stats["rounds"] += 1
             stats["target_steps"] += 1
-            stats["proposed"] += len(props)
-            stats["accepted"] += acc
-            self.rewind(P + len(new))                              # t and the accepted proposals stay cached
-            self.logits.copy_(rows[len(new) - 1])
-            if d_eng is not None and d_pos > len(out):             # the draft keeps out + the accepted proposals it had cached
-                d_pos = min(d_pos, len(out) + acc)
-                d_eng.rewind(d_pos)
+            new, acc, stop = self._spec_keep(drawn, props, eos, max_new_tokens - made, self.rlogits)
+            select.recount(self, [], new)
+            draft.settle(out, new, acc, props)
             out += new
             made += len(new)
             if stop:
@@ -1409,96 +1566,15 @@ class DecodeEngine(_DecodeBase):
                              eos_token_id=None, prefill: bool = True):
         """Speculative decoding under seeded sampling: returns, token for token, the ids of
         generate(context_ids, max_new_tokens, sampling=sampling, stream=stream, ...).  Token n of a sequence is a function of its logits,
-        the request, the stream and n alone, so no rejection scheme is needed: the first token comes from sample(); then per round, with t
-        the last token (not yet cached) and P the position, k proposals (k bounded as in the greedy path), ONE step_tokens([t, d1..dk])
-        with mq_sample_rows drawing every row at its own index (one graph after capture()), one read-back of the T tokens, spec_accept
-        on them and rewind to P + the kept tokens; under a penalised request row j sees the history plus d1..dj, and the kept tokens are
-        then counted with history_count(+1).  draft: another DecodeEngine of the same vocabulary size, or a callable draft(ids, k).  An
-        engine draft is set to the SAME sampling and stream and proposes with its own sample_step() / sample(): it shares the Gumbel
-        noise with the target, so it is accepted wherever its logits are close (a self-draft: always); its history is brought back to
-        the sequence's with history_count (-1 for the rejected proposals, +1 for the token that replaced them and for the first token),
-        its cache with extend / rewind.  self.spec_stats counts the rounds.  Afterwards the caches hold out[:position()]."""
+        the request, the stream and n alone, so no rejection scheme is needed: the first token comes from sample(); then per round
+        (_speculate) ONE step_tokens([t, d1..dk]) with mq_sample_rows drawing every row at its own index (one graph after capture()),
+        one read-back of the T tokens, spec_accept on them and rewind to P + the kept tokens; under a penalised request row j sees the
+        history plus d1..dj, and the kept tokens are then counted with history_count(+1).  draft: another DecodeEngine of the same
+        vocabulary size, or a callable draft(ids, k).  An engine draft is set to the SAME sampling and stream and proposes with its own
+        sample_step() / sample(): it shares the Gumbel noise with the target, so it is accepted wherever its logits are close (a
+        self-draft: always); its history is brought back to the sequence's with history_count (-1 for the rejected proposals, +1 for the
+        token that replaced them and for the first token), its cache with extend / rewind.  self.spec_stats counts the rounds."""
         if not isinstance(sampling, SamplingParams):
             raise TypeError(f"DecodeEngine.generate_speculative: sampling must be SamplingParams, got {type(sampling).__name__}")
-        stream = check_stream(stream)
-        d_eng = draft if isinstance(draft, DecodeEngine) else None
-        if d_eng is self:
-            raise ValueError("DecodeEngine.generate_speculative: the draft must be another engine (it keeps its own cache)")
-        if d_eng is None and not callable(draft):
-            raise TypeError("DecodeEngine.generate_speculative: draft must be a DecodeEngine or a callable draft(ids, k) -> list of token ids")
-        if isinstance(num_draft, bool) or int(num_draft) < 0:
-            raise ValueError(f"DecodeEngine.generate_speculative: num_draft={num_draft} must be >= 0")
-        if d_eng is not None and d_eng.shape.vocab != self.shape.vocab:
-            raise ValueError(f"DecodeEngine.generate_speculative: draft vocabulary {d_eng.shape.vocab} != target vocabulary {self.shape.vocab}")
-        ids = [int(t) for t in context_ids]
-        assert len(ids) + max_new_tokens <= self.cache_len
-        eos = _eos_set(eos_token_id)
-        stats = self.spec_stats = {"rounds": 0, "proposed": 0, "accepted": 0, "target_steps": 0}
-        self.set_sampling(sampling, stream)
-        self._start_sequence(ids, prefill)
-        penalized = self._sampler.penalized
-        if penalized:
-            self._sampler.observe_prompt(0, ids)                   # the history is rebuilt for every sequence
-        out = list(ids)
-        if max_new_tokens <= 0:
-            return out
-        dev_ids = lambda v: torch.tensor(v, dtype=torch.int64, device=self.dev)      # noqa: E731
-        d_pos = 0                                                  # the draft engine's cache holds out[:d_pos]
-        if d_eng is not None:
-            d_eng.set_sampling(sampling, stream)
-            d_eng._start_sequence(ids, prefill)
-            d_pos = len(ids)
-            if penalized:
-                d_eng._sampler.observe_prompt(0, ids)
-            d_buf = torch.zeros(self.max_rows, dtype=torch.int64, device=d_eng.dev)
-        self.sample()                                              # token len(ids), counted in the history by the launch itself
-        nxt = int(self.tok.item())
-        out.append(nxt)
-        made = 1
-        if d_eng is not None and penalized:
-            history_count(d_eng._sampler.history[0], dev_ids([nxt]).to(d_eng.dev), 1)
-        if nxt in eos or made >= max_new_tokens or self._host_pos >= self.cache_len:
-            return out
-        while True:
-            P = self._host_pos
-            k = max(0, min(int(num_draft), self.max_rows - 1, max_new_tokens - made - 1, self.cache_len - P - 1))
-            props: List[int] = []
-            if k > 0 and d_eng is not None:
-                kd = min(k, d_eng.cache_len - len(out))             # (its last draw, at index len(out) + kd - 1, must not be an idle row)
-                if kd > 0:
-                    d_eng.extend(out[d_pos:])                      # its logits: behind out, the row token len(out) is drawn from
-                    for i in range(kd):                            # d(i+1) at index len(out) + i, counted in the draft's own history
-                        if i < kd - 1:
-                            d_eng.sample_step()
-                        else:
-                            d_eng.sample()
-                        d_buf[i:i + 1].copy_(d_eng.tok)
-                    props = d_buf[:kd].tolist()
-                    d_pos = len(out) + kd - 1                      # out + props[:-1]
-            elif k > 0:
-                props = [int(v) for v in draft(list(out), k)][:k]
-            T = 1 + len(props)
-            drawn = self.step_sample_tokens([out[-1]] + props).tolist()      # ONE read-back of the T tokens
-            new, acc, stop = spec_accept(drawn, props, eos, budget=max_new_tokens - made, room=self.cache_len - P)
-            stats["rounds"] += 1
-            stats["target_steps"] += 1
-            stats["proposed"] += len(props)
-            stats["accepted"] += acc
-            self.rewind(P + len(new))                              # t and the accepted proposals stay cached
-            self.logits.copy_(self.rlogits[len(new) - 1])
-            if penalized:
-                history_count(self._sampler.history[0], dev_ids(new), 1)
-            if d_eng is not None:
-                if penalized:                                      # the draft counted every proposal: back to the sequence's truth, out + new
-                    h = d_eng._sampler.history[0]
-                    if props[acc:]:
-                        history_count(h, dev_ids(props[acc:]).to(d_eng.dev), -1)
-                    if new[acc:]:
-                        history_count(h, dev_ids(new[acc:]).to(d_eng.dev), 1)
-                if d_pos > len(out):                               # the draft keeps out + the accepted proposals it had cached
-                    d_pos = min(d_pos, len(out) + acc)
-                    d_eng.rewind(d_pos)
-            out += new
-            made += len(new)
-            if stop:
-                return out
+        return self._speculate("DecodeEngine.generate_speculative", context_ids, max_new_tokens, eos_token_id, prefill,
+                               _Sampled(sampling, check_stream(stream)), draft, num_draft)

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .decode import DecodeEngine, _DecodeBase, _eos_set, _Target, plan_rows, spec_accept, spec_row_budget
+from .decode import DecodeEngine, _check_draft, _DecodeBase, _eos_set, _spec_stats, _Target, plan_rows, spec_row_budget
 from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
 
 MAX_BATCH = 8
@@ -128,34 +128,16 @@ class BatchDecodeEngine(_DecodeBase):
         return self
 
     # -- ragged steps: several tokens per slot (csrc/mq_decode_ragged.hip) ----------------------------------------
-    _ENTRY_ROWS = {"gemv": "mq_decode_gemv_batch", "gemv_grouped": "mq_decode_gemv_grouped", "attn_ragged": "mq_decode_attention_ragged"}
-
     def _lower_rows(self):
-        """The launch records of a ragged step: per layer the five-launch chain over max_rows rows (mq_decode_gemv_batch / _grouped,
-        mq_decode_attention_ragged over the engine's own caches) on the norms and weight images the slot chain already holds
-        (self._images: no weight is stored twice), plus mq_decode_head_batch.  Row buffers of their own; the row count is set per
-        launch (_set_rows).  The plan of a step -- tokens, row table, where each row's logits go, the slots' position advance -- is
-        ONE packed int32 buffer (rplan), written by one host -> device copy; rtok / row_dst (int64) and row_seq / row_pos / radv
-        (int32) are views of it."""
-        s, dev, R, B = self.shape, self.dev, self.max_rows, self.batch
-        H, D = s.heads, s.head_dim
-        self.rx = torch.zeros(R, s.hidden, device=dev)
-        self.rqkv = torch.zeros(R, self.qkv.shape[1], device=dev)
-        self.rattn_q = torch.zeros(R, H * D, dtype=torch.int8, device=dev)
-        self.rpart = torch.zeros(R, self.LONG_SPLITS, H * D, dtype=torch.int64, device=dev)
-        self.rticket = torch.zeros(R, H, dtype=torch.int32, device=dev)
-        self.rgate = torch.zeros(R, s.ffn, dtype=torch.int8, device=dev)
-        self.rlogits = torch.zeros(R, s.vocab, device=dev)
-        self.rplan = torch.zeros(6 * R + B, dtype=torch.int32, device=dev)
+        """The launch records of a ragged step (_lower_row_chain): mq_decode_attention_ragged over the engine's own caches.  The plan
+        of a step -- tokens, row table, where each row's logits go, the slots' position advance -- is ONE packed int32 buffer (rplan),
+        written by one host -> device copy; rtok / row_dst (int64) and row_seq / row_pos / radv (int32) are views of it."""
+        R, B = self.max_rows, self.batch
+        self.rplan = torch.zeros(6 * R + B, dtype=torch.int32, device=self.dev)
         self.rtok, self.row_dst = self.rplan[:2 * R].view(torch.int64), self.rplan[2 * R:4 * R].view(torch.int64)
         self.row_seq, self.row_pos, self.radv = self.rplan[4 * R:5 * R], self.rplan[5 * R:6 * R], self.rplan[6 * R:]
         self._upload_plan(None)
-        t = _Target(self.rx, self.rqkv, self.rattn_q, self.rpart, self.rticket, self.rgate, self.k_cache, self.v_cache, nsplit=self.LONG_SPLITS,
-                    rows=R, attn="ragged", batch=B, row_seq=self.row_seq, row_pos=self.row_pos)
-        with torch.no_grad():
-            phases = [p for li, im in enumerate(self._images) for p in self._lower_chain(li, im, t)]
-        self._rows = (phases, self._head_batch(self.rx, self.rlogits, R, pos=self.row_pos))
-        self._row_graphs = {}
+        self._lower_row_chain(head_pos=self.row_pos, attn="ragged", batch=B, row_seq=self.row_seq, row_pos=self.row_pos)
 
     def _upload_plan(self, plan):
         """A plan_rows plan (None: every row idle, no slot advances) into rplan: one host -> device copy.  An idle row names
@@ -172,26 +154,6 @@ class BatchDecodeEngine(_DecodeBase):
                 dst[r0 + cnt - 1] = slot
                 h[6 * R + slot] = cnt
         self.rplan.copy_(torch.from_numpy(h), non_blocking=False)
-
-    def _set_rows(self, R: int):
-        phases, hb = self._rows
-        for kind, a in phases:
-            if kind == "gemv":
-                a.batch = R
-            elif kind == "gemv_grouped":
-                a.b.batch = R
-            else:
-                a.rows = R
-        hb.batch = R
-
-    def _launch_rows(self, R: int):
-        """Embedding rows + 5 launches per layer over R rows + norm / lm_head for R rows, on the current stream (reads rplan)."""
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        phases, hb = self._rows
-        torch.index_select(self.embed, 0, self.rtok[:R], out=self.rx[:R])
-        for kind, a in phases:
-            _lib.call(self._ENTRY_ROWS[kind], ctypes.byref(a), st)
-        _lib.call("mq_decode_head_batch", ctypes.byref(hb), st)
 
     def _finish_rows(self, R: int):
         """logits[slot] <- the slot's last row (the others, idle ones included, land in the spare row) and the slots' position advance:
@@ -389,7 +351,7 @@ class BatchDecodeEngine(_DecodeBase):
         self.set_position(slot, n)
 
     @torch.no_grad()
-    def _step_slot(self, slot: int, tokens: Sequence[int]):
+    def _step_seq(self, tokens: Sequence[int], slot: int):
         """step() for ONE slot, token by token: the other active slots are parked at the cache_len sentinel for the duration (an idle
         slot's cache and logits row do not change) and get their positions back afterwards."""
         others = [b for b in range(self.batch) if b != slot and self._active[b]]
@@ -406,34 +368,14 @@ class BatchDecodeEngine(_DecodeBase):
                 self._active[b] = True
                 self.pos[b] = saved[b]
 
-    @torch.no_grad()
-    def _prefill_append(self, slot: int, context_ids) -> torch.Tensor:
-        t = [int(v) for v in context_ids]
-        if not self._active[slot]:
-            raise RuntimeError(f"BatchDecodeEngine.prefill: slot {slot} is idle: append continues a live sequence (prefill() or start() it first)")
-        P = self._host_pos[slot]
-        if not t:
-            raise ValueError("BatchDecodeEngine.prefill: no tokens to append")
-        if P + len(t) > self.cache_len:
-            raise RuntimeError(f"BatchDecodeEngine.prefill: {len(t)} tokens appended at position {P} overflow slot {slot}'s KV cache "
-                               f"({self.cache_len} positions)")
-        if P == 0:
-            self.append_stats = {"stepped": 0, "prefilled": len(t), "reason": None}
-            return self.prefill(slot, t)
-        self._sync_grids()
-        head, reason = self._append_split(P, len(t))
-        if head:
-            self._step_slot(slot, t[:head])
-        if head < len(t):
-            row = self._append_chunk(t[head:], P + head, lambda li: (self.k_cache[li][slot], self.v_cache[li][slot]), False)
-            if row is None:
-                reason = "the model's attention refused the image cache"
-                self._step_slot(slot, t[head:])
-                head = len(t)
-            else:
-                self.set_position(slot, P + len(t))
-                self.logits[slot].copy_(row)
-        self.append_stats = {"stepped": head, "prefilled": len(t) - head, "reason": reason}
+    # a slot's sequence as _DecodeBase's prefill and speculative bodies see it
+    def _seq_caches(self, li: int, slot: int):
+        return self.k_cache[li][slot], self.v_cache[li][slot]
+
+    def _store_values(self, li: int, values: torch.Tensor, slot: int):
+        self.v_cache[li][slot, :, :values.shape[1]] = values
+
+    def _logits_row(self, slot: int) -> torch.Tensor:
         return self.logits[slot]
 
     @torch.no_grad()
@@ -445,23 +387,11 @@ class BatchDecodeEngine(_DecodeBase):
         the slot's caches are imported and written in place through their head strides.  The stepped tokens run as single-slot steps
         with the other slots parked; their caches, positions and logits rows do not change."""
         self._check_slot(slot)
-        if append:
-            return self._prefill_append(slot, context_ids)
-        ids = torch.as_tensor([int(t) for t in context_ids], dtype=torch.long, device=self.dev).view(1, -1)
-        S = ids.shape[1]
-        assert 0 < S <= self.cache_len
-        self._sync_grids()
-        raw = self.model.new_cache(1, S, device=self.dev)
-        logits = self.model(ids, cache=raw, last_logits_only=True)
-        for li, layer in enumerate(self.model.layers):
-            att = layer.self_attn
-            self.k_cache[li][slot].zero_()
-            self.v_cache[li][slot].zero_()
-            self.k_cache[li][slot, :, :S] = att.qk_bmm.input2_quantizer.quantize_to_int(raw[li][0][0].contiguous())[0]
-            self.v_cache[li][slot, :, :S] = att.pv_bmm.input2_quantizer.quantize_to_int(raw[li][1][0].contiguous())[0]
-        self.set_position(slot, S)
-        self.logits[slot].copy_(logits[0, -1])
-        return self.logits[slot]
+        if not append:
+            return self._prefill_fill(context_ids, True, slot)
+        if not self._active[slot]:
+            raise RuntimeError(f"BatchDecodeEngine.prefill: slot {slot} is idle: append continues a live sequence (prefill() or start() it first)")
+        return self._prefill_append(context_ids, slot)
 
     def start(self, slot: int):
         """Make the slot active at position 0 with an empty cache (a sequence fed token by token through step())."""
@@ -517,17 +447,15 @@ class BatchDecodeEngine(_DecodeBase):
                 validate_generate_args("BatchDecodeEngine.generate", sampling, do_sample, draft)
             if do_sample:
                 raise ValueError("BatchDecodeEngine.generate: a draft is for greedy decoding only (do_sample=True with a draft)")
-            drafts = [draft] * n if callable(draft) and not isinstance(draft, _DecodeBase) else draft
-            if isinstance(drafts, _DecodeBase) or (isinstance(drafts, (list, tuple)) and any(isinstance(d, _DecodeBase) for d in drafts)):
+            drafts = list(draft) if isinstance(draft, (list, tuple)) else [draft] * n
+            if any(isinstance(d, _DecodeBase) for d in drafts):
                 raise TypeError("BatchDecodeEngine.generate: an engine cannot draft for a batch: pass callable drafts, draft(ids, k) -> list of "
                                 "token ids (one for all prompts or one per prompt)")
-            if not isinstance(drafts, (list, tuple)) or any(not callable(d) for d in drafts):
-                raise TypeError("BatchDecodeEngine.generate: draft must be a callable draft(ids, k) -> list of token ids, or a sequence of "
-                                "such callable drafts, one per prompt")
+            for d in drafts:
+                _check_draft("BatchDecodeEngine.generate", self, d, num_draft, (), "a callable draft(ids, k) -> list of token ids, or a sequence "
+                             "of such callable drafts, one per prompt")
             if len(drafts) != n:
                 raise ValueError(f"BatchDecodeEngine.generate: {len(drafts)} drafts for {n} prompts")
-            if isinstance(num_draft, bool) or int(num_draft) < 0:
-                raise ValueError(f"BatchDecodeEngine.generate: num_draft={num_draft} must be >= 0")
         if sampling is not None:
             validate_generate_args("BatchDecodeEngine.generate", sampling, do_sample)
             rows = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
@@ -605,7 +533,7 @@ class BatchDecodeEngine(_DecodeBase):
         rewind(slot, P_i + kept) drops the rest.  The stops are plain generate's: EOS, max_new_tokens, the cache end.  More live slots
         than max_rows (an engine whose shape lowered max_rows below its batch) take a plain step() instead."""
         n = len(outs)
-        stats = self.spec_stats = {"rounds": 0, "proposed": 0, "accepted": 0, "target_steps": 0}
+        stats = self.spec_stats = _spec_stats()
         made, live = [0] * n, []
         first = torch.argmax(self.logits, dim=-1).tolist()
         for i in range(n):
@@ -624,7 +552,7 @@ class BatchDecodeEngine(_DecodeBase):
                 arg = torch.argmax(self.logits, dim=-1).tolist()
                 props = {i: [] for i in live}
                 rows = {i: [arg[i]] for i in live}
-                views = None
+                views = {}
             else:
                 ks = spec_row_budget(num_draft, self.max_rows, [max_new_tokens - made[i] for i in live], [self.cache_len - P[i] for i in live])
                 props = {i: ([int(v) for v in drafts[i](list(outs[i]), k)][:k] if k > 0 else []) for i, k in zip(live, ks)}
@@ -635,12 +563,7 @@ class BatchDecodeEngine(_DecodeBase):
                     rows[i] = arg[r0:r0 + 1 + len(props[i])]
                     r0 += 1 + len(props[i])
             for i in list(live):
-                new, acc, stop = spec_accept(rows[i], props[i], eos, budget=max_new_tokens - made[i], room=self.cache_len - P[i])
-                stats["proposed"] += len(props[i])
-                stats["accepted"] += acc
-                if views is not None:
-                    self.rewind(i, P[i] + len(new))                # t and the accepted proposals stay cached
-                    self.logits[i].copy_(views[i][len(new) - 1])
+                new, _, stop = self._spec_keep(rows[i], props[i], eos, max_new_tokens - made[i], views.get(i), i)
                 outs[i] += new
                 made[i] += len(new)
                 if stop:
