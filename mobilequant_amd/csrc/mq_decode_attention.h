@@ -1,8 +1,8 @@
 // The five-launch decode attention, phase by phase: ONE text for decode_attention_kernel<D> (mq_decode.hip: one token of one
 // sequence), decode_attention_batch_kernel<D> (mq_decode_batch.hip: one token of each of B sequences) and
-// decode_attention_multi_kernel<D, VCH> (mq_decode_multi.hip: consecutive positions of one sequence).  Their contract -- row b / row j
-// computes the single-sequence launch's bits -- holds because they run THESE expressions in THESE reduction orders; a kernel adds only
-// its indexing, where its new keys and values live, and what is truly its own.
+// decode_attention_rows_kernel<D, VCH, TABLE> (mq_decode_rows.hip: consecutive positions of one sequence, or table rows over a batch of
+// caches).  Their contract -- row b / row j / row r computes the single-sequence launch's bits -- holds because they run THESE expressions
+// in THESE reduction orders; a kernel adds only its indexing, where its new keys and values live, and what is truly its own.
 // The phases are statement macros (MQ_ATTN_*), expanded in the kernel's own scope, not functions: the kernels then compile to the
 // instruction streams of the spelled-out text (loop peeling, register count and block layout depend on the form), and a `return` in a
 // phase leaves the kernel.  Each phase lists the names it needs and the names it defines; common to all: D (head_dim), the argument
@@ -17,7 +17,8 @@
 //   MQ_ATTN_SPLIT_BLOCKS, MQ_ATTN_PV_FLAT      exact integer p.v over this split's cached blocks
 //   MQ_ATTN_PV_ADD_NEW, MQ_ATTN_FOLD_GROUPS    one new position from LDS; the zero-point fold and the groups' sums to s_acc
 //   MQ_ATTN_FINISH                             position groups -> head; the split protocol; pv_bmm's output grid, the consumer's image
-// Also the host checks the three entries share.  Compiled under each includer's flags, as the prologue in mq_decode_common.h.
+// Also the host checks the entries share and the launch of those with a (heads, nsplit, rows) grid.  Compiled under each includer's
+// flags, as the prologue in mq_decode_common.h.
 #pragma once
 #include "mq_decode_common.h"
 
@@ -27,7 +28,7 @@ namespace mq {
 
 // One element d of a new token's q / k / v row on its 8-bit attention input grid, as stored (index - 128): RoPE (rotate-half over the
 // first rot dimensions: x * cos + rot(x) * sin) then the grid -- MQ_ATTN_NEW_TOKEN's expressions as a function, for the launch
-// that builds new rows in a loop (mq_decode_multi.hip).  par: the element's RoPE partner; rot = 0: no rotation (v).
+// that builds new rows in a loop (mq_decode_rows.hip).  par: the element's RoPE partner; rot = 0: no rotation (v).
 __device__ __forceinline__ int8_t attn_new_elem(float raw, float par, float cs, float sn, int d, int rot, const Grid& g) {
   float x = raw;
   if (d < rot) {
@@ -283,12 +284,12 @@ __device__ __forceinline__ float attn_score(int dot, int ks, int zq, int qconst,
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 // The largest cache_len the five-launch attention serves: LDS per workgroup on gfx950 (160 KiB) = static + 4 B per cached position
-// (scores); the static arrays are <= 9008 B (single, batched) / 12592 B (multi: the new rows' keys and values) at head_dim 256, so
+// (scores); the static arrays are <= 9008 B (single, batched) / 12592 B (rows: the new rows' keys and values) at head_dim 256, so
 // 4 x 32768 fits everywhere and this is the bound.  mobilequant_amd/decode.py mirrors it to choose the chain.
 constexpr int kAttnMaxCache = 32768;
 
-// What mq_decode_attention, _batch and _multi require of the argument block they share, in two parts (the multi entry's own checks
-// stand between them); `entry` names the caller in the message.
+// What mq_decode_attention, _batch, _multi and _ragged require of the argument block they share, in two parts (the value layout's
+// checks of check_row_run_attention stand between them); `entry` names the caller in the message.
 inline int check_five_launch_attention_shape(const char* entry, const mq_decode_attention_args& a) {
   MQ_REQUIRE(a.qkv && a.k_cache && a.v_cache && a.cos && a.sin && a.pos && a.consts && (a.out || a.out_q), "%s: null pointer", entry);
   MQ_REQUIRE(a.heads > 0 && a.kv_heads > 0 && a.heads % a.kv_heads == 0 && (a.head_dim == 32 || a.head_dim == 64 || a.head_dim == 128 || a.head_dim == 256) &&
@@ -309,6 +310,43 @@ inline int check_five_launch_attention_grids(const char* entry, const mq_decode_
 inline int check_five_launch_attention(const char* entry, const mq_decode_attention_args& a) {
   const int rc = check_five_launch_attention_shape(entry, a);
   return rc != MQ_OK ? rc : check_five_launch_attention_grids(entry, a);
+}
+// What mq_decode_attention_multi and _ragged (mq_decode_rows.hip) both require: the row count, the shared block (the value layout's
+// checks between its two parts; the ragged entry serves the flat layout only and passes 0), no prefetch rows, a stride that covers a row.
+inline int check_row_run_attention(const char* entry, const mq_decode_attention_args& a, int rows, int64_t qkv_stride, int v_chunked) {
+  MQ_REQUIRE(rows >= 1 && rows <= MQ_DECODE_MAX_BATCH, "%s: rows=%d outside 1..%d", entry, rows, MQ_DECODE_MAX_BATCH);
+  int rc = check_five_launch_attention_shape(entry, a);
+  if (rc != MQ_OK) return rc;
+  MQ_REQUIRE(v_chunked == 0 || v_chunked == 1, "%s: v_chunked=%d (0 or 1)", entry, v_chunked);
+  MQ_REQUIRE(!v_chunked || a.cache_len % 16 == 0, "%s: v_chunked needs cache_len %% 16 == 0 (cache_len=%d)", entry, a.cache_len);
+  rc = check_five_launch_attention_grids(entry, a);
+  if (rc != MQ_OK) return rc;
+  MQ_REQUIRE(a.prefetch_wgs == 0, "%s: no prefetch rows (prefetch_wgs must be 0)", entry);
+  MQ_REQUIRE(rows == 1 || qkv_stride >= (int64_t)(a.heads + 2 * a.kv_heads) * a.head_dim, "%s: qkv_stride must cover a q | k | v row", entry);
+  return MQ_OK;
+}
+
+// The launch of the entries with a (heads, nsplit, rows) grid -- mq_decode_attention_batch, _multi, _ragged -- on a checked block:
+// 4 bytes of dynamic LDS per cached position (the scores), the kernel's LDS ceiling raised once per kernel and device (the function-local
+// cache: one per instantiation).  Kernels: a type whose member template kernel<D> is the entry's kernel at head_dim D.
+template <auto Kernel, class Args>
+inline int launch_attention_rows_kernel(const char* entry, const Args& args, const mq_decode_attention_args& a, int rows, mq_stream_t stream) {
+  static std::atomic<size_t> lds_set[kMaxDevices];
+  const size_t lds = (size_t)a.cache_len * sizeof(float);
+  const int rc = set_lds(reinterpret_cast<const void*>(Kernel), lds_set, lds, entry);
+  if (rc != MQ_OK) return rc;
+  Kernel<<<dim3((unsigned)a.heads, (unsigned)a.nsplit, (unsigned)rows), 256, lds, as_stream(stream)>>>(args);
+  MQ_LAUNCH_CHECK(entry);
+  return MQ_OK;
+}
+template <class Kernels, class Args>
+inline int launch_attention_rows(const char* entry, const Args& args, const mq_decode_attention_args& a, int rows, mq_stream_t stream) {
+  switch (a.head_dim) {
+    case 32: return launch_attention_rows_kernel<Kernels::template kernel<32>>(entry, args, a, rows, stream);
+    case 64: return launch_attention_rows_kernel<Kernels::template kernel<64>>(entry, args, a, rows, stream);
+    case 128: return launch_attention_rows_kernel<Kernels::template kernel<128>>(entry, args, a, rows, stream);
+    default: return launch_attention_rows_kernel<Kernels::template kernel<256>>(entry, args, a, rows, stream);
+  }
 }
 
 }  // namespace mq

@@ -231,6 +231,11 @@ __global__ void __launch_bounds__(256) decode_attention_batch_kernel(const mq_de
                  const size_t o = ((size_t)sb * H + h) * D + tid;, o)
 }
 
+struct BatchKernels {
+  template <int D>
+  static constexpr auto kernel = decode_attention_batch_kernel<D>;
+};
+
 // ---- final norm for B rows + the fp32 lm_head streamed once -----------------------------------------------------------------------
 // decode_head_kernel's arithmetic per row: the norm's reductions over 256 threads (i = tid, tid + 256, ...), wave_sum_f_rowbcast, the four wave
 // partials as (w0 + w1) + (w2 + w3); a vocabulary row per wave, lane l summing float4 chunks l, l + 64, ... ascending with four adds
@@ -458,24 +463,7 @@ int mq_decode_attention_batch(const mq_decode_attention_batch_args* args, mq_str
   if (rc != MQ_OK) return rc;
   MQ_REQUIRE(a.prefetch_wgs == 0, "mq_decode_attention_batch: no prefetch rows (prefetch_wgs must be 0)");
   MQ_REQUIRE(B == 1 || args->qkv_stride >= (int64_t)(a.heads + 2 * a.kv_heads) * a.head_dim, "mq_decode_attention_batch: qkv_stride must cover a q | k | v row");
-  const size_t lds = (size_t)a.cache_len * sizeof(float);
-  const void* fn = a.head_dim == 32 ? reinterpret_cast<const void*>(decode_attention_batch_kernel<32>)
-                   : a.head_dim == 64 ? reinterpret_cast<const void*>(decode_attention_batch_kernel<64>)
-                   : a.head_dim == 128 ? reinterpret_cast<const void*>(decode_attention_batch_kernel<128>)
-                                       : reinterpret_cast<const void*>(decode_attention_batch_kernel<256>);
-  static std::atomic<size_t> lds_set[4][kMaxDevices];
-  rc = set_lds(fn, lds_set[a.head_dim == 32 ? 0 : a.head_dim == 64 ? 1 : a.head_dim == 128 ? 2 : 3], lds, "mq_decode_attention_batch");
-  if (rc != MQ_OK) return rc;
-  const dim3 grid((unsigned)a.heads, (unsigned)a.nsplit, (unsigned)B);
-  hipStream_t st = as_stream(stream);
-  switch (a.head_dim) {
-    case 32: decode_attention_batch_kernel<32><<<grid, 256, lds, st>>>(*args); break;
-    case 64: decode_attention_batch_kernel<64><<<grid, 256, lds, st>>>(*args); break;
-    case 128: decode_attention_batch_kernel<128><<<grid, 256, lds, st>>>(*args); break;
-    default: decode_attention_batch_kernel<256><<<grid, 256, lds, st>>>(*args); break;
-  }
-  MQ_LAUNCH_CHECK("mq_decode_attention_batch");
-  return MQ_OK;
+  return launch_attention_rows<BatchKernels>("mq_decode_attention_batch", *args, a, B, stream);
 }
 
 int mq_decode_head_batch(const mq_decode_head_batch_args* args, mq_stream_t stream) {

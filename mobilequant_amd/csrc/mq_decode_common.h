@@ -1,5 +1,5 @@
 // Device helpers shared by the single-sequence decode kernels (mq_decode.hip), the batched ones (mq_decode_batch.hip), the grouped
-// GEMV (mq_decode_grouped.hip) and the multi-token attention (mq_decode_multi.hip): the
+// GEMV (mq_decode_grouped.hip) and the multi-token / ragged attention (mq_decode_rows.hip): the
 // launch-constants line, the layout constants the families agree on, the batched GEMV's prologue and epilogue and the GEMV launches'
 // row geometry.  The five-launch attention's phases build on this header in mq_decode_attention.h.
 #pragma once

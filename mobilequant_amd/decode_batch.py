@@ -14,7 +14,7 @@ its logits row do not change.
 
 Ragged steps: ``step_tokens`` / ``extend`` move chosen slots by several tokens in ONE step while the others stand
 still, ``rewind`` drops a slot's last positions, and ``generate(draft=...)`` is greedy speculative decoding across the batch.  Their
-rows run the same weight launches over row buffers of their own and ``mq_decode_attention_ragged`` (csrc/mq_decode_ragged.hip), whose
+rows run the same weight launches over row buffers of their own and ``mq_decode_attention_ragged`` (csrc/mq_decode_rows.hip), whose
 row table -- like the tokens and the position advance -- is device data: one hipGraph per total row count serves every plan.
 """
 from __future__ import annotations
@@ -127,7 +127,7 @@ class BatchDecodeEngine(_DecodeBase):
         self._row_graphs = {}                     # (ragged steps: one graph per total row count, recorded on first use)
         return self
 
-    # -- ragged steps: several tokens per slot (csrc/mq_decode_ragged.hip) ----------------------------------------
+    # -- ragged steps: several tokens per slot (csrc/mq_decode_rows.hip) ----------------------------------------
     def _lower_rows(self):
         """The launch records of a ragged step (_lower_row_chain): mq_decode_attention_ragged over the engine's own caches.  The plan
         of a step -- tokens, row table, where each row's logits go, the slots' position advance -- is ONE packed int32 buffer (rplan),

@@ -1,4 +1,4 @@
-"""GPU: multi-token decode steps and speculative greedy generation (csrc/mq_decode_multi.hip, DecodeEngine.step_tokens / extend /
+"""GPU: multi-token decode steps and speculative greedy generation (csrc/mq_decode_rows.hip, DecodeEngine.step_tokens / extend /
 rewind / generate(draft=...)).
 
 The single-token path is the oracle and the bar is bit identity.  Kernel: mq_decode_attention_multi against `rows` sequential

@@ -1,4 +1,4 @@
-"""GPU: ragged decode steps of the batched engine (csrc/mq_decode_ragged.hip, BatchDecodeEngine.step_tokens / extend / rewind /
+"""GPU: ragged decode steps of the batched engine (csrc/mq_decode_rows.hip, BatchDecodeEngine.step_tokens / extend / rewind /
 generate(draft=...)).
 
 The single-token path is the oracle and the bar is bit identity.  Kernel: one mq_decode_attention_ragged launch against sequential
