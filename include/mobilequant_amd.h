@@ -151,7 +151,14 @@ int mq_attention_probs_train_backward(const float* raw, const float* grad_out, i
  * of the quantizer -- the index of x[m,k] / chan_scale[k] (IEEE divide, then the arithmetic above op for op).  This is the
  * run-time form of the scales the reference folds into the weights (`ln.weight /= s; fc.weight *= s`:
  * ptq/smoothquant.py:64-69, mobilellm/quantization/algorithm.py:47-68) for an activation whose producer cannot absorb
- * 1/s; the consumer's integer weights are then formed from weight * s. */
+ * 1/s; the consumer's integer weights are then formed from weight * s.
+ * x of MQ_F16 is widened to fp32 element by element and the whole expression runs in fp32 (NOT mq_fake_quant's per-op half
+ * arithmetic): the index of the half value as an fp32 number.  With chan_scale the quotient x / chan_scale is rounded to fp32 and then
+ * quantized: two roundings.
+ * Non-finite values: integer storage has no NaN.  Where the reference's index is NaN -- x is NaN or +-inf (round_ste makes
+ * inf - inf of an infinite quotient, qmodule.py:17-21), or a finite x whose quotient x / scale (or x / chan_scale) overflows fp32 --
+ * the stored value is qmin - shift, and it enters row_sum as such.  Every finite quotient is rounded half to even and clamped as
+ * above.  mq_quantize_tiled follows the same two rules in both of its kernels. */
 int mq_quantize(const void* x, int dtype, int64_t rows, int64_t cols, const float* scale,
                 const float* offset, int64_t n_scale, float qmin, float qmax, int shift,
                 const float* chan_scale, void* q, int q_dtype, int32_t* row_sum, mq_stream_t stream);
@@ -200,7 +207,8 @@ int mq_w8a8_linear_residual(const int8_t* a, const int8_t* w, int64_t M, int64_t
  * Layout of q_tiled (ceil(rows/16)*16 * cols bytes): 1-KiB blocks of 16 rows x 64 k ordered [row block][k block]; inside
  * a block byte offset 16 * ((row & 15) + 16 * ((k & 63) >> 4)) + (k & 15).  Rows past `rows` are padding.
  * mq_quantize_tiled: per-tensor grid (scale/offset: 1 element), int8 storage (index - shift), cols % 128 == 0; row_sum
- * (nullable) and chan_scale (nullable, [cols], 16-byte aligned, float32 x only) as in mq_quantize. */
+ * (nullable) and chan_scale (nullable, [cols], 16-byte aligned, float32 x only) as in mq_quantize; MQ_F16 x is widened to fp32, and a
+ * NaN, +-inf or overflowing quotient stores qmin - shift, as there.  The bytes of the padding rows are written but unspecified. */
 int mq_gemm_tiled_supported(int64_t M, int64_t N, int64_t K);
 int mq_quantize_tiled(const void* x, int dtype, int64_t rows, int64_t cols, const float* scale,
                       const float* offset, float qmin, float qmax, int shift, const float* chan_scale,

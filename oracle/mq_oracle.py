@@ -175,6 +175,82 @@ def fake_quant_f16_per_tensor(x, scale, offset, qmin: int, qmax: int):
     return (d.astype(F32) * s).astype(H), q
 
 
+def fake_quant_f16_per_row(x, scale, offset, qmin: int, qmax: int):
+    """fp16 input with a [rows, 1] fp32 scale / offset: torch promotes the whole expression to fp32 and the result is cast back to
+    half once (qmodule.py:295; frozen in quantizer_cases.npz) -- fp32 arithmetic on the widened half, ONE final rounding."""
+    x = np.asarray(x, dtype=np.float16)
+    s = np.asarray(scale, dtype=F32).reshape(-1, 1)
+    o = np.asarray(offset, dtype=F32).reshape(-1, 1)
+    with np.errstate(over="ignore"):
+        return fake_quant(x.astype(F32), s, o, qmin, qmax).astype(np.float16)
+
+
+def quantize_storage(x, scale, offset, qmin: int, qmax: int, shift: int, chan_scale=None):
+    """What mq_quantize / mq_quantize_tiled store for a [rows, cols] activation: (stored int64 [rows, cols], row_sum int32 [rows]).
+
+    stored = quantize_index(x) - shift.  scale / offset hold one element (per-tensor) or `rows` (per-row grids, broadcast down the
+    rows).  fp16 input is widened to fp32 first and everything behind is fp32 (NOT the per-op half arithmetic of
+    fake_quant_f16_per_tensor).  chan_scale [cols]: the quotient x / chan_scale is rounded to fp32 and THEN quantized (two roundings:
+    include/mobilequant_amd.h at mq_quantize).  Integer storage has no NaN: where the reference's index is NaN (the input is NaN or
+    +-inf -- round_ste makes inf - inf of it -- or a quotient overflows) the stored value is qmin - shift (csrc/mq_quant.h, storage
+    and image forms: "NaN -> qmin"; csrc/mq_common.h at div_by_scale).  Row sums are exact integer sums of the stored values."""
+    x = np.asarray(x)
+    assert x.ndim == 2 and x.dtype in (np.float32, np.float16)
+    xf = x.astype(F32)
+    rows = xf.shape[0]
+    s = np.asarray(scale, dtype=F32).reshape(-1)
+    o = np.asarray(offset, dtype=F32).reshape(-1)
+    assert s.size == o.size and s.size in (1, rows)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        if chan_scale is not None:
+            xf = (xf / np.asarray(chan_scale, dtype=F32).reshape(1, -1)).astype(F32)
+        idx = quantize_index(xf, s.reshape(-1, 1), o.reshape(-1, 1), qmin, qmax)
+    stored = np.where(np.isnan(idx), F32(qmin), idx).astype(np.int64) - int(shift)
+    rs = stored.sum(axis=1)
+    assert np.all(np.abs(rs) < 2 ** 31)
+    return stored, rs.astype(np.int32)
+
+
+def tiled_offset(row, k, cols):
+    """Byte offset of element (row, k) in the fragment-blocked int8 image (include/mobilequant_amd.h at mq_quantize_tiled): 1-KiB
+    blocks of 16 rows x 64 k ordered [row block][k block]; inside a block byte 16 * ((row & 15) + 16 * ((k & 63) >> 4)) + (k & 15).
+    Plain index arithmetic on integers or integer arrays."""
+    block = (row >> 4) * (cols >> 6) + (k >> 6)
+    return block * 1024 + 16 * ((row & 15) + 16 * ((k & 63) >> 4)) + (k & 15)
+
+
+def tiled_image_bytes(stored, rows, cols):
+    """(image int8 [ceil16(rows) * cols], real bool [same]): `stored` [rows, cols] scattered byte by byte through tiled_offset, and
+    the mask of the bytes that belong to real rows (padding rows are "written, never used": their bytes stay 0 here, unmasked)."""
+    stored = np.asarray(stored)
+    assert stored.shape == (rows, cols) and cols % 64 == 0
+    assert stored.min() >= -128 and stored.max() <= 127
+    n = (rows + 15) // 16 * 16 * cols
+    image, real = np.zeros(n, np.int8), np.zeros(n, bool)
+    r, k = np.meshgrid(np.arange(rows, dtype=np.int64), np.arange(cols, dtype=np.int64), indexing="ij")
+    off = tiled_offset(r, k, cols)
+    image[off] = stored.astype(np.int8)
+    real[off] = True
+    return image, real
+
+
+def linear_epilogue_vectors(a_scale, a_offset, a_shift: int, w_scale, w_offset, w_shift: int, w_colsum, K: int):
+    """(alpha fp32 [N], w_zp int32 [N], col_term int32 [N]) of mq_linear_epilogue_prepare (include/mobilequant_amd.h):
+    alpha = a_scale * w_scale (one fp32 product), w_zp = (int)w_offset - w_shift, col_term = -za * w_colsum + K * za * w_zp with
+    za = (int)a_offset - a_shift, evaluated in Python integers and reduced modulo 2^32 to int32 (two's complement).  w_scale /
+    w_offset hold one element or N."""
+    colsum = np.asarray(w_colsum).reshape(-1)
+    n = colsum.size
+    ws = np.broadcast_to(np.asarray(w_scale, dtype=F32).reshape(-1), (n,))
+    wo = np.broadcast_to(np.asarray(w_offset, dtype=F32).reshape(-1), (n,))
+    alpha = (F32(np.asarray(a_scale).reshape(-1)[0]) * ws).astype(F32)
+    za = int(np.asarray(a_offset).reshape(-1)[0]) - int(a_shift)
+    zw = [int(v) - int(w_shift) for v in wo]
+    term = [(-za * int(c) + int(K) * za * z) % (1 << 32) for c, z in zip(colsum, zw)]
+    term = [t - (1 << 32) if t >= (1 << 31) else t for t in term]
+    return alpha, np.array(zw, dtype=np.int32), np.array(term, dtype=np.int32)
+
+
 class QuantizerOracle:
     """State machine of ``Quantizer`` (qmodule.py:112-295) without autograd.
 
