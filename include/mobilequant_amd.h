@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -970,6 +970,56 @@ int mq_sample_rows(const mq_sample_rows_args* args, mq_stream_t stream);
  * -1), saturating at 65 535 and at 0; bit 31 is kept; an id outside [0, V) is ignored; repeated ids count repeatedly -- the result of
  * applying them one by one.  One launch, capturable. */
 int mq_sample_history_count(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int delta, mq_stream_t stream);
+
+/* rows (1 .. MQ_DECODE_MAX_BATCH) logits rows of a RAGGED step over batch (1 .. MQ_DECODE_MAX_BATCH) sequences (the rule's
+ * extension in csrc/mq_sample.hip's header).  row_seq[rows] / row_pos[rows] (device int32) are the table mq_decode_attention_ragged takes and
+ * row_tok[rows] (device int64) the tokens the rows were stepped with.  A run is a maximal stretch of consecutive rows with equal row_seq
+ * whose row_pos rise by exactly one, as there.  A row whose row_seq is outside [0, batch) or whose row_pos is outside [0, cache_len) is
+ * idle and ends a run: its tok, kept and logprob keep their bytes.  A live row r at distance j from its run's first row, with s =
+ * row_seq[r], is drawn at n = row_pos[r] + n_offset (n_offset in [-2^30, 2^30]) under params[s] (params [batch]), with penalty[s] (penalty
+ * [batch]; NULL: every sequence neutral), the bias bias[s] (bias: NULL, or [batch] device pointers in device memory, each NULL or a 16-byte
+ * aligned dense fp32 [V]: mq_sample_penalized's layout) and the history row history + s * history_stride (history [batch][history_stride];
+ * NULL: all zeros), on which the proposals in front of the row, row_tok[r-j+1 .. r], are counted as it is read:
+ * c_i(j) = min(65535, c_i + #{m in r-j+1 .. r : row_tok[m] == i}), seen_i(j) = (h_i != 0) or (c_i(j) > 0) (mq_sample_rows' formula).  The run's
+ * first token row_tok[r-j] is no proposal: it is the sequence's last accepted token, which the history already holds.  A token outside
+ * [0, V) matches no entry.  A neutral sequence (no penalty row or a neutral one, no bias) keeps the bits of its logits, history or not.
+ * Nothing but tok / kept / logprob / scratch is written; no token is counted (mq_sample_history_count_ragged counts what the caller keeps).
+ * tok[r] and kept[r] (nullable, like logprob[r]) are, bit for bit, what mq_sample_rows draws for row j of that run alone -- sequence s's
+ * request and history, *n_base + n_offset = the run's first index, those proposals -- and what mq_sample / mq_sample_penalized draw for the
+ * row alone from the counted history; logprob[r] is within mq_sample's bound.  The table is device data: row_seq and row_pos are
+ * range-checked on the device before any address is formed from them, so whatever they hold the launch stays inside its buffers.
+ * Limits and alignments of mq_sample; with a penalty or a history, history_stride >= V and % 4 == 0; penalty and history 16-byte, row_tok
+ * and bias 8-byte aligned.  scratch >= MQ_SAMPLE_SCRATCH_BYTES.  Two launches (one while V <= 4096), no host synchronisation: capturable. */
+typedef struct mq_sample_ragged_args {
+  const float* logits;
+  int64_t logits_stride;
+  int64_t V;
+  int rows;  /* 1 .. MQ_DECODE_MAX_BATCH */
+  int batch; /* 1 .. MQ_DECODE_MAX_BATCH */
+  int cache_len;
+  const int* row_seq;
+  const int* row_pos;
+  int n_offset;
+  const int64_t* row_tok;
+  const mq_sample_row* params;
+  const mq_sample_penalty_row* penalty;
+  const uint32_t* history;
+  int64_t history_stride;
+  const float* const* bias;
+  int64_t* tok;
+  int* kept;
+  float* logprob;
+  void* scratch;
+  int64_t scratch_bytes;
+} mq_sample_ragged_args;
+int mq_sample_ragged(const mq_sample_ragged_args* args, mq_stream_t stream);
+/* mq_sample_history_count over a block of histories [batch][history_stride] (batch 1 .. MQ_DECODE_MAX_BATCH; history_stride >= V and % 4 ==
+ * 0): pairs [n][2] of int64 in DEVICE memory, pairs[j] = (sequence, id).  Each pair moves the count of id in its sequence's history by
+ * delta (+1 or -1), saturating at 65 535 and at 0; bit 31 is kept; a pair whose sequence is outside [0, batch) or whose id is outside
+ * [0, V) is ignored; repeated pairs count repeatedly -- the result of applying them one by one.  n = 0 launches nothing.  One launch,
+ * capturable. */
+int mq_sample_history_count_ragged(uint32_t* history, int64_t history_stride, int64_t V, int batch, const int64_t* pairs, int64_t n, int delta,
+                                   mq_stream_t stream);
 
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes

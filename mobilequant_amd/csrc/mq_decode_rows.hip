@@ -23,6 +23,7 @@
 // one dimension per 16-byte request (the four-launch kernel's mapping); the new positions are added from LDS by the split that owns
 // their 64-position block.
 #include "mq_decode_attention.h"
+#include "mq_row_runs.h"
 
 namespace mq {
 
@@ -40,8 +41,7 @@ __global__ void __launch_bounds__(256) decode_attention_rows_kernel(const mq_dec
   if constexpr (TABLE) {
     sb = ra.row_seq[r], pos = ra.row_pos[r];
     if (sb < 0 || sb >= ra.batch || pos < 0 || pos >= CL) return;  // an idle row: nothing is read or written
-    j = 0;                                                         // rows of this run in front of row r (uniform: scalar loads)
-    while (j < r && j < DB_MAXB - 1 && pos - 1 - j >= 0 && ra.row_seq[r - 1 - j] == sb && ra.row_pos[r - 1 - j] == pos - 1 - j) ++j;
+    j = run_rows_in_front(ra.row_seq, ra.row_pos, r, sb, pos, DB_MAXB - 1);      // rows of this run in front of row r (uniform: scalar loads)
   } else {
     const int p0 = a.pos[0];
     j = r, pos = p0 + j;

@@ -57,7 +57,27 @@
 // nothing more is staged in LDS and no pass over V is added.
 // mq_sample_history_count moves the counts of n ids by +1 or -1 (saturating at 65 535 and at 0, bit 31 kept, ids outside [0, V) ignored)
 // with one compare-and-swap loop per id: the result of applying them one by one, in any order.
+//
+// ROWS OF SEVERAL SEQUENCES (mq_sample_ragged).  R <= 8 logits rows of a ragged step: row r belongs to sequence
+// row_seq[r] at cached position row_pos[r], the table mq_decode_attention_ragged reads (device int32), and was stepped with token
+// row_tok[r] (device int64).  Runs are that launch's (mq_row_runs.h): a maximal stretch of consecutive rows with equal row_seq whose
+// row_pos rise by exactly one.  A row whose row_seq is outside [0, batch) or whose row_pos is outside [0, cache_len) is idle and ends a
+// run: its tok, kept and logprob keep their bytes.  A live row r at distance j from its run's first row, with s = row_seq[r], is drawn
+// at n = row_pos[r] + n_offset under params[s], with penalty[s], bias[s] and the history row of s (each of the three arrays nullable: no
+// penalty row is the neutral one, no history is all zeros, no bias array is no bias), and step 0 uses the entry of mq_sample_rows,
+//      c_i(j) = min(65535, c_i + #{m < j : d[m] == i})      seen_i(j) = (h_i != 0) or (c_i(j) > 0)      with d[0 .. j-1] = row_tok[r-j+1 .. r],
+// the proposals in front of the row.  The run's first token row_tok[r-j] is no proposal: it is the sequence's last accepted token and
+// the history holds it already.  A token outside [0, V) matches no entry; a neutral sequence keeps the bits of its logits, history or
+// not; nothing but tok, kept, logprob and scratch is written; there is no observe.  So tok[r] and kept[r] are, bit for bit, what
+// mq_sample_rows draws for row j of that run alone (the sequence's request and history, n_base + n_offset = the run's first index,
+// those proposals) and what mq_sample / mq_sample_penalized draw for the row alone from the counted history.
+// The same two kernels with a fourth load policy, Ragged (sample_scan_ragged_kernel, sample_select_ragged_kernel): the row is the
+// workgroup's blockIdx, so the walk back over the table (at most 7 steps), the request lookup and the at most 7 proposals are
+// wave-uniform scalar loads; row_seq and row_pos are range-checked before any address is formed from them -- the table is device data,
+// and whatever it holds the launch stays inside its buffers.  Behind its constructor the policy IS Rows: no pass over V and no LDS is added.
+// mq_sample_history_count_ragged is mq_sample_history_count over (sequence, id) pairs and a [batch][history_stride] block of histories.
 #include "mq_common.h"
+#include "mq_row_runs.h"
 
 #include <limits.h>
 
@@ -201,6 +221,7 @@ struct Rows {
   float r, a, f;
   bool active;
   int d[SM_MAX_PROPOSALS];        // the proposals in front of this row (wave-uniform), -1: none
+  __device__ __forceinline__ Rows() {}                                 // (Ragged fills the fields itself)
   __device__ __forceinline__ Rows(const RowsArgs& ra, int row) {
     r = 1.f; a = 0.f; f = 0.f;
     if (ra.pen) {
@@ -257,6 +278,45 @@ struct Rows {
   __device__ __forceinline__ void observe(int) const {}               // the caller counts what it keeps (mq_sample_history_count)
 };
 
+// mq_sample_ragged: R rows of up to `batch` sequences, named by the row table of mq_decode_attention_ragged.  A live row reads its
+// sequence's request, penalty row, bias row and history, and the tokens its run was stepped with behind the run's first row are the
+// proposals in front of it; from there on it is a Rows policy.
+struct RaggedArgs {
+  const int* row_seq;                 // [rows] the row's sequence; outside [0, batch): idle
+  const int* row_pos;                 // [rows] the row's cached position; outside [0, cache_len): idle
+  const long long* row_tok;           // [rows] the tokens the rows were stepped with
+  const mq_sample_penalty_row* pen;   // [batch], or nullptr (every sequence neutral)
+  const unsigned* hist;               // [batch][hstride], or nullptr (all zeros)
+  long long hstride;
+  const float* const* bias;           // [batch] device pointers (each nullptr or a dense row), or nullptr
+  int batch, V, n_offset;
+};
+
+struct Ragged : Rows {
+  // only built for a live row (row_index below has range-checked row_seq[row] and row_pos[row])
+  __device__ __forceinline__ Ragged(const RaggedArgs& ga, int row) {
+    const int s = ga.row_seq[row];
+    r = 1.f; a = 0.f; f = 0.f;
+    if (ga.pen) {
+      const mq_sample_penalty_row p = ga.pen[s];
+      r = (p.repetition > 0.f && p.repetition < __builtin_inff()) ? p.repetition : 1.f;
+      a = p.presence; f = p.frequency;
+    }
+    h = ga.hist ? ga.hist + (long long)s * ga.hstride : nullptr;
+    b = ga.bias ? ga.bias[s] : nullptr;
+    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral sequence keeps the bits of its logits, history or not
+    const int j = active ? run_rows_in_front(ga.row_seq, ga.row_pos, row, s, ga.row_pos[row], SM_MAX_PROPOSALS) : 0;
+#pragma unroll
+    for (int m = 0; m < SM_MAX_PROPOSALS; ++m) {
+      d[m] = -1;
+      if (m < j) {                                                  // row_tok[row - j] is the run's first token: no proposal
+        const long long t = ga.row_tok[row - j + 1 + m];
+        if (t >= 0 && t < (long long)ga.V) d[m] = (int)t;
+      }
+    }
+  }
+};
+
 // running best of z + g (greedy: z) over entries [lo, hi) of the row, 4 per thread and step; lo, hi multiples of 4
 template <class Pol>
 __device__ __forceinline__ Best scan_range(const float* __restrict__ row, int lo, int hi, const RowCfg& c, const Pol& p, int tid, int nthreads) {
@@ -304,15 +364,22 @@ __device__ __forceinline__ bool row_idle(const int* pos, int row, int cache_len,
 }
 
 // Which index a row draws at and which request it reads.  mq_sample / mq_sample_penalized: pos[row] with the idle sentinel, params[row].
-// mq_sample_rows: *pos + n_offset + row, never idle, the one request.
+// mq_sample_rows: *pos + n_offset + row, never idle, the one request.  mq_sample_ragged: row_pos[row] + n_offset with the table's idle rows
+// (sequence or position out of range, checked before anything is addressed by them), the request of the row's sequence.
 template <class PolArgs>
 __device__ __forceinline__ bool row_index(const PolArgs&, const int* pos, int row, int cache_len, int* n) { return row_idle(pos, row, cache_len, n); }
 __device__ __forceinline__ bool row_index(const RowsArgs& ra, const int* pos, int row, int, int* n) {
   *n = pos[0] + ra.n_offset + row;
   return false;
 }
+__device__ __forceinline__ bool row_index(const RaggedArgs& ga, const int*, int row, int cache_len, int* n) {
+  const int s = ga.row_seq[row], p = ga.row_pos[row];
+  *n = p + ga.n_offset;
+  return s < 0 || s >= ga.batch || p < 0 || p >= cache_len;
+}
 template <class PolArgs>
 __device__ __forceinline__ int request_of(const PolArgs&, int row) { return row; }
+__device__ __forceinline__ int request_of(const RaggedArgs& ga, int row) { return ga.row_seq[row]; }
 __device__ __forceinline__ int request_of(const RowsArgs&, int) { return 0; }
 
 __device__ __forceinline__ void slice_bounds(int V, int S, int s, int* lo, int* hi) {
@@ -354,6 +421,12 @@ __global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_rows_kernel(const
                                                                            const int* __restrict__ n_base, const mq_sample_row* __restrict__ params,
                                                                            Best* __restrict__ part, RowsArgs ra) {
   sample_scan<Rows>(logits, stride, V, n_base, 0, params, part, ra);
+}
+
+__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_ragged_kernel(const float* __restrict__ logits, long long stride, int V, int cache_len,
+                                                                             const mq_sample_row* __restrict__ params, Best* __restrict__ part,
+                                                                             RaggedArgs ga) {
+  sample_scan<Ragged>(logits, stride, V, ga.row_pos, cache_len, params, part, ga);
 }
 
 // ---- launch 2 ------------------------------------------------------------------------------------------------------------------
@@ -631,6 +704,15 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_rows_kernel(const fl
   sample_select<Rows>(smem, logits, stride, V, S, lds_row, n_base, 0, params, part, tok, kept, logprob, ra);
 }
 
+// mq_sample_ragged: the rows of a ragged step, each under its own sequence's request with the proposals of its run counted as it reads
+__global__ __launch_bounds__(SM_THREADS) void sample_select_ragged_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
+                                                                          int cache_len, const mq_sample_row* __restrict__ params,
+                                                                          const Best* __restrict__ part, long long* __restrict__ tok, int* __restrict__ kept,
+                                                                          float* __restrict__ logprob, RaggedArgs ga) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  sample_select<Ragged>(smem, logits, stride, V, S, lds_row, ga.row_pos, cache_len, params, part, tok, kept, logprob, ga);
+}
+
 __global__ void history_clear_kernel(uint4* __restrict__ h, int n4) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n4) h[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -661,6 +743,25 @@ __global__ void history_count_kernel(unsigned* __restrict__ h, int V, const long
   }
 }
 
+// history_count_kernel over pairs[j] = (sequence, id) and the histories [batch][hstride]: a pair whose sequence is outside [0, batch) or
+// whose id is outside [0, V) is ignored, before anything is addressed by it.
+__global__ void history_count_ragged_kernel(unsigned* __restrict__ h, long long hstride, int V, int batch, const long long* __restrict__ pairs,
+                                            long long n, int delta) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const long long s = pairs[2 * j], t = pairs[2 * j + 1];
+  if (s < 0 || s >= batch || t < 0 || t >= V) return;
+  unsigned* e = h + s * hstride + t;
+  unsigned old = *e;
+  for (;;) {
+    const unsigned c = old & 0xFFFFu;
+    if (delta > 0 ? c == 0xFFFFu : c == 0u) return;
+    const unsigned seen = atomicCAS(e, old, delta > 0 ? old + 1u : old - 1u);
+    if (seen == old) return;
+    old = seen;
+  }
+}
+
 __global__ void sample_uniforms_kernel(unsigned long long seed, unsigned long long stream, unsigned n, long long first, long long count,
                                        float* __restrict__ out) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -675,7 +776,7 @@ size_t select_lds_bytes(int lds_row) {
   return (size_t)lds_row * 4 + (size_t)SM_BINS * 8 + 8 * 8 + 2 * SM_WAVES * 8 + (size_t)SM_BINS * 4 + 2 * SM_WAVES * 4;
 }
 
-PerDeviceOnce g_lds_set, g_lds_set_pen, g_lds_set_rows;
+PerDeviceOnce g_lds_set, g_lds_set_pen, g_lds_set_rows, g_lds_set_ragged;
 
 int check_sample_args(const mq_sample_args* a, const char* who) {
   MQ_REQUIRE(a->logits && a->pos && a->params && a->tok && a->scratch,
@@ -694,16 +795,20 @@ int check_sample_args(const mq_sample_args* a, const char* who) {
   return MQ_OK;
 }
 
-// the two launches of mq_sample (pa == ra == nullptr), of mq_sample_penalized (pa) and of mq_sample_rows (ra; a->pos is n_base)
-int launch_sample(const mq_sample_args* a, const PenArgs* pa, const RowsArgs* ra, const char* who, mq_stream_t stream) {
+// the two launches of mq_sample (pa == ra == ga == nullptr), of mq_sample_penalized (pa), of mq_sample_rows (ra; a->pos is n_base) and of
+// mq_sample_ragged (ga; a->pos is row_pos)
+int launch_sample(const mq_sample_args* a, const PenArgs* pa, const RowsArgs* ra, const char* who, mq_stream_t stream, const RaggedArgs* ga = nullptr) {
   const int V = (int)a->V;
   const int S = min(SM_MAX_SLICES, (V + SM_SLICE - 1) / SM_SLICE);
   const int lds_row = V <= SM_LDS_ROW ? V : 0;
   const size_t lds = select_lds_bytes(lds_row);
   const int dev = current_device();
-  PerDeviceOnce& once = ra ? g_lds_set_rows : pa ? g_lds_set_pen : g_lds_set;
+  PerDeviceOnce& once = ga ? g_lds_set_ragged : ra ? g_lds_set_rows : pa ? g_lds_set_pen : g_lds_set;
   if (!once.done(dev)) {
-    const void* fn = ra ? (const void*)sample_select_rows_kernel : pa ? (const void*)sample_select_penalized_kernel : (const void*)sample_select_kernel;
+    const void* fn = ga   ? (const void*)sample_select_ragged_kernel
+                     : ra ? (const void*)sample_select_rows_kernel
+                     : pa ? (const void*)sample_select_penalized_kernel
+                          : (const void*)sample_select_kernel;
     MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_LDS_ROW)) == hipSuccess,
                "%s: hipFuncSetAttribute(%zu B LDS) failed", who, select_lds_bytes(SM_LDS_ROW));
     once.mark(dev);
@@ -713,7 +818,9 @@ int launch_sample(const mq_sample_args* a, const PenArgs* pa, const RowsArgs* ra
   long long* tok = reinterpret_cast<long long*>(a->tok);
   if (S > 1) {
     const dim3 grid((unsigned)S, (unsigned)a->rows);
-    if (ra)
+    if (ga)
+      sample_scan_ragged_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->cache_len, a->params, part, *ga);
+    else if (ra)
       sample_scan_rows_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->params, part, *ra);
     else if (pa)
       sample_scan_penalized_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part, *pa);
@@ -721,7 +828,10 @@ int launch_sample(const mq_sample_args* a, const PenArgs* pa, const RowsArgs* ra
       sample_scan_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part);
     MQ_LAUNCH_CHECK(who);
   }
-  if (ra)
+  if (ga)
+    sample_select_ragged_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->cache_len, a->params, part,
+                                                                           tok, a->kept, a->logprob, *ga);
+  else if (ra)
     sample_select_rows_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->params, part, tok,
                                                                          a->kept, a->logprob, *ra);
   else if (pa)
@@ -794,6 +904,44 @@ int mq_sample_rows(const mq_sample_rows_args* a, mq_stream_t stream) {
              "mq_sample_rows: penalty, history and bias must be 16-byte aligned, proposals 8-byte aligned");
   const RowsArgs ra{a->penalty, a->history, a->bias, reinterpret_cast<const long long*>(a->proposals), (int)a->V, a->n_offset};
   return launch_sample(&s, nullptr, &ra, "mq_sample_rows", stream);
+}
+
+int mq_sample_ragged(const mq_sample_ragged_args* a, mq_stream_t stream) {
+  MQ_REQUIRE(a != nullptr, "mq_sample_ragged: null argument block");
+  MQ_REQUIRE(a->row_seq && a->row_pos && a->row_tok, "mq_sample_ragged: null pointer (the row table row_seq / row_pos and row_tok are required)");
+  MQ_REQUIRE(a->batch >= 1 && a->batch <= MQ_DECODE_MAX_BATCH, "mq_sample_ragged: batch=%d outside 1..%d", a->batch, MQ_DECODE_MAX_BATCH);
+  // mq_sample's block over the same rows: its limits and alignments are this entry's (pos = row_pos)
+  mq_sample_args s;
+  s.logits = a->logits; s.logits_stride = a->logits_stride; s.V = a->V; s.rows = a->rows;
+  s.pos = a->row_pos; s.cache_len = a->cache_len; s.params = a->params; s.tok = a->tok; s.kept = a->kept; s.logprob = a->logprob;
+  s.scratch = a->scratch; s.scratch_bytes = a->scratch_bytes;
+  if (const int rc = check_sample_args(&s, "mq_sample_ragged")) return rc;
+  MQ_REQUIRE(a->n_offset >= -(1 << 30) && a->n_offset <= (1 << 30), "mq_sample_ragged: n_offset=%d outside [-2^30, 2^30]", a->n_offset);
+  MQ_REQUIRE((a->penalty == nullptr && a->history == nullptr) || (a->history_stride >= a->V && a->history_stride % 4 == 0),
+             "mq_sample_ragged: history_stride=%lld must be >= V and a multiple of 4 (with a penalty or a history)", (long long)a->history_stride);
+  MQ_REQUIRE(aligned(a->row_seq, 4) && aligned(a->row_tok, 8) && aligned(a->penalty, 16) && aligned(a->history, 16) && aligned(a->bias, 8),
+             "mq_sample_ragged: penalty and history must be 16-byte aligned, row_tok and bias 8-byte, row_seq 4-byte aligned");
+  const RaggedArgs ga{a->row_seq, a->row_pos, reinterpret_cast<const long long*>(a->row_tok), a->penalty, a->history, (long long)a->history_stride,
+                      a->bias, a->batch, (int)a->V, a->n_offset};
+  return launch_sample(&s, nullptr, nullptr, "mq_sample_ragged", stream, &ga);
+}
+
+int mq_sample_history_count_ragged(uint32_t* history, int64_t history_stride, int64_t V, int batch, const int64_t* pairs, int64_t n, int delta,
+                                   mq_stream_t stream) {
+  MQ_REQUIRE(history != nullptr && aligned(history, 16), "mq_sample_history_count_ragged: history must be a 16-byte aligned pointer");
+  MQ_REQUIRE(V >= 4 && V % 4 == 0 && V <= (1 << 20), "mq_sample_history_count_ragged: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)V);
+  MQ_REQUIRE(history_stride >= V && history_stride % 4 == 0, "mq_sample_history_count_ragged: history_stride=%lld must be >= V and a multiple of 4",
+             (long long)history_stride);
+  MQ_REQUIRE(batch >= 1 && batch <= MQ_DECODE_MAX_BATCH, "mq_sample_history_count_ragged: batch=%d outside 1..%d", batch, MQ_DECODE_MAX_BATCH);
+  MQ_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "mq_sample_history_count_ragged: n=%lld outside [0, 2^31]", (long long)n);
+  MQ_REQUIRE(n == 0 || (pairs != nullptr && aligned(pairs, 8)), "mq_sample_history_count_ragged: pairs must be an 8-byte aligned pointer when n > 0");
+  MQ_REQUIRE(delta == 1 || delta == -1, "mq_sample_history_count_ragged: delta=%d must be +1 or -1", delta);
+  if (n > 0) {
+    history_count_ragged_kernel<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(history, (long long)history_stride, (int)V, batch,
+                                                                                           reinterpret_cast<const long long*>(pairs), (long long)n, delta);
+    MQ_LAUNCH_CHECK("mq_sample_history_count_ragged");
+  }
+  return MQ_OK;
 }
 
 int mq_sample_history_count(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int delta, mq_stream_t stream) {

@@ -16,6 +16,10 @@ Ragged steps: ``step_tokens`` / ``extend`` move chosen slots by
 still, ``rewind`` drops a slot's last positions, and ``generate(draft=...)`` is greedy speculative decoding across the batch.  Their
 rows run the same weight launches over row buffers of their own and ``mq_decode_attention_ragged`` (csrc/mq_decode_rows.hip), whose
 row table -- like the tokens and the position advance -- is device data: one hipGraph per total row count serves every plan.
+
+Speculation under seeded sampling: ``sample_rows`` / ``step_sample_tokens`` draw every row of a ragged step at its own
+index under its own slot's request (``mq_sample_ragged``, csrc/mq_sample.hip, over the step's row table) and ``generate_speculative``
+returns, token for token, the ids of ``generate(sampling=...)``.
 """
 from __future__ import annotations
 
@@ -27,9 +31,62 @@ import torch
 
 from . import _lib
 from .decode import DecodeEngine, _check_draft, _DecodeBase, _eos_set, _spec_stats, _Target, plan_rows, spec_row_budget
-from .sampling import SampleLaunch, SamplingParams, check_stream, validate_generate_args
+from .sampling import RaggedRowsLaunch, SampleLaunch, SamplingParams, check_stream, history_count_ragged, validate_generate_args
 
 MAX_BATCH = 8
+
+
+class _BatchGreedy:
+    """How BatchDecodeEngine._generate_speculative chooses tokens: plain generate's torch.argmax per row (ties break as they do there)."""
+
+    def first(self, eng) -> List[int]:
+        """The token behind every slot's cached sequence, from eng.logits (an idle slot's entry means nothing)."""
+        return torch.argmax(eng.logits, dim=-1).tolist()
+
+    def plain(self, eng, tokens: Sequence[int]) -> List[int]:
+        """ONE step() of every active slot on `tokens` and the token behind each."""
+        eng.step(tokens)
+        return self.first(eng)
+
+    def rows(self, eng, tokens: Mapping[int, Sequence[int]]) -> List[int]:
+        """ONE ragged step of eng over `tokens`: the token behind every row, in row order (one read-back for all slots)."""
+        eng.step_tokens(tokens)
+        return torch.argmax(eng.rlogits[:sum(len(t) for t in tokens.values())], dim=-1).tolist()
+
+    def count(self, eng, kept):
+        pass
+
+
+class _BatchSampled:
+    """_BatchGreedy's counterpart for generate(sampling=..., streams=...): every slot under its own request and stream -- sample() and,
+    behind a ragged step, mq_sample_ragged (one graph with the step after capture(), ONE read-back of the R tokens).  Under a penalised
+    request start() rebuilds the slots' histories from the prompts; sample() counts what it draws itself (first, plain), mq_sample_ragged
+    counts nothing: count() adds the kept tokens of a round, (slot, token) pairs, with one staging copy and one launch for all slots."""
+
+    def __init__(self, rows, streams):
+        self.requests, self.streams = list(rows), list(streams)
+
+    def start(self, eng, prompts):
+        idle = eng.batch - len(self.requests)
+        eng.set_sampling(self.requests + [SamplingParams(temperature=0.0)] * idle, self.streams + [0] * idle)
+        if eng._sampler.penalized:
+            for i, p in enumerate(prompts):
+                eng._sampler.observe_prompt(i, p)                  # slot i's history: cleared, then its prompt
+
+    def first(self, eng) -> List[int]:
+        eng.sample()
+        return eng.tok.tolist()
+
+    def plain(self, eng, tokens: Sequence[int]) -> List[int]:
+        eng.step(tokens)
+        return self.first(eng)
+
+    def rows(self, eng, tokens: Mapping[int, Sequence[int]]) -> List[int]:
+        return eng.step_sample_tokens(tokens).tolist()
+
+    def count(self, eng, kept):
+        if kept and eng._sampler.penalized:
+            history_count_ragged(eng._sampler.history, torch.tensor(kept, dtype=torch.int64).to(eng.dev), 1)
 
 
 class BatchDecodeEngine(_DecodeBase):
@@ -79,7 +136,8 @@ class BatchDecodeEngine(_DecodeBase):
         if isinstance(max_rows, bool) or int(max_rows) < 1:
             raise ValueError(f"BatchDecodeEngine: max_rows={max_rows} must be >= 1")
         self.max_rows = max(1, min(int(max_rows), self.MAX_ROWS, self.MAX_IMAGE_BYTES // big, self.MAX_HEAD_FLOATS // s.hidden))
-        self.spec_stats = None               # what the last generate(draft=...) did
+        self.spec_stats = None               # what the last generate(draft=...) / generate_speculative did
+        self._rows_at = None                 # (rows, positions behind it) of the last step_tokens call: what sample_rows may draw
         self.graph = None
         self.append_stats = None             # what the last prefill(slot, ids, append=True) did
         self._append_images = None           # per layer ImageCache of prefill(append=True), allocated on first use
@@ -125,6 +183,7 @@ class BatchDecodeEngine(_DecodeBase):
         self.pos.copy_(pos0)
         self._sample_graphs = {}
         self._row_graphs = {}                     # (ragged steps: one graph per total row count, recorded on first use)
+        self._row_sample_graphs = {}              # (with the selection behind them: one per (total row count, penalised))
         return self
 
     # -- ragged steps: several tokens per slot (csrc/mq_decode_rows.hip) ----------------------------------------
@@ -137,6 +196,8 @@ class BatchDecodeEngine(_DecodeBase):
         self.rtok, self.row_dst = self.rplan[:2 * R].view(torch.int64), self.rplan[2 * R:4 * R].view(torch.int64)
         self.row_seq, self.row_pos, self.radv = self.rplan[4 * R:5 * R], self.rplan[5 * R:6 * R], self.rplan[6 * R:]
         self._upload_plan(None)
+        self.rsel = torch.zeros(R, dtype=torch.int64, device=self.dev)                   # sample_rows: row r's drawn token
+        self._row_sel, self._row_sample_graphs = None, {}
         self._lower_row_chain(head_pos=self.row_pos, attn="ragged", batch=B, row_seq=self.row_seq, row_pos=self.row_pos)
 
     def _upload_plan(self, plan):
@@ -161,13 +222,23 @@ class BatchDecodeEngine(_DecodeBase):
         self._logits_rows.index_copy_(0, self.row_dst[:R], self.rlogits[:R])
         self.pos.add_(self.radv)
 
-    def _capture_rows(self, R: int, plan):
-        """Record the R-row ragged step (incl. the logits rows and the position advance) as a hipGraph.  The warm-up launch outside
-        the capture runs with every row idle: no cache byte, logits row or position changes."""
+    def _capture_rows(self, R: int, plan, sel: Optional[RaggedRowsLaunch] = None):
+        """Record the R-row ragged step (incl. the logits rows and the position advance) as a hipGraph; with sel, mq_sample_ragged over
+        the rows behind it, in the same graph.  The warm-up launch outside the capture runs with every row idle: no cache byte, logits
+        row or position changes (the selection's own warm-up draws nothing: an idle row keeps its token)."""
         self._set_rows(R)
         self._upload_plan(None)
         self.rticket.zero_()
-        g = self._row_graphs[R] = self._record(lambda: self._launch_rows(R), lambda: self._finish_rows(R))
+        if sel is None:
+            g = self._row_graphs[R] = self._record(lambda: self._launch_rows(R), lambda: self._finish_rows(R))
+        else:
+            with torch.cuda.device(self.dev):
+                sel.launch(R)                                  # outside the capture: the select kernel's LDS ceiling
+
+            def finish():
+                self._finish_rows(R)
+                sel.launch(R)
+            g = self._row_sample_graphs[(R, self._sampler.penalized)] = self._record(lambda: self._launch_rows(R), finish)
         self._upload_plan(plan)
         return g
 
@@ -182,14 +253,21 @@ class BatchDecodeEngine(_DecodeBase):
         ValueError: total rows outside 1..max_rows, an empty token list, a slot out of range; RuntimeError: an idle slot, tokens
         that would overflow the slot's cache.  After capture(): one hipGraph per TOTAL row count, recorded on first use; the row
         table, the tokens, the position advance and the logits[slot] update are device data and device ops inside it."""
-        plan = plan_rows(tokens, [p if a else None for p, a in zip(self._host_pos, self._active)], self.max_rows, self.cache_len)
+        plan = self._step_rows(tokens, False, "step_tokens")
+        return {slot: self.rlogits[r0:r0 + cnt] for slot, (r0, cnt) in plan.spans.items()}
+
+    def _step_rows(self, tokens: Mapping[int, Sequence[int]], select: bool, who: str):
+        """The ragged step of step_tokens (select: with mq_sample_ragged over its rows behind it, step_sample_tokens).  Returns the plan."""
+        plan = plan_rows(tokens, [p if a else None for p, a in zip(self._host_pos, self._active)], self.max_rows, self.cache_len,
+                         "BatchDecodeEngine." + who)
         R = len(plan.row_tok)
         if self._rows is None:
             self._lower_rows()
+        sel = self._row_launch() if select else None
         if self.graph is not None:
-            g = self._row_graphs.get(R)
+            g = self._row_sample_graphs.get((R, self._sampler.penalized)) if select else self._row_graphs.get(R)
             if g is None:
-                g = self._capture_rows(R, plan)
+                g = self._capture_rows(R, plan, sel)
             else:
                 self._upload_plan(plan)
             g.replay()
@@ -199,9 +277,47 @@ class BatchDecodeEngine(_DecodeBase):
             with torch.cuda.device(self.dev):
                 self._launch_rows(R)
                 self._finish_rows(R)
+                if select:
+                    sel.launch(R)
         for slot, (_, cnt) in plan.spans.items():
             self._host_pos[slot] += cnt
-        return {slot: self.rlogits[r0:r0 + cnt] for slot, (r0, cnt) in plan.spans.items()}
+        self._rows_at = (R, list(self._host_pos))
+        return plan
+
+    def _row_launch(self) -> RaggedRowsLaunch:
+        if self._sampler is None:
+            self.set_sampling(SamplingParams(temperature=0.0))
+        if self._rows is None:
+            self._lower_rows()
+        if self._row_sel is None:
+            self._row_sel = RaggedRowsLaunch(self._sampler, self.rlogits, self.row_seq, self.row_pos, self.rtok, self.rsel, self.cache_len, n_offset=1)
+        return self._row_sel
+
+    @torch.no_grad()
+    def sample_rows(self, R: int) -> torch.Tensor:
+        """mq_sample_ragged on the R rows of the last step_tokens call, each under its own slot's request of
+        set_sampling (greedy until one is set): returns a device tensor [R] (overwritten by the next call; no host read), rows in the
+        step's order (ascending slots, a slot's rows contiguous).  The row cached at position p predicts token index p + 1 -- the index
+        sample() would draw at after a plain step -- so a slot's row j is the token plain sampling draws behind tokens[slot][:j + 1]:
+        what DecodeEngine.sample_rows draws for that sequence alone.  Under a penalised request the row sees its slot's history plus
+        tokens[slot][1:j + 1], the proposals in front of it (read from the step's own token buffer); no history is written: count what
+        is kept with sampling.history_count_ragged.  R must be that call's total row count, with every position still behind it."""
+        R = int(R)
+        if self._rows_at != (R, self._host_pos):
+            raise RuntimeError(f"BatchDecodeEngine.sample_rows: R={R} is not the row count of a step_tokens call that the slots' positions "
+                               f"({self._host_pos}) still stand behind")
+        with torch.cuda.device(self.dev):
+            self._row_launch().launch(R)
+        return self.rsel[:R]
+
+    @torch.no_grad()
+    def step_sample_tokens(self, tokens: Mapping[int, Sequence[int]]) -> torch.Tensor:
+        """step_tokens(tokens) and sample_rows(total rows): returns the drawn tokens [R] (device), rows in ascending slot order.  After
+        capture() the ragged step and the selection are ONE graph per (total rows, penalised), recorded on first use with every row
+        idle; any assignment of rows to slots and any requests replay it.  The uncaptured launches give the same bits.  step_tokens'
+        logits rows are in self.rlogits[:R]."""
+        self._step_rows(tokens, True, "step_sample_tokens")
+        return self.rsel[:self._rows_at[0]]
 
     @torch.no_grad()
     def extend(self, tokens: Mapping[int, Sequence[int]]) -> torch.Tensor:
@@ -447,15 +563,7 @@ class BatchDecodeEngine(_DecodeBase):
                 validate_generate_args("BatchDecodeEngine.generate", sampling, do_sample, draft)
             if do_sample:
                 raise ValueError("BatchDecodeEngine.generate: a draft is for greedy decoding only (do_sample=True with a draft)")
-            drafts = list(draft) if isinstance(draft, (list, tuple)) else [draft] * n
-            if any(isinstance(d, _DecodeBase) for d in drafts):
-                raise TypeError("BatchDecodeEngine.generate: an engine cannot draft for a batch: pass callable drafts, draft(ids, k) -> list of "
-                                "token ids (one for all prompts or one per prompt)")
-            for d in drafts:
-                _check_draft("BatchDecodeEngine.generate", self, d, num_draft, (), "a callable draft(ids, k) -> list of token ids, or a sequence "
-                             "of such callable drafts, one per prompt")
-            if len(drafts) != n:
-                raise ValueError(f"BatchDecodeEngine.generate: {len(drafts)} drafts for {n} prompts")
+            drafts = self._check_drafts("BatchDecodeEngine.generate", draft, num_draft, n)
         if sampling is not None:
             validate_generate_args("BatchDecodeEngine.generate", sampling, do_sample)
             rows = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
@@ -473,22 +581,12 @@ class BatchDecodeEngine(_DecodeBase):
         eos = _eos_set(eos_token_id)
         if max_new_tokens <= 0:
             return prompts
-        for b in range(self.batch):
-            self.release(b)
-        # one-token prompts go through the step kernels (as DecodeEngine.generate), alone; longer ones through the prefill forward
-        short = [i for i, p in enumerate(prompts) if len(p) == 1]
-        if short:
-            for i in short:
-                self.start(i)
-            self.step([prompts[i][0] if i in short else 0 for i in range(self.batch)])
-        for i, p in enumerate(prompts):
-            if len(p) > 1:
-                self.prefill(i, p)
+        self._start_prompts(prompts)
         outs = [list(p) for p in prompts]
         made = [0] * n
         live = list(range(n))
         if drafts is not None:
-            return self._generate_speculative(outs, max_new_tokens, eos, drafts, int(num_draft))
+            return self._generate_speculative(outs, max_new_tokens, eos, drafts, int(num_draft), _BatchGreedy())
         if sampling is not None:
             idle = SamplingParams(temperature=0.0)
             self.set_sampling(rows + [idle] * (self.batch - n), st + [0] * (self.batch - n))
@@ -525,17 +623,87 @@ class BatchDecodeEngine(_DecodeBase):
                 self.step()
         return outs
 
-    def _generate_speculative(self, outs: List[List[int]], max_new_tokens: int, eos: set, drafts, num_draft: int) -> List[List[int]]:
-        """Greedy speculative decoding across the batch; slot i holds outs[i] (its prompt, cached).  The first new token of every prompt
-        is the argmax of its context's logits.  Then per round, with t_i slot i's last token (not yet cached) and P_i its position: the
-        live slots share the step's rows (spec_row_budget), slot i's draft proposes k_i tokens, ONE step_tokens call runs [t_i, d1 ..
-        dk_i] for every live slot, one read-back brings the rows' argmax, and per slot spec_accept keeps plain greedy's next tokens and
-        rewind(slot, P_i + kept) drops the rest.  The stops are plain generate's: EOS, max_new_tokens, the cache end.  More live slots
-        than max_rows (an engine whose shape lowered max_rows below its batch) take a plain step() instead."""
+    def _check_drafts(self, who: str, draft, num_draft, n: int) -> list:
+        """The drafts of a batched speculative generation, one per prompt: a callable (for every prompt) or a sequence of n callables."""
+        drafts = list(draft) if isinstance(draft, (list, tuple)) else [draft] * n
+        if any(isinstance(d, _DecodeBase) for d in drafts):
+            raise TypeError(f"{who}: an engine cannot draft for a batch: pass callable drafts, draft(ids, k) -> list of "
+                            "token ids (one for all prompts or one per prompt)")
+        for d in drafts:
+            _check_draft(who, self, d, num_draft, (), "a callable draft(ids, k) -> list of token ids, or a sequence "
+                         "of such callable drafts, one per prompt")
+        if len(drafts) != n:
+            raise ValueError(f"{who}: {len(drafts)} drafts for {n} prompts")
+        return drafts
+
+    def _start_prompts(self, prompts: Sequence[Sequence[int]]):
+        """Every slot released, then prompt i cached in slot i: one-token prompts go through the step kernels (as DecodeEngine.generate),
+        alone; longer ones through the prefill forward."""
+        for b in range(self.batch):
+            self.release(b)
+        short = [i for i, p in enumerate(prompts) if len(p) == 1]
+        if short:
+            for i in short:
+                self.start(i)
+            self.step([prompts[i][0] if i in short else 0 for i in range(self.batch)])
+        for i, p in enumerate(prompts):
+            if len(p) > 1:
+                self.prefill(i, p)
+
+    @torch.no_grad()
+    def generate_speculative(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, draft, *, sampling, streams: Optional[Sequence[int]] = None,
+                             num_draft: int = 4, eos_token_id=None) -> List[List[int]]:
+        """Speculative decoding under seeded sampling for up to `batch` prompts at once: prompt i's list is, token for
+        token, what generate(prompts, max_new_tokens, sampling=sampling, streams=streams)[i] and DecodeEngine.generate(prompts[i],
+        sampling=rows[i], stream=streams[i]) return, whatever the drafts propose and whatever else is in the batch.  Token n of a
+        sequence is a function of its logits, its request, its stream and n alone, so there is no rejection scheme: every prompt's
+        first token comes from sample(); then per round (_generate_speculative) ONE step_sample_tokens runs [t_i, d1 .. dk_i] for all
+        live slots with mq_sample_ragged drawing every row at its own index under its own slot's request (one graph after capture()),
+        one read-back brings the R tokens, spec_accept keeps plain sampling's next tokens per slot and rewind drops the rest; while any
+        request is penalised the kept tokens of all slots are then counted into the histories by one history_count_ragged launch.
+        sampling: one SamplingParams or one per prompt; streams: default, the prompt's index.  draft: a callable draft(ids, k) -> at
+        most k proposals, or one callable per prompt; an engine cannot draft for a batch (TypeError).  The stops are the sampled
+        generate's: a sequence ends at its own EOS or after max_new_tokens.  self.spec_stats counts the rounds."""
+        who = "BatchDecodeEngine.generate_speculative"
+        n = len(prompts)
+        if not 0 < n <= self.batch:
+            raise ValueError(f"{who}: {n} prompts for {self.batch} slots")
+        drafts = self._check_drafts(who, draft, num_draft, n)
+        if isinstance(sampling, SamplingParams):
+            rows = [sampling] * n
+        elif isinstance(sampling, (list, tuple)) and all(isinstance(r, SamplingParams) for r in sampling):
+            rows = list(sampling)
+        else:
+            raise TypeError(f"{who}: sampling must be SamplingParams or a sequence of them, got {type(sampling).__name__}")
+        st = list(range(n)) if streams is None else [check_stream(v) for v in streams]
+        if len(rows) != n or len(st) != n:
+            raise ValueError(f"{who}: {len(rows)} SamplingParams / {len(st)} streams for {n} prompts")
+        if any(len(p) + max_new_tokens > self.cache_len for p in prompts):
+            raise ValueError(f"{who}: a prompt plus {max_new_tokens} new tokens exceeds the cache ({self.cache_len} positions)")
+        prompts = [[int(t) for t in p] for p in prompts]
+        assert all(len(p) > 0 for p in prompts)
+        if max_new_tokens <= 0:
+            return prompts
+        self._start_prompts(prompts)
+        select = _BatchSampled(rows, st)
+        select.start(self, prompts)
+        return self._generate_speculative([list(p) for p in prompts], max_new_tokens, _eos_set(eos_token_id), drafts, int(num_draft), select)
+
+    def _generate_speculative(self, outs: List[List[int]], max_new_tokens: int, eos: set, drafts, num_draft: int, select) -> List[List[int]]:
+        """Speculative decoding across the batch, for generate(draft=...) (select: _BatchGreedy) and generate_speculative (_BatchSampled);
+        slot i holds outs[i] (its prompt, cached).  The first new token of every prompt is chosen from its context's logits.  Then per
+        round, with t_i slot i's last token (not yet cached) and P_i its position: the live slots share the step's rows
+        (spec_row_budget), slot i's draft proposes k_i tokens, ONE ragged step runs [t_i, d1 .. dk_i] for every live slot with `select`
+        choosing the token behind every row, one read-back brings them, and per slot spec_accept keeps the plain loop's next tokens and
+        rewind(slot, P_i + kept) drops the rest (_spec_keep); select.count then sees the kept tokens of all slots at once.  Every kept
+        token is the plain loop's: a slot's row j holds the logits after t, d1 .. dj, bit for bit, and a token depends on its row
+        (greedy) or on its row, its slot's request and its index (sampling) alone.  The stops are plain generate's: EOS,
+        max_new_tokens, the cache end.  More live slots than max_rows (an engine whose shape lowered max_rows below its batch) take a
+        plain step() instead, whose own selection counts what it draws."""
         n = len(outs)
         stats = self.spec_stats = _spec_stats()
         made, live = [0] * n, []
-        first = torch.argmax(self.logits, dim=-1).tolist()
+        first = select.first(self)
         for i in range(n):
             outs[i].append(first[i])
             made[i] = 1
@@ -548,25 +716,29 @@ class BatchDecodeEngine(_DecodeBase):
             stats["rounds"] += 1
             stats["target_steps"] += 1
             if len(live) > self.max_rows:
-                self.step([outs[i][-1] if i in P else 0 for i in range(self.batch)])
-                arg = torch.argmax(self.logits, dim=-1).tolist()
+                drawn = select.plain(self, [outs[i][-1] if i in P else 0 for i in range(self.batch)])
                 props = {i: [] for i in live}
-                rows = {i: [arg[i]] for i in live}
+                rows = {i: [drawn[i]] for i in live}
                 views = {}
             else:
                 ks = spec_row_budget(num_draft, self.max_rows, [max_new_tokens - made[i] for i in live], [self.cache_len - P[i] for i in live])
                 props = {i: ([int(v) for v in drafts[i](list(outs[i]), k)][:k] if k > 0 else []) for i, k in zip(live, ks)}
-                views = self.step_tokens({i: [outs[i][-1]] + props[i] for i in live})
-                arg = torch.argmax(self.rlogits[:sum(1 + len(props[i]) for i in live)], dim=-1).tolist()      # ONE read-back for all slots
-                rows, r0 = {}, 0
+                drawn = select.rows(self, {i: [outs[i][-1]] + props[i] for i in live})       # ONE read-back for all slots
+                rows, views, r0 = {}, {}, 0
                 for i in live:                                     # (ascending slots: the rows' order)
-                    rows[i] = arg[r0:r0 + 1 + len(props[i])]
+                    rows[i], views[i] = drawn[r0:r0 + 1 + len(props[i])], self.rlogits[r0:r0 + 1 + len(props[i])]
                     r0 += 1 + len(props[i])
-            for i in list(live):
+            kept, stopped = [], []
+            for i in live:
                 new, _, stop = self._spec_keep(rows[i], props[i], eos, max_new_tokens - made[i], views.get(i), i)
                 outs[i] += new
                 made[i] += len(new)
+                if views:
+                    kept += [(i, t) for t in new]
                 if stop:
-                    self.release(i)
-                    live.remove(i)
+                    stopped.append(i)
+            select.count(self, kept)                               # (before a stopped slot's release forgets its history)
+            for i in stopped:
+                self.release(i)
+                live.remove(i)
         return outs

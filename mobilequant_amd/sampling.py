@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MQ_SAMPLE_SCRATCH_BYTES, MqSampleArgs, MqSamplePenalizedArgs, MqSampleRowsArgs
+from ._lib import MQ_SAMPLE_SCRATCH_BYTES, MqSampleArgs, MqSamplePenalizedArgs, MqSampleRaggedArgs, MqSampleRowsArgs
 
 MAX_ROWS = 8
 MAX_VOCAB = 1 << 20
@@ -280,6 +280,41 @@ class RowsLaunch:
         _lib.call("mq_sample_rows", ctypes.byref(a), torch.cuda.current_stream(self.logits.device).cuda_stream)
 
 
+class RaggedRowsLaunch:
+    """mq_sample_ragged over a batched engine's ragged step (DESIGN.md 4.3i): rows logits [R, V] of up to `batch` sequences -> out [R];
+    the row table (row_seq, row_pos: device int32) and the rows' tokens (row_tok: device int64) are the step's own.  A live row of
+    sequence s at position p is drawn at p + n_offset under request s of `sampler` (a batch SampleLaunch: its device requests, penalty
+    rows, histories and bias pointers are read in place, so a captured launch serves any plan and any requests of the same kind).  One
+    argument block per (row count, penalised): a penalised block names the sampler's penalty rows, histories and bias pointers."""
+
+    def __init__(self, sampler: "SampleLaunch", logits: torch.Tensor, row_seq: torch.Tensor, row_pos: torch.Tensor, row_tok: torch.Tensor,
+                 out: torch.Tensor, cache_len: int, n_offset: int = 1):
+        self.sampler, self.logits, self.out = sampler, logits, out
+        self.row_seq, self.row_pos, self.row_tok = row_seq, row_pos, row_tok
+        self.cache_len, self.n_offset = int(cache_len), int(n_offset)
+        self.scratch = torch.zeros(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=logits.device)
+        self._args = {}
+
+    def args(self, R: int, penalized: bool) -> MqSampleRaggedArgs:
+        a = self._args.get((R, penalized))
+        if a is None:
+            s, lg = self.sampler, self.logits
+            a = MqSampleRaggedArgs()
+            a.logits, a.logits_stride, a.V, a.rows, a.batch, a.cache_len = lg.data_ptr(), lg.stride(0), lg.shape[1], R, s.rows, self.cache_len
+            a.row_seq, a.row_pos, a.n_offset, a.row_tok = self.row_seq.data_ptr(), self.row_pos.data_ptr(), self.n_offset, self.row_tok.data_ptr()
+            a.params, a.tok, a.kept, a.logprob = s.params.data_ptr(), self.out.data_ptr(), None, None
+            a.scratch, a.scratch_bytes = self.scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+            if penalized:
+                a.penalty, a.history, a.history_stride, a.bias = s.penalty.data_ptr(), s.history.data_ptr(), s.history.stride(0), s.bias_ptr.data_ptr()
+            self._args[(R, penalized)] = a
+        return a
+
+    def launch(self, R: int):
+        """On the current stream (capturable: kernel launches, nothing else)."""
+        a = self.args(R, self.sampler.penalized)
+        _lib.call("mq_sample_ragged", ctypes.byref(a), torch.cuda.current_stream(self.logits.device).cuda_stream)
+
+
 def validate_generate_args(who: str, sampling, do_sample: bool, draft=None):
     if do_sample:
         raise ValueError(f"{who}: sampling= and do_sample=True are two different selection rules; pass one of them")
@@ -428,6 +463,116 @@ def sample_rows(logits: torch.Tensor, n_base: torch.Tensor, n_offset: int, param
     with _on(logits, n_base, pr, tok):
         _lib.call("mq_sample_rows", ctypes.byref(a), _stream())
     return tok
+
+
+def sample_ragged(logits: torch.Tensor, row_seq: torch.Tensor, row_pos: torch.Tensor, row_tok: torch.Tensor, n_offset: int, params_rows,
+                  tok: torch.Tensor, *, cache_len: int = 2 ** 31 - 1, penalties=None, history: Optional[torch.Tensor] = None, bias=None,
+                  kept: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mq_sample_ragged: logits [rows, V] fp32 (row stride >= V), the rows of a ragged step over `batch` sequences.
+    row_seq / row_pos: int32 device tensors [rows], the table of mq_decode_attention_ragged; row_tok: int64 device tensor [rows], the
+    tokens the rows were stepped with.  params_rows: a uint8 device tensor holding the mq_sample_row array of the batch, or (list of
+    SamplingParams, list of streams), one per sequence: its length is the batch.  A live row of sequence s at position p is drawn at
+    p + n_offset into tok [rows] int64 (written in place, returned) under request s, with the proposals of its run in front of it
+    counted into the history as it reads; a row whose sequence is outside [0, batch) or whose position is outside [0, cache_len) keeps
+    its tok / kept / logprob.  penalties: None (the SamplingParams of params_rows; a packed params_rows: neutral), a uint8 device tensor
+    holding the mq_sample_penalty_row array, or per sequence a SamplingParams or (repetition, presence, frequency); history: None (all
+    zeros) or int32 (uint32 bits) [batch, >= V]; bias: None, or per sequence None or a dense fp32 [V] device tensor.  Nothing but the
+    outputs is written."""
+    from .ops import _dev, _on, _stream
+    if isinstance(logits, torch.Tensor) and logits.dim() == 1:
+        logits = logits.view(1, -1)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise RuntimeError("mobilequant_amd: sample_ragged logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    if not 1 <= rows <= MAX_ROWS:
+        raise RuntimeError(f"mobilequant_amd: sample_ragged rows={rows} outside 1..{MAX_ROWS}")
+    if isinstance(n_offset, bool) or not isinstance(n_offset, (int, np.integer)) or not -2 ** 30 <= int(n_offset) <= 2 ** 30:
+        raise ValueError(f"mobilequant_amd: sample_ragged n_offset={n_offset!r} must be an int in [-2^30, 2^30]")
+    host = None
+    if isinstance(params_rows, torch.Tensor):
+        if params_rows.dtype != torch.uint8 or params_rows.numel() % ROW_DTYPE.itemsize or not params_rows.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: sample_ragged params_rows must be contiguous uint8 bytes, {ROW_DTYPE.itemsize} per sequence")
+        batch = params_rows.numel() // ROW_DTYPE.itemsize
+    else:
+        host = pack_rows(*params_rows)
+        batch = len(host)
+    if not 1 <= batch <= MAX_ROWS:
+        raise RuntimeError(f"mobilequant_amd: sample_ragged batch={batch} outside 1..{MAX_ROWS}")
+    _dev(logits, "sample_ragged logits")
+    pr = _dev(params_rows, "sample_ragged params_rows") if host is None else torch.from_numpy(host.view(np.uint8).reshape(-1)).to(logits.device)
+    for t, dt, what in ((row_seq, torch.int32, "row_seq"), (row_pos, torch.int32, "row_pos"), (row_tok, torch.int64, "row_tok"), (tok, torch.int64, "tok"),
+                        (kept, torch.int32, "kept"), (logprob, torch.float32, "logprob")):
+        if t is None:
+            if what in ("kept", "logprob"):
+                continue
+            raise RuntimeError(f"mobilequant_amd: sample_ragged needs {what} ({dt} [{rows}])")
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != rows or not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: sample_ragged {what} must be contiguous {dt} [{rows}]")
+        _dev(t, "sample_ragged " + what)
+    if history is not None:
+        if not isinstance(history, torch.Tensor) or history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 2 \
+                or history.shape[0] != batch or history.shape[1] < V or history.stride(1) != 1 or history.stride(0) % 4:
+            raise RuntimeError(f"mobilequant_amd: sample_ragged history must be int32 (uint32 bits) [{batch}, >= {V}] with unit column stride")
+        _dev(history, "sample_ragged history")
+    if penalties is None and host is not None:
+        penalties = params_rows[0]
+    pen = None
+    if isinstance(penalties, torch.Tensor):
+        pen = _dev(penalties, "sample_ragged penalties")
+        if pen.dtype != torch.uint8 or pen.numel() != batch * PENALTY_DTYPE.itemsize or not pen.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: sample_ragged penalties must be {batch * PENALTY_DTYPE.itemsize} contiguous uint8 bytes")
+    elif penalties is not None:
+        hp = pack_penalty_rows(list(penalties))
+        if len(hp) != batch:
+            raise RuntimeError(f"mobilequant_amd: sample_ragged got {len(hp)} penalty rows for {batch} sequences")
+        pen = torch.from_numpy(hp.view(np.uint8).reshape(-1)).to(logits.device)
+    bias_ptr = None
+    if bias is not None:
+        brows = list(bias)
+        if len(brows) != batch:
+            raise RuntimeError(f"mobilequant_amd: sample_ragged got {len(brows)} bias rows for {batch} sequences")
+        for b in brows:
+            if b is not None and (_dev(b, "sample_ragged bias").dtype != torch.float32 or b.dim() != 1 or b.numel() < V or not b.is_contiguous()):
+                raise RuntimeError(f"mobilequant_amd: a sample_ragged bias row must be a contiguous fp32 [{V}] tensor")
+        bias_ptr = torch.tensor([0 if b is None else b.data_ptr() for b in brows], dtype=torch.int64).to(logits.device)
+    a = MqSampleRaggedArgs()
+    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=logits.device)
+    a.logits, a.logits_stride, a.V, a.rows = logits.data_ptr(), logits.stride(0) if rows > 1 else max(V, logits.stride(0)), V, rows
+    a.batch, a.cache_len, a.n_offset = batch, int(cache_len), int(n_offset)
+    a.row_seq, a.row_pos, a.row_tok, a.params, a.tok = row_seq.data_ptr(), row_pos.data_ptr(), row_tok.data_ptr(), pr.data_ptr(), tok.data_ptr()
+    a.penalty = pen.data_ptr() if pen is not None else None
+    a.history = history.data_ptr() if history is not None else None
+    a.history_stride = (history.stride(0) if batch > 1 else max(V, history.stride(0))) if history is not None else V
+    a.bias = bias_ptr.data_ptr() if bias_ptr is not None else None
+    a.kept = kept.data_ptr() if kept is not None else None
+    a.logprob = logprob.data_ptr() if logprob is not None else None
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+    with _on(logits, row_seq, pr, tok):
+        _lib.call("mq_sample_ragged", ctypes.byref(a), _stream())
+    return tok
+
+
+def history_count_ragged(history: torch.Tensor, pairs: torch.Tensor, delta: int):
+    """mq_sample_history_count_ragged on a block of histories ([batch, >= V] int32 device tensor holding the uint32 entries; V is its
+    column count): pairs is an int64 device tensor [n, 2] of (sequence, id); the count (bits 0..15) of each pair's id in its sequence's
+    history moves by delta = +1 or -1, saturating at 65 535 and at 0.  Bit 31 is kept; a pair whose sequence is outside [0, batch) or
+    whose id is outside [0, V) is ignored on the device; pairs repeat.  One launch for all sequences (none for n = 0), capturable."""
+    if isinstance(delta, bool) or delta not in (1, -1):
+        raise ValueError(f"mobilequant_amd: history_count_ragged delta={delta!r} must be +1 or -1")
+    if not isinstance(history, torch.Tensor) or history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 2 \
+            or not 1 <= history.shape[0] <= MAX_ROWS or history.stride(1) != 1 or history.stride(0) < history.shape[1] or history.stride(0) % 4:
+        raise RuntimeError(f"mobilequant_amd: history_count_ragged history must be int32 (uint32 bits) [1..{MAX_ROWS}, V] with unit column stride")
+    if not history.is_cuda:
+        raise RuntimeError("mobilequant_amd: history_count_ragged history must be a ROCm device tensor; there is no CPU path")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int64 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise RuntimeError("mobilequant_amd: history_count_ragged pairs must be a contiguous int64 [n, 2] tensor of (sequence, id)")
+    if pairs.device != history.device:
+        raise RuntimeError("mobilequant_amd: history_count_ragged pairs must be a ROCm device tensor on the history's device")
+    n = pairs.shape[0]
+    with torch.cuda.device(history.device):
+        _lib.call("mq_sample_history_count_ragged", history.data_ptr(), history.stride(0), history.shape[1], history.shape[0],
+                  pairs.data_ptr() if n else None, n, int(delta), torch.cuda.current_stream(history.device).cuda_stream)
+    return history
 
 
 def sample_uniforms(seed: int, stream: int, n: int, first: int, count: int, device) -> torch.Tensor:
