@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -1020,6 +1020,54 @@ int mq_sample_ragged(const mq_sample_ragged_args* args, mq_stream_t stream);
  * capturable. */
 int mq_sample_history_count_ragged(uint32_t* history, int64_t history_stride, int64_t V, int batch, const int64_t* pairs, int64_t n, int delta,
                                    mq_stream_t stream);
+
+/* ---- per-token log-probabilities and top-n alternatives of the tokens a selection launch chose ----------------- */
+#define MQ_LOGPROB_MAX_TOP 20
+#define MQ_LOGPROB_SCRATCH_BYTES 360448
+
+/* For each live row r < rows (1 .. MQ_DECODE_MAX_BATCH) of RAW logits (no temperature, penalty or bias: the model's distribution) and
+ * the chosen token t = tok[r] (device int64: what the selection launch in front has just written), by the rule in
+ * csrc/mq_logprob.hip's header: logprob = the log-softmax of the row at t, rank = 1 + the tokens in front of t in the order (logit
+ * descending, ties by index ascending; a NaN logit is -inf, -0 counts as +0), and for k < n_top (0 .. MQ_LOGPROB_MAX_TOP) top_id[k] /
+ * top_logprob[k] = the k-th token of that order and its log-probability (k >= V: -1 and -inf).  t outside [0, V): logprob NaN, rank 0.
+ * Every output bit of a row is a function of the row's logits, t, n_top and V only -- not of rows, the row's index, logits_stride,
+ * the index form, or eager / replayed -- and top_logprob[k] carries the bits logprob carries for t = top_id[k].  Error bound against
+ * the exact log-softmax: that header.
+ * Which record a row writes -- at most ONE index form, each that of a sampler entry:
+ *   pos (mq_sample's): row r is sequence r at n = pos[r]; a row with n outside [0, cache_len) is idle;
+ *   n_base (mq_sample_rows'): every row is sequence 0, row j at n = *n_base + n_offset + j;
+ *   row_seq / row_pos (mq_sample_ragged's): row r is sequence row_seq[r] at n = row_pos[r] + n_offset; a row whose row_seq is outside
+ *     [0, batch) or whose row_pos is outside [0, cache_len) is idle (range-checked on the device before any address is formed);
+ *   none: row r writes at [r][0].
+ * The record goes to logprob / rank [batch][record_len] and top_id / top_logprob [batch][record_len][n_top] at [sequence][n]; n is
+ * read on the device, so a replayed launch lands on the next record.  n outside [0, record_len) writes nothing; an idle row writes
+ * nothing.  Limits (MQ_EINVAL with a message, before any HIP call): V % 4 == 0, 4 <= V <= 2^20; logits_stride >= V and % 4 == 0; rows and
+ * batch 1 .. MQ_DECODE_MAX_BATCH (rows <= batch unless n_base or row_seq is given); n_offset in [-2^30, 2^30]; top_id and top_logprob
+ * both or neither, both with n_top > 0; logits and scratch 16-byte aligned, scratch >= MQ_LOGPROB_SCRATCH_BYTES, owned by the call on
+ * `stream`.  Two launches (one while V <= 4096), no host synchronisation, no launch attribute: capturable without a warm-up. */
+typedef struct mq_logprob_top_args {
+  const float* logits;
+  int64_t logits_stride;
+  int64_t V;
+  int rows;  /* 1 .. MQ_DECODE_MAX_BATCH */
+  int n_top; /* 0 .. MQ_LOGPROB_MAX_TOP */
+  const int64_t* tok;
+  const int* pos;
+  const int* n_base;
+  const int* row_seq;
+  const int* row_pos;
+  int n_offset;
+  int batch; /* sequences in the record arrays, 1 .. MQ_DECODE_MAX_BATCH */
+  int cache_len;
+  int record_len;
+  float* logprob;
+  int* rank;
+  int* top_id;
+  float* top_logprob;
+  void* scratch;
+  int64_t scratch_bytes;
+} mq_logprob_top_args;
+int mq_logprob_top(const mq_logprob_top_args* args, mq_stream_t stream);
 
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes

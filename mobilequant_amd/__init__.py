@@ -7,7 +7,7 @@ from . import _lib, ops, sampling, scoring  # noqa: F401
 from .decode import DecodeEngine, prompt_lookup_draft, spec_accept  # noqa: F401
 from .decode_batch import BatchDecodeEngine  # noqa: F401
 from .quantization import *  # noqa: F401,F403
-from .sampling import SamplingParams  # noqa: F401
+from .sampling import SamplingParams, TokenLogprobs  # noqa: F401
 
 __version__ = "0.1.0"
 

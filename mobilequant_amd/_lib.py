@@ -122,6 +122,17 @@ class MqSampleRaggedArgs(ctypes.Structure):
                 ("kept", c_void_p), ("logprob", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_int64)]
 
 
+class MqLogprobTopArgs(ctypes.Structure):
+    _fields_ = [("logits", c_void_p), ("logits_stride", c_int64), ("V", c_int64), ("rows", c_int), ("n_top", c_int), ("tok", c_void_p),
+                ("pos", c_void_p), ("n_base", c_void_p), ("row_seq", c_void_p), ("row_pos", c_void_p), ("n_offset", c_int), ("batch", c_int),
+                ("cache_len", c_int), ("record_len", c_int), ("logprob", c_void_p), ("rank", c_void_p), ("top_id", c_void_p),
+                ("top_logprob", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_int64)]
+
+
+MQ_LOGPROB_MAX_TOP = 20
+MQ_LOGPROB_SCRATCH_BYTES = 360448
+
+
 class MqAttentionArgs(ctypes.Structure):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("seq", c_int),
                 ("heads", c_int), ("kv_heads", c_int), ("head_dim", c_int), ("inv_sqrt_d", c_float), ("qk_a", MqGrid),
@@ -227,6 +238,7 @@ _SIGNATURES = {
     "mq_sample_history_count": (c_int, [_P, c_int64, _P, c_int64, c_int, _P]),
     "mq_sample_ragged": (c_int, [POINTER(MqSampleRaggedArgs), _P]),
     "mq_sample_history_count_ragged": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, _P]),
+    "mq_logprob_top": (c_int, [POINTER(MqLogprobTopArgs), _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

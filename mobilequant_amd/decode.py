@@ -23,6 +23,7 @@ recorded by ``_DecodeBase._record``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -32,7 +33,8 @@ from . import _lib, ops
 from ._lib import (MQ_U8, MqDecodeAttentionArgs, MqDecodeAttentionBatchArgs, MqDecodeAttentionMultiArgs, MqDecodeAttentionOprojArgs, MqDecodeAttentionRaggedArgs, MqDecodeGemvArgs, MqDecodeGemvBatchArgs,
                    MqDecodeGemvGroupedArgs, MqDecodeHeadBatchArgs, MqGrid)
 from .quantization import qmodule as Q
-from .sampling import RowsLaunch, SampleLaunch, SamplingParams, check_stream, history_count, validate_generate_args
+from .sampling import (LogprobLaunch, RowsLaunch, SampleLaunch, SamplingParams, TokenLogprobs, check_logprobs, check_stream, history_count,
+                       validate_generate_args)
 
 
 def _grid(q: Optional[Q.Quantizer], keep: list) -> MqGrid:
@@ -658,6 +660,56 @@ class _DecodeBase:
         self.set_position(*seq, S)
         return self._logits_row(*seq).copy_(logits[0, -1])
 
+    # -- per-token log-probabilities behind the selection launches (csrc/mq_logprob.hip) --------------------------
+    _lp = None                           # the LogprobLaunch behind every selection launch while the switch is on (set_logprobs)
+
+    def set_logprobs(self, n_top: Optional[int]):
+        """The switch: from now on every selection launch -- sample(), sample_step(), sample_rows(), step_sample_tokens() -- is followed
+        on the same stream by mq_logprob_top over the same RAW logits and the token just written, before the step that overwrites
+        the logits; after capture() inside the same graph (a graph with the launch is recorded on first use beside the one without,
+        which is kept).  n_top in 0 .. 20: that many alternatives per token; None: off, today's launches and graphs.  The record
+        buffers [sequences, cache_len] are allocated on the first request of each n_top and kept (a few bytes per position and
+        alternative; the launches' scratch is one buffer for all of them).  generate(..., logprobs=n) sets the switch for its own run
+        and puts it back as it found it; generate without logprobs= leaves it alone.  A record is written at its own
+        (sequence, token index): a speculative round's rejected rows are overwritten when their index is drawn again, and
+        release() / reset() need not clear anything -- read only the indices that were drawn (logprob_records)."""
+        n = check_logprobs(type(self).__name__ + ".set_logprobs", n_top, True)
+        if n is None:
+            self._lp = None
+        else:
+            lp = self._lp_launches.get(n)
+            if lp is None:
+                shared = next(iter(self._lp_launches.values())).scratch if self._lp_launches else None
+                lp = self._lp_launches[n] = LogprobLaunch(self.logits, self.pos, self.tok, self.cache_len, n, scratch=shared)
+            self._lp = lp
+        return self
+
+    @contextlib.contextmanager
+    def _logprobs_for(self, n_top: Optional[int]):
+        """generate(logprobs=n_top): the switch set for this run and put back afterwards; None leaves it as it is."""
+        before = self._lp
+        if n_top is not None:
+            self.set_logprobs(n_top)
+        try:
+            yield
+        finally:
+            self._lp = before
+
+    def _lp_key(self, *key):
+        """A sample graph's key: with the switch on, one more component (n_top); off, the key as it always was."""
+        return key + (self._lp.n_top,) if self._lp is not None else (key if len(key) > 1 else key[0])
+
+    def _select(self):
+        """The selection launch of sample(): mq_sample / mq_sample_penalized and, with the switch on, mq_logprob_top behind it."""
+        self._sampler.launch()
+        if self._lp is not None:
+            self._lp.launch()
+
+    def _records(self, seq: int, start: int, stop: int) -> TokenLogprobs:
+        if self._lp is None:
+            raise RuntimeError(f"{type(self).__name__}.logprob_records: no records are kept (set_logprobs(n_top) first)")
+        return self._lp.records(seq, int(start), int(stop))
+
     def _record(self, launch, append, before_capture=None):
         """launch() followed by append() as ONE hipGraph on one stream.  launch() first runs once on a side stream outside the capture:
         it sets the launches' LDS ceilings, which must not happen while capturing.  What that warm-up may touch (pos parked at the
@@ -1002,6 +1054,8 @@ class DecodeEngine(_DecodeBase):
         self.graph_long = None
         self._sampler = None                                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
         self._sample_graphs = {}                             # (step variant, penalised) -> the captured sample + step graph, recorded on first use
+        self._lp = None                                      # mq_logprob_top behind every selection launch (set_logprobs), or None
+        self._lp_launches = {}                               # n_top -> its LogprobLaunch (record buffers), allocated on first request
         self._rows_at = None                                 # (T, position behind it) of the last step_tokens call: what sample_rows may draw
         self._lower()
 
@@ -1124,7 +1178,9 @@ class DecodeEngine(_DecodeBase):
             def finish():
                 self._finish_rows(T)
                 sel.launch(T)
-            g = self._row_sample_graphs[(T, self._sampler.penalized)] = self._record(lambda: self._launch_rows(T), finish)
+                if self._lp is not None:
+                    self._lp.launch_rows(sel, T)
+            g = self._row_sample_graphs[self._lp_key(T, self._sampler.penalized)] = self._record(lambda: self._launch_rows(T), finish)
         self.pos.copy_(pos0)
         return g
 
@@ -1150,7 +1206,7 @@ class DecodeEngine(_DecodeBase):
         self.rtok[:T].copy_(torch.tensor(t, dtype=torch.int64), non_blocking=False)
         if self.graph is not None:
             if select:
-                (self._row_sample_graphs.get((T, self._sampler.penalized)) or self._capture_rows(T, sel)).replay()
+                (self._row_sample_graphs.get(self._lp_key(T, self._sampler.penalized)) or self._capture_rows(T, sel)).replay()
             else:
                 (self._row_graphs.get(T) or self._capture_rows(T)).replay()
         else:
@@ -1160,6 +1216,8 @@ class DecodeEngine(_DecodeBase):
                 self._finish_rows(T)
                 if select:
                     sel.launch(T)
+                    if self._lp is not None:
+                        self._lp.launch_rows(sel, T)
         self._host_pos += T
         self._rows_at = (T, self._host_pos)
         return self.rsel[:T] if select else self.rlogits[:T]
@@ -1186,7 +1244,10 @@ class DecodeEngine(_DecodeBase):
             raise RuntimeError(f"DecodeEngine.sample_rows: T={T} is not the row count of a step_tokens call that the position ({self._host_pos}) "
                                f"still stands behind")
         with torch.cuda.device(self.dev):
-            self._row_launch().launch(T)
+            sel = self._row_launch()
+            sel.launch(T)
+            if self._lp is not None:
+                self._lp.launch_rows(sel, T)
         return self.rsel[:T]
 
     @torch.no_grad()
@@ -1383,8 +1444,13 @@ class DecodeEngine(_DecodeBase):
         if self._sampler is None:
             self.set_sampling(SamplingParams(temperature=0.0))
         with torch.cuda.device(self.dev):
-            self._sampler.launch()
+            self._select()
         return self.tok
+
+    def logprob_records(self, start: int, stop: int) -> TokenLogprobs:
+        """The records of the tokens at sequence indices [start, stop) (CPU tensors, read back here): index n is the token sample()
+        drew at position() == n.  Only indices drawn since set_logprobs(n_top) hold records."""
+        return self._records(0, start, stop)
 
     def _capture_sample_step(self, variant: int, penalized: bool):
         """Record mq_sample (penalized: mq_sample_penalized) followed by the step (and the position advance) as one graph: the embedding launch reads the token the
@@ -1398,7 +1464,7 @@ class DecodeEngine(_DecodeBase):
         def step():
             self._launch(phases)
             self.pos.add_(1)
-        g = self._sample_graphs[(variant, penalized)] = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
+        g = self._sample_graphs[self._lp_key(variant, penalized)] = self._record(self._select, step, before_capture=lambda: self.pos.copy_(pos0))
         self._set_splits(*self._variants()[0])
         return g
 
@@ -1414,7 +1480,7 @@ class DecodeEngine(_DecodeBase):
             self.sample()
             return self.step()
         key = (self._variant_at(self._host_pos), self._sampler.penalized)      # a request of the other kind records a graph of its own
-        (self._sample_graphs.get(key) or self._capture_sample_step(*key)).replay()
+        (self._sample_graphs.get(self._lp_key(*key)) or self._capture_sample_step(*key)).replay()
         self._host_pos += 1
         self._rows_at = None
         return self.logits
@@ -1453,7 +1519,7 @@ class DecodeEngine(_DecodeBase):
     def generate(self, context_ids, max_new_tokens: int, eos_token_id=None, prefill: bool = True, do_sample: bool = False,
                  temperature: float = 0.5, generator: Optional[torch.Generator] = None,
                  draft: Union[None, "DecodeEngine", Callable[[List[int], int], List[int]]] = None, num_draft: int = 4,
-                 sampling: Optional[SamplingParams] = None, stream: int = 0):
+                 sampling: Optional[SamplingParams] = None, stream: int = 0, logprobs: Optional[int] = None):
         """SimModel.generate (mobilellm/model/sim_model.py:160-221): context encoding in one prefill forward (prefill=False: token by
         token through the step kernels), then per new token: next = argmax(logits) or, with do_sample, multinomial(softmax(logits /
         temperature)) (:198-201) -- on the device, into self.tok --, append it, stop if it is an EOS (:202-204), else run the step.
@@ -1465,10 +1531,16 @@ class DecodeEngine(_DecodeBase):
         min-p, behind the repetition / presence / frequency penalties and the logit bias of the sequence's own tokens; DESIGN.md
         4.3e) -- the ids depend on (context, sampling, stream) only: BatchDecodeEngine.generate returns the same ids for this sequence
         in any batch and slot.  After capture() a token costs one graph replay (sample + step) and one token read-back; a sequence
-        that ends on an EOS has then cached that token too (position() is one past the returned ids)."""
+        that ends on an EOS has then cached that token too (position() is one past the returned ids).
+        logprobs (with sampling= only; 0 .. 20): returns (ids, TokenLogprobs) -- one record per new token (its log-probability under
+        the model's RAW distribution, its rank, and the `logprobs` most likely alternatives), written on the device
+        behind every sample launch and read back once at the end.  The ids are those of the same call without logprobs.  None (the
+        default) returns what it always did, through the launches and graphs without mq_logprob_top."""
+        n_top = check_logprobs("DecodeEngine.generate", logprobs, sampling)
         if sampling is not None:
             validate_generate_args("DecodeEngine.generate", sampling, do_sample, draft)
-            return self._generate_sampled(context_ids, max_new_tokens, eos_token_id, prefill, sampling, stream)
+            with self._logprobs_for(n_top):
+                return self._generate_sampled(context_ids, max_new_tokens, eos_token_id, prefill, sampling, stream, n_top)
         if draft is not None:
             if do_sample:
                 raise ValueError("DecodeEngine.generate: a draft is for greedy decoding only (do_sample=True with a draft)")
@@ -1493,7 +1565,8 @@ class DecodeEngine(_DecodeBase):
             self.step()
         return out
 
-    def _generate_sampled(self, context_ids, max_new_tokens: int, eos_token_id, prefill: bool, sampling: SamplingParams, stream: int):
+    def _generate_sampled(self, context_ids, max_new_tokens: int, eos_token_id, prefill: bool, sampling: SamplingParams, stream: int,
+                          n_top: Optional[int] = None):
         ids = [int(t) for t in context_ids]
         assert len(ids) + max_new_tokens <= self.cache_len
         self.set_sampling(sampling, stream)
@@ -1511,7 +1584,7 @@ class DecodeEngine(_DecodeBase):
             out.append(nxt)
             if nxt in eos:
                 break
-        return out
+        return out if n_top is None else (out, self.logprob_records(len(ids), len(out)))
 
     def _start_sequence(self, ids: List[int], prefill: bool):
         self.reset()
@@ -1563,7 +1636,7 @@ class DecodeEngine(_DecodeBase):
 
     @torch.no_grad()
     def generate_speculative(self, context_ids, max_new_tokens: int, draft, *, sampling: SamplingParams, stream: int = 0, num_draft: int = 4,
-                             eos_token_id=None, prefill: bool = True):
+                             eos_token_id=None, prefill: bool = True, logprobs: Optional[int] = None):
         """Speculative decoding under seeded sampling: returns, token for token, the ids of
         generate(context_ids, max_new_tokens, sampling=sampling, stream=stream, ...).  Token n of a sequence is a function of its logits,
         the request, the stream and n alone, so no rejection scheme is needed: the first token comes from sample(); then per round
@@ -1573,8 +1646,16 @@ class DecodeEngine(_DecodeBase):
         vocabulary size, or a callable draft(ids, k).  An engine draft is set to the SAME sampling and stream and proposes with its own
         sample_step() / sample(): it shares the Gumbel noise with the target, so it is accepted wherever its logits are close (a
         self-draft: always); its history is brought back to the sequence's with history_count (-1 for the rejected proposals, +1 for the
-        token that replaced them and for the first token), its cache with extend / rewind.  self.spec_stats counts the rounds."""
+        token that replaced them and for the first token), its cache with extend / rewind.  self.spec_stats counts the rounds.
+        logprobs (0 .. 20): returns (ids, TokenLogprobs), the records of generate(..., logprobs=logprobs).  Every row of a round writes
+        its record at its own token index, so a rejected row's record is overwritten when that index is drawn again (by the next
+        round's row 0 at the latest) and nothing behind the returned ids is read: no bookkeeping is needed.  Only the target computes
+        log-probabilities; a draft engine's switch is left as it is."""
         if not isinstance(sampling, SamplingParams):
             raise TypeError(f"DecodeEngine.generate_speculative: sampling must be SamplingParams, got {type(sampling).__name__}")
-        return self._speculate("DecodeEngine.generate_speculative", context_ids, max_new_tokens, eos_token_id, prefill,
-                               _Sampled(sampling, check_stream(stream)), draft, num_draft)
+        n_top = check_logprobs("DecodeEngine.generate_speculative", logprobs, sampling)
+        ids = [int(t) for t in context_ids]
+        with self._logprobs_for(n_top):
+            out = self._speculate("DecodeEngine.generate_speculative", ids, max_new_tokens, eos_token_id, prefill,
+                                  _Sampled(sampling, check_stream(stream)), draft, num_draft)
+            return out if n_top is None else (out, self.logprob_records(len(ids), len(out)))

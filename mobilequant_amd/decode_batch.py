@@ -31,7 +31,8 @@ import torch
 
 from . import _lib
 from .decode import DecodeEngine, _check_draft, _DecodeBase, _eos_set, _spec_stats, _Target, plan_rows, spec_row_budget
-from .sampling import RaggedRowsLaunch, SampleLaunch, SamplingParams, check_stream, history_count_ragged, validate_generate_args
+from .sampling import (RaggedRowsLaunch, SampleLaunch, SamplingParams, TokenLogprobs, check_logprobs, check_stream, history_count_ragged,
+                       validate_generate_args)
 
 MAX_BATCH = 8
 
@@ -143,6 +144,8 @@ class BatchDecodeEngine(_DecodeBase):
         self._append_images = None           # per layer ImageCache of prefill(append=True), allocated on first use
         self._sampler = None                 # mq_sample over logits / pos / tok (sample(), generate(sampling=...))
         self._sample_graphs = {}             # penalised -> the captured sample + step graph, recorded on first use after capture()
+        self._lp = None                      # mq_logprob_top behind every selection launch (set_logprobs), or None
+        self._lp_launches = {}               # n_top -> its LogprobLaunch (record buffers [batch, cache_len]), allocated on first request
         self._lower()
 
     def _lower(self):
@@ -238,7 +241,9 @@ class BatchDecodeEngine(_DecodeBase):
             def finish():
                 self._finish_rows(R)
                 sel.launch(R)
-            g = self._row_sample_graphs[(R, self._sampler.penalized)] = self._record(lambda: self._launch_rows(R), finish)
+                if self._lp is not None:
+                    self._lp.launch_ragged(sel, R)
+            g = self._row_sample_graphs[self._lp_key(R, self._sampler.penalized)] = self._record(lambda: self._launch_rows(R), finish)
         self._upload_plan(plan)
         return g
 
@@ -265,7 +270,7 @@ class BatchDecodeEngine(_DecodeBase):
             self._lower_rows()
         sel = self._row_launch() if select else None
         if self.graph is not None:
-            g = self._row_sample_graphs.get((R, self._sampler.penalized)) if select else self._row_graphs.get(R)
+            g = self._row_sample_graphs.get(self._lp_key(R, self._sampler.penalized)) if select else self._row_graphs.get(R)
             if g is None:
                 g = self._capture_rows(R, plan, sel)
             else:
@@ -279,6 +284,8 @@ class BatchDecodeEngine(_DecodeBase):
                 self._finish_rows(R)
                 if select:
                     sel.launch(R)
+                    if self._lp is not None:
+                        self._lp.launch_ragged(sel, R)
         for slot, (_, cnt) in plan.spans.items():
             self._host_pos[slot] += cnt
         self._rows_at = (R, list(self._host_pos))
@@ -307,7 +314,10 @@ class BatchDecodeEngine(_DecodeBase):
             raise RuntimeError(f"BatchDecodeEngine.sample_rows: R={R} is not the row count of a step_tokens call that the slots' positions "
                                f"({self._host_pos}) still stand behind")
         with torch.cuda.device(self.dev):
-            self._row_launch().launch(R)
+            sel = self._row_launch()
+            sel.launch(R)
+            if self._lp is not None:
+                self._lp.launch_ragged(sel, R)
         return self.rsel[:R]
 
     @torch.no_grad()
@@ -388,8 +398,14 @@ class BatchDecodeEngine(_DecodeBase):
         if self._sampler is None:
             self.set_sampling(SamplingParams(temperature=0.0))
         with torch.cuda.device(self.dev):
-            self._sampler.launch()
+            self._select()
         return self.tok
+
+    def logprob_records(self, slot: int, start: int, stop: int) -> TokenLogprobs:
+        """The records of slot's tokens at sequence indices [start, stop) (CPU tensors, read back here): index n is the token drawn
+        for the slot at position(slot) == n.  Only indices drawn since set_logprobs(n_top) hold records; release() clears nothing."""
+        self._check_slot(slot)
+        return self._records(slot, start, stop)
 
     def _capture_sample_step(self):
         """mq_sample + the step for all slots + the position advance as one graph (BatchDecodeEngine.capture's recipe: the launch
@@ -400,7 +416,7 @@ class BatchDecodeEngine(_DecodeBase):
         def step():
             self._launch()
             self._advance()
-        g = self._sample_graphs[self._sampler.penalized] = self._record(self._sampler.launch, step, before_capture=lambda: self.pos.copy_(pos0))
+        g = self._sample_graphs[self._lp_key(self._sampler.penalized)] = self._record(self._select, step, before_capture=lambda: self.pos.copy_(pos0))
         return g
 
     @torch.no_grad()
@@ -414,7 +430,7 @@ class BatchDecodeEngine(_DecodeBase):
         for b in range(self.batch):
             if self._active[b] and self._host_pos[b] >= self.cache_len:
                 raise RuntimeError(f"BatchDecodeEngine.sample_step: slot {b}'s KV cache is full ({self.cache_len} positions); release() it first")
-        (self._sample_graphs.get(self._sampler.penalized) or self._capture_sample_step()).replay()
+        (self._sample_graphs.get(self._lp_key(self._sampler.penalized)) or self._capture_sample_step()).replay()
         for b in range(self.batch):
             if self._active[b]:
                 self._host_pos[b] += 1
@@ -542,7 +558,7 @@ class BatchDecodeEngine(_DecodeBase):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_token_id=None, do_sample: bool = False,
                  temperature: float = 0.5, generator: Optional[torch.Generator] = None, sampling=None,
-                 streams: Optional[Sequence[int]] = None, draft=None, num_draft: int = 4) -> List[List[int]]:
+                 streams: Optional[Sequence[int]] = None, draft=None, num_draft: int = 4, logprobs: Optional[int] = None):
         """DecodeEngine.generate for up to `batch` prompts at once, each in its own slot: prompt i's list is what DecodeEngine.generate
         returns for it alone (context + new tokens).  Per step the next tokens are chosen on the device (argmax, or multinomial of
         softmax(logits / temperature) per row); the host reads the B token ids.  A sequence stops at its own EOS, after max_new_tokens
@@ -553,7 +569,12 @@ class BatchDecodeEngine(_DecodeBase):
         graph replay (sample + step) and one read-back of the B tokens.
         draft (greedy only; a callable draft(ids, k) -> at most k proposals such as prompt_lookup_draft(), or one callable per prompt):
         greedy speculative decoding for every prompt at once (_generate_speculative).  Prompt i's list equals the plain greedy one
-        token for token; self.spec_stats counts the rounds."""
+        token for token; self.spec_stats counts the rounds.
+        logprobs (with sampling= only; 0 .. 20): returns (list of ids, list of TokenLogprobs) -- prompt i's records are those of
+        DecodeEngine.generate(prompts[i], ..., logprobs=logprobs), bit for bit: one per new token, written on the device behind every
+        sample launch and read back once at the end.  None returns what it always did, through the launches and
+        graphs without mq_logprob_top."""
+        n_top = check_logprobs("BatchDecodeEngine.generate", logprobs, sampling)
         n = len(prompts)
         if not 0 < n <= self.batch:
             raise ValueError(f"BatchDecodeEngine.generate: {n} prompts for {self.batch} slots")
@@ -579,8 +600,16 @@ class BatchDecodeEngine(_DecodeBase):
         prompts = [[int(t) for t in p] for p in prompts]
         assert all(len(p) > 0 for p in prompts)
         eos = _eos_set(eos_token_id)
+        with self._logprobs_for(n_top):
+            return self._generate(prompts, max_new_tokens, eos, do_sample, temperature, generator, (rows, st) if sampling is not None else None, drafts,
+                                  num_draft, n_top)
+
+    def _generate(self, prompts, max_new_tokens: int, eos: set, do_sample: bool, temperature: float, generator, sampling, drafts, num_draft: int,
+                  n_top: Optional[int]):
+        """generate's body behind its argument checks (sampling: None or (requests, streams) per prompt)."""
+        n = len(prompts)
         if max_new_tokens <= 0:
-            return prompts
+            return prompts if n_top is None else (prompts, [self.logprob_records(i, 0, 0) for i in range(n)])
         self._start_prompts(prompts)
         outs = [list(p) for p in prompts]
         made = [0] * n
@@ -588,6 +617,7 @@ class BatchDecodeEngine(_DecodeBase):
         if drafts is not None:
             return self._generate_speculative(outs, max_new_tokens, eos, drafts, int(num_draft), _BatchGreedy())
         if sampling is not None:
+            rows, st = sampling
             idle = SamplingParams(temperature=0.0)
             self.set_sampling(rows + [idle] * (self.batch - n), st + [0] * (self.batch - n))
             if self._sampler.penalized:
@@ -605,7 +635,7 @@ class BatchDecodeEngine(_DecodeBase):
                     if nxt[i] in eos or made[i] >= max_new_tokens:
                         self.release(i)
                         live.remove(i)
-            return outs
+            return outs if n_top is None else (outs, [self.logprob_records(i, len(prompts[i]), len(outs[i])) for i in range(n)])
         while live:
             if do_sample:
                 probs = torch.softmax(self.logits / temperature, dim=-1)
@@ -652,7 +682,7 @@ class BatchDecodeEngine(_DecodeBase):
 
     @torch.no_grad()
     def generate_speculative(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, draft, *, sampling, streams: Optional[Sequence[int]] = None,
-                             num_draft: int = 4, eos_token_id=None) -> List[List[int]]:
+                             num_draft: int = 4, eos_token_id=None, logprobs: Optional[int] = None):
         """Speculative decoding under seeded sampling for up to `batch` prompts at once: prompt i's list is, token for
         token, what generate(prompts, max_new_tokens, sampling=sampling, streams=streams)[i] and DecodeEngine.generate(prompts[i],
         sampling=rows[i], stream=streams[i]) return, whatever the drafts propose and whatever else is in the batch.  Token n of a
@@ -663,8 +693,12 @@ class BatchDecodeEngine(_DecodeBase):
         request is penalised the kept tokens of all slots are then counted into the histories by one history_count_ragged launch.
         sampling: one SamplingParams or one per prompt; streams: default, the prompt's index.  draft: a callable draft(ids, k) -> at
         most k proposals, or one callable per prompt; an engine cannot draft for a batch (TypeError).  The stops are the sampled
-        generate's: a sequence ends at its own EOS or after max_new_tokens.  self.spec_stats counts the rounds."""
+        generate's: a sequence ends at its own EOS or after max_new_tokens.  self.spec_stats counts the rounds.
+        logprobs (0 .. 20): returns (list of ids, list of TokenLogprobs), the records of generate(..., logprobs=logprobs).  Every row of
+        a round writes its record at its own (slot, token index): a rejected row's record is overwritten when that index is drawn
+        again, and nothing behind the returned ids is read, so no bookkeeping is needed."""
         who = "BatchDecodeEngine.generate_speculative"
+        n_top = check_logprobs(who, logprobs, sampling)
         n = len(prompts)
         if not 0 < n <= self.batch:
             raise ValueError(f"{who}: {n} prompts for {self.batch} slots")
@@ -682,12 +716,14 @@ class BatchDecodeEngine(_DecodeBase):
             raise ValueError(f"{who}: a prompt plus {max_new_tokens} new tokens exceeds the cache ({self.cache_len} positions)")
         prompts = [[int(t) for t in p] for p in prompts]
         assert all(len(p) > 0 for p in prompts)
-        if max_new_tokens <= 0:
-            return prompts
-        self._start_prompts(prompts)
-        select = _BatchSampled(rows, st)
-        select.start(self, prompts)
-        return self._generate_speculative([list(p) for p in prompts], max_new_tokens, _eos_set(eos_token_id), drafts, int(num_draft), select)
+        with self._logprobs_for(n_top):
+            if max_new_tokens <= 0:
+                return prompts if n_top is None else (prompts, [self.logprob_records(i, 0, 0) for i in range(n)])
+            self._start_prompts(prompts)
+            select = _BatchSampled(rows, st)
+            select.start(self, prompts)
+            outs = self._generate_speculative([list(p) for p in prompts], max_new_tokens, _eos_set(eos_token_id), drafts, int(num_draft), select)
+            return outs if n_top is None else (outs, [self.logprob_records(i, len(prompts[i]), len(outs[i])) for i in range(n)])
 
     def _generate_speculative(self, outs: List[List[int]], max_new_tokens: int, eos: set, drafts, num_draft: int, select) -> List[List[int]]:
         """Speculative decoding across the batch, for generate(draft=...) (select: _BatchGreedy) and generate_speculative (_BatchSampled);

@@ -1112,3 +1112,4 @@ def score_head(y: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
 # ---- seeded token selection on the device (mq_sample): the binding lives with SamplingParams -------------------------
 from .sampling import history_count as sample_history_count, history_count_ragged as sample_history_count_ragged  # noqa: E402,F401
 from .sampling import history_prompt as sample_history_prompt, sample, sample_ragged, sample_rows, sample_uniforms  # noqa: E402,F401
+from .sampling import logprob_top  # noqa: E402,F401

@@ -5,13 +5,14 @@ from __future__ import annotations
 import ctypes
 import math
 from dataclasses import dataclass
-from typing import Mapping, Optional, Sequence, Tuple
+from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MQ_SAMPLE_SCRATCH_BYTES, MqSampleArgs, MqSamplePenalizedArgs, MqSampleRaggedArgs, MqSampleRowsArgs
+from ._lib import (MQ_LOGPROB_MAX_TOP, MQ_LOGPROB_SCRATCH_BYTES, MQ_SAMPLE_SCRATCH_BYTES, MqLogprobTopArgs, MqSampleArgs, MqSamplePenalizedArgs,
+                   MqSampleRaggedArgs, MqSampleRowsArgs)
 
 MAX_ROWS = 8
 MAX_VOCAB = 1 << 20
@@ -315,6 +316,101 @@ class RaggedRowsLaunch:
         _lib.call("mq_sample_ragged", ctypes.byref(a), torch.cuda.current_stream(self.logits.device).cuda_stream)
 
 
+class TokenLogprobs(NamedTuple):
+    """The records of T tokens (CPU tensors; csrc/mq_logprob.hip's rule): logprob [T] fp32, the log-softmax of the RAW
+    logits row (no temperature, penalty or bias) at the chosen token; rank [T] int32, its place in that row (1 = the top token);
+    top_id [T, n] int32 and top_logprob [T, n] fp32, the row's first n tokens (logit descending, ties by index) and their
+    log-probabilities."""
+    logprob: torch.Tensor
+    rank: torch.Tensor
+    top_id: torch.Tensor
+    top_logprob: torch.Tensor
+
+
+def check_logprobs(who: str, logprobs, sampling) -> Optional[int]:
+    """generate(logprobs=...): None, or an int in 0 .. 20 together with sampling= (the records are written behind the sample launch;
+    the plain greedy, do_sample and generate(draft=...) paths pick their tokens with torch and stay as they are)."""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not 0 <= int(logprobs) <= MQ_LOGPROB_MAX_TOP:
+        raise ValueError(f"{who}: logprobs={logprobs!r} must be None or an int in 0..{MQ_LOGPROB_MAX_TOP} (the number of alternatives per token)")
+    if sampling is None:
+        raise ValueError(f"{who}: logprobs= needs sampling= (the records are written behind the device-side selection; for greedy "
+                         f"decoding pass sampling=SamplingParams(temperature=0))")
+    return int(logprobs)
+
+
+class LogprobLaunch:
+    """mq_logprob_top behind an engine's selection launches: the record buffers logprob / rank [batch, cache_len] and
+    top_id / top_logprob [batch, cache_len, n_top], and one argument block per way the samplers address rows -- the engine's own
+    logits / pos / tok (mq_sample's form), the T rows of a multi-token step (mq_sample_rows' form) and the R rows of a ragged step
+    (mq_sample_ragged's form).  A live row's record goes to [its sequence][its token index], computed on the device: a captured launch
+    moves on by itself, and a speculative round's rejected rows are overwritten when their index is drawn again."""
+
+    def __init__(self, logits: torch.Tensor, pos: torch.Tensor, tok: torch.Tensor, cache_len: int, n_top: int,
+                 scratch: Optional[torch.Tensor] = None):
+        lg = logits.view(-1, logits.shape[-1])
+        self.batch, self.cache_len, self.n_top, self.dev = lg.shape[0], int(cache_len), int(n_top), logits.device
+        B, L, n, dev = self.batch, self.cache_len, self.n_top, self.dev
+        self.logprob = torch.full((B, L), float("nan"), dtype=torch.float32, device=dev)
+        self.rank = torch.zeros(B, L, dtype=torch.int32, device=dev)
+        self.top_id = torch.full((B, L, n), -1, dtype=torch.int32, device=dev)
+        self.top_logprob = torch.full((B, L, n), float("-inf"), dtype=torch.float32, device=dev)
+        # (an engine's launches of every n_top run one after the other on one stream: they share its scratch)
+        self.scratch = scratch if scratch is not None else torch.zeros(MQ_LOGPROB_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+        self._keep = [lg, pos, tok]
+        self.args = self._block(lg, B, tok, pos=pos.data_ptr())
+        self._row_args = {}
+        # one launch with every row idle, outside any capture: the kernels' code is loaded before a graph records them; nothing is written
+        idle = torch.full((B,), self.cache_len, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("mq_logprob_top", ctypes.byref(self._block(lg, B, tok, pos=idle.data_ptr())), torch.cuda.current_stream(dev).cuda_stream)
+            torch.cuda.current_stream(dev).synchronize()
+
+    def _block(self, lg: torch.Tensor, rows: int, tok: torch.Tensor, **index) -> MqLogprobTopArgs:
+        a = MqLogprobTopArgs()
+        a.logits, a.logits_stride, a.V, a.rows, a.n_top, a.tok = lg.data_ptr(), lg.stride(0), lg.shape[1], rows, self.n_top, tok.data_ptr()
+        a.batch, a.cache_len, a.record_len = self.batch, self.cache_len, self.cache_len
+        a.logprob, a.rank = self.logprob.data_ptr(), self.rank.data_ptr()
+        if self.n_top:
+            a.top_id, a.top_logprob = self.top_id.data_ptr(), self.top_logprob.data_ptr()
+        a.scratch, a.scratch_bytes = self.scratch.data_ptr(), MQ_LOGPROB_SCRATCH_BYTES
+        for k, v in index.items():
+            setattr(a, k, v)
+        return a
+
+    def launch(self):
+        """Behind mq_sample / mq_sample_penalized on the engine's logits, pos and tok; on the current stream (capturable)."""
+        _lib.call("mq_logprob_top", ctypes.byref(self.args), torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def _row_block(self, sel, rows: int, make) -> MqLogprobTopArgs:
+        """The argument block behind `sel` at this row count.  A block holds raw pointers into sel's buffers, and an engine that
+        lowers its row chain again (refresh_grids, a stale grid) allocates new row buffers and builds a new selection launch: a block
+        is therefore cached WITH the selection launch it was made for (which keeps those buffers alive) and made again for another."""
+        held = self._row_args.get(rows)
+        if held is None or held[0] is not sel:
+            held = self._row_args[rows] = (sel, make())
+        return held[1]
+
+    def launch_rows(self, sel: "RowsLaunch", T: int):
+        """Behind sel.launch(T) (mq_sample_rows): the same rows, the same base index, the tokens it drew."""
+        a = self._row_block(sel, T, lambda: self._block(sel.logits, T, sel.out, n_base=sel.pos.data_ptr(), n_offset=1 - T))
+        _lib.call("mq_logprob_top", ctypes.byref(a), torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def launch_ragged(self, sel: "RaggedRowsLaunch", R: int):
+        """Behind sel.launch(R) (mq_sample_ragged): the same rows and row table, the tokens it drew."""
+        a = self._row_block(sel, R, lambda: self._block(sel.logits, R, sel.out, row_seq=sel.row_seq.data_ptr(), row_pos=sel.row_pos.data_ptr(),
+                                                        n_offset=sel.n_offset))
+        _lib.call("mq_logprob_top", ctypes.byref(a), torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def records(self, seq: int, start: int, stop: int) -> TokenLogprobs:
+        """The records [start, stop) of sequence seq, read back (the only host reads of this class)."""
+        if not 0 <= seq < self.batch or not 0 <= start <= stop <= self.cache_len:
+            raise ValueError(f"logprob records [{start}, {stop}) of sequence {seq} outside [0, {self.cache_len}] x {self.batch} sequences")
+        return TokenLogprobs(self.logprob[seq, start:stop].cpu(), self.rank[seq, start:stop].cpu(), self.top_id[seq, start:stop].cpu(),
+                             self.top_logprob[seq, start:stop].cpu())
+
+
 def validate_generate_args(who: str, sampling, do_sample: bool, draft=None):
     if do_sample:
         raise ValueError(f"{who}: sampling= and do_sample=True are two different selection rules; pass one of them")
@@ -573,6 +669,43 @@ def history_count_ragged(history: torch.Tensor, pairs: torch.Tensor, delta: int)
         _lib.call("mq_sample_history_count_ragged", history.data_ptr(), history.stride(0), history.shape[1], history.shape[0],
                   pairs.data_ptr() if n else None, n, int(delta), torch.cuda.current_stream(history.device).cuda_stream)
     return history
+
+
+def logprob_top(logits: torch.Tensor, tok: torch.Tensor, n_top: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """mq_logprob_top: logits [rows, V] fp32 (row stride >= V; the RAW rows), tok [rows] int64 device tensor of chosen
+    ids, n_top in 0 .. 20.  Returns device tensors (logprob [rows] fp32, rank [rows] int32, top_id [rows, n_top] int32, top_logprob
+    [rows, n_top] fp32) by the rule in csrc/mq_logprob.hip's header: a row's outputs depend on that row, its token, n_top and V only.
+    A token outside [0, V) gives logprob NaN and rank 0."""
+    from .ops import _dev, _on, _stream
+    _dev(logits, "logprob_top logits")
+    if logits.dim() == 1:
+        logits = logits.view(1, -1)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise RuntimeError("mobilequant_amd: logprob_top logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    if not 1 <= rows <= MAX_ROWS:
+        raise RuntimeError(f"mobilequant_amd: logprob_top rows={rows} outside 1..{MAX_ROWS}")
+    if isinstance(n_top, bool) or not isinstance(n_top, (int, np.integer)) or not 0 <= int(n_top) <= MQ_LOGPROB_MAX_TOP:
+        raise ValueError(f"mobilequant_amd: logprob_top n_top={n_top!r} must be an int in 0..{MQ_LOGPROB_MAX_TOP}")
+    _dev(tok, "logprob_top tok")
+    if tok.dtype != torch.int64 or tok.numel() != rows or not tok.is_contiguous():
+        raise RuntimeError(f"mobilequant_amd: logprob_top tok must be contiguous int64 [{rows}]")
+    n, dev = int(n_top), logits.device
+    logprob = torch.empty(rows, dtype=torch.float32, device=dev)
+    rank = torch.empty(rows, dtype=torch.int32, device=dev)
+    top_id = torch.empty(rows, n, dtype=torch.int32, device=dev)
+    top_logprob = torch.empty(rows, n, dtype=torch.float32, device=dev)
+    scratch = torch.empty(MQ_LOGPROB_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+    a = MqLogprobTopArgs()
+    a.logits, a.logits_stride, a.V, a.rows, a.n_top = logits.data_ptr(), logits.stride(0) if rows > 1 else max(V, logits.stride(0)), V, rows, n
+    a.tok, a.batch, a.cache_len, a.record_len = tok.data_ptr(), rows, 1, 1
+    a.logprob, a.rank = logprob.data_ptr(), rank.data_ptr()
+    if n:
+        a.top_id, a.top_logprob = top_id.data_ptr(), top_logprob.data_ptr()
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_LOGPROB_SCRATCH_BYTES
+    with _on(logits, tok):
+        _lib.call("mq_logprob_top", ctypes.byref(a), _stream())
+    return logprob, rank, top_id, top_logprob
 
 
 def sample_uniforms(seed: int, stream: int, n: int, first: int, count: int, device) -> torch.Tensor:
