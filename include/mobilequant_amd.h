@@ -1069,6 +1069,26 @@ typedef struct mq_logprob_top_args {
 } mq_logprob_top_args;
 int mq_logprob_top(const mq_logprob_top_args* args, mq_stream_t stream);
 
+/* ---- fork cached sequences into other slots of the batched engine's caches: n samples from one prefill ----------- */
+/* ONE launch copies the live part of every source slot's int8 KV caches, in all n_caches caches (every layer's keys and values), into
+ * any number of destination slots; a source byte is loaded once, however many destinations take it.  The rule (csrc/mq_decode_fork.hip's
+ * header): slot s is a source iff parent[s] == s; slot d is a live destination iff p = parent[d] has 0 <= p < batch, p != d,
+ * parent[p] == p and 0 <= pos[p] < cache_len; then for every cache c and head h bytes [0, pos[p] * head_dim) of caches[c][d][h] become
+ * those of caches[c][p][h].  Nothing else is written -- no byte at or past pos[p] of a destination, no byte of any other slot, never
+ * pos.  Every parent entry is range-checked on the device before any address is formed from it: an entry outside [0, batch), a chain
+ * (parent[d] = p, parent[p] != p), an idle source and pos[p] == 0 are no-ops for that slot.  pos and parent are read on the device, so
+ * one captured launch serves any later table; no host synchronisation, no LDS, no launch attribute: capturable without a warm-up.
+ * Limits (MQ_EINVAL with a message, before any HIP call): a null block, caches, pos or parent; n_caches 1 .. 1024; batch 1 ..
+ * MQ_DECODE_MAX_BATCH; kv_heads >= 1; cache_len >= 1; head_dim a multiple of 16 in [16, 256] (every head's live span is then a whole
+ * number of 16-byte chunks); n_caches x kv_heads <= 65535; the table 8-byte, pos and parent 4-byte aligned. */
+typedef struct mq_decode_cache_fork_args {
+  int8_t* const* caches; /* DEVICE table of n_caches base pointers; each cache is [batch][kv_heads][cache_len][head_dim] int8, contiguous, 16-byte aligned */
+  int n_caches, batch, kv_heads, cache_len, head_dim;
+  const int32_t* pos;    /* device [batch]: the engines' position vector (cache_len = idle) */
+  const int32_t* parent; /* device [batch]: the fork table */
+} mq_decode_cache_fork_args;
+int mq_decode_cache_fork(const mq_decode_cache_fork_args* args, mq_stream_t stream);
+
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes
  * per operand, an fp32 library bmm and two more passes over the product in the reference -- by ONE launch: both fp32 operands are

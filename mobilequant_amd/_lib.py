@@ -129,6 +129,11 @@ class MqLogprobTopArgs(ctypes.Structure):
                 ("top_logprob", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_int64)]
 
 
+class MqDecodeCacheForkArgs(ctypes.Structure):
+    _fields_ = [("caches", c_void_p), ("n_caches", c_int), ("batch", c_int), ("kv_heads", c_int), ("cache_len", c_int), ("head_dim", c_int),
+                ("pos", c_void_p), ("parent", c_void_p)]
+
+
 MQ_LOGPROB_MAX_TOP = 20
 MQ_LOGPROB_SCRATCH_BYTES = 360448
 
@@ -239,6 +244,7 @@ _SIGNATURES = {
     "mq_sample_ragged": (c_int, [POINTER(MqSampleRaggedArgs), _P]),
     "mq_sample_history_count_ragged": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, _P]),
     "mq_logprob_top": (c_int, [POINTER(MqLogprobTopArgs), _P]),
+    "mq_decode_cache_fork": (c_int, [POINTER(MqDecodeCacheForkArgs), _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

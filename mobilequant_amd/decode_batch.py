@@ -20,6 +20,10 @@ row table -- like the tokens and the position advance -- is device data: one hip
 Speculation under seeded sampling: ``sample_rows`` / ``step_sample_tokens`` draw every row of a ragged step at its own
 index under its own slot's request (``mq_sample_ragged``, csrc/mq_sample.hip, over the step's row table) and ``generate_speculative``
 returns, token for token, the ids of ``generate(sampling=...)``.
+
+Forks: ``fork({src: [dst, ...]})`` makes one slot's cached sequence the start of others -- ONE ``mq_decode_cache_fork``
+launch (csrc/mq_decode_fork.hip) copies the live cache bytes of all sources, in all layers, to all destinations -- and
+``generate(..., n=k)`` / ``generate_speculative(..., n=k)`` draw k samples of every prompt from ONE prefill of it.
 """
 from __future__ import annotations
 
@@ -29,12 +33,24 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .decode import DecodeEngine, _check_draft, _DecodeBase, _eos_set, _spec_stats, _Target, plan_rows, spec_row_budget
 from .sampling import (RaggedRowsLaunch, SampleLaunch, SamplingParams, TokenLogprobs, check_logprobs, check_stream, history_count_ragged,
                        validate_generate_args)
 
 MAX_BATCH = 8
+
+
+def _count(n: int, fan: int) -> str:
+    """How an error message names n slots: as prompts, or under generate(n=fan) as the samples of n / fan prompts."""
+    return f"{n} prompts" if fan == 1 else f"{n} samples ({n // fan} prompts x n={fan}, one per slot)"
+
+
+def _nest(res, k: int, with_records: bool):
+    """generate(n=k)'s return: the flat per-slot lists as out[i][j] = slot i * k + j (and the records the same way)."""
+    def fold(flat):
+        return [list(flat[i:i + k]) for i in range(0, len(flat), k)]
+    return (fold(res[0]), fold(res[1])) if with_records else fold(res)
 
 
 class _BatchGreedy:
@@ -146,6 +162,10 @@ class BatchDecodeEngine(_DecodeBase):
         self._sample_graphs = {}             # penalised -> the captured sample + step graph, recorded on first use after capture()
         self._lp = None                      # mq_logprob_top behind every selection launch (set_logprobs), or None
         self._lp_launches = {}               # n_top -> its LogprobLaunch (record buffers [batch, cache_len]), allocated on first request
+        self._fork_caches = self.k_cache + self.v_cache
+        self._fork_table = ops.decode_cache_table(self._fork_caches)     # fork(): built once, the caches are never reallocated
+        self._fork_parent = torch.arange(B, dtype=torch.int32, device=dev)
+        self.fork_stats = None               # what the last fork() did
         self._lower()
 
     def _lower(self):
@@ -474,6 +494,74 @@ class BatchDecodeEngine(_DecodeBase):
         if self._sampler is not None:
             self._sampler.clear_history(slot)                  # (a no-op until a penalised request has allocated the histories)
 
+    @torch.no_grad()
+    def fork(self, forks: Mapping[int, Sequence[int]]):
+        """Make source slots' sequences the start of other slots: forks is {source slot: destination slots}.  After the call every
+        destination is an active slot that holds its source's sequence, indistinguishable from a slot that prefilled (and stepped) the
+        same tokens itself: its caches below position(source) are the source's bytes -- ONE mq_decode_cache_fork launch for all
+        sources, destinations and layers -- and its position, pending token (tok), logits row and, once a penalised
+        request has allocated the histories, sampler history row are the source's.  A destination may be idle or active; an active
+        one is overwritten (bytes at or past the source's position keep their old values and are never read).  The sources and every
+        other slot are untouched.
+        NOT copied: a slot's sampling request and stream (different streams are the point: set_sampling), and the log-probability
+        records below the fork position, which stay with the source -- generate reads only indices from the prompt's end on.
+        The captured graphs stay valid (no buffer moves); fork itself runs eagerly, between replays: one small host -> device copy of
+        the fork table, the launch, and four index copies of the per-slot state on the same stream.  sample_rows() needs a new
+        step_tokens() afterwards.  self.fork_stats = {"sources", "destinations", "positions" (cached positions copied, summed over
+        the destinations), "bytes" (cache bytes written)}.
+        ValueError / IndexError / RuntimeError with "BatchDecodeEngine.fork: " in front, before anything is launched: a slot out of
+        range, an idle source, a source whose cache is full (position cache_len), a destination equal to its source, a destination named twice (by one source or by two), a source that is
+        also a destination, an empty mapping or an empty destination list."""
+        who = "BatchDecodeEngine.fork: "
+        plan = {}
+        try:
+            plan = {int(src): [int(d) for d in dsts] for src, dsts in forks.items()}
+        except (AttributeError, TypeError, ValueError):
+            raise ValueError(who + "forks must be a mapping {source slot: sequence of destination slots}") from None
+        if not plan:
+            raise ValueError(who + "an empty mapping (nothing to fork)")
+        parent = list(range(self.batch))
+        taken = {}
+        for src, dsts in plan.items():
+            if not 0 <= src < self.batch:
+                raise IndexError(who + f"source slot {src} outside 0..{self.batch - 1}")
+            if not self._active[src]:
+                raise RuntimeError(who + f"source slot {src} is idle (prefill() or start() it first)")
+            if self._host_pos[src] >= self.cache_len:                  # (on the device a full cache reads as the idle sentinel: nothing would be copied)
+                raise RuntimeError(who + f"source slot {src}'s KV cache is full ({self.cache_len} positions): its position is the idle "
+                                   "sentinel on the device, rewind() it first")
+            if not dsts:
+                raise ValueError(who + f"source slot {src} has an empty destination list")
+            for d in dsts:
+                if not 0 <= d < self.batch:
+                    raise IndexError(who + f"destination slot {d} outside 0..{self.batch - 1}")
+                if d == src:
+                    raise ValueError(who + f"slot {src} is its own destination")
+                if d in taken:
+                    raise ValueError(who + f"destination slot {d} is named twice (by source {taken[d]} and by source {src})")
+                taken[d] = src
+                parent[d] = src
+        both = sorted(set(plan) & set(taken))
+        if both:
+            raise ValueError(who + f"slot {both[0]} is a source and a destination (no chains: fork from the first source)")
+        dst = sorted(taken)
+        idx = torch.tensor([dst, [taken[d] for d in dst]], dtype=torch.int64).to(self.dev)
+        self._fork_parent.copy_(torch.tensor(parent, dtype=torch.int32), non_blocking=False)
+        ops.decode_cache_fork(self._fork_caches, self.pos, self._fork_parent, table=self._fork_table)
+        state = [self.pos, self.tok, self.logits]
+        if self._sampler is not None and self._sampler.pargs is not None:
+            state.append(self._sampler.history)
+        for t in state:                                            # (behind the launch, which reads the SOURCES' positions only)
+            t.index_copy_(0, idx[0], t.index_select(0, idx[1]))
+        for d, src in taken.items():
+            self._host_pos[d], self._active[d] = self._host_pos[src], True
+        self._rows_at = None
+        s = self.shape
+        positions = sum(self._host_pos[d] for d in dst)
+        self.fork_stats = {"sources": len(plan), "destinations": len(dst), "positions": positions,
+                           "bytes": positions * s.head_dim * s.kv_heads * len(self._fork_caches)}
+        return self
+
     def fill_cache_random(self, slot: int, n: int, seed: int = 0):
         """Benchmark helper: n positions of random cached indices in one slot, which becomes active at position n."""
         g = torch.Generator(device=self.dev).manual_seed(seed)
@@ -558,7 +646,8 @@ class BatchDecodeEngine(_DecodeBase):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_token_id=None, do_sample: bool = False,
                  temperature: float = 0.5, generator: Optional[torch.Generator] = None, sampling=None,
-                 streams: Optional[Sequence[int]] = None, draft=None, num_draft: int = 4, logprobs: Optional[int] = None):
+                 streams: Optional[Sequence[int]] = None, draft=None, num_draft: int = 4, logprobs: Optional[int] = None,
+                 n: Optional[int] = None):
         """DecodeEngine.generate for up to `batch` prompts at once, each in its own slot: prompt i's list is what DecodeEngine.generate
         returns for it alone (context + new tokens).  Per step the next tokens are chosen on the device (argmax, or multinomial of
         softmax(logits / temperature) per row); the host reads the B token ids.  A sequence stops at its own EOS, after max_new_tokens
@@ -573,8 +662,44 @@ class BatchDecodeEngine(_DecodeBase):
         logprobs (with sampling= only; 0 .. 20): returns (list of ids, list of TokenLogprobs) -- prompt i's records are those of
         DecodeEngine.generate(prompts[i], ..., logprobs=logprobs), bit for bit: one per new token, written on the device behind every
         sample launch and read back once at the end.  None returns what it always did, through the launches and
-        graphs without mq_logprob_top."""
+        graphs without mq_logprob_top.
+        n (with sampling= only; k >= 1): k samples of every prompt from ONE encoding of it: each prompt is cached once
+        (prefill, or the step path for a one-token prompt) and forked into k - 1 more slots (fork()); sample j of prompt i lives in slot
+        i * k + j, so len(prompts) * k <= batch.  sampling is one SamplingParams or one per prompt (it serves that prompt's k samples);
+        streams has len(prompts) * k entries in slot order (default: the slot index).  The return nests: out[i][j] is an id list --
+        token for token what DecodeEngine.generate(prompts[i], sampling=rows[i], stream=streams[i * k + j]) returns, and so what this
+        call returns with the prompt repeated k times -- and with logprobs= the TokenLogprobs nest the same way, bit for bit.  n with a
+        greedy draft= is a ValueError (generate_speculative takes n); None runs today's call, launches, graphs and return shape."""
         n_top = check_logprobs("BatchDecodeEngine.generate", logprobs, sampling)
+        fan = None
+        if n is not None:
+            if draft is not None:
+                raise ValueError("BatchDecodeEngine.generate: n= draws samples; a draft here is for greedy decoding only (generate_speculative takes n=)")
+            prompts, sampling, fan = self._fan_out("BatchDecodeEngine.generate", prompts, sampling, n)
+        res = self._generate_checked(prompts, max_new_tokens, eos_token_id, do_sample, temperature, generator, sampling, streams, draft, num_draft,
+                                     n_top, fan or 1)
+        return res if fan is None else _nest(res, fan, n_top is not None)
+
+    def _fan_out(self, who: str, prompts, sampling, n):
+        """generate(n=k)'s arguments in slot order: every prompt and its request k times in a row.  Returns (prompts, requests, k)."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"{who}: n={n!r} must be an integer >= 1 (or None)")
+        k, count = int(n), len(prompts)
+        if sampling is None:
+            raise ValueError(f"{who}: n={k} draws samples and needs sampling= (SamplingParams, one or one per prompt)")
+        if count < 1 or count * k > self.batch:
+            raise ValueError(f"{who}: {count} prompts x n={k} samples for {self.batch} slots")
+        if not isinstance(sampling, SamplingParams):
+            if not isinstance(sampling, (list, tuple)) or any(not isinstance(r, SamplingParams) for r in sampling):
+                raise TypeError(f"{who}: sampling must be SamplingParams or a sequence of them")
+            if len(sampling) != count:
+                raise ValueError(f"{who}: {len(sampling)} SamplingParams for {count} prompts (with n= a request serves its prompt's {k} samples)")
+            sampling = [r for r in sampling for _ in range(k)]
+        return [p for p in prompts for _ in range(k)], sampling, k
+
+    def _generate_checked(self, prompts, max_new_tokens, eos_token_id, do_sample, temperature, generator, sampling, streams, draft, num_draft,
+                          n_top, fan: int):
+        """generate behind n=: the checks of its other arguments and its body (fan: slots i * fan .. i * fan + fan - 1 hold one prompt)."""
         n = len(prompts)
         if not 0 < n <= self.batch:
             raise ValueError(f"BatchDecodeEngine.generate: {n} prompts for {self.batch} slots")
@@ -590,7 +715,7 @@ class BatchDecodeEngine(_DecodeBase):
             rows = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
             st = list(range(n)) if streams is None else [check_stream(v) for v in streams]
             if len(rows) != n or len(st) != n:
-                raise ValueError(f"BatchDecodeEngine.generate: {len(rows)} SamplingParams / {len(st)} streams for {n} prompts")
+                raise ValueError(f"BatchDecodeEngine.generate: {len(rows)} SamplingParams / {len(st)} streams for {_count(n, fan)}")
             if any(not isinstance(r, SamplingParams) for r in rows):
                 raise TypeError("BatchDecodeEngine.generate: sampling must be SamplingParams or a sequence of them")
             if any(len(p) + max_new_tokens > self.cache_len for p in prompts):
@@ -602,15 +727,15 @@ class BatchDecodeEngine(_DecodeBase):
         eos = _eos_set(eos_token_id)
         with self._logprobs_for(n_top):
             return self._generate(prompts, max_new_tokens, eos, do_sample, temperature, generator, (rows, st) if sampling is not None else None, drafts,
-                                  num_draft, n_top)
+                                  num_draft, n_top, fan)
 
     def _generate(self, prompts, max_new_tokens: int, eos: set, do_sample: bool, temperature: float, generator, sampling, drafts, num_draft: int,
-                  n_top: Optional[int]):
+                  n_top: Optional[int], fan: int = 1):
         """generate's body behind its argument checks (sampling: None or (requests, streams) per prompt)."""
         n = len(prompts)
         if max_new_tokens <= 0:
             return prompts if n_top is None else (prompts, [self.logprob_records(i, 0, 0) for i in range(n)])
-        self._start_prompts(prompts)
+        self._start_prompts(prompts, fan)
         outs = [list(p) for p in prompts]
         made = [0] * n
         live = list(range(n))
@@ -653,7 +778,7 @@ class BatchDecodeEngine(_DecodeBase):
                 self.step()
         return outs
 
-    def _check_drafts(self, who: str, draft, num_draft, n: int) -> list:
+    def _check_drafts(self, who: str, draft, num_draft, n: int, fan: int = 1) -> list:
         """The drafts of a batched speculative generation, one per prompt: a callable (for every prompt) or a sequence of n callables."""
         drafts = list(draft) if isinstance(draft, (list, tuple)) else [draft] * n
         if any(isinstance(d, _DecodeBase) for d in drafts):
@@ -663,26 +788,30 @@ class BatchDecodeEngine(_DecodeBase):
             _check_draft(who, self, d, num_draft, (), "a callable draft(ids, k) -> list of token ids, or a sequence "
                          "of such callable drafts, one per prompt")
         if len(drafts) != n:
-            raise ValueError(f"{who}: {len(drafts)} drafts for {n} prompts")
+            raise ValueError(f"{who}: {len(drafts)} drafts for {_count(n, fan)}" + (f": one draft, one per prompt ({n // fan}) or one per sample" if fan > 1 else ""))
         return drafts
 
-    def _start_prompts(self, prompts: Sequence[Sequence[int]]):
+    def _start_prompts(self, prompts: Sequence[Sequence[int]], fan: int = 1):
         """Every slot released, then prompt i cached in slot i: one-token prompts go through the step kernels (as DecodeEngine.generate),
-        alone; longer ones through the prefill forward."""
+        alone; longer ones through the prefill forward.  fan > 1 (generate(n=fan): prompts holds every prompt fan times in a row): only
+        the first slot of each run caches its prompt, and ONE fork() gives it to the run's other slots."""
         for b in range(self.batch):
             self.release(b)
-        short = [i for i, p in enumerate(prompts) if len(p) == 1]
+        first = range(0, len(prompts), fan)
+        short = [i for i in first if len(prompts[i]) == 1]
         if short:
             for i in short:
                 self.start(i)
             self.step([prompts[i][0] if i in short else 0 for i in range(self.batch)])
-        for i, p in enumerate(prompts):
-            if len(p) > 1:
-                self.prefill(i, p)
+        for i in first:
+            if len(prompts[i]) > 1:
+                self.prefill(i, prompts[i])
+        if fan > 1:
+            self.fork({i: range(i + 1, i + fan) for i in first})
 
     @torch.no_grad()
     def generate_speculative(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, draft, *, sampling, streams: Optional[Sequence[int]] = None,
-                             num_draft: int = 4, eos_token_id=None, logprobs: Optional[int] = None):
+                             num_draft: int = 4, eos_token_id=None, logprobs: Optional[int] = None, n: Optional[int] = None):
         """Speculative decoding under seeded sampling for up to `batch` prompts at once: prompt i's list is, token for
         token, what generate(prompts, max_new_tokens, sampling=sampling, streams=streams)[i] and DecodeEngine.generate(prompts[i],
         sampling=rows[i], stream=streams[i]) return, whatever the drafts propose and whatever else is in the batch.  Token n of a
@@ -696,13 +825,27 @@ class BatchDecodeEngine(_DecodeBase):
         generate's: a sequence ends at its own EOS or after max_new_tokens.  self.spec_stats counts the rounds.
         logprobs (0 .. 20): returns (list of ids, list of TokenLogprobs), the records of generate(..., logprobs=logprobs).  Every row of
         a round writes its record at its own (slot, token index): a rejected row's record is overwritten when that index is drawn
-        again, and nothing behind the returned ids is read, so no bookkeeping is needed."""
+        again, and nothing behind the returned ids is read, so no bookkeeping is needed.
+        n: generate's n= through the same prompt start (one encoding per prompt, then fork()): out[i][j], nested, is generate(...,
+        n=n)'s.  A callable draft serves every sample; a sequence holds one draft per prompt, or one per sample (len(prompts) * n, in
+        slot order)."""
         who = "BatchDecodeEngine.generate_speculative"
         n_top = check_logprobs(who, logprobs, sampling)
+        fan = 1
+        if n is not None:
+            count = len(prompts)
+            prompts, sampling, fan = self._fan_out(who, prompts, sampling, n)
+            if isinstance(draft, (list, tuple)) and len(draft) == count:
+                draft = [d for d in draft for _ in range(fan)]
+        res = self._speculative_checked(who, prompts, max_new_tokens, draft, sampling, streams, num_draft, eos_token_id, n_top, fan)
+        return res if n is None else _nest(res, fan, n_top is not None)
+
+    def _speculative_checked(self, who, prompts, max_new_tokens, draft, sampling, streams, num_draft, eos_token_id, n_top, fan: int):
+        """generate_speculative behind n=: the checks of its other arguments and its body."""
         n = len(prompts)
         if not 0 < n <= self.batch:
             raise ValueError(f"{who}: {n} prompts for {self.batch} slots")
-        drafts = self._check_drafts(who, draft, num_draft, n)
+        drafts = self._check_drafts(who, draft, num_draft, n, fan)
         if isinstance(sampling, SamplingParams):
             rows = [sampling] * n
         elif isinstance(sampling, (list, tuple)) and all(isinstance(r, SamplingParams) for r in sampling):
@@ -711,7 +854,7 @@ class BatchDecodeEngine(_DecodeBase):
             raise TypeError(f"{who}: sampling must be SamplingParams or a sequence of them, got {type(sampling).__name__}")
         st = list(range(n)) if streams is None else [check_stream(v) for v in streams]
         if len(rows) != n or len(st) != n:
-            raise ValueError(f"{who}: {len(rows)} SamplingParams / {len(st)} streams for {n} prompts")
+            raise ValueError(f"{who}: {len(rows)} SamplingParams / {len(st)} streams for {_count(n, fan)}")
         if any(len(p) + max_new_tokens > self.cache_len for p in prompts):
             raise ValueError(f"{who}: a prompt plus {max_new_tokens} new tokens exceeds the cache ({self.cache_len} positions)")
         prompts = [[int(t) for t in p] for p in prompts]
@@ -719,7 +862,7 @@ class BatchDecodeEngine(_DecodeBase):
         with self._logprobs_for(n_top):
             if max_new_tokens <= 0:
                 return prompts if n_top is None else (prompts, [self.logprob_records(i, 0, 0) for i in range(n)])
-            self._start_prompts(prompts)
+            self._start_prompts(prompts, fan)
             select = _BatchSampled(rows, st)
             select.start(self, prompts)
             outs = self._generate_speculative([list(p) for p in prompts], max_new_tokens, _eos_set(eos_token_id), drafts, int(num_draft), select)

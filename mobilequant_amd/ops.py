@@ -502,6 +502,57 @@ def decode_attention_ragged(args: "_lib.MqDecodeAttentionRaggedArgs") -> None:
     _lib.call("mq_decode_attention_ragged", ctypes.byref(args), _stream())
 
 
+def decode_cache_table(caches) -> torch.Tensor:
+    """The int64 device table of the caches' base pointers that decode_cache_fork takes as table=: built once for caches that are
+    never reallocated (the tensors must outlive it)."""
+    return torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64).to(caches[0].device)
+
+
+def decode_cache_fork(caches, pos: torch.Tensor, parent: torch.Tensor, table: Optional[torch.Tensor] = None) -> None:
+    """mq_decode_cache_fork on the current stream (csrc/mq_decode_fork.hip): ONE launch copies the live part of every
+    source slot of `caches` -- a list of int8 device tensors [batch, kv_heads, cache_len, head_dim], all of one shape, contiguous, on one
+    device -- into its destination slots, in place.  pos / parent: int32 [batch] device tensors, read on the device: slot s is a source
+    iff parent[s] == s; slot d with p = parent[d] != d takes bytes [0, pos[p] * head_dim) of every head of every cache from slot p iff
+    p is in range, parent[p] == p and 0 <= pos[p] < cache_len; nothing else is written.  table: decode_cache_table(caches), prebuilt
+    (otherwise it is built here: one host -> device copy).  RuntimeError / ValueError on any violation, before the C call."""
+    caches = list(caches)
+    if not caches:
+        raise ValueError("mobilequant_amd: decode_cache_fork needs at least one cache")
+    c0 = caches[0]
+    if not isinstance(c0, torch.Tensor) or c0.dim() != 4:
+        raise ValueError(f"mobilequant_amd: decode_cache_fork: a cache is a tensor [batch, kv_heads, cache_len, head_dim], got {getattr(c0, 'shape', type(c0))}")
+    for t in caches:                                               # (what a cache is, then where it lives: a CPU tensor is refused last)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int8:
+            raise RuntimeError(f"mobilequant_amd: decode_cache_fork: caches are int8 tensors, got {getattr(t, 'dtype', type(t))}")
+        if t.shape != c0.shape:
+            raise ValueError(f"mobilequant_amd: decode_cache_fork: caches of different shapes ({tuple(c0.shape)} vs {tuple(t.shape)})")
+        if not t.is_contiguous():
+            raise RuntimeError("mobilequant_amd: decode_cache_fork: a cache is not contiguous")
+    B, H, L, D = (int(v) for v in c0.shape)
+    for t, what in ((pos, "pos"), (parent, "parent")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: decode_cache_fork: {what} must be a contiguous int32 [{B}] tensor, got "
+                               f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if D % 16 or not 16 <= D <= 256:
+        raise ValueError(f"mobilequant_amd: decode_cache_fork: head_dim={D} must be a multiple of 16 in [16, 256]")
+    if not 1 <= B <= 8 or not 1 <= len(caches) <= 1024 or H < 1 or L < 1:
+        raise ValueError(f"mobilequant_amd: decode_cache_fork: {len(caches)} caches of shape {tuple(c0.shape)} outside the launch's limits "
+                         "(1 .. 1024 caches, batch 1 .. 8, no empty dimension)")
+    for t in caches + [pos, parent]:
+        _dev(t, "decode_cache_fork: every cache, pos and parent")
+    if any(t.data_ptr() % 16 for t in caches):
+        raise RuntimeError("mobilequant_amd: decode_cache_fork: a cache is not 16-byte aligned")
+    if table is None:
+        table = decode_cache_table(caches)
+    else:
+        _dev(table, "decode_cache_fork: table")
+        if table.dtype != torch.int64 or tuple(table.shape) != (len(caches),) or not table.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: decode_cache_fork: table must be a contiguous int64 [{len(caches)}] tensor of the caches' base pointers")
+    a = _lib.MqDecodeCacheForkArgs(table.data_ptr(), len(caches), B, H, L, D, pos.data_ptr(), parent.data_ptr())
+    with _on(c0, *caches[1:], pos, parent, table):
+        _lib.call("mq_decode_cache_fork", ctypes.byref(a), _stream())
+
+
 def int8_linear_segmented(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: torch.Tensor, alpha: torch.Tensor, w_zp: torch.Tensor,
                           col_term: torch.Tensor, bias: Optional[torch.Tensor], seg_ends, grids, w4: bool = False,
                           a_tiled_rows: Optional[int] = None) -> torch.Tensor:

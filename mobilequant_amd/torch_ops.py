@@ -19,10 +19,11 @@ Operators (reference code each one replaces):
                                                                                     QLinear.forward, qmodule.py:341-358
     pack_w4(nibbles) -> uint8                                                       the 4-bit image of a quantised weight
     w4a8_linear(xq, row_sum, w_packed, ...) -> Tensor                               the same linear on packed 4-bit weights
+    decode_cache_fork(caches, pos, parent) -> ()                                    (no reference code: DESIGN.md 4.3k; caches in place)
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -123,4 +124,14 @@ def _(xq, row_sum, w_packed, alpha, w_zp, col_term, bias=None, out_scale=None, o
     return xq.new_empty((xq.shape[0], w_packed.shape[0]), dtype=torch.float32)
 
 
-OPS = ("fake_quant", "quantize", "minmax", "minmax_update_", "w8a8_linear", "pack_w4", "w4a8_linear")
+@torch.library.custom_op(f"{_NS}::decode_cache_fork", mutates_args=("caches",), device_types="cuda")
+def decode_cache_fork(caches: List[torch.Tensor], pos: torch.Tensor, parent: torch.Tensor) -> None:
+    ops.decode_cache_fork(caches, pos, parent)
+
+
+@decode_cache_fork.register_fake
+def _(caches, pos, parent):
+    return None
+
+
+OPS = ("fake_quant", "quantize", "minmax", "minmax_update_", "w8a8_linear", "pack_w4", "w4a8_linear", "decode_cache_fork")
