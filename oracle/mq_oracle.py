@@ -1298,3 +1298,154 @@ def prefill_gate(y1, vb, out_q, q_shift):
         idx = quantize_index(prod, out_q.scale, out_q.offset, out_q.qmin, out_q.qmax)
     q8 = (np.where(np.isnan(idx), F32(out_q.qmin), idx).astype(np.int64) - int(q_shift)).astype(np.int8)
     return dict(prod=prod, idx=idx, q8=q8)
+
+
+# ----------------------------------------------------------------------------------------------
+# a12 (calibration passes)  mq_calib_attention_probs(_causal), mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv)  (csrc/mq_reduce.hip)
+# ----------------------------------------------------------------------------------------------
+def calib_probs(raw, inv_sqrt_d, mask=None, causal=False):
+    """The calibration score chain (hf_model.py:513-530): raw [rows, cols] fp32, inv_sqrt_d = float32(1 / float32(sqrt_d)), mask None or an
+    additive fp32 [mask_rows, cols] (row r takes mask[r % mask_rows]), causal: square blocks of cols rows, row r masks the columns
+    > r % cols.  x is formed op for op in fp32 -- ONE rounded multiply, then ONE rounded add of the mask or of the causal -inf / 0 -- and the
+    softmax of that fp32 x is float64: exp(x - max x) / sum.  Row disposition: a row whose x holds a NaN or +inf, or no finite entry at
+    all (max x = -inf: every x - max is inf - inf), is NaN in every entry -- torch's softmax and the kernel alike; -inf entries of any
+    other row are exactly 0.  Returns dict(x fp32, p float64 (NaN rows all-NaN), nan_row bool [rows], masked bool: x == -inf)."""
+    raw = np.asarray(raw, F32)
+    rows, cols = raw.shape
+    with np.errstate(all="ignore"):
+        x = (raw * F32(inv_sqrt_d)).astype(F32)
+        if mask is not None:
+            m = np.asarray(mask, F32)
+            x = (x + m[np.arange(rows) % m.shape[0]]).astype(F32)
+        if causal:
+            above = np.arange(cols)[None, :] > (np.arange(rows) % cols)[:, None]
+            x = (x + np.where(above, F32(-np.inf), F32(0))).astype(F32)
+        mx = x.max(axis=1)                                            # np.max propagates NaN
+        nan_row = np.isnan(mx) | np.isinf(mx)                         # NaN inside, +inf inside (inf - inf), or nothing but -inf
+        x64 = x.astype(np.float64)
+        e = np.exp(x64 - np.where(nan_row, 0.0, mx.astype(np.float64))[:, None])
+        p = e / e.sum(axis=1, keepdims=True)
+        p[nan_row] = np.nan
+    return dict(x=x, p=p, nan_row=nan_row, masked=np.isneginf(x))
+
+
+def calib_norm_n_red(cols, layernorm):
+    """(n_mu, n_r): fp32 roundings on the longest path of calib_norm_kernel<VPT, LN>'s two row sums, VPT = 1 | 2 | 4 | 8 for cols <= 1024 |
+    2048 | 4096 | 8192.  A thread forms a 4-term sum per float4, (a + b) + (c + d): 2 adds; adds it into its accumulator: VPT adds;
+    wave_sum_f_readlane: 6 levels; the four wave partials (s0 + s1) + (s2 + s3): 2 -- VPT + 10 adds.
+      mean (LayerNorm)      the terms are h itself:                         n_mu = VPT + 10, + 1 for the divide by cols
+      sum of squares (RMS)  + 1 for each square's rounding:                 n_r  = VPT + 11
+      squared deviations    + 1 for d = fl(h - mu), squared (2 u), rounded: n_r  = VPT + 13
+    Under the root come / cols and + eps (one u each): gamma(n_r + 2), which the root halves; + u for the root, + u for the reciprocal."""
+    vpt = 1 if cols <= 1024 else 2 if cols <= 2048 else 4 if cols <= 4096 else 8
+    return vpt + 11, vpt + (13 if layernorm else 11)
+
+
+def calib_norm_r_width(n_r):
+    """Relative half-width of the fp32 r = fl(1 / fl(sqrt(fl(fl(ss / cols) + eps)))) around its float64 value: gamma(n_r + 2) / 2 + 2 u (the
+    factor 1.001 covers the second-order terms); the candidates number at most 2 width / u + 1 <= n_r + 8 (fp32 spacing >= u |r|)."""
+    return (_gamma(n_r + 2) / 2 + 2 * U32) * 1.001
+
+
+def calib_norm_candidates(h_row, eps, layernorm, cols=None):
+    """The fp32 row scalars mq_calib_norm can have formed for one row h (fp32): a list of (mu fp32, r candidates fp32 array).  RMS: mu = 0
+    and every fp32 r within calib_norm_r_width of float64 1 / sqrt(mean(h^2) + eps).  LayerNorm: every fp32 mu within
+    gamma(n_mu) sum|h| / cols of the float64 mean (the sum's error is relative to sum|h|, not to the mean), and for EACH of them the r
+    candidates around float64 1 / sqrt(mean((h - mu)^2) + eps) with that fp32 mu."""
+    h64 = np.asarray(h_row, F32).astype(np.float64)
+    cols = h64.size if cols is None else cols
+    n_mu, n_r = calib_norm_n_red(cols, layernorm)
+    e, w = float(F32(eps)), calib_norm_r_width(n_r)
+    if not layernorm:
+        r64 = 1.0 / np.sqrt((h64 * h64).sum() / cols + e)
+        return [(F32(0), f32_between(r64 * (1 - w), r64 * (1 + w)))]
+    m64, a = h64.sum() / cols, _gamma(n_mu) * 1.001 * np.abs(h64).sum() / cols
+    lo, hi = m64 - a, m64 + a
+    assert lo > 0.0 or hi < 0.0, "calib_norm_candidates: the row mean's error interval holds 0 -- no finite candidate list"
+    mus = f32_between(lo, hi) if lo > 0.0 else -f32_between(-hi, -lo)[::-1]
+    out = []
+    for mu in mus:
+        d = (np.asarray(h_row, F32) - mu).astype(F32).astype(np.float64)
+        r64 = 1.0 / np.sqrt((d * d).sum() / cols + e)
+        out.append((mu, f32_between(r64 * (1 - w), r64 * (1 + w))))
+    return out
+
+
+def calib_norm_emit(h_row, mu, r, weight, bias, layernorm):
+    """calib_norm_kernel's elementwise expression in fp32, op for op: RMS fl(w fl(h r)); LayerNorm fl(fl(fl(h - mu) r) w) (+ bias)."""
+    h, w = np.asarray(h_row, F32), np.asarray(weight, F32)
+    with np.errstate(all="ignore"):
+        if not layernorm:
+            return (w * (h * F32(r)).astype(F32)).astype(F32)
+        y = (((h - F32(mu)).astype(F32) * F32(r)).astype(F32) * w).astype(F32)
+        return (y + np.asarray(bias, F32)).astype(F32) if bias is not None else y
+
+
+def calib_norm_rows(x, delta, weight, bias, eps, layernorm, candidates=True):
+    """mq_calib_norm: h = fl(x + delta) (fp32, bit for bit), the float64 norm y64 of each row of h, and each row's candidate list.
+    err bounds |y - y64| of the fp32 kernel element by element (the row scalars' widths of calib_norm_candidates pushed through the
+    elementwise expression).  Returns dict(h fp32, y64, err float64, cand: per row a list of (mu, r array), None without `candidates`)."""
+    x = np.asarray(x, F32)
+    h = (x + np.asarray(delta, F32)).astype(F32) if delta is not None else x
+    h64, w64 = h.astype(np.float64), np.asarray(weight, F32).astype(np.float64)
+    e, cols = float(F32(eps)), h.shape[1]
+    n_mu, n_r = calib_norm_n_red(cols, layernorm)
+    wr = calib_norm_r_width(n_r)
+    if layernorm:
+        d = h64 - h64.mean(axis=1, keepdims=True)
+        r64 = 1.0 / np.sqrt((d * d).mean(axis=1, keepdims=True) + e)
+        t64 = d * r64 * w64
+        a_mu = _gamma(n_mu) * 1.001 * np.abs(h64).sum(axis=1, keepdims=True) / cols
+        y64 = t64 + np.asarray(bias, F32).astype(np.float64) if bias is not None else t64
+        # mu moves d by a_mu (and r, through the variance, by less than a_mu r^2 |mean d| = 0 to first order: doubled instead), then
+        # fl(h - mu), the two products and the bias add: 4 u
+        err = (np.abs(t64) * (wr + 4 * U32) + 2 * a_mu * r64 * np.abs(w64)) * 1.01 + 2 * U32 * np.abs(y64)
+    else:
+        y64 = w64 * (h64 / np.sqrt((h64 * h64).mean(axis=1, keepdims=True) + e))
+        err = np.abs(y64) * (wr + 3 * U32) * 1.01
+    return dict(h=h, y64=y64, err=err + 1e-45, cand=None if not candidates else [calib_norm_candidates(h[i], eps, layernorm) for i in range(h.shape[0])])
+
+
+def calib_norm_replay(y_row, h_row, cand, weight, bias, layernorm, probe=16):
+    """The (mu, r) pairs of `cand` whose calib_norm_emit equals y_row bit for bit (NaN never matches).  The first `probe` columns sift the
+    pairs, the survivors are replayed over the whole row.  Returns the list of matching (mu, r)."""
+    y, h, w = np.asarray(y_row, F32), np.asarray(h_row, F32), np.asarray(weight, F32)
+    b = np.asarray(bias, F32) if bias is not None else None
+    k = min(probe, y.size)
+    hits = []
+    for mu, rs in cand:
+        for r in rs:
+            if np.array_equal(calib_norm_emit(h[:k], mu, r, w[:k], b[:k] if b is not None else None, layernorm).view(np.uint32), y[:k].view(np.uint32)) \
+                    and np.array_equal(calib_norm_emit(h, mu, r, w, b, layernorm).view(np.uint32), y.view(np.uint32)):
+                hits.append((mu, r))
+    return hits
+
+
+def _erf64(x):
+    import math
+    u, inv = np.unique(np.asarray(x, np.float64), return_inverse=True)
+    return np.frompyfunc(math.erf, 1, 1)(u).astype(np.float64)[inv].reshape(np.shape(x))
+
+
+def calib_gated(a, b, act):
+    """mq_calib_gated in float64: act 0 SiLU a / (1 + exp(-a)), act 1 GELU a (1 + erf(a / sqrt 2)) / 2.  Returns (act(a) * b, act(a))."""
+    a64, b64 = np.asarray(a, F32).astype(np.float64), np.asarray(b, F32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        s = a64 / (1.0 + np.exp(-a64)) if int(act) == 0 else 0.5 * a64 * (1.0 + _erf64(a64 / np.sqrt(2.0)))
+    return s * b64, s
+
+
+def repeat_kv(x, rep):
+    """x [B, KV, S, D] -> [B, KV * rep, S, D], every head rep times in a row (hf_model.py:509-510): index arithmetic."""
+    return np.repeat(np.asarray(x), int(rep), axis=1)
+
+
+def calib_rope(x_lin, heads, head_dim, cos, sin, rotate=True, rep=1):
+    """One segment of mq_calib_rope(_qkv): x_lin [B, S, heads * D] as the linear wrote it -> [B, heads * rep, S, D], the first rot dims
+    rotated with cos / sin [S, rot] (rope_partial: two rounded products and one rounded sum) when `rotate`, every head rep times."""
+    x = np.asarray(x_lin, F32)
+    B, S = x.shape[:2]
+    x = x.reshape(B, S, heads, head_dim).transpose(0, 2, 1, 3)
+    if rotate:
+        x = rope_partial(x, np.asarray(cos, F32), np.asarray(sin, F32)).astype(F32)
+    return np.ascontiguousarray(repeat_kv(x, rep))
