@@ -308,53 +308,102 @@ static int launch_quantize(const T* x, QT* q, int64_t rows, int64_t cols, const 
 
 // fp32 rows of 1024 .. 4096 columns: loads along the rows (a wave reads 1 KiB runs), the int8 results staged in an LDS tile in the
 // image's order, stores as 128-byte runs (8 rows x 16 B: whole lines of a fragment block).  1024 threads = four groups of 256, two
-// rows each, every load in flight before the first conversion.  Same index arithmetic as quantize_tiled_kernel: identical images.
+// rows each, every load in flight before the first conversion (held to that in full workgroups: see the request order below).  Same
+// index arithmetic as quantize_tiled_kernel: identical images.
 // GRPS = 2: four rows per 512-thread workgroup, TWO workgroups per CU -- one's loads fly while the other converts and stores
 // (mq_quantize_tiled_set_rows; the same change as in mq_norm.hip's norm_tiled8_kernel).
 template <int V, bool HAS_SUM, int GRPS = 4>
 __global__ void __launch_bounds__(256 * GRPS) quantize_tiled8_kernel(const float* __restrict__ x, int8_t* __restrict__ q, int64_t rows, int64_t cols,
                                                                const float* __restrict__ scale, const float* __restrict__ offset, float qmin,
                                                                float qmax, int shift, int32_t* __restrict__ row_sum) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
   constexpr int RW = 2 * GRPS;                                      // rows per workgroup
+  constexpr int KCOLS = 1024 * V;                                   // == cols (mq_quantize_tiled's dispatch)
   extern __shared__ __attribute__((aligned(16))) int8_t stage8[];   // [cols / 16 pieces][RW rows][16 B]
   __shared__ int s_part[RW][4];
+  // Request order (it matters on cold caches only, DESIGN 4.1: every wait below is a round trip to the fabric, and they stand in a row).
+  // ONE batch of kernel-argument reads: the image and row-sum pointers are consumed here, so hipcc cannot leave their reads to the
+  // tail behind the barrier, where each would be waited for in front of the stores it feeds.
+  asm volatile("" ::"s"(q), "s"(row_sum));
+  // the grid values: requested before any address arithmetic, waited for behind the last x request (as bit patterns: scalar registers)
+  uint32_t s_bits = reinterpret_cast<const uint32_t*>(scale)[0], o_bits = reinterpret_cast<const uint32_t*>(offset)[0];
+  asm volatile("; mq-grid-requested" ::: "memory");
   const int grp = threadIdx.x >> 8, lane = threadIdx.x & 255, wv_id = (threadIdx.x >> 6) & 3;
-  const int nvec = (int)(cols >> 2);
   const int64_t row0 = (int64_t)blockIdx.x * RW;
-  const float s = scale[0], o = offset[0];
-  const float inv_s = __fdiv_rn(1.0f, s);
   const float ubias = (float)(128 - shift);               // image_u8f / image_pack4 (mq_common.h)
-  float4 xs[2][V];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int64_t row = row0 + grp * 2 + j;
-    const float4* xr = reinterpret_cast<const float4*>(x + (row < rows ? row : rows - 1) * cols);
-#pragma unroll
-    for (int k = 0; k < V; ++k) xs[j][k] = xr[lane + 256 * k < nvec ? lane + 256 * k : nvec - 1];
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    uint32_t usum = 0;
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const int i = lane + 256 * k;
-      if (i < nvec) {
-        const float4 f = xs[j][k];
-        // two elements per VALU instruction where a packed form exists (mq_common.h image_u8f2: the same bits)
-        const v2f u01 = image_u8f2((v2f){f.x, f.y}, s, inv_s, o, qmin, qmax, ubias), u23 = image_u8f2((v2f){f.z, f.w}, s, inv_s, o, qmin, qmax, ubias);
-        const uint32_t pk = image_pack4(u01.x, u01.y, u23.x, u23.y, usum);
-        *reinterpret_cast<uint32_t*>(stage8 + (i >> 2) * (RW * 16) + ((grp * 2 + j) << 4) + ((i & 3) << 2)) = pk;
-      }
-    }
+  // vector lane + 256 k of row j of this group -> its dword of the staging tile; two elements per VALU instruction where a packed form
+  // exists (mq_common.h image_u8f2: the same bits)
+  auto convert = [&](int j, int k, const float4 f, float s, float inv_s, float o, uint32_t& usum) {
+    const int i = lane + 256 * k;
+    const v2f u01 = image_u8f2((v2f){f.x, f.y}, s, inv_s, o, qmin, qmax, ubias), u23 = image_u8f2((v2f){f.z, f.w}, s, inv_s, o, qmin, qmax, ubias);
+    const uint32_t pk = image_pack4(u01.x, u01.y, u23.x, u23.y, usum);
+    *reinterpret_cast<uint32_t*>(stage8 + (i >> 2) * (RW * 16) + ((grp * 2 + j) << 4) + ((i & 3) << 2)) = pk;
+  };
+  auto row_done = [&](int j, uint32_t usum) {
     if (HAS_SUM) {
       const int acc = mq::wave_sum((int)usum);
       if ((threadIdx.x & 63) == 0) s_part[grp * 2 + j][wv_id] = acc;
     }
+  };
+  if (row0 + RW <= rows) {
+    // Full workgroup (every one of a launch whose rows are a multiple of 16): no clamped address and no per-vector condition, so
+    // nothing stands between a load and its use -- a conditional use makes hipcc sink the load into the branch, behind the grid
+    // values' wait and the divide, and wait for it with vmcnt(0).  All 2 V requests go out behind the argument wait, the
+    // conversions follow in issue order behind counted waits.  tools/load_order_audit.py holds the compiled order to this
+    // (the two comment markers delimit the path for it).
+    asm volatile("; mq-full-path-begin" ::: "memory");
+    const char* xb = reinterpret_cast<const char*>(x + row0 * KCOLS);
+    const uint32_t off = (uint32_t)(grp * 2) * (KCOLS * 4) + (uint32_t)lane * 16;
+    float4 xs[2][V];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const char* xjk = xb + (j * KCOLS * 4 + k * 4096);            // a scalar base per request and ONE lane offset: no vector address
+        asm("" : "+s"(xjk));                                          // arithmetic stands between two requests (hipcc would fold the constant into 64-bit lane adds)
+        const v4f g = *reinterpret_cast<const __attribute__((address_space(1))) v4f*>((const __attribute__((address_space(1))) char*)xjk + off);   // (the tie hides that x is global memory)
+        xs[j][k] = make_float4(g.x, g.y, g.z, g.w);
+      }
+    // the grid values' wait, and the divide, behind the last request: nothing is scheduled across the barrier, and the values pass
+    // through the marker, so neither they nor a copy of them can be needed (and waited for) in front of it
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("; mq-x-requested" : "+s"(s_bits), "+s"(o_bits)::"memory");
+    const float s = __builtin_bit_cast(float, s_bits), o = __builtin_bit_cast(float, o_bits);
+    const float inv_s = __fdiv_rn(1.0f, s);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      uint32_t usum = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) convert(j, k, xs[j][k], s, inv_s, o, usum);
+      row_done(j, usum);
+    }
+    asm volatile("; mq-full-path-end" ::: "memory");
+  } else {
+    // ragged and padding workgroups (row0 + RW > rows): addresses clamped to the last real row
+    const int nvec = (int)(cols >> 2);
+    const float s = __builtin_bit_cast(float, s_bits), o = __builtin_bit_cast(float, o_bits);
+    const float inv_s = __fdiv_rn(1.0f, s);
+    float4 xs[2][V];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int64_t row = row0 + grp * 2 + j;
+      const float4* xr = reinterpret_cast<const float4*>(x + (row < rows ? row : rows - 1) * cols);
+#pragma unroll
+      for (int k = 0; k < V; ++k) xs[j][k] = xr[lane + 256 * k < nvec ? lane + 256 * k : nvec - 1];
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      uint32_t usum = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if (lane + 256 * k < nvec) convert(j, k, xs[j][k], s, inv_s, o, usum);
+      row_done(j, usum);
+    }
   }
   __syncthreads();
   if (HAS_SUM && threadIdx.x < RW && row0 + threadIdx.x < rows)
-    row_sum[row0 + threadIdx.x] = (s_part[threadIdx.x][0] + s_part[threadIdx.x][1]) + (s_part[threadIdx.x][2] + s_part[threadIdx.x][3]) - 128 * (int)cols;
-  staged_copy_out<RW, 256 * GRPS, true>(stage8, q, row0, rows, cols);   // rows past `rows` are padding of the image: written like the others
+    row_sum[row0 + threadIdx.x] = (s_part[threadIdx.x][0] + s_part[threadIdx.x][1]) + (s_part[threadIdx.x][2] + s_part[threadIdx.x][3]) - 128 * KCOLS;
+  staged_copy_out<RW, 256 * GRPS, true>(stage8, q, row0, rows, KCOLS);   // rows past `rows` are padding of the image: written like the others
 }
 
 }  // namespace mq
