@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -75,6 +75,16 @@ int mq_minmax_init(float* min_out, float* max_out, int64_t n, mq_stream_t stream
 /* per-tensor: compute_min_max_from_tensor (qmodule.py:31-33); generate_act_range.py:65 */
 int mq_minmax_tensor(const void* x, int dtype, int64_t numel, float* min_out, float* max_out,
                      mq_stream_t stream);
+/* per-tensor histogram on the fp32 BIT PATTERN, with the running min / max, in ONE pass over x (percentile activation ranges:
+ * calibration.ActRangeCollector(method="percentile"); the rule in full: DESIGN.md 4.1h and the head of the kernel in mq_reduce.hip).
+ * mantissa_bits m in 0..6, NB = 256 << m, counts[2 * NB].  Per element (fp16 converted to fp32 first, exact): -0 counts as +0; a NaN
+ * goes to nan_count[0] and to no bin; otherwise mag = (bits & 0x7fffffff) >> (23 - m), bin = NB + mag for x >= 0 and NB - 1 - mag for
+ * x < 0 -- bin order is value order, bin bounds are exact fp32 numbers.  counts and nan_count are RUNNING 64-bit totals: the call ADDS
+ * (integer atomics: exact in any order, so histograms of shards add up to the histogram of the whole).  min_out / max_out: the running
+ * statistic with the bits mq_minmax_tensor produces (NaN sticky, -0 canonical); nullable as a pair.  x: MQ_F32 or MQ_F16, any element
+ * alignment.  numel == 0 returns MQ_OK without a launch; numel <= 2^40.  Bad arguments return MQ_EINVAL before any launch. */
+int mq_hist_minmax_tensor(const void* x, int dtype, int64_t numel, int mantissa_bits, uint64_t* counts, uint64_t* nan_count,
+                          float* min_out, float* max_out, mq_stream_t stream);
 /* per-tensor, FRESH statistic: min_out[0] / max_out[0] are OVERWRITTEN with the tensor's min / max (what a dynamic
  * quantizer or a first-forward weight range needs, qmodule.py:262-277).  Two launches without atomics (per-workgroup
  * partials into `scratch`, >= 1024 floats of device memory the caller owns for the duration of the call on `stream`,

@@ -65,6 +65,9 @@ int mq_attention_set_f16(int on);
 /* 1 = two heads of a KV group per eight-wave workgroup over one copy of the K / vT tiles (f16 form with in-kernel q rows, even heads per
  * KV group); default 0.  Identical results, measured slower: built only with -DMQ_BUILD_EXPERIMENTS, otherwise the call returns 1. */
 int mq_attention_set_pair(int on);
+/* mq_hist_minmax_tensor: 1 (default) = a wave whose active lanes all hold the same bin adds the lane count with ONE LDS atomic (constant
+ * runs: masked zeros, saturated activations), 0 = every lane issues its own (A/B timing of the contention remedy; identical counts). */
+int mq_hist_set_aggregate(int on);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,10 @@ one process.  Here:
   * at the end every rank packs ``[-min..., max...]`` of all tensors into one flat fp32 buffer and
     the group performs ONE all-reduce(MAX) (RCCL over xGMI on GPUs; payload is KBs for per-tensor
     mode, ~10 MB for per-channel mode: latency bound, so one collective, not one per tensor);
+  * ``method="percentile"`` (no reference counterpart): the same hook takes a bit-pattern histogram of the tensor beside
+    its min / max in the same single pass (``mq_hist_minmax_tensor``); histograms are integer counts, so they merge across samples and
+    ranks by addition (one more all-reduce, SUM) and the clipped ``[min, max]`` pairs read from them depend on the multiset of values
+    only.  ``act_dict()`` keeps its format: everything downstream takes the percentile ranges unchanged;
   * artefacts keep the reference formats: ``act_dict.json`` (indent 4, sorted keys;
     mobilellm/utils/io.py:34-36), ``act_dict_per_channel.pth``, ``act_scales.pth`` keys
     ``"<module>_<input|output>"``.
@@ -20,9 +24,10 @@ one process.  Here:
 from __future__ import annotations
 
 import json
+import math
 from contextlib import nullcontext as _nullcontext
 from collections import OrderedDict
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.distributed as dist
@@ -47,14 +52,88 @@ def _is_matmul(m: nn.Module) -> bool:
     return isinstance(m, FMatMul) or any(c.__name__ == "FMatMul" for c in type(m).__mro__)
 
 
+# ---- percentile ranges from bit-pattern histograms (the rule: DESIGN.md 4.1h, csrc/mq_reduce.hip) ------------------------------------
+def _check_mantissa_bits(mantissa_bits: int) -> int:
+    if not isinstance(mantissa_bits, int) or isinstance(mantissa_bits, bool) or not 0 <= mantissa_bits <= 6:
+        raise ValueError(f"mantissa_bits={mantissa_bits!r}: an integer in 0..6")
+    return mantissa_bits
+
+
+def _check_percentile(p) -> float:
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:        # (NaN fails the comparison too)
+        raise ValueError(f"percentile={p!r}: a coverage in (0, 1]")
+    return float(p)
+
+
+def histogram_bin_bounds(mantissa_bits: int = 5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 (lo[2 * NB], hi[2 * NB]) of mq_hist_minmax_tensor's bins, NB = 256 << mantissa_bits: with
+    f(k) = float_from_bits(min(k, 255 << m) << (23 - m)) the non-negative bin NB + k holds [f(k), f(k + 1)) and the negative bin
+    NB - 1 - k holds (-f(k + 1), -f(k)] -- exact fp32 numbers (the bins of +-inf have equal bounds; keys beyond belong to NaNs and stay
+    empty)."""
+    m = _check_mantissa_bits(mantissa_bits)
+    nb = 256 << m
+    k = torch.arange(nb + 1, dtype=torch.int64)
+    f = (torch.clamp(k, max=255 << m) << (23 - m)).to(torch.int32).view(torch.float32)
+    return torch.cat((-f[1:].flip(0), f[:-1])), torch.cat((-f[:-1].flip(0), f[1:]))
+
+
+def _percentile_bins(counts: torch.Tensor, p: float) -> Optional[Tuple[int, int]]:
+    """(lo, hi) bins of the rule for coverage p; None for an empty histogram."""
+    n = int(counts.sum())
+    if n == 0:
+        return None
+    tail = math.floor((1.0 - p) * 0.5 * n)
+    t = torch.tensor([tail], dtype=torch.int64)
+    lo = int(torch.searchsorted(torch.cumsum(counts, 0), t, right=True))
+    hi = counts.numel() - 1 - int(torch.searchsorted(torch.cumsum(counts.flip(0), 0), t, right=True))
+    return lo, hi
+
+
+def percentile_range(counts, mn: float, mx: float, p: float, mantissa_bits: int = 5) -> Tuple[float, float]:
+    """The rule on the host, a pure function: counts[2 * NB] of one tensor's histogram (NaNs not in it), its observed exact mn / mx and
+    a coverage p in (0, 1] -> (min, max) as Python floats holding fp32 values.  tail = floor((1.0 - p) * 0.5 * N); lo = the lowest bin
+    with sum_{i <= lo} c[i] > tail, hi = the highest bin with sum_{i >= hi} c[i] > tail; min = max(lower bound of lo, mn),
+    max = min(upper bound of hi, mx).  p = 1 returns (mn, mx); at least N - 2 * tail counted values lie inside the result."""
+    p = _check_percentile(p)
+    c = torch.as_tensor(counts).to(torch.int64).reshape(-1).cpu()
+    blo, bhi = histogram_bin_bounds(mantissa_bits)
+    if c.numel() != blo.numel():
+        raise ValueError(f"percentile_range: {c.numel()} counts, mantissa_bits={mantissa_bits} has {blo.numel()} bins")
+    mn, mx = float(mn), float(mx)
+    bins = _percentile_bins(c, p)
+    if bins is None:
+        return mn, mx
+    lo_v, hi_v = float(blo[bins[0]]), float(bhi[bins[1]])
+    return (lo_v if lo_v > mn else mn), (hi_v if hi_v < mx else mx)
+
+
 class ActRangeCollector:
     """Running min/max of the input / output (/ input2) of every calibrated leaf of ``model``.
 
     Slots are laid out from ``model.named_modules()`` order, not from the order tensors happen to be
     seen, so every rank has the same layout even if it processed no sample.
+
+    method: "minmax" (the reference's statistic, the default) or "percentile": every hooked tensor's bit-pattern histogram is taken
+    beside its min / max (per-tensor mode only) and act_dict() reports the range that keeps a coverage ``percentile`` of the values:
+    a float in (0, 1] or a callable (module name, field) -> float (leave softmax outputs at 1.0, say).  mantissa_bits 0..6: bins per
+    power of two = 2^mantissa_bits.
     """
 
-    def __init__(self, model: nn.Module, per_channel: bool = False, device=None):
+    def __init__(self, model: nn.Module, per_channel: bool = False, device=None, method: str = "minmax",
+                 percentile: Union[None, float, Callable[[str, str], float]] = None, mantissa_bits: int = 5):
+        if method not in ("minmax", "percentile"):
+            raise ValueError(f"method={method!r}: 'minmax' or 'percentile'")
+        if method == "percentile":
+            if per_channel:
+                raise ValueError("method='percentile' keeps one histogram per tensor: per_channel=True is not served")
+            if percentile is None:
+                raise ValueError("method='percentile' needs percentile=: a coverage in (0, 1] or a callable (name, field) -> coverage")
+            if not callable(percentile):
+                percentile = _check_percentile(percentile)
+            _check_mantissa_bits(mantissa_bits)
+        elif percentile is not None:
+            raise ValueError("percentile= is read by method='percentile' only")
+        self.method, self.percentile, self.mantissa_bits = method, percentile, mantissa_bits
         self.model = model
         self.per_channel = per_channel
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
@@ -93,6 +172,10 @@ class ActRangeCollector:
         self.bytes_seen = 0            # bytes of hooked tensors reduced so far (host-side bookkeeping for the benchmark)
         self.bytes_fused = 0           # bytes of tensors whose statistics were folded into the pass that produced them
         self.n_collectives = 0
+        if method == "percentile":
+            # the fused statistics passes (below) produce no histograms: the model runs its plain forward under the hooks
+            self.fuse_attention_statistics = self.fuse_layer_statistics = False
+            self._cnt, self._nan = ops.hist_new(n, mantissa_bits, self.device)
 
     # -- hooks -------------------------------------------------------------------------------------
     def _update(self, name: str, field: str, t: torch.Tensor) -> None:
@@ -109,6 +192,9 @@ class ActRangeCollector:
             if not self.per_channel:
                 self._mn[i:i + 1].copy_(self._mn[j:j + 1])
                 self._mx[i:i + 1].copy_(self._mx[j:j + 1])
+            if self.method == "percentile":
+                self._cnt[i].copy_(self._cnt[j])
+                self._nan[i:i + 1].copy_(self._nan[j:j + 1])
         self.bytes_seen += t.numel() * t.element_size()
         if t.device != self.device:
             raise RuntimeError(f"calibration of {name}.{field}: tensor on {t.device}, statistics on {self.device} -- run one "
@@ -128,6 +214,9 @@ class ActRangeCollector:
             if not t.is_contiguous():
                 p = t.permute(sorted(range(t.dim()), key=lambda d: -t.stride(d)))
                 t = p if p.is_contiguous() else t.contiguous()      # transposed views (k^T in qk_bmm): no copy
+            if self.method == "percentile":                         # histogram and min / max together: the tensor is read once
+                ops.hist_minmax_tensor_(t, self._cnt[i], self._nan[i:i + 1], self._mn[i:i + 1], self._mx[i:i + 1], self.mantissa_bits)
+                return
             ops.minmax_tensor_(t, self._mn[i:i + 1], self._mx[i:i + 1])
 
     def _hook(self, name: str, matmul: bool):
@@ -174,7 +263,7 @@ class ActRangeCollector:
     fuse_layer_statistics = True
 
     def can_fuse_layer(self, x: torch.Tensor) -> bool:
-        return (self.fuse_layer_statistics and not self.per_channel and x.dtype == torch.float32 and x.device == self.device
+        return (self.method == "minmax" and self.fuse_layer_statistics and not self.per_channel and x.dtype == torch.float32 and x.device == self.device
                 and x.device.type == "cuda" and x.is_contiguous() and x.shape[-1] % 4 == 0 and x.shape[-1] <= 8192)
 
     def norm_pass(self, name: str, module: nn.Module, x: torch.Tensor, delta: Optional[torch.Tensor] = None, delta_slot: Optional[tuple] = None):
@@ -244,7 +333,7 @@ class ActRangeCollector:
         return True
 
     def can_fuse_attention(self, raw_shape, dtype, device, mask) -> bool:
-        return (self.fuse_attention_statistics and not self.per_channel and dtype == torch.float32 and device == self.device
+        return (self.method == "minmax" and self.fuse_attention_statistics and not self.per_channel and dtype == torch.float32 and device == self.device
                 and device.type == "cuda" and raw_shape[-1] % 4 == 0 and raw_shape[-1] <= 4096
                 and (mask is None or (mask.dim() == 2 and mask.dtype == torch.float32 and mask.is_contiguous()
                                       and tuple(mask.shape) == tuple(raw_shape[-2:]))))
@@ -267,7 +356,10 @@ class ActRangeCollector:
         mn, mx = self._mn.tolist(), self._mx.tolist()
         for idx in pending:
             root = idx[0]
-            if mn[root] <= mx[root] and all(mn[i] == mn[root] and mx[i] == mx[root] for i in idx[1:]):
+            same = mn[root] <= mx[root] and all(mn[i] == mn[root] and mx[i] == mx[root] for i in idx[1:])
+            if same and self.method == "percentile":                # equal extremes do not make equal tensors: equal histograms as well
+                same = all(torch.equal(self._cnt[i], self._cnt[root]) for i in idx[1:]) and len(set(self._nan[idx].tolist())) == 1
+            if same:
                 for i in idx[1:]:
                     self._mirror[i] = root
 
@@ -284,6 +376,9 @@ class ActRangeCollector:
         jj = torch.tensor(list(self._mirror.values()), device=self._mn.device)
         self._mn[ii] = self._mn[jj]
         self._mx[ii] = self._mx[jj]
+        if self.method == "percentile":                             # a mirrored slot shares its source's histogram
+            self._cnt[ii] = self._cnt[jj]
+            self._nan[ii] = self._nan[jj]
 
     def attach(self) -> "ActRangeCollector":
         names = {id(m): name for name, m in self.model.named_modules()}
@@ -401,7 +496,8 @@ class ActRangeCollector:
         mis-merging.  Different LENGTHS (a hooked module that ran on some ranks only: data-dependent paths, MoE) would abort inside
         the collective, so callers with such graphs pass verify_layout=True: a 4-float guard all-reduce first and, on a mismatch,
         one all_gather_object of the slot widths to agree on the union layout (ranks fill what they did not see with the neutral
-        element).  force: also run the pack / reduce / unpack path in a 1-rank group (tests)."""
+        element).  force: also run the pack / reduce / unpack path in a 1-rank group (tests).
+        method="percentile": then ONE all-reduce(SUM) over the int64 histograms and NaN counters of every slot (integer adds: exact)."""
         if not (dist.is_available() and dist.is_initialized()):
             return
         if dist.get_world_size(group) == 1 and not force:
@@ -426,6 +522,13 @@ class ActRangeCollector:
             dist.all_reduce(buf, op=dist.ReduceOp.MAX, group=group)
             self.n_collectives += 1
         self._unpack(buf, layout)
+        if self.method == "percentile":
+            n = len(self.slots)
+            h = torch.cat((self._cnt.reshape(-1), self._nan))
+            if h.numel():
+                dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+                self.n_collectives += 1
+            self._cnt, self._nan = h[:h.numel() - n].view(n, -1), h[h.numel() - n:]
 
     # -- results -----------------------------------------------------------------------------------
     def act_dict(self) -> Dict[str, dict]:
@@ -438,11 +541,50 @@ class ActRangeCollector:
                 if self._pc[i] is not None:
                     out.setdefault(name, {})[field] = torch.stack(self._pc[i], dim=0).cpu()
             return out
+        if self.method == "percentile":
+            for (name, field), r in self._ranges().items():
+                out.setdefault(name, {})[field] = [r["lo"], r["hi"]]
+            return out
         self._resolve()
         mn, mx = self._mn.tolist(), self._mx.tolist()
         for (name, field), i in self.slots.items():
             if mn[i] <= mx[i]:
                 out.setdefault(name, {})[field] = [mn[i], mx[i]]
+        return out
+
+    # -- percentile mode ---------------------------------------------------------------------------
+    def _coverage(self, name: str, field: str) -> float:
+        return _check_percentile(self.percentile(name, field)) if callable(self.percentile) else self.percentile
+
+    def _ranges(self) -> "OrderedDict[tuple, dict]":
+        """{(name, field): clip_report()'s entry} of every slot seen whose min / max is not NaN (one host readback of the histograms)."""
+        assert self.method == "percentile", "histograms are kept by method='percentile' only"
+        self._resolve()
+        mn, mx, nan, cnt = self._mn.tolist(), self._mx.tolist(), self._nan.tolist(), self._cnt.cpu()
+        blo, bhi = histogram_bin_bounds(self.mantissa_bits)
+        out: "OrderedDict[tuple, dict]" = OrderedDict()
+        for (name, field), i in self.slots.items():
+            if not mn[i] <= mx[i]:
+                continue
+            bins = _percentile_bins(cnt[i], self._coverage(name, field))
+            lo_v, hi_v = float(blo[bins[0]]), float(bhi[bins[1]])
+            out[(name, field)] = {"min": mn[i], "max": mx[i], "lo": lo_v if lo_v > mn[i] else mn[i], "hi": hi_v if hi_v < mx[i] else mx[i],
+                                  "clipped_low": int(cnt[i, :bins[0]].sum()), "clipped_high": int(cnt[i, bins[1] + 1:].sum()), "nan": int(nan[i])}
+        return out
+
+    def histogram(self, name: str, field: str) -> Tuple[torch.Tensor, int]:
+        """(counts CPU int64 [2 * NB], NaN count) of one slot: what a user needs to try another range search (MSE, entropy)."""
+        assert self.method == "percentile", "histograms are kept by method='percentile' only"
+        self._resolve()
+        i = self.slots[(name, field)]
+        return self._cnt[i].cpu(), int(self._nan[i])
+
+    def clip_report(self) -> Dict[str, dict]:
+        """{name: {field: {"min", "max": observed extremes, "lo", "hi": the chosen range, "clipped_low", "clipped_high": counts in bins
+        wholly outside it, "nan"}}}."""
+        out: Dict[str, dict] = {}
+        for (name, field), r in self._ranges().items():
+            out.setdefault(name, {})[field] = r
         return out
 
     def act_scales(self) -> Dict[str, torch.Tensor]:
@@ -463,21 +605,24 @@ class ActRangeCollector:
 
 @torch.no_grad()
 def get_act_range(model: nn.Module, samples: Sequence[torch.Tensor], per_channel: bool = False, group=None,
-                  forward=None, force_collective: bool = False, verify_layout: bool = False) -> Dict[str, dict]:
+                  forward=None, force_collective: bool = False, verify_layout: bool = False, method: str = "minmax",
+                  percentile=None, mantissa_bits: int = 5) -> Dict[str, dict]:
     """Data-parallel counterpart of ``get_act_range`` (generate_act_range.py:49-122).
 
     ``samples``: the full list of calibration inputs (token-id tensors), identical on every rank; rank r
     processes samples r, r + world, ...  Returns the merged act_dict on every rank.
+    method / percentile / mantissa_bits: ActRangeCollector's (percentile ranges from one-pass histograms, same dict format).
     """
     model.eval()
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-    col = ActRangeCollector(model, per_channel).attach()
+    col = ActRangeCollector(model, per_channel, method=method, percentile=percentile, mantissa_bits=mantissa_bits).attach()
     dev = col.device
     run = forward if forward is not None else (lambda s: model(s))
     mine = list(range(rank, len(samples), world))
-    if not mine and len(samples):
+    if not mine and len(samples) and method == "minmax":
         mine = [rank % len(samples)]          # a duplicate: min / max are idempotent, and the rank learns every slot's shape
+    # (percentile: counts are not idempotent -- a rank without a sample runs none; the per-tensor layout is static anyway)
     try:
         for i in mine:
             with torch.cuda.device(dev) if dev.type == "cuda" else _nullcontext():

@@ -9,6 +9,7 @@
 #include <hip/hip_fp16.h>
 
 #include "mq_common.h"
+#include "mobilequant_amd_tuning.h"
 
 namespace mq {
 
@@ -304,6 +305,163 @@ static int launch_tensor(const T* x, int64_t numel, float* mn, float* mx, hipStr
   if (g > 512) g = 512;               // 2 workgroups per CU keep 8 MB in flight; a fresh statistic sees <= 1024 atomics
   minmax_tensor_kernel<T><<<(unsigned)g, 256, 0, st>>>(x, numel, head, nvec, mn, mx);
   MQ_LAUNCH_CHECK("mq_minmax_tensor");
+  return MQ_OK;
+}
+
+// ---- per-tensor histogram on the fp32 bit pattern, with the running min / max, in one pass (mq_hist_minmax_tensor) -------------------
+// THE RULE.  mantissa_bits m in 0..6, NB = 256 << m magnitude keys, 2 NB bins.  For an element x (fp16 is converted
+// to fp32 first: exact), u = bits(x):
+//   * -0 counts as +0 (as the min / max kernels canonicalise it); a NaN goes to nan_count and to no bin;
+//   * otherwise mag = (u & 0x7fffffff) >> (23 - m); bin = NB + mag for x >= 0, bin = NB - 1 - mag for x < 0.
+// Bin order is value order; denormals fall in the linear exponent-0 bins; +-inf are the only occupants of keys 255 << m.  Bin bounds
+// are exact fp32 numbers: with f(k) = float_from_bits(min(k, 255 << m) << (23 - m)) a non-negative bin of key k holds [f(k), f(k + 1)),
+// a negative one (-f(k + 1), -f(k)].
+// Range from a histogram (host: calibration.percentile_range): counts c[0 .. 2 NB), N = sum c (NaNs are not in it), the observed exact
+// mn / mx and a coverage p in (0, 1]: tail = floor((1.0 - p) * 0.5 * N) in IEEE double in exactly this order; lo = the lowest bin with
+// sum_{i <= lo} c[i] > tail, hi = the highest bin with sum_{i >= hi} c[i] > tail; min = max(lower bound of lo, mn),
+// max = min(upper bound of hi, mx), both fp32.  p = 1 returns [mn, mx]; at least N - 2 tail counted values lie inside the result; the
+// result depends on the multiset of values only.
+// THE KERNEL.  The streaming loop of minmax_tensor_kernel (16-byte loads, scalar head / tail); every workgroup keeps a private u32
+// histogram in dynamic LDS (2 NB dwords: 64 KiB at m = 5 -- two workgroups per CU --, 128 KiB at m = 6 -- one), filled with LDS integer
+// atomics, and commits its non-zero bins with 64-bit vector integer atomics: integer adds, exact in any order.  A workgroup flushes
+// once, at its end: the grid has 512 workgroups whenever a tensor has more than 2^19 vectors, so at numel <= 2^40 (checked by the entry
+// point) a workgroup sees at most 2^31 + 2064 elements and no u32 counter can wrap.
+// CONTENTION.  Same-address LDS atomics of one wave serialise.  AGG: when every active lane of a wave holds the same key (a constant
+// run of 256 elements or more: the masked zeros of causal probabilities, a saturated activation) one lane adds the lane count -- a
+// readfirstlane, a compare and a ballot per element.  mq_hist_set_aggregate(0) (tuning header) takes the check out for A/B timing.
+template <typename T>
+struct HistLd;
+template <>
+struct HistLd<float> {
+  static constexpr int N = 4;
+  __device__ static void load(const float* p, float (&f)[4]) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+  }
+};
+template <>
+struct HistLd<__half> {
+  static constexpr int N = 8;
+  __device__ static void load(const __half* p, float (&f)[8]) {
+    struct alignas(16) H8 { __half h[8]; };
+    const H8 v = *reinterpret_cast<const H8*>(p);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = __half2float(v.h[j]);
+  }
+};
+
+template <bool AGG>
+__device__ __forceinline__ void hist_count(unsigned int* hist, float f, int shift, unsigned int nb, unsigned int& nan) {
+  const unsigned int u = __float_as_uint(f), a = u & 0x7fffffffu;
+  const bool isnan = a > 0x7f800000u;
+  const unsigned int mag = a >> shift;                               // < nb for every pattern: the bin is inside the histogram even for a NaN
+  const unsigned int bin = ((u >> 31) && a) ? nb - 1 - mag : nb + mag;
+  nan += isnan ? 1u : 0u;
+  if (AGG) {
+    const unsigned int key = isnan ? 0xffffffffu : bin;
+    const unsigned long long active = __builtin_amdgcn_ballot_w64(true);
+    const unsigned int first = __builtin_amdgcn_readfirstlane(key);
+    if (__builtin_amdgcn_ballot_w64(key == first) == active) {     // wave-uniform branch
+      if ((int)(threadIdx.x & 63) == __builtin_ctzll(active) && !isnan) atomicAdd(hist + bin, (unsigned int)__builtin_popcountll(active));
+      return;
+    }
+  }
+  if (!isnan) atomicAdd(hist + bin, 1u);
+}
+
+template <typename T, bool AGG>
+__global__ void __launch_bounds__(256) hist_minmax_tensor_kernel(const T* __restrict__ x, int64_t numel, int64_t head, int64_t nvec, int mbits,
+                                                                 unsigned long long* counts, unsigned long long* nan_count, float* mn, float* mx) {
+  using L = HistLd<T>;
+  constexpr int N = L::N;
+  extern __shared__ __attribute__((aligned(16))) unsigned int s_hist[];
+  const unsigned int nb = 256u << mbits;
+  const int shift = 23 - mbits, nbins = (int)(2 * nb);
+  for (int i = threadIdx.x; i < nbins; i += 256) s_hist[i] = 0u;
+  __syncthreads();
+  float lo = __int_as_float(0x7f800000), hi = __int_as_float(0xff800000);
+  unsigned int nan = 0;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const T* xv = x + head;
+  auto take = [&](const float (&f)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      lo = min_p(lo, f[j]);
+      hi = max_p(hi, f[j]);
+      hist_count<AGG>(s_hist, f[j], shift, nb, nan);
+    }
+  };
+  int64_t i = tid;
+  for (; i + 3 * stride < nvec; i += 4 * stride) {                   // four 16-byte loads in flight per lane, as stream_minmax
+    float f0[N], f1[N], f2[N], f3[N];
+    L::load(xv + i * N, f0);
+    L::load(xv + (i + stride) * N, f1);
+    L::load(xv + (i + 2 * stride) * N, f2);
+    L::load(xv + (i + 3 * stride) * N, f3);
+    take(f0);
+    take(f1);
+    take(f2);
+    take(f3);
+  }
+  for (; i < nvec; i += stride) {
+    float f0[N];
+    L::load(xv + i * N, f0);
+    take(f0);
+  }
+  // scalar ends: [0, head) and [head + nvec * N, numel)
+  const int64_t tail0 = head + nvec * N;
+  const int64_t nscalar = head + (numel - tail0);
+  for (int64_t i2 = tid; i2 < nscalar; i2 += stride) {
+    const float f = Ld16<T>::one(x + (i2 < head ? i2 : tail0 + (i2 - head)));
+    lo = min_p(lo, f);
+    hi = max_p(hi, f);
+    hist_count<AGG>(s_hist, f, shift, nb, nan);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < nbins; b += 256) {                   // a wave commits 64 adjacent bins: 512 contiguous bytes where they are occupied
+    const unsigned int c = s_hist[b];
+    if (c) atomicAdd(counts + b, (unsigned long long)c);
+  }
+  const int nn = wave_sum((int)nan);                                 // (<= 2^31 + 2064 elements per workgroup: see above)
+  if ((threadIdx.x & 63) == 0 && nn) atomicAdd(nan_count, (unsigned long long)(unsigned int)nn);
+  if (mn) block_commit(lo, hi, mn, mx);
+}
+
+constexpr int64_t kHistMaxNumel = (int64_t)1 << 40;
+static std::atomic<int> g_hist_aggregate{1};
+
+template <typename T>
+static int launch_hist(const T* x, int64_t numel, int mbits, unsigned long long* counts, unsigned long long* nan_count, float* mn, float* mx,
+                       hipStream_t st) {
+  constexpr int N = HistLd<T>::N;
+  int64_t head = 0;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x);
+  if (a % 16) head = (int64_t)((16 - a % 16) / sizeof(T));
+  if (a % sizeof(T)) head = numel;  // cannot happen for real tensors
+  if (head > numel) head = numel;
+  const int64_t nvec = (numel - head) / N;
+  int64_t g = (nvec + 1023) / 1024;
+  if (g < 1) g = 1;
+  if (g > 512) g = 512;               // with numel <= kHistMaxNumel: at most 2^31 + 2064 elements per workgroup, no u32 bin can wrap
+  const size_t lds = (size_t)(512u << mbits) * sizeof(unsigned int);
+  const bool agg = g_hist_aggregate.load(std::memory_order_relaxed) != 0;
+  const void* fn = agg ? (const void*)hist_minmax_tensor_kernel<T, true> : (const void*)hist_minmax_tensor_kernel<T, false>;
+  static PerDeviceOnce attr_set[2];
+  const int dev = current_device();
+  if (lds >= 65536 && !attr_set[agg].done(dev)) {                   // (+ block_commit's 32 static bytes: m = 5 is already past the default 64 KiB)
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    if (e != hipSuccess) {
+      set_error("mq_hist_minmax_tensor: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+      return MQ_EHIP;
+    }
+    attr_set[agg].mark(dev);
+  }
+  if (agg)
+    hist_minmax_tensor_kernel<T, true><<<(unsigned)g, 256, lds, st>>>(x, numel, head, nvec, mbits, counts, nan_count, mn, mx);
+  else
+    hist_minmax_tensor_kernel<T, false><<<(unsigned)g, 256, lds, st>>>(x, numel, head, nvec, mbits, counts, nan_count, mn, mx);
+  MQ_LAUNCH_CHECK("mq_hist_minmax_tensor");
   return MQ_OK;
 }
 
@@ -702,6 +860,28 @@ int mq_minmax_tensor(const void* x, int dtype, int64_t numel, float* min_out, fl
   if (dtype == MQ_F16) return launch_tensor<__half>((const __half*)x, numel, min_out, max_out, as_stream(stream));
   set_error("mq_minmax_tensor: dtype %d not supported", dtype);
   return MQ_EUNSUPPORTED;
+}
+
+int mq_hist_minmax_tensor(const void* x, int dtype, int64_t numel, int mantissa_bits, uint64_t* counts, uint64_t* nan_count, float* min_out,
+                          float* max_out, mq_stream_t stream) {
+  const char* fn = "mq_hist_minmax_tensor";
+  MQ_REQUIRE(counts && nan_count, "%s: null pointer (counts / nan_count)", fn);
+  MQ_REQUIRE((min_out == nullptr) == (max_out == nullptr), "%s: null pointer (min_out / max_out are nullable as a pair only)", fn);
+  MQ_REQUIRE(mantissa_bits >= 0 && mantissa_bits <= 6, "%s: mantissa_bits=%d outside 0..6", fn, mantissa_bits);
+  MQ_REQUIRE(dtype == MQ_F32 || dtype == MQ_F16, "%s: dtype %d not supported", fn, dtype);
+  MQ_REQUIRE(numel >= 0 && numel <= kHistMaxNumel, "%s: numel=%lld outside 0..2^40 (a workgroup's 32-bit bins could wrap)", fn, (long long)numel);
+  if (numel == 0) return MQ_OK;   // empty input leaves the running statistics untouched
+  MQ_REQUIRE(x, "%s: null pointer (x)", fn);
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit counters");
+  unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
+  unsigned long long* n = reinterpret_cast<unsigned long long*>(nan_count);
+  if (dtype == MQ_F32) return launch_hist<float>((const float*)x, numel, mantissa_bits, c, n, min_out, max_out, as_stream(stream));
+  return launch_hist<__half>((const __half*)x, numel, mantissa_bits, c, n, min_out, max_out, as_stream(stream));
+}
+
+int mq_hist_set_aggregate(int on) {
+  g_hist_aggregate.store(on ? 1 : 0, std::memory_order_relaxed);
+  return 0;
 }
 
 int mq_minmax_tensor_fresh(const void* x, int dtype, int64_t numel, float* min_out, float* max_out, float* scratch,

@@ -99,6 +99,30 @@ def minmax_tensor_(x: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor) -> None:
         _lib.call("mq_minmax_tensor", x.data_ptr(), _fdt(x), x.numel(), mn.data_ptr(), mx.data_ptr(), _stream())
 
 
+def hist_new(n_slots: int, mantissa_bits: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fresh running histograms of mq_hist_minmax_tensor: (counts int64 [n_slots, 2 * NB], nan int64 [n_slots]), NB = 256 << mantissa_bits.
+    The kernel reads the int64 words as unsigned 64-bit counters (counts stay below 2^63)."""
+    if not 0 <= int(mantissa_bits) <= 6:
+        raise ValueError(f"mobilequant_amd: mantissa_bits={mantissa_bits} outside 0..6")
+    return (torch.zeros((n_slots, 512 << int(mantissa_bits)), dtype=torch.int64, device=device),
+            torch.zeros((n_slots,), dtype=torch.int64, device=device))
+
+
+def hist_minmax_tensor_(t: torch.Tensor, counts_row: torch.Tensor, nan_row: torch.Tensor, mn: Optional[torch.Tensor], mx: Optional[torch.Tensor],
+                        mantissa_bits: int) -> None:
+    """ONE pass over t: its bit-pattern histogram is ADDED to counts_row [2 * NB] / nan_row [1] (int64, read as u64) and its min / max
+    folded into the running mn / mx (1-element fp32, the bits of minmax_tensor_; None as a pair: histogram only)."""
+    x = _dev(t, "x").contiguous()
+    for c, what, n in ((counts_row, "counts_row", 512 << int(mantissa_bits)), (nan_row, "nan_row", 1)):
+        if _dev(c, what).dtype != torch.int64 or not c.is_contiguous() or c.numel() != n:
+            raise RuntimeError(f"mobilequant_amd: {what} must be a contiguous int64 tensor of {n} elements (got {c.dtype}, {tuple(c.shape)})")
+    if (mn is None) != (mx is None):
+        raise RuntimeError("mobilequant_amd: hist_minmax_tensor_ takes mn and mx as a pair")
+    with _on(x, counts_row, nan_row, mn, mx):
+        _lib.call("mq_hist_minmax_tensor", x.data_ptr(), _fdt(x), x.numel(), int(mantissa_bits), counts_row.data_ptr(), nan_row.data_ptr(),
+                  None if mn is None else mn.data_ptr(), None if mx is None else mx.data_ptr(), _stream())
+
+
 def minmax_rows_(x2d: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor) -> None:
     x2d = _dev(x2d, "x").contiguous()
     rows, cols = x2d.shape

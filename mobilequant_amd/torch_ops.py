@@ -15,6 +15,7 @@ Operators (reference code each one replaces):
     quantize(x, scale, offset, qmin, qmax, shift, chan_scale?) -> (int8, int32)      the index half of it (+ row sums), n1
     minmax(x, per_channel) -> Tensor[2] | Tensor[2, C]                              compute_min_max_from_tensor, qmodule.py:26-34
     minmax_update_(running[2, n], x) -> ()                                         update_act_range, generate_act_range.py:49-76
+    hist_minmax_update_(counts[2 NB], nan[1], running[2, 1], x, mantissa_bits) -> ()  (no reference code: DESIGN.md 4.1h; percentile ranges)
     w8a8_linear(xq, row_sum, wq, alpha, w_zp, col_term, bias?, out_scale?, out_offset?, out_qmin, out_qmax) -> Tensor
                                                                                     QLinear.forward, qmodule.py:341-358
     pack_w4(nibbles) -> uint8                                                       the 4-bit image of a quantised weight
@@ -85,6 +86,18 @@ def _(running, x):
     return None
 
 
+@torch.library.custom_op(f"{_NS}::hist_minmax_update_", mutates_args=("counts", "nan", "running"), device_types="cuda")
+def hist_minmax_update_(counts: torch.Tensor, nan: torch.Tensor, running: torch.Tensor, x: torch.Tensor, mantissa_bits: int) -> None:
+    """counts int64 [2 * (256 << mantissa_bits)] and nan int64 [1] grow by x's bit-pattern histogram; running [2, 1] (row 0 = min,
+    row 1 = max) folds x's min / max in -- one pass over x."""
+    ops.hist_minmax_tensor_(x, counts, nan, running[0], running[1], mantissa_bits)
+
+
+@hist_minmax_update_.register_fake
+def _(counts, nan, running, x, mantissa_bits):
+    return None
+
+
 def _linear(xq, row_sum, wq, alpha, w_zp, col_term, bias, out_scale, out_offset, out_qmin, out_qmax, w4):
     return ops.int8_linear(xq, wq, row_sum, alpha, w_zp, col_term, bias, out_scale=out_scale, out_offset=out_offset, out_qmin=out_qmin,
                            out_qmax=out_qmax, out_dtype=MQ_F32, w4=w4)
@@ -134,4 +147,4 @@ def _(caches, pos, parent):
     return None
 
 
-OPS = ("fake_quant", "quantize", "minmax", "minmax_update_", "w8a8_linear", "pack_w4", "w4a8_linear", "decode_cache_fork")
+OPS = ("fake_quant", "quantize", "minmax", "minmax_update_", "hist_minmax_update_", "w8a8_linear", "pack_w4", "w4a8_linear", "decode_cache_fork")
