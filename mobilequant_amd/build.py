@@ -26,8 +26,13 @@ SOURCES = ["mq_fake_quant.hip", "mq_quantize.hip", "mq_reduce.hip", "mq_gemm.hip
 # mq_decode.hip: no SLP vectorisation -- a v_pk_mul_f32 names a register PAIR although op_sel reads one half; when the other half
 # is the destination of a load still in flight, hipcc's waitcnt pass waits for it (vmcnt(0) = the whole weight stream) in front of
 # the activation-image arithmetic (mq_decode_batch.hip, mq_decode_grouped.hip: the same prologue and stream structure, the same reason)
+# mq_quantize.hip, mq_gemm.hip: kernel-argument preload -- the leading scalar parameters (14 dwords at most; never a struct by value)
+# arrive in user SGPRs at wave launch, so quantize_tiled8_kernel and gemm_i8_fr_kernel do not open with a cold read of their own
+# kernel-argument segment (tools/kernarg_audit.py)
+KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 PER_FILE_FLAGS = {"mq_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "mq_decode.hip": ["-fno-slp-vectorize"],
-                  "mq_decode_batch.hip": ["-fno-slp-vectorize"], "mq_decode_grouped.hip": ["-fno-slp-vectorize"]}
+                  "mq_decode_batch.hip": ["-fno-slp-vectorize"], "mq_decode_grouped.hip": ["-fno-slp-vectorize"],
+                  "mq_quantize.hip": KERNARG_PRELOAD, "mq_gemm.hip": KERNARG_PRELOAD}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ABLATE = (["-DMQ_GEMM_ABLATE"] if os.environ.get("MQ_GEMM_ABLATE") else []) + \
     ([f"-DMQ_PP_PRIO={os.environ['MQ_PP_PRIO']}"] if os.environ.get("MQ_PP_PRIO") else [])

@@ -767,8 +767,8 @@ __global__ void __launch_bounds__(64 * WM * WN)
 // ---- one launch path ------------------------------------------------------------------------------------------------------------------
 // The dynamic-LDS attribute once per device and kernel (KFN is a template argument: one PerDeviceOnce per kernel instantiation), the
 // launch, the check.
-template <auto KFN, typename Args>
-static int launch_kernel(const Args& args, int blocks, int threads, int lds, hipStream_t st) {
+template <auto KFN, typename Args, typename... Lead>   // lead: scalar parameters in front of the struct (preloaded kernel arguments)
+static int launch_kernel(const Args& args, int blocks, int threads, int lds, hipStream_t st, Lead... lead) {
   static PerDeviceOnce attr_set;
   const int dev = current_device();
   if (!attr_set.done(dev)) {
@@ -779,7 +779,7 @@ static int launch_kernel(const Args& args, int blocks, int threads, int lds, hip
     }
     attr_set.mark(dev);
   }
-  KFN<<<blocks, threads, lds, st>>>(args);
+  KFN<<<blocks, threads, lds, st>>>(lead..., args);
   MQ_LAUNCH_CHECK("mq_gemm");
   return MQ_OK;
 }
@@ -974,7 +974,25 @@ __device__ __forceinline__ void gemm_i8_fr_body(const GemmArgs& args, int bid, i
   MQ_FR_ZERO_TAIL(bid, 512)
 }
 
-__global__ void __launch_bounds__(512) gemm_i8_fr_kernel(const GemmArgs args) { gemm_i8_fr_body(args, blockIdx.x, args.grid_m * args.grid_n); }
+// Kernel-argument preload (build.PER_FILE_FLAGS): gfx950 delivers up to 14 leading dwords of scalar parameters in user SGPRs at wave
+// launch; a struct passed by value is never preloaded.  The 13 dwords in front are what the tile map, the W pieces and the fragment
+// offsets need, and the grid pointers the program dereferences first; `rest` is the whole GemmArgs (its copies of the leading fields
+// are not read): requested first, waited for behind the tile map's two divisions, where the per-n pointers are formed.  The phases
+// read `args` as everywhere else -- here a local GemmArgs whose leading fields come from the registers (tools/kernarg_audit.py).
+__global__ void __launch_bounds__(512) gemm_i8_fr_kernel(const int8_t* a, const void* w, int M, int N, int K, int grid_m, int grid_n,
+                                                         const float* out_scale, const float* out_offset, const GemmArgs rest) {
+  GemmArgs args = rest;
+  args.a = a;
+  args.w = w;
+  args.M = M;
+  args.N = N;
+  args.K = K;
+  args.grid_m = grid_m;
+  args.grid_n = grid_n;
+  args.out_scale = out_scale;
+  args.out_offset = out_offset;
+  gemm_i8_fr_body(args, blockIdx.x, grid_m * grid_n);
+}
 
 // ---- the free-running program on 128-column tiles (tools/gen_fr_asm.py variants fr128 / fr128r / fr128r8) ------------------------------
 // N = 2048 / 2560 outputs do not tile by 176.  FR128: 256 x 128 tiles, eight waves, 8-bit unsigned output grid PER COLUMN (the q | k | v
@@ -1272,7 +1290,8 @@ static int launch_fr_pair(const GemmArgs& a0, const GemmArgs& a1, hipStream_t st
 
 static int launch_fr(GemmArgs a, hipStream_t st) {
   prepare_tiles(a, 256, 176);
-  return launch_kernel<gemm_i8_fr_kernel>(a, a.grid_m * a.grid_n, 512, MQ_FR_LDS_BYTES, st);
+  return launch_kernel<gemm_i8_fr_kernel>(a, a.grid_m * a.grid_n, 512, MQ_FR_LDS_BYTES, st, a.a, a.w, a.M, a.N, a.K, a.grid_m, a.grid_n, a.out_scale,
+                                          a.out_offset);
 }
 
 // ---- variants & dispatch --------------------------------------------------------------------------

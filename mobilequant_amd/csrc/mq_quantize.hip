@@ -313,17 +313,23 @@ static int launch_quantize(const T* x, QT* q, int64_t rows, int64_t cols, const 
 // GRPS = 2: four rows per 512-thread workgroup, TWO workgroups per CU -- one's loads fly while the other converts and stores
 // (mq_quantize_tiled_set_rows; the same change as in mq_norm.hip's norm_tiled8_kernel).
 template <int V, bool HAS_SUM, int GRPS = 4>
-__global__ void __launch_bounds__(256 * GRPS) quantize_tiled8_kernel(const float* __restrict__ x, int8_t* __restrict__ q, int64_t rows, int64_t cols,
-                                                               const float* __restrict__ scale, const float* __restrict__ offset, float qmin,
-                                                               float qmax, int shift, int32_t* __restrict__ row_sum) {
+__global__ void __launch_bounds__(256 * GRPS) quantize_tiled8_kernel(const float* __restrict__ x, int8_t* __restrict__ q, const float* __restrict__ scale,
+                                                               const float* __restrict__ offset, int32_t* __restrict__ row_sum, int rows32, int shift,
+                                                               float qmin, float qmax) {
+  // The parameter list is 14 dwords, the most gfx950 delivers in user SGPRs at wave launch (kernarg preload, build.PER_FILE_FLAGS): the
+  // body reads nothing from the kernel-argument segment (tools/kernarg_audit.py).  cols is the compile-time KCOLS; rows fits 32 bits
+  // (checked by mq_quantize_tiled).
+  const int64_t rows = rows32;
   typedef float v4f __attribute__((ext_vector_type(4)));
   constexpr int RW = 2 * GRPS;                                      // rows per workgroup
   constexpr int KCOLS = 1024 * V;                                   // == cols (mq_quantize_tiled's dispatch)
   extern __shared__ __attribute__((aligned(16))) int8_t stage8[];   // [cols / 16 pieces][RW rows][16 B]
   __shared__ int s_part[RW][4];
   // Request order (it matters on cold caches only, DESIGN 4.1: every wait below is a round trip to the fabric, and they stand in a row).
-  // ONE batch of kernel-argument reads: the image and row-sum pointers are consumed here, so hipcc cannot leave their reads to the
-  // tail behind the barrier, where each would be waited for in front of the stores it feeds.
+  // The kernel arguments arrive preloaded, so the first request is the grid values'; on firmware that does not preload, the compiler's
+  // entry block reads all of them in ONE batch.  (The empty asm consumes the image and row-sum pointers here: it kept hipcc from leaving
+  // their reads to the tail behind the barrier, each waited for in front of the stores it feeds, and still would if the list outgrew
+  // the preload.)
   asm volatile("" ::"s"(q), "s"(row_sum));
   // the grid values: requested before any address arithmetic, waited for behind the last x request (as bit patterns: scalar registers)
   uint32_t s_bits = reinterpret_cast<const uint32_t*>(scale)[0], o_bits = reinterpret_cast<const uint32_t*>(offset)[0];
@@ -380,14 +386,14 @@ __global__ void __launch_bounds__(256 * GRPS) quantize_tiled8_kernel(const float
     asm volatile("; mq-full-path-end" ::: "memory");
   } else {
     // ragged and padding workgroups (row0 + RW > rows): addresses clamped to the last real row
-    const int nvec = (int)(cols >> 2);
+    constexpr int nvec = KCOLS >> 2;
     const float s = __builtin_bit_cast(float, s_bits), o = __builtin_bit_cast(float, o_bits);
     const float inv_s = __fdiv_rn(1.0f, s);
     float4 xs[2][V];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int64_t row = row0 + grp * 2 + j;
-      const float4* xr = reinterpret_cast<const float4*>(x + (row < rows ? row : rows - 1) * cols);
+      const float4* xr = reinterpret_cast<const float4*>(x + (row < rows ? row : rows - 1) * KCOLS);
 #pragma unroll
       for (int k = 0; k < V; ++k) xs[j][k] = xr[lane + 256 * k < nvec ? lane + 256 * k : nvec - 1];
     }
@@ -502,6 +508,7 @@ int mq_quantize_tiled(const void* x, int dtype, int64_t rows, int64_t cols, cons
     if (row_sum) quantize_tiled_kernel<float, true, 0, true><<<grid, 512, 0, st>>>((const float*)x, q_tiled, rows, cols, scale, offset, qmin, qmax, shift, row_sum, chan_scale);
     else quantize_tiled_kernel<float, false, 0, true><<<grid, 512, 0, st>>>((const float*)x, q_tiled, rows, cols, scale, offset, qmin, qmax, shift, row_sum, chan_scale);
   } else if (dtype == MQ_F32 && cols >= 1024 && cols <= 4096 && cols % 1024 == 0 && rows >= 64 && g_tiled8.load()) {
+    MQ_REQUIRE(rows <= (int64_t)0x7fffffff, "mq_quantize_tiled: %lld rows do not fit the staged kernel's 32-bit row count", (long long)rows);
     const int rows_knob = g_tiled8_rows.load();
     const bool four = rows_knob == 4 || (rows_knob == 0 && cols <= 2048);
     const unsigned grid8 = (unsigned)(((rows + 15) / 16) * (four ? 4 : 2));
@@ -509,10 +516,10 @@ int mq_quantize_tiled(const void* x, int dtype, int64_t rows, int64_t cols, cons
 #define MQ_QT8(V)                                                                                                                              \
   do {                                                                                                                                         \
     if (four) {                                                                                                                                \
-      if (row_sum) quantize_tiled8_kernel<V, true, 2><<<grid8, 512, lds, st>>>((const float*)x, q_tiled, rows, cols, scale, offset, qmin, qmax, shift, row_sum);  \
-      else quantize_tiled8_kernel<V, false, 2><<<grid8, 512, lds, st>>>((const float*)x, q_tiled, rows, cols, scale, offset, qmin, qmax, shift, row_sum);        \
-    } else if (row_sum) quantize_tiled8_kernel<V, true><<<grid8, 1024, lds, st>>>((const float*)x, q_tiled, rows, cols, scale, offset, qmin, qmax, shift, row_sum);  \
-    else quantize_tiled8_kernel<V, false><<<grid8, 1024, lds, st>>>((const float*)x, q_tiled, rows, cols, scale, offset, qmin, qmax, shift, row_sum);        \
+      if (row_sum) quantize_tiled8_kernel<V, true, 2><<<grid8, 512, lds, st>>>((const float*)x, q_tiled, scale, offset, row_sum, (int)rows, shift, qmin, qmax);  \
+      else quantize_tiled8_kernel<V, false, 2><<<grid8, 512, lds, st>>>((const float*)x, q_tiled, scale, offset, row_sum, (int)rows, shift, qmin, qmax);        \
+    } else if (row_sum) quantize_tiled8_kernel<V, true><<<grid8, 1024, lds, st>>>((const float*)x, q_tiled, scale, offset, row_sum, (int)rows, shift, qmin, qmax);  \
+    else quantize_tiled8_kernel<V, false><<<grid8, 1024, lds, st>>>((const float*)x, q_tiled, scale, offset, row_sum, (int)rows, shift, qmin, qmax);        \
   } while (0)
     if (cols == 1024) MQ_QT8(1);
     else if (cols == 2048) MQ_QT8(2);
