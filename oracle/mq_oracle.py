@@ -1449,3 +1449,139 @@ def calib_rope(x_lin, heads, head_dim, cos, sin, rotate=True, rep=1):
     if rotate:
         x = rope_partial(x, np.asarray(cos, F32), np.asarray(sin, F32)).astype(F32)
     return np.ascontiguousarray(repeat_kv(x, rep))
+
+
+# ----------------------------------------------------------------------------------------------
+# a7 (prefill)  the GEMM family's fused epilogues   csrc/mq_gemm.hip, tools/gen_fr_asm.py
+# ----------------------------------------------------------------------------------------------
+def fma_f32(a, b, c):
+    """The correctly rounded fp32 of a * b + c for fp32 arrays (v_fma_f32, __builtin_fmaf), finite results.
+
+    The float64 product of two fp32 values is exact (48 significant bits); the float64 sum s = p + c is not, and float32(s) can round
+    twice.  TwoSum gives the sum's residual e exactly (p + c = s + e).  float32(s) is wrong only where s lies exactly on the midpoint
+    of two neighbouring fp32 values and e != 0: a float64 that is no midpoint is at least one float64 ulp away from every midpoint,
+    |e| is at most half of one, so s + e is on the same side of every midpoint as s.  On a midpoint the sign of e decides."""
+    a64, b64, c64 = (np.asarray(v, F32).astype(np.float64) for v in (a, b, c))
+    p = a64 * b64
+    s = p + c64
+    bb = s - p
+    e = (p - (s - bb)) + (c64 - bb)                   # TwoSum (Knuth): exact residual of the float64 add
+    r = s.astype(F32)
+    d = s - r.astype(np.float64)                      # exact: r is the fp32 next to s
+    other = np.nextafter(r, np.where(d > 0, F32(np.inf), F32(-np.inf)).astype(F32)).astype(F32)
+    midpoint = (d != 0) & (s == (r.astype(np.float64) + other.astype(np.float64)) * 0.5)
+    toward_other = midpoint & (e != 0) & ((e > 0) == (d > 0))
+    # on a midpoint with e == 0 the tie is real and r (ties-to-even) stands; with e pointing back to r, r stands as well
+    return np.where(toward_other, other, r).astype(F32)
+
+
+def prefill_gemm_acc(a_idx, w_idx, a_rowsum, w_zp, col_term):
+    """int32 [M, N]: wrap32(a . w^T - w_zp[n] * a_rowsum[m] + col_term[n]), what the accumulators hold in front of every prefill GEMM
+    epilogue (they START at the zero-point correction, in int32 wrap-around arithmetic, and the MFMAs add the contraction).  a_idx
+    [M, K] and w_idx [N, K] are the stored integers (packed 4-bit weights: the unsigned nibbles).  The contraction is a float64 BLAS
+    product, exact below 2^53 as in qlinear_int_exact(blas=True).  a_rowsum None: no correction term (the caller guarantees w_zp == 0)."""
+    a = np.asarray(a_idx)
+    w = np.asarray(w_idx)
+    assert a.shape[1] == w.shape[1] and a.shape[1] * 255 * 255 < 2 ** 53
+    acc = np.rint(a.astype(np.float64) @ w.astype(np.float64).T).astype(np.int64)
+    zp = np.asarray(w_zp, np.int64).reshape(1, -1)
+    if a_rowsum is not None:
+        acc = acc - zp * np.asarray(a_rowsum, np.int64).reshape(-1, 1)
+    else:
+        assert not zp.any(), "a_rowsum None needs w_zp == 0"
+    return _wrap32(acc + np.asarray(col_term, np.int64).reshape(1, -1))
+
+
+PREFILL_GEMM_STORAGE = {"f32": np.float32, "f16": np.float16, "u8": np.uint8, "i8": np.int8, "u16": np.uint16, "i16": np.int16}
+
+
+def prefill_gemm_columns(N, grids, seg_end):
+    """(scale fp32 [N], offset fp32 [N]): grids = [(scale, offset)] per column segment, seg_end their increasing ends (the last is N; a
+    single segment may come without ends)."""
+    ends = [int(N)] if len(grids) == 1 else [int(v) for v in seg_end]
+    assert len(ends) == len(grids) and ends[-1] == N and all(b > a for a, b in zip([0] + ends, ends))
+    sc, oo = np.empty(N, F32), np.empty(N, F32)
+    lo = 0
+    for (s, o), hi in zip(grids, ends):
+        sc[lo:hi], oo[lo:hi] = F32(s), F32(o)
+        lo = hi
+    return sc, oo
+
+
+def prefill_gemm_epilogue(t, alpha, bias=None, grids=None, seg_end=None, out_qmin=0, out_qmax=255, out_dtype="f32", resid=None):
+    """What every prefill GEMM stores for the int32 accumulators t [M, N] (prefill_gemm_acc), one rounding per step: the C++ epilogue
+    of gemm_i8_kernel and the generated one of tools/gen_fr_asm.py are the same fixed sequence of correctly rounded fp32 operations
+    (the library is built with -ffp-contract=off).  Returns (stored [M, N] in the storage type, q float64, tie float64): q is the value
+    in front of the rounding to an index (the fma's fp32 result; without a grid, the fp32 output) and tie its distance to the nearest
+    half-integer, so that a failure can say how close to a rounding boundary the element was.
+
+    grids None (f32 / f16 output only):  fl(fl(float(t) * alpha) + bias), bias 0.0f when absent; f16 rounds once more.
+    grids = [(scale, offset)] per column segment (prefill_gemm_columns), per column n:
+        inv = fl(1 / scale),  A' = fl(alpha * inv),  B' = fl(bias * inv) (bias 0.0f when absent),
+        B' = fl(B' + offset)  when out_qmax - out_qmin <= 255 (the offset rides in the addend for EVERY storage type),
+        q  = fma(float(t), A', B')   with float(t) = int32 -> fp32, round to nearest even (v_cvt_f32_i32),
+        r  = rint(q) (to even);  r = fl(r + offset) when the offset was not folded;  r = clamp(r, out_qmin, out_qmax).
+    Storage: u8 the index (saturated to 0..255, what v_cvt_pk_u8_f32 does); i8 on the grid 0..255 byte ^ 0x80 (= index - 128), on
+    any other grid int & 0xff; u16 / i16 int & 0xffff; f32 / f16 fl(fl(r - offset) * scale), f16 rounded once more.  resid (f32
+    only): fl(resid + y).
+
+    Where this differs from the plain reading of "clamp(round(v / scale) + offset)": the kernels multiply by the rounded reciprocal and
+    fold alpha and the bias into it BEFORE the contraction's value is known, so v itself is never formed.  The unsigned 8-bit fast path
+    (grid 0..255, u8 / i8 storage) has no rint and no clamp instruction: v_cvt_pk_u8_f32 rounds to nearest even and saturates, which
+    is the same function.  A dequantised output (f32 / f16) takes scale and offset of the FIRST grid only: the kernels read column
+    segments for u8 / i8 storage alone, and the entry points pass them nowhere else."""
+    t = np.asarray(t)
+    assert t.dtype == np.int32 and t.ndim == 2
+    N = t.shape[1]
+    tf = t.astype(F32)                                             # int32 -> fp32, round to nearest even
+    al = np.asarray(alpha, F32).reshape(1, N)
+    bs = np.zeros((1, N), F32) if bias is None else np.asarray(bias, F32).reshape(1, N)
+    st = PREFILL_GEMM_STORAGE[out_dtype]
+    if grids is None:
+        assert out_dtype in ("f32", "f16")
+        with np.errstate(over="ignore"):
+            v = ((tf * al).astype(F32) + bs).astype(F32)
+        q = v.astype(np.float64)
+    else:
+        qmin, qmax = F32(out_qmin), F32(out_qmax)
+        fold = (qmax - qmin) <= F32(255.0)
+        assert len(grids) == 1 or out_dtype in ("u8", "i8"), "column segments: index outputs only"
+        sc, oo = prefill_gemm_columns(N, grids, seg_end)
+        inv = (F32(1.0) / sc).astype(F32).reshape(1, N)
+        oo = oo.reshape(1, N)
+        a1 = (al * inv).astype(F32)
+        b1 = (bs * inv).astype(F32)
+        if fold:
+            b1 = (b1 + oo).astype(F32)
+        qf = fma_f32(tf, np.broadcast_to(a1, tf.shape), np.broadcast_to(b1, tf.shape))
+        q = qf.astype(np.float64)
+        r = np.rint(qf).astype(F32)
+        if not fold:
+            r = (r + oo).astype(F32)
+        r = np.minimum(np.maximum(r, qmin), qmax)
+        ri = r.astype(np.int64)
+        if out_dtype == "u8":
+            v = np.clip(ri, 0, 255).astype(np.uint8)
+        elif out_dtype == "i8":
+            v = ((np.clip(ri, 0, 255) ^ 0x80) if out_qmin == 0 else (ri & 0xFF)).astype(np.uint8).view(np.int8)
+        elif out_dtype in ("u16", "i16"):
+            v = (ri & 0xFFFF).astype(np.uint16).view(st)
+        else:
+            v = ((r - oo).astype(F32) * sc.reshape(1, N)).astype(F32)
+    if out_dtype in ("f32", "f16"):
+        if resid is not None:
+            assert out_dtype == "f32"
+            v = (np.asarray(resid, F32) + v).astype(F32)
+        with np.errstate(over="ignore"):
+            v = v.astype(st)
+    return v, q, _tie_dist(q)
+
+
+def prefill_gemm_gated(ia, ib, table):
+    """w2's int8 input image from the gated pair: table[ia * 256 + ib] for w1's indices ia and w3's indices ib (u8 [M, N]; table int8
+    [65536], mq_gated_table).  Returns (image int8 [M, N] row-major, (bytes int8 [ceil16(M) * N], real bool) in the fragment-blocked
+    layout of tiled_image_bytes, row sums int32 [M])."""
+    ia, ib = np.asarray(ia).astype(np.int64), np.asarray(ib).astype(np.int64)
+    assert ia.shape == ib.shape and ia.min() >= 0 and ib.min() >= 0 and ia.max() <= 255 and ib.max() <= 255
+    img = np.asarray(table, np.int8).reshape(-1)[ia * 256 + ib]
+    return img, tiled_image_bytes(img, *img.shape), img.astype(np.int64).sum(axis=1).astype(np.int32)
