@@ -1585,3 +1585,215 @@ def prefill_gemm_gated(ia, ib, table):
     assert ia.shape == ib.shape and ia.min() >= 0 and ib.min() >= 0 and ia.max() <= 255 and ib.max() <= 255
     img = np.asarray(table, np.int8).reshape(-1)[ia * 256 + ib]
     return img, tiled_image_bytes(img, *img.shape), img.astype(np.int64).sum(axis=1).astype(np.int32)
+
+
+# ----------------------------------------------------------------------------------------------
+# a13 (training passes)  mq_fake_quant_backward, mq_lwc_fake_quant(_backward), mq_attention_probs_train(_backward)  (csrc/mq_fake_quant.hip)
+# ----------------------------------------------------------------------------------------------
+EXPF_ULP = 1          # ASSUMED error of the device expf, in ulp of its result: the vendor's math-API tables document 1 ulp; not measured, not
+#                       fitted to any kernel output.  An ulp is charged at its largest relative size, 2^-23 = 2 u.
+TRAIN_MUTATION = None  # tests only: "half_away" | "trunc" | "exclusive_mask" | "tie_one" | "mask_no_mod" make the functions below deliberately wrong
+P_ABS = 2.0 ** -125   # absolute allowance on exp() for results below the normal range (flushed or denormal)
+
+
+def _mutation(m):
+    return TRAIN_MUTATION if m is None else m
+
+
+def _rint_m(t, m):
+    if m == "half_away":
+        return (np.sign(t) * np.floor(np.abs(t) + 0.5)).astype(t.dtype)
+    if m == "trunc":
+        return np.trunc(t)
+    return np.rint(t)
+
+
+def fq_point(x, s, o, qmin, qmax, mutation=None):
+    """The fake-quant expression tree at every element, fp32 op for op (fake_quant_bwd_kernel's names): t = x / s (IEEE), r = round_ste(t)
+    = (rint(t) - t) + t, q = r + o, inside = qmin <= q <= qmax (inclusive: torch.clamp's backward mask), qc = clamp(q) with NaN kept,
+    y = (qc - o) * s.  Returns (t, r, inside, qc, y)."""
+    m = _mutation(mutation)
+    x, s, o = np.asarray(x, F32), np.asarray(s, F32), np.asarray(o, F32)
+    with np.errstate(all="ignore"):
+        t = (x / s).astype(F32)
+        r = ((_rint_m(t, m) - t).astype(F32) + t).astype(F32)
+        q = (r + o).astype(F32)
+        inside = ((q > F32(qmin)) & (q < F32(qmax))) if m == "exclusive_mask" else ((q >= F32(qmin)) & (q <= F32(qmax)))
+        qc = np.clip(q, F32(qmin), F32(qmax)).astype(F32)
+        y = ((qc - o).astype(F32) * s).astype(F32)
+    return t, r, inside, qc, y
+
+
+def fake_quant_backward_terms(x, grad_y, scale, offset, qmin, qmax, mutation=None):
+    """fake_quant_backward with the sums left open: grad_x bit for bit (inside ? (g * s) / s : 0), and the fp32 TERMS of the two sums exactly
+    as every kernel forms them -- ts = inside ? g * (r - t) : g * (qc - o), to = inside ? 0 : -g * s, one rounded product each (r - t and,
+    for grids of at most 2^24 steps, qc - o are exact).  A kernel's grad_scale / grad_offset is some fp32 summation of these terms: within
+    gamma_n * sum|term| of their float64 sum, n the adds on its longest path.  scale / offset: 0-d, or [rows, 1] against x [rows, cols]."""
+    g, s, o = np.asarray(grad_y, F32), np.asarray(scale, F32), np.asarray(offset, F32)
+    t, r, inside, qc, _ = fq_point(x, s, o, qmin, qmax, mutation)
+    with np.errstate(all="ignore"):
+        gx = np.where(inside, ((g * s).astype(F32) / s).astype(F32), F32(0)).astype(F32)
+        ts = np.where(inside, (g * (r - t).astype(F32)).astype(F32), (g * (qc - o).astype(F32)).astype(F32)).astype(F32)
+        to = np.where(inside, F32(0), (-g * s).astype(F32)).astype(F32)
+    return dict(gx=gx, ts=ts, to=to, inside=inside, t=t, r=r)
+
+
+def lwc_grid(mn, mx, sig_lo, sig_hi, qmax, is_symmetric):
+    """lwc_grid of the fused pass, fp32 op for op: lo = sig_lo * mn, hi = sig_hi * mx (qmodule.py:271-273), alpha = max(|lo|, |hi|) (NaN
+    kept) or hi - lo, scale = clamp(alpha / qmax) with the TRUE quotient and NaN kept, offset = -rint(beta / scale) (qmodule.py:40-61)."""
+    with np.errstate(all="ignore"):
+        lo, hi = (np.asarray(sig_lo, F32) * mn).astype(F32), (np.asarray(sig_hi, F32) * mx).astype(F32)
+        if is_symmetric:
+            alpha, beta = np.maximum(np.abs(lo), np.abs(hi)), np.zeros_like(lo)
+        else:
+            alpha, beta = (hi - lo).astype(F32), lo
+        raw = (alpha / F32(qmax)).astype(F32)
+        scale = np.clip(raw, CLIPMIN, CLIPMAX).astype(F32)
+        offset = (-np.rint((beta / scale).astype(F32))).astype(F32)
+    return dict(lo=lo, hi=hi, alpha=alpha, raw=raw, scale=scale, offset=offset)
+
+
+def lwc_fused_forward(w, sig_lo, sig_hi, bitwidth, is_symmetric):
+    """mq_lwc_fused's forward on its own interface (the sigmoids, not the factors; lwc_forward is the same expression behind sigmoid_f32):
+    row amin / amax with NaN propagated, lwc_grid, the fake-quant.  Everything fp32 op for op -- every output is exact."""
+    w = np.asarray(w, F32)
+    qmin, qmax = qrange(bitwidth, is_symmetric)
+    mn, mx = w.min(axis=1), w.max(axis=1)                                  # np.min / np.max propagate NaN, as amin / amax do
+    g = lwc_grid(mn, mx, sig_lo, sig_hi, qmax, is_symmetric)
+    y = fq_point(w, g["scale"][:, None], g["offset"][:, None], qmin, qmax)[4]
+    return dict(y=y, row_min=mn, row_max=mx, scale=g["scale"], offset=g["offset"])
+
+
+def lwc_fused_backward(w, grad_y, sig_lo, sig_hi, row_min, row_max, bitwidth, is_symmetric, mutation=None):
+    """mq_lwc_fake_quant_backward.  Exact part: gx = inside ? (g * s) / s : 0 -- grad_w wherever the element is no row extreme.  Behind the
+    row sum S = sum(ts) (terms as in fake_quant_backward_terms) everything is LINEAR in S: g_alpha = S / qmax where CLIPMIN <= alpha / qmax
+    <= CLIPMAX (bounds included) and exactly 0 elsewhere; alpha = hi - lo gives (g_lo, g_hi) = (-g_alpha, g_alpha), alpha = max(|lo|, |hi|)
+    gives the larger one g_alpha sign(.) and a tie half each; grad_sig_lo = g_lo mn, grad_sig_hi = g_hi mx; the extreme elements receive
+    g_lo sig_lo / n_mn and g_hi sig_hi / n_mx, n the number of elements EQUAL to the extreme (ties share evenly, +0 == -0).  Returned in
+    float64 with the factors c (value = c * S) so that a bound gamma_n * |c| * sum|ts| can be formed; NaN / inf follow IEEE through the
+    same expression (0 * NaN = NaN: a NaN row has grad_sig NaN and grad_w exactly 0)."""
+    m = _mutation(mutation)
+    w, g = np.asarray(w, F32), np.asarray(grad_y, F32)
+    qmin, qmax = qrange(bitwidth, is_symmetric)
+    mn, mx = np.asarray(row_min, F32), np.asarray(row_max, F32)
+    slo, shi = np.asarray(sig_lo, F32), np.asarray(sig_hi, F32)
+    gd = lwc_grid(mn, mx, slo, shi, qmax, is_symmetric)
+    b = fake_quant_backward_terms(w, g, gd["scale"][:, None], gd["offset"][:, None], qmin, qmax, m)
+    ts = b["ts"].astype(np.float64)
+    with np.errstate(all="ignore"):
+        S, sumabs = ts.sum(axis=1), np.abs(ts).sum(axis=1)
+        passes = (gd["raw"] >= CLIPMIN) & (gd["raw"] <= CLIPMAX)
+        c_alpha = np.where(passes, 1.0 / qmax, 0.0)
+        if is_symmetric:
+            alo, ahi = np.abs(gd["lo"]).astype(np.float64), np.abs(gd["hi"]).astype(np.float64)
+            c_lo = c_alpha * np.where(alo > ahi, 1.0, np.where(alo == ahi, 0.5, 0.0)) * np.sign(np.nan_to_num(gd["lo"], nan=0.0))
+            c_hi = c_alpha * np.where(ahi > alo, 1.0, np.where(alo == ahi, 0.5, 0.0)) * np.sign(np.nan_to_num(gd["hi"], nan=0.0))
+        else:
+            c_lo, c_hi = -c_alpha, c_alpha
+        Sz = np.where(passes, S, 0.0)                                        # the kernel selects 0 there, whatever S is
+        is_mn, is_mx = w == mn[:, None], w == mx[:, None]
+        if m == "tie_one":                                                   # wrong on purpose: the first of several tied elements takes it all
+            is_mn = is_mn & (np.cumsum(is_mn, axis=1) == 1)
+            is_mx = is_mx & (np.cumsum(is_mx, axis=1) == 1)
+        n_mn, n_mx = is_mn.sum(axis=1).astype(np.float64), is_mx.sum(axis=1).astype(np.float64)
+        c_add_mn, c_add_mx = c_lo * slo / n_mn, c_hi * shi / n_mx
+        g_sig_lo, g_sig_hi = (c_lo * Sz) * mn, (c_hi * Sz) * mx
+        c_sig_lo, c_sig_hi = np.abs(c_lo * mn.astype(np.float64)), np.abs(c_hi * mx.astype(np.float64))
+        scat = np.where(is_mn, (c_add_mn * Sz)[:, None], 0.0) + np.where(is_mx, (c_add_mx * Sz)[:, None], 0.0)
+        c_scat = np.where(is_mn, np.abs(c_add_mn)[:, None], 0.0) + np.where(is_mx, np.abs(c_add_mx)[:, None], 0.0)
+    return dict(gx=b["gx"], ts=b["ts"], S=S, sumabs=sumabs, extreme=is_mn | is_mx, grad_w=b["gx"].astype(np.float64) + scat, c_scat=c_scat,
+                grad_sig_lo=g_sig_lo, grad_sig_hi=g_sig_hi, c_sig_lo=c_sig_lo, c_sig_hi=c_sig_hi, passes=passes, scale=gd["scale"],
+                offset=gd["offset"])
+
+
+def train_attn_probs(raw, mask, grid1, grid2, sqrt_d, n_sum, mutation=None):
+    """mq_attention_probs_train: Q2(softmax(Q1(raw) / sqrt_d + mask)), grid = (scale, offset, qmin, qmax), mask None or additive fp32
+    [mask_rows, cols] (row r takes mask[r % mask_rows]).  x is fp32 op for op -- Q1's output has the same bits in the kernel's FAST and
+    !FAST bodies (the fast quotient is the IEEE one from |t| = 1/4 up and r = 0 below either way), one rounded division by sqrt_d (an
+    exact multiplication by its reciprocal when sqrt_d is a power of two), one rounded add of the mask.  The softmax of that x is float64,
+    rows disposed of as in calib_probs.  t2 = p / s2 in float64 and the Q2 index from it.
+    env: bound on the relative error of the kernel's fp32 p: fl(x - max) moves the exponent by u |x - max|, expf by EXPF_ULP ulp (2 u
+    each), both again as the p-weighted row mean through the sum l, gamma_n_sum for l's summation path (n_sum adds: the caller counts them
+    from the launch geometry), one division.  et: the absolute error of the kernel's t2 (its quotient: 2 u more).  An element is
+    UNDECIDED when t2 lies within et of a half-integer: the kernel may return either neighbour (out / out_alt); edge: such an element
+    straddles a Q2 clamp edge (cases are re-seeded until there is none)."""
+    m = _mutation(mutation)
+    raw = np.asarray(raw, F32)
+    rows, cols = raw.shape
+    s1, o1, qmin1, qmax1 = grid1
+    s2, o2, qmin2, qmax2 = grid2
+    s1, o1, s2, o2 = F32(s1), F32(o1), F32(s2), F32(o2)
+    t1, r1, in1, qc1, y1 = fq_point(raw, s1, o1, qmin1, qmax1, m)
+    with np.errstate(all="ignore"):
+        x = (y1 / F32(sqrt_d)).astype(F32)
+        if mask is not None:
+            mk = np.asarray(mask, F32)
+            ri = np.minimum(np.arange(rows), mk.shape[0] - 1) if m == "mask_no_mod" else np.arange(rows) % mk.shape[0]
+            x = (x + mk[ri]).astype(F32)
+        mx = x.max(axis=1)
+        nan_row = np.isnan(mx) | np.isinf(mx)
+        d = x.astype(np.float64) - np.where(nan_row, 0.0, mx.astype(np.float64))[:, None]
+        e = np.exp(d)
+        p = e / e.sum(axis=1, keepdims=True)
+        p[nan_row] = np.nan
+        a = np.where(np.isfinite(d), U32 * np.abs(d) + 2 * U32 * EXPF_ULP, 0.0)
+        env = 1.001 * (a + np.nansum(p * a, axis=1)[:, None] + _gamma(n_sum) + U32)
+        t2 = p / np.float64(s2)
+        et = (env + 2 * U32) * t2 + P_ABS / np.float64(s2)
+        r2 = _rint_m(t2, m)
+        undecided = _tie_dist(t2) <= et
+        r2_alt = np.where(t2 >= r2, r2 + 1.0, r2 - 1.0)
+
+        def q2(r):
+            q = r + np.float64(o2)
+            ins = ((q > qmin2) & (q < qmax2)) if m == "exclusive_mask" else ((q >= qmin2) & (q <= qmax2))
+            qc = np.clip(q, qmin2, qmax2)
+            return ins, qc, ((qc.astype(F32) - o2).astype(F32) * s2).astype(F32)
+        in2, qc2, out = q2(r2)
+        in2_alt, _, out_alt = q2(r2_alt)
+        edge = undecided & (in2 != in2_alt)
+    return dict(x=x, p=p, env=env, et=et, t2=t2, r2=r2, in2=in2, qc2=qc2, out=out, out_alt=out_alt, undecided=undecided, edge=edge,
+                nan_row=nan_row, masked=np.isneginf(x), t1=t1, r1=r1, in1=in1, qc1=qc1)
+
+
+def train_attn_probs_backward(raw, grad_out, mask, grid1, grid2, sqrt_d, n_sum, mutation=None):
+    """mq_attention_probs_train_backward in float64 on train_attn_probs' p, with first-order error envelopes (times 1.01 for the second
+    order) of what the kernel's fp32 chain may return:
+      Q2 backward  gp = inside2 ? (g s2) / s2 : 0 (3 u); d s2 terms g (r2 - t2) | g (qc2 - o2), error |g| et + u |term|, an undecided
+                   element |g| more; d o2 terms -g s2 outside.
+      softmax      dot = sum(gp p): sum |gp p| (env + 4 u) + gamma_n_sum sum |gp p|; ga = p (gp - dot).
+      / sqrt_d     gs, one rounding.
+      Q1 backward  grad_raw = inside1 ? (gs s1) / s1 : exactly 0; d s1 terms gs (r1 - t1) | gs (qc1 - o1) (the fast body's t1 is within an
+                   ulp below 1/4: 3 u on the term), d o1 terms -gs s1 outside.
+    Returns grad_raw, e_raw [rows, cols], terms / errs: the four [rows, cols] term arrays (d s1, d o1, d s2, d o2) and their error arrays,
+    and prod = gp p with e_dot per row.  NaN rows carry NaN through the same expressions (inside is false for a NaN index)."""
+    f = train_attn_probs(raw, mask, grid1, grid2, sqrt_d, n_sum, mutation)
+    s1, o1 = np.float64(F32(grid1[0])), np.float64(F32(grid1[1]))
+    s2, o2 = np.float64(F32(grid2[0])), np.float64(F32(grid2[1]))
+    g = np.asarray(grad_out, F32).astype(np.float64)
+    p, env, in1, in2 = f["p"], f["env"], f["in1"], f["in2"]
+    sd = np.float64(F32(sqrt_d))
+    with np.errstate(all="ignore"):
+        ts2 = np.where(in2, g * (f["r2"] - f["t2"]), g * (f["qc2"] - o2))
+        e_ts2 = np.where(in2, np.abs(g) * f["et"], 0.0) + U32 * np.abs(ts2) + np.where(f["undecided"], np.abs(g), 0.0)
+        to2 = np.where(in2, 0.0, -g * s2)
+        e_to2 = U32 * np.abs(to2)
+        gp = np.where(in2, g, 0.0)
+        prod = gp * p
+        dot = prod.sum(axis=1)
+        e_dot = (np.abs(prod) * (env + 4 * U32)).sum(axis=1) + _gamma(n_sum) * np.abs(prod).sum(axis=1)
+        diff = gp - dot[:, None]
+        e_diff = 3 * U32 * np.abs(gp) + e_dot[:, None] + U32 * np.abs(diff)
+        ga = p * diff
+        e_ga = p * e_diff + np.abs(ga) * (env + U32) + P_ABS * np.abs(diff)
+        gs = ga / sd
+        e_gs = e_ga / sd + U32 * np.abs(gs)
+        graw = np.where(in1, gs, 0.0)
+        e_raw = np.where(in1, e_gs + 3 * U32 * np.abs(gs), 0.0)
+        w1 = np.where(in1, f["r1"].astype(np.float64) - f["t1"].astype(np.float64), f["qc1"].astype(np.float64) - o1)
+        ts1 = gs * w1
+        e_ts1 = e_gs * np.abs(w1) + 3 * U32 * np.abs(ts1)
+        to1 = np.where(in1, 0.0, -gs * s1)
+        e_to1 = np.where(in1, 0.0, e_gs * s1 + U32 * np.abs(to1))
+    return dict(fwd=f, grad_raw=graw, e_raw=1.01 * e_raw, terms=(ts1, to1, ts2, to2), errs=tuple(1.01 * v for v in (e_ts1, e_to1, e_ts2, e_to2)),
+                prod=prod, dot=dot, e_dot=1.01 * e_dot, p=p, gp=gp)
