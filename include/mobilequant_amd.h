@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -1098,6 +1098,54 @@ typedef struct mq_decode_cache_fork_args {
   const int32_t* parent; /* device [batch]: the fork table */
 } mq_decode_cache_fork_args;
 int mq_decode_cache_fork(const mq_decode_cache_fork_args* args, mq_stream_t stream);
+
+/* ---- beam search on the batched engine: the group's best candidates and the in-place cache re-order -------------- */
+#define MQ_BEAM_SCRATCH_BYTES 363008 /* MQ_LOGPROB_SCRATCH_BYTES + 8 rows x MQ_LOGPROB_MAX_TOP entries of 16 bytes */
+
+/* The best n_cand continuations of every group of beams, by the rule in csrc/mq_beam.hip's header.  Row r < rows (1 ..
+ * MQ_DECODE_MAX_BATCH) of RAW logits belongs to group g = group[r] iff 0 <= g < n_groups (device int32, range-checked before any
+ * address is formed; any other value makes the row a member of nothing: its logits and cum are never read).  Per member row the
+ * order (logit descending, ties by index ascending; NaN is -inf, -0 is +0) and the log-probabilities lp are mq_logprob_top's -- the
+ * same body, the same bits as its top_logprob[k] -- and the row's list is the first n_cand entries.  Candidate (r, k) scores
+ * s = cum[r] + lp: one fp32 addition, a NaN cum counting as -inf, -0 as +0, a NaN sum as -inf.  The group's order is s descending,
+ * ties by r ascending, then k ascending; for j < n_cand the j-th candidate goes to cand_score / cand_row / cand_token / cand_logprob
+ * [n_groups][n_cand] (s, r, the token id, lp), padded with -inf, -1, -1, -inf where the group has fewer.  row_lse [rows] gets
+ * m + logf(S) for member rows.  Every output bit of a group is a function of its member rows' logits, their cum, their relative
+ * order, n_cand and V only -- not of the other groups, the rows' indices beyond their order, logits_stride, or eager / replayed.
+ * Limits (MQ_EINVAL with a message, before any HIP call): V % 4 == 0, 4 <= V <= 2^20; logits_stride >= V and % 4 == 0; rows and
+ * n_groups 1 .. MQ_DECODE_MAX_BATCH; n_cand 1 .. MQ_LOGPROB_MAX_TOP; logits and scratch 16-byte aligned, the others 4-byte; scratch >=
+ * MQ_BEAM_SCRATCH_BYTES, owned by the call on `stream`.  Three launches (two while V <= 4096), static LDS, no host synchronisation, no
+ * launch attribute, no floating-point atomics: capturable without a warm-up. */
+typedef struct mq_beam_select_args {
+  const float* logits;
+  int64_t logits_stride;
+  int64_t V;
+  int rows;     /* 1 .. MQ_DECODE_MAX_BATCH */
+  int n_groups; /* 1 .. MQ_DECODE_MAX_BATCH */
+  int n_cand;   /* 1 .. MQ_LOGPROB_MAX_TOP */
+  const float* cum;     /* device [rows]: the beams' summed log-probabilities */
+  const int32_t* group; /* device [rows] */
+  float* cand_score;    /* [n_groups][n_cand] */
+  int32_t* cand_row;
+  int32_t* cand_token;
+  float* cand_logprob;
+  float* row_lse;       /* [rows] */
+  void* scratch;
+  int64_t scratch_bytes;
+} mq_beam_select_args;
+int mq_beam_select(const mq_beam_select_args* args, mq_stream_t stream);
+
+/* Re-order the slots of the caches in place: a SIMULTANEOUS assignment "slot d continues old slot parent[d]" over all slots (the
+ * rule: csrc/mq_decode_reorder.hip's header).  The argument block, the caches table, pos and parent are mq_decode_cache_fork's.  Slot
+ * d is a live destination iff p = parent[d] has 0 <= p < batch, p != d and 0 < pos[p] < cache_len; then for every cache c and head h
+ * bytes [0, pos[p] * head_dim) of caches[c][d][h] become those of caches[c][p][h] AS THEY WERE BEFORE THE CALL.  A source may itself be
+ * a live destination: swaps, cycles, chains (1 <- 2 <- 3) and fan-out from an overwritten slot are all served, with no second buffer
+ * (the grid has no dimension over slots: the thread that owns a 16-byte chunk of a (cache, head) loads it from every needed slot,
+ * then stores).  Nothing else is written, never pos; the identity writes nothing.  Every table entry is range-checked on the device
+ * before any address is formed from it: an entry outside [0, batch), an idle source and pos[p] == 0 are no-ops for that slot.  One
+ * captured launch serves any later table; no host synchronisation, no LDS, no launch attribute.  Limits and errors: those of
+ * mq_decode_cache_fork. */
+int mq_decode_cache_reorder(const mq_decode_cache_fork_args* args, mq_stream_t stream);
 
 /* ---- QMatMul as a module: quantized batched matmul of two activations ------------------------ */
 /* Replaces QMatMul.forward (mobilellm/quantization/qmodule.py:453-466): out = Qout(matmul(Q1(x1), Q2(x2))) -- two fake-quant passes

@@ -134,8 +134,15 @@ class MqDecodeCacheForkArgs(ctypes.Structure):
                 ("pos", c_void_p), ("parent", c_void_p)]
 
 
+class MqBeamSelectArgs(ctypes.Structure):
+    _fields_ = [("logits", c_void_p), ("logits_stride", c_int64), ("V", c_int64), ("rows", c_int), ("n_groups", c_int), ("n_cand", c_int),
+                ("cum", c_void_p), ("group", c_void_p), ("cand_score", c_void_p), ("cand_row", c_void_p), ("cand_token", c_void_p),
+                ("cand_logprob", c_void_p), ("row_lse", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_int64)]
+
+
 MQ_LOGPROB_MAX_TOP = 20
 MQ_LOGPROB_SCRATCH_BYTES = 360448
+MQ_BEAM_SCRATCH_BYTES = 363008
 
 
 class MqAttentionArgs(ctypes.Structure):
@@ -247,6 +254,8 @@ _SIGNATURES = {
     "mq_sample_history_count_ragged": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, _P]),
     "mq_logprob_top": (c_int, [POINTER(MqLogprobTopArgs), _P]),
     "mq_decode_cache_fork": (c_int, [POINTER(MqDecodeCacheForkArgs), _P]),
+    "mq_beam_select": (c_int, [POINTER(MqBeamSelectArgs), _P]),
+    "mq_decode_cache_reorder": (c_int, [POINTER(MqDecodeCacheForkArgs), _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

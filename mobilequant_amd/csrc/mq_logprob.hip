@@ -27,6 +27,7 @@
 // the row's index, its neighbours, logits_stride, the index form, or eager / replayed.  Maxima, counts and the key selection are
 // order-free (exact).
 //
+// The per-slice pass (lp_slice) and the fixed-order row sum (lp_row_stats) live in mq_logprob_slice.h, which mq_beam.hip shares.
 // THE KERNELS.  Launch 1 (logprob_slices_kernel, grid ns x rows, 256 threads): a workgroup reads its slice ONCE into registers (16
 // entries per thread), writes (m_s, S_s), its count of keys above t's key (l[t]: one uniform load) and its first n_top keys, found by
 // n_top rounds of a block arg-max over the thread-local best (the owner of a round's winner removes it and rescans its 16 keys; a DPP
@@ -53,30 +54,12 @@
 // logf(S) adds 2 u log S <= 2 u log V (1 <= S <= V); d_i is rounded once, u |l'_i - m| <= u |lp_i|; the final subtraction once, u |lp_i|:
 //     |lp^_i - lp_i| <= E_S + 2 u log V + 2 u |lp_i|
 // V = 2^20, |lp| = 34 (Gaussian logits of scale 3): 3.2e-6 + 1.7e-6 + 4.1e-6 = 9.0e-6.  tests/test_gpu_logprob.py evaluates the formula per entry.
-#include "mq_common.h"
+#include "mq_logprob_slice.h"
 
 #include <limits.h>
 
 namespace mq {
 namespace {
-
-constexpr int LP_THREADS = 256;
-constexpr int LP_WAVES = LP_THREADS / 64;
-constexpr int LP_SLICE = 4096;                       // entries per slice: 16 per thread, held in registers
-constexpr int LP_STEPS = LP_SLICE / (4 * LP_THREADS);
-constexpr int LP_MAX_SLICES = (1 << 20) / LP_SLICE;  // 256
-constexpr int LP_MAX_TOP = MQ_LOGPROB_MAX_TOP;
-constexpr unsigned long long LP_IDX_MASK = (1ull << 20) - 1;
-typedef unsigned long long u64;
-
-struct LpPart {
-  float m, s;                     // the slice's maximum and its sum of e_i
-  int c, pad;                     // keys of the slice above the chosen token's key
-};
-
-static_assert(MQ_LOGPROB_SCRATCH_BYTES == MQ_DECODE_MAX_BATCH * LP_MAX_SLICES * (sizeof(LpPart) + LP_MAX_TOP * sizeof(u64)),
-              "scratch holds every row's partials and candidate keys");
-static_assert(LP_STEPS == 4 && LP_WAVES == 4, "the order of the sum in the header is written for 4 steps and 4 waves");
 
 struct LpIndex {
   const int* pos;                 // (a)
@@ -100,14 +83,6 @@ struct LpArgs {
   u64* keys;                      // [rows][LP_MAX_SLICES][LP_MAX_TOP]
 };
 
-// reduction slots of one body (each reduction has its own: no barrier is needed between two of them)
-struct LpRed {
-  float f[2][LP_WAVES];
-  int i[LP_WAVES];
-  u64 k[2][LP_WAVES];
-  float sum;
-};
-
 // The record a row writes, as an element offset into [batch][record_len]; false: the row is idle or its index is outside the record.
 // Every table entry is range-checked before it addresses anything.  Workgroup-uniform.
 __device__ __forceinline__ bool lp_record(const LpIndex& x, int row, long long* rec) {
@@ -129,172 +104,14 @@ __device__ __forceinline__ bool lp_record(const LpIndex& x, int row, long long* 
   return true;
 }
 
-__device__ __forceinline__ float lp_norm(float l) { return l != l ? -__builtin_inff() : l + 0.f; }
-
-__device__ __forceinline__ u64 lp_key(float z, int i) {
-  const unsigned u = __float_as_uint(z);
-  const unsigned k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((u64)k << 20) | (LP_IDX_MASK - (u64)i);
-}
-__device__ __forceinline__ int lp_key_id(u64 key) { return (int)(LP_IDX_MASK - (key & LP_IDX_MASK)); }
-__device__ __forceinline__ float lp_key_value(u64 key) {
-  const unsigned k = (unsigned)(key >> 20);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-// step 3 of the rule
-__device__ __forceinline__ float lp_term(float l, float m) { return l == m ? 1.f : expf(l - m); }
-__device__ __forceinline__ float lp_of(float l, float m, float log_s) {
-  if (m == -__builtin_inff()) return m;
-  const float d = l == m ? 0.f : l - m;
-  return d - log_s;
-}
-
-// a barrier with none of this wave's LDS operations (the shuffles are LDS operations) in flight
-__device__ __forceinline__ void lp_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-__device__ __forceinline__ float lp_wave_sum(float a) {           // the xor butterfly of the header: every lane ends with the same bits
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a = a + __shfl_xor(a, o);
-  return a;
-}
-__device__ __forceinline__ float lp_wave_max(float a) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
-  return a;
-}
-__device__ __forceinline__ int lp_wave_sum_i(int a) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o);
-  return a;
-}
-// The key maximum of a wave (all 64 lanes active), wave-uniform: mq_common.h's DPP row reduction on the key's two dwords -- a shuffle is
-// an LDS round trip, and the n_top dependent rounds of a launch are nothing but this reduction and a barrier.  A maximum is exact in any order.
-template <int CTRL>
-__device__ __forceinline__ u64 lp_dpp_k(u64 v) {
-  const unsigned lo = (unsigned)dpp_mov_i<CTRL>((int)(unsigned)v), hi = (unsigned)dpp_mov_i<CTRL>((int)(unsigned)(v >> 32));
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 lp_readlane_k(u64 v, int l) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 lp_max_k(u64 a, u64 b) { return b > a ? b : a; }
-__device__ __forceinline__ u64 lp_wave_max_k(u64 a) {
-  a = lp_max_k(a, lp_dpp_k<0xB1>(a));                                // quad_perm [1,0,3,2]
-  a = lp_max_k(a, lp_dpp_k<0x4E>(a));                                // quad_perm [2,3,0,1]
-  a = lp_max_k(a, lp_dpp_k<0x141>(a));                               // row_half_mirror
-  a = lp_max_k(a, lp_dpp_k<0x140>(a));                               // row_mirror: every lane = its row-of-16 maximum
-  return lp_max_k(lp_max_k(lp_readlane_k(a, 15), lp_readlane_k(a, 31)), lp_max_k(lp_readlane_k(a, 47), lp_readlane_k(a, 63)));
-}
-
-// One slice of a live row: (m_s, S_s), the count of keys above the chosen token's and the slice's first n_top keys in order (0: none
-// left), written by thread 0 through o_part / o_keys (scratch, or LDS in the one-launch form).
-__device__ __forceinline__ void lp_slice(const float* __restrict__ row, int V, int s, long long t, int n_top, LpPart* o_part, u64* o_keys, LpRed& R) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lo = s * LP_SLICE, hi = min(V, lo + LP_SLICE);
-  const float NEG_INF = -__builtin_inff();
-  float x[4 * LP_STEPS];
-  bool in[LP_STEPS];
-#pragma unroll
-  for (int k = 0; k < LP_STEPS; ++k) {
-    const int i = lo + 4 * LP_THREADS * k + 4 * tid;
-    in[k] = i < hi;                                                  // (lo, hi and i are multiples of 4: i < hi covers i + 3)
-    const float4 l = in[k] ? *reinterpret_cast<const float4*>(row + i) : make_float4(NEG_INF, NEG_INF, NEG_INF, NEG_INF);
-    x[4 * k] = lp_norm(l.x); x[4 * k + 1] = lp_norm(l.y); x[4 * k + 2] = lp_norm(l.z); x[4 * k + 3] = lp_norm(l.w);
-  }
-  const bool have_t = t >= 0 && t < (long long)V;
-  const u64 kt = have_t ? lp_key(lp_norm(row[t]), (int)t) : ~0ull;   // uniform load, behind the range check
-
-  float mx = NEG_INF;
-#pragma unroll
-  for (int j = 0; j < 4 * LP_STEPS; ++j) mx = fmaxf(mx, x[j]);
-  mx = lp_wave_max(mx);
-  if (lane == 0) R.f[0][wave] = mx;
-  lp_sync();
-  const float ms = fmaxf(fmaxf(R.f[0][0], R.f[0][1]), fmaxf(R.f[0][2], R.f[0][3]));
-
-  float a = 0.f;
-  int c = 0;
-  u64 key[4 * LP_STEPS];
-  u64 best = 0;
-#pragma unroll
-  for (int k = 0; k < LP_STEPS; ++k)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int j = 4 * k + e;
-      if (ms != NEG_INF) a = a + lp_term(x[j], ms);
-      key[j] = in[k] ? lp_key(x[j], lo + 4 * LP_THREADS * k + 4 * tid + e) : 0ull;          // (a key of an entry is never 0)
-      c += key[j] > kt ? 1 : 0;
-      best = key[j] > best ? key[j] : best;
-    }
-  a = lp_wave_sum(a);
-  c = lp_wave_sum_i(c);
-  if (lane == 0) { R.f[1][wave] = a; R.i[wave] = c; }
-  lp_sync();
-  if (tid == 0) {
-    LpPart p;
-    p.m = ms;
-    p.s = ((R.f[1][0] + R.f[1][1]) + R.f[1][2]) + R.f[1][3];
-    p.c = (R.i[0] + R.i[1]) + (R.i[2] + R.i[3]);
-    p.pad = 0;
-    *o_part = p;
-  }
-
-  // the first n_top keys: per round the block's best key; its owner drops it and rescans its 16
-  for (int r = 0; r < n_top; ++r) {
-    const u64 wb = lp_wave_max_k(best);
-    if (lane == 0) R.k[r & 1][wave] = wb;
-    lp_sync();                                                       // (double-buffered: round r + 2 writes after round r + 1's barrier)
-    u64 g = R.k[r & 1][0];
-#pragma unroll
-    for (int w = 1; w < LP_WAVES; ++w) g = R.k[r & 1][w] > g ? R.k[r & 1][w] : g;
-    if (tid == 0) o_keys[r] = g;
-    if (g != 0ull && best == g) {                                    // keys are distinct: one owner
-      best = 0;
-#pragma unroll
-      for (int j = 0; j < 4 * LP_STEPS; ++j) {
-        if (key[j] == g) key[j] = 0ull;
-        best = key[j] > best ? key[j] : best;
-      }
-    }
-  }
-}
-
 // The row's record from its ns partials and candidate lists (both in LDS).
 __device__ __forceinline__ void lp_finish(const float* __restrict__ row, int V, int ns, long long t, int n_top, const LpPart* part, const u64* cand,
                                           long long rec, const LpArgs& a, LpRed& R) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float NEG_INF = -__builtin_inff();
-  float mx = tid < ns ? part[tid].m : NEG_INF;
-  int c = tid < ns ? part[tid].c : 0;
-  mx = lp_wave_max(mx);
-  c = lp_wave_sum_i(c);
-  if (lane == 0) { R.f[0][wave] = mx; R.i[wave] = c; }
-  lp_sync();
-  const float m = fmaxf(fmaxf(R.f[0][0], R.f[0][1]), fmaxf(R.f[0][2], R.f[0][3]));
-  const int in_front = (R.i[0] + R.i[1]) + (R.i[2] + R.i[3]);
-  if (wave == 0) {
-    float b = 0.f;
-    if (m != NEG_INF) {
-#pragma unroll
-      for (int q = 0; q < LP_MAX_SLICES / 64; ++q) {
-        const int s = lane + 64 * q;
-        if (s < ns && part[s].m != NEG_INF) {
-          const float f = lp_term(part[s].m, m);
-          const float w = part[s].s * f;
-          b = b + w;
-        }
-      }
-    }
-    b = lp_wave_sum(b);
-    if (lane == 0) R.sum = b;
-  }
-  lp_sync();
-  const float log_s = m != NEG_INF ? logf(R.sum) : 0.f;
+  float m, log_s;
+  int in_front;
+  lp_row_stats(part, ns, R, &m, &log_s, &in_front);                  // (the fixed-order sum: mq_logprob_slice.h)
 
   if (tid == 0) {
     const bool have_t = t >= 0 && t < (long long)V;

@@ -24,11 +24,17 @@ returns, token for token, the ids of ``generate(sampling=...)``.
 Forks: ``fork({src: [dst, ...]})`` makes one slot's cached sequence the start of others -- ONE ``mq_decode_cache_fork``
 launch (csrc/mq_decode_fork.hip) copies the live cache bytes of all sources, in all layers, to all destinations -- and
 ``generate(..., n=k)`` / ``generate_speculative(..., n=k)`` draw k samples of every prompt from ONE prefill of it.
+
+Beam search: ``generate_beam(prompts, max_new_tokens, num_beams)`` keeps W beams of every prompt in W neighbouring
+slots.  Per step ONE ``mq_beam_select`` (csrc/mq_beam.hip) picks every prompt's best K continuations from the logits rows on the
+device, the host reads n_groups x K records and runs the hypothesis bookkeeping, and ONE ``mq_decode_cache_reorder``
+(csrc/mq_decode_reorder.hip) makes "slot d continues old slot parent[d]" true for all slots at once, in place, before the ordinary
+``step()``.  A prompt's result is a function of the prompt and the arguments only.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Mapping, Optional, Sequence
+from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -39,6 +45,32 @@ from .sampling import (RaggedRowsLaunch, SampleLaunch, SamplingParams, TokenLogp
                        validate_generate_args)
 
 MAX_BATCH = 8
+
+
+class BeamResult(NamedTuple):
+    """generate_beam's return for one prompt, best hypothesis first."""
+    sequences: List[List[int]]           # context + new tokens, an ending EOS included
+    scores: List[float]                  # sum_logprob / L ** length_penalty, L the hypothesis' new tokens
+    sum_logprobs: List[float]            # the fp32 sums of the tokens' log-probabilities
+
+
+class _BeamHyps:
+    """A prompt's finished hypotheses: the best W by score; adding drops the worst, and on equal scores the earlier entry stays."""
+
+    def __init__(self, width: int):
+        self.width, self.items, self.added = width, [], 0
+
+    def add(self, ids: List[int], sum_logprob: float, score: float):
+        self.items.append((score, self.added, ids, sum_logprob))
+        self.added += 1
+        self.items.sort(key=lambda e: (-e[0], e[1]))               # score descending, earlier-added first
+        del self.items[self.width:]
+
+    def full(self) -> bool:
+        return len(self.items) >= self.width
+
+    def worst(self) -> float:
+        return self.items[-1][0]
 
 
 def _count(n: int, fan: int) -> str:
@@ -166,6 +198,8 @@ class BatchDecodeEngine(_DecodeBase):
         self._fork_table = ops.decode_cache_table(self._fork_caches)     # fork(): built once, the caches are never reallocated
         self._fork_parent = torch.arange(B, dtype=torch.int32, device=dev)
         self.fork_stats = None               # what the last fork() did
+        self._beam = None                    # generate_beam's device buffers, allocated on first use
+        self.beam_stats = None               # what the last generate_beam() did
         self._lower()
 
     def _lower(self):
@@ -777,6 +811,189 @@ class BatchDecodeEngine(_DecodeBase):
             if live:
                 self.step()
         return outs
+
+    # -- beam search (csrc/mq_beam.hip, csrc/mq_decode_reorder.hip) -----------------------------------------------
+    def _beam_buffers(self, G: int, K: int):
+        """generate_beam's device buffers: `pack` (ONE host -> device copy per step: tok int64 [B], then parent, group int32 [B] and cum
+        fp32 [B]) and `rec` (ONE read-back per step: score, row, token, logprob [G][K], then row_lse [B]); both int32, viewed."""
+        B = self.batch
+        if self._beam is None:
+            pack = torch.zeros(5 * B, dtype=torch.int32, device=self.dev)
+            self._beam = {"pack": pack, "tok": pack[:2 * B].view(torch.int64), "parent": pack[2 * B:3 * B], "group": pack[3 * B:4 * B],
+                          "cum": pack[4 * B:].view(torch.float32), "rec": torch.zeros(4 * MAX_BATCH * _lib.MQ_LOGPROB_MAX_TOP + B, dtype=torch.int32, device=self.dev),
+                          "scratch": torch.empty(_lib.MQ_BEAM_SCRATCH_BYTES, dtype=torch.uint8, device=self.dev)}
+        b, n = self._beam, G * K
+        rec = b["rec"]
+        b["out"] = (rec[:n].view(torch.float32).view(G, K), rec[n:2 * n].view(G, K), rec[2 * n:3 * n].view(G, K),
+                    rec[3 * n:4 * n].view(torch.float32).view(G, K), rec[4 * n:4 * n + B].view(torch.float32))
+        return b
+
+    def _beam_upload(self, tok, parent, group, cum):
+        B = self.batch
+        h = np.zeros(5 * B, dtype=np.int32)
+        h[:2 * B].view(np.int64)[:] = tok
+        h[2 * B:3 * B], h[3 * B:4 * B] = parent, group
+        h[4 * B:].view(np.float32)[:] = cum
+        self._beam["pack"].copy_(torch.from_numpy(h), non_blocking=False)
+
+    @torch.no_grad()
+    def generate_beam(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, num_beams: int, *, eos_token_id=None,
+                      length_penalty: float = 1.0, early_stopping: bool = True, num_return_sequences: int = 1) -> List[BeamResult]:
+        """Beam search for up to batch // num_beams prompts at once (DESIGN.md 4.3l): W = num_beams beams per prompt, prompt g's in
+        slots g W .. g W + W - 1.  Returns one BeamResult per prompt: the best num_return_sequences hypotheses (sequences: context +
+        new tokens, an ending EOS included; scores; sum_logprobs), best first.  No sampling and no penalties are involved: the sampler
+        histories and the logprobs= records stay untouched.  Each prompt is encoded ONCE (slot g W); then per step: mq_beam_select over
+        self.logits (K = max(2, 1 + |eos|) W candidates per prompt), one read-back of the n_groups x K records, the host rule, one
+        packed upload of parent / token / cum, mq_decode_cache_reorder (skipped when the table is the identity), the per-slot state
+        from a gathered temporary, and the ordinary step() (a graph replay after capture()).  A finished prompt's slots are released
+        and the others go on.  self.beam_stats = {"steps", "selects", "reorders", "positions", "bytes"} (step() calls, select and
+        re-order launches, cached positions moved, cache bytes written).
+        THE HOST RULE (after transformers' BeamSearchScorer).  L = the new tokens of a hypothesis once the current token is appended.
+        The K candidates are walked in order: an EOS at j >= W is skipped; an EOS at j < W adds (ids of the row + EOS, s) to the
+        prompt's finished list with score s / L ** length_penalty; any other candidate becomes the next beam (row, token, s) until W
+        are taken.  The finished list keeps the best W: adding drops the worst, and on equal scores the earlier entry stays.  After
+        the walk the prompt is done iff it has W finished hypotheses and early_stopping is true or the worst finished score is >=
+        cand_score[0] / L ** length_penalty.  At max_new_tokens every live beam of a prompt that is not done is added in beam order
+        with cum / L ** length_penalty.  Returned: score descending, earlier-added first on ties.  Scores are Python floats (the
+        fp32 sum divided in double precision).
+        CONTRACT.  Prompt g's result is a function of the prompt and the arguments only: bit for bit the same alone or beside other
+        prompts, in any group position, captured or eager.
+        ValueError / IndexError with "BatchDecodeEngine.generate_beam: " in front, before anything is launched: num_beams outside
+        1 .. 8, no prompt or len(prompts) * num_beams > batch, an empty prompt, a token outside the vocabulary (IndexError),
+        max_new_tokens < 1, num_return_sequences outside 1 .. num_beams, K > 20 or above the vocabulary, a prompt plus max_new_tokens
+        past the cache, a length_penalty that is not a finite number, an early_stopping that is not a bool."""
+        who = "BatchDecodeEngine.generate_beam: "
+
+        def integer(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if not integer(num_beams) or not 1 <= num_beams <= MAX_BATCH:
+            raise ValueError(who + f"num_beams={num_beams!r} must be an integer in 1..{MAX_BATCH}")
+        W = int(num_beams)
+        try:
+            prompts = [[int(t) for t in p] for p in prompts]
+        except (TypeError, ValueError):
+            raise ValueError(who + "prompts must be a sequence of token id sequences") from None
+        G = len(prompts)
+        if G < 1 or G * W > self.batch:
+            raise ValueError(who + f"{G} prompts x num_beams={W} for {self.batch} slots")
+        for g, p in enumerate(prompts):
+            if not p:
+                raise ValueError(who + f"prompt {g} is empty")
+            for t in p:
+                if not 0 <= t < self.shape.vocab:
+                    raise IndexError(who + f"token {t} of prompt {g} outside the vocabulary (0..{self.shape.vocab - 1})")
+        if not integer(max_new_tokens) or max_new_tokens < 1:
+            raise ValueError(who + f"max_new_tokens={max_new_tokens!r} must be an integer >= 1")
+        T = int(max_new_tokens)
+        if not integer(num_return_sequences) or not 1 <= num_return_sequences <= W:
+            raise ValueError(who + f"num_return_sequences={num_return_sequences!r} must be an integer in 1..num_beams ({W})")
+        if not (eos_token_id is None or integer(eos_token_id) or (isinstance(eos_token_id, (list, tuple, set, frozenset)) and all(integer(t) for t in eos_token_id))):
+            raise ValueError(who + f"eos_token_id={eos_token_id!r} must be None, a token id or a collection of token ids")
+        eos = {int(t) for t in _eos_set(int(eos_token_id) if integer(eos_token_id) else eos_token_id)}
+        K = max(2, 1 + len(eos)) * W
+        if K > _lib.MQ_LOGPROB_MAX_TOP:
+            raise ValueError(who + f"max(2, 1 + {len(eos)} EOS ids) x num_beams={W} = {K} candidates per step, above {_lib.MQ_LOGPROB_MAX_TOP}")
+        if K > self.shape.vocab:
+            raise ValueError(who + f"{K} candidates per step, above the vocabulary ({self.shape.vocab})")
+        if any(len(p) + T > self.cache_len for p in prompts):
+            raise ValueError(who + f"a prompt plus {T} new tokens exceeds the cache ({self.cache_len} positions)")
+        if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float, np.integer, np.floating)) or not np.isfinite(length_penalty):
+            raise ValueError(who + f"length_penalty={length_penalty!r} must be a finite number")
+        if not isinstance(early_stopping, (bool, np.bool_)):
+            raise ValueError(who + f"early_stopping={early_stopping!r} must be True or False")
+        lp_exp = float(length_penalty)
+
+        # every prompt encoded once, in its group's first slot (generate's own start: one-token prompts through the step kernels)
+        B = self.batch
+        for b in range(B):
+            self.release(b)
+        first = [g * W for g in range(G)]
+        short = [g for g in range(G) if len(prompts[g]) == 1]
+        if short:
+            for g in short:
+                self.start(first[g])
+            toks = [0] * B
+            for g in short:
+                toks[first[g]] = prompts[g][0]
+            self.step(toks)
+        for g in range(G):
+            if len(prompts[g]) > 1:
+                self.prefill(first[g], prompts[g])
+        self._rows_at = None
+
+        buf = self._beam_buffers(G, K)
+        s = self.shape
+        pos_bytes = s.head_dim * s.kv_heads * len(self._fork_caches)
+        stats = self.beam_stats = {"steps": 0, "selects": 0, "reorders": 0, "positions": 0, "bytes": 0}
+        beams = [[([], np.float32(0.0))] for _ in range(G)]        # per prompt: (new ids, cum) of the live beams, beam b in slot g W + b
+        hyps = [_BeamHyps(W) for _ in range(G)]
+        live = list(range(G))
+        group = [-1] * B
+        cum = [0.0] * B
+        for g in live:
+            group[first[g]] = g
+        self._beam_upload([0] * B, list(range(B)), group, cum)
+        for step in range(T):
+            L = step + 1
+            norm = float(L) ** lp_exp
+            ops.beam_select(self.logits, buf["cum"], buf["group"], G, K, out=buf["out"], scratch=buf["scratch"])
+            stats["selects"] += 1
+            rec = buf["rec"][:4 * G * K].cpu().numpy()             # ONE read-back: the n_groups x K records
+            score, row = rec[:G * K].view(np.float32).reshape(G, K), rec[G * K:2 * G * K].reshape(G, K)
+            token, parent = rec[2 * G * K:3 * G * K].reshape(G, K), list(range(B))
+            tok = [0] * B
+            for g in list(live):
+                nxt = []
+                for j in range(K):
+                    r, t, sc = int(row[g, j]), int(token[g, j]), score[g, j]
+                    if r < 0:
+                        break                                      # (padding: the group has no more candidates)
+                    ids = beams[g][r - first[g]][0]
+                    if t in eos:
+                        if j < W:
+                            hyps[g].add(ids + [t], float(sc), float(sc) / norm)
+                        continue
+                    nxt.append((r, t, sc))
+                    if len(nxt) == W:
+                        break
+                done = hyps[g].full() and (bool(early_stopping) or hyps[g].worst() >= float(score[g, 0]) / norm)
+                if not done and len(nxt) < W:
+                    raise RuntimeError(who + f"prompt {g} has {len(nxt)} continuations for {W} beams at step {step}")
+                if not done and L == T:                            # the end: the live beams, in beam order
+                    for r, t, sc in nxt:
+                        hyps[g].add(beams[g][r - first[g]][0] + [t], float(sc), float(sc) / norm)
+                    done = True
+                if done:
+                    live.remove(g)
+                    for b in range(first[g], first[g] + W):
+                        self.release(b)
+                        group[b] = -1
+                    continue
+                beams[g] = [(beams[g][r - first[g]][0] + [t], sc) for r, t, sc in nxt]
+                for b, (r, t, sc) in enumerate(nxt):
+                    d = first[g] + b
+                    parent[d], tok[d], group[d], cum[d] = r, t, g, float(sc)
+            if not live:
+                break
+            self._beam_upload(tok, parent, group, cum)
+            moved = sum(self._host_pos[p] for d, p in enumerate(parent) if p != d)
+            if moved:                                              # (the identity writes nothing: no launch)
+                ops.decode_cache_reorder(self._fork_caches, self.pos, buf["parent"], table=self._fork_table)
+                stats["reorders"] += 1
+                stats["positions"] += moved
+                stats["bytes"] += moved * pos_bytes
+                self.pos.copy_(self.pos.index_select(0, buf["parent"]))      # (behind the launch, which reads the old positions)
+                hp, act = list(self._host_pos), list(self._active)
+                for d, p in enumerate(parent):
+                    self._host_pos[d], self._active[d] = hp[p], act[p]
+            self.tok.copy_(buf["tok"])
+            self.step()
+            stats["steps"] += 1
+        out = []
+        for g in range(G):
+            best = hyps[g].items[:int(num_return_sequences)]
+            out.append(BeamResult([prompts[g] + ids for _, _, ids, _ in best], [sc for sc, _, _, _ in best], [sl for _, _, _, sl in best]))
+        return out
 
     def _check_drafts(self, who: str, draft, num_draft, n: int, fan: int = 1) -> list:
         """The drafts of a batched speculative generation, one per prompt: a callable (for every prompt) or a sequence of n callables."""

@@ -532,6 +532,46 @@ def decode_cache_table(caches) -> torch.Tensor:
     return torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64).to(caches[0].device)
 
 
+def _cache_slots_call(who: str, caches, pos: torch.Tensor, parent: torch.Tensor, table: Optional[torch.Tensor]) -> None:
+    """The argument checks and the call of decode_cache_fork / decode_cache_reorder (who: the operation's name; one argument block)."""
+    caches = list(caches)
+    if not caches:
+        raise ValueError(f"mobilequant_amd: {who} needs at least one cache")
+    c0 = caches[0]
+    if not isinstance(c0, torch.Tensor) or c0.dim() != 4:
+        raise ValueError(f"mobilequant_amd: {who}: a cache is a tensor [batch, kv_heads, cache_len, head_dim], got {getattr(c0, 'shape', type(c0))}")
+    for t in caches:                                               # (what a cache is, then where it lives: a CPU tensor is refused last)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int8:
+            raise RuntimeError(f"mobilequant_amd: {who}: caches are int8 tensors, got {getattr(t, 'dtype', type(t))}")
+        if t.shape != c0.shape:
+            raise ValueError(f"mobilequant_amd: {who}: caches of different shapes ({tuple(c0.shape)} vs {tuple(t.shape)})")
+        if not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: {who}: a cache is not contiguous")
+    B, H, L, D = (int(v) for v in c0.shape)
+    for t, what in ((pos, "pos"), (parent, "parent")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: {who}: {what} must be a contiguous int32 [{B}] tensor, got "
+                               f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if D % 16 or not 16 <= D <= 256:
+        raise ValueError(f"mobilequant_amd: {who}: head_dim={D} must be a multiple of 16 in [16, 256]")
+    if not 1 <= B <= 8 or not 1 <= len(caches) <= 1024 or H < 1 or L < 1:
+        raise ValueError(f"mobilequant_amd: {who}: {len(caches)} caches of shape {tuple(c0.shape)} outside the launch's limits "
+                         "(1 .. 1024 caches, batch 1 .. 8, no empty dimension)")
+    for t in caches + [pos, parent]:
+        _dev(t, f"{who}: every cache, pos and parent")
+    if any(t.data_ptr() % 16 for t in caches):
+        raise RuntimeError(f"mobilequant_amd: {who}: a cache is not 16-byte aligned")
+    if table is None:
+        table = decode_cache_table(caches)
+    else:
+        _dev(table, f"{who}: table")
+        if table.dtype != torch.int64 or tuple(table.shape) != (len(caches),) or not table.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: {who}: table must be a contiguous int64 [{len(caches)}] tensor of the caches' base pointers")
+    a = _lib.MqDecodeCacheForkArgs(table.data_ptr(), len(caches), B, H, L, D, pos.data_ptr(), parent.data_ptr())
+    with _on(c0, *caches[1:], pos, parent, table):
+        _lib.call("mq_" + who, ctypes.byref(a), _stream())
+
+
 def decode_cache_fork(caches, pos: torch.Tensor, parent: torch.Tensor, table: Optional[torch.Tensor] = None) -> None:
     """mq_decode_cache_fork on the current stream (csrc/mq_decode_fork.hip): ONE launch copies the live part of every
     source slot of `caches` -- a list of int8 device tensors [batch, kv_heads, cache_len, head_dim], all of one shape, contiguous, on one
@@ -539,42 +579,68 @@ def decode_cache_fork(caches, pos: torch.Tensor, parent: torch.Tensor, table: Op
     iff parent[s] == s; slot d with p = parent[d] != d takes bytes [0, pos[p] * head_dim) of every head of every cache from slot p iff
     p is in range, parent[p] == p and 0 <= pos[p] < cache_len; nothing else is written.  table: decode_cache_table(caches), prebuilt
     (otherwise it is built here: one host -> device copy).  RuntimeError / ValueError on any violation, before the C call."""
-    caches = list(caches)
-    if not caches:
-        raise ValueError("mobilequant_amd: decode_cache_fork needs at least one cache")
-    c0 = caches[0]
-    if not isinstance(c0, torch.Tensor) or c0.dim() != 4:
-        raise ValueError(f"mobilequant_amd: decode_cache_fork: a cache is a tensor [batch, kv_heads, cache_len, head_dim], got {getattr(c0, 'shape', type(c0))}")
-    for t in caches:                                               # (what a cache is, then where it lives: a CPU tensor is refused last)
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int8:
-            raise RuntimeError(f"mobilequant_amd: decode_cache_fork: caches are int8 tensors, got {getattr(t, 'dtype', type(t))}")
-        if t.shape != c0.shape:
-            raise ValueError(f"mobilequant_amd: decode_cache_fork: caches of different shapes ({tuple(c0.shape)} vs {tuple(t.shape)})")
-        if not t.is_contiguous():
-            raise RuntimeError("mobilequant_amd: decode_cache_fork: a cache is not contiguous")
-    B, H, L, D = (int(v) for v in c0.shape)
-    for t, what in ((pos, "pos"), (parent, "parent")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: decode_cache_fork: {what} must be a contiguous int32 [{B}] tensor, got "
-                               f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    if D % 16 or not 16 <= D <= 256:
-        raise ValueError(f"mobilequant_amd: decode_cache_fork: head_dim={D} must be a multiple of 16 in [16, 256]")
-    if not 1 <= B <= 8 or not 1 <= len(caches) <= 1024 or H < 1 or L < 1:
-        raise ValueError(f"mobilequant_amd: decode_cache_fork: {len(caches)} caches of shape {tuple(c0.shape)} outside the launch's limits "
-                         "(1 .. 1024 caches, batch 1 .. 8, no empty dimension)")
-    for t in caches + [pos, parent]:
-        _dev(t, "decode_cache_fork: every cache, pos and parent")
-    if any(t.data_ptr() % 16 for t in caches):
-        raise RuntimeError("mobilequant_amd: decode_cache_fork: a cache is not 16-byte aligned")
-    if table is None:
-        table = decode_cache_table(caches)
+    _cache_slots_call("decode_cache_fork", caches, pos, parent, table)
+
+
+def decode_cache_reorder(caches, pos: torch.Tensor, parent: torch.Tensor, table: Optional[torch.Tensor] = None) -> None:
+    """mq_decode_cache_reorder on the current stream (csrc/mq_decode_reorder.hip): ONE launch assigns "slot d continues
+    old slot parent[d]" for all slots of `caches` AT ONCE, in place -- decode_cache_fork's arguments (caches, pos, parent, table), but a
+    source may itself be a destination: swaps, cycles, chains and fan-out from an overwritten slot.  Slot d with p = parent[d] takes
+    bytes [0, pos[p] * head_dim) of every head of every cache from slot p, as they were before the call, iff p is in range, p != d and
+    0 < pos[p] < cache_len; nothing else is written (the identity writes nothing).  RuntimeError / ValueError on any violation, before
+    the C call."""
+    _cache_slots_call("decode_cache_reorder", caches, pos, parent, table)
+
+
+def beam_select(logits: torch.Tensor, cum: torch.Tensor, group: torch.Tensor, n_groups: int, n_cand: int, out=None, scratch: Optional[torch.Tensor] = None):
+    """mq_beam_select on the current stream (csrc/mq_beam.hip): logits [rows, V] fp32 (row stride >= V; the RAW rows),
+    cum [rows] fp32 and group [rows] int32 device tensors, n_groups in 1 .. 8, n_cand in 1 .. 20.  Returns device tensors (cand_score
+    [n_groups, n_cand] fp32, cand_row int32, cand_token int32, cand_logprob fp32, row_lse [rows] fp32): per group the first n_cand
+    (row, token) pairs by cum[row] + log-softmax(row)[token] descending, ties by row, then by the row's own order; -inf / -1 / -1 /
+    -inf where a group has fewer.  A row whose group entry is outside [0, n_groups) is a member of nothing and is never read; row_lse
+    is written for member rows only.  out: the five tensors of an earlier call, written in place (a captured launch); scratch: uint8
+    [>= MQ_BEAM_SCRATCH_BYTES], owned by the call."""
+    _dev(logits, "beam_select logits")
+    if logits.dim() == 1:
+        logits = logits.view(1, -1)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise RuntimeError("mobilequant_amd: beam_select logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    if not 1 <= rows <= 8:
+        raise RuntimeError(f"mobilequant_amd: beam_select rows={rows} outside 1..8")
+    for v, hi, what in ((n_groups, 8, "n_groups"), (n_cand, _lib.MQ_LOGPROB_MAX_TOP, "n_cand")):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError(f"mobilequant_amd: beam_select {what}={v!r} must be an int in 1..{hi}")
+    for t, dt, what in ((cum, torch.float32, "cum"), (group, torch.int32, "group")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (rows,) or not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: beam_select {what} must be a contiguous {dt} [{rows}] tensor")
+        _dev(t, "beam_select " + what)
+    dev = logits.device
+    if out is None:
+        out = (torch.empty(n_groups, n_cand, dtype=torch.float32, device=dev), torch.empty(n_groups, n_cand, dtype=torch.int32, device=dev),
+               torch.empty(n_groups, n_cand, dtype=torch.int32, device=dev), torch.empty(n_groups, n_cand, dtype=torch.float32, device=dev),
+               torch.empty(rows, dtype=torch.float32, device=dev))
     else:
-        _dev(table, "decode_cache_fork: table")
-        if table.dtype != torch.int64 or tuple(table.shape) != (len(caches),) or not table.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: decode_cache_fork: table must be a contiguous int64 [{len(caches)}] tensor of the caches' base pointers")
-    a = _lib.MqDecodeCacheForkArgs(table.data_ptr(), len(caches), B, H, L, D, pos.data_ptr(), parent.data_ptr())
-    with _on(c0, *caches[1:], pos, parent, table):
-        _lib.call("mq_decode_cache_fork", ctypes.byref(a), _stream())
+        out = tuple(out)
+        want = [(torch.float32, (n_groups, n_cand)), (torch.int32, (n_groups, n_cand)), (torch.int32, (n_groups, n_cand)),
+                (torch.float32, (n_groups, n_cand)), (torch.float32, (rows,))]
+        if len(out) != 5 or any(not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev
+                                for t, (dt, sh) in zip(out, want)):
+            raise RuntimeError(f"mobilequant_amd: beam_select out must be the five contiguous tensors of a call with n_groups={n_groups}, n_cand={n_cand}, rows={rows}")
+    if scratch is None:
+        scratch = torch.empty(_lib.MQ_BEAM_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+    elif not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.numel() < _lib.MQ_BEAM_SCRATCH_BYTES or not scratch.is_contiguous() \
+            or scratch.device != dev:
+        raise RuntimeError(f"mobilequant_amd: beam_select scratch must be a contiguous uint8 device tensor of >= {_lib.MQ_BEAM_SCRATCH_BYTES} bytes")
+    a = _lib.MqBeamSelectArgs()
+    a.logits, a.logits_stride, a.V = logits.data_ptr(), logits.stride(0) if rows > 1 else max(V, logits.stride(0)), V
+    a.rows, a.n_groups, a.n_cand = rows, n_groups, n_cand
+    a.cum, a.group = cum.data_ptr(), group.data_ptr()
+    a.cand_score, a.cand_row, a.cand_token, a.cand_logprob, a.row_lse = (t.data_ptr() for t in out)
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+    with _on(logits, cum, group, *out):
+        _lib.call("mq_beam_select", ctypes.byref(a), _stream())
+    return out
 
 
 def int8_linear_segmented(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: torch.Tensor, alpha: torch.Tensor, w_zp: torch.Tensor,

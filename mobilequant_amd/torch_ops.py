@@ -21,6 +21,8 @@ Operators (reference code each one replaces):
     pack_w4(nibbles) -> uint8                                                       the 4-bit image of a quantised weight
     w4a8_linear(xq, row_sum, w_packed, ...) -> Tensor                               the same linear on packed 4-bit weights
     decode_cache_fork(caches, pos, parent) -> ()                                    (no reference code: DESIGN.md 4.3k; caches in place)
+    decode_cache_reorder(caches, pos, parent) -> ()                                 (no reference code: DESIGN.md 4.3l; caches in place)
+    beam_select(logits, cum, group, n_groups, n_cand) -> (score, row, token, logprob, row_lse)   (no reference code: DESIGN.md 4.3l)
 """
 from __future__ import annotations
 
@@ -147,4 +149,28 @@ def _(caches, pos, parent):
     return None
 
 
-OPS = ("fake_quant", "quantize", "minmax", "minmax_update_", "hist_minmax_update_", "w8a8_linear", "pack_w4", "w4a8_linear", "decode_cache_fork")
+@torch.library.custom_op(f"{_NS}::decode_cache_reorder", mutates_args=("caches",), device_types="cuda")
+def decode_cache_reorder(caches: List[torch.Tensor], pos: torch.Tensor, parent: torch.Tensor) -> None:
+    ops.decode_cache_reorder(caches, pos, parent)
+
+
+@decode_cache_reorder.register_fake
+def _(caches, pos, parent):
+    return None
+
+
+@torch.library.custom_op(f"{_NS}::beam_select", mutates_args=(), device_types="cuda")
+def beam_select(logits: torch.Tensor, cum: torch.Tensor, group: torch.Tensor, n_groups: int,
+                n_cand: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.beam_select(logits, cum, group, n_groups, n_cand)
+
+
+@beam_select.register_fake
+def _(logits, cum, group, n_groups, n_cand):
+    rows = logits.shape[0] if logits.dim() == 2 else 1
+    f, i = (lambda *sh: logits.new_empty(sh, dtype=torch.float32)), (lambda *sh: logits.new_empty(sh, dtype=torch.int32))
+    return f(n_groups, n_cand), i(n_groups, n_cand), i(n_groups, n_cand), f(n_groups, n_cand), f(rows)
+
+
+OPS = ("fake_quant", "quantize", "minmax", "minmax_update_", "hist_minmax_update_", "w8a8_linear", "pack_w4", "w4a8_linear", "decode_cache_fork", "decode_cache_reorder",
+       "beam_select")
