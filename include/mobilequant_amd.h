@@ -236,7 +236,16 @@ int mq_w8a8_linear_tiled(const int8_t* a_tiled, const int8_t* w, int64_t M, int6
  * a_gsum [G, M]: per-group sums of the stored activations; alpha [G, N] = s_a s_w; cw [G, N] = w_shift - o_w; t [G, N] =
  * c_a W_g + group_size c_a cw with c_a = a_shift - z_a and W_g the per-group sums of the stored weights (all exact integers: the
  * bracket is the reference's sum of (ia - z_a)(iw - o_w) over the group).  fp32 output (an output quantizer follows as its own
- * kernel).  group_size % 64 == 0, K % group_size == 0, N % 128 == 0. */
+ * kernel).  group_size % 64 == 0, K % group_size == 0, N % 128 == 0, group_size <= 32768.
+ * The arithmetic is one fixed sequence (oracle.mq_oracle.grouped_linear restates it): per output acc = 0, then for g = 0 .. G - 1 in
+ * this order acc = fma(float(bracket_g), alpha[g, n], acc) -- one int32 -> fp32 conversion (round to nearest even) and one fused
+ * multiply-add per group --, then one fp32 add of bias[n] when there is a bias.
+ * DOMAIN the kernel relies on and does not check (the vectors live on the device): |cw[g, n]| < 2^23 and |a_gsum[g, m]| < 2^23 (their
+ * product is formed by a 24-bit multiply; stored int8 activations give |a_gsum| <= 128 group_size <= 2^22), and every group's
+ * bracket -- each of its partial sums included -- fits int32.  Offsets inside their grids are far inside it (|cw| <= 383, |bracket|
+ * <= group_size 255 255 < 2^31 at group_size <= 32768); a narrow group or an activation grid far from zero can leave it, so the
+ * caller has to check: QLinear does (quantization/qmodule.py, _grouped_plan and _forward_int8_grouped) and keeps such a layer off
+ * this kernel or poisons alpha with NaN. */
 int mq_w8a8_linear_grouped(const int8_t* a_q, const int8_t* w_q, int64_t M, int64_t N, int64_t K, int64_t group_size,
                            const int32_t* a_gsum, const float* alpha, const int32_t* cw, const int32_t* t, const float* bias,
                            float* out, mq_stream_t stream);
@@ -1160,6 +1169,24 @@ int mq_decode_cache_reorder(const mq_decode_cache_fork_args* args, mq_stream_t s
  * mq_attention_quant).  Non-finite inputs saturate like every integer image (NaN -> qmin). */
 int mq_qmatmul(const float* x1, const float* x2, float* out, int64_t batch, int64_t M, int64_t N, int64_t K, int x2_k_contiguous,
                const mq_grid* grid1, const mq_grid* grid2, const mq_grid* grid_out, mq_stream_t stream);
+
+/* The kernel and the launch dimensions mq_qmatmul takes for a call, from the host arithmetic the launcher itself runs (no GPU is
+ * touched, nothing is launched): what a test needs to state which of the 28 instantiations a case reaches.
+ *   panel 1: qmatmul_panel_kernel<bkm, kc, vec> (an x1 of at most 8 bits, K <= 256, M > 64, N > 64; kc = 1 / 2 / 4 chunks of 64 k), a
+ *            workgroup per (batch element, 128-row panel, range of tiles_per_split column tiles): nblk = batch tiles_m nsplit;
+ *   panel 0: qmatmul_kernel<a16, bkm, rf, vec> (kc = 0), a workgroup per 64 rf x 64 tile: nblk = batch tiles_m tiles_n.
+ * a16: x1_span = qmax - qmin of grid1 exceeds 255 (two byte planes).  bkm: x2_k_contiguous.  a_vec / b_vec / o_vec: 16-byte accesses
+ * to x1 / x2 / out (K % 4 == 0 -- N % 4 == 0 for out -- on a 16-byte aligned base; an N-contiguous x2 always).  vec: the template
+ * argument -- a_vec && b_vec, in the panel kernel also o_vec and M N < 2^29 (buffer stores with 32-bit byte offsets).
+ * x1_aligned16 / x2_aligned16 / out_aligned16: whether the bases the call would pass are 16-byte aligned.  Shapes and spans mq_qmatmul
+ * refuses are refused here with the same status. */
+typedef struct {
+  int panel, a16, bkm, rf, kc, vec;
+  int a_vec, b_vec, o_vec;
+  int64_t tiles_m, tiles_n, nsplit, tiles_per_split, nblk;
+} mq_qmatmul_choice;
+int mq_qmatmul_geometry(int64_t batch, int64_t M, int64_t N, int64_t K, int x2_k_contiguous, int x1_aligned16, int x2_aligned16,
+                        int out_aligned16, double x1_span, mq_qmatmul_choice* choice);
 
 #ifdef __cplusplus
 }

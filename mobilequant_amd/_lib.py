@@ -28,6 +28,12 @@ class MqGrid(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("offset", c_void_p), ("qmin", c_float), ("qmax", c_float)]
 
 
+class MqQmatmulChoice(ctypes.Structure):
+    _fields_ = [("panel", c_int), ("a16", c_int), ("bkm", c_int), ("rf", c_int), ("kc", c_int), ("vec", c_int), ("a_vec", c_int),
+                ("b_vec", c_int), ("o_vec", c_int), ("tiles_m", c_int64), ("tiles_n", c_int64), ("nsplit", c_int64),
+                ("tiles_per_split", c_int64), ("nblk", c_int64)]
+
+
 class MqDecodeGemvArgs(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("xq", c_void_p), ("K", c_int), ("N", c_int), ("norm_w", c_void_p), ("norm_bias", c_void_p), ("layernorm", c_int), ("norm_in", MqGrid),
                 ("eps", c_float), ("a_grid", MqGrid), ("w", c_void_p), ("alpha", c_void_p), ("w_zp", c_void_p),
@@ -263,6 +269,7 @@ _SIGNATURES = {
     "mq_calib_rope": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "mq_calib_rope_qkv": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "mq_qmatmul": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(MqGrid), POINTER(MqGrid), POINTER(MqGrid), _P]),
+    "mq_qmatmul_geometry": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, ctypes.c_double, POINTER(MqQmatmulChoice)]),
     "mq_gemm_set_variant": (c_int, [c_int]),
     "mq_gemm_variant_name": (c_char_p, [c_int]),
     "mq_gemm_set_debug": (c_int, [c_int]),

@@ -545,6 +545,75 @@ __global__ void __launch_bounds__(256, KC == 1 ? 3 : 1) qmatmul_panel_kernel(con
 
 using namespace mq;
 
+// The launcher's whole choice of kernel and launch dimensions as one pure host function (mq_qmatmul_geometry exposes it: the dispatch
+// predicate of tests/qmatmul_cases.py is checked against it without a GPU).  al1 / al2 / alo: the bases are 16-byte aligned.
+// 128-row tiles where that still gives every CU two workgroups: the x2 tile is fetched and quantised once per 128 rows instead of per 64
+// (S = 2048: qk_bmm 229 -> 202 us, pv_bmm 184 -> 152 us; 256-row tiles fall back to one workgroup per CU -- 256 VGPRs -- and lose it
+// again: 236 / 187 us, profiles/r06/bench_qmatmul.log)
+static int tile_rf(int64_t batch, int64_t M, int64_t N) { return (M >= 256 && batch * ((M + 127) / 128) * ((N + 63) / 64) >= 512) ? 2 : 1; }
+// workgroups of the tile kernel; the launcher bounds this count for every shape, also where the row-panel kernel (fewer) is launched
+static int64_t tile_blocks(int64_t batch, int64_t M, int64_t N) {
+  const int rf = tile_rf(batch, M, N);
+  return batch * ((M + 64 * rf - 1) / (64 * rf)) * ((N + 63) / 64);
+}
+
+static mq_qmatmul_choice choose_kernel(int64_t batch, int64_t M, int64_t N, int64_t K, int x2_k_contiguous, bool al1, bool al2, bool alo, bool a16) {
+  mq_qmatmul_choice c;
+  c.a16 = a16;
+  c.bkm = x2_k_contiguous != 0;
+  c.rf = tile_rf(batch, M, N);
+  int64_t tiles_m = (M + 64 * c.rf - 1) / (64 * c.rf), tiles_n = (N + 63) / 64;
+  c.a_vec = K % 4 == 0 && al1;
+  c.b_vec = x2_k_contiguous ? (K % 4 == 0 && al2) : 1;
+  c.o_vec = N % 4 == 0 && alo;
+  c.vec = c.a_vec && c.b_vec;                    // every K-contiguous operand takes unconditional 16-byte loads
+  c.panel = 0;
+  c.kc = 0;
+  int64_t nsplit = 1, per = tiles_n;
+  // row-panel kernel: an x1 of at most 8 bits with K <= 256 against several column tiles (qk_bmm).  Column ranges of at least four
+  // tiles (the panel's quantisation amortised), split until the launch has ~8 workgroups per CU (S = T = 2048, 32 heads: 1 / 2 / 3 / 4 /
+  // 8 ranges per row panel = 145 / 141 / 125 / 120 / 137 us)
+  if (!a16 && K <= 256 && M > 64 && N > 64) {
+    c.panel = 1;
+    c.rf = 2;
+    c.kc = K <= 64 ? 1 : (K <= 128 ? 2 : 4);
+    tiles_m = (M + 127) / 128;
+    const int64_t base = batch * tiles_m;
+    nsplit = std::min<int64_t>(tiles_n, std::max<int64_t>(1, (2048 + base - 1) / base));
+    per = std::max<int64_t>((tiles_n + nsplit - 1) / nsplit, std::min<int64_t>(4, tiles_n));
+    nsplit = (tiles_n + per - 1) / per;
+    c.vec = c.vec && c.o_vec && M * N < (1ll << 29);     // + buffer stores of whole quads with 32-bit byte offsets
+  }
+  c.tiles_m = tiles_m;
+  c.tiles_n = tiles_n;
+  c.nsplit = nsplit;
+  c.tiles_per_split = per;
+  c.nblk = c.panel ? batch * tiles_m * nsplit : tile_blocks(batch, M, N);
+  return c;
+}
+
+// the shapes and grids mq_qmatmul serves (the message names them all)
+static bool served(int64_t batch, int64_t M, int64_t N, int64_t K, int x2_k_contiguous, double span1, double span2) {
+  return span1 >= 1 && span1 <= 65535 && span2 >= 1 && span2 <= 255 && (x2_k_contiguous || N % 4 == 0) && K <= 131071 &&
+         M < (1ll << 31) - 64 && N < (1ll << 31) - 64 && batch < (1ll << 31) && M * K < (1ll << 40) && N * K < (1ll << 40);
+}
+
+extern "C" int mq_qmatmul_geometry(int64_t batch, int64_t M, int64_t N, int64_t K, int x2_k_contiguous, int x1_aligned16, int x2_aligned16,
+                                   int out_aligned16, double x1_span, mq_qmatmul_choice* choice) {
+  const char* fn = "mq_qmatmul_geometry";
+  MQ_REQUIRE(choice, "%s: null pointer", fn);
+  MQ_REQUIRE(batch > 0 && M > 0 && N > 0 && K > 0, "%s: bad shape batch=%lld M=%lld N=%lld K=%lld", fn, (long long)batch, (long long)M,
+             (long long)N, (long long)K);
+  MQ_REQUIRE(x2_k_contiguous || x2_aligned16, "%s: an N-contiguous x2 must be 16-byte aligned", fn);
+  if (!served(batch, M, N, K, x2_k_contiguous, x1_span, 255.0)) {
+    set_error("%s: a shape or an x1 span mq_qmatmul does not serve", fn);
+    return MQ_EUNSUPPORTED;
+  }
+  *choice = choose_kernel(batch, M, N, K, x2_k_contiguous, x1_aligned16 != 0, x2_aligned16 != 0, out_aligned16 != 0, x1_span > 255);
+  MQ_REQUIRE(tile_blocks(batch, M, N) < (1ll << 31) && choice->nblk < (1ll << 31), "%s: too many tiles", fn);
+  return MQ_OK;
+}
+
 extern "C" int mq_qmatmul(const float* x1, const float* x2, float* out, int64_t batch, int64_t M, int64_t N, int64_t K, int x2_k_contiguous,
                           const mq_grid* grid1, const mq_grid* grid2, const mq_grid* grid_out, mq_stream_t stream) {
   const char* fn = "mq_qmatmul";
@@ -557,83 +626,62 @@ extern "C" int mq_qmatmul(const float* x1, const float* x2, float* out, int64_t 
   MQ_REQUIRE(grid1->scale && grid1->offset && grid2->scale && grid2->offset, "%s: both operands need a (static per-tensor) grid", fn);
   MQ_REQUIRE(!grid_out || !grid_out->scale || grid_out->offset, "%s: output grid without an offset", fn);
   const double span1 = (double)grid1->qmax - (double)grid1->qmin, span2 = (double)grid2->qmax - (double)grid2->qmin;
-  if (!(span1 >= 1 && span1 <= 65535 && span2 >= 1 && span2 <= 255) || (!x2_k_contiguous && N % 4 != 0) || K > 131071 ||
-      M >= (1ll << 31) - 64 || N >= (1ll << 31) - 64 || batch >= (1ll << 31) || M * K >= (1ll << 40) || N * K >= (1ll << 40)) {
+  if (!served(batch, M, N, K, x2_k_contiguous, span1, span2)) {
     set_error("%s: not served: grids of at most 16 (x1) / 8 (x2) bits, N %% 4 == 0 for an N-contiguous x2 (pass other widths K-contiguous), K <= 131071 (the int32 MFMA accumulators hold K x 128 x 128)", fn);
     return MQ_EUNSUPPORTED;
   }
+  const bool a16 = span1 > 255;
+  const mq_qmatmul_choice ch = choose_kernel(batch, M, N, K, x2_k_contiguous, aligned(x1, 16), aligned(x2, 16), aligned(out, 16), a16);
   QmmArgs g;
   g.a = x1; g.b = x2; g.out = out;
   g.batch = (int)batch; g.M = (int)M; g.N = (int)N; g.K = (int)K;
   g.a_bs = M * K; g.b_bs = N * K; g.o_bs = M * N;
   g.ga = *grid1; g.gb = *grid2;
   g.go = (grid_out && grid_out->scale) ? *grid_out : mq_grid{nullptr, nullptr, 0.f, 0.f};
-  const bool a16 = span1 > 255;
   // stored bytes: <= 8-bit grids as index - (qmin + 128); a wider x1 as the two byte planes of index - qmin, each minus 128
   g.a_shift = a16 ? (int)grid1->qmin + 32896 : (int)grid1->qmin + 128;
   g.b_shift = (int)grid2->qmin + 128;
-  // 256-row tiles where that still gives every CU several workgroups (the x2 tile is quantised once per 256 rows instead of per 64)
-  // 128-row tiles where that still gives every CU two workgroups: the x2 tile is fetched and quantised once per 128 rows instead of per 64
-  // (S = 2048: qk_bmm 229 -> 202 us, pv_bmm 184 -> 152 us; 256-row tiles fall back to one workgroup per CU -- 256 VGPRs -- and lose it
-  // again: 236 / 187 us, profiles/r06/bench_qmatmul.log)
-  const int rf = (M >= 256 && batch * ((M + 127) / 128) * ((N + 63) / 64) >= 512) ? 2 : 1;
-  g.tiles_m = (int)((M + 64 * rf - 1) / (64 * rf));
-  g.tiles_n = (int)((N + 63) / 64);
-  g.nblk = (long long)batch * g.tiles_m * g.tiles_n;
-  g.a_vec = K % 4 == 0 && aligned(x1, 16);
-  g.b_vec = x2_k_contiguous ? (K % 4 == 0 && aligned(x2, 16)) : 1;
-  g.o_vec = N % 4 == 0 && aligned(out, 16);
-  MQ_REQUIRE(g.nblk < (1ll << 31), "%s: too many tiles", fn);
+  g.tiles_m = (int)ch.tiles_m;
+  g.tiles_n = (int)ch.tiles_n;
+  g.nsplit = (int)ch.nsplit;
+  g.tiles_per_split = (int)ch.tiles_per_split;
+  g.nblk = ch.nblk;
+  g.a_vec = ch.a_vec;
+  g.b_vec = ch.b_vec;
+  g.o_vec = ch.o_vec;
+  MQ_REQUIRE(tile_blocks(batch, M, N) < (1ll << 31) && g.nblk < (1ll << 31), "%s: too many tiles", fn);
   hipStream_t st = as_stream(stream);
-  const bool vec = g.a_vec && g.b_vec;          // every K-contiguous operand takes unconditional 16-byte loads
-  g.nsplit = 1;
-  g.tiles_per_split = g.tiles_n;
-  // row-panel kernel: an x1 of at most 8 bits with K <= 256 against several column tiles (qk_bmm).  Column ranges of at least four
-  // tiles (the panel's quantisation amortised), split until the launch has ~8 workgroups per CU (S = T = 2048, 32 heads: 1 / 2 / 3 / 4 /
-  // 8 ranges per row panel = 145 / 141 / 125 / 120 / 137 us)
-  if (!a16 && K <= 256 && M > 64 && N > 64) {
-    const long long tiles_m = (M + 127) / 128, tiles_n = (N + 63) / 64, base = batch * tiles_m;
-    long long nsplit = std::min<long long>(tiles_n, std::max<long long>(1, (2048 + base - 1) / base));
-    long long per = std::max<long long>((tiles_n + nsplit - 1) / nsplit, std::min<long long>(4, tiles_n));
-    nsplit = (tiles_n + per - 1) / per;
-    g.tiles_m = (int)tiles_m;
-    g.tiles_n = (int)tiles_n;
-    g.nsplit = (int)nsplit;
-    g.tiles_per_split = (int)per;
-    g.nblk = base * nsplit;
-    MQ_REQUIRE(g.nblk < (1ll << 31), "%s: too many tiles", fn);
-    const dim3 pgrid((unsigned)g.nblk), pblock(256);
+  const dim3 grid((unsigned)g.nblk), block(256);
+  if (ch.panel) {
 #define MQ_QMM_PANEL(BKM, VEC)                                                            \
   do {                                                                                    \
-    if (K <= 64) qmatmul_panel_kernel<BKM, 1, VEC><<<pgrid, pblock, 0, st>>>(g);          \
-    else if (K <= 128) qmatmul_panel_kernel<BKM, 2, VEC><<<pgrid, pblock, 0, st>>>(g);    \
-    else qmatmul_panel_kernel<BKM, 4, VEC><<<pgrid, pblock, 0, st>>>(g);                  \
+    if (ch.kc == 1) qmatmul_panel_kernel<BKM, 1, VEC><<<grid, block, 0, st>>>(g);         \
+    else if (ch.kc == 2) qmatmul_panel_kernel<BKM, 2, VEC><<<grid, block, 0, st>>>(g);    \
+    else qmatmul_panel_kernel<BKM, 4, VEC><<<grid, block, 0, st>>>(g);                    \
   } while (0)
-    const bool vecp = vec && g.o_vec && M * N < (1ll << 29);       // + buffer stores of whole quads with 32-bit byte offsets
-    if (x2_k_contiguous) {
-      if (vecp) MQ_QMM_PANEL(true, true);
+    if (ch.bkm) {
+      if (ch.vec) MQ_QMM_PANEL(true, true);
       else MQ_QMM_PANEL(true, false);
     } else {
-      if (vecp) MQ_QMM_PANEL(false, true);
+      if (ch.vec) MQ_QMM_PANEL(false, true);
       else MQ_QMM_PANEL(false, false);
     }
 #undef MQ_QMM_PANEL
     MQ_LAUNCH_CHECK(fn);
     return MQ_OK;
   }
-  const dim3 grid((unsigned)g.nblk), block(256);
 #define MQ_QMM_LAUNCH(A16, BKM)                                                           \
   do {                                                                                    \
-    if (rf == 2 && vec) qmatmul_kernel<A16, BKM, 2, true><<<grid, block, 0, st>>>(g);     \
-    else if (rf == 2) qmatmul_kernel<A16, BKM, 2, false><<<grid, block, 0, st>>>(g);      \
-    else if (vec) qmatmul_kernel<A16, BKM, 1, true><<<grid, block, 0, st>>>(g);           \
+    if (ch.rf == 2 && ch.vec) qmatmul_kernel<A16, BKM, 2, true><<<grid, block, 0, st>>>(g);  \
+    else if (ch.rf == 2) qmatmul_kernel<A16, BKM, 2, false><<<grid, block, 0, st>>>(g);   \
+    else if (ch.vec) qmatmul_kernel<A16, BKM, 1, true><<<grid, block, 0, st>>>(g);        \
     else qmatmul_kernel<A16, BKM, 1, false><<<grid, block, 0, st>>>(g);                   \
   } while (0)
   if (a16) {
-    if (x2_k_contiguous) MQ_QMM_LAUNCH(true, true);
+    if (ch.bkm) MQ_QMM_LAUNCH(true, true);
     else MQ_QMM_LAUNCH(true, false);
   } else {
-    if (x2_k_contiguous) MQ_QMM_LAUNCH(false, true);
+    if (ch.bkm) MQ_QMM_LAUNCH(false, true);
     else MQ_QMM_LAUNCH(false, false);
   }
 #undef MQ_QMM_LAUNCH

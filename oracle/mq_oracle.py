@@ -1797,3 +1797,123 @@ def train_attn_probs_backward(raw, grad_out, mask, grid1, grid2, sqrt_d, n_sum, 
         e_to1 = np.where(in1, 0.0, e_gs * s1 + U32 * np.abs(to1))
     return dict(fwd=f, grad_raw=graw, e_raw=1.01 * e_raw, terms=(ts1, to1, ts2, to2), errs=tuple(1.01 * v for v in (e_ts1, e_to1, e_ts2, e_to2)),
                 prod=prod, dot=dot, e_dot=1.01 * e_dot, p=p, gp=gp)
+
+
+# ----------------------------------------------------------------------------------------------
+# a10 / a8 (pins)  mq_qmatmul (csrc/mq_qmatmul.hip) and mq_w8a8_linear_grouped (csrc/mq_gemm_grouped.hip), op for op
+# ----------------------------------------------------------------------------------------------
+QMATMUL_MUTATIONS = ("scale64", "in_half_up", "out_half_up", "nan_qmax", "no_zero_row")
+GROUPED_MUTATIONS = ("mul_add", "reverse", "bracket_f64")
+QMATMUL_MUTATION = None   # tests only (like TRAIN_MUTATION): a name from the lists above makes every call without its own `mutation` wrong on purpose
+GROUPED_MUTATION = None
+
+
+def _rint_half_up(t):
+    """floor(t + 1/2) for fp32 t, exact in float64 (wrong on purpose: ties go up instead of to even); NaN / inf pass."""
+    t64 = np.asarray(t, F32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.abs(t64) < 2.0 ** 52, np.floor(t64 + 0.5), t64).astype(F32)
+
+
+def image_index(x, grid, mutation=None):
+    """int64 indices of an integer IMAGE (csrc/mq_quant.h index_image_nan2qmin): clamp(rint(x / s) + o), the logic of quantize_storage
+    with shift 0 -- where the reference's index is NaN (x NaN or +-inf: round_ste's inf - inf; an overflowing quotient) the index is
+    qmin.  grid = (scale, offset, qmin, qmax) per tensor.  mutation "in_half_up": ties up; "nan_qmax": NaN becomes qmax."""
+    s, o, qmin, qmax = grid
+    x = np.asarray(x, F32)
+    with np.errstate(all="ignore"):
+        t = (x / F32(s)).astype(F32)
+        rt = _rint_half_up(t) if mutation == "in_half_up" else np.rint(t)
+        r = ((rt - t).astype(F32) + t).astype(F32)
+        idx = np.clip((r + F32(o)).astype(F32), F32(qmin), F32(qmax))
+    return np.where(np.isnan(idx), F32(qmax if mutation == "nan_qmax" else qmin), idx).astype(np.int64)
+
+
+def qmatmul_launch(x1, x2, g1, g2, g_out, mutation=None):
+    """What one mq_qmatmul launch stores, op for op, knowing nothing of kernels, routes or tiles.  x1 [batch, M, K], x2 [batch, K, N]
+    fp32 (the LOGICAL operand, whichever memory order the call uses); g1 / g2 / g_out = (scale, offset, qmin, qmax), g_out None for no
+    output quantizer.
+      ia, ib   image_index: clamp(rint(x / s) + o), NaN -> qmin
+      t        sum_k (ia - rint(o1))(ib - rint(o2)) in exact integers (a float64 contraction below 2^53, asserted)
+      domain   |rint(o)| >= 2^20 for either operand: every output is NaN
+      v        x1 of at most 8 bits (qmax - qmin <= 255): fl32(t), then ONE fp32 multiply by alpha = fl32(s1 s2);
+               a wider x1: fl32(float64(t) * float64(alpha))
+      out      the reference's output quantizer (qmodule.py:286-290) op for op: q = v / s (IEEE), r = (rint(q) - q) + q (round_ste:
+               +-inf -> NaN), idx = clamp(r + o) with NaN kept, (idx - o) * s.
+    Returns dict(out fp32 [batch, M, N], t int64, alpha, v fp32, q fp32 | None, tie float64 | None: the distance of q to a half step,
+    idx fp32 | None, ia, ib).  mutation (tests only) makes it deliberately wrong: QMATMUL_MUTATIONS."""
+    mutation = QMATMUL_MUTATION if mutation is None else mutation
+    assert mutation is None or mutation in QMATMUL_MUTATIONS, mutation
+    x1, x2 = np.asarray(x1, F32), np.asarray(x2, F32)
+    assert x1.ndim == 3 and x2.ndim == 3 and x1.shape[0] == x2.shape[0] and x1.shape[2] == x2.shape[1]
+    ia, ib = image_index(x1, g1, mutation), image_index(x2, g2, mutation)
+    z1, z2 = np.rint(F32(g1[1])), np.rint(F32(g2[1]))
+    sane = bool(abs(z1) < 2.0 ** 20 and abs(z2) < 2.0 ** 20)
+    a1 = ia.astype(np.float64) - (np.float64(z1) if sane else 0.0)
+    b1 = ib.astype(np.float64) - (np.float64(z2) if sane else 0.0)
+    assert x1.shape[2] * np.abs(a1).max() * np.abs(b1).max() < 2.0 ** 53
+    t = np.rint(np.matmul(a1, b1)).astype(np.int64)
+    if mutation == "no_zero_row":                                # the term -z2 sum_k (ia - z1) is lost
+        t = t + np.int64(z2) * np.rint(a1.sum(axis=2, keepdims=True)).astype(np.int64)
+    alpha = F32(F32(g1[0]) * F32(g2[0]))
+    wide = float(g1[3]) - float(g1[2]) > 255
+    with np.errstate(all="ignore"):
+        if wide or mutation == "scale64":
+            v = (t.astype(np.float64) * np.float64(alpha)).astype(F32)
+        else:
+            v = (t.astype(F32) * alpha).astype(F32)
+        if not sane:
+            v = np.full(v.shape, np.nan, F32)
+        if g_out is None:
+            return dict(out=v, t=t, alpha=alpha, v=v, q=None, tie=None, idx=None, ia=ia, ib=ib)
+        so, oo, qmin, qmax = g_out
+        so, oo = F32(so), F32(oo)
+        q = (v / so).astype(F32)
+        rq = _rint_half_up(q) if mutation == "out_half_up" else np.rint(q)
+        r = ((rq - q).astype(F32) + q).astype(F32)
+        idx = np.clip((r + oo).astype(F32), F32(qmin), F32(qmax)).astype(F32)
+        out = ((idx - oo).astype(F32) * so).astype(F32)
+        q64 = q.astype(np.float64)
+        tie = np.abs(q64 - np.floor(q64) - 0.5)
+    return dict(out=out, t=t, alpha=alpha, v=v, q=q, tie=tie, idx=idx, ia=ia, ib=ib)
+
+
+def grouped_linear(a, w, gs, a_gsum, alpha, cw, t, bias, mutation=None):
+    """What mq_w8a8_linear_grouped stores: a [M, K], w [N, K] stored int8 values, group g = columns [g gs, (g + 1) gs); a_gsum int32
+    [G, M], alpha fp32 [G, N], cw / t int32 [G, N], bias fp32 [N] or None.  Per output acc = 0, then for g = 0 .. G - 1:
+        acc = fma_f32(fl32(P_g[m, n] + cw[g, n] a_gsum[g, m] + t[g, n]), alpha[g, n], acc)
+    (one int32 -> fp32 conversion, one fused multiply-add), then one fp32 add of bias[n].  The brackets are formed in int64 and asserted
+    to lie inside the kernel's domain: |cw|, |a_gsum| < 2^23 (a 24-bit multiply), the product and the bracket inside int32.
+    Returns dict(out fp32 [M, N], bracket int64 [G, M, N]).  mutation (tests only): "mul_add" -- a rounded multiply and a rounded add
+    for the fma; "reverse" -- the groups folded from the last to the first; "bracket_f64" -- the bracket enters the fma as a float64
+    (its rounding to fp32 is lost)."""
+    mutation = GROUPED_MUTATION if mutation is None else mutation
+    assert mutation is None or mutation in GROUPED_MUTATIONS, mutation
+    a, w = np.asarray(a), np.asarray(w)
+    M, K = a.shape
+    N = w.shape[0]
+    assert K % gs == 0 and w.shape[1] == K
+    G = K // gs
+    ag, cw, t = (np.asarray(v, np.int64) for v in (a_gsum, cw, t))
+    alpha = np.asarray(alpha, F32)
+    assert ag.shape == (G, M) and cw.shape == (G, N) and t.shape == (G, N) and alpha.shape == (G, N)
+    assert np.abs(cw).max() < 2 ** 23 and np.abs(ag).max() < 2 ** 23
+    br = np.empty((G, M, N), np.int64)
+    for g in range(G):
+        P = np.rint(a[:, g * gs:(g + 1) * gs].astype(np.float64) @ w[:, g * gs:(g + 1) * gs].astype(np.float64).T).astype(np.int64)
+        prod = cw[g][None, :] * ag[g][:, None]
+        assert np.abs(prod).max() < 2 ** 31
+        br[g] = P + prod + t[g][None, :]
+    assert br.min() >= -2 ** 31 and br.max() < 2 ** 31
+    acc = np.zeros((M, N), F32)
+    for g in (range(G - 1, -1, -1) if mutation == "reverse" else range(G)):
+        al = np.broadcast_to(alpha[g][None, :], (M, N))
+        if mutation == "bracket_f64":
+            acc = (br[g].astype(np.float64) * al.astype(np.float64) + acc.astype(np.float64)).astype(F32)
+        elif mutation == "mul_add":
+            acc = ((br[g].astype(F32) * al).astype(F32) + acc).astype(F32)
+        else:
+            acc = fma_f32(br[g].astype(F32), al, acc)
+    if bias is not None:
+        acc = (acc + np.asarray(bias, F32)[None, :]).astype(F32)
+    return dict(out=acc, bracket=br)
