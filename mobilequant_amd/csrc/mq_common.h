@@ -191,16 +191,27 @@ __device__ __forceinline__ int64_t tiled_image_offset(int64_t row, int64_t k, in
 // inside one row block) as 16-byte units p = RW * piece + r, piece = k >> 4; unit p goes to block (row0 >> 4, piece >> 2), byte
 // 256 (piece & 3) + 16 ((row0 & 15) + r) -- RW x 16 B contiguous per piece: whole cache lines of a fragment block.  PAD: the rows
 // past `rows` (padding of the image's last row block) are written like the others; otherwise they stay untouched.
-template <int RW, int THREADS, bool PAD>
+// POLICY: cache policy of the image stores.  STORE_DEFAULT keeps the written lines in the XCD's L2 like any store (today's statement,
+// word for word: norm_tiled8_kernel compiles to the code it always had); STORE_NT marks them streaming.
+enum StorePolicy { STORE_DEFAULT = 0, STORE_NT = 1 };
+template <int RW, int THREADS, bool PAD, int POLICY = STORE_DEFAULT>
 __device__ __forceinline__ void staged_copy_out(const int8_t* stage, int8_t* q_tiled, int64_t row0, int64_t rows, int64_t cols) {
+  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   const int units = (int)(cols >> 4) * RW;
   const int64_t rb = row0 >> 4;
   const int half = (int)(row0 & 15);
   for (int p = threadIdx.x; p < units; p += THREADS) {
     const int piece = p / RW, r = p % RW;
-    if (PAD || row0 + r < rows)
-      *reinterpret_cast<uint4*>(q_tiled + tiled_block_base(rb, piece >> 2, cols) + ((piece & 3) << 8) + ((half + r) << 4)) =
-          *reinterpret_cast<const uint4*>(stage + (p << 4));
+    if (PAD || row0 + r < rows) {
+      if constexpr (POLICY == STORE_DEFAULT) {
+        *reinterpret_cast<uint4*>(q_tiled + tiled_block_base(rb, piece >> 2, cols) + ((piece & 3) << 8) + ((half + r) << 4)) =
+            *reinterpret_cast<const uint4*>(stage + (p << 4));
+      } else {
+        int8_t* dst = q_tiled + tiled_block_base(rb, piece >> 2, cols) + ((piece & 3) << 8) + ((half + r) << 4);
+        const v4u v = *reinterpret_cast<const v4u*>(stage + (p << 4));
+        __builtin_nontemporal_store(v, reinterpret_cast<v4u*>(dst));
+      }
+    }
   }
 }
 

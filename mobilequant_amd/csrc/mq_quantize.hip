@@ -409,7 +409,11 @@ __global__ void __launch_bounds__(256 * GRPS) quantize_tiled8_kernel(const float
   __syncthreads();
   if (HAS_SUM && threadIdx.x < RW && row0 + threadIdx.x < rows)
     row_sum[row0 + threadIdx.x] = (s_part[threadIdx.x][0] + s_part[threadIdx.x][1]) + (s_part[threadIdx.x][2] + s_part[threadIdx.x][3]) - 128 * KCOLS;
-  staged_copy_out<RW, 256 * GRPS, true>(stage8, q, row0, rows, KCOLS);   // rows past `rows` are padding of the image: written like the others
+  // rows past `rows` are padding of the image: written like the others.  Streaming stores: the image is read next by the GEMM, seven in
+  // eight of its workgroups on other XCDs, so this XCD's L2 has no use for the lines; written with the default policy they stay dirty
+  // in it until the kernel ends.  Same bytes, same image; this kernel's dispatch is 1.1 us shorter inside the headline step, the step
+  // 0.95 us (DESIGN 4.2 "cache policy", NOTES 11.2: sc1 stores gain 0.6 us; streaming x LOADS cost 0.3 us wherever they were tried)
+  staged_copy_out<RW, 256 * GRPS, true, STORE_NT>(stage8, q, row0, rows, KCOLS);
 }
 
 }  // namespace mq

@@ -72,11 +72,26 @@ VARIANTS = {
 # ISA in csrc/); `python -m mobilequant_amd.build --experiments` regenerates them into csrc/ before it compiles with -DMQ_BUILD_EXPERIMENTS
 EXPERIMENTAL = ("fr128rs", "frw4", "frw4_128")
 
+# Cache policy, a field per variant (beside VARIANTS, whose five-field rows tests/test_cabi.py unpacks): the instruction modifier of
+#   store   the output stores of the u8 epilogues ("" = write-back | nt | sc1 | "sc0 sc1" | none = no stores, a what-if),
+#   a_load  the activation-fragment loads (a_load, a_load_spare),
+#   w_dma   the W LDS-DMA loads.
+# A variant that is not listed takes "" everywhere (the instructions as they have always been emitted).  A modifier is a bit of the
+# encoding: no instruction moves.  MQ_FR_STORE / MQ_FR_A_LOAD / MQ_FR_W_DMA override the field for experiments (every variant generated in
+# that run); the committed files are generated with none of them set.
+POLICY_FIELDS = {"store": "MQ_FR_STORE", "a_load": "MQ_FR_A_LOAD", "w_dma": "MQ_FR_W_DMA"}
+VARIANT_POLICY = {
+    "fr": {"store": "", "a_load": "", "w_dma": ""},
+}
+
 
 def configure(name):
     """binds the module-level tile constants of one variant (the emitters read them at call time)"""
     global BN, NW, EPI, PREFIX, FILE, BM, W_BYTES, PAR, STG, ROWP, STG_WAVE, LDS_BYTES, FN, PIECES, HALF, RING_BASE, SCALAR_GRID
     BN, NW, EPI, PREFIX, FILE = VARIANTS[name]
+    global STORE_POLICY, A_POLICY, W_POLICY
+    STORE_POLICY, A_POLICY, W_POLICY = (os.environ.get(env, VARIANT_POLICY.get(name, {}).get(field, ""))
+                                        for field, env in POLICY_FIELDS.items())
     SCALAR_GRID = (BN == 176 or EPI not in ("u8", "u8w4", "u8w4x"))      # ONE output grid per launch (scalars); otherwise per-column grids (q | k | v segments)
     # round 4: the u8 epilogue is interleaved with the MFMAs of the LAST TWO stages (final_block) unless MQ_FR_TAIL=0
     global TAIL
@@ -179,10 +194,15 @@ S_SO, S_OO, S_ISO = 96, 97, 98    # the output grid: scale, offset (s_load at th
 # what-if switches for profiling builds (results are wrong): MQ_FR_NO_A / _NO_W / _NO_READ / _NO_MFMA drop the in-loop activation
 # loads / W LDS-DMA / W fragment reads / MFMAs
 NO_A, NO_W, NO_READ, NO_MFMA = (bool(os.environ.get("MQ_FR_" + k)) for k in ("NO_A", "NO_W", "NO_READ", "NO_MFMA"))
-# cache policy of the output stores: "" (write-back, default) | nt | sc1 | "sc0 sc1" | none.  Same kernel time for all (profiles/r02),
-# but nt pushes the partial 32 B sectors of the 176-byte tile rows out before their neighbours merge: WRITE_SIZE 14.5 MB vs the exact
-# M * N = 11.5 MB with write-back
-STORE_POLICY = os.environ.get("MQ_FR_STORE", "")
+# cache policy of the output stores, the activation loads and the W LDS-DMA: VARIANT_POLICY, bound by configure().  (Output stores on
+# their own: same kernel time for all (profiles/r02), but nt pushes the partial 32 B sectors of the 176-byte tile rows out before their
+# neighbours merge: WRITE_SIZE 14.5 MB vs the exact M * N = 11.5 MB with write-back)
+STORE_POLICY = A_POLICY = W_POLICY = ""
+
+
+def with_policy(text, policy):
+    """an instruction with its cache-policy modifier ("" = none)"""
+    return f"{text} {policy}".rstrip()
 
 out = []
 
@@ -251,7 +271,7 @@ def issue_w(q, t, nw, slot_sgpr):
     for i in range(nw):
         emit(f"s_add_u32 m0, s{slot_sgpr}, s{S_WK[i]}")
         emit("s_nop 0")
-        emit(f"global_load_lds_dwordx4 %[sw{i}], s[{S_WBASE}:{S_WBASE + 1}]")
+        emit(with_policy(f"global_load_lds_dwordx4 %[sw{i}], s[{S_WBASE}:{S_WBASE + 1}]", W_POLICY))
         q.issue(("W", t))
     emit(f"s_add_u32 s{S_WBASE}, s{S_WBASE}, {BK}")
     emit(f"s_addc_u32 s{S_WBASE + 1}, s{S_WBASE + 1}, 0")
@@ -261,7 +281,7 @@ def w_piece(q, t, i, slot_sgpr):
     def f():
         emit(f"s_add_u32 m0, s{slot_sgpr}, s{S_WK[i]}")
         emit("s_nop 0")
-        emit(f"global_load_lds_dwordx4 %[sw{i}], s[{S_WBASE}:{S_WBASE + 1}]")
+        emit(with_policy(f"global_load_lds_dwordx4 %[sw{i}], s[{S_WBASE}:{S_WBASE + 1}]", W_POLICY))
         q.issue(("W", t))
     return f
 
@@ -269,7 +289,7 @@ def w_piece(q, t, i, slot_sgpr):
 def a_load(q, t, ks, i, set_, off):
     """A(t) fragment (ks, i) -> register set; address = S_ABASE + av{i} + off"""
     def f():
-        emit(f"global_load_dwordx4 {areg(set_, ks, i)}, %[av{i}], s[{S_ABASE}:{S_ABASE + 1}]" + (f" offset:{off}" if off else ""))
+        emit(with_policy(f"global_load_dwordx4 {areg(set_, ks, i)}, %[av{i}], s[{S_ABASE}:{S_ABASE + 1}]" + (f" offset:{off}" if off else ""), A_POLICY))
         q.issue(("A", t, ks))
     return f
 
@@ -558,7 +578,7 @@ def fb_read(lq, j):
 
 def a_load_spare(q, t, i, off):
     def f():
-        emit(f"global_load_dwordx4 {areg_spare(i)}, %[av{i}], s[{S_ABASE}:{S_ABASE + 1}] offset:{off}")
+        emit(with_policy(f"global_load_dwordx4 {areg_spare(i)}, %[av{i}], s[{S_ABASE}:{S_ABASE + 1}] offset:{off}", A_POLICY))
         q.issue(("A", t, 1))
     return f
 
@@ -623,6 +643,9 @@ def stage_pre_final(q, lq, t, nw):
 PROBE = False      # set per variant in main(): the headline kernel ("fr") always stamps its start / end clocks and stores them when asked
 DINIT = os.environ.get("MQ_FR_DINIT", "1") != "0"       # deferred accumulator initialisation (round 4); 0 = in the prologue
 PRO_SPLIT = bool(os.environ.get("MQ_FR_PRO_SPLIT"))
+# diagnostic build (tools/xcc_phase_probe.py): the clock probe stores the wave's HW_REG_XCC_ID -- the XCD it ran on -- in place of its
+# real-time ticks
+PROBE_XCC = bool(os.environ.get("MQ_FR_PROBE_XCC"))
 PSTAMP = bool(os.environ.get("MQ_FR_PSTAMP"))      # stamp build: five more s_memtime stamps inside the prologue (dbg slots 8..12)
 PST = (88, 90, 92, 94, 100)
 
@@ -822,6 +845,8 @@ def final_block(q, lq, stamp):
         emit(f"s_subb_u32 s{S_TS + 7}, s{S_TS + 7}, s{S_TS + 1}")
         emit(f"s_sub_u32 s{S_RT + 2}, s{S_RT + 2}, s{S_RT}")
         emit(f"s_subb_u32 s{S_RT + 3}, s{S_RT + 3}, s{S_RT + 1}")
+        if PROBE_XCC:
+            emit(f"s_getreg_b32 s{S_RT + 2}, hwreg(HW_REG_XCC_ID)")
         emit(f"v_and_b32 v{V_TMP}, 63, %[tid]")
         emit(f"v_cmp_eq_u32 vcc, 0, v{V_TMP}")
         emit("s_and_b64 exec, exec, vcc")
