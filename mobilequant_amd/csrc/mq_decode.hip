@@ -69,7 +69,6 @@ __global__ void decode_pack_grids_kernel(const mq_decode_grid_pack p, float* __r
 //   XM_LNORM: QLayerNorm.forward (qmodule.py:624-640 around F.layer_norm; StableLM-2's norm) instead of QRMSNorm: mean, biased variance,
 //     y = (xi * rstd + (-rstd * mean)) * gamma + beta -- the arithmetic of mq_layernorm_quant; three barriers instead of two.
 
-// PAIR_GATE: two consecutive weight rows (w1 row i, w3 row i) -> the gated activation (above).
 // OPRE (round 6; the w1 | w3 stream): the activation row is not x but x + Qo(alpha (acc + ct) + bias): o_proj's epilogue and the
 //   residual add on the integer sums mq_decode_attention_oproj left in o_acc -- the o_proj launch is gone.  Each workgroup also stores
 //   a share of that row to x_mid (the residual input of the w2 launch).
@@ -77,12 +76,9 @@ __global__ void decode_pack_grids_kernel(const mq_decode_grid_pack p, float* __r
 // (Tried and dropped in round 6: RoPE + the QMatMul input quantizers + the cache append as this launch's epilogue on rotation-partner
 // row pairs -- bit-identical, but one row pair per LANE is a 250-instruction serial chain at the launch's tail: +0.9 us on the q | k | v
 // launch against 0.15 us of 64-wide arithmetic in the attention launch; profiles/r06/decode_stamps_L4_rope_epilogue.log.)
-enum { PAIR_NONE = 0, PAIR_GATE = 1 };
-
-template <int XMODE, int PAIR, bool W4, bool OPRE>
+template <int XMODE, bool GATE, bool W4, bool OPRE>
 __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode_gemv_args g, const int rows_per_wg, unsigned long long* stamps) {
   DG_STAMP(0);
-  constexpr bool GATE = PAIR == PAIR_GATE, PAIRED = PAIR != PAIR_NONE;
   constexpr int XPRE = OPRE ? 2 : DG_XPRE;                         // OPRE holds four more vectors per element: K <= 4096 there
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [K] int8 activation image
   __shared__ float s_red[DG_PRO], s_red2[DG_PRO];
@@ -281,10 +277,10 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
   }
 #endif
   const int sw = wave - DG_PRO;                                    // 0 .. DG_STR-1
-  const int NL = PAIRED ? g.N >> 1 : g.N;                          // logical rows
+  const int NL = GATE ? g.N >> 1 : g.N;                          // logical rows
   const int kchunks = W4 ? K >> 5 : K >> 4;                        // 16-byte chunks per weight row
   const int wrow = W4 ? K >> 1 : K;                                // bytes per weight row
-  const int lchunks = PAIRED ? 2 * kchunks : kchunks;              // chunks per logical row
+  const int lchunks = GATE ? 2 * kchunks : kchunks;              // chunks per logical row
   const int cpl = (lchunks + 63) >> 6;
   const int row0 = blockIdx.x * rows_per_wg + sw;
   const int row_end = (blockIdx.x + 1) * rows_per_wg < NL ? (blockIdx.x + 1) * rows_per_wg : NL;
@@ -297,25 +293,25 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
       const int row = row0 + DG_STR * t;
       const int c = lane + 64 * j;
       if (row < row_end && c < lchunks)
-        buf[u] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g.w + (size_t)row * (PAIRED ? 2 : 1) * wrow) + c);
+        buf[u] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g.w + (size_t)row * (GATE ? 2 : 1) * wrow) + c);
       else
         buf[u] = v4i{0, 0, 0, 0};
       if (++j == cpl) { j = 0; ++t; }
     }
   };
   issue_pass(0, 0);
-  float p_alpha[PAIRED ? 2 : 1], p_bias[PAIRED ? 2 : 1];
-  int p_zp[PAIRED ? 2 : 1], p_ct[PAIRED ? 2 : 1];
+  float p_alpha[GATE ? 2 : 1], p_bias[GATE ? 2 : 1];
+  int p_zp[GATE ? 2 : 1], p_ct[GATE ? 2 : 1];
 #pragma unroll
-  for (int h = 0; h < (PAIRED ? 2 : 1); ++h) {
-    const int wr = PAIRED ? 2 * prow + h : prow;
+  for (int h = 0; h < (GATE ? 2 : 1); ++h) {
+    const int wr = GATE ? 2 * prow + h : prow;
     p_alpha[h] = prow_ok ? g.alpha[wr] : 0.f;
     p_zp[h] = prow_ok ? g.w_zp[wr] : 0;
     p_ct[h] = prow_ok ? g.col_term[wr] : 0;
     p_bias[h] = (prow_ok && g.bias) ? g.bias[wr] : 0.f;
   }
   float p_res = 0.f;
-  if (!PAIRED && g.resid && prow_ok) p_res = g.resid[prow];
+  if (!GATE && g.resid && prow_ok) p_res = g.resid[prow];
   if (g.zero_acc && sw == 0) {                                     // clear this workgroup's share of the o_proj accumulators (the next launch adds)
     const int per = (g.zero_n + (int)gridDim.x - 1) / (int)gridDim.x, lo = (int)blockIdx.x * per;
     const int hi = lo + per < g.zero_n ? lo + per : g.zero_n;
@@ -355,7 +351,7 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
       if (t2 < nslots) {
         int c = lane + 64 * j2;
         c = c < lchunks ? c : lchunks - 1;                       // buf[u] is zero there
-        const int ck = PAIRED ? (c >= kchunks ? c - kchunks : c) : c;
+        const int ck = GATE ? (c >= kchunks ? c - kchunks : c) : c;
         int part;
         if constexpr (W4) {
           const v4i a_lo = *reinterpret_cast<const v4i*>(smem + (size_t)ck * 32), a_hi = *reinterpret_cast<const v4i*>(smem + (size_t)ck * 32 + 16);
@@ -369,10 +365,10 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
         } else {
           part = dot16(buf[u], *reinterpret_cast<const v4i*>(smem + (size_t)ck * 16), 0);
         }
-        if (PAIRED && c >= kchunks) acc1 += part;
+        if (GATE && c >= kchunks) acc1 += part;
         else acc0 += part;
         if (j2 == cpl - 1) {                                     // logical row slot t2 complete
-          const int s0 = wave_sum_dpp(acc0), s1 = PAIRED ? wave_sum_dpp(acc1) : 0;
+          const int s0 = wave_sum_dpp(acc0), s1 = GATE ? wave_sum_dpp(acc1) : 0;
           acc0 = acc1 = 0;
           if (lane == t2) {                                      // lane t keeps the contraction(s) of row slot t
             sum0 = s0;
@@ -395,9 +391,9 @@ __global__ void __launch_bounds__(DG_THREADS) decode_gemv_kernel(const mq_decode
       const int tt = (int)((unsigned)sum0 - (unsigned)p_zp[0] * (unsigned)rs + (unsigned)p_ct[0]);
       e0 = __fadd_rn(__fmul_rn((float)tt, p_alpha[0]), p_bias[0]);
     }
-    if constexpr (PAIRED) {
-      const int tt = (int)((unsigned)sum1 - (unsigned)p_zp[PAIRED ? 1 : 0] * (unsigned)rs + (unsigned)p_ct[PAIRED ? 1 : 0]);
-      e1 = __fadd_rn(__fmul_rn((float)tt, p_alpha[PAIRED ? 1 : 0]), p_bias[PAIRED ? 1 : 0]);
+    if constexpr (GATE) {
+      const int tt = (int)((unsigned)sum1 - (unsigned)p_zp[GATE ? 1 : 0] * (unsigned)rs + (unsigned)p_ct[GATE ? 1 : 0]);
+      e1 = __fadd_rn(__fmul_rn((float)tt, p_alpha[GATE ? 1 : 0]), p_bias[GATE ? 1 : 0]);
     }
     if constexpr (GATE) {
       const float fa = out_q(og0, e0), fb = out_q(og1, e1);
@@ -1153,19 +1149,9 @@ int mq_decode_gemv_geometry(const mq_decode_gemv_args* args, int64_t* workgroups
 int mq_decode_gemv(const mq_decode_gemv_args* args, mq_stream_t stream) {
   MQ_REQUIRE(args != nullptr, "mq_decode_gemv: null argument block");
   const mq_decode_gemv_args& g = *args;
-  MQ_REQUIRE(g.w && g.alpha && g.w_zp && g.col_term && (g.x || g.xq), "mq_decode_gemv: null pointer");
-  MQ_REQUIRE(g.consts != nullptr && aligned(g.consts, 16), "mq_decode_gemv: consts (64 floats: mq_decode_pack_grids of this launch's 8 grids, zero padded) is required");
-  MQ_REQUIRE(g.xq || g.K <= DG_XPRE * 4 * DG_PRO * 64, "mq_decode_gemv: K=%d exceeds the fp32 activation row the prologue waves hold in registers (8192)", g.K);
-  MQ_REQUIRE(g.K > 0 && g.K % 256 == 0 && g.K <= 32768 && g.N > 0, "mq_decode_gemv: K=%d must be a positive multiple of 256 (<= 32768), N=%d", g.K, g.N);
-  MQ_REQUIRE(g.xq || (g.a_grid.scale && g.a_grid.offset && g.a_grid.qmin == 0.f && g.a_grid.qmax == 255.f),
-             "mq_decode_gemv: fp32 activations need an 8-bit unsigned activation grid");
-  MQ_REQUIRE(aligned(g.w, 16) && (!g.x || aligned(g.x, 16)) && (!g.xq || aligned(g.xq, 4)) && (!g.norm_w || aligned(g.norm_w, 16)),
-             "mq_decode_gemv: pointers must be 16-byte aligned");
+  MQ_REQUIRE(g.alpha && g.w_zp && g.col_term, "mq_decode_gemv: null pointer");
+  if (const int rc = check_gemv("mq_decode_gemv", g, 1, 0, 0, 0, true)) return rc;
   const bool gate = g.gate_q != nullptr, opre = g.o_acc != nullptr;
-  MQ_REQUIRE(gate || g.y, "mq_decode_gemv: no output");
-  MQ_REQUIRE(!gate || (g.norm_w && !g.xq), "mq_decode_gemv: gate mode is served for the norm-fused prologue (fp32 x + norm_w)");
-  MQ_REQUIRE(!gate || (g.N % 2 == 0 && g.gate_out.scale && g.out_grid[0].scale && g.out_grid[1].scale && (g.gate_act == 0 || g.gate_act == 1)),
-             "mq_decode_gemv: gate mode needs an even N (interleaved w1 / w3 rows), both output grids and the w2 input grid");
   MQ_REQUIRE(!g.zero_acc || (g.zero_n > 0 && aligned(g.zero_acc, 4)), "mq_decode_gemv: zero_acc needs zero_n > 0");
   MQ_REQUIRE(!opre || (gate && g.o_alpha && g.o_ct && g.x_mid && g.K <= 2 * 4 * DG_PRO * 64 && aligned(g.o_acc, 16) && aligned(g.o_alpha, 16) &&
                        aligned(g.o_ct, 16) && aligned(g.x_mid, 16) && (!g.o_bias || aligned(g.o_bias, 16))),
@@ -1176,34 +1162,18 @@ int mq_decode_gemv(const mq_decode_gemv_args* args, mq_stream_t stream) {
   const size_t lds = (size_t)g.K + 64;
   hipStream_t st = as_stream(stream);
   unsigned long long* stamps = STAMP_SLOT(gate ? 1 : (g.norm_w ? 0 : (g.xq ? 3 : 2)), grid);
-  const int xmode = g.xq ? XM_I8 : (g.norm_w ? (g.layernorm ? XM_LNORM : XM_NORM) : XM_F32);
-  MQ_REQUIRE(!g.norm_bias || (g.layernorm && aligned(g.norm_bias, 16)), "mq_decode_gemv: norm_bias belongs to the LayerNorm prologue (layernorm = 1), 16-byte aligned");
-#define MQ_DG_LAUNCH(XM, PR, W4, OP)                                                                                   \
-  decode_gemv_kernel<XM, PR, W4, OP><<<grid, DG_THREADS, lds, st>>>(g, rows_per_wg, stamps)
-#define MQ_DG_LAUNCH_W4(XM, PR, OP)                    \
-  do {                                                 \
-    if (g.w4) MQ_DG_LAUNCH(XM, PR, true, OP);          \
-    else MQ_DG_LAUNCH(XM, PR, false, OP);              \
-  } while (0)
-  if (gate && opre) {
-    if (xmode == XM_LNORM) MQ_DG_LAUNCH_W4(XM_LNORM, PAIR_GATE, true);
-    else MQ_DG_LAUNCH_W4(XM_NORM, PAIR_GATE, true);
-  } else if (gate) {
-    if (xmode == XM_LNORM) MQ_DG_LAUNCH_W4(XM_LNORM, PAIR_GATE, false);
-    else MQ_DG_LAUNCH_W4(XM_NORM, PAIR_GATE, false);
-  } else if (xmode == XM_LNORM) {
-    MQ_DG_LAUNCH_W4(XM_LNORM, PAIR_NONE, false);
-  } else if (xmode == XM_NORM) {
-    MQ_DG_LAUNCH_W4(XM_NORM, PAIR_NONE, false);
-  } else if (xmode == XM_F32) {
-    MQ_DG_LAUNCH_W4(XM_F32, PAIR_NONE, false);
-  } else {
-    MQ_DG_LAUNCH_W4(XM_I8, PAIR_NONE, false);
-  }
-#undef MQ_DG_LAUNCH_W4
-#undef MQ_DG_LAUNCH
-  MQ_LAUNCH_CHECK("mq_decode_gemv");
-  return MQ_OK;
+  return gemv_dispatch(gemv_xmode(g), gate, g.w4, [&](auto xm, auto gt, auto w4) -> int {
+    constexpr int XM = decltype(xm)::value;
+    constexpr bool GT = decltype(gt)::value, W4 = decltype(w4)::value;
+    if constexpr (GT) {                                            // OPRE: the gate launch of the four-launch chain
+      if (opre) decode_gemv_kernel<XM, true, W4, true><<<grid, DG_THREADS, lds, st>>>(g, rows_per_wg, stamps);
+      else decode_gemv_kernel<XM, true, W4, false><<<grid, DG_THREADS, lds, st>>>(g, rows_per_wg, stamps);
+    } else {
+      decode_gemv_kernel<XM, false, W4, false><<<grid, DG_THREADS, lds, st>>>(g, rows_per_wg, stamps);
+    }
+    MQ_LAUNCH_CHECK("mq_decode_gemv");
+    return MQ_OK;
+  });
 }
 
 // ---- the largest cache_len the four-launch attention serves: LDS per workgroup on gfx950 (160 KiB) = static + dynamic LDS ------------

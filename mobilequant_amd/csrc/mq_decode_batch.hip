@@ -15,7 +15,6 @@ namespace mq {
 #pragma clang fp contract(off)
 
 constexpr int DB_INFLIGHT = 12;      // weight chunks per lane in flight, as decode_gemv_kernel
-constexpr int DB_MAX_IMAGE = 128 * 1024;
 
 // ---- weight stream x B activation rows ---------------------------------------------------------------------------------------------
 // Roles, barriers, geometry and epilogue as decode_gemv_kernel (mq_decode.hip): PROLOGUE waves 0 .. DG_PRO-1 build the images, STREAM
@@ -395,63 +394,27 @@ int mq_decode_gemv_batch(const mq_decode_gemv_batch_args* args, mq_stream_t stre
   const mq_decode_gemv_args& g = args->g;
   const int B = args->batch;
   MQ_REQUIRE(B >= 1 && B <= MQ_DECODE_MAX_BATCH, "mq_decode_gemv_batch: batch=%d outside 1..%d", B, MQ_DECODE_MAX_BATCH);
-  MQ_REQUIRE(g.w && g.alpha && g.w_zp && g.col_term && (g.x || g.xq), "mq_decode_gemv_batch: null pointer");
-  MQ_REQUIRE(g.consts != nullptr && aligned(g.consts, 16), "mq_decode_gemv_batch: consts (mq_decode_pack_grids of this launch's grids) is required, 16-byte aligned");
-  MQ_REQUIRE(g.K > 0 && g.K % 256 == 0 && g.K <= 32768 && g.N > 0, "mq_decode_gemv_batch: K=%d must be a positive multiple of 256 (<= 32768), N=%d", g.K, g.N);
+  MQ_REQUIRE(g.alpha && g.w_zp && g.col_term, "mq_decode_gemv_batch: null pointer");
+  if (const int rc = check_gemv("mq_decode_gemv_batch", g, B, args->x_stride, args->y_stride, args->gate_stride, false)) return rc;
   MQ_REQUIRE((int64_t)B * g.K <= DB_MAX_IMAGE, "mq_decode_gemv_batch: batch * K = %lld exceeds the %d bytes of int8 images the workgroup holds in LDS",
              (long long)B * g.K, DB_MAX_IMAGE);
-  MQ_REQUIRE(g.xq || g.K <= DG_XPRE * 4 * DG_PRO * 64, "mq_decode_gemv_batch: K=%d exceeds the fp32 activation row the prologue serves (8192)", g.K);
   MQ_REQUIRE(!g.zero_acc && !g.o_acc, "mq_decode_gemv_batch: zero_acc / o_acc (the four-launch chain) are not served by the batched launch");
-  MQ_REQUIRE(g.xq || (g.a_grid.scale && g.a_grid.offset && g.a_grid.qmin == 0.f && g.a_grid.qmax == 255.f),
-             "mq_decode_gemv_batch: fp32 activations need an 8-bit unsigned activation grid");
-  MQ_REQUIRE(args->x_stride >= (B > 1 ? g.K : 0) && args->x_stride % 16 == 0 && aligned(g.w, 16) && (!g.x || aligned(g.x, 16)) &&
-                 (!g.xq || aligned(g.xq, 16)) && (!g.norm_w || aligned(g.norm_w, 16)),
-             "mq_decode_gemv_batch: pointers must be 16-byte aligned and x_stride a multiple of 16 covering K");
   const bool gate = g.gate_q != nullptr;
-  MQ_REQUIRE(gate || g.y, "mq_decode_gemv_batch: no output");
-  MQ_REQUIRE(!gate || (g.norm_w && !g.xq), "mq_decode_gemv_batch: gate mode is served for the norm-fused prologue (fp32 x + norm_w)");
-  MQ_REQUIRE(!gate || (g.N % 2 == 0 && g.gate_out.scale && g.out_grid[0].scale && g.out_grid[1].scale && (g.gate_act == 0 || g.gate_act == 1)),
-             "mq_decode_gemv_batch: gate mode needs an even N (interleaved w1 / w3 rows), both output grids and the w2 input grid");
-  const int NLr = gate ? g.N / 2 : g.N;
-  MQ_REQUIRE(B == 1 || ((!g.y || args->y_stride >= NLr) && (!g.resid || args->y_stride >= NLr) && (!gate || args->gate_stride >= NLr)),
-             "mq_decode_gemv_batch: y_stride / gate_stride must cover a row (%d)", NLr);
-  MQ_REQUIRE(!g.norm_bias || (g.layernorm && aligned(g.norm_bias, 16)), "mq_decode_gemv_batch: norm_bias belongs to the LayerNorm prologue (layernorm = 1), 16-byte aligned");
   int rows_per_wg;
   unsigned grid;
-  gemv_row_geometry(NLr, &rows_per_wg, &grid);
+  gemv_row_geometry(gate ? g.N / 2 : g.N, &rows_per_wg, &grid);
   const size_t lds = (size_t)B * g.K;
   hipStream_t st = as_stream(stream);
-  const int xmode = g.xq ? XM_I8 : (g.norm_w ? (g.layernorm ? XM_LNORM : XM_NORM) : XM_F32);
-  // instantiation index: xmode (4) x gate (2) x w4 (2)
-  static std::atomic<size_t> lds_set[16][kMaxDevices];
-  const int ki = (xmode * 2 + (gate ? 1 : 0)) * 2 + (g.w4 ? 1 : 0);
-#define MQ_DB_LAUNCH(XM, GT, W4)                                                                                            \
-  do {                                                                                                                      \
-    const int rc = set_lds(reinterpret_cast<const void*>(decode_gemv_batch_kernel<XM, GT, W4>), lds_set[ki], lds, "mq_decode_gemv_batch"); \
-    if (rc != MQ_OK) return rc;                                                                                             \
-    decode_gemv_batch_kernel<XM, GT, W4><<<grid, DG_THREADS, lds, st>>>(*args, rows_per_wg);                                \
-  } while (0)
-#define MQ_DB_LAUNCH_W4(XM, GT)                 \
-  do {                                          \
-    if (g.w4) MQ_DB_LAUNCH(XM, GT, true);       \
-    else MQ_DB_LAUNCH(XM, GT, false);           \
-  } while (0)
-  if (gate) {
-    if (xmode == XM_LNORM) MQ_DB_LAUNCH_W4(XM_LNORM, true);
-    else MQ_DB_LAUNCH_W4(XM_NORM, true);
-  } else if (xmode == XM_LNORM) {
-    MQ_DB_LAUNCH_W4(XM_LNORM, false);
-  } else if (xmode == XM_NORM) {
-    MQ_DB_LAUNCH_W4(XM_NORM, false);
-  } else if (xmode == XM_F32) {
-    MQ_DB_LAUNCH_W4(XM_F32, false);
-  } else {
-    MQ_DB_LAUNCH_W4(XM_I8, false);
-  }
-#undef MQ_DB_LAUNCH_W4
-#undef MQ_DB_LAUNCH
-  MQ_LAUNCH_CHECK("mq_decode_gemv_batch");
-  return MQ_OK;
+  const int xmode = gemv_xmode(g);
+  static std::atomic<size_t> lds_set[16][kMaxDevices];            // per instantiation: xmode (4) x gate (2) x w4 (2)
+  std::atomic<size_t>* const lds_cache = lds_set[gemv_kernel_index(xmode, gate, g.w4)];
+  return gemv_dispatch(xmode, gate, g.w4, [&](auto xm, auto gt, auto w4) -> int {
+    const auto kernel = decode_gemv_batch_kernel<decltype(xm)::value, decltype(gt)::value, decltype(w4)::value>;
+    if (const int rc = set_lds(reinterpret_cast<const void*>(kernel), lds_cache, lds, "mq_decode_gemv_batch")) return rc;
+    kernel<<<grid, DG_THREADS, lds, st>>>(*args, rows_per_wg);
+    MQ_LAUNCH_CHECK("mq_decode_gemv_batch");
+    return MQ_OK;
+  });
 }
 
 int mq_decode_attention_batch(const mq_decode_attention_batch_args* args, mq_stream_t stream) {

@@ -1,8 +1,10 @@
 // Device helpers shared by the single-sequence decode kernels (mq_decode.hip), the batched ones (mq_decode_batch.hip), the grouped
 // GEMV (mq_decode_grouped.hip) and the multi-token / ragged attention (mq_decode_rows.hip): the
-// launch-constants line, the layout constants the families agree on, the batched GEMV's prologue and epilogue and the GEMV launches'
-// row geometry.  The five-launch attention's phases build on this header in mq_decode_attention.h.
+// launch-constants line, the layout constants the families agree on, the batched GEMV's prologue and epilogue and, on the host, what
+// the three GEMV entries share: their argument checks (check_gemv), the dispatch over instantiations (gemv_dispatch) and the row
+// geometry.  The five-launch attention's phases build on this header in mq_decode_attention.h.
 #pragma once
+#include <type_traits>
 #include "mq_common.h"
 
 namespace mq {
@@ -341,6 +343,60 @@ inline int gemv_row_geometry(int NL, int* rows_per_wg, unsigned* grid) {
   *grid = (unsigned)((NL + rpw - 1) / rpw);
   return NL;
 }
+
+// What mq_decode_gemv, mq_decode_gemv_batch and mq_decode_gemv_grouped all require of the argument block g and its B rows at
+// x_stride / y_stride / gate_stride, refused under the entry's name `who`.  `single`: mq_decode_gemv, whose rows have no strides --
+// three messages keep its wording, and its int8 image is copied in 4-byte pieces.  The entry's own conditions (the per-channel or
+// per-group vectors, zero_acc / o_acc, the LDS bound of B images, the group size) stay at the entry, behind these.
+inline int check_gemv(const char* who, const mq_decode_gemv_args& g, const int B, const int64_t x_stride, const int64_t y_stride, const int64_t gate_stride,
+                      const bool single) {
+  MQ_REQUIRE(g.w && (g.x || g.xq), "%s: null pointer", who);
+  MQ_REQUIRE(g.consts != nullptr && aligned(g.consts, 16),
+             single ? "%s: consts (64 floats: mq_decode_pack_grids of this launch's 8 grids, zero padded) is required"
+                    : "%s: consts (mq_decode_pack_grids of this launch's grids) is required, 16-byte aligned", who);
+  MQ_REQUIRE(g.K > 0 && g.K % 256 == 0 && g.K <= 32768 && g.N > 0, "%s: K=%d must be a positive multiple of 256 (<= 32768), N=%d", who, g.K, g.N);
+  MQ_REQUIRE(g.xq || g.K <= DG_XPRE * 4 * DG_PRO * 64,
+             single ? "%s: K=%d exceeds the fp32 activation row the prologue waves hold in registers (8192)"
+                    : "%s: K=%d exceeds the fp32 activation row the prologue serves (8192)", who, g.K);
+  MQ_REQUIRE(g.xq || (g.a_grid.scale && g.a_grid.offset && g.a_grid.qmin == 0.f && g.a_grid.qmax == 255.f),
+             "%s: fp32 activations need an 8-bit unsigned activation grid", who);
+  MQ_REQUIRE(x_stride >= (B > 1 ? g.K : 0) && x_stride % 16 == 0 && aligned(g.w, 16) && (!g.x || aligned(g.x, 16)) &&
+                 (!g.xq || aligned(g.xq, single ? 4 : 16)) && (!g.norm_w || aligned(g.norm_w, 16)),
+             single ? "%s: pointers must be 16-byte aligned" : "%s: pointers must be 16-byte aligned and x_stride a multiple of 16 covering K", who);
+  const bool gate = g.gate_q != nullptr;
+  MQ_REQUIRE(gate || g.y, "%s: no output", who);
+  MQ_REQUIRE(!gate || (g.norm_w && !g.xq), "%s: gate mode is served for the norm-fused prologue (fp32 x + norm_w)", who);
+  MQ_REQUIRE(!gate || (g.N % 2 == 0 && g.gate_out.scale && g.out_grid[0].scale && g.out_grid[1].scale && (g.gate_act == 0 || g.gate_act == 1)),
+             "%s: gate mode needs an even N (interleaved w1 / w3 rows), both output grids and the w2 input grid", who);
+  const int NLr = gate ? g.N / 2 : g.N;
+  MQ_REQUIRE(B == 1 || ((!g.y || y_stride >= NLr) && (!g.resid || y_stride >= NLr) && (!gate || gate_stride >= NLr)),
+             "%s: y_stride / gate_stride must cover a row (%d)", who, NLr);
+  MQ_REQUIRE(!g.norm_bias || (g.layernorm && aligned(g.norm_bias, 16)), "%s: norm_bias belongs to the LayerNorm prologue (layernorm = 1), 16-byte aligned", who);
+  return MQ_OK;
+}
+
+constexpr int DB_MAX_IMAGE = 128 * 1024;   // B * K int8 images in LDS (the batched and the grouped launch)
+
+inline int gemv_xmode(const mq_decode_gemv_args& g) { return g.xq ? XM_I8 : (g.norm_w ? (g.layernorm ? XM_LNORM : XM_NORM) : XM_F32); }
+
+// (xmode, gate, w4) of a launch as compile-time constants: launch(XM, GATE, W4) is called with std::integral_constant values.  Gate
+// launches exist for the two norm prologues only (check_gemv), so an entry instantiates 12 kernels per further flag of its own.
+template <class Launch>
+inline int gemv_dispatch(const int xmode, const bool gate, const bool w4, Launch&& launch) {
+  auto with_w4 = [&](auto xm, auto gt) { return w4 ? launch(xm, gt, std::true_type{}) : launch(xm, gt, std::false_type{}); };
+  if (gate) {
+    if (xmode == XM_LNORM) return with_w4(std::integral_constant<int, XM_LNORM>{}, std::true_type{});
+    return with_w4(std::integral_constant<int, XM_NORM>{}, std::true_type{});
+  }
+  switch (xmode) {
+    case XM_LNORM: return with_w4(std::integral_constant<int, XM_LNORM>{}, std::false_type{});
+    case XM_NORM: return with_w4(std::integral_constant<int, XM_NORM>{}, std::false_type{});
+    case XM_F32: return with_w4(std::integral_constant<int, XM_F32>{}, std::false_type{});
+    default: return with_w4(std::integral_constant<int, XM_I8>{}, std::false_type{});
+  }
+}
+// index of an instantiation in an entry's set_lds cache
+inline int gemv_kernel_index(const int xmode, const bool gate, const bool w4) { return (xmode * 2 + (gate ? 1 : 0)) * 2 + (w4 ? 1 : 0); }
 
 // raise a kernel's dynamic-LDS ceiling once per device (above the default 64 KiB)
 inline int set_lds(const void* fn, std::atomic<size_t>* cache, size_t lds, const char* name) {

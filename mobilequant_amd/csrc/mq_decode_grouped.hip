@@ -27,7 +27,6 @@ namespace mq {
 // gate launch's W4 instantiation at 128 VGPRs)
 template <int NB>
 constexpr int dgr_inflight() { return NB == 1 ? 12 : 6; }
-constexpr int DGR_MAX_IMAGE = 128 * 1024;   // B * K int8 images in LDS, as mq_decode_gemv_batch
 
 // sum over aligned groups of 2^lg adjacent lanes (lg <= 6, wave-uniform): wave_sum_dpp's steps, stopped where the group ends.  The
 // group's sum is valid in its LAST lane (every lane of it for lg <= 4; lanes 16..31 / 48..63 for lg = 5; lane 63 for lg = 6).
@@ -219,75 +218,37 @@ int mq_decode_gemv_grouped(const mq_decode_gemv_grouped_args* args, mq_stream_t 
   const mq_decode_gemv_args& g = ba.g;
   const int B = ba.batch, gs = args->group_size;
   MQ_REQUIRE(B >= 1 && B <= MQ_DECODE_MAX_BATCH, "mq_decode_gemv_grouped: batch=%d outside 1..%d", B, MQ_DECODE_MAX_BATCH);
-  MQ_REQUIRE(g.w && args->alpha && args->cw && args->t && (g.x || g.xq), "mq_decode_gemv_grouped: null pointer");
-  MQ_REQUIRE(g.consts != nullptr && aligned(g.consts, 16), "mq_decode_gemv_grouped: consts (mq_decode_pack_grids of this launch's grids) is required, 16-byte aligned");
-  MQ_REQUIRE(g.K > 0 && g.K % 256 == 0 && g.K <= 32768 && g.N > 0, "mq_decode_gemv_grouped: K=%d must be a positive multiple of 256 (<= 32768), N=%d", g.K, g.N);
+  MQ_REQUIRE(args->alpha && args->cw && args->t, "mq_decode_gemv_grouped: null pointer");
+  if (const int rc = check_gemv("mq_decode_gemv_grouped", g, B, ba.x_stride, ba.y_stride, ba.gate_stride, false)) return rc;
   MQ_REQUIRE(gs >= 64 && gs % 64 == 0 && g.K % gs == 0, "mq_decode_gemv_grouped: group_size=%d must be a multiple of 64 that divides K=%d", gs, g.K);
   if ((gs & (gs - 1)) != 0) {
     set_error("mq_decode_gemv_grouped: group_size=%d is not a power of two (a group must be whole lanes of a pass or whole passes)", gs);
     return MQ_EUNSUPPORTED;
   }
-  MQ_REQUIRE((int64_t)B * g.K <= DGR_MAX_IMAGE, "mq_decode_gemv_grouped: batch * K = %lld exceeds the %d bytes of int8 images the workgroup holds in LDS",
-             (long long)B * g.K, DGR_MAX_IMAGE);
+  MQ_REQUIRE((int64_t)B * g.K <= DB_MAX_IMAGE, "mq_decode_gemv_grouped: batch * K = %lld exceeds the %d bytes of int8 images the workgroup holds in LDS",
+             (long long)B * g.K, DB_MAX_IMAGE);
   MQ_REQUIRE((int64_t)(g.K / gs) * g.N < (1ll << 31), "mq_decode_gemv_grouped: the [G, N] group vectors are too large");
-  MQ_REQUIRE(g.xq || g.K <= DG_XPRE * 4 * DG_PRO * 64, "mq_decode_gemv_grouped: K=%d exceeds the fp32 activation row the prologue serves (8192)", g.K);
   MQ_REQUIRE(!g.zero_acc && !g.o_acc, "mq_decode_gemv_grouped: zero_acc / o_acc (the four-launch chain) are not served by the grouped launch");
-  MQ_REQUIRE(g.xq || (g.a_grid.scale && g.a_grid.offset && g.a_grid.qmin == 0.f && g.a_grid.qmax == 255.f),
-             "mq_decode_gemv_grouped: fp32 activations need an 8-bit unsigned activation grid");
-  MQ_REQUIRE(ba.x_stride >= (B > 1 ? g.K : 0) && ba.x_stride % 16 == 0 && aligned(g.w, 16) && (!g.x || aligned(g.x, 16)) &&
-                 (!g.xq || aligned(g.xq, 16)) && (!g.norm_w || aligned(g.norm_w, 16)) && aligned(args->alpha, 16) && aligned(args->cw, 16) &&
-                 aligned(args->t, 16),
+  MQ_REQUIRE(aligned(args->alpha, 16) && aligned(args->cw, 16) && aligned(args->t, 16),
              "mq_decode_gemv_grouped: pointers must be 16-byte aligned and x_stride a multiple of 16 covering K");
   const bool gate = g.gate_q != nullptr;
-  MQ_REQUIRE(gate || g.y, "mq_decode_gemv_grouped: no output");
-  MQ_REQUIRE(!gate || (g.norm_w && !g.xq), "mq_decode_gemv_grouped: gate mode is served for the norm-fused prologue (fp32 x + norm_w)");
-  MQ_REQUIRE(!gate || (g.N % 2 == 0 && g.gate_out.scale && g.out_grid[0].scale && g.out_grid[1].scale && (g.gate_act == 0 || g.gate_act == 1)),
-             "mq_decode_gemv_grouped: gate mode needs an even N (interleaved w1 / w3 rows), both output grids and the w2 input grid");
-  const int NLr = gate ? g.N / 2 : g.N;
-  MQ_REQUIRE(B == 1 || ((!g.y || ba.y_stride >= NLr) && (!g.resid || ba.y_stride >= NLr) && (!gate || ba.gate_stride >= NLr)),
-             "mq_decode_gemv_grouped: y_stride / gate_stride must cover a row (%d)", NLr);
-  MQ_REQUIRE(!g.norm_bias || (g.layernorm && aligned(g.norm_bias, 16)), "mq_decode_gemv_grouped: norm_bias belongs to the LayerNorm prologue (layernorm = 1), 16-byte aligned");
   int rows_per_wg;
   unsigned grid;
-  gemv_row_geometry(NLr, &rows_per_wg, &grid);
+  gemv_row_geometry(gate ? g.N / 2 : g.N, &rows_per_wg, &grid);
   const size_t lds = (size_t)B * g.K;
   hipStream_t st = as_stream(stream);
-  const int xmode = g.xq ? XM_I8 : (g.norm_w ? (g.layernorm ? XM_LNORM : XM_NORM) : XM_F32);
-  // instantiation index: xmode (4) x gate (2) x w4 (2) x (B == 1) (2)
-  static std::atomic<size_t> lds_set[32][kMaxDevices];
-  const int ki = ((xmode * 2 + (gate ? 1 : 0)) * 2 + (g.w4 ? 1 : 0)) * 2 + (B == 1 ? 1 : 0);
-#define MQ_DGR_LAUNCH(XM, GT, W4, NB)                                                                                        \
-  do {                                                                                                                      \
-    const int rc = set_lds(reinterpret_cast<const void*>(decode_gemv_grouped_kernel<XM, GT, W4, NB>), lds_set[ki], lds, "mq_decode_gemv_grouped"); \
-    if (rc != MQ_OK) return rc;                                                                                             \
-    decode_gemv_grouped_kernel<XM, GT, W4, NB><<<grid, DG_THREADS, lds, st>>>(*args, rows_per_wg);                           \
-  } while (0)
-#define MQ_DGR_LAUNCH_W4(XM, GT)                                          \
-  do {                                                                    \
-    if (B == 1) {                                                         \
-      if (g.w4) MQ_DGR_LAUNCH(XM, GT, true, 1);                           \
-      else MQ_DGR_LAUNCH(XM, GT, false, 1);                               \
-    } else {                                                              \
-      if (g.w4) MQ_DGR_LAUNCH(XM, GT, true, DB_MAXB);                     \
-      else MQ_DGR_LAUNCH(XM, GT, false, DB_MAXB);                         \
-    }                                                                     \
-  } while (0)
-  if (gate) {
-    if (xmode == XM_LNORM) MQ_DGR_LAUNCH_W4(XM_LNORM, true);
-    else MQ_DGR_LAUNCH_W4(XM_NORM, true);
-  } else if (xmode == XM_LNORM) {
-    MQ_DGR_LAUNCH_W4(XM_LNORM, false);
-  } else if (xmode == XM_NORM) {
-    MQ_DGR_LAUNCH_W4(XM_NORM, false);
-  } else if (xmode == XM_F32) {
-    MQ_DGR_LAUNCH_W4(XM_F32, false);
-  } else {
-    MQ_DGR_LAUNCH_W4(XM_I8, false);
-  }
-#undef MQ_DGR_LAUNCH_W4
-#undef MQ_DGR_LAUNCH
-  MQ_LAUNCH_CHECK("mq_decode_gemv_grouped");
-  return MQ_OK;
+  const int xmode = gemv_xmode(g);
+  static std::atomic<size_t> lds_set[32][kMaxDevices];            // per instantiation: xmode (4) x gate (2) x w4 (2) x (B == 1) (2)
+  std::atomic<size_t>* const lds_cache = lds_set[gemv_kernel_index(xmode, gate, g.w4) * 2 + (B == 1 ? 1 : 0)];
+  return gemv_dispatch(xmode, gate, g.w4, [&](auto xm, auto gt, auto w4) -> int {
+    constexpr int XM = decltype(xm)::value;
+    constexpr bool GT = decltype(gt)::value, W4 = decltype(w4)::value;
+    const auto kernel = B == 1 ? decode_gemv_grouped_kernel<XM, GT, W4, 1> : decode_gemv_grouped_kernel<XM, GT, W4, DB_MAXB>;
+    if (const int rc = set_lds(reinterpret_cast<const void*>(kernel), lds_cache, lds, "mq_decode_gemv_grouped")) return rc;
+    kernel<<<grid, DG_THREADS, lds, st>>>(*args, rows_per_wg);
+    MQ_LAUNCH_CHECK("mq_decode_gemv_grouped");
+    return MQ_OK;
+  });
 }
 
 }  // extern "C"

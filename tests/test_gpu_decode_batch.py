@@ -396,6 +396,28 @@ def test_gemv_batch_launch_is_the_single_launch_per_row_in_every_mode(dev):
         _assert_same(outs, (geom, "fp32"))
 
 
+@pytest.mark.parametrize("geom", ["llama", "stablelm"])
+def test_gemv_batch_launch_is_the_single_launch_on_a_partial_last_pass_and_a_ragged_last_workgroup(dev, geom):
+    """K = 2304 is 144 16-byte chunks per weight row (288 per w1|w3 pair, 72 / 144 packed): the last 64-chunk pass of a logical row is
+    partial in every mode, and 257 logical rows leave the last workgroup short.  The q|k|v, the gated w1|w3 and the int8-input record,
+    W8 and W4, at B = 3 and B = 8, row by row against mq_decode_gemv."""
+    from mobilequant_amd.decode_batch import BatchDecodeEngine
+    gen = torch.Generator().manual_seed(1)
+    keep = []
+    be = BatchDecodeEngine(_model(dev, geom, 1, 8), 1, cache_len=64)
+    K, NL = 2304, 257
+    assert be.phases[3][1].g.gate_q and be.phases[4][1].g.xq and not be.phases[0][1].g.gate_q
+    for name, rec in (("qkv", be.phases[0][1]), ("w13", be.phases[3][1]), ("w2", be.phases[4][1])):
+        for w4 in (False, True):
+            for B in (3, 8):
+                ba = _clone_struct(rec)
+                ba.batch = B
+                gate = bool(ba.g.gate_q)
+                _random_linear(ba, K, 2 * NL if gate else NL, w4, gen, dev, keep)
+                outs = _gemv_rows(ba, B, NL, NL, K, not ba.g.xq, dev, gen, keep)
+                _assert_same(outs, (geom, name, w4, B))
+
+
 @pytest.mark.parametrize("geom", ["llama", "stablelm", "gemma"])
 def test_attention_batch_launch_is_the_single_launch_per_sequence(dev, geom):
     """Different positions per sequence -- 0, block edges, the split threshold, cache_len - 1 and the idle sentinel -- in one launch:
