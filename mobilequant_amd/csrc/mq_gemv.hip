@@ -1,8 +1,18 @@
 // Decode-shape QLinear (M <= 8 tokens): int8 GEMV, weight-streaming.
 //
-// Same arithmetic and epilogue as the MFMA GEMM (mq_gemm.hip):
-//   out[m,n] = alpha[n] * ( sum_k a[m,k]*w[n,k] - w_zp[n]*a_rowsum[m] + col_term[n] ) + bias[n]  (+ output quantizer)
-// but at M = 1 the matrix cores would idle on a 16-row tile, and every weight byte is used once per
+// The same linear as the MFMA GEMM (mq_gemm.hip), in its own fixed sequence of correctly rounded operations (pinned bit for bit by
+// oracle.linear_gemv_launch / tests/test_gpu_linear_gemv.py):
+//   tt = sum_k a[m,k]*w[n,k] - w_zp[n]*a_rowsum[m] + col_term[n]      int32, wrap-around; a_rowsum is the caller's word (0 when NULL),
+//                                                                      or the sum of the image the fused quantize (FUSEQ) stores
+//   f  = fl(fl(float(tt) * alpha[n]) + bias[n])                        int32 -> fp32 to nearest even, a multiply, an add: no fma
+//   no grid:  f (f32), or f rounded once more (f16)
+//   grid:     q = fl(rint(fl(f * fl(1 / s))) + o),  q = fminf(fmaxf(q, qmin), qmax),  then the index or fl(fl(q - o) * s)
+// Without a grid this IS the GEMM's epilogue.  With one it is not: the GEMM folds alpha, the bias and (8-bit grids) the offset into
+// ONE fma in front of its rint, q = rint(fma(float(tt), fl(alpha * fl(1/s)), fl(bias * fl(1/s)) [+ o])) (oracle.prefill_gemm_epilogue).
+// The same QLinear row at M = 8 (here) and at M = 9 (there) can therefore land on neighbouring indices next to a rounding boundary,
+// and on an exact tie under an odd folded offset it always does ("The M = 8 / M = 9 seam").  The decode engines follow
+// THIS form by design (decode_gemv_epilogue): do not change it to the folded one.
+// At M = 1 the matrix cores would idle on a 16-row tile, and every weight byte is used once per
 // token, so the kernel is a stream of 16-byte weight loads straight into registers (no LDS round trip
 // for W: it is not shared between waves) feeding v_dot4_i32_i8.  Algorithmic bytes per token: N*K weight
 // bytes (+ K activation bytes, L2 resident).  TinyLlama-1.1B W8: 22 x 44.04 MB = 0.969 GB per token.

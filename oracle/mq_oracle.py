@@ -1917,3 +1917,96 @@ def grouped_linear(a, w, gs, a_gsum, alpha, cw, t, bias, mutation=None):
     if bias is not None:
         acc = (acc + np.asarray(bias, F32)[None, :]).astype(F32)
     return dict(out=acc, bracket=br)
+
+
+# ----------------------------------------------------------------------------------------------
+# a8 (pin)  the M <= 8 weight-streaming GEMV behind mq_w8a8_linear / mq_w4a8_linear and their _f32in forms (csrc/mq_gemv.hip)
+# ----------------------------------------------------------------------------------------------
+LINEAR_GEMV_MUTATIONS = ("fma", "divide", "half_up", "fold_offset", "gemm_form", "rowsum_recomputed")
+LINEAR_GEMV_MUTATION = None   # tests only (like QMATMUL_MUTATION): makes every call without its own `mutation` wrong on purpose
+
+
+def _contract_rows(image, w, w4=False, block=16384):
+    """Exact int64 [M, N] of image [M, K] . w[N, K]^T, in blocks of weight rows (a float64 product of integers below 2^53); w4: w is
+    pack_w4's image and is unpacked block by block."""
+    a = np.asarray(image).astype(np.float64)
+    assert a.shape[1] * 128 * 255 < 2 ** 53
+    out = np.empty((a.shape[0], w.shape[0]), np.int64)
+    for lo in range(0, w.shape[0], block):
+        wi = unpack_w4(w[lo:lo + block], 0) if w4 else w[lo:lo + block]
+        assert wi.shape[1] == a.shape[1]
+        out[:, lo:lo + block] = np.rint(a @ wi.astype(np.float64).T).astype(np.int64)
+    return out
+
+
+def linear_gemv_launch(w, alpha, w_zp, col_term, bias=None, a=None, a_rowsum=None, x=None, a_grid=None, w4=False, out_grid=None,
+                       out_dtype="f32", mutation=None):
+    """What one launch of gemv_i8_fat_kernel stores, op for op, knowing nothing of workgroups, waves or passes.
+      w         int8 [N, K] stored weights, or (w4) mq_pack_w4's image [N, K / 2]: the unsigned nibbles in pack_w4's layout
+      a         int8 [M, K] stored activation image (index - shift) with a_rowsum int32 [M] or None -- the int8 entry points.  The
+                kernel does NOT recompute the row sum: it takes the caller's word, and 0 when the pointer is NULL
+      x, a_grid fp32 [M, K] and (scale, offset, qmin, qmax, shift) -- the _f32in entry points: the image is quantize_storage's (STORAGE
+                form: IEEE x / s behind the guarded reciprocal, rint, + offset, fminf / fmaxf clamp, NaN and +-inf -> qmin) and the row
+                sum is the sum of that image
+      tt        wrap32(sum_k a[m, k] w[n, k] - w_zp[n] rs[m] + col_term[n]), the contraction exact
+      f         fl(fl(float(tt) alpha[n]) + bias[n]): int32 -> fp32 to nearest even, a rounded multiply, a rounded add (bias 0.0f when absent)
+      out_grid  None: f as f32, or rounded once more to f16.  (scale, offset, qmin, qmax): inv = fl(1 / scale), v = fl(f inv),
+                q = fl(rint(v) + offset), q = fminf(fmaxf(q, qmin), qmax) (a NaN operand dropped); storage u8 (uint8)(int)q, i8
+                (int)q - 128 on a grid that starts at 0 and (int)q otherwise (low byte), u16 / i16 the low 16 bits, f32 / f16
+                fl(fl(q - offset) scale), f16 rounded once more.
+    Returns dict(stored [M, N] in the storage type, tt int32, f fp32, v float64: the value in front of the rint (f without a grid), tie:
+    its distance to the nearest half-integer, image int8 [M, K], rs int64 [M]).
+    mutation (tests only, LINEAR_GEMV_MUTATIONS) makes it wrong on purpose: "fma" one fma for the multiply and the add; "divide" f / s
+    for f inv; "half_up" ties rounded half up; "fold_offset" rint(v + offset); "gemm_form" the prefill GEMM's folded epilogue
+    (prefill_gemm_epilogue on the same tt); "rowsum_recomputed" the image's true row sum for the caller's (or for 0 when it is NULL)."""
+    mutation = LINEAR_GEMV_MUTATION if mutation is None else mutation
+    assert mutation is None or mutation in LINEAR_GEMV_MUTATIONS, mutation
+    w = np.asarray(w)
+    assert w.ndim == 2 and w.dtype == (np.uint8 if w4 else np.int8)
+    N = w.shape[0]
+    if x is not None:
+        assert a is None and a_rowsum is None and a_grid is not None
+        s, o, qmin, qmax, shift = a_grid
+        stored_a, rs32 = quantize_storage(np.asarray(x, F32), F32(s), F32(o), int(qmin), int(qmax), int(shift))
+        assert stored_a.min() >= -128 and stored_a.max() <= 127, "index - shift has to fit int8"
+        image, rs = stored_a.astype(np.int8), rs32.astype(np.int64)
+    else:
+        image = np.asarray(a)
+        assert image.dtype == np.int8
+        rs = np.zeros(image.shape[0], np.int64) if a_rowsum is None else np.asarray(a_rowsum, np.int64)
+        if mutation == "rowsum_recomputed":
+            rs = image.astype(np.int64).sum(axis=1)
+    sums = _contract_rows(image, w, w4)
+    tt = _wrap32(sums - np.asarray(w_zp, np.int64)[None, :] * rs[:, None] + np.asarray(col_term, np.int64)[None, :])
+    tf = tt.astype(F32)                                            # int32 -> fp32, round to nearest even
+    al = np.broadcast_to(np.asarray(alpha, F32).reshape(1, N), tf.shape)
+    bs = np.broadcast_to((np.zeros(N, F32) if bias is None else np.asarray(bias, F32)).reshape(1, N), tf.shape)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = fma_f32(tf, al, bs) if mutation == "fma" else ((tf * al).astype(F32) + bs).astype(F32)
+        st = PREFILL_GEMM_STORAGE[out_dtype]
+        if out_grid is None:
+            assert out_dtype in ("f32", "f16")
+            v = f.astype(np.float64)
+            return dict(stored=f.astype(st), tt=tt, f=f, v=v, tie=_tie_dist(v), image=image, rs=rs)
+        so, oo, oqmin, oqmax = F32(out_grid[0]), F32(out_grid[1]), F32(out_grid[2]), F32(out_grid[3])
+        if mutation == "gemm_form":
+            stored, q, tie = prefill_gemm_epilogue(tt, alpha, bias, [(so, oo)], None, float(oqmin), float(oqmax), out_dtype)
+            return dict(stored=stored, tt=tt, f=f, v=q, tie=tie, image=image, rs=rs)
+        inv = (F32(1.0) / so).astype(F32)
+        vf = (f / so).astype(F32) if mutation == "divide" else (f * inv).astype(F32)
+        if mutation == "fold_offset":
+            q = np.rint((vf + oo).astype(F32)).astype(F32)
+        else:
+            q = ((_rint_half_up(vf) if mutation == "half_up" else np.rint(vf)) + oo).astype(F32)
+        q = np.fmin(np.fmax(q, oqmin), oqmax)
+        qi = q.astype(np.int64)
+        if out_dtype == "u8":
+            stored = (qi & 0xFF).astype(np.uint8)
+        elif out_dtype == "i8":
+            stored = ((qi - (128 if float(oqmin) == 0.0 else 0)) & 0xFF).astype(np.uint8).view(np.int8)
+        elif out_dtype in ("u16", "i16"):
+            stored = (qi & 0xFFFF).astype(np.uint16).view(st)
+        else:
+            stored = ((q - oo).astype(F32) * so).astype(F32).astype(st)
+    v = vf.astype(np.float64)
+    return dict(stored=stored, tt=tt, f=f, v=v, tie=_tie_dist(v), image=image, rs=rs)
