@@ -92,7 +92,7 @@ __device__ __forceinline__ void beam_finish(int row, int ns, const LpPart* part,
     if (g == 0ull) {                                                 // fewer than K entries (k >= V)
       if (tid == 0) list[r] = BeamEntry{0ull, -__builtin_inff(), 0};
     } else if (cur == g) {                                           // keys are distinct: one owner
-      list[r] = BeamEntry{g, lp_of(lp_key_value(g), m, log_s), 0};
+      list[r] = BeamEntry{g, lp_of(sort_key_value(g), m, log_s), 0};
       ++head;
       cur = head < a.K ? cand[tid * LP_MAX_TOP + head] : 0ull;
     }
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(LP_THREADS) void beam_groups_kernel(BeamArgs a) {
   if (mine != 0ull && rank < a.K) {
     a.cand_score[base + rank] = s;
     a.cand_row[base + rank] = r;
-    a.cand_token[base + rank] = lp_key_id(e.key);
+    a.cand_token[base + rank] = sort_key_id(e.key);
     a.cand_logprob[base + rank] = e.lp;
   }
   if (t < a.K && t >= n) {                                           // fewer than K candidates: the padding

@@ -180,6 +180,21 @@ __device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
   else atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
+// The (value, index) sort key of the selection kernels (mq_sample.hip, mq_logprob.hip, mq_beam.hip), for a value that is no NaN and an
+// index below 2^20: (monotone u32 of z) << 20 | (2^20 - 1 - i).  Keys are distinct and never 0, and their descending order is value
+// descending, ties by index ascending.
+constexpr unsigned long long SORT_KEY_IDX_MASK = (1ull << 20) - 1;
+__device__ __forceinline__ unsigned long long sort_key(float z, int i) {
+  const unsigned u = __float_as_uint(z);
+  const unsigned k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)k << 20) | (SORT_KEY_IDX_MASK - (unsigned long long)i);
+}
+__device__ __forceinline__ int sort_key_id(unsigned long long key) { return (int)(SORT_KEY_IDX_MASK - (key & SORT_KEY_IDX_MASK)); }
+__device__ __forceinline__ float sort_key_value(unsigned long long key) {
+  const unsigned k = (unsigned)(key >> 20);
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
 // Byte offset of element (row, k) in the fragment-blocked ("tiled") int8 image of a [rows, cols] activation -- the layout
 // include/mobilequant_amd.h describes at mq_quantize_tiled: 1-KiB blocks of 16 rows x 64 k ordered [row block][k block]; inside a block
 // lane (row & 15) + 16 * ((k >> 4) & 3) owns the 16 bytes k & 15.

@@ -134,8 +134,8 @@ __device__ __forceinline__ void lp_finish(const float* __restrict__ row, int V, 
     if (g == 0ull) {                                                 // fewer than n_top entries (k >= V)
       if (tid == 0) { top_id[r] = -1; top_lp[r] = NEG_INF; }
     } else if (cur == g) {                                           // keys are distinct: one owner
-      top_id[r] = lp_key_id(g);
-      top_lp[r] = lp_of(lp_key_value(g), m, log_s);
+      top_id[r] = sort_key_id(g);
+      top_lp[r] = lp_of(sort_key_value(g), m, log_s);
       ++head;
       cur = head < n_top ? cand[tid * LP_MAX_TOP + head] : 0ull;
     }

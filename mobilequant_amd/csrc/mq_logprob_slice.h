@@ -15,7 +15,6 @@ constexpr int LP_SLICE = 4096;                       // entries per slice: 16 pe
 constexpr int LP_STEPS = LP_SLICE / (4 * LP_THREADS);
 constexpr int LP_MAX_SLICES = (1 << 20) / LP_SLICE;  // 256
 constexpr int LP_MAX_TOP = MQ_LOGPROB_MAX_TOP;
-constexpr unsigned long long LP_IDX_MASK = (1ull << 20) - 1;
 typedef unsigned long long u64;
 
 struct LpPart {
@@ -36,17 +35,6 @@ struct LpRed {
 };
 
 __device__ __forceinline__ float lp_norm(float l) { return l != l ? -__builtin_inff() : l + 0.f; }
-
-__device__ __forceinline__ u64 lp_key(float z, int i) {
-  const unsigned u = __float_as_uint(z);
-  const unsigned k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((u64)k << 20) | (LP_IDX_MASK - (u64)i);
-}
-__device__ __forceinline__ int lp_key_id(u64 key) { return (int)(LP_IDX_MASK - (key & LP_IDX_MASK)); }
-__device__ __forceinline__ float lp_key_value(u64 key) {
-  const unsigned k = (unsigned)(key >> 20);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 
 // step 3 of the rule
 __device__ __forceinline__ float lp_term(float l, float m) { return l == m ? 1.f : expf(l - m); }
@@ -113,7 +101,7 @@ __device__ __forceinline__ void lp_slice(const float* __restrict__ row, int V, i
     x[4 * k] = lp_norm(l.x); x[4 * k + 1] = lp_norm(l.y); x[4 * k + 2] = lp_norm(l.z); x[4 * k + 3] = lp_norm(l.w);
   }
   const bool have_t = t >= 0 && t < (long long)V;
-  const u64 kt = have_t ? lp_key(lp_norm(row[t]), (int)t) : ~0ull;   // uniform load, behind the range check
+  const u64 kt = have_t ? sort_key(lp_norm(row[t]), (int)t) : ~0ull;   // uniform load, behind the range check
 
   float mx = NEG_INF;
 #pragma unroll
@@ -133,7 +121,7 @@ __device__ __forceinline__ void lp_slice(const float* __restrict__ row, int V, i
     for (int e = 0; e < 4; ++e) {
       const int j = 4 * k + e;
       if (ms != NEG_INF) a = a + lp_term(x[j], ms);
-      key[j] = in[k] ? lp_key(x[j], lo + 4 * LP_THREADS * k + 4 * tid + e) : 0ull;          // (a key of an entry is never 0)
+      key[j] = in[k] ? sort_key(x[j], lo + 4 * LP_THREADS * k + 4 * tid + e) : 0ull;          // (a key of an entry is never 0)
       c += key[j] > kt ? 1 : 0;
       best = key[j] > best ? key[j] : best;
     }

@@ -38,10 +38,10 @@
 // each w carries expf's error (1 ulp ASSUMED) and the rounding of z_i - z_max, |d_i| 2^-24 relative, whose p-weighted mean is at
 // most 2^-24 log V; flooring drops less than one unit of 2^-32 per token; one rounding of z_tok - z_max and one of the result.  Not
 // part of the bit contract.  All results leave through ordinary vector stores.
-// mq_sample_penalized runs the same two kernels instantiated with the Penalty load policy (sample_scan_penalized_kernel,
-// sample_select_penalized_kernel): step 0 is applied wherever a logit is loaded -- once for a row held in LDS, on every re-read of a longer
-// one -- reading 4 more bytes of history (8 with a bias) per entry; the history is never staged in LDS.  The thread that writes a row's
-// token then counts it in the row's history (observe).
+// Both kernels are templates over a load policy, instantiated four times (sample_scan_kernel<Pol>, sample_select_kernel<Pol>).
+// mq_sample_penalized runs them with the Penalty policy: step 0 is applied wherever a logit is loaded -- once for a row held in LDS, on
+// every re-read of a longer one -- reading 4 more bytes of history (8 with a bias) per entry; the history is never staged in LDS.  The
+// thread that writes a row's token then counts it in the row's history (observe).
 //
 // SEVERAL ROWS OF ONE SEQUENCE (mq_sample_rows).  T <= 8 logits rows of ONE sequence -- the rows of a multi-token step over
 // [t, d_1 .. d_(T-1)] -- under one request, one optional penalty row, one optional dense bias row and one optional history h[0..V); the
@@ -52,7 +52,7 @@
 // no entry.  Everything else is the rule above, unchanged; there is no idle row: every row draws.  The history and the logits are not
 // written.  So tok[j] is what mq_sample draws for that row alone at n_j (a neutral request, with or without a history, keeps the bits of
 // its logits) and what mq_sample_penalized draws there from a history that has counted d[0..j-1].
-// The same two kernels with a third load policy, Rows (sample_scan_rows_kernel, sample_select_rows_kernel): a workgroup reads the at most
+// The same two kernels with a third load policy, Rows: a workgroup reads the at most
 // seven proposals in front of its row once, wave-uniform, and compares them with the 4-entry block index as the entries are loaded --
 // nothing more is staged in LDS and no pass over V is added.
 // mq_sample_history_count moves the counts of n ids by +1 or -1 (saturating at 65 535 and at 0, bit 31 kept, ids outside [0, V) ignored)
@@ -71,7 +71,7 @@
 // not; nothing but tok, kept, logprob and scratch is written; there is no observe.  So tok[r] and kept[r] are, bit for bit, what
 // mq_sample_rows draws for row j of that run alone (the sequence's request and history, n_base + n_offset = the run's first index,
 // those proposals) and what mq_sample / mq_sample_penalized draw for the row alone from the counted history.
-// The same two kernels with a fourth load policy, Ragged (sample_scan_ragged_kernel, sample_select_ragged_kernel): the row is the
+// The same two kernels with a fourth load policy, Ragged: the row is the
 // workgroup's blockIdx, so the walk back over the table (at most 7 steps), the request lookup and the at most 7 proposals are
 // wave-uniform scalar loads; row_seq and row_pos are range-checked before any address is formed from them -- the table is device data,
 // and whatever it holds the launch stays inside its buffers.  Behind its constructor the policy IS Rows: no pass over V and no LDS is added.
@@ -92,7 +92,6 @@ constexpr int SM_WAVES = SM_THREADS / 64;
 constexpr int SM_BINS = 2048;
 constexpr int SM_LDS_ROW = 32768;              // entries of a row held in LDS (128 KiB of the 160)
 constexpr int SM_LEVELS = 5;
-constexpr unsigned long long SM_IDX_MASK = (1ull << 20) - 1;
 
 struct Best {
   float v;
@@ -147,6 +146,7 @@ __device__ __forceinline__ float z_of(float l, const RowCfg& c) {
 struct NoArgs {};
 
 struct NoPenalty {
+  typedef NoArgs Args;
   __device__ __forceinline__ NoPenalty(const NoArgs&, int) {}
   __device__ __forceinline__ float4 load4(const float* __restrict__ row, int i) const { return *reinterpret_cast<const float4*>(row + i); }
   __device__ __forceinline__ float load1(const float* __restrict__ row, int i) const { return row[i]; }
@@ -161,38 +161,53 @@ struct PenArgs {
   int observe;
 };
 
-struct Penalty {
-  unsigned* h;                    // the row's history: bit 31 = in the prompt, bits 0..15 = times generated
-  const float* b;                 // the row's dense bias, or nullptr
+// Step 0 on one entry, for the three penalised policies: the request's (r, a, f), its dense bias row and whether the step runs at all.
+struct Step0 {
+  const float* b;                 // the dense bias row, or nullptr
   float r, a, f;
-  bool active, count;
-  __device__ __forceinline__ Penalty(const PenArgs& pa, int row) {
-    const mq_sample_penalty_row p = pa.pen[row];
-    h = pa.hist + (long long)row * pa.hstride;
-    b = pa.bias ? pa.bias[row] : nullptr;
-    r = (p.repetition > 0.f && p.repetition < __builtin_inff()) ? p.repetition : 1.f;
-    a = p.presence; f = p.frequency;
-    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral row keeps the bits of its logits (-0 stays -0)
-    count = pa.observe != 0;
+  bool active;
+  // (r, a, f) of pen[i], the request's penalty row; pen == nullptr: of the neutral one
+  __device__ __forceinline__ void decode(const mq_sample_penalty_row* pen, int i) {
+    r = 1.f; a = 0.f; f = 0.f;
+    if (pen) {
+      const mq_sample_penalty_row q = pen[i];
+      r = (q.repetition > 0.f && q.repetition < __builtin_inff()) ? q.repetition : 1.f;
+      a = q.presence; f = q.frequency;
+    }
   }
+  // the entry is hv with `extra` in-flight occurrences added to its count
   // one correctly rounded fp32 operation per line (the build has no contraction: -ffp-contract=off)
-  __device__ __forceinline__ float one(float l, unsigned hv, float bv) const {
-    const unsigned c = hv & 0xFFFFu;
-    const float l1 = hv != 0u ? (l > 0.f ? l / r : l * r) : l;
+  __device__ __forceinline__ float one(float l, unsigned hv, unsigned extra, float bv) const {
+    const unsigned c = min(0xFFFFu, (hv & 0xFFFFu) + extra);
+    const float l1 = (hv != 0u || extra != 0u) ? (l > 0.f ? l / r : l * r) : l;
     float t = f * (float)c;
     t = t + (c > 0u ? a : 0.f);
     const float l2 = l1 - t;
     return b ? l2 + bv : l2;
+  }
+};
+
+struct Penalty : Step0 {
+  typedef PenArgs Args;
+  unsigned* h;                    // the row's history: bit 31 = in the prompt, bits 0..15 = times generated
+  bool count;
+  __device__ __forceinline__ Penalty(const PenArgs& pa, int row) {
+    __builtin_assume(pa.pen != nullptr);                            // (mq_sample_penalized refuses a null penalty)
+    decode(pa.pen, row);
+    h = pa.hist + (long long)row * pa.hstride;
+    b = pa.bias ? pa.bias[row] : nullptr;
+    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral request keeps the bits of its logits (-0 stays -0), history or not
+    count = pa.observe != 0;
   }
   __device__ __forceinline__ float4 load4(const float* __restrict__ row, int i) const {
     const float4 l = *reinterpret_cast<const float4*>(row + i);
     if (!active) return l;                                          // workgroup-uniform
     const uint4 hv = *reinterpret_cast<const uint4*>(h + i);
     const float4 bv = b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-    return make_float4(one(l.x, hv.x, bv.x), one(l.y, hv.y, bv.y), one(l.z, hv.z, bv.z), one(l.w, hv.w, bv.w));
+    return make_float4(one(l.x, hv.x, 0u, bv.x), one(l.y, hv.y, 0u, bv.y), one(l.z, hv.z, 0u, bv.z), one(l.w, hv.w, 0u, bv.w));
   }
   __device__ __forceinline__ float load1(const float* __restrict__ row, int i) const {
-    return active ? one(row[i], h[i], b ? b[i] : 0.f) : row[i];
+    return active ? one(row[i], h[i], 0u, b ? b[i] : 0.f) : row[i];
   }
   // the drawn token's count, saturating at 65 535: one thread, after every read of the row's history in this launch
   __device__ __forceinline__ void observe(int t) const {
@@ -215,23 +230,16 @@ struct RowsArgs {
 
 constexpr int SM_MAX_PROPOSALS = MQ_DECODE_MAX_BATCH - 1;
 
-struct Rows {
-  const unsigned* h;
-  const float* b;
-  float r, a, f;
-  bool active;
+struct Rows : Step0 {
+  typedef RowsArgs Args;
+  const unsigned* h;              // the sequence's history, or nullptr (all zeros)
   int d[SM_MAX_PROPOSALS];        // the proposals in front of this row (wave-uniform), -1: none
   __device__ __forceinline__ Rows() {}                                 // (Ragged fills the fields itself)
   __device__ __forceinline__ Rows(const RowsArgs& ra, int row) {
-    r = 1.f; a = 0.f; f = 0.f;
-    if (ra.pen) {
-      const mq_sample_penalty_row p = ra.pen[0];
-      r = (p.repetition > 0.f && p.repetition < __builtin_inff()) ? p.repetition : 1.f;
-      a = p.presence; f = p.frequency;
-    }
+    decode(ra.pen, 0);
     h = ra.hist;
     b = ra.bias;
-    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral request keeps the bits of its logits, history or not
+    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral request keeps the bits of its logits (-0 stays -0), history or not
 #pragma unroll
     for (int m = 0; m < SM_MAX_PROPOSALS; ++m) {
       d[m] = -1;
@@ -240,15 +248,6 @@ struct Rows {
         if (t >= 0 && t < (long long)ra.V) d[m] = (int)t;
       }
     }
-  }
-  // Penalty::one on the entry (hv with `extra` in-flight occurrences added to its count)
-  __device__ __forceinline__ float one(float l, unsigned hv, unsigned extra, float bv) const {
-    const unsigned c = min(0xFFFFu, (hv & 0xFFFFu) + extra);
-    const float l1 = (hv != 0u || extra != 0u) ? (l > 0.f ? l / r : l * r) : l;
-    float t = f * (float)c;
-    t = t + (c > 0u ? a : 0.f);
-    const float l2 = l1 - t;
-    return b ? l2 + bv : l2;
   }
   __device__ __forceinline__ float4 load4(const float* __restrict__ row, int i) const {
     const float4 l = *reinterpret_cast<const float4*>(row + i);
@@ -294,17 +293,13 @@ struct RaggedArgs {
 
 struct Ragged : Rows {
   // only built for a live row (row_index below has range-checked row_seq[row] and row_pos[row])
+  typedef RaggedArgs Args;
   __device__ __forceinline__ Ragged(const RaggedArgs& ga, int row) {
     const int s = ga.row_seq[row];
-    r = 1.f; a = 0.f; f = 0.f;
-    if (ga.pen) {
-      const mq_sample_penalty_row p = ga.pen[s];
-      r = (p.repetition > 0.f && p.repetition < __builtin_inff()) ? p.repetition : 1.f;
-      a = p.presence; f = p.frequency;
-    }
+    decode(ga.pen, s);
     h = ga.hist ? ga.hist + (long long)s * ga.hstride : nullptr;
     b = ga.bias ? ga.bias[s] : nullptr;
-    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral sequence keeps the bits of its logits, history or not
+    active = r != 1.f || a != 0.f || f != 0.f || b != nullptr;     // a neutral request keeps the bits of its logits (-0 stays -0), history or not
     const int j = active ? run_rows_in_front(ga.row_seq, ga.row_pos, row, s, ga.row_pos[row], SM_MAX_PROPOSALS) : 0;
 #pragma unroll
     for (int m = 0; m < SM_MAX_PROPOSALS; ++m) {
@@ -405,37 +400,15 @@ __device__ __forceinline__ void sample_scan(const float* __restrict__ logits, lo
   if (tid == 0) part[row * SM_MAX_SLICES + s] = b;
 }
 
+// pos / cache_len: mq_sample's; mq_sample_rows: n_base / unused; mq_sample_ragged: the table's row_pos / cache_len (row_index)
+template <class Pol>
 __global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_kernel(const float* __restrict__ logits, long long stride, int V, const int* __restrict__ pos,
-                                                                      int cache_len, const mq_sample_row* __restrict__ params, Best* __restrict__ part) {
-  sample_scan<NoPenalty>(logits, stride, V, pos, cache_len, params, part, NoArgs{});
-}
-
-__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_penalized_kernel(const float* __restrict__ logits, long long stride, int V,
-                                                                                const int* __restrict__ pos, int cache_len,
-                                                                                const mq_sample_row* __restrict__ params, Best* __restrict__ part,
-                                                                                PenArgs pa) {
-  sample_scan<Penalty>(logits, stride, V, pos, cache_len, params, part, pa);
-}
-
-__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_rows_kernel(const float* __restrict__ logits, long long stride, int V,
-                                                                           const int* __restrict__ n_base, const mq_sample_row* __restrict__ params,
-                                                                           Best* __restrict__ part, RowsArgs ra) {
-  sample_scan<Rows>(logits, stride, V, n_base, 0, params, part, ra);
-}
-
-__global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_ragged_kernel(const float* __restrict__ logits, long long stride, int V, int cache_len,
-                                                                             const mq_sample_row* __restrict__ params, Best* __restrict__ part,
-                                                                             RaggedArgs ga) {
-  sample_scan<Ragged>(logits, stride, V, ga.row_pos, cache_len, params, part, ga);
+                                                                      int cache_len, const mq_sample_row* __restrict__ params, Best* __restrict__ part,
+                                                                      typename Pol::Args pa) {
+  sample_scan<Pol>(logits, stride, V, pos, cache_len, params, part, pa);
 }
 
 // ---- launch 2 ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long key_of(float z, int i) {
-  const unsigned u = __float_as_uint(z);
-  const unsigned k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)k << 20) | (SM_IDX_MASK - (unsigned long long)i);
-}
-
 __device__ __forceinline__ unsigned long long mass_of(float z, float zmax) {
   const float e = expf(z - zmax) * 0x1p32f;
   return e >= 0.f ? (unsigned long long)floorf(e) : 0ull;            // (a NaN, from z = z_max = +inf, carries no mass)
@@ -495,7 +468,7 @@ __device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c
       const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const unsigned long long k = key_of(zv[e], i + e);
+        const unsigned long long k = sort_key(zv[e], i + e);
         if (k >= lb && (level == 0 || (k >> up) == (prefix >> up))) {
           const unsigned d = (unsigned)(k >> sh) & dmask;
           atomicAdd(&L.hc[d], 1u);
@@ -540,7 +513,7 @@ __device__ unsigned long long select_cut(const RowSrc& r, int V, const RowCfg& c
           const float zv[4] = {z4.x, z4.y, z4.z, z4.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const unsigned long long k = key_of(zv[e], i + e);
+            const unsigned long long k = sort_key(zv[e], i + e);
             if (k >= lb && (k >> sh) == (prefix >> sh)) L.found[5] = k;
           }
         }
@@ -647,7 +620,7 @@ __device__ __forceinline__ void sample_select(unsigned char* smem, const float* 
     bool in[4], any = false;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      in[e] = key_of(zv[e], i + e) >= cut && (zv[e] - zmax >= lmin || i + e == zb.i);
+      in[e] = sort_key(zv[e], i + e) >= cut && (zv[e] - zmax >= lmin || i + e == zb.i);
       any = any || in[e];
     }
     if (!any) continue;
@@ -677,40 +650,17 @@ __device__ __forceinline__ void sample_select(unsigned char* smem, const float* 
   }
 }
 
+// NoPenalty: mq_sample.  Penalty: step 0 applied as a row is read, the drawn token counted in the row's history at the tail.  Rows: the rows
+// of one sequence, each with the proposals in front of it counted as its entries are read.  Ragged: the rows of a ragged step, each under
+// its own sequence's request with the proposals of its run counted as it reads.  pos / cache_len: as in sample_scan_kernel.
+template <class Pol>
 __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
                                                                    const int* __restrict__ pos, int cache_len,
                                                                    const mq_sample_row* __restrict__ params, const Best* __restrict__ part,
-                                                                   long long* __restrict__ tok, int* __restrict__ kept, float* __restrict__ logprob) {
+                                                                   long long* __restrict__ tok, int* __restrict__ kept, float* __restrict__ logprob,
+                                                                   typename Pol::Args pa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  sample_select<NoPenalty>(smem, logits, stride, V, S, lds_row, pos, cache_len, params, part, tok, kept, logprob, NoArgs{});
-}
-
-// mq_sample_penalized: the same selection with step 0 applied as a row is read; the drawn token is counted in the row's history at the tail
-__global__ __launch_bounds__(SM_THREADS) void sample_select_penalized_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
-                                                                             const int* __restrict__ pos, int cache_len,
-                                                                             const mq_sample_row* __restrict__ params, const Best* __restrict__ part,
-                                                                             long long* __restrict__ tok, int* __restrict__ kept,
-                                                                             float* __restrict__ logprob, PenArgs pa) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  sample_select<Penalty>(smem, logits, stride, V, S, lds_row, pos, cache_len, params, part, tok, kept, logprob, pa);
-}
-
-// mq_sample_rows: the rows of one sequence, each with the proposals in front of it counted as its entries are read
-__global__ __launch_bounds__(SM_THREADS) void sample_select_rows_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
-                                                                        const int* __restrict__ n_base, const mq_sample_row* __restrict__ params,
-                                                                        const Best* __restrict__ part, long long* __restrict__ tok, int* __restrict__ kept,
-                                                                        float* __restrict__ logprob, RowsArgs ra) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  sample_select<Rows>(smem, logits, stride, V, S, lds_row, n_base, 0, params, part, tok, kept, logprob, ra);
-}
-
-// mq_sample_ragged: the rows of a ragged step, each under its own sequence's request with the proposals of its run counted as it reads
-__global__ __launch_bounds__(SM_THREADS) void sample_select_ragged_kernel(const float* __restrict__ logits, long long stride, int V, int S, int lds_row,
-                                                                          int cache_len, const mq_sample_row* __restrict__ params,
-                                                                          const Best* __restrict__ part, long long* __restrict__ tok, int* __restrict__ kept,
-                                                                          float* __restrict__ logprob, RaggedArgs ga) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  sample_select<Ragged>(smem, logits, stride, V, S, lds_row, ga.row_pos, cache_len, params, part, tok, kept, logprob, ga);
+  sample_select<Pol>(smem, logits, stride, V, S, lds_row, pos, cache_len, params, part, tok, kept, logprob, pa);
 }
 
 __global__ void history_clear_kernel(uint4* __restrict__ h, int n4) {
@@ -726,21 +676,26 @@ __global__ void history_mark_kernel(unsigned* __restrict__ h, int V, const long 
   if (t >= 0 && t < V) atomicOr(&h[t], 0x80000000u);
 }
 
-// The count (bits 0..15) of every id moves by delta = +1 / -1, saturating at 65 535 / at 0; bit 31 stays.  One compare-and-swap loop per
-// id: repeated ids count repeatedly, and since every id moves its entry the same way the result is that of applying them one by one.
+// The count (bits 0..15) of a history entry moves by delta = +1 / -1, saturating at 65 535 / at 0; bit 31 stays.  One compare-and-swap loop.
+__device__ __forceinline__ void count_entry(unsigned* e, int delta) {
+  unsigned old = *e;
+  for (;;) {
+    const unsigned c = old & 0xFFFFu;
+    if (delta > 0 ? c == 0xFFFFu : c == 0u) return;
+    const unsigned seen = atomicCAS(e, old, delta > 0 ? old + 1u : old - 1u);
+    if (seen == old) return;
+    old = seen;
+  }
+}
+
+// count_entry for every id: repeated ids count repeatedly, and since every id moves its entry the same way the result is that of applying
+// them one by one.  An id outside [0, V) is ignored.
 __global__ void history_count_kernel(unsigned* __restrict__ h, int V, const long long* __restrict__ ids, long long n, int delta) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const long long t = ids[j];
   if (t < 0 || t >= V) return;
-  unsigned old = h[t];
-  for (;;) {
-    const unsigned c = old & 0xFFFFu;
-    if (delta > 0 ? c == 0xFFFFu : c == 0u) return;
-    const unsigned seen = atomicCAS(&h[t], old, delta > 0 ? old + 1u : old - 1u);
-    if (seen == old) return;
-    old = seen;
-  }
+  count_entry(h + t, delta);
 }
 
 // history_count_kernel over pairs[j] = (sequence, id) and the histories [batch][hstride]: a pair whose sequence is outside [0, batch) or
@@ -751,15 +706,7 @@ __global__ void history_count_ragged_kernel(unsigned* __restrict__ h, long long 
   if (j >= n) return;
   const long long s = pairs[2 * j], t = pairs[2 * j + 1];
   if (s < 0 || s >= batch || t < 0 || t >= V) return;
-  unsigned* e = h + s * hstride + t;
-  unsigned old = *e;
-  for (;;) {
-    const unsigned c = old & 0xFFFFu;
-    if (delta > 0 ? c == 0xFFFFu : c == 0u) return;
-    const unsigned seen = atomicCAS(e, old, delta > 0 ? old + 1u : old - 1u);
-    if (seen == old) return;
-    old = seen;
-  }
+  count_entry(h + s * hstride + t, delta);
 }
 
 __global__ void sample_uniforms_kernel(unsigned long long seed, unsigned long long stream, unsigned n, long long first, long long count,
@@ -776,13 +723,35 @@ size_t select_lds_bytes(int lds_row) {
   return (size_t)lds_row * 4 + (size_t)SM_BINS * 8 + 8 * 8 + 2 * SM_WAVES * 8 + (size_t)SM_BINS * 4 + 2 * SM_WAVES * 4;
 }
 
-PerDeviceOnce g_lds_set, g_lds_set_pen, g_lds_set_rows, g_lds_set_ragged;
+// ---- the checks the entries share -------------------------------------------------------------------------------------------------
+int check_V(int64_t V, const char* who) {
+  MQ_REQUIRE(V >= 4 && V % 4 == 0 && V <= (1 << 20), "%s: V=%lld must be a multiple of 4 in [4, 2^20]", who, (long long)V);
+  return MQ_OK;
+}
+
+int check_history_stride(int64_t history_stride, int64_t V, const char* who) {
+  MQ_REQUIRE(history_stride >= V && history_stride % 4 == 0, "%s: history_stride=%lld must be >= V and a multiple of 4", who, (long long)history_stride);
+  return MQ_OK;
+}
+
+// the history entries: a history of V entries per row
+int check_history(const uint32_t* history, int64_t V, const char* who) {
+  MQ_REQUIRE(history != nullptr && aligned(history, 16), "%s: history must be a 16-byte aligned pointer", who);
+  return check_V(V, who);
+}
+
+// the history entries: n ids (`what`: their name in the message) in device memory
+int check_ids(const int64_t* ids, int64_t n, const char* what, const char* who) {
+  MQ_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "%s: n=%lld outside [0, 2^31]", who, (long long)n);
+  MQ_REQUIRE(n == 0 || (ids != nullptr && aligned(ids, 8)), "%s: %s must be an 8-byte aligned pointer when n > 0", who, what);
+  return MQ_OK;
+}
 
 int check_sample_args(const mq_sample_args* a, const char* who) {
   MQ_REQUIRE(a->logits && a->pos && a->params && a->tok && a->scratch,
              "%s: null pointer (logits, pos, params, tok and scratch are required; kept and logprob are optional)", who);
   MQ_REQUIRE(a->rows >= 1 && a->rows <= MQ_DECODE_MAX_BATCH, "%s: rows=%d outside 1..%d", who, a->rows, MQ_DECODE_MAX_BATCH);
-  MQ_REQUIRE(a->V >= 4 && a->V % 4 == 0 && a->V <= (1 << 20), "%s: V=%lld must be a multiple of 4 in [4, 2^20]", who, (long long)a->V);
+  if (const int rc = check_V(a->V, who)) return rc;
   MQ_REQUIRE(a->logits_stride >= a->V && a->logits_stride % 4 == 0, "%s: logits_stride=%lld must be >= V and a multiple of 4", who,
              (long long)a->logits_stride);
   MQ_REQUIRE(a->cache_len >= 1, "%s: cache_len=%d must be >= 1 (a row with pos outside [0, cache_len) is idle)", who, a->cache_len);
@@ -795,21 +764,29 @@ int check_sample_args(const mq_sample_args* a, const char* who) {
   return MQ_OK;
 }
 
-// the two launches of mq_sample (pa == ra == ga == nullptr), of mq_sample_penalized (pa), of mq_sample_rows (ra; a->pos is n_base) and of
-// mq_sample_ragged (ga; a->pos is row_pos)
-int launch_sample(const mq_sample_args* a, const PenArgs* pa, const RowsArgs* ra, const char* who, mq_stream_t stream, const RaggedArgs* ga = nullptr) {
+// An mq_sample_rows_args / mq_sample_ragged_args as mq_sample's block over the same rows (the shared fields carry the same names): its
+// limits and alignments are the entry's.
+template <class A>
+mq_sample_args as_sample_args(const A* a, const int* pos, int cache_len) {
+  mq_sample_args s;
+  s.logits = a->logits; s.logits_stride = a->logits_stride; s.V = a->V; s.rows = a->rows;
+  s.pos = pos; s.cache_len = cache_len; s.params = a->params; s.tok = a->tok; s.kept = a->kept; s.logprob = a->logprob;
+  s.scratch = a->scratch; s.scratch_bytes = a->scratch_bytes;
+  return s;
+}
+
+// the two launches of an entry under its load policy (mq_sample_rows: a->pos is n_base; mq_sample_ragged: a->pos is row_pos)
+template <class Pol>
+int launch_sample(const mq_sample_args* a, const typename Pol::Args& pa, const char* who, mq_stream_t stream) {
   const int V = (int)a->V;
   const int S = min(SM_MAX_SLICES, (V + SM_SLICE - 1) / SM_SLICE);
   const int lds_row = V <= SM_LDS_ROW ? V : 0;
   const size_t lds = select_lds_bytes(lds_row);
   const int dev = current_device();
-  PerDeviceOnce& once = ga ? g_lds_set_ragged : ra ? g_lds_set_rows : pa ? g_lds_set_pen : g_lds_set;
+  static PerDeviceOnce once;                                         // (one per instantiation)
   if (!once.done(dev)) {
-    const void* fn = ga   ? (const void*)sample_select_ragged_kernel
-                     : ra ? (const void*)sample_select_rows_kernel
-                     : pa ? (const void*)sample_select_penalized_kernel
-                          : (const void*)sample_select_kernel;
-    MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_LDS_ROW)) == hipSuccess,
+    MQ_REQUIRE(hipFuncSetAttribute((const void*)sample_select_kernel<Pol>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)select_lds_bytes(SM_LDS_ROW)) == hipSuccess,
                "%s: hipFuncSetAttribute(%zu B LDS) failed", who, select_lds_bytes(SM_LDS_ROW));
     once.mark(dev);
   }
@@ -817,29 +794,12 @@ int launch_sample(const mq_sample_args* a, const PenArgs* pa, const RowsArgs* ra
   Best* part = static_cast<Best*>(a->scratch);
   long long* tok = reinterpret_cast<long long*>(a->tok);
   if (S > 1) {
-    const dim3 grid((unsigned)S, (unsigned)a->rows);
-    if (ga)
-      sample_scan_ragged_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->cache_len, a->params, part, *ga);
-    else if (ra)
-      sample_scan_rows_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->params, part, *ra);
-    else if (pa)
-      sample_scan_penalized_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part, *pa);
-    else
-      sample_scan_kernel<<<grid, SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len, a->params, part);
+    sample_scan_kernel<Pol><<<dim3((unsigned)S, (unsigned)a->rows), SM_SCAN_THREADS, 0, st>>>(a->logits, (long long)a->logits_stride, V, a->pos, a->cache_len,
+                                                                                            a->params, part, pa);
     MQ_LAUNCH_CHECK(who);
   }
-  if (ga)
-    sample_select_ragged_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->cache_len, a->params, part,
-                                                                           tok, a->kept, a->logprob, *ga);
-  else if (ra)
-    sample_select_rows_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->params, part, tok,
-                                                                         a->kept, a->logprob, *ra);
-  else if (pa)
-    sample_select_penalized_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len,
-                                                                              a->params, part, tok, a->kept, a->logprob, *pa);
-  else
-    sample_select_kernel<<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len, a->params,
-                                                                    part, tok, a->kept, a->logprob);
+  sample_select_kernel<Pol><<<(unsigned)a->rows, SM_THREADS, lds, st>>>(a->logits, (long long)a->logits_stride, V, S, lds_row, a->pos, a->cache_len, a->params,
+                                                                       part, tok, a->kept, a->logprob, pa);
   MQ_LAUNCH_CHECK(who);
   return MQ_OK;
 }
@@ -854,7 +814,7 @@ extern "C" {
 int mq_sample(const mq_sample_args* a, mq_stream_t stream) {
   MQ_REQUIRE(a != nullptr, "mq_sample: null argument block");
   if (const int rc = check_sample_args(a, "mq_sample")) return rc;
-  return launch_sample(a, nullptr, nullptr, "mq_sample", stream);
+  return launch_sample<NoPenalty>(a, NoArgs{}, "mq_sample", stream);
 }
 
 int mq_sample_penalized(const mq_sample_penalized_args* a, mq_stream_t stream) {
@@ -863,18 +823,14 @@ int mq_sample_penalized(const mq_sample_penalized_args* a, mq_stream_t stream) {
   MQ_REQUIRE(a->penalty != nullptr && a->history != nullptr, "mq_sample_penalized: null pointer (penalty and history are required; bias is optional)");
   MQ_REQUIRE(aligned(a->penalty, 16) && aligned(a->history, 16) && aligned(a->bias, 8),
              "mq_sample_penalized: penalty and history must be 16-byte aligned, bias 8-byte aligned");
-  MQ_REQUIRE(a->history_stride >= a->s.V && a->history_stride % 4 == 0, "mq_sample_penalized: history_stride=%lld must be >= V and a multiple of 4",
-             (long long)a->history_stride);
+  if (const int rc = check_history_stride(a->history_stride, a->s.V, "mq_sample_penalized")) return rc;
   MQ_REQUIRE(a->observe == 0 || a->observe == 1, "mq_sample_penalized: observe=%d must be 0 or 1", a->observe);
-  const PenArgs pa{a->penalty, a->history, (long long)a->history_stride, a->bias, a->observe};
-  return launch_sample(&a->s, &pa, nullptr, "mq_sample_penalized", stream);
+  return launch_sample<Penalty>(&a->s, PenArgs{a->penalty, a->history, (long long)a->history_stride, a->bias, a->observe}, "mq_sample_penalized", stream);
 }
 
 int mq_sample_history_prompt(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int clear, mq_stream_t stream) {
-  MQ_REQUIRE(history != nullptr && aligned(history, 16), "mq_sample_history_prompt: history must be a 16-byte aligned pointer");
-  MQ_REQUIRE(V >= 4 && V % 4 == 0 && V <= (1 << 20), "mq_sample_history_prompt: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)V);
-  MQ_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "mq_sample_history_prompt: n=%lld outside [0, 2^31]", (long long)n);
-  MQ_REQUIRE(n == 0 || (ids != nullptr && aligned(ids, 8)), "mq_sample_history_prompt: ids must be an 8-byte aligned pointer when n > 0");
+  if (const int rc = check_history(history, V, "mq_sample_history_prompt")) return rc;
+  if (const int rc = check_ids(ids, n, "ids", "mq_sample_history_prompt")) return rc;
   MQ_REQUIRE(clear == 0 || clear == 1, "mq_sample_history_prompt: clear=%d must be 0 or 1", clear);
   hipStream_t st = as_stream(stream);
   if (clear) {
@@ -892,29 +848,21 @@ int mq_sample_history_prompt(uint32_t* history, int64_t V, const int64_t* ids, i
 int mq_sample_rows(const mq_sample_rows_args* a, mq_stream_t stream) {
   MQ_REQUIRE(a != nullptr, "mq_sample_rows: null argument block");
   MQ_REQUIRE(a->n_base != nullptr, "mq_sample_rows: null pointer (n_base is required)");
-  // mq_sample's block over the same rows: its limits and alignments are this entry's (pos = n_base; no row is idle, cache_len is unused)
-  mq_sample_args s;
-  s.logits = a->logits; s.logits_stride = a->logits_stride; s.V = a->V; s.rows = a->rows;
-  s.pos = a->n_base; s.cache_len = 1; s.params = a->params; s.tok = a->tok; s.kept = a->kept; s.logprob = a->logprob;
-  s.scratch = a->scratch; s.scratch_bytes = a->scratch_bytes;
+  const mq_sample_args s = as_sample_args(a, a->n_base, 1);          // (no row is idle: cache_len is unused)
   if (const int rc = check_sample_args(&s, "mq_sample_rows")) return rc;
   MQ_REQUIRE(a->n_offset >= -(1 << 30) && a->n_offset <= (1 << 30), "mq_sample_rows: n_offset=%d outside [-2^30, 2^30]", a->n_offset);
   MQ_REQUIRE(a->rows == 1 || a->proposals != nullptr, "mq_sample_rows: null pointer (proposals holds rows - 1 ids when rows > 1)");
   MQ_REQUIRE(aligned(a->penalty, 16) && aligned(a->history, 16) && aligned(a->bias, 16) && aligned(a->proposals, 8),
              "mq_sample_rows: penalty, history and bias must be 16-byte aligned, proposals 8-byte aligned");
   const RowsArgs ra{a->penalty, a->history, a->bias, reinterpret_cast<const long long*>(a->proposals), (int)a->V, a->n_offset};
-  return launch_sample(&s, nullptr, &ra, "mq_sample_rows", stream);
+  return launch_sample<Rows>(&s, ra, "mq_sample_rows", stream);
 }
 
 int mq_sample_ragged(const mq_sample_ragged_args* a, mq_stream_t stream) {
   MQ_REQUIRE(a != nullptr, "mq_sample_ragged: null argument block");
   MQ_REQUIRE(a->row_seq && a->row_pos && a->row_tok, "mq_sample_ragged: null pointer (the row table row_seq / row_pos and row_tok are required)");
   MQ_REQUIRE(a->batch >= 1 && a->batch <= MQ_DECODE_MAX_BATCH, "mq_sample_ragged: batch=%d outside 1..%d", a->batch, MQ_DECODE_MAX_BATCH);
-  // mq_sample's block over the same rows: its limits and alignments are this entry's (pos = row_pos)
-  mq_sample_args s;
-  s.logits = a->logits; s.logits_stride = a->logits_stride; s.V = a->V; s.rows = a->rows;
-  s.pos = a->row_pos; s.cache_len = a->cache_len; s.params = a->params; s.tok = a->tok; s.kept = a->kept; s.logprob = a->logprob;
-  s.scratch = a->scratch; s.scratch_bytes = a->scratch_bytes;
+  const mq_sample_args s = as_sample_args(a, a->row_pos, a->cache_len);
   if (const int rc = check_sample_args(&s, "mq_sample_ragged")) return rc;
   MQ_REQUIRE(a->n_offset >= -(1 << 30) && a->n_offset <= (1 << 30), "mq_sample_ragged: n_offset=%d outside [-2^30, 2^30]", a->n_offset);
   MQ_REQUIRE((a->penalty == nullptr && a->history == nullptr) || (a->history_stride >= a->V && a->history_stride % 4 == 0),
@@ -923,32 +871,28 @@ int mq_sample_ragged(const mq_sample_ragged_args* a, mq_stream_t stream) {
              "mq_sample_ragged: penalty and history must be 16-byte aligned, row_tok and bias 8-byte, row_seq 4-byte aligned");
   const RaggedArgs ga{a->row_seq, a->row_pos, reinterpret_cast<const long long*>(a->row_tok), a->penalty, a->history, (long long)a->history_stride,
                       a->bias, a->batch, (int)a->V, a->n_offset};
-  return launch_sample(&s, nullptr, nullptr, "mq_sample_ragged", stream, &ga);
+  return launch_sample<Ragged>(&s, ga, "mq_sample_ragged", stream);
 }
 
 int mq_sample_history_count_ragged(uint32_t* history, int64_t history_stride, int64_t V, int batch, const int64_t* pairs, int64_t n, int delta,
                                    mq_stream_t stream) {
-  MQ_REQUIRE(history != nullptr && aligned(history, 16), "mq_sample_history_count_ragged: history must be a 16-byte aligned pointer");
-  MQ_REQUIRE(V >= 4 && V % 4 == 0 && V <= (1 << 20), "mq_sample_history_count_ragged: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)V);
-  MQ_REQUIRE(history_stride >= V && history_stride % 4 == 0, "mq_sample_history_count_ragged: history_stride=%lld must be >= V and a multiple of 4",
-             (long long)history_stride);
-  MQ_REQUIRE(batch >= 1 && batch <= MQ_DECODE_MAX_BATCH, "mq_sample_history_count_ragged: batch=%d outside 1..%d", batch, MQ_DECODE_MAX_BATCH);
-  MQ_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "mq_sample_history_count_ragged: n=%lld outside [0, 2^31]", (long long)n);
-  MQ_REQUIRE(n == 0 || (pairs != nullptr && aligned(pairs, 8)), "mq_sample_history_count_ragged: pairs must be an 8-byte aligned pointer when n > 0");
-  MQ_REQUIRE(delta == 1 || delta == -1, "mq_sample_history_count_ragged: delta=%d must be +1 or -1", delta);
+  const char* who = "mq_sample_history_count_ragged";
+  if (const int rc = check_history(history, V, who)) return rc;
+  if (const int rc = check_history_stride(history_stride, V, who)) return rc;
+  MQ_REQUIRE(batch >= 1 && batch <= MQ_DECODE_MAX_BATCH, "%s: batch=%d outside 1..%d", who, batch, MQ_DECODE_MAX_BATCH);
+  if (const int rc = check_ids(pairs, n, "pairs", who)) return rc;
+  MQ_REQUIRE(delta == 1 || delta == -1, "%s: delta=%d must be +1 or -1", who, delta);
   if (n > 0) {
     history_count_ragged_kernel<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(history, (long long)history_stride, (int)V, batch,
                                                                                            reinterpret_cast<const long long*>(pairs), (long long)n, delta);
-    MQ_LAUNCH_CHECK("mq_sample_history_count_ragged");
+    MQ_LAUNCH_CHECK(who);
   }
   return MQ_OK;
 }
 
 int mq_sample_history_count(uint32_t* history, int64_t V, const int64_t* ids, int64_t n, int delta, mq_stream_t stream) {
-  MQ_REQUIRE(history != nullptr && aligned(history, 16), "mq_sample_history_count: history must be a 16-byte aligned pointer");
-  MQ_REQUIRE(V >= 4 && V % 4 == 0 && V <= (1 << 20), "mq_sample_history_count: V=%lld must be a multiple of 4 in [4, 2^20]", (long long)V);
-  MQ_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "mq_sample_history_count: n=%lld outside [0, 2^31]", (long long)n);
-  MQ_REQUIRE(n == 0 || (ids != nullptr && aligned(ids, 8)), "mq_sample_history_count: ids must be an 8-byte aligned pointer when n > 0");
+  if (const int rc = check_history(history, V, "mq_sample_history_count")) return rc;
+  if (const int rc = check_ids(ids, n, "ids", "mq_sample_history_count")) return rc;
   MQ_REQUIRE(delta == 1 || delta == -1, "mq_sample_history_count: delta=%d must be +1 or -1", delta);
   if (n > 0) {
     history_count_kernel<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(history, (int)V, reinterpret_cast<const long long*>(ids), (long long)n, delta);

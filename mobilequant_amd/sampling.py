@@ -21,6 +21,7 @@ assert ROW_DTYPE.itemsize == ctypes.sizeof(_lib.MqSampleRow) == 32
 PENALTY_DTYPE = np.dtype([("repetition", "<f4"), ("presence", "<f4"), ("frequency", "<f4"), ("reserved", "<i4")])
 assert PENALTY_DTYPE.itemsize == ctypes.sizeof(_lib.MqSamplePenaltyRow) == 16
 HISTORY_PROMPT_BIT = 1 << 31                      # a history entry: bit 31 = in the prompt, bits 0..15 = times generated (saturating)
+HISTORY_DTYPES = (torch.int32, getattr(torch, "uint32", torch.int32))
 
 
 def _f32(v) -> np.float32:
@@ -129,7 +130,7 @@ def history_prompt(history_row: torch.Tensor, ids, clear: bool = True):
     """mq_sample_history_prompt on one row's history ([V] int32 device tensor holding the uint32 entries): clear it, then mark the ids
     as prompt tokens (bit 31).  The ids are checked here, on the host: one outside [0, V) raises ValueError."""
     V = history_row.numel()
-    if history_row.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not history_row.is_contiguous():
+    if history_row.dtype not in HISTORY_DTYPES or not history_row.is_contiguous():
         raise RuntimeError("mobilequant_amd: a history row must be a contiguous int32 (uint32 bits) tensor")
     dev = history_row.device
     t = _check_ids(ids, V).to(dev)
@@ -138,30 +139,51 @@ def history_prompt(history_row: torch.Tensor, ids, clear: bool = True):
                   torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _history_row(history_row, who: str) -> torch.Tensor:
-    if not isinstance(history_row, torch.Tensor) or history_row.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
-            or history_row.dim() != 1 or not history_row.is_contiguous():
-        raise RuntimeError(f"mobilequant_amd: {who} history must be one contiguous int32 (uint32 bits) row [V]")
-    if not history_row.is_cuda:
+def _check_count(who: str, delta, history, history_ok: bool, history_form: str, ids, ids_name: str, ids_ok: bool, ids_form: str):
+    """The checks of the two history_count functions, in their order: delta, the history (its form, then its device), the ids."""
+    if isinstance(delta, bool) or delta not in (1, -1):
+        raise ValueError(f"mobilequant_amd: {who} delta={delta!r} must be +1 or -1")
+    if not history_ok:
+        raise RuntimeError(f"mobilequant_amd: {who} history must be {history_form}")
+    if not history.is_cuda:
         raise RuntimeError(f"mobilequant_amd: {who} history must be a ROCm device tensor; there is no CPU path")
-    return history_row
+    if not ids_ok:
+        raise RuntimeError(f"mobilequant_amd: {who} {ids_name} must be a contiguous {ids_form}")
+    if ids.device != history.device:
+        raise RuntimeError(f"mobilequant_amd: {who} {ids_name} must be a ROCm device tensor on the history's device")
+
+
+def _is_row(t, dtypes, V: int) -> bool:
+    return isinstance(t, torch.Tensor) and t.dtype in dtypes and t.dim() == 1 and t.numel() >= V and t.is_contiguous()
+
+
+def _is_ids(t, dim: int) -> bool:
+    return isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == dim and t.is_contiguous()
 
 
 def history_count(history_row: torch.Tensor, ids: torch.Tensor, delta: int):
     """mq_sample_history_count on one row's history ([V] int32 device tensor holding the uint32 entries): the count (bits 0..15) of every
     id in `ids` (an int64 device tensor, any number; ids repeat) moves by delta = +1 or -1, saturating at 65 535 and at 0.  Bit 31 is kept
     and an id outside [0, V) is ignored on the device: no id is read on the host.  One launch, capturable."""
-    if isinstance(delta, bool) or delta not in (1, -1):
-        raise ValueError(f"mobilequant_amd: history_count delta={delta!r} must be +1 or -1")
-    h = _history_row(history_row, "history_count")
-    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous():
-        raise RuntimeError("mobilequant_amd: history_count ids must be a contiguous int64 [n] tensor")
-    if ids.device != h.device:
-        raise RuntimeError("mobilequant_amd: history_count ids must be a ROCm device tensor on the history's device")
+    h = history_row
+    _check_count("history_count", delta, h, _is_row(h, HISTORY_DTYPES, 0), "one contiguous int32 (uint32 bits) row [V]",
+                 ids, "ids", _is_ids(ids, 1), "int64 [n] tensor")
     with torch.cuda.device(h.device):
         _lib.call("mq_sample_history_count", h.data_ptr(), h.numel(), ids.data_ptr() if ids.numel() else None, ids.numel(), int(delta),
                   torch.cuda.current_stream(h.device).cuda_stream)
     return history_row
+
+
+def _fill_shared(a, logits: torch.Tensor, rows: int, params: torch.Tensor, tok: torch.Tensor, scratch: torch.Tensor,
+                 kept: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None):
+    """The fields every mq_sample* argument struct shares, over the first `rows` rows of logits [>= rows, V].  Returns a."""
+    V = logits.shape[1]
+    a.logits, a.logits_stride, a.V, a.rows = logits.data_ptr(), logits.stride(0) if logits.shape[0] > 1 else max(V, logits.stride(0)), V, rows
+    a.params, a.tok = params.data_ptr(), tok.data_ptr()
+    a.kept = kept.data_ptr() if kept is not None else None
+    a.logprob = logprob.data_ptr() if logprob is not None else None
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+    return a
 
 
 class SampleLaunch:
@@ -178,12 +200,8 @@ class SampleLaunch:
         self.rows, self.dev = rows, dev
         self.params = torch.zeros(rows * ROW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.scratch = torch.zeros(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
-        a = MqSampleArgs()
-        a.logits, a.logits_stride, a.V, a.rows = lg.data_ptr(), lg.stride(0), V, rows
-        a.pos, a.cache_len, a.params, a.tok = pos.data_ptr(), int(cache_len), self.params.data_ptr(), tok.data_ptr()
-        a.kept, a.logprob = None, None
-        a.scratch, a.scratch_bytes = self.scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
-        self.args = a
+        self.args = a = _fill_shared(MqSampleArgs(), lg, rows, self.params, tok, self.scratch)
+        a.pos, a.cache_len = pos.data_ptr(), int(cache_len)
         self._keep = (lg, pos, tok)
         self.V = V
         self.penalized = False
@@ -263,13 +281,10 @@ class RowsLaunch:
     def args(self, T: int, penalized: bool) -> MqSampleRowsArgs:
         a = self._args.get((T, penalized))
         if a is None:
-            s, lg = self.sampler, self.logits
-            a = MqSampleRowsArgs()
-            a.logits, a.logits_stride, a.V, a.rows = lg.data_ptr(), lg.stride(0), lg.shape[1], T
-            a.n_base, a.n_offset, a.params = self.pos.data_ptr(), 1 - T, s.params.data_ptr()
+            s = self.sampler
+            a = _fill_shared(MqSampleRowsArgs(), self.logits, T, s.params, self.out, self.scratch)
+            a.n_base, a.n_offset = self.pos.data_ptr(), 1 - T
             a.proposals = self.proposals.data_ptr() if T > 1 else None
-            a.tok, a.kept, a.logprob = self.out.data_ptr(), None, None
-            a.scratch, a.scratch_bytes = self.scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
             if penalized:
                 a.penalty, a.history, a.bias = s.penalty.data_ptr(), s.history[0].data_ptr(), s.bias[0].data_ptr()
             self._args[(T, penalized)] = a
@@ -299,12 +314,10 @@ class RaggedRowsLaunch:
     def args(self, R: int, penalized: bool) -> MqSampleRaggedArgs:
         a = self._args.get((R, penalized))
         if a is None:
-            s, lg = self.sampler, self.logits
-            a = MqSampleRaggedArgs()
-            a.logits, a.logits_stride, a.V, a.rows, a.batch, a.cache_len = lg.data_ptr(), lg.stride(0), lg.shape[1], R, s.rows, self.cache_len
-            a.row_seq, a.row_pos, a.n_offset, a.row_tok = self.row_seq.data_ptr(), self.row_pos.data_ptr(), self.n_offset, self.row_tok.data_ptr()
-            a.params, a.tok, a.kept, a.logprob = s.params.data_ptr(), self.out.data_ptr(), None, None
-            a.scratch, a.scratch_bytes = self.scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+            s = self.sampler
+            a = _fill_shared(MqSampleRaggedArgs(), self.logits, R, s.params, self.out, self.scratch)
+            a.batch, a.cache_len, a.n_offset = s.rows, self.cache_len, self.n_offset
+            a.row_seq, a.row_pos, a.row_tok = self.row_seq.data_ptr(), self.row_pos.data_ptr(), self.row_tok.data_ptr()
             if penalized:
                 a.penalty, a.history, a.history_stride, a.bias = s.penalty.data_ptr(), s.history.data_ptr(), s.history.stride(0), s.bias_ptr.data_ptr()
             self._args[(R, penalized)] = a
@@ -418,6 +431,89 @@ def validate_generate_args(who: str, sampling, do_sample: bool, draft=None):
         raise ValueError(f"{who}: a draft is for greedy decoding only (sampling= with a draft)")
 
 
+# ---- the checks of the one-shot functions, by the caller's name ----------------------------------------------------------------------
+# Every check of a value or a type runs before the first check of a device (_place): a call that is wrong in both ways reports the former.
+def _check_logits(who: str, logits):
+    """-> (logits [rows, V], rows, V); 1-D logits are one row."""
+    if isinstance(logits, torch.Tensor) and logits.dim() == 1:
+        logits = logits.view(1, -1)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise RuntimeError(f"mobilequant_amd: {who} logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    if not 1 <= rows <= MAX_ROWS:
+        raise RuntimeError(f"mobilequant_amd: {who} rows={rows} outside 1..{MAX_ROWS}")
+    return logits, rows, V
+
+
+def _check_n_offset(who: str, n_offset) -> int:
+    if isinstance(n_offset, bool) or not isinstance(n_offset, (int, np.integer)) or not -2 ** 30 <= int(n_offset) <= 2 ** 30:
+        raise ValueError(f"mobilequant_amd: {who} n_offset={n_offset!r} must be an int in [-2^30, 2^30]")
+    return int(n_offset)
+
+
+def _check_vectors(who: str, *specs):
+    """specs: (tensor or None, dtype, count, name, required) -- contiguous vectors of exactly `count` entries."""
+    for t, dt, n, what, required in specs:
+        if t is None:
+            if required:
+                raise RuntimeError(f"mobilequant_amd: {who} needs {what} ({dt} [{n}])")
+        elif not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: {who} {what} must be contiguous {dt} [{n}]")
+
+
+def _packed(who: str, what: str, src, pack, dtype: np.dtype, count: Optional[int], noun: str = "", unit: str = "rows"):
+    """`count` packed rows of `dtype` (count None: as many as src holds): src itself when it is a uint8 tensor of that size (the caller's
+    device array), else the host array pack(src).  -> (tensor or array, number of rows)"""
+    if not isinstance(src, torch.Tensor):
+        host = pack(src)
+        if count is not None and len(host) != count:
+            raise RuntimeError(f"mobilequant_amd: {who} got {len(host)} {noun} for {count} {unit}")
+        return host, len(host)
+    if count is None:
+        if src.dtype != torch.uint8 or src.numel() % dtype.itemsize or not src.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: {who} {what} must be contiguous uint8 bytes, {dtype.itemsize} per sequence")
+        return src, src.numel() // dtype.itemsize
+    if src.dtype != torch.uint8 or src.numel() != count * dtype.itemsize or not src.is_contiguous():
+        raise RuntimeError(f"mobilequant_amd: {who} {what} must be {count * dtype.itemsize} contiguous uint8 bytes")
+    return src, count
+
+
+def _check_history_block(who: str, history, count: int, V: int, aligned_rows: bool = False) -> int:
+    """history [count, >= V] -> the row stride the C entry takes"""
+    if not isinstance(history, torch.Tensor) or history.dtype not in HISTORY_DTYPES or history.dim() != 2 or history.shape[0] != count \
+            or history.shape[1] < V or history.stride(1) != 1 or (aligned_rows and history.stride(0) % 4):
+        raise RuntimeError(f"mobilequant_amd: {who} history must be int32 (uint32 bits) [{count}, >= {V}] with unit column stride")
+    return history.stride(0) if count > 1 else max(V, history.stride(0))
+
+
+def _check_bias_rows(who: str, bias, count: int, V: int, unit: str) -> list:
+    brows = list(bias)
+    if len(brows) != count:
+        raise RuntimeError(f"mobilequant_amd: {who} got {len(brows)} bias rows for {count} {unit}")
+    if not all(b is None or _is_row(b, (torch.float32,), V) for b in brows):
+        raise RuntimeError(f"mobilequant_amd: a {who} bias row must be a contiguous fp32 [{V}] tensor")
+    return brows
+
+
+def _place(who: str, dev, **tensors) -> list:
+    """The device checks, behind all others: a tensor of the caller's must be a ROCm device tensor; a host array of _packed goes to dev."""
+    from .ops import _dev
+    return [None if t is None else torch.from_numpy(t.view(np.uint8).reshape(-1)).to(dev) if isinstance(t, np.ndarray) else _dev(t, f"{who} {what}")
+            for what, t in tensors.items()]
+
+
+def _bias_table(who: str, dev, brows) -> Optional[torch.Tensor]:
+    """[count] int64 on dev: each row's bias pointer, or NULL"""
+    from .ops import _dev
+    if brows is None:
+        return None
+    return torch.tensor([0 if b is None else _dev(b, who + " bias").data_ptr() for b in brows], dtype=torch.int64).to(dev)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
 def sample(logits: torch.Tensor, pos: torch.Tensor, params_rows, tok: torch.Tensor, *, cache_len: int = 2 ** 31 - 1,
            kept: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None, penalties=None,
            history: Optional[torch.Tensor] = None, bias=None, observe: bool = False) -> torch.Tensor:
@@ -428,74 +524,40 @@ def sample(logits: torch.Tensor, pos: torch.Tensor, params_rows, tok: torch.Tens
     int32 (the uint32 entries: bit 31 = in the prompt, bits 0..15 = times generated) is required; penalties: a uint8 device tensor
     holding the mq_sample_penalty_row array, or per row a SamplingParams or (repetition, presence, frequency) (default: the
     SamplingParams of params_rows, else neutral); bias: None, or per row None or a dense fp32 [V] device tensor; observe: count each
-    drawn token in its row's history.  The logits are not written."""
+    drawn token in its row's history.  The logits are not written.
+    Like sample_rows and sample_ragged, every shape, dtype and value is checked before any tensor's device: a call that is wrong in both
+    ways (fp64 logits on the CPU, say) reports the former."""
     from .ops import _dev, _on, _stream
-    _dev(logits, "sample logits")
-    if logits.dim() == 1:
-        logits = logits.view(1, -1)
-    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
-        raise RuntimeError("mobilequant_amd: sample logits must be fp32 [rows, V] with unit column stride")
-    rows, V = logits.shape
-    if not 1 <= rows <= MAX_ROWS:
-        raise RuntimeError(f"mobilequant_amd: sample rows={rows} outside 1..{MAX_ROWS}")
-    if isinstance(params_rows, torch.Tensor):
-        pr = _dev(params_rows, "sample params_rows")
-        if pr.dtype != torch.uint8 or pr.numel() != rows * ROW_DTYPE.itemsize or not pr.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample params_rows must be {rows * ROW_DTYPE.itemsize} contiguous uint8 bytes")
-    else:
-        host = pack_rows(*params_rows)
-        if len(host) != rows:
-            raise RuntimeError(f"mobilequant_amd: sample got {len(host)} requests for {rows} rows")
-        pr = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(logits.device)
-    for t, dt, what in ((pos, torch.int32, "pos"), (tok, torch.int64, "tok"), (kept, torch.int32, "kept"), (logprob, torch.float32, "logprob")):
-        if t is None:
-            continue
-        _dev(t, "sample " + what)
-        if t.dtype != dt or t.numel() != rows or not t.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample {what} must be contiguous {dt} [{rows}]")
-    a = MqSampleArgs()
-    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=logits.device)
-    a.logits, a.logits_stride, a.V, a.rows = logits.data_ptr(), logits.stride(0) if rows > 1 else max(V, logits.stride(0)), V, rows
-    a.pos, a.cache_len, a.params, a.tok = pos.data_ptr(), int(cache_len), pr.data_ptr(), tok.data_ptr()
-    a.kept = kept.data_ptr() if kept is not None else None
-    a.logprob = logprob.data_ptr() if logprob is not None else None
-    a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
-    if penalties is None and history is None and bias is None and not observe:
+    who = "sample"
+    logits, rows, V = _check_logits(who, logits)
+    pr, _ = _packed(who, "params_rows", params_rows, lambda p: pack_rows(*p), ROW_DTYPE, rows, "requests")
+    _check_vectors(who, (pos, torch.int32, rows, "pos", True), (tok, torch.int64, rows, "tok", True), (kept, torch.int32, rows, "kept", False),
+                   (logprob, torch.float32, rows, "logprob", False))
+    penalized = penalties is not None or history is not None or bias is not None or bool(observe)
+    if penalized:
+        if history is None:
+            raise RuntimeError("mobilequant_amd: sample with penalties=, bias= or observe= needs history=")
+        if isinstance(history, torch.Tensor) and history.dim() == 1:
+            history = history.view(1, -1)
+        hstride = _check_history_block(who, history, rows, V)
+        if penalties is None:
+            penalties = params_rows[0] if not isinstance(params_rows, torch.Tensor) else [(1.0, 0.0, 0.0)] * rows
+        pen, _ = _packed(who, "penalties", penalties, lambda p: pack_penalty_rows(list(p)), PENALTY_DTYPE, rows, "penalty rows")
+        brows = None if bias is None else _check_bias_rows(who, bias, rows, V, "rows")
+    dev = _dev(logits, who + " logits").device
+    pr, pos, tok, kept, logprob = _place(who, dev, params_rows=pr, pos=pos, tok=tok, kept=kept, logprob=logprob)
+    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+    a = _fill_shared(MqSampleArgs(), logits, rows, pr, tok, scratch, kept, logprob)
+    a.pos, a.cache_len = pos.data_ptr(), int(cache_len)
+    if not penalized:
         with _on(logits, pos, pr, tok):
             _lib.call("mq_sample", ctypes.byref(a), _stream())
         return tok
-    if history is None:
-        raise RuntimeError("mobilequant_amd: sample with penalties=, bias= or observe= needs history=")
-    _dev(history, "sample history")
-    if history.dim() == 1:
-        history = history.view(1, -1)
-    if history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 2 or history.shape[0] != rows \
-            or history.shape[1] < V or history.stride(1) != 1:
-        raise RuntimeError(f"mobilequant_amd: sample history must be int32 (uint32 bits) [{rows}, >= {V}] with unit column stride")
-    if penalties is None:
-        penalties = params_rows[0] if not isinstance(params_rows, torch.Tensor) else [(1.0, 0.0, 0.0)] * rows
-    if isinstance(penalties, torch.Tensor):
-        pen = _dev(penalties, "sample penalties")
-        if pen.dtype != torch.uint8 or pen.numel() != rows * PENALTY_DTYPE.itemsize or not pen.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample penalties must be {rows * PENALTY_DTYPE.itemsize} contiguous uint8 bytes")
-    else:
-        host = pack_penalty_rows(list(penalties))
-        if len(host) != rows:
-            raise RuntimeError(f"mobilequant_amd: sample got {len(host)} penalty rows for {rows} rows")
-        pen = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(logits.device)
-    bias_ptr = None
-    if bias is not None:
-        brows = list(bias)
-        if len(brows) != rows:
-            raise RuntimeError(f"mobilequant_amd: sample got {len(brows)} bias rows for {rows} rows")
-        for b in brows:
-            if b is not None and (_dev(b, "sample bias").dtype != torch.float32 or b.dim() != 1 or b.numel() < V or not b.is_contiguous()):
-                raise RuntimeError(f"mobilequant_amd: a sample bias row must be a contiguous fp32 [{V}] tensor")
-        bias_ptr = torch.tensor([0 if b is None else b.data_ptr() for b in brows], dtype=torch.int64).to(logits.device)
+    history, pen = _place(who, dev, history=history, penalties=pen)
+    bias_ptr = _bias_table(who, dev, brows)
     p = MqSamplePenalizedArgs()
     p.s = a
-    p.penalty, p.history, p.history_stride = pen.data_ptr(), history.data_ptr(), history.stride(0) if rows > 1 else max(V, history.stride(0))
-    p.bias, p.observe = (bias_ptr.data_ptr() if bias_ptr is not None else None), int(bool(observe))
+    p.penalty, p.history, p.history_stride, p.bias, p.observe = pen.data_ptr(), history.data_ptr(), hstride, _ptr(bias_ptr), int(bool(observe))
     with _on(logits, pos, pr, tok):
         _lib.call("mq_sample_penalized", ctypes.byref(p), _stream())
     return tok
@@ -511,51 +573,26 @@ def sample_rows(logits: torch.Tensor, n_base: torch.Tensor, n_offset: int, param
     the rows; penalties: None (params' own), a SamplingParams or (repetition, presence, frequency); bias: None or a dense fp32 [>= V]
     device row.  Row j sees the history with proposals[:j] counted; nothing but the outputs is written."""
     from .ops import _dev, _on, _stream
-    if isinstance(logits, torch.Tensor) and logits.dim() == 1:
-        logits = logits.view(1, -1)
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
-        raise RuntimeError("mobilequant_amd: sample_rows logits must be fp32 [rows, V] with unit column stride")
-    rows, V = logits.shape
-    if not 1 <= rows <= MAX_ROWS:
-        raise RuntimeError(f"mobilequant_amd: sample_rows rows={rows} outside 1..{MAX_ROWS}")
+    who = "sample_rows"
+    logits, rows, V = _check_logits(who, logits)
     if not isinstance(params, SamplingParams):
         raise TypeError(f"mobilequant_amd: sample_rows expected SamplingParams, got {type(params).__name__}")
-    if isinstance(n_offset, bool) or not isinstance(n_offset, (int, np.integer)) or not -2 ** 30 <= int(n_offset) <= 2 ** 30:
-        raise ValueError(f"mobilequant_amd: sample_rows n_offset={n_offset!r} must be an int in [-2^30, 2^30]")
-    host = pack_rows([params], [stream])
-    _dev(logits, "sample_rows logits")
-    pr = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(logits.device)
-    for t, dt, n, what in ((n_base, torch.int32, 1, "n_base"), (tok, torch.int64, rows, "tok"), (kept, torch.int32, rows, "kept"),
-                           (logprob, torch.float32, rows, "logprob"), (proposals, torch.int64, rows - 1, "proposals")):
-        if t is None:
-            if what in ("n_base", "tok") or (what == "proposals" and rows > 1):
-                raise RuntimeError(f"mobilequant_amd: sample_rows needs {what} ({dt} [{n}])")
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != n or not t.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample_rows {what} must be contiguous {dt} [{n}]")
-        _dev(t, "sample_rows " + what)
-    if history is not None:
-        if not isinstance(history, torch.Tensor) or history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 1 or history.numel() < V \
-                or not history.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample_rows history must be one contiguous int32 (uint32 bits) row [>= {V}]")
-        _dev(history, "sample_rows history")
-    if bias is not None:
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() < V or not bias.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample_rows bias must be a contiguous fp32 [>= {V}] tensor")
-        _dev(bias, "sample_rows bias")
-    pen_src = params if penalties is None else penalties
-    pen = torch.from_numpy(pack_penalty_rows([pen_src]).view(np.uint8).reshape(-1)).to(logits.device)
-    a = MqSampleRowsArgs()
-    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=logits.device)
-    a.logits, a.logits_stride, a.V, a.rows = logits.data_ptr(), logits.stride(0) if rows > 1 else max(V, logits.stride(0)), V, rows
-    a.n_base, a.n_offset, a.params, a.penalty = n_base.data_ptr(), int(n_offset), pr.data_ptr(), pen.data_ptr()
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.history = history.data_ptr() if history is not None else None
-    a.proposals = proposals.data_ptr() if proposals is not None and rows > 1 else None
-    a.tok = tok.data_ptr()
-    a.kept = kept.data_ptr() if kept is not None else None
-    a.logprob = logprob.data_ptr() if logprob is not None else None
-    a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+    n_offset = _check_n_offset(who, n_offset)
+    pr = pack_rows([params], [stream])
+    _check_vectors(who, (n_base, torch.int32, 1, "n_base", True), (tok, torch.int64, rows, "tok", True), (kept, torch.int32, rows, "kept", False),
+                   (logprob, torch.float32, rows, "logprob", False), (proposals, torch.int64, rows - 1, "proposals", rows > 1))
+    if history is not None and not _is_row(history, HISTORY_DTYPES, V):
+        raise RuntimeError(f"mobilequant_amd: sample_rows history must be one contiguous int32 (uint32 bits) row [>= {V}]")
+    if bias is not None and not _is_row(bias, (torch.float32,), V):
+        raise RuntimeError(f"mobilequant_amd: sample_rows bias must be a contiguous fp32 [>= {V}] tensor")
+    pen = pack_penalty_rows([params if penalties is None else penalties])
+    dev = _dev(logits, who + " logits").device
+    pr, n_base, tok, kept, logprob, proposals, history, bias, pen = _place(
+        who, dev, params=pr, n_base=n_base, tok=tok, kept=kept, logprob=logprob, proposals=proposals, history=history, bias=bias, penalties=pen)
+    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+    a = _fill_shared(MqSampleRowsArgs(), logits, rows, pr, tok, scratch, kept, logprob)
+    a.n_base, a.n_offset, a.penalty, a.bias, a.history = n_base.data_ptr(), n_offset, pen.data_ptr(), _ptr(bias), _ptr(history)
+    a.proposals = _ptr(proposals) if rows > 1 else None
     with _on(logits, n_base, pr, tok):
         _lib.call("mq_sample_rows", ctypes.byref(a), _stream())
     return tok
@@ -575,74 +612,31 @@ def sample_ragged(logits: torch.Tensor, row_seq: torch.Tensor, row_pos: torch.Te
     zeros) or int32 (uint32 bits) [batch, >= V]; bias: None, or per sequence None or a dense fp32 [V] device tensor.  Nothing but the
     outputs is written."""
     from .ops import _dev, _on, _stream
-    if isinstance(logits, torch.Tensor) and logits.dim() == 1:
-        logits = logits.view(1, -1)
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
-        raise RuntimeError("mobilequant_amd: sample_ragged logits must be fp32 [rows, V] with unit column stride")
-    rows, V = logits.shape
-    if not 1 <= rows <= MAX_ROWS:
-        raise RuntimeError(f"mobilequant_amd: sample_ragged rows={rows} outside 1..{MAX_ROWS}")
-    if isinstance(n_offset, bool) or not isinstance(n_offset, (int, np.integer)) or not -2 ** 30 <= int(n_offset) <= 2 ** 30:
-        raise ValueError(f"mobilequant_amd: sample_ragged n_offset={n_offset!r} must be an int in [-2^30, 2^30]")
-    host = None
-    if isinstance(params_rows, torch.Tensor):
-        if params_rows.dtype != torch.uint8 or params_rows.numel() % ROW_DTYPE.itemsize or not params_rows.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample_ragged params_rows must be contiguous uint8 bytes, {ROW_DTYPE.itemsize} per sequence")
-        batch = params_rows.numel() // ROW_DTYPE.itemsize
-    else:
-        host = pack_rows(*params_rows)
-        batch = len(host)
+    who = "sample_ragged"
+    logits, rows, V = _check_logits(who, logits)
+    n_offset = _check_n_offset(who, n_offset)
+    pr, batch = _packed(who, "params_rows", params_rows, lambda p: pack_rows(*p), ROW_DTYPE, None)
     if not 1 <= batch <= MAX_ROWS:
         raise RuntimeError(f"mobilequant_amd: sample_ragged batch={batch} outside 1..{MAX_ROWS}")
-    _dev(logits, "sample_ragged logits")
-    pr = _dev(params_rows, "sample_ragged params_rows") if host is None else torch.from_numpy(host.view(np.uint8).reshape(-1)).to(logits.device)
-    for t, dt, what in ((row_seq, torch.int32, "row_seq"), (row_pos, torch.int32, "row_pos"), (row_tok, torch.int64, "row_tok"), (tok, torch.int64, "tok"),
-                        (kept, torch.int32, "kept"), (logprob, torch.float32, "logprob")):
-        if t is None:
-            if what in ("kept", "logprob"):
-                continue
-            raise RuntimeError(f"mobilequant_amd: sample_ragged needs {what} ({dt} [{rows}])")
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != rows or not t.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample_ragged {what} must be contiguous {dt} [{rows}]")
-        _dev(t, "sample_ragged " + what)
-    if history is not None:
-        if not isinstance(history, torch.Tensor) or history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 2 \
-                or history.shape[0] != batch or history.shape[1] < V or history.stride(1) != 1 or history.stride(0) % 4:
-            raise RuntimeError(f"mobilequant_amd: sample_ragged history must be int32 (uint32 bits) [{batch}, >= {V}] with unit column stride")
-        _dev(history, "sample_ragged history")
-    if penalties is None and host is not None:
+    _check_vectors(who, (row_seq, torch.int32, rows, "row_seq", True), (row_pos, torch.int32, rows, "row_pos", True),
+                   (row_tok, torch.int64, rows, "row_tok", True), (tok, torch.int64, rows, "tok", True), (kept, torch.int32, rows, "kept", False),
+                   (logprob, torch.float32, rows, "logprob", False))
+    hstride = V if history is None else _check_history_block(who, history, batch, V, aligned_rows=True)
+    if penalties is None and not isinstance(params_rows, torch.Tensor):
         penalties = params_rows[0]
     pen = None
-    if isinstance(penalties, torch.Tensor):
-        pen = _dev(penalties, "sample_ragged penalties")
-        if pen.dtype != torch.uint8 or pen.numel() != batch * PENALTY_DTYPE.itemsize or not pen.is_contiguous():
-            raise RuntimeError(f"mobilequant_amd: sample_ragged penalties must be {batch * PENALTY_DTYPE.itemsize} contiguous uint8 bytes")
-    elif penalties is not None:
-        hp = pack_penalty_rows(list(penalties))
-        if len(hp) != batch:
-            raise RuntimeError(f"mobilequant_amd: sample_ragged got {len(hp)} penalty rows for {batch} sequences")
-        pen = torch.from_numpy(hp.view(np.uint8).reshape(-1)).to(logits.device)
-    bias_ptr = None
-    if bias is not None:
-        brows = list(bias)
-        if len(brows) != batch:
-            raise RuntimeError(f"mobilequant_amd: sample_ragged got {len(brows)} bias rows for {batch} sequences")
-        for b in brows:
-            if b is not None and (_dev(b, "sample_ragged bias").dtype != torch.float32 or b.dim() != 1 or b.numel() < V or not b.is_contiguous()):
-                raise RuntimeError(f"mobilequant_amd: a sample_ragged bias row must be a contiguous fp32 [{V}] tensor")
-        bias_ptr = torch.tensor([0 if b is None else b.data_ptr() for b in brows], dtype=torch.int64).to(logits.device)
-    a = MqSampleRaggedArgs()
-    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=logits.device)
-    a.logits, a.logits_stride, a.V, a.rows = logits.data_ptr(), logits.stride(0) if rows > 1 else max(V, logits.stride(0)), V, rows
-    a.batch, a.cache_len, a.n_offset = batch, int(cache_len), int(n_offset)
-    a.row_seq, a.row_pos, a.row_tok, a.params, a.tok = row_seq.data_ptr(), row_pos.data_ptr(), row_tok.data_ptr(), pr.data_ptr(), tok.data_ptr()
-    a.penalty = pen.data_ptr() if pen is not None else None
-    a.history = history.data_ptr() if history is not None else None
-    a.history_stride = (history.stride(0) if batch > 1 else max(V, history.stride(0))) if history is not None else V
-    a.bias = bias_ptr.data_ptr() if bias_ptr is not None else None
-    a.kept = kept.data_ptr() if kept is not None else None
-    a.logprob = logprob.data_ptr() if logprob is not None else None
-    a.scratch, a.scratch_bytes = scratch.data_ptr(), MQ_SAMPLE_SCRATCH_BYTES
+    if penalties is not None:
+        pen, _ = _packed(who, "penalties", penalties, lambda p: pack_penalty_rows(list(p)), PENALTY_DTYPE, batch, "penalty rows", "sequences")
+    brows = None if bias is None else _check_bias_rows(who, bias, batch, V, "sequences")
+    dev = _dev(logits, who + " logits").device
+    pr, row_seq, row_pos, row_tok, tok, kept, logprob, history, pen = _place(
+        who, dev, params_rows=pr, row_seq=row_seq, row_pos=row_pos, row_tok=row_tok, tok=tok, kept=kept, logprob=logprob, history=history, penalties=pen)
+    bias_ptr = _bias_table(who, dev, brows)
+    scratch = torch.empty(MQ_SAMPLE_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+    a = _fill_shared(MqSampleRaggedArgs(), logits, rows, pr, tok, scratch, kept, logprob)
+    a.batch, a.cache_len, a.n_offset = batch, int(cache_len), n_offset
+    a.row_seq, a.row_pos, a.row_tok = row_seq.data_ptr(), row_pos.data_ptr(), row_tok.data_ptr()
+    a.penalty, a.history, a.history_stride, a.bias = _ptr(pen), _ptr(history), hstride, _ptr(bias_ptr)
     with _on(logits, row_seq, pr, tok):
         _lib.call("mq_sample_ragged", ctypes.byref(a), _stream())
     return tok
@@ -653,21 +647,15 @@ def history_count_ragged(history: torch.Tensor, pairs: torch.Tensor, delta: int)
     column count): pairs is an int64 device tensor [n, 2] of (sequence, id); the count (bits 0..15) of each pair's id in its sequence's
     history moves by delta = +1 or -1, saturating at 65 535 and at 0.  Bit 31 is kept; a pair whose sequence is outside [0, batch) or
     whose id is outside [0, V) is ignored on the device; pairs repeat.  One launch for all sequences (none for n = 0), capturable."""
-    if isinstance(delta, bool) or delta not in (1, -1):
-        raise ValueError(f"mobilequant_amd: history_count_ragged delta={delta!r} must be +1 or -1")
-    if not isinstance(history, torch.Tensor) or history.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or history.dim() != 2 \
-            or not 1 <= history.shape[0] <= MAX_ROWS or history.stride(1) != 1 or history.stride(0) < history.shape[1] or history.stride(0) % 4:
-        raise RuntimeError(f"mobilequant_amd: history_count_ragged history must be int32 (uint32 bits) [1..{MAX_ROWS}, V] with unit column stride")
-    if not history.is_cuda:
-        raise RuntimeError("mobilequant_amd: history_count_ragged history must be a ROCm device tensor; there is no CPU path")
-    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int64 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
-        raise RuntimeError("mobilequant_amd: history_count_ragged pairs must be a contiguous int64 [n, 2] tensor of (sequence, id)")
-    if pairs.device != history.device:
-        raise RuntimeError("mobilequant_amd: history_count_ragged pairs must be a ROCm device tensor on the history's device")
+    h = history
+    ok = isinstance(h, torch.Tensor) and h.dtype in HISTORY_DTYPES and h.dim() == 2 and 1 <= h.shape[0] <= MAX_ROWS and h.stride(1) == 1 \
+        and h.stride(0) >= h.shape[1] and h.stride(0) % 4 == 0
+    _check_count("history_count_ragged", delta, h, ok, f"int32 (uint32 bits) [1..{MAX_ROWS}, V] with unit column stride",
+                 pairs, "pairs", _is_ids(pairs, 2) and pairs.shape[1] == 2, "int64 [n, 2] tensor of (sequence, id)")
     n = pairs.shape[0]
-    with torch.cuda.device(history.device):
-        _lib.call("mq_sample_history_count_ragged", history.data_ptr(), history.stride(0), history.shape[1], history.shape[0],
-                  pairs.data_ptr() if n else None, n, int(delta), torch.cuda.current_stream(history.device).cuda_stream)
+    with torch.cuda.device(h.device):
+        _lib.call("mq_sample_history_count_ragged", h.data_ptr(), h.stride(0), h.shape[1], h.shape[0], pairs.data_ptr() if n else None, n, int(delta),
+                  torch.cuda.current_stream(h.device).cuda_stream)
     return history
 
 

@@ -10,6 +10,7 @@ import tempfile
 
 import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -180,7 +181,7 @@ def test_no_barrier_with_lds_traffic_in_flight(tmp_path):
     rep = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "barrier_audit.py"), asm], stdout=subprocess.PIPE, text=True).stdout
     assert "PENDING" not in rep and "possibly in flight 0" in rep, rep
     text = open(asm).read()
-    assert re.search(r"sample_select_kernel", text) and re.search(r"sample_scan_kernel", text)
+    assert re.search(r"sample_select_kernelINS\S*9NoPenalty", text) and re.search(r"sample_scan_kernelINS\S*9NoPenalty", text)
     assert "ds_add_u64" in text                                     # the mass histogram is 64-bit LDS integer atomics
 
 
@@ -216,6 +217,34 @@ def test_pack_rows_lays_out_mq_sample_row():
         pack_rows([SamplingParams()], [-1])
     with pytest.raises(TypeError):
         pack_rows([0.7], [0])
+
+
+def _one_shot(name, lg):
+    """sampling.<name> over the logits lg with every other argument sized to its rows, all on the CPU."""
+    from mobilequant_amd import SamplingParams, sampling
+    sp = SamplingParams(temperature=0.8, seed=1)
+    rows = 1 if lg.dim() == 1 else lg.shape[0]
+    i32, i64 = torch.zeros(rows, dtype=torch.int32), torch.zeros(rows, dtype=torch.int64)
+    if name == "sample":
+        return sampling.sample(lg, i32, ([sp] * rows, list(range(rows))), i64)
+    if name == "sample_rows":
+        return sampling.sample_rows(lg, torch.zeros(1, dtype=torch.int32), 0, sp, 0, i64, proposals=torch.zeros(max(rows - 1, 0), dtype=torch.int64))
+    return sampling.sample_ragged(lg, i32, i32.clone(), i64, 1, ([sp, sp], [0, 1]), i64.clone())
+
+
+@pytest.mark.parametrize("name", ["sample", "sample_rows", "sample_ragged"])
+def test_the_one_shot_functions_check_their_logits_alike_and_before_any_device(name):
+    with pytest.raises(RuntimeError, match="ROCm device tensor"):
+        _one_shot(name, torch.zeros(4, 160))
+    with pytest.raises(RuntimeError, match="fp32"):
+        _one_shot(name, torch.zeros(4, 160).double())
+    for rows in (0, 9):
+        with pytest.raises(RuntimeError, match="outside 1..8"):
+            _one_shot(name, torch.zeros(rows, 160))
+    with pytest.raises(RuntimeError, match="unit column stride"):
+        _one_shot(name, torch.zeros(160, 4).t())
+    with pytest.raises(RuntimeError, match="ROCm device tensor"):
+        _one_shot(name, torch.zeros(160))                             # 1-D logits are one row: only the device is wrong
 
 
 def test_engines_refuse_sampling_with_do_sample_or_a_draft_before_touching_the_device():

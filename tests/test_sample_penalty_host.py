@@ -164,7 +164,7 @@ def test_rejects_argument_blocks_outside_the_limits(lib):
 
 
 def test_no_barrier_with_lds_traffic_in_flight_in_the_penalised_instantiations(tmp_path):
-    """tools/barrier_audit.py on mq_sample.hip with the penalised kernels in it; the plain kernels keep their names."""
+    """tools/barrier_audit.py on mq_sample.hip with the penalised instantiations in it, next to the plain ones."""
     from mobilequant_amd import build
     flags = [f for f in build.FLAGS if f != "-fPIC"]
     src = "mq_sample.hip"
@@ -175,10 +175,11 @@ def test_no_barrier_with_lds_traffic_in_flight_in_the_penalised_instantiations(t
     rep = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "barrier_audit.py"), asm], stdout=subprocess.PIPE, text=True).stdout
     assert "PENDING" not in rep and "possibly in flight 0" in rep, rep
     text = open(asm).read()
-    for k in ("sample_scan_kernel", "sample_select_kernel", "sample_scan_penalized_kernel", "sample_select_penalized_kernel"):
+    for k in (r"sample_scan_kernelINS\S*9NoPenalty", r"sample_select_kernelINS\S*9NoPenalty", r"sample_scan_kernelINS\S*7Penalty",
+              r"sample_select_kernelINS\S*7Penalty"):
         assert re.search(k, text), k
     # the penalised select kernel keeps no scratch memory and no static LDS of its own (the history is read from memory, never staged)
-    m = re.search(r"\.amdhsa_kernel \S*sample_select_penalized_kernel\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    m = re.search(r"\.amdhsa_kernel \S*sample_select_kernelINS\S*7Penalty\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
     assert m and re.search(r"\.amdhsa_group_segment_fixed_size 0\b", m.group(1)) and re.search(r"\.amdhsa_private_segment_fixed_size 0\b", m.group(1))
 
 

@@ -145,11 +145,11 @@ def test_the_ragged_kernels_keep_no_scratch_memory_and_no_static_lds(tmp_path):
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout[-2000:]
     text = open(asm).read()
-    for k in ("sample_scan_ragged_kernel", "sample_select_ragged_kernel", "history_count_ragged_kernel"):
+    for k in (r"sample_scan_kernelINS\S*6Ragged", r"sample_select_kernelINS\S*6Ragged", "history_count_ragged_kernel"):
         m = re.search(r"\.amdhsa_kernel \S*" + k + r"\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
         assert m, k
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", m.group(1)), k
-    m = re.search(r"\.amdhsa_kernel \S*sample_select_ragged_kernel\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    m = re.search(r"\.amdhsa_kernel \S*sample_select_kernelINS\S*6Ragged\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
     assert re.search(r"\.amdhsa_group_segment_fixed_size 0\b", m.group(1))
 
 

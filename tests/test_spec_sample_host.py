@@ -175,11 +175,11 @@ def test_the_new_kernels_keep_no_scratch_memory_and_no_static_lds(tmp_path):
     rep = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "barrier_audit.py"), asm], stdout=subprocess.PIPE, text=True).stdout
     assert "PENDING" not in rep and "possibly in flight 0" in rep, rep
     text = open(asm).read()
-    for k in ("sample_scan_rows_kernel", "sample_select_rows_kernel", "history_count_kernel"):
+    for k in (r"sample_scan_kernelINS\S*4Rows", r"sample_select_kernelINS\S*4Rows", "history_count_kernel"):
         m = re.search(r"\.amdhsa_kernel \S*" + k + r"\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
         assert m, k
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", m.group(1)), k
-    m = re.search(r"\.amdhsa_kernel \S*sample_select_rows_kernel\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    m = re.search(r"\.amdhsa_kernel \S*sample_select_kernelINS\S*4Rows\S*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
     assert re.search(r"\.amdhsa_group_segment_fixed_size 0\b", m.group(1))
 
 
