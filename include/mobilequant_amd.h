@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_lwc_search -- the clip search that initialises learnable weight clipping; + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -135,6 +135,20 @@ int mq_lwc_fake_quant(const float* w, int64_t rows, int64_t cols, const float* s
 int mq_lwc_fake_quant_backward(const float* w, const float* grad_out, int64_t rows, int64_t cols, const float* sig_lo,
                                const float* sig_hi, const float* row_min, const float* row_max, int bitwidth, int is_symmetric,
                                float* grad_w, float* grad_sig_lo, float* grad_sig_hi, mq_stream_t stream);
+
+/* Clip search for learnable weight clipping (no reference code: the reference obtains clip factors by training only): every
+ * row of w [rows, cols] (fp32; the per-channel weight [N, K] or the reference's reshape(-1, group_size)) is read once and scored under
+ * n_cand candidate pairs sig_lo[c], sig_hi[c] (fp32 on the device, shared by all rows: sigmoid(bound factor) already evaluated, as
+ * mq_lwc_fake_quant takes them per row).  cost[r, c] = the fp64 sum over the row of e * e (* col_weight), e = y - w in fp32 with y the
+ * value mq_lwc_fake_quant writes for that pair; the square is exact in fp64, the weighting is one rounding.  col_weight (NULL, or fp32
+ * [cw_len], cw_len a multiple of cols) is one vector over K: row r uses elements (r % (cw_len / cols)) * cols + i.  Candidate 0 is the
+ * incumbent; a later candidate wins only with a strictly smaller cost, so ties keep the lowest index and a row with a NaN reports
+ * index 0 (and NaN costs).  Writes best_idx (int32), best_cost, base_cost = cost[r, 0] (fp64), [rows] each, and, if costs is not
+ * NULL, the whole table costs [rows, n_cand] (fp64).  cols a multiple of 4 in [16, 16384], w and col_weight 16-byte aligned,
+ * 1 <= n_cand <= 1024, 2 <= bitwidth <= 16; rows == 0 returns MQ_OK without a launch. */
+int mq_lwc_search(const float* w, int64_t rows, int64_t cols, const float* sig_lo, const float* sig_hi, int64_t n_cand, int bitwidth,
+                  int is_symmetric, const float* col_weight, int64_t cw_len, int32_t* best_idx, double* best_cost, double* base_cost,
+                  double* costs, mq_stream_t stream);
 
 /* f3: what a training-mode attention block does to the [rows = batch * heads * S, cols = keys] scores between its two matmuls
  * (mobilellm/model/hf_model.py:511-520 with the QMatMuls of qmodule.py:408-466, under algorithm.py:381 / :587), in one pass:

@@ -185,6 +185,7 @@ _SIGNATURES = {
     "mq_fake_quant_backward": (c_int, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_float, c_float, _P, _P, _P, _P]),
     "mq_lwc_fake_quant": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "mq_lwc_fake_quant_backward": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P]),
+    "mq_lwc_search": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, c_int, c_int, _P, c_int64, _P, _P, _P, _P, _P]),
     "mq_attention_probs_train": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, _P, c_float, c_float, _P, _P, c_float, c_float, c_float, _P, _P]),
     "mq_attention_probs_train_backward": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_float, c_float, _P, _P, c_float, c_float,
                                                   c_float, _P, _P, _P]),

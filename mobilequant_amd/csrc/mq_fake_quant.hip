@@ -7,6 +7,7 @@
 // equal the reference CPU path's bit for bit.  The quantizer is the VALUE form of mq_quant.h.  Build flags: -ffp-contract=off,
 // no fast-math, -fhip-fp32-correctly-rounded-divide-sqrt (hipcc default, stated explicitly in build.py).
 #include "mq_common.h"
+#include "mq_lwc.h"
 
 #pragma clang fp contract(off)
 
@@ -111,33 +112,7 @@ __global__ void __launch_bounds__(256) fake_quant_scalar_kernel(const T* __restr
 // elements.  Here a workgroup owns a row, holds it in registers and does all of it: one read + one write of the weight forward, two
 // reads + one write backward.  Same fp32 operations in the same order as the module chain (scale_offset_kernel, index_value_keepnan,
 // fake_quant_bwd_kernel above), so forward values are bit-identical; the row sums of the backward associate differently (float4 per
-// thread) -- inside every gradient tolerance the goldens use.
-template <int VPT>
-struct LwcRow {
-  vf4 v[VPT];
-};
-
-struct LwcGrid {
-  float lo, hi, scale, offset, alpha;
-};
-// sigmoid(bound) * range -> grid: qmodule.py:271-273 then :40-61 (scale_offset_kernel's expression)
-__device__ __forceinline__ LwcGrid lwc_grid(float mn, float mx, float sig_lo, float sig_hi, float qmax, int symmetric) {
-  LwcGrid g;
-  g.lo = __fmul_rn(sig_lo, mn);
-  g.hi = __fmul_rn(sig_hi, mx);
-  float beta;
-  if (symmetric) {
-    g.alpha = (g.lo != g.lo || g.hi != g.hi) ? __fadd_rn(g.lo, g.hi) : fmaxf(fabsf(g.lo), fabsf(g.hi));
-    beta = 0.0f;
-  } else {
-    g.alpha = __fsub_rn(g.hi, g.lo);
-    beta = g.lo;
-  }
-  g.scale = clamp_nan(__fdiv_rn(g.alpha, qmax), 1e-5f, 1e6f);
-  g.offset = -rintf(__fdiv_rn(beta, g.scale));
-  return g;
-}
-
+// thread) -- inside every gradient tolerance the goldens use.  (LwcRow, LwcGrid, lwc_grid: mq_lwc.h, shared with the clip search.)
 template <int VPT>
 __global__ void __launch_bounds__(256) lwc_fake_quant_kernel(const float* __restrict__ w, int cols, const float* __restrict__ sig_lo,
                                                              const float* __restrict__ sig_hi, float qmin, float qmax, int symmetric,

@@ -355,6 +355,52 @@ def lwc_fake_quant_backward(w, grad_out, sig_lo, sig_hi, row_min, row_max, bitwi
     return gw, glo, ghi
 
 
+LWC_SEARCH_MAX_CANDIDATES = 1024
+
+
+def lwc_search(w2d: torch.Tensor, sig_lo: torch.Tensor, sig_hi: torch.Tensor, bitwidth: int, is_symmetric: bool,
+               col_weight: Optional[torch.Tensor] = None, return_costs: bool = False):
+    """Clip search over a weight viewed [rows, cols] (mq_lwc_search): every row is scored under the C candidate pairs sig_lo[c], sig_hi[c]
+    (fp32 [C], sigmoid(bound factor) already evaluated) by the fp64 sum of (Q(w) - w)^2 (* col_weight), Q the LWC fake-quant of
+    lwc_fake_quant at that pair.  col_weight: fp32, a multiple of cols long; row r uses elements (r % (len / cols)) * cols + i.
+    Returns (best_idx int32 [rows], best_cost fp64 [rows], base_cost fp64 [rows] = the cost of candidate 0) and, with return_costs, the
+    table costs fp64 [rows, C].  Candidate 0 is the incumbent, a later one wins only with a strictly smaller cost.
+    The arguments' dtypes and shapes are checked first (nothing is converted: what was scored is what the caller holds), the device last."""
+    for t, what in ((w2d, "w2d"), (sig_lo, "sig_lo"), (sig_hi, "sig_hi"), (col_weight, "col_weight")):
+        if t is None and what == "col_weight":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise RuntimeError(f"mobilequant_amd: lwc_search takes float32 tensors ({what}: {getattr(t, 'dtype', type(t))})")
+        if not t.is_contiguous():
+            raise RuntimeError(f"mobilequant_amd: lwc_search takes contiguous tensors ({what})")
+    if w2d.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: lwc_search takes the weight viewed [rows, cols] (got {tuple(w2d.shape)})")
+    rows, cols = w2d.shape
+    if cols % 4 != 0 or not 16 <= cols <= 16384:
+        raise RuntimeError(f"mobilequant_amd: lwc_search takes rows of 16 to 16384 columns, a multiple of 4 (cols={cols})")
+    if sig_lo.dim() != 1 or sig_lo.shape != sig_hi.shape:
+        raise RuntimeError(f"mobilequant_amd: lwc_search takes two candidate tables [C] of one length (got {tuple(sig_lo.shape)}, {tuple(sig_hi.shape)})")
+    C = sig_lo.numel()
+    if not 1 <= C <= LWC_SEARCH_MAX_CANDIDATES:
+        raise RuntimeError(f"mobilequant_amd: lwc_search takes 1 to {LWC_SEARCH_MAX_CANDIDATES} candidates (got {C})")
+    if not 2 <= int(bitwidth) <= 16:
+        raise RuntimeError(f"mobilequant_amd: lwc_search bitwidth={bitwidth} outside 2..16")
+    if col_weight is not None and (col_weight.dim() != 1 or col_weight.numel() < cols or col_weight.numel() % cols != 0):
+        raise RuntimeError(f"mobilequant_amd: lwc_search col_weight holds a multiple of cols={cols} entries (got {tuple(col_weight.shape)})")
+    for t, what in ((w2d, "w2d"), (sig_lo, "sig_lo"), (sig_hi, "sig_hi"), (col_weight, "col_weight")):
+        if t is not None:
+            _dev(t, what)
+    dev = w2d.device
+    idx = torch.empty(rows, dtype=torch.int32, device=dev)
+    best, base = torch.empty(rows, dtype=torch.float64, device=dev), torch.empty(rows, dtype=torch.float64, device=dev)
+    costs = torch.empty((rows, C), dtype=torch.float64, device=dev) if return_costs else None
+    with _on(w2d, sig_lo, sig_hi, col_weight):
+        _lib.call("mq_lwc_search", w2d.data_ptr(), rows, cols, sig_lo.data_ptr(), sig_hi.data_ptr(), C, int(bitwidth), int(bool(is_symmetric)),
+                  col_weight.data_ptr() if col_weight is not None else None, col_weight.numel() if col_weight is not None else 0,
+                  idx.data_ptr(), best.data_ptr(), base.data_ptr(), costs.data_ptr() if return_costs else None, _stream())
+    return (idx, best, base, costs) if return_costs else (idx, best, base)
+
+
 def attention_probs_train_supported(raw: torch.Tensor, mask: Optional[torch.Tensor]) -> bool:
     if not (raw.is_cuda and raw.dtype == torch.float32 and raw.dim() >= 2 and raw.is_contiguous() and raw.shape[-1] % 4 == 0
             and 0 < raw.shape[-1] <= 4096 and raw.data_ptr() % 16 == 0):

@@ -24,7 +24,7 @@ import threading
 import weakref
 from copy import deepcopy
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -282,6 +282,33 @@ class _RangeFn(torch.autograd.Function):
         return gx.to(x2.dtype), None
 
 
+LWC_INIT_FACTOR = 4.0          # the bound factor enable_lwc starts every row from (qmodule.py:147-148): sigmoid(4) = 0.982 of the range
+
+
+def lwc_factor_table(n_grid: int = 64, min_ratio: float = 0.5) -> torch.Tensor:
+    """The default candidate table of Quantizer.search_lwc: fp32 bound factors whose sigmoids are n_grid shrink ratios evenly spaced from
+    sigmoid(4) -- the reference's own init, entry 0, exactly 4.0 -- down to min_ratio; factor = float32(logit(ratio)), strictly decreasing."""
+    top = 1.0 / (1.0 + math.exp(-LWC_INIT_FACTOR))
+    if int(n_grid) < 1 or not 0.0 < float(min_ratio) < top:
+        raise ValueError(f"mobilequant_amd: lwc_factor_table needs n_grid >= 1 and 0 < min_ratio < sigmoid(4) (got {n_grid}, {min_ratio})")
+    n = int(n_grid)
+    ratios = [top + (float(min_ratio) - top) * i / (n - 1) for i in range(n)] if n > 1 else [top]
+    f = torch.tensor([math.log(r / (1.0 - r)) for r in ratios], dtype=torch.float64).to(torch.float32)
+    f[0] = LWC_INIT_FACTOR
+    if n > 1 and not bool((f[1:] < f[:-1]).all()):
+        raise ValueError(f"mobilequant_amd: {n} ratios between sigmoid(4) and {min_ratio} are not distinct in fp32")
+    return f
+
+
+class LwcSearchReport(NamedTuple):
+    """What Quantizer.search_lwc did: rows searched, rows whose best candidate is not candidate 0 (the 4.0 init), and the fp64 sums over
+    the rows of the cost at candidate 0 and at the chosen candidate."""
+    rows: int
+    clipped_rows: int
+    base_cost: float
+    best_cost: float
+
+
 class Quantizer(nn.Module):
     """Fake-quantizer with cached or on-the-fly (scale, offset) (reference: qmodule.py:112-295)."""
 
@@ -357,6 +384,68 @@ class Quantizer(nn.Module):
             self.disable_lwc()
         x = torch.maximum(torch.minimum(x, mx.to(x.dtype)), mn.to(x.dtype))
         return x.reshape(input_.shape).type(input_.dtype)
+
+    def lwc_search_skip_reason(self, w) -> Optional[str]:
+        """None when search_lwc can run on weight w, else why not (in words, for search_weight_clipping's list)."""
+        if self.bypassed():
+            return "weight quantizer is bypassed"
+        if not self.qcfg.is_per_channel:
+            return "per-tensor weight grid"
+        if self.qcfg.bitwidth > 8:
+            return f"{self.qcfg.bitwidth}-bit weight grid"
+        if self.qcfg.is_dynamic:
+            return "dynamic weight grid"
+        if not torch.is_tensor(w) or w.dim() != 2:
+            return "weight is not 2-D"
+        g = self.qcfg.group_size
+        cols = w.shape[1] if g == -1 else g
+        if g != -1 and w.shape[1] % g != 0:
+            return f"group_size {g} does not divide K = {w.shape[1]}"
+        if cols % 4 != 0 or not 16 <= cols <= 16384:
+            return f"rows of {cols} columns (the search takes 16 to 16384, a multiple of 4)"
+        return None
+
+    @torch.no_grad()
+    def search_lwc(self, w, *, factors=None, n_grid=64, min_ratio=0.5, col_weight=None, mode="joint") -> LwcSearchReport:
+        """Initialise learnable weight clipping by search instead of by the constant 4.0 (no reference code: DESIGN.md 4.7b).  Every row
+        (output row, or group with group_size) of w is scored by mq_lwc_search under a table of bound factors and gets the pair with the
+        least sum of (Q(w) - w)^2, optionally weighted per input channel by col_weight [K]; the factors land in lowbound_factor /
+        upbound_factor (enable_lwc is called if LWC is off), so afterwards this is an ordinary LWC quantizer: trainable, foldable by
+        run_lwc.  factors: fp32 vector with factors[0] == 4.0, the reference's init (the result is never worse than enable_lwc's state);
+        default lwc_factor_table(n_grid, min_ratio).  mode "joint": candidate c = (factors[c], factors[c]); "independent": the cross
+        product (low, up) = (factors[c // n], factors[c % n]) -- at most 1024 pairs, so the default table is cut to 32 ratios.
+        The sigmoids the kernel scores are torch.sigmoid of the factors on the device, the call the forward applies to the parameters."""
+        why = self.lwc_search_skip_reason(w)
+        if why is not None:
+            raise ValueError(f"mobilequant_amd: search_lwc cannot run on this quantizer: {why}")
+        if mode not in ("joint", "independent"):
+            raise ValueError(f"mobilequant_amd: search_lwc mode {mode!r} (joint, independent)")
+        if factors is None:
+            factors = lwc_factor_table(min(int(n_grid), 32) if mode == "independent" else n_grid, min_ratio)
+        f = torch.as_tensor(factors)
+        if f.dtype != torch.float32 or f.dim() != 1 or f.numel() < 1:
+            raise ValueError(f"mobilequant_amd: search_lwc factors must be a float32 vector (got {f.dtype}, {tuple(f.shape)})")
+        if float(f[0]) != LWC_INIT_FACTOR:
+            raise ValueError(f"mobilequant_amd: search_lwc factors[0] must be {LWC_INIT_FACTOR}, the init of enable_lwc (got {float(f[0])})")
+        n = f.numel()
+        n_cand = n if mode == "joint" else n * n
+        if n_cand > ops.LWC_SEARCH_MAX_CANDIDATES:
+            raise ValueError(f"mobilequant_amd: search_lwc scores at most {ops.LWC_SEARCH_MAX_CANDIDATES} candidates (got {n_cand}, mode {mode})")
+        if col_weight is not None and (not torch.is_tensor(col_weight) or col_weight.numel() != w.shape[1]):
+            raise ValueError(f"mobilequant_amd: search_lwc col_weight has one entry per input channel, K = {w.shape[1]}")
+        f = f.to(w.device)
+        lo_f, hi_f = (f, f) if mode == "joint" else (f.repeat_interleave(n), f.repeat(n))
+        g = self.qcfg.group_size
+        x = w.detach().reshape(-1, g) if g != -1 else w.detach()
+        x = x.to(torch.float32).contiguous()
+        cw = None if col_weight is None else col_weight.detach().to(device=w.device, dtype=torch.float32).reshape(-1).contiguous()
+        idx, best, base = ops.lwc_search(x, torch.sigmoid(lo_f), torch.sigmoid(hi_f), int(self.qcfg.bitwidth), bool(self.qcfg.is_symmetric), cw)
+        if not self.lwc:
+            self.enable_lwc(w)
+        pick = idx.long()
+        self.lowbound_factor.data = lo_f[pick].reshape(self.lowbound_factor.shape).to(self.lowbound_factor.dtype)
+        self.upbound_factor.data = hi_f[pick].reshape(self.upbound_factor.shape).to(self.upbound_factor.dtype)
+        return LwcSearchReport(int(idx.numel()), int((idx != 0).sum()), float(base.sum()), float(best.sum()))
 
     # -- grid -----------------------------------------------------------------------------------
     def set_scale_offset_from_minmax(self, min_val, max_val, cache_mode=None, device=None):

@@ -23,6 +23,8 @@ Operators (reference code each one replaces):
     decode_cache_fork(caches, pos, parent) -> ()                                    (no reference code: DESIGN.md 4.3k; caches in place)
     decode_cache_reorder(caches, pos, parent) -> ()                                 (no reference code: DESIGN.md 4.3l; caches in place)
     beam_select(logits, cum, group, n_groups, n_cand) -> (score, row, token, logprob, row_lse)   (no reference code: DESIGN.md 4.3l)
+    lwc_search(w2d, sig_lo, sig_hi, bitwidth, is_symmetric, col_weight?) -> (best_idx, best_cost, base_cost, costs)
+                                                                                    (no reference code: DESIGN.md 4.7b; clip search)
 """
 from __future__ import annotations
 
@@ -172,5 +174,19 @@ def _(logits, cum, group, n_groups, n_cand):
     return f(n_groups, n_cand), i(n_groups, n_cand), i(n_groups, n_cand), f(n_groups, n_cand), f(rows)
 
 
+@torch.library.custom_op(f"{_NS}::lwc_search", mutates_args=(), device_types="cuda")
+def lwc_search(w2d: torch.Tensor, sig_lo: torch.Tensor, sig_hi: torch.Tensor, bitwidth: int, is_symmetric: bool,
+               col_weight: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(best_idx int32 [rows], best_cost fp64 [rows], base_cost fp64 [rows], costs fp64 [rows, C]) of ops.lwc_search."""
+    return ops.lwc_search(w2d, sig_lo, sig_hi, bitwidth, is_symmetric, col_weight, return_costs=True)
+
+
+@lwc_search.register_fake
+def _(w2d, sig_lo, sig_hi, bitwidth, is_symmetric, col_weight=None):
+    rows, C = w2d.shape[0], sig_lo.shape[0]
+    d = lambda *sh: w2d.new_empty(sh, dtype=torch.float64)  # noqa: E731
+    return w2d.new_empty((rows,), dtype=torch.int32), d(rows), d(rows), d(rows, C)
+
+
 OPS = ("fake_quant", "quantize", "minmax", "minmax_update_", "hist_minmax_update_", "w8a8_linear", "pack_w4", "w4a8_linear", "decode_cache_fork", "decode_cache_reorder",
-       "beam_select")
+       "beam_select", "lwc_search")
