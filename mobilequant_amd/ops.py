@@ -3,6 +3,13 @@
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every computation is a
 hand-written HIP kernel in libmobilequant_amd.so.  All functions require ROCm device tensors and raise
 otherwise -- there is no CPU or eager-PyTorch fallback.
+
+Operands come in three kinds (tests/ops_contract_cases.py lists every one).  A *converted* operand (grids, bias, weights of the norms: `_f32`)
+may be any floating dtype in any layout; it is read as contiguous float32, copied where it is not that already, and the copy lives until
+the launch is queued.  An integer or bool tensor is refused there on purpose, not converted: a grid of integers is a caller's mistake
+(an index tensor passed for a scale), and a silent conversion would hide it.  A *layout* operand (activations) keeps its dtype and is made
+contiguous.  Every other pointer -- outputs, in-place statistics, integer images, epilogue vectors -- goes to the entry as it is: `_raw`
+checks device, dtype, contiguity and element count and copies nothing.
 """
 from __future__ import annotations
 
@@ -57,24 +64,65 @@ class _on:
         return False
 
 
-def _fdt(t: torch.Tensor) -> int:
+def _fdt(t: torch.Tensor, what: str = "x") -> int:
     try:
         return _DT[t.dtype]
     except KeyError:
-        raise RuntimeError(f"mobilequant_amd: dtype {t.dtype} not supported (float32, float16)") from None
+        raise RuntimeError(f"mobilequant_amd: dtype {t.dtype} not supported (float32, float16) for {what}") from None
 
 
-def _f32(t: torch.Tensor, what: str) -> torch.Tensor:
+def _f32(t: torch.Tensor, what: str, align16: bool = False) -> torch.Tensor:
+    """The contiguous float32 form of a converted operand: the tensor itself when it is that already, else a copy the CALLER keeps alive
+    until its launch is queued.  align16: the entry takes a 16-byte aligned pointer, so a contiguous view off that boundary is copied too."""
     _dev(t, what)
     if t.dtype != torch.float32 or not t.is_contiguous():
+        if not t.dtype.is_floating_point:
+            raise RuntimeError(f"mobilequant_amd: {what} must be a floating-point tensor (got {t.dtype}); it is read as float32")
         t = t.to(torch.float32).contiguous()
+    if align16 and t.data_ptr() % 16:
+        t = t.clone()
     return t
+
+
+def _raw(t: torch.Tensor, what: str, dtype, numel: Optional[int] = None, at_least: bool = False) -> torch.Tensor:
+    """An operand whose pointer goes to the C entry as it is (outputs, in-place statistics, integer images and epilogue vectors): a
+    contiguous device tensor of `dtype` (one dtype or a tuple) with `numel` elements (at_least: that many or more -- a read-only
+    buffer may be longer than the launch reads).  Nothing is converted or copied; host attribute reads only."""
+    _dev(t, what)
+    dts = dtype if isinstance(dtype, tuple) else (dtype,)
+    if t.dtype not in dts or not t.is_contiguous() or (numel is not None and (t.numel() < numel if at_least else t.numel() != numel)):
+        raise RuntimeError(f"mobilequant_amd: {what} must be a contiguous {' / '.join(str(d) for d in dts)} device tensor"
+                           + (f" of {'at least ' if at_least else ''}{numel} elements" if numel is not None else "")
+                           + f" (got {t.dtype}, shape {tuple(t.shape)}, strides {tuple(t.stride())})")
+    return t
+
+
+def _same_len(a: torch.Tensor, b: torch.Tensor, what_a: str, what_b: str) -> None:
+    if a.numel() != b.numel():
+        raise RuntimeError(f"mobilequant_amd: {what_b} holds {b.numel()} elements, {what_a} {a.numel()}: one {what_b} entry per {what_a} entry")
+
+
+def _stats(stats, n: int, who: str):
+    """The n 1-element fp32 running statistics of a calibration pass, each handed over by pointer."""
+    stats = list(stats)
+    if len(stats) != n:
+        raise RuntimeError(f"mobilequant_amd: {who} stats must hold {n} tensors (got {len(stats)})")
+    return [_raw(t, f"{who} stats[{i}]", torch.float32, 1) for i, t in enumerate(stats)]
+
+
+_I8 = (torch.int8, torch.uint8)
+
+
+def _al16(t: torch.Tensor) -> torch.Tensor:
+    """A contiguous input for an entry that takes 16-byte aligned pointers: a view off that boundary is copied, like any other layout."""
+    return t.clone() if t.data_ptr() % 16 else t
 
 
 # ---- a1 --------------------------------------------------------------------------------------------
 def scale_offset_from_minmax(min_val: torch.Tensor, max_val: torch.Tensor, bitwidth: int, is_symmetric: bool):
     """Device version of compute_scale_offset_from_min_max (qmodule.py:40-61); shapes follow min_val."""
     mn, mx = _f32(min_val, "min_val"), _f32(max_val, "max_val")
+    _same_len(mn, mx, "min_val", "max_val")
     scale, offset = torch.empty_like(mn), torch.empty_like(mn)
     with _on(mn, mx):
         _lib.call("mq_scale_offset_from_minmax", mn.data_ptr(), mx.data_ptr(), mn.numel(), int(bitwidth),
@@ -85,6 +133,8 @@ def scale_offset_from_minmax(min_val: torch.Tensor, max_val: torch.Tensor, bitwi
 # ---- a3 / a12 --------------------------------------------------------------------------------------
 def minmax_new(n: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """Fresh running statistics (min = +inf, max = -inf)."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"mobilequant_amd: minmax_new needs a ROCm device (got {device}); there is no CPU path")
     mn = torch.empty(n, dtype=torch.float32, device=device)
     mx = torch.empty(n, dtype=torch.float32, device=device)
     with _on(mn, mx):
@@ -95,6 +145,7 @@ def minmax_new(n: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
 def minmax_tensor_(x: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor) -> None:
     """Running per-tensor update: mn[0] = min(mn[0], x.min()), mx[0] = max(mx[0], x.max())."""
     x = _dev(x, "x").contiguous()
+    _raw(mn, "mn", torch.float32, 1), _raw(mx, "mx", torch.float32, 1)
     with _on(x, mn, mx):
         _lib.call("mq_minmax_tensor", x.data_ptr(), _fdt(x), x.numel(), mn.data_ptr(), mx.data_ptr(), _stream())
 
@@ -118,6 +169,8 @@ def hist_minmax_tensor_(t: torch.Tensor, counts_row: torch.Tensor, nan_row: torc
             raise RuntimeError(f"mobilequant_amd: {what} must be a contiguous int64 tensor of {n} elements (got {c.dtype}, {tuple(c.shape)})")
     if (mn is None) != (mx is None):
         raise RuntimeError("mobilequant_amd: hist_minmax_tensor_ takes mn and mx as a pair")
+    if mn is not None:
+        _raw(mn, "mn", torch.float32, 1), _raw(mx, "mx", torch.float32, 1)
     with _on(x, counts_row, nan_row, mn, mx):
         _lib.call("mq_hist_minmax_tensor", x.data_ptr(), _fdt(x), x.numel(), int(mantissa_bits), counts_row.data_ptr(), nan_row.data_ptr(),
                   None if mn is None else mn.data_ptr(), None if mx is None else mx.data_ptr(), _stream())
@@ -125,14 +178,20 @@ def hist_minmax_tensor_(t: torch.Tensor, counts_row: torch.Tensor, nan_row: torc
 
 def minmax_rows_(x2d: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor) -> None:
     x2d = _dev(x2d, "x").contiguous()
+    if x2d.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: minmax_rows_ x must be [rows, cols] (got {tuple(x2d.shape)})")
     rows, cols = x2d.shape
+    _raw(mn, "mn", torch.float32, rows), _raw(mx, "mx", torch.float32, rows)
     with _on(x2d, mn, mx):
         _lib.call("mq_minmax_rows", x2d.data_ptr(), _fdt(x2d), rows, cols, mn.data_ptr(), mx.data_ptr(), _stream())
 
 
 def minmax_cols_(x2d: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor) -> None:
     x2d = _dev(x2d, "x").contiguous()
+    if x2d.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: minmax_cols_ x must be [rows, cols] (got {tuple(x2d.shape)})")
     rows, cols = x2d.shape
+    _raw(mn, "mn", torch.float32, cols), _raw(mx, "mx", torch.float32, cols)
     with _on(x2d, mn, mx):
         _lib.call("mq_minmax_cols", x2d.data_ptr(), _fdt(x2d), rows, cols, mn.data_ptr(), mx.data_ptr(), _stream())
 
@@ -154,6 +213,8 @@ def calib_attention_probs_(raw: torch.Tensor, mask: Optional[torch.Tensor], sqrt
         if mask.dtype != torch.float32 or not mask.is_contiguous() or mask.dim() != 2 or mask.shape[1] != cols or raw.shape[-2] != mask.shape[0]:
             raise RuntimeError("mobilequant_amd: calib_attention_probs_ mask must be a contiguous float32 [S, T] tensor")
         mrows = mask.shape[0]
+    for t, what in ((raw_min, "raw_min"), (raw_max, "raw_max"), (probs_min, "probs_min"), (probs_max, "probs_max")):
+        _raw(t, what, torch.float32, 1)
     with _on(raw, mask, raw_min, raw_max, probs_min, probs_max):
         _lib.call("mq_calib_attention_probs", raw.data_ptr(), raw.data_ptr(), rows, cols, mask.data_ptr() if mask is not None else None, mrows,
                   float(sqrt_d), raw_min.data_ptr(), raw_max.data_ptr(), probs_min.data_ptr(), probs_max.data_ptr(), _stream())
@@ -167,6 +228,8 @@ def calib_norm_(x: torch.Tensor, delta: Optional[torch.Tensor], weight: torch.Te
     input hook) and of y (its output hook) taken in the same pass; delta_min / delta_max: also that of delta itself.  Returns (h, y); h is x
     itself without a delta."""
     x = _dev(x, "x")
+    if delta is not None:
+        _dev(delta, "delta")
     if x.dtype != torch.float32 or not x.is_contiguous() or (delta is not None and (delta.dtype != torch.float32 or not delta.is_contiguous()
                                                                                         or delta.shape != x.shape)):
         raise RuntimeError("mobilequant_amd: calib_norm_ takes contiguous float32 tensors of one shape")
@@ -174,8 +237,17 @@ def calib_norm_(x: torch.Tensor, delta: Optional[torch.Tensor], weight: torch.Te
     rows = x.numel() // max(cols, 1)
     y = torch.empty_like(x)
     h = torch.empty_like(x) if delta is not None else None
-    w = _f32(weight, "weight").contiguous()
-    b = _f32(bias, "bias").contiguous() if bias is not None else None
+    w = _f32(weight, "weight", True)
+    b = _f32(bias, "bias", True) if bias is not None else None
+    if w.numel() != cols or (b is not None and b.numel() != cols):
+        raise RuntimeError(f"mobilequant_amd: calib_norm_ weight / bias must hold {cols} elements (got {w.numel()}"
+                           + (f", {b.numel()}" if b is not None else "") + ")")
+    if (delta_min is None) != (delta_max is None):
+        raise RuntimeError("mobilequant_amd: calib_norm_ takes delta_min and delta_max as a pair")
+    for t, what in ((in_min, "in_min"), (in_max, "in_max"), (out_min, "out_min"), (out_max, "out_max"), (delta_min, "delta_min"),
+                    (delta_max, "delta_max")):
+        if t is not None:
+            _raw(t, what, torch.float32, 1)
     with _on(x, delta, w, b, y, h, in_min, in_max, out_min, out_max, delta_min, delta_max):
         _lib.call("mq_calib_norm", x.data_ptr(), delta.data_ptr() if delta is not None else None, h.data_ptr() if h is not None else None,
                   y.data_ptr(), rows, cols, w.data_ptr(), b.data_ptr() if b is not None else None, float(eps), int(bool(layernorm)),
@@ -190,6 +262,7 @@ def calib_gated_(a: torch.Tensor, b: torch.Tensor, act: str, stats) -> torch.Ten
     a, b = _dev(a, "a"), _dev(b, "b")
     if a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous():
         raise RuntimeError("mobilequant_amd: calib_gated_ takes two contiguous float32 tensors of one shape")
+    stats = _stats(stats, 8, "calib_gated_")
     out = torch.empty_like(a)
     ptrs = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in stats])
     with _on(a, b, out, *stats):
@@ -202,11 +275,14 @@ def calib_rope_(q_lin: torch.Tensor, k_lin: torch.Tensor, heads: int, kv_heads: 
     S, D], k [B, kv_heads, S, D] contiguous, rotated with cos / sin [S, rot]; stats = eight 1-element fp32 device tensors: (min, max) of
     q_lin, q, k_lin, k.  The bits of llama.apply_rope."""
     q_lin, k_lin = _dev(q_lin, "q"), _dev(k_lin, "k")
+    if q_lin.dim() != 3 or k_lin.dim() != 3 or k_lin.shape[:2] != q_lin.shape[:2]:
+        raise RuntimeError("mobilequant_amd: calib_rope_ takes the contiguous float32 outputs of q_proj / k_proj [B, S, heads * D] and cos / sin [S, rot]")
     B, S = q_lin.shape[0], q_lin.shape[1]
-    cos, sin = _f32(cos, "cos").contiguous(), _f32(sin, "sin").contiguous()
+    cos, sin = _f32(cos, "cos", True), _f32(sin, "sin", True)
     if (q_lin.dtype != torch.float32 or k_lin.dtype != torch.float32 or not q_lin.is_contiguous() or not k_lin.is_contiguous()
             or q_lin.shape[-1] != heads * head_dim or k_lin.shape[-1] != kv_heads * head_dim or cos.shape != sin.shape or cos.shape[0] != S):
         raise RuntimeError("mobilequant_amd: calib_rope_ takes the contiguous float32 outputs of q_proj / k_proj and cos / sin [S, rot]")
+    stats = _stats(stats, 8, "calib_rope_")
     q = torch.empty((B, heads, S, head_dim), dtype=torch.float32, device=q_lin.device)
     k = torch.empty((B, kv_heads, S, head_dim), dtype=torch.float32, device=q_lin.device)
     ptrs = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in stats])
@@ -221,11 +297,15 @@ def calib_rope_qkv_(q_lin: torch.Tensor, k_lin: torch.Tensor, v_lin: torch.Tenso
     """calib_rope_ with v carried along and repeat_kv inside (mq_calib_rope_qkv): returns q [B, heads, S, D] and k, v [B, heads, S, D]
     with every kv head repeated heads / kv_heads times; stats = ten 1-element fp32 device tensors: (min, max) of q_lin, q, k_lin, k, v_lin."""
     q_lin, k_lin, v_lin = _dev(q_lin, "q"), _dev(k_lin, "k"), _dev(v_lin, "v")
+    if q_lin.dim() != 3 or k_lin.dim() != 3 or k_lin.shape[:2] != q_lin.shape[:2] or v_lin.shape != k_lin.shape:
+        raise RuntimeError("mobilequant_amd: calib_rope_qkv_ takes the contiguous float32 outputs of q_proj / k_proj / v_proj [B, S, heads * D] "
+                           "and cos / sin [S, rot]")
     B, S = q_lin.shape[0], q_lin.shape[1]
-    cos, sin = _f32(cos, "cos").contiguous(), _f32(sin, "sin").contiguous()
+    cos, sin = _f32(cos, "cos", True), _f32(sin, "sin", True)
     if (any(t.dtype != torch.float32 or not t.is_contiguous() for t in (q_lin, k_lin, v_lin)) or q_lin.shape[-1] != heads * head_dim
             or k_lin.shape[-1] != kv_heads * head_dim or v_lin.shape != k_lin.shape or cos.shape != sin.shape or cos.shape[0] != S):
         raise RuntimeError("mobilequant_amd: calib_rope_qkv_ takes the contiguous float32 outputs of q_proj / k_proj / v_proj and cos / sin [S, rot]")
+    stats = _stats(stats, 10, "calib_rope_qkv_")
     q, k, v = (torch.empty((B, heads, S, head_dim), dtype=torch.float32, device=q_lin.device) for _ in range(3))
     ptrs = (ctypes.c_void_p * 12)(*([t.data_ptr() for t in stats] + [None, None]))
     with _on(q_lin, k_lin, v_lin, q, k, v, cos, sin, *stats):
@@ -244,6 +324,10 @@ def calib_attention_probs_causal_(raw: torch.Tensor, out: torch.Tensor, sqrt_d: 
     if (raw.dtype != torch.float32 or out.dtype != torch.float32 or not raw.is_contiguous() or not out.is_contiguous() or raw.shape != out.shape
             or raw.dim() < 2 or raw.shape[-2] != S):
         raise RuntimeError("mobilequant_amd: calib_attention_probs_causal_ takes contiguous float32 [..., S, S] tensors")
+    if out.data_ptr() == raw.data_ptr():
+        raise RuntimeError("mobilequant_amd: calib_attention_probs_causal_ out must not be raw itself")
+    for t, what in ((raw_min, "raw_min"), (raw_max, "raw_max"), (probs_min, "probs_min"), (probs_max, "probs_max")):
+        _raw(t, what, torch.float32, 1)
     with _on(raw, out, raw_min, raw_max, probs_min, probs_max):
         _lib.call("mq_calib_attention_probs_causal", raw.data_ptr(), out.data_ptr(), raw.numel() // max(S, 1), S, float(sqrt_d), int(bool(store_masked)),
                   raw_min.data_ptr(), raw_max.data_ptr(), probs_min.data_ptr(), probs_max.data_ptr(), _stream())
@@ -261,13 +345,23 @@ def minmax_tensor(x: torch.Tensor):
     return mn, mx
 
 
+def _x2d(x2d: torch.Tensor, who: str) -> torch.Tensor:
+    """The checks of minmax_rows_ / minmax_cols_ on x, made before the fresh statistics are initialised (a launch of its own)."""
+    _fdt(_dev(x2d, "x"))
+    if x2d.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: {who} x must be [rows, cols] (got {tuple(x2d.shape)})")
+    return x2d
+
+
 def minmax_rows(x2d: torch.Tensor):
+    _x2d(x2d, "minmax_rows")
     mn, mx = minmax_new(x2d.shape[0], x2d.device)
     minmax_rows_(x2d, mn, mx)
     return mn, mx
 
 
 def minmax_cols(x2d: torch.Tensor):
+    _x2d(x2d, "minmax_cols")
     mn, mx = minmax_new(x2d.shape[1], x2d.device)
     minmax_cols_(x2d, mn, mx)
     return mn, mx
@@ -288,8 +382,14 @@ def fake_quant(x: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor, qmin:
     or one per row of x viewed as [n_scale, -1] (per-channel / per-group)."""
     x = _dev(x, "x").contiguous()
     s, o = _f32(scale, "scale"), _f32(offset, "offset")
+    _same_len(s, o, "scale", "offset")
     rows, cols = _rows_cols(x, s.numel())
-    y = torch.empty_like(x) if out is None else out
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        y = _raw(out, "out", x.dtype, x.numel())
+        if y.shape != x.shape:
+            raise RuntimeError(f"mobilequant_amd: out must have x's shape {tuple(x.shape)} (got {tuple(y.shape)})")
     with _on(x, s, o, y):
         _lib.call("mq_fake_quant", x.data_ptr(), y.data_ptr(), _fdt(x), rows, cols, s.data_ptr(), o.data_ptr(),
                   s.numel(), float(qmin), float(qmax), _stream())
@@ -302,6 +402,9 @@ def fake_quant_backward(x: torch.Tensor, grad_y: torch.Tensor, scale: torch.Tens
     x = _f32(x, "x")
     g = _f32(grad_y, "grad_y")
     s, o = _f32(scale, "scale"), _f32(offset, "offset")
+    _same_len(s, o, "scale", "offset")
+    if g.shape != x.shape:
+        raise RuntimeError(f"mobilequant_amd: grad_y must have x's shape {tuple(x.shape)} (got {tuple(g.shape)})")
     rows, cols = _rows_cols(x, s.numel())
     gx = torch.empty_like(x)
     acc = torch.zeros(2 * s.numel(), dtype=torch.float32, device=x.device)      # one fill for both accumulators
@@ -329,7 +432,7 @@ def lwc_fake_quant_supported(w: torch.Tensor) -> bool:
 def lwc_fake_quant(w: torch.Tensor, sig_lo: torch.Tensor, sig_hi: torch.Tensor, bitwidth: int, is_symmetric: bool):
     """Per-row range -> sigmoid(bound) * range -> grid -> fake-quant of a weight [N, K] in one pass (mq_lwc_fake_quant).
     Returns (w_q, row_min, row_max, scale, offset), the last four [N]."""
-    w = _f32(_dev(w, "w"), "w")
+    w = _f32(_dev(w, "w"), "w", True)
     N, K = w.shape
     lo, hi = _f32(sig_lo, "sig_lo").reshape(-1), _f32(sig_hi, "sig_hi").reshape(-1)
     if lo.numel() != N or hi.numel() != N:
@@ -344,9 +447,14 @@ def lwc_fake_quant(w: torch.Tensor, sig_lo: torch.Tensor, sig_hi: torch.Tensor, 
 
 def lwc_fake_quant_backward(w, grad_out, sig_lo, sig_hi, row_min, row_max, bitwidth: int, is_symmetric: bool):
     """(grad_w, grad_sig_lo, grad_sig_hi) of lwc_fake_quant (mq_lwc_fake_quant_backward)."""
-    w, g = _f32(_dev(w, "w"), "w"), _f32(_dev(grad_out, "grad_out"), "grad_out")
+    w, g = _f32(_dev(w, "w"), "w", True), _f32(_dev(grad_out, "grad_out"), "grad_out", True)
     N, K = w.shape
     lo, hi = _f32(sig_lo, "sig_lo").reshape(-1), _f32(sig_hi, "sig_hi").reshape(-1)
+    if lo.numel() != N or hi.numel() != N:
+        raise RuntimeError("mobilequant_amd: lwc_fake_quant_backward needs one bound factor (sig_lo, sig_hi) per output row")
+    if g.shape != w.shape:
+        raise RuntimeError(f"mobilequant_amd: grad_out must have w's shape {tuple(w.shape)} (got {tuple(g.shape)})")
+    _raw(row_min, "row_min", torch.float32, N), _raw(row_max, "row_max", torch.float32, N)
     gw = torch.empty_like(w)
     glo, ghi = torch.empty(N, dtype=torch.float32, device=w.device), torch.empty(N, dtype=torch.float32, device=w.device)
     with _on(w, g, lo, hi, row_min, row_max):
@@ -414,14 +522,16 @@ def attention_probs_train_supported(raw: torch.Tensor, mask: Optional[torch.Tens
 def _attn_probs_args(raw, mask, g1, g2):
     cols = raw.shape[-1]
     rows = raw.numel() // cols
-    m = None if mask is None else _f32(mask, "mask").reshape(-1, cols)
+    m = None if mask is None else _f32(mask, "mask", True).reshape(-1, cols)
     s1, o1, s2, o2 = (_f32(t, "grid") for t in (g1[0], g1[1], g2[0], g2[1]))
+    if any(t.numel() != 1 for t in (s1, o1, s2, o2)):
+        raise RuntimeError("mobilequant_amd: attention_probs_train takes per-tensor grids: every grid scale and offset holds one element")
     return rows, cols, m, (s1, o1, s2, o2)
 
 
 def attention_probs_train(raw, mask, grid1, grid2, sqrt_d: float):
     """Q2(softmax(Q1(raw) / sqrt_d + mask)) over the last dimension (mq_attention_probs_train); grid = (scale, offset, qmin, qmax)."""
-    raw = _f32(_dev(raw, "raw"), "raw")
+    raw = _f32(_dev(raw, "raw"), "raw", True)
     rows, cols, m, (s1, o1, s2, o2) = _attn_probs_args(raw, mask, grid1, grid2)
     out = torch.empty_like(raw)
     with _on(raw, m, s1, o1, s2, o2):
@@ -433,7 +543,9 @@ def attention_probs_train(raw, mask, grid1, grid2, sqrt_d: float):
 
 def attention_probs_train_backward(raw, grad_out, mask, grid1, grid2, sqrt_d: float):
     """(grad_raw, [d s1, d o1, d s2, d o2]) of attention_probs_train."""
-    raw, g = _f32(_dev(raw, "raw"), "raw"), _f32(_dev(grad_out, "grad_out"), "grad_out")
+    raw, g = _f32(_dev(raw, "raw"), "raw", True), _f32(_dev(grad_out, "grad_out"), "grad_out", True)
+    if g.shape != raw.shape:
+        raise RuntimeError(f"mobilequant_amd: grad_out must have raw's shape {tuple(raw.shape)} (got {tuple(g.shape)})")
     rows, cols, m, (s1, o1, s2, o2) = _attn_probs_args(raw, mask, grid1, grid2)
     graw = torch.empty_like(raw)
     gg = torch.zeros(4, dtype=torch.float32, device=raw.device)
@@ -452,8 +564,13 @@ def quantize(x: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor, qmin: f
     chan_scale [cols]: SmoothQuant per-channel scale fused in front (index of x / chan_scale; per-tensor grids, fp32)."""
     x = _dev(x, "x").contiguous()
     s, o = _f32(scale, "scale"), _f32(offset, "offset")
+    _same_len(s, o, "scale", "offset")
     if rows is None:
         rows = s.numel() if s.numel() > 1 else (x.numel() // x.shape[-1] if x.dim() > 0 else 1)
+    rows = int(rows)
+    if rows < 1 or x.numel() % rows or s.numel() not in (1, rows):
+        raise RuntimeError(f"mobilequant_amd: quantize rows={rows} must divide x's {x.numel()} elements and take 1 or {rows} scales "
+                           f"(got {s.numel()})")
     cols = x.numel() // max(rows, 1)
     q = torch.empty(x.shape, dtype=_QDT[q_dtype], device=x.device)
     rs = torch.empty(rows, dtype=torch.int32, device=x.device) if want_row_sum else None
@@ -469,7 +586,12 @@ def quantize(x: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor, qmin: f
 def linear_epilogue_prepare(a_scale, a_offset, a_shift: int, w_scale, w_offset, w_shift: int, w_colsum, K: int):
     sa, oa = _f32(a_scale, "a_scale"), _f32(a_offset, "a_offset")
     sw, ow = _f32(w_scale, "w_scale"), _f32(w_offset, "w_offset")
+    _same_len(sa, oa, "a_scale", "a_offset"), _same_len(sw, ow, "w_scale", "w_offset")
+    _raw(w_colsum, "w_colsum", torch.int32)
     N = w_colsum.numel()
+    if sa.numel() != 1 or sw.numel() not in (1, N):
+        raise RuntimeError(f"mobilequant_amd: linear_epilogue_prepare takes a per-tensor activation grid (a_scale, a_offset of one element) "
+                           f"and 1 or {N} weight scales (w_scale, w_offset) (got {sa.numel()}, {sw.numel()})")
     dev = w_colsum.device
     alpha = torch.empty(N, dtype=torch.float32, device=dev)
     w_zp = torch.empty(N, dtype=torch.int32, device=dev)
@@ -485,6 +607,49 @@ _OUT_TORCH = {MQ_F32: torch.float32, MQ_F16: torch.float16, MQ_U8: torch.uint8, 
               MQ_U16: torch.uint16, MQ_I16: torch.int16}
 
 
+def _gemm_images(a_q: torch.Tensor, w_q: torch.Tensor, w4: bool, a_tiled_rows: Optional[int], what_a: str = "a_q", what_w: str = "w_q"):
+    """(M, N, K) of an integer GEMM whose two byte images go to the entry by pointer: a_q [M, K] (a_tiled_rows = M: the fragment-blocked
+    [>= ceil16(M), K] buffer), w_q [N, K] or, packed, [N, K / 2]."""
+    _raw(a_q, what_a, _I8), _raw(w_q, what_w, _I8)
+    if a_q.dim() != 2 or w_q.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: {what_a} and {what_w} must be 2-D byte images (got {tuple(a_q.shape)}, {tuple(w_q.shape)})")
+    M, K = a_q.shape
+    if a_tiled_rows is not None:
+        M = int(a_tiled_rows)
+        if M < 1 or (M + 15) // 16 * 16 > a_q.shape[0]:
+            raise RuntimeError(f"mobilequant_amd: {what_a} holds {a_q.shape[0]} rows, the fragment-blocked image of {M} rows needs "
+                               f"{(M + 15) // 16 * 16}")
+    if w_q.shape[1] * (2 if w4 else 1) != K:
+        raise RuntimeError(f"mobilequant_amd: {what_w} {tuple(w_q.shape)} does not match {what_a}'s K = {K}"
+                           + (" (packed nibbles: [N, K / 2])" if w4 else ""))
+    return M, w_q.shape[0], K
+
+
+def _gemm_vectors(M: int, N: int, a_rowsum, alpha, w_zp, col_term, sfx: str = "") -> None:
+    """The epilogue vectors of an integer GEMM, read by pointer: a_rowsum int32 [>= M] or None, alpha fp32, w_zp / col_term int32 [>= N]."""
+    if a_rowsum is not None:
+        _raw(a_rowsum, "a_rowsum", torch.int32, M, at_least=True)
+    _raw(alpha, "alpha" + sfx, torch.float32, N, at_least=True)
+    _raw(w_zp, "w_zp" + sfx, torch.int32, N, at_least=True)
+    _raw(col_term, "col_term" + sfx, torch.int32, N, at_least=True)
+
+
+def _gemm_bias(bias, N: int):
+    """The bias of an integer GEMM as contiguous, 16-byte aligned float32 with one entry per output column (None stays None)."""
+    if bias is None:
+        return None
+    b = _f32(bias, "bias", True)
+    if b.numel() != N:
+        raise RuntimeError(f"mobilequant_amd: bias must hold {N} elements, one per output column (got {b.numel()})")
+    return b
+
+
+def _gemm_out(out: Optional[torch.Tensor], M: int, N: int, out_dtype: int, like: torch.Tensor) -> torch.Tensor:
+    if out is None:
+        return torch.empty((M, N), dtype=_OUT_TORCH[out_dtype], device=like.device)
+    return _raw(out, "out", _OUT_TORCH[out_dtype], M * N)
+
+
 def int8_linear(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: Optional[torch.Tensor], alpha: torch.Tensor,
                 w_zp: torch.Tensor, col_term: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
                 out_scale: Optional[torch.Tensor] = None, out_offset: Optional[torch.Tensor] = None,
@@ -496,14 +661,10 @@ def int8_linear(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: Optional[torch.T
     quantize_tiled ([ceil16(M), K] bytes) and the generated-ISA GEMM path runs (gemm_tiled_supported shapes).
     resid [M, N] fp32 (row-major int8 weights and activations, fp32 output, M > 8): out = resid + Qout(linear), the add fused into
     the GEMM's store (residual_supported())."""
-    _dev(a_q, "a_q"); _dev(w_q, "w_q")
-    M, K = a_q.shape
-    if a_tiled_rows is not None:
-        M = int(a_tiled_rows)
-    N = w_q.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=_OUT_TORCH[out_dtype], device=a_q.device)
-    b = _f32(bias, "bias") if bias is not None else None
+    M, N, K = _gemm_images(a_q, w_q, w4 and not (a_tiled_rows is not None and resid is None), a_tiled_rows)
+    _gemm_vectors(M, N, a_rowsum, alpha, w_zp, col_term)
+    out = _gemm_out(out, M, N, out_dtype, a_q)
+    b = _gemm_bias(bias, N)
     os_ = _f32(out_scale, "out_scale") if out_scale is not None else None
     oo_ = _f32(out_offset, "out_offset") if out_offset is not None else None
     if resid is not None:
@@ -514,7 +675,7 @@ def int8_linear(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: Optional[torch.T
         if a_tiled_rows is not None and not (os_ is not None and out_qmax - out_qmin > 255.0 and gemm_tiled128_supported(M, N, K)):
             raise RuntimeError("mobilequant_amd: int8_linear(resid=..., a_tiled_rows=...) needs a 16-bit output grid and a "
                                "gemm_tiled128_supported shape")
-        resid = _f32(_dev(resid, "resid"), "resid")
+        resid = _f32(_dev(resid, "resid"), "resid", True)
         if resid.numel() != M * N or resid.data_ptr() == out.data_ptr():
             raise RuntimeError("mobilequant_amd: resid must be [M, N] and must not alias the output")
         with _on(a_q, w_q, a_rowsum, alpha, w_zp, col_term, b, os_, oo_, out, resid):
@@ -539,12 +700,18 @@ def int8_linear_grouped(a_q: torch.Tensor, w_q: torch.Tensor, group_size: int, a
                         t: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """QLinear with per-group weight grids as an int8 MFMA GEMM (mq_w8a8_linear_grouped): a_q [M, K] / w_q [N, K] stored int8 values,
     a_gsum [G, M] int32, alpha [G, N] fp32, cw / t [G, N] int32 (include/mobilequant_amd.h); fp32 [M, N] out."""
-    _dev(a_q, "a_q"); _dev(w_q, "w_q")
-    M, K = a_q.shape
-    N = w_q.shape[0]
+    M, N, K = _gemm_images(a_q, w_q, False, None)
+    gs_ = int(group_size)
+    if gs_ < 1 or K % gs_:
+        raise RuntimeError(f"mobilequant_amd: int8_linear_grouped group_size={group_size} must divide K = {K}")
+    G = K // gs_
     out = torch.empty((M, N), dtype=torch.float32, device=a_q.device)
-    b = _f32(bias, "bias") if bias is not None else None
-    al = _f32(alpha, "alpha")
+    b = _gemm_bias(bias, N)
+    al = _f32(alpha, "alpha", True)
+    _raw(a_gsum, "a_gsum", torch.int32, G * M, at_least=True), _raw(cw, "cw", torch.int32, G * N, at_least=True)
+    _raw(t, "t", torch.int32, G * N, at_least=True)
+    if al.numel() < G * N:
+        raise RuntimeError(f"mobilequant_amd: alpha must hold {G * N} elements (got {al.numel()})")
     with _on(a_q, w_q, a_gsum, al, cw, t, b):
         _lib.call("mq_w8a8_linear_grouped", a_q.data_ptr(), w_q.data_ptr(), M, N, K, int(group_size), a_gsum.data_ptr(), al.data_ptr(),
                   cw.data_ptr(), t.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(), _stream())
@@ -696,21 +863,24 @@ def int8_linear_segmented(a_q: torch.Tensor, w_q: torch.Tensor, a_rowsum: torch.
     bias concatenated along N, seg_ends = cumulative column ends, grids[i] = (scale, offset) of segment i's 8-bit unsigned output
     grid.  Returns the uint8 output indices [M, N].  w4: w_q holds packed nibbles [N, K/2] (pack_w4).  a_tiled_rows = M: a_q is the
     fragment-blocked image (gemm_tiled128_supported shapes, int8 weights)."""
-    _dev(a_q, "a_q"); _dev(w_q, "w_q")
-    M, K = a_q.shape
     fn = "mq_w4a8_linear_segmented" if w4 else "mq_w8a8_linear_segmented"
     if a_tiled_rows is not None:
         if w4:
             raise RuntimeError("mobilequant_amd: the fragment-blocked segmented GEMM takes int8 weights")
-        M, fn = int(a_tiled_rows), "mq_w8a8_linear_tiled_segmented"
-    N = w_q.shape[0]
+        fn = "mq_w8a8_linear_tiled_segmented"
+    M, N, K = _gemm_images(a_q, w_q, w4, a_tiled_rows)
+    _gemm_vectors(M, N, a_rowsum, alpha, w_zp, col_term)
     n = len(seg_ends)
+    if len(grids) != n:
+        raise RuntimeError(f"mobilequant_amd: int8_linear_segmented takes one grid per segment ({len(grids)} grids, {n} seg_ends)")
     out = torch.empty((M, N), dtype=torch.uint8, device=a_q.device)
-    b = _f32(bias, "bias") if bias is not None else None
+    b = _gemm_bias(bias, N)
     ends = (ctypes.c_int64 * n)(*[int(e) for e in seg_ends])
     keep, gs = [], (_lib.MqGrid * n)()
     for i, g in enumerate(grids):
         sc, of = _f32(g[0], "scale"), _f32(g[1], "offset")
+        if sc.numel() != 1 or of.numel() != 1:
+            raise RuntimeError(f"mobilequant_amd: segment {i} takes a per-tensor grid: scale and offset of one element (got {sc.numel()}, {of.numel()})")
         keep += [sc, of]
         gs[i] = _lib.MqGrid(sc.data_ptr(), of.data_ptr(), 0.0, 255.0)
     with _on(a_q, w_q, a_rowsum, alpha, w_zp, col_term, b, out, *keep):
@@ -731,16 +901,19 @@ def w4a8_linear_tiled(a_tiled: torch.Tensor, M: int, w_packed: torch.Tensor, a_r
     """Packed 4-bit weights [N, K/2] (pack_w4) x fragment-blocked int8 activations (quantize_tiled, M rows) on the generated-ISA kernels
     (mq_w4a8_linear_tiled): 8-bit unsigned output grid(s) -> uint8 indices (or int8 = index - 128) [M, N].  grids: [(scale, offset)] per
     column segment; seg_ends: cumulative column ends when there is more than one."""
-    _dev(a_tiled, "a_tiled"); _dev(w_packed, "w_packed")
-    N, K = int(w_packed.shape[0]), 2 * int(w_packed.shape[1])
+    M, N, K = _gemm_images(a_tiled, w_packed, True, M, "a_tiled", "w_packed")
+    _gemm_vectors(M, N, a_rowsum, alpha, w_zp, col_term)
     n = len(grids)
-    if out is None:
-        out = torch.empty((int(M), N), dtype=_OUT_TORCH[out_dtype], device=a_tiled.device)
-    b = _f32(bias, "bias") if bias is not None else None
+    if len(seg_ends if seg_ends is not None else [N]) != n:
+        raise RuntimeError(f"mobilequant_amd: w4a8_linear_tiled takes one grid per segment ({n} grids)")
+    out = _gemm_out(out, M, N, out_dtype, a_tiled)
+    b = _gemm_bias(bias, N)
     ends = (ctypes.c_int64 * n)(*[int(e) for e in (seg_ends if seg_ends is not None else [N])])
     keep, gs = [], (_lib.MqGrid * n)()
     for i, g in enumerate(grids):
         sc, of = _f32(g[0], "scale"), _f32(g[1], "offset")
+        if sc.numel() != 1 or of.numel() != 1:
+            raise RuntimeError(f"mobilequant_amd: segment {i} takes a per-tensor grid: scale and offset of one element (got {sc.numel()}, {of.numel()})")
         keep += [sc, of]
         gs[i] = _lib.MqGrid(sc.data_ptr(), of.data_ptr(), 0.0, 255.0)
     with _on(a_tiled, w_packed, a_rowsum, alpha, w_zp, col_term, b, out, *keep):
@@ -764,11 +937,20 @@ def quantize_tiled(x2d: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor,
                    want_row_sum: bool = True, chan_scale: Optional[torch.Tensor] = None):
     """[M,K] activations -> fragment-blocked int8 ([ceil16(M), K] buffer, layout: include/mobilequant_amd.h) + row sums."""
     x2d = _dev(x2d, "x").contiguous()
+    if x2d.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: quantize_tiled x must be [M, K] (got {tuple(x2d.shape)})")
+    if x2d.data_ptr() % 16:              # the entry takes 16-byte aligned activations and channel scales: a view off that boundary is copied
+        x2d = x2d.clone()
     M, K = x2d.shape
     q = torch.empty(((M + 15) // 16 * 16, K), dtype=torch.int8, device=x2d.device)
     rs = torch.empty(M, dtype=torch.int32, device=x2d.device) if want_row_sum else None
     s, o = _f32(scale, "scale"), _f32(offset, "offset")
+    _same_len(s, o, "scale", "offset")
+    if s.numel() != 1:
+        raise RuntimeError(f"mobilequant_amd: quantize_tiled takes a per-tensor grid: scale and offset of one element (got {s.numel()})")
     cs = _chan(chan_scale, K, x2d)
+    if cs is not None and cs.data_ptr() % 16:
+        cs = cs.clone()
     with _on(x2d, s, o, cs):
         _lib.call("mq_quantize_tiled", x2d.data_ptr(), _fdt(x2d), M, K, s.data_ptr(), o.data_ptr(), float(qmin), float(qmax),
                   int(shift), cs.data_ptr() if cs is not None else None, q.data_ptr(), rs.data_ptr() if rs is not None else None,
@@ -786,13 +968,18 @@ def int8_linear_f32in(x2d: torch.Tensor, a_scale, a_offset, a_qmin: float, a_qma
                       out_qmax: float = 255.0, out_dtype: int = MQ_F32, out: Optional[torch.Tensor] = None, w4: bool = False):
     """Decode-shape QLinear in ONE kernel: fp32 activations are quantised inside the GEMV (M <= 8).
     w4: w_q holds packed nibbles ([N, K/2], pack_w4)."""
-    x2d = _f32(_dev(x2d, "x"), "x")
+    x2d = _f32(_dev(x2d, "x"), "x", True)
+    if x2d.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: int8_linear_f32in x must be [M, K] (got {tuple(x2d.shape)})")
     M, K = x2d.shape
+    _raw(w_q, "w_q", _I8)
+    if w_q.dim() != 2 or w_q.shape[1] * (2 if w4 else 1) != K:
+        raise RuntimeError(f"mobilequant_amd: w_q {tuple(w_q.shape)} does not match x's K = {K}" + (" (packed nibbles: [N, K / 2])" if w4 else ""))
     N = w_q.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=_OUT_TORCH[out_dtype], device=x2d.device)
+    _gemm_vectors(M, N, None, alpha, w_zp, col_term)
+    out = _gemm_out(out, M, N, out_dtype, x2d)
     sa, oa = _f32(a_scale, "a_scale"), _f32(a_offset, "a_offset")
-    b = _f32(bias, "bias") if bias is not None else None
+    b = _gemm_bias(bias, N)
     os_ = _f32(out_scale, "out_scale") if out_scale is not None else None
     oo_ = _f32(out_offset, "out_offset") if out_offset is not None else None
     with _on(x2d, sa, oa, w_q, alpha, w_zp, col_term, b, os_, oo_, out):
@@ -810,11 +997,14 @@ def rmsnorm_quant(x: torch.Tensor, weight: torch.Tensor, bias, eps: float, in_gr
     (scale, offset, qmin, qmax) per-tensor.  Returns y, or (y, q_int8, row_sum, shift, q_tiled) with emit_int8
     (8-bit output grids only; q_tiled = the fragment-blocked copy when emit_tiled, else None).  want_y=False (emit_int8 only): the
     fp32 result is not written (y = None); emit_rowmajor=False: only the fragment-blocked image (q_int8 = None)."""
-    x = _f32(_dev(x, "x"), "x").contiguous()
+    x = _f32(_dev(x, "x"), "x", True)
     cols = x.shape[-1]
     rows = x.numel() // cols
-    w = _f32(weight, "weight").contiguous()
-    b = _f32(bias, "bias").contiguous() if bias is not None else None
+    w = _f32(weight, "weight", True)
+    b = _f32(bias, "bias", True) if bias is not None else None
+    if w.numel() != cols or (b is not None and b.numel() != cols):
+        raise RuntimeError(f"mobilequant_amd: rmsnorm_quant weight / bias must hold {cols} elements (got {w.numel()}"
+                           + (f", {b.numel()}" if b is not None else "") + ")")
     if not want_y and not emit_int8:
         raise RuntimeError("mobilequant_amd: rmsnorm_quant(want_y=False) needs emit_int8")
     y = torch.empty_like(x) if want_y else None
@@ -824,6 +1014,10 @@ def rmsnorm_quant(x: torch.Tensor, weight: torch.Tensor, bias, eps: float, in_gr
         si, oi, iqmin, iqmax = _f32(in_grid[0], "in_scale"), _f32(in_grid[1], "in_offset"), float(in_grid[2]), float(in_grid[3])
     if out_grid is not None:
         so, oo, oqmin, oqmax = _f32(out_grid[0], "out_scale"), _f32(out_grid[1], "out_offset"), float(out_grid[2]), float(out_grid[3])
+    for sg, og in ((si, oi), (so, oo)):
+        if sg is not None and (sg.numel() != 1 or og.numel() != 1):
+            raise RuntimeError(f"mobilequant_amd: rmsnorm_quant takes per-tensor grids: in_scale / in_offset / out_scale / out_offset of one "
+                               f"element (got {sg.numel()}, {og.numel()})")
     q = rs = qt = None
     shift = 0
     if emit_int8:
@@ -846,22 +1040,29 @@ def rmsnorm_quant(x: torch.Tensor, weight: torch.Tensor, bias, eps: float, in_gr
 
 def act_quant(x: torch.Tensor, act: str, in_grid=None, mid_grid=None, out_grid=None):
     """QSiLU ("silu") / QGELU ("gelu") forward in one launch; grids: None or (scale, offset, qmin, qmax) per-tensor."""
-    x = _f32(_dev(x, "x"), "x").contiguous()
+    x = _f32(_dev(x, "x"), "x", True)
     y = torch.empty_like(x)
-    ptrs = []
+    ptrs, keep = [], []
     for g in (in_grid, mid_grid, out_grid):
         if g is None:
             ptrs += [None, None, 0.0, 0.0]
         else:
-            ptrs += [_f32(g[0], "scale").data_ptr(), _f32(g[1], "offset").data_ptr(), float(g[2]), float(g[3])]
-    with _on(x):
+            s, o = _f32(g[0], "scale"), _f32(g[1], "offset")        # a converted copy lives in `keep` until the launch is queued
+            if s.numel() != 1 or o.numel() != 1:
+                raise RuntimeError(f"mobilequant_amd: act_quant takes per-tensor grids: scale and offset of one element (got {s.numel()}, {o.numel()})")
+            keep += [s, o]
+            ptrs += [s.data_ptr(), o.data_ptr(), float(g[2]), float(g[3])]
+    with _on(x, *keep):
         _lib.call("mq_act_quant", x.data_ptr(), x.numel(), {"silu": 0, "gelu": 1}[act], *ptrs, y.data_ptr(), _stream())
     return y
 
 
 def pack_w4(nibbles: torch.Tensor) -> torch.Tensor:
     """[N,K] uint8 nibbles (0..15) -> [N,K/2] packed (layout: include/mobilequant_amd.h, mq_pack_w4)."""
-    nibbles = _dev(nibbles, "nibbles").contiguous()
+    nibbles = _dev(nibbles, "nibbles")
+    if nibbles.dtype != torch.uint8 or nibbles.dim() != 2 or nibbles.shape[1] % 2:
+        raise RuntimeError(f"mobilequant_amd: nibbles must be a uint8 [N, K] tensor with K even (got {nibbles.dtype}, {tuple(nibbles.shape)})")
+    nibbles = nibbles.contiguous()
     N, K = nibbles.shape
     packed = torch.empty((N, K // 2), dtype=torch.uint8, device=nibbles.device)
     with _on(nibbles):
@@ -870,19 +1071,37 @@ def pack_w4(nibbles: torch.Tensor) -> torch.Tensor:
 
 
 # ---- f1: integer chaining inside the gated FFN ---------------------------------------------------------------------------------
+def _pair_halves(M: int, N: int, a_rowsum, first: dict, second: dict) -> None:
+    """Both halves of a two-linear launch: the second's weight image has the first's shape and dtype, each half's vectors hold N entries."""
+    _raw(second["w"], "second['w']", _I8)
+    if second["w"].shape != first["w"].shape or second["w"].dtype != first["w"].dtype:
+        raise RuntimeError(f"mobilequant_amd: second['w'] {tuple(second['w'].shape)} {second['w'].dtype} must match first['w'] "
+                           f"{tuple(first['w'].shape)} {first['w'].dtype}")
+    for p, sfx in ((first, " (first)"), (second, " (second)")):
+        _gemm_vectors(M, N, a_rowsum, p["alpha"], p["w_zp"], p["col_term"], sfx)
+
+
+def _half_grid(p: dict, N: int, keep: list):
+    """(bias | None, out_scale, out_offset) of one half as contiguous float32, kept alive in `keep`; the grid is per-tensor."""
+    b = _gemm_bias(p.get("bias"), N)
+    os_, oo_ = _f32(p["out_scale"], "out_scale"), _f32(p["out_offset"], "out_offset")
+    if os_.numel() != 1 or oo_.numel() != 1:
+        raise RuntimeError(f"mobilequant_amd: out_scale and out_offset hold one element each (got {os_.numel()}, {oo_.numel()})")
+    keep += [b, os_, oo_]
+    return b, os_, oo_
+
+
 def int8_linear_pair(a_tiled: torch.Tensor, rows: int, a_rowsum: Optional[torch.Tensor], first: dict, second: dict,
                      out_dtype: int = MQ_U8):
     """Two QLinears over the SAME fragment-blocked activation in one launch (w1 / w3 of a gated FFN).  `first` / `second`:
     dicts with w [N,K] int8, alpha, w_zp, col_term, bias (or None), out_scale, out_offset (8-bit unsigned output grids).
     Returns the two [rows, N] index tensors (u8, or i8 = index - 128)."""
-    M, K = int(rows), a_tiled.shape[1]
-    N = first["w"].shape[0]
+    M, N, K = _gemm_images(a_tiled, first["w"], False, rows, "a_tiled", "first['w']")
+    _pair_halves(M, N, a_rowsum, first, second)
     outs = [torch.empty((M, N), dtype=_OUT_TORCH[out_dtype], device=a_tiled.device) for _ in range(2)]
     ptrs, keep = [], []
     for p, o in zip((first, second), outs):
-        b = _f32(p["bias"], "bias") if p.get("bias") is not None else None
-        os_, oo_ = _f32(p["out_scale"], "out_scale"), _f32(p["out_offset"], "out_offset")
-        keep += [b, os_, oo_]
+        b, os_, oo_ = _half_grid(p, N, keep)
         ptrs += [p["w"].data_ptr(), p["alpha"].data_ptr(), p["w_zp"].data_ptr(), p["col_term"].data_ptr(),
                  b.data_ptr() if b is not None else None, os_.data_ptr(), oo_.data_ptr(), o.data_ptr()]
     with _on(a_tiled, a_rowsum, first["w"], second["w"], first["alpha"], second["alpha"], *[k for k in keep if k is not None]):
@@ -897,19 +1116,17 @@ def int8_linear_gated(a_tiled: torch.Tensor, rows: int, a_rowsum: Optional[torch
     (w3) looks (w1 index, w3 index) up in `table` (gated_table) inside its epilogue.  Returns (w2's int8 input image, fragment-blocked
     [ceil16(rows), N]; its row sums [rows]) -- the bits of int8_linear_pair + gated_lookup(tiled=True)."""
     # w4: both weights are mq_pack_w4 images ([N, K / 2] bytes) and the packed kernels run (mq_w4a8_linear_tiled_gated: identical bytes)
-    M, K = int(rows), a_tiled.shape[1]
-    N = first["w"].shape[0]
+    M, N, K = _gemm_images(a_tiled, first["w"], w4, rows, "a_tiled", "first['w']")
+    _pair_halves(M, N, a_rowsum, first, second)
     dev = a_tiled.device
-    if table.dtype != torch.int8 or table.numel() != 65536:
+    if _dev(table, "table").dtype != torch.int8 or table.numel() != 65536 or not table.is_contiguous():
         raise RuntimeError("mobilequant_amd: int8_linear_gated needs an int8 [65536] table (gated_table)")
     idx = torch.empty((M, N), dtype=torch.uint8, device=dev)
     q = torch.empty(((M + 15) // 16 * 16, N), dtype=torch.int8, device=dev)
     rs = torch.empty(M, dtype=torch.int32, device=dev)
     ptrs, keep = [], []
     for p in (first, second):
-        b = _f32(p["bias"], "bias") if p.get("bias") is not None else None
-        os_, oo_ = _f32(p["out_scale"], "out_scale"), _f32(p["out_offset"], "out_offset")
-        keep += [b, os_, oo_]
+        b, os_, oo_ = _half_grid(p, N, keep)
         ptrs += [p["w"].data_ptr(), p["alpha"].data_ptr(), p["w_zp"].data_ptr(), p["col_term"].data_ptr(),
                  b.data_ptr() if b is not None else None, os_.data_ptr(), oo_.data_ptr()]
     with _on(a_tiled, a_rowsum, first["w"], second["w"], first["alpha"], second["alpha"], table, *[k for k in keep if k is not None]):
@@ -924,7 +1141,7 @@ def gated_act_quant(a: torch.Tensor, b: torch.Tensor, act: str, out_grid, *, a_g
     """act(a) * b -> int8 image on `out_grid` (+ row sums, + the fp32 product when want_y) in one launch: the gated FFN between
     the w1 / w3 GEMMs and w2.  a / b: fp32 values [rows, cols], or uint8 output indices of the GEMMs with their grids
     (a_grid / b_grid).  Grids: (scale, offset, qmin, qmax) per-tensor or None."""
-    a, b = _dev(a, "a").contiguous(), _dev(b, "b").contiguous()
+    a, b = _al16(_dev(a, "a").contiguous()), _al16(_dev(b, "b").contiguous())
     if a.dtype != b.dtype or a.shape != b.shape or a.dtype not in (torch.float32, torch.uint8):
         raise RuntimeError("mobilequant_amd: gated_act_quant needs two float32 or two uint8 tensors of one shape")
     cols = a.shape[-1]
@@ -938,6 +1155,8 @@ def gated_act_quant(a: torch.Tensor, b: torch.Tensor, act: str, out_grid, *, a_g
             ptrs += [None, None] + ([0.0, 0.0] if with_limits else [])
         else:
             s, o = _f32(g[0], "scale"), _f32(g[1], "offset")
+            if s.numel() != 1 or o.numel() != 1:
+                raise RuntimeError(f"mobilequant_amd: the gated activation takes per-tensor grids: scale and offset of one element (got {s.numel()}, {o.numel()})")
             keep += [s, o]
             ptrs += [s.data_ptr(), o.data_ptr()] + ([float(g[2]), float(g[3])] if with_limits else [])
     with _on(a, b, *keep):
@@ -957,6 +1176,8 @@ def gated_table(act: str, out_grid, a_grid, b_grid, mid_grid=None, act_grid=None
             ptrs += [None, None] + ([0.0, 0.0] if with_limits else [])
         else:
             s, o = _f32(g[0], "scale"), _f32(g[1], "offset")
+            if s.numel() != 1 or o.numel() != 1:
+                raise RuntimeError(f"mobilequant_amd: the gated activation takes per-tensor grids: scale and offset of one element (got {s.numel()}, {o.numel()})")
             keep += [s, o]
             ptrs += [s.data_ptr(), o.data_ptr()] + ([float(g[2]), float(g[3])] if with_limits else [])
     with _on(table, *keep):
@@ -967,8 +1188,10 @@ def gated_table(act: str, out_grid, a_grid, b_grid, mid_grid=None, act_grid=None
 def gated_lookup(a: torch.Tensor, b: torch.Tensor, table: torch.Tensor, tiled: bool = False):
     """uint8 index tensors a, b [rows, cols] -> (int8 image, row sums) through a gated_table (mq_gated_lookup).  tiled: the image
     in the fragment-blocked layout of quantize_tiled ([ceil16(rows), cols], cols % 64 == 0)."""
-    a, b = _dev(a, "a").contiguous(), _dev(b, "b").contiguous()
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.shape != b.shape or table.dtype != torch.int8 or table.numel() != 65536:
+    a, b = _al16(_dev(a, "a").contiguous()), _al16(_dev(b, "b").contiguous())
+    _dev(table, "table")
+    if (a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.shape != b.shape or table.dtype != torch.int8 or table.numel() != 65536
+            or not table.is_contiguous()):
         raise RuntimeError("mobilequant_amd: gated_lookup needs two uint8 tensors of one shape and an int8 [65536] table")
     cols = a.shape[-1]
     rows = a.numel() // max(cols, 1)
@@ -1042,6 +1265,26 @@ def attention_image_cache(kv_heads: int, head_dim: int, max_len: int, device) ->
             "v_pre": torch.zeros(kv_heads * (rows // 64) * head_dim, dtype=torch.int32, device=dev) if head_dim != 64 else None}
 
 
+def _image_cache(cache: dict, who: str) -> None:
+    """The tensors of an attention_image_cache dict, every one of which goes to the entry by pointer: dtype, contiguity and the element
+    count its kv_heads / head_dim / rows give."""
+    KV, D, rows = int(cache["kv_heads"]), int(cache["head_dim"]), int(cache["rows"])
+    for name, dt, n in (("k_i8", torch.int8, KV * rows * D), ("vt_i8", torch.int8, KV * rows * D), ("k_rs", torch.int32, KV * rows),
+                        ("k_f16", torch.float16, KV * rows * D), ("v_pre", torch.int32, KV * (rows // 64) * D)):
+        if cache.get(name) is not None:
+            _raw(cache[name], f"{who} cache['{name}']", dt, n)
+    if cache.get("v_pre") is None and D != 64:
+        raise RuntimeError(f"mobilequant_amd: {who} cache['v_pre'] is missing (head_dim {D} keeps a value prefix)")
+
+
+def _grid1(g, who: str):
+    """(scale, offset) of a per-tensor grid tuple as contiguous float32, one element each."""
+    s, o = _f32(g[0], "scale"), _f32(g[1], "offset")
+    if s.numel() != 1 or o.numel() != 1:
+        raise RuntimeError(f"mobilequant_amd: {who} takes per-tensor grids: scale and offset of one element (got {s.numel()}, {o.numel()})")
+    return s, o
+
+
 F16_OFFSETS = (-256.0, 511.0)     # q / k offsets the f16 score contraction holds exactly: |index - offset| <= 511 (mq_attention.hip)
 
 
@@ -1067,7 +1310,7 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     f16: head_dim 64 with a score grid contracts q.k^T over fp16 images of the centred indices, exact only while both q / k offsets
     lie in F16_OFFSETS (the prep kernel poisons the images with NaN otherwise).  True / False choose; None reads the offsets on the
     host (int8 contraction while a graph is being captured: no device read there).  The int8 contraction is exact for any grid."""
-    cos, sin = _f32(cos, "cos"), _f32(sin, "sin")
+    cos, sin = _f32(cos, "cos", True), _f32(sin, "sin", True)
     D = int(head_dim)
     if D not in (64, 128, 256):
         raise RuntimeError("mobilequant_amd: attention_quant serves head_dim 64, 128 and 256")
@@ -1077,14 +1320,14 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     idx = None
     if qkv_idx is not None:       # (uint8 [S, (heads + 2 kv_heads) * 64] of int8_linear_segmented, ((scale, offset) x 3))
         idx, in_grids = qkv_idx
-        idx = _dev(idx, "qkv_idx").contiguous()
+        idx = _al16(_dev(idx, "qkv_idx").contiguous())
         B = idx.shape[0] if idx.dim() == 3 else 0                    # 0: one sequence, 2-D tensors
         S = idx.shape[-2]
         if idx.dtype != torch.uint8 or idx.shape[-2:] != (S, (heads + 2 * kv_heads) * D) or idx.dim() not in (2, 3) or cos.shape != (S, rot):
             raise RuntimeError("mobilequant_amd: attention_quant qkv_idx must be uint8 [(B,) S, (H + 2 KV) * 64], cos / sin [S, 64]")
         q = k = v = None
     else:
-        q, k, v = (_dev(t, n).contiguous() for t, n in ((q, "q"), (k, "k"), (v, "v")))
+        q, k, v = (_al16(_dev(t, n).contiguous()) for t, n in ((q, "q"), (k, "k"), (v, "v")))
         B = q.shape[0] if q.dim() == 3 else 0
         S = q.shape[-2]
         lead = (B,) if B else ()
@@ -1110,7 +1353,7 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
         if g is None:
             setattr(a, name, _lib.MqGrid(None, None, 0.0, 0.0))
         else:
-            s, o = _f32(g[0], "scale"), _f32(g[1], "offset")
+            s, o = _grid1(g, "attention_quant")
             keep += [s, o]
             setattr(a, name, _lib.MqGrid(s.data_ptr(), o.data_ptr(), float(g[2]), float(g[3])))
     first = idx if idx is not None else q
@@ -1118,7 +1361,7 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     if idx is not None:
         a.qkv_idx = idx.data_ptr()
         for name, g in zip(("q_in", "k_in", "v_in"), in_grids):
-            sc, of = _f32(g[0], "scale"), _f32(g[1], "offset")
+            sc, of = _grid1(g, "attention_quant")
             keep += [sc, of]
             setattr(a, name, _lib.MqGrid(sc.data_ptr(), of.data_ptr(), 0.0, 255.0))
     out = torch.empty(((B,) if B else ()) + (S, heads * D), dtype=torch.float32, device=dev) if want_out or image is None else None
@@ -1128,6 +1371,7 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     if cache is not None:
         if (cache["kv_heads"], cache["head_dim"]) != (kv_heads, D) or cache["k_i8"].device != dev:
             raise RuntimeError("mobilequant_amd: attention_quant cache was built for another shape / device")
+        _image_cache(cache, "attention_quant")
         if pos0 % 64 or pos0 < 0 or pos0 + S > cache["rows"]:
             raise RuntimeError(f"mobilequant_amd: attention_quant cache continuation needs pos0 % 64 == 0 and pos0 + padded S <= {cache['rows']} "
                                f"(pos0={pos0}, S={S})")
@@ -1169,8 +1413,9 @@ def attention_quant(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Opt
     a.seq_real = S_real
     if image is not None:
         q_t, rs_t, row0, shift, tiled = image
+        _dev(q_t, "image"), _dev(rs_t, "image row sums")
         need = (row0 + nb * S_real + 15) // 16 * 16 if tiled else row0 + nb * S_real
-        if (q_t.dtype != torch.int8 or rs_t.dtype != torch.int32 or not q_t.is_contiguous() or q_t.shape[-1] != heads * D
+        if (q_t.dtype != torch.int8 or rs_t.dtype != torch.int32 or not q_t.is_contiguous() or not rs_t.is_contiguous() or q_t.shape[-1] != heads * D
                 or row0 < 0 or row0 + nb * S_real > rs_t.numel() or need > q_t.shape[0]):
             raise RuntimeError("mobilequant_amd: attention_quant image must be int8 [rows (tiled: ceil16), heads*64] + int32 row sums [rows]")
         keep += [q_t, rs_t]
@@ -1202,6 +1447,7 @@ def _cache_bridge_args(fn: str, cache: dict, k: torch.Tensor, v: torch.Tensor, p
     _dev(k, "k"), _dev(v, "v")
     if cache["k_i8"].device != k.device or v.device != k.device:
         raise RuntimeError(f"mobilequant_amd: {fn} image cache and decode caches live on different devices")
+    _image_cache(cache, fn)
     a = _lib.MqAttentionCacheArgs()
     a.k, a.v, a.k_head_stride, a.v_head_stride, a.v_chunked = k.data_ptr(), v.data_ptr(), int(k.stride(0)), int(v.stride(0)), int(bool(v_chunked))
     a.kv_heads, a.head_dim, a.cache_len, a.p0, a.n, a.cache_seq = KV, D, L, p0, n, rows
@@ -1226,7 +1472,7 @@ def attention_cache_import(cache: dict, k: torch.Tensor, v: torch.Tensor, n: int
     keep = []
     for name in ("qk_a", "qk_b"):
         g = grids[name]
-        s, o = _f32(g[0], "scale"), _f32(g[1], "offset")
+        s, o = _grid1(g, "attention_cache_import")
         keep += [s, o]
         setattr(a, name, _lib.MqGrid(s.data_ptr(), o.data_ptr(), float(g[2]), float(g[3])))
     a.k_rowsum = cache["k_rs"].data_ptr()
@@ -1259,9 +1505,11 @@ def score_head(y: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     if y.dim() != 2 or y.dtype != torch.float32:
         raise RuntimeError("mobilequant_amd: score_head y must be fp32 [M, K]")
     M, K = y.shape
-    if y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:
+    if y.stride(1) != 1 or y.stride(0) % 4:
         y = y.contiguous()
-    w = _f32(weight, "score_head weight")
+    if y.data_ptr() % 16:                # (.contiguous() hands a dense view off a 16-byte boundary back as it is)
+        y = y.contiguous().clone()
+    w = _f32(weight, "score_head weight", True)
     V = w.shape[0]
     if w.dim() != 2 or w.shape[1] != K:
         raise RuntimeError(f"mobilequant_amd: score_head weight must be [V, {K}], got {tuple(w.shape)}")
@@ -1275,8 +1523,8 @@ def score_head(y: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     t = None
     if targets is not None:
         _dev(targets, "score_head targets")
-        if targets.shape != (M,):
-            raise RuntimeError(f"mobilequant_amd: score_head targets must be [{M}]")
+        if targets.shape != (M,) or targets.dtype.is_floating_point or targets.dtype == torch.bool:
+            raise RuntimeError(f"mobilequant_amd: score_head targets must be [{M}] integers (got {tuple(targets.shape)}, {targets.dtype})")
         t = targets.to(torch.int64).contiguous()
         if M and int(t.max()) >= V:
             raise RuntimeError(f"mobilequant_amd: score_head target {int(t.max())} outside the vocabulary [0, {V})")
