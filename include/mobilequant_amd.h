@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_lwc_search -- the clip search that initialises learnable weight clipping; + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_w4a16_linear, mq_w4a16_supported -- fp16 activations on packed 4-bit group-wise weights (weight-only W4A16), DESIGN.md 4.9: a new entry and struct only; + mq_lwc_search -- the clip search that initialises learnable weight clipping; + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -1157,6 +1157,37 @@ typedef struct mq_beam_select_args {
   int64_t scratch_bytes;
 } mq_beam_select_args;
 int mq_beam_select(const mq_beam_select_args* args, mq_stream_t stream);
+
+/* ---- W4A16: weight-only 4-bit linears ---------------------------------------------------------------------------------------------
+ * The arithmetic the reference delegates to auto_gptq's QuantLinear (qmodule.py:803-829: x.half() @ (scales * (q - zeros)), cast back
+ * to x.dtype), with an fp32 accumulator.  For weight row n and group G = k / group_size (G groups per row):
+ *   w16[n, k] = fp16_rne(float(scales[n, G]) * float(u[n, k] - zeros[n, G]))   u: the stored nibble 0..15 of the mq_pack_w4 image
+ *                                                                              w_packed [N, K / 2]; zeros: the grid's offset minus
+ *                                                                              qmin, INTEGER-valued with |zero| <= 1024 (the caller's
+ *                                                                              duty; u - zero is then exact in fp16: one rounding)
+ *   x16[m, k] = fp16_rne(x[m, k])                                              (x_dtype MQ_F16: as is)
+ *   out[m, n] = out_dtype(sum_k x16[m, k] * w16[n, k] + bias[n])               exact products, fp32 accumulation in an order the kernel
+ *                                                                              chooses, fp32 bias (nullable) added in fp32, one rounding
+ * scales / zeros: fp16 [N, G].  x [M, K] and out [M, N] dense, MQ_F32 or MQ_F16 each.
+ * mq_w4a16_supported: 0 when the shape is not served, else which kernel the entry takes -- 1: the weight-streaming GEMV (M <= 8 and
+ * M * K <= 65536), 2: the MFMA GEMM (everything else).  Served: 1 <= M <= 2^30, N % 16 == 0 (N <= 4194240), K % 64 == 0
+ * (K <= 2^24), group_size a multiple of 32 that divides K (per-row grids: group_size = K).  Others: MQ_EUNSUPPORTED with the rule in
+ * the message.  Null or misaligned pointers (x, w_packed, out, bias: 16 bytes; scales, zeros: 2) and dtypes other than MQ_F32 / MQ_F16:
+ * MQ_EINVAL, before any HIP call.  M == 0 returns MQ_OK without a launch.  One launch, no host synchronisation: capturable. */
+typedef struct mq_w4a16_args {
+  const void* x;
+  int x_dtype;
+  int64_t M, N, K;
+  int64_t group_size;
+  const uint8_t* w_packed;
+  const void* scales; /* fp16 [N, K / group_size] */
+  const void* zeros;  /* fp16 [N, K / group_size] */
+  const float* bias;  /* [N] or NULL */
+  void* out;
+  int out_dtype;
+} mq_w4a16_args;
+int mq_w4a16_supported(int64_t M, int64_t N, int64_t K, int64_t group_size);
+int mq_w4a16_linear(const mq_w4a16_args* args, mq_stream_t stream);
 
 /* Re-order the slots of the caches in place: a SIMULTANEOUS assignment "slot d continues old slot parent[d]" over all slots (the
  * rule: csrc/mq_decode_reorder.hip's header).  The argument block, the caches table, pos and parent are mq_decode_cache_fork's.  Slot

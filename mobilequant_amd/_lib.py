@@ -146,6 +146,11 @@ class MqBeamSelectArgs(ctypes.Structure):
                 ("cand_logprob", c_void_p), ("row_lse", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_int64)]
 
 
+class MqW4A16Args(ctypes.Structure):
+    _fields_ = [("x", c_void_p), ("x_dtype", c_int), ("M", c_int64), ("N", c_int64), ("K", c_int64), ("group_size", c_int64),
+                ("w_packed", c_void_p), ("scales", c_void_p), ("zeros", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("out_dtype", c_int)]
+
+
 MQ_LOGPROB_MAX_TOP = 20
 MQ_LOGPROB_SCRATCH_BYTES = 360448
 MQ_BEAM_SCRATCH_BYTES = 363008
@@ -263,6 +268,8 @@ _SIGNATURES = {
     "mq_decode_cache_fork": (c_int, [POINTER(MqDecodeCacheForkArgs), _P]),
     "mq_beam_select": (c_int, [POINTER(MqBeamSelectArgs), _P]),
     "mq_decode_cache_reorder": (c_int, [POINTER(MqDecodeCacheForkArgs), _P]),
+    "mq_w4a16_supported": (c_int, [c_int64, c_int64, c_int64, c_int64]),
+    "mq_w4a16_linear": (c_int, [POINTER(MqW4A16Args), _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),

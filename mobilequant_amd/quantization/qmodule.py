@@ -1465,11 +1465,147 @@ def create_fp_model(model):
     return model
 
 
-def create_weight_only_qmodel(model, w_qcfg=None):
-    """W4A16 packing is the third-party auto_gptq path of the reference (qmodule.py:803-886), which is
-    outside the W8A8 / W4A8 hot path this package implements."""
-    raise NotImplementedError("weight-only (W4A16) packing relies on auto_gptq in the reference and is out of scope "
-                              "here; use the W4A8 path (QLinear with a 4-bit weight quantizer)")
+class WeightOnlyLinear(nn.Module):
+    """A linear with packed 4-bit group-wise weights and 16-bit activations (W4A16) on mq_w4a16_linear -- what the reference gets from
+    auto_gptq's QuantLinear (qmodule.py:827-829).  Buffers: qweight uint8 [N, K / 2] (the mq_pack_w4 image of index - qmin), scales and
+    zeros fp16 [N, K / group_size] (zeros = offset - qmin), bias fp32 [N] or None.  forward: fp32 or fp16 in, the same dtype out,
+    y = sum_k fp16(x) * w16 + bias with w16 = fp16(scales * (u - zeros)), accumulated in fp32."""
+
+    bits = 4
+
+    def __init__(self, in_features: int, out_features: int, group_size: int = -1, bias: bool = False, device=None):
+        super().__init__()
+        g = in_features if group_size == -1 else int(group_size)
+        if g <= 0 or in_features % g:
+            raise ValueError(f"mobilequant_amd: WeightOnlyLinear group_size {group_size} does not divide in_features = {in_features}")
+        self.in_features, self.out_features, self.group_size = int(in_features), int(out_features), g
+        G = in_features // g
+        self.register_buffer("qweight", torch.zeros((out_features, in_features // 2), dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.zeros((out_features, G), dtype=torch.float16, device=device))
+        self.register_buffer("zeros", torch.zeros((out_features, G), dtype=torch.float16, device=device))
+        if bias:
+            self.register_buffer("bias", torch.zeros(out_features, dtype=torch.float32, device=device))
+        else:
+            self.bias = None
+
+    def _grid16(self):
+        # module.float() / .half() convert floating buffers: the values are fp16 numbers either way
+        f16 = lambda t: t if t.dtype == torch.float16 else t.to(torch.float16)   # noqa: E731
+        return f16(self.scales), f16(self.zeros)
+
+    def forward(self, x):
+        from .. import weight_only
+        scales, zeros = self._grid16()
+        self.__dict__["_calls"] = self.__dict__.get("_calls", 0) + 1
+        return weight_only.w4a16_linear(x, self.qweight, scales, zeros, self.bias, self.group_size)
+
+    def dequantize(self) -> torch.Tensor:
+        """w16 [out_features, in_features] fp16: the weight the forward multiplies by, bit for bit."""
+        from .. import weight_only
+        scales, zeros = self._grid16()
+        return weight_only.w4a16_dequantize(self.qweight, scales, zeros, self.group_size)
+
+    def to_float(self) -> nn.Linear:
+        w = self.dequantize().float()
+        out = nn.Linear(self.in_features, self.out_features, bias=self.bias is not None, device=w.device)
+        out.weight.data = w
+        if self.bias is not None:
+            out.bias.data = self.bias.detach().float().clone()
+        return out
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, bits={self.bits}, group_size={self.group_size}, "
+                f"bias={self.bias is not None}")
+
+
+_W4A16_RULE = "N % 16 == 0, K % 64 == 0, group_size a multiple of 32 that divides K"
+
+
+def to_weight_only_quantized_linear(module, w_qcfg=None, w_scale=None, w_offset=None, *, name: str = ""):
+    """An nn.Linear / QLinear as a WeightOnlyLinear (reference: qmodule.py:803-829).  From a QLinear: its weight quantizer's cfg, scale and
+    offset (an LWC or dynamic weight quantizer: the grid its forward would use on this weight); its input / output quantizers must be
+    absent or >= 16 bits.  From an nn.Linear: w_qcfg, the grid from compute_min_max_from_tensor.  ValueError, naming the module and the
+    rule, for anything mq_w4a16_linear does not serve (bit widths 2 / 3, a grid that is not per-channel, a shape outside
+    mq_w4a16_supported): never another path.  name: the module's name for those messages.  A weight on the meta device gives the
+    module with empty buffers (structure only)."""
+    from .. import weight_only
+    who = f"{name or type(module).__name__} ({type(module).__name__} {tuple(module.weight.shape)})"
+    if isinstance(module, QLinear):
+        for slot, q in (("input", module.input_quantizer), ("output", module.output_quantizer)):
+            if q is not None and q.qcfg.bitwidth < 16:
+                raise ValueError(f"mobilequant_amd: {who} has a {q.qcfg.bitwidth}-bit {slot} quantizer: weight-only conversion takes "
+                                 "activation quantizers of 16 bits or more, or none")
+        wq = module.weight_quantizer
+        if wq is None:
+            raise ValueError(f"mobilequant_amd: {who} has no weight quantizer")
+        if w_qcfg is None:
+            w_qcfg = wq.qcfg
+        if (w_scale is None or w_offset is None) and (wq.lwc or wq.qcfg.is_dynamic) and not module.weight.is_meta and w_qcfg is wq.qcfg \
+                and w_qcfg.bitwidth == 4 and w_qcfg.is_per_channel:
+            with torch.no_grad():
+                wq(module.weight.detach().to(torch.float32))          # leaves the grid it used (clipped range under LWC) as plain tensors
+        if w_scale is None:
+            w_scale = getattr(wq, "scale", None)
+        if w_offset is None:
+            w_offset = getattr(wq, "offset", None)
+    if w_qcfg is None:
+        raise ValueError(f"mobilequant_amd: {who} needs a weight QuantConfig (w_qcfg) for weight-only conversion")
+    if w_qcfg.bitwidth != 4:
+        raise ValueError(f"mobilequant_amd: {who} has a {w_qcfg.bitwidth}-bit weight grid: weight-only linears are built for 4 bits "
+                         "(2 and 3 are out of scope)")
+    if not w_qcfg.is_per_channel:
+        raise ValueError(f"mobilequant_amd: {who} has a per-tensor weight grid: weight-only linears take per-channel grids "
+                         "(one scale and offset per row, or per row and group)")
+    out_features, in_features = module.weight.shape
+    group_size = in_features if w_qcfg.group_size == -1 else int(w_qcfg.group_size)
+    if group_size <= 0 or in_features % group_size:
+        raise ValueError(f"mobilequant_amd: {who}: group_size {w_qcfg.group_size} does not divide K = {in_features} ({_W4A16_RULE})")
+    if not weight_only.w4a16_supported(out_features, in_features, group_size):
+        raise ValueError(f"mobilequant_amd: {who} with group_size {group_size} is outside mq_w4a16_supported ({_W4A16_RULE})")
+    device = module.weight.device
+    out = WeightOnlyLinear(in_features, out_features, group_size, module.bias is not None, device=device)
+    if module.weight.is_meta:
+        return out
+    weight = module.weight.detach().to(torch.float32)
+    if w_scale is None or w_offset is None:
+        min_val, max_val = compute_min_max_from_tensor(weight, w_qcfg.is_per_channel, w_qcfg.group_size)
+        w_scale, w_offset, *_ = compute_scale_offset_from_min_max(min_val, max_val, w_qcfg.bitwidth, w_qcfg.is_symmetric)
+    n_groups = in_features // group_size
+    if w_scale.numel() != out_features * n_groups or w_offset.numel() != out_features * n_groups:
+        raise ValueError(f"mobilequant_amd: {who}: the weight grid holds {w_scale.numel()} scales, {out_features} x {n_groups} are needed")
+    try:
+        qweight, scales, zeros = weight_only.w4a16_pack(weight, w_scale.detach().reshape(out_features, n_groups),
+                                                        w_offset.detach().reshape(out_features, n_groups), w_qcfg.bitwidth,
+                                                        w_qcfg.is_symmetric, group_size)
+    except ValueError as e:
+        raise ValueError(f"mobilequant_amd: {who}: {e}") from None
+    out.qweight, out.scales, out.zeros = qweight, scales, zeros
+    if module.bias is not None:
+        out.bias = module.bias.detach().to(torch.float32).clone()
+    return out
+
+
+def create_weight_only_qmodel(model, w_qcfg=None, *, _prefix: str = ""):
+    """Weight-only (W4A16) surgery with the reference's traversal (qmodule.py:868-886): QLinear -> WeightOnlyLinear on its own weight
+    grid, Q-norms to float, QMatMul / QSiLU / QGELU to their float modules, a plain nn.Linear whose name lacks `lm_head` ->
+    WeightOnlyLinear on w_qcfg; modules with more than one child are descended into."""
+    for name, module in reversed(list(model._modules.items())):
+        full = _prefix + name
+        if isinstance(module, QLinear):
+            model._modules[name] = to_weight_only_quantized_linear(module, name=full)
+        elif isinstance(module, (QRMSNorm, QLayerNorm)):
+            model._modules[name] = type(module).to_float(module)
+        elif isinstance(module, QMatMul):
+            model._modules[name] = FMatMul()
+        elif isinstance(module, QSiLU):
+            model._modules[name] = nn.SiLU()
+        elif isinstance(module, QGELU):
+            model._modules[name] = nn.GELU()
+        elif isinstance(module, nn.Linear) and "lm_head" not in name:
+            model._modules[name] = to_weight_only_quantized_linear(module, w_qcfg, name=full)
+        elif module is not None and len(list(module.children())) > 1:
+            create_weight_only_qmodel(module, w_qcfg, _prefix=full + ".")
+    return model
 
 
 def _minmax_entry(q: Quantizer):
@@ -1673,9 +1809,14 @@ def int8_coverage(model, reset=False):
     "simulated_modules": [names], "summary": str}.  The simulated path is correct by the reference's semantics but ~10x slower; an
     evaluation that silently lands on it (a 16-bit producer in front of q/k/v, a per-group recipe, grad mode) shows up here.
     Modules executed inside a fused block (fuse_gated_mlp / fuse_attention / fuse_decoder_layer) count as "int8 (fused block)"."""
-    mods, n_int, n_sim, sim_names = {}, 0, 0, []
+    mods, n_int, n_sim, sim_names, w4a16 = {}, 0, 0, [], []
     for name, mod in model.named_modules():
-        if isinstance(mod, (QLinear, QMatMul)):
+        if isinstance(mod, WeightOnlyLinear):              # no integer activations, nothing simulated: listed, counted apart
+            mods[name] = {"w4a16": mod.__dict__.get("_calls", 0)}
+            w4a16.append(name)
+            if reset:
+                mod.__dict__["_calls"] = 0
+        elif isinstance(mod, (QLinear, QMatMul)):
             c = dict(mod.__dict__.get("_path_counts", {}))
             mods[name] = c
             i = sum(v for k, v in c.items() if k.startswith("int8"))
@@ -1690,10 +1831,15 @@ def int8_coverage(model, reset=False):
         for k, v in mods[name].items():
             if k.startswith("simulated"):
                 why[k] = why.get(k, 0) + v
-    summary = f"{n_int} integer-path calls, {n_sim} simulated-path calls in {len(sim_names)} of {len(mods)} QLinear / QMatMul modules"
+    summary = (f"{n_int} integer-path calls, {n_sim} simulated-path calls in {len(sim_names)} of {len(mods) - len(w4a16)} "
+               "QLinear / QMatMul modules")
     if why:
         summary += "; " + "; ".join(f"{v} x {k}" for k, v in sorted(why.items(), key=lambda kv: -kv[1]))
-    return {"modules": mods, "int8_calls": n_int, "simulated_calls": n_sim, "simulated_modules": sim_names, "summary": summary}
+    res = {"modules": mods, "int8_calls": n_int, "simulated_calls": n_sim, "simulated_modules": sim_names, "summary": summary}
+    if w4a16:
+        res["w4a16_modules"] = w4a16
+        res["summary"] += f"; {len(w4a16)} weight-only (w4a16) linears"
+    return res
 
 
 def fuse_gated_mlp(model) -> int:
