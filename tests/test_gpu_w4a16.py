@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(1, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import w4a16_ref as R  # noqa: E402
+from w4a16_cases import exact_x, one_hot_x  # noqa: E402,F401  (shared with the launch-branch pin, tests/test_gpu_w4a16_oracle.py)
 from oracle import mq_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -84,22 +85,6 @@ def exact_weights(rng, N, K, g):
     z16 = rng.integers(-3, 19, size=(N, G)).astype(F16)
     s16 = (2.0 ** rng.integers(-6, 0, size=(N, G))).astype(F16)
     return u, s16, z16
-
-
-def exact_x(rng, M, K):
-    x = rng.integers(-4, 5, size=(M, K)).astype(F32)
-    x[:, 0] = 3.0                                             # (no all-zero row even at K = 64)
-    return x
-
-
-def one_hot_x(rng, M, K):
-    """Row m reads out weight column k_m (value 1), and -- from the second row on -- a second column with weight -2."""
-    x = np.zeros((M, K), F32)
-    for m in range(M):
-        x[m, rng.integers(0, K)] = 1.0
-        if m:
-            x[m, (7 * m + 3) % K] += -2.0
-    return x
 
 
 GEMV_SHAPES = [(16, 64, 32), (48, 128, 64), (272, 512, 128), (16, 256, 256)]
