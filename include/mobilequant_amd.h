@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_w4a16_linear, mq_w4a16_supported -- fp16 activations on packed 4-bit group-wise weights (weight-only W4A16), DESIGN.md 4.9: a new entry and struct only; + mq_lwc_search -- the clip search that initialises learnable weight clipping; + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_gptq_round, mq_gptq_workspace_bytes -- GPTQ error-compensated rounding onto a fixed weight grid, DESIGN.md 4.10: a new entry and struct only; + mq_w4a16_linear, mq_w4a16_supported -- fp16 activations on packed 4-bit group-wise weights (weight-only W4A16), DESIGN.md 4.9: a new entry and struct only; + mq_lwc_search -- the clip search that initialises learnable weight clipping; + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -1188,6 +1188,46 @@ typedef struct mq_w4a16_args {
 } mq_w4a16_args;
 int mq_w4a16_supported(int64_t M, int64_t N, int64_t K, int64_t group_size);
 int mq_w4a16_linear(const mq_w4a16_args* args, mq_stream_t stream);
+
+/* ---- GPTQ: error-compensated rounding of a weight onto a fixed grid ---------------------------------------------------------------
+ * Rounds w [N, K] (fp32, row-major) onto the per-(row, group) grid scale / offset [N, G] (fp32, G = K / group_size, in the ORIGINAL
+ * column order: static groups), feeding each column's rounding error forward through u [K, K] (fp32, row-major), the UPPER Cholesky
+ * factor of the inverse input Hessian in WALK order (H^-1 = u^T u, positive diagonal; only the upper triangle is read).  perm: int32
+ * [K] or NULL -- step t handles original column perm[t]; NULL is the identity.  For every row n independently, in fp32 with
+ * round-to-nearest:
+ *   for t = 0 .. K-1:   k = perm[t], g = k / group_size
+ *     q   = clamp(round_ste(w[k] / s[g]) + o[g], qmin, qmax)          the index of mq_quantize: IEEE divide, (rint(t) - t) + t, fp32 add
+ *     dq  = (q - o[g]) * s[g]                                         fp32 subtraction, then fp32 multiplication
+ *     e   = (w[k] - dq) / u[t][t]                                     fp32 subtraction, then the IEEE divide
+ *     loss += (double)e * (double)e                                   ascending t
+ *     for every t' > t:   w[perm[t']] = fmaf(-e, u[t][t'], w[perm[t']])
+ * Every element receives its updates as one fmaf each in ascending t; nothing is contracted, reassociated or replaced by a reciprocal,
+ * so the result does not depend on how the kernel blocks the work.  A NaN weight stores qmin and poisons the later columns of its own
+ * row only.  Outputs: index uint8 [N, K] = q - qmin at the ORIGINAL column (what mq_quantize writes with q_dtype MQ_U8, shift = qmin,
+ * and mq_pack_w4 reads); w_deq fp32 [N, K] or NULL = dq; loss fp64 [N] or NULL.  w is not modified.
+ * workspace: a device buffer of at least mq_gptq_workspace_bytes(N, K) bytes (-1 for a shape not served), workspace_bytes its size.
+ * Served: N >= 1 (N == 0 returns MQ_OK without a launch), 16 <= K <= 16384 with K % 4 == 0, group_size a multiple of 4 that divides K,
+ * integer qmin < qmax with qmax - qmin <= 255 (bit widths 2 to 8), every pointer 16-byte aligned.  Everything else, a null required
+ * pointer and perm without u: MQ_EINVAL with a message, before any HIP call.  The CONTENTS of u and perm are the caller's duty (a perm
+ * entry outside [0, K) is held inside it: wrong results, no stray address).  Six launches on `stream`, no host synchronisation:
+ * capturable. */
+typedef struct mq_gptq_args {
+  const float* w;
+  int64_t N, K;
+  int64_t group_size;
+  const float* scale;  /* [N, K / group_size] */
+  const float* offset; /* [N, K / group_size] */
+  float qmin, qmax;
+  const float* u;      /* [K, K] */
+  const int32_t* perm; /* [K] or NULL */
+  void* workspace;
+  int64_t workspace_bytes;
+  uint8_t* index; /* [N, K] */
+  float* w_deq;   /* [N, K] or NULL */
+  double* loss;   /* [N] or NULL */
+} mq_gptq_args;
+int64_t mq_gptq_workspace_bytes(int64_t N, int64_t K);
+int mq_gptq_round(const mq_gptq_args* args, mq_stream_t stream);
 
 /* Re-order the slots of the caches in place: a SIMULTANEOUS assignment "slot d continues old slot parent[d]" over all slots (the
  * rule: csrc/mq_decode_reorder.hip's header).  The argument block, the caches table, pos and parent are mq_decode_cache_fork's.  Slot

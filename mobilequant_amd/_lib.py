@@ -151,6 +151,12 @@ class MqW4A16Args(ctypes.Structure):
                 ("w_packed", c_void_p), ("scales", c_void_p), ("zeros", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("out_dtype", c_int)]
 
 
+class MqGptqArgs(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("N", c_int64), ("K", c_int64), ("group_size", c_int64), ("scale", c_void_p), ("offset", c_void_p),
+                ("qmin", c_float), ("qmax", c_float), ("u", c_void_p), ("perm", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_int64), ("index", c_void_p), ("w_deq", c_void_p), ("loss", c_void_p)]
+
+
 MQ_LOGPROB_MAX_TOP = 20
 MQ_LOGPROB_SCRATCH_BYTES = 360448
 MQ_BEAM_SCRATCH_BYTES = 363008
@@ -270,6 +276,8 @@ _SIGNATURES = {
     "mq_decode_cache_reorder": (c_int, [POINTER(MqDecodeCacheForkArgs), _P]),
     "mq_w4a16_supported": (c_int, [c_int64, c_int64, c_int64, c_int64]),
     "mq_w4a16_linear": (c_int, [POINTER(MqW4A16Args), _P]),
+    "mq_gptq_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "mq_gptq_round": (c_int, [POINTER(MqGptqArgs), _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mq_calib_attention_probs_causal": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, c_int, _P, _P, _P, _P, _P]),
     "mq_calib_norm": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),
