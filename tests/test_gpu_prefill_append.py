@@ -18,17 +18,18 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _model(dev, D, fused=True):
-    """LlamaShape.toy variant (2 layers, 4 / 2 heads) at head_dim D, W8A8, calibrated, the attention QMatMuls on fixed grids; fused
-    through fuse_decoder_layer unless fused=False.  Built once per (D, fused)."""
-    key = (D, fused)
+def _model(dev, D, fused=True, kv_heads=2):
+    """LlamaShape.toy variant (2 layers, 4 / kv_heads heads; kv_heads = 1 at head_dim 256 is Gemma's MQA geometry) at head_dim D, W8A8,
+    calibrated, the attention QMatMuls on fixed grids; fused through fuse_decoder_layer unless fused=False.  Built once per
+    (D, fused, kv_heads)."""
+    key = (D, fused, kv_heads)
     if key in _MODELS:
         return _MODELS[key]
     import mobilequant_amd as mq
     from mobilequant_amd import llama
     from mobilequant_amd.calibration import get_act_range
     from mobilequant_amd.llama import LlamaForCausalLM, LlamaShape
-    shape = LlamaShape.toy(hidden=256, layers=2, heads=4, kv_heads=2, head_dim=D, ffn=512, vocab=97, max_pos=CACHE_LEN)
+    shape = LlamaShape.toy(hidden=256, layers=2, heads=4, kv_heads=kv_heads, head_dim=D, ffn=512, vocab=97, max_pos=CACHE_LEN)
     m = LlamaForCausalLM(shape)
     m.reset_parameters(seed=3, std=0.08)
     m = m.to(dev).eval().requires_grad_(False)
@@ -54,6 +55,11 @@ def _model(dev, D, fused=True):
         assert llama.fuse_decoder_layer(m) == 2
     _MODELS[key] = m
     return m
+
+
+def _engine_kv_heads(D):
+    """The engine tests run head_dim 256 as MQA (one kv head under four query heads); the import tests keep two kv heads there."""
+    return 1 if D == 256 else 2
 
 
 def _ids(m, n=CACHE_LEN, seed=7):
@@ -117,7 +123,7 @@ def _greedy(e, n=4):
 
 # ---- 1 / 2: import ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("launches", [4, 5])
-@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("D", [64, 128, 256])
 def test_import_matches_the_header_formulas(dev, D, launches):
     from mobilequant_amd import ops
     m = _model(dev, D)
@@ -149,7 +155,7 @@ def test_import_matches_the_header_formulas(dev, D, launches):
     assert bool((iv["k_i8"][:, 128:] == 0x33).all()) and bool((iv["vt_i8"][:, 2:] == 0x33).all()) and bool((iv["k_rs"][:, 128:] == 0x33333333).all())
 
 
-@pytest.mark.parametrize("D,launches", [(64, 4), (128, 5)])
+@pytest.mark.parametrize("D,launches", [(64, 4), (128, 5), (256, 4), (256, 5)])
 def test_import_matches_the_prefill_preparation(dev, D, launches):
     """The images the model's own chunk at pos 0 leaves are, byte for byte, what the import makes of the caches prefill() filled."""
     from mobilequant_amd import ops
@@ -177,7 +183,7 @@ def test_import_matches_the_prefill_preparation(dev, D, launches):
 
 # ---- 3: export ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("chunked", [False, True])
-@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("D", [64, 128, 256])
 def test_export_writes_the_rows_and_nothing_else(dev, D, chunked):
     from mobilequant_amd import ops
     KV, p0, n = 2, 64, 37
@@ -185,22 +191,24 @@ def test_export_writes_the_rows_and_nothing_else(dev, D, chunked):
     c = ops.attention_image_cache(KV, D, CACHE_LEN, dev)
     for name in ("k_i8", "vt_i8"):
         c[name].copy_(torch.randint(-128, 128, c[name].shape, generator=g, device=dev, dtype=torch.int8))
-    k = torch.full((KV, CACHE_LEN, D), 0x55, dtype=torch.int8, device=dev)
-    v = torch.full((KV, CACHE_LEN // 16, D, 16) if chunked else (KV, CACHE_LEN, D), 0x55, dtype=torch.int8, device=dev)
+    # the state before is seeded random bytes, not a constant: a stray write of any byte shows
+    k = torch.randint(-128, 128, (KV, CACHE_LEN, D), generator=g, device=dev, dtype=torch.int8)
+    v = torch.randint(-128, 128, (KV, CACHE_LEN // 16, D, 16) if chunked else (KV, CACHE_LEN, D), generator=g, device=dev, dtype=torch.int8)
+    k0, v0 = k.clone(), v.clone()
     ops.attention_cache_export(c, k, v, p0, n, v_chunked=chunked)
     torch.cuda.synchronize()
     want_k, want_v = _decoded(c, CACHE_LEN)
-    logical = v.permute(0, 1, 3, 2).reshape(KV, CACHE_LEN, D) if chunked else v
-    for got, want in ((k, want_k), (logical, want_v)):
+    logical, logical0 = (t.permute(0, 1, 3, 2).reshape(KV, CACHE_LEN, D) if chunked else t for t in (v, v0))
+    for got, want, before in ((k, want_k, k0), (logical, want_v, logical0)):
         assert torch.equal(got[:, p0:p0 + n], want[:, p0:p0 + n])
-        assert bool((got[:, :p0] == 0x55).all()) and bool((got[:, p0 + n:] == 0x55).all())
+        assert torch.equal(got[:, :p0], before[:, :p0]) and torch.equal(got[:, p0 + n:], before[:, p0 + n:])
 
 
 # ---- 4 .. 7, 9, 10: the engine --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,launches", [(64, 4), (64, 5), (128, 4), (128, 5)])
+@pytest.mark.parametrize("D,launches", [(64, 4), (64, 5), (128, 4), (128, 5), (256, 4), (256, 5)])
 def test_aligned_append_is_the_models_chunked_forward(dev, D, launches):
     from mobilequant_amd.decode import DecodeEngine
-    m = _model(dev, D)
+    m = _model(dev, D, kv_heads=_engine_kv_heads(D))
     ids = _ids(m)
     ref = m.new_image_cache(1, CACHE_LEN)
     with torch.no_grad():
@@ -224,9 +232,9 @@ def test_aligned_append_is_the_models_chunked_forward(dev, D, launches):
     assert torch.equal(_greedy(e), _greedy(e2))
 
 
-@pytest.mark.parametrize("D,launches", [(64, 4), (128, 5)])
+@pytest.mark.parametrize("D,launches", [(64, 4), (128, 5), (256, 4)])
 def test_unaligned_append_steps_to_the_boundary(dev, D, launches):
-    m = _model(dev, D)
+    m = _model(dev, D, kv_heads=_engine_kv_heads(D))
     ids = _ids(m)
     a, b = _engine(m, launches), _engine(m, launches)
     for e in (a, b):
@@ -287,10 +295,10 @@ def test_rewind_then_append_is_a_fresh_engine_at_that_position(dev):
     assert torch.equal(_greedy(a, 2), _greedy(b, 2))
 
 
-@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("D", [64, 128, 256])
 def test_batched_engine_appends_on_one_slot(dev, D):
     from mobilequant_amd.decode_batch import BatchDecodeEngine
-    m = _model(dev, D)
+    m = _model(dev, D, kv_heads=_engine_kv_heads(D))
     ids, ids0, ids2 = _ids(m), _ids(m, 40, seed=8), _ids(m, 90, seed=9)
     be, twin = BatchDecodeEngine(m, 3, cache_len=CACHE_LEN), BatchDecodeEngine(m, 3, cache_len=CACHE_LEN)
     for e in (be, twin):
