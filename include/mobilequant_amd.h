@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_gptq_round, mq_gptq_workspace_bytes -- GPTQ error-compensated rounding onto a fixed weight grid, DESIGN.md 4.10: a new entry and struct only; + mq_w4a16_linear, mq_w4a16_supported -- fp16 activations on packed 4-bit group-wise weights (weight-only W4A16), DESIGN.md 4.9: a new entry and struct only; + mq_lwc_search -- the clip search that initialises learnable weight clipping; + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
+#define MQ_VERSION 304 /* 0.3.4 (additive entries since, no struct changed, number kept: + mq_w4a16_decode_gemv, mq_w4a16_decode_attention, mq_w4a16_decode_supported -- the launches of the W4A16 decode engine, DESIGN.md 4.11: new entries and structs only; + mq_gptq_round, mq_gptq_workspace_bytes -- GPTQ error-compensated rounding onto a fixed weight grid, DESIGN.md 4.10: a new entry and struct only; + mq_w4a16_linear, mq_w4a16_supported -- fp16 activations on packed 4-bit group-wise weights (weight-only W4A16), DESIGN.md 4.9: a new entry and struct only; + mq_lwc_search -- the clip search that initialises learnable weight clipping; + mq_beam_select, mq_decode_cache_reorder -- a beam-search step's candidate selection and in-place cache re-order; + mq_hist_minmax_tensor -- one-pass bit-pattern histogram beside the running min / max: percentile activation ranges; + mq_logprob_top -- per-token log-probabilities and top-n alternatives behind a selection launch; + mq_sample_ragged, mq_sample_history_count_ragged -- the rows of a ragged step under their sequences' own requests; + mq_sample_rows, mq_sample_history_count -- several rows of one sequence under one request; + mq_decode_attention_ragged -- attention rows as a (sequence, position) table over a batch of caches, DESIGN.md 4.3h: a new entry and struct only): + mq_decode_gemv_grouped (per-group weight grids in the five-launch decode GEMV), + mq_decode_attention_multi (several positions of one sequence per attention launch; a new entry and struct only, no existing struct changed).  0.3.3: + mq_score_head, mq_score_head_scratch_bytes (lm_head fused with its log-softmax).  0.3.2: + mq_decode_gemv_batch, mq_decode_attention_batch, mq_decode_head_batch (batched decode step).  0.3.1: + mq_calib_norm, mq_calib_gated, mq_calib_rope(_qkv), mq_calib_attention_probs_causal.  0.3.0: ABI BREAK -- argument structs grew at their tails (mq_decode_gemv_args in 0.3.0, mq_attention_args in 0.2.x): a caller MUST compare mq_version() / 100 with MQ_VERSION / 100 of the header it was built against (mobilequant_amd/_lib.py does) before passing a struct; + mq_decode_attention_oproj.  0.2.1: + mq_qmatmul, mq_calib_attention_probs (0.2.0: chan_scale in mq_quantize / mq_quantize_tiled; tuning knobs moved to mobilequant_amd_tuning.h) */
 
 typedef void* mq_stream_t;
 
@@ -1188,6 +1188,83 @@ typedef struct mq_w4a16_args {
 } mq_w4a16_args;
 int mq_w4a16_supported(int64_t M, int64_t N, int64_t K, int64_t group_size);
 int mq_w4a16_linear(const mq_w4a16_args* args, mq_stream_t stream);
+
+/* ---- W4A16 decode: the launches of a weight-only model's single-sequence decode step -----------------------------
+ * mq_w4a16_decode_gemv: one activation row through a packed W4A16 weight, the linear contract of mq_w4a16_linear (M = 1, fp32 in,
+ * fp32 out, the same weight walk) with a prologue that forms the row and an epilogue that consumes the sums, each chosen per launch:
+ *   prologue MQ_W4A16_PRO_PLAIN      y = x
+ *            MQ_W4A16_PRO_RMSNORM    y = norm_weight * (x * (1 / sqrt(mean(x^2) + eps)))   (+ norm_bias when given)     HFRMSNorm
+ *            MQ_W4A16_PRO_LAYERNORM  y = (x * r - r * mu) * norm_weight + norm_bias, r = 1 / sqrt(mean((x - mu)^2) + eps)  nn.LayerNorm
+ *                                    (norm_weight / norm_bias nullable); the statistics are recomputed by every workgroup, in fp32
+ *   then     x16 = fp16_rne(y), acc[n] = sum_k x16[k] * w16[n, k]                          exact products, fp32 accumulation
+ *   epilogue MQ_W4A16_EPI_BIAS       out[n] = acc[n] + bias[n]                             (bias nullable), out [N]
+ *            MQ_W4A16_EPI_RESID      out[n] = resid[n] + (acc[n] + bias[n])                one more fp32 add; out [N] must not be resid
+ *                                                                                          or x (other workgroups still read them)
+ *            MQ_W4A16_EPI_GATED      out[n] = act(acc[2 n]) * acc[2 n + 1]                 the image holds the rows of the gate linear
+ *                                    (w1) and of the up linear (w3) INTERLEAVED row by row, scales / zeros alike; out [N / 2];
+ *                                    act 0: SiLU a / (1 + exp(-a)), act 1: GELU a * 0.5 * (1 + erf(a / sqrt 2)); fp32; no bias
+ * Served (mq_w4a16_decode_supported != 0): the rule of mq_w4a16_supported -- N % 16 == 0, K % 64 == 0, group_size a multiple of 32
+ * that divides K -- with K <= 32768 (the fp16 row sits in LDS) and, gated, N % 32 == 0.  Others: MQ_EUNSUPPORTED with the rule in the
+ * message.  Null or misaligned pointers (x, w_packed, out, bias, resid, norm_weight, norm_bias: 16 bytes; scales, zeros: 4), an
+ * unknown prologue / epilogue / act, a norm prologue without eps > 0, MQ_W4A16_EPI_RESID without resid, out == resid or out == x:
+ * MQ_EINVAL, before any HIP call.  One launch, no host synchronisation: capturable. */
+#define MQ_W4A16_PRO_PLAIN 0
+#define MQ_W4A16_PRO_RMSNORM 1
+#define MQ_W4A16_PRO_LAYERNORM 2
+#define MQ_W4A16_EPI_BIAS 0
+#define MQ_W4A16_EPI_RESID 1
+#define MQ_W4A16_EPI_GATED 2
+typedef struct mq_w4a16_decode_gemv_args {
+  const float* x; /* [K] */
+  int64_t N, K;   /* rows of the packed image (gated: both linears' rows), row length */
+  int64_t group_size;
+  const uint8_t* w_packed; /* [N, K / 2] */
+  const void* scales;      /* fp16 [N, K / group_size] */
+  const void* zeros;       /* fp16 [N, K / group_size] */
+  int prologue;
+  const float* norm_weight; /* [K] or NULL */
+  const float* norm_bias;   /* [K] or NULL */
+  float eps;
+  int epilogue;
+  const float* bias;  /* [N] or NULL */
+  const float* resid; /* [N] (MQ_W4A16_EPI_RESID) */
+  int act;
+  float* out; /* [N], gated [N / 2] */
+} mq_w4a16_decode_gemv_args;
+int mq_w4a16_decode_supported(int64_t N, int64_t K, int64_t group_size, int epilogue);
+int mq_w4a16_decode_gemv(const mq_w4a16_decode_gemv_args* args, mq_stream_t stream);
+
+/* mq_w4a16_decode_attention: RoPE, the cache append and the attention of ONE new token at position p = *pos, in one launch, fp32.
+ * qkv [(heads + 2 kv_heads) * head_dim]: the q | k | v linears' outputs.  rope_row {cos[p][0 .. rot_dim), sin[p][0 .. rot_dim)} as
+ * mq_decode_embed stages it.  k_cache / v_cache [kv_heads][cache_len][head_dim] fp32 (LlamaForCausalLM.new_cache's layout for one
+ * sequence).  With half = rot_dim / 2, for d < rot_dim
+ *   rope(x)[d] = x[d] * cos[d] + (d < half ? -x[d + half] : x[d - half]) * sin[d]          two rounded products, one rounded add, no
+ *                                                                                          fma; d >= rot_dim passes through
+ *   k_cache[g][p] = rope(k_g), v_cache[g][p] = v_g                                         the only bytes of the caches written
+ *   s_t = (rope(q_h) . k_cache[g][t]) / sqrt(head_dim), t = 0 .. p, g = h / (heads / kv_heads)
+ *   out[h] = sum_t softmax(s)_t v_cache[g][t]                                              out [heads * head_dim]
+ * Nothing at a position above p is read; the row at p itself is taken from qkv, not from the cache.  p outside [0, cache_len): the
+ * launch does nothing.  Grid (heads, nsplit), the same for every p: split c owns the positions [c ch, (c + 1) ch), ch = ceil((p + 1) /
+ * nsplit).  nsplit > 1: each split leaves (max, sum, partial out) in part [heads][nsplit][head_dim + 4] and takes a ticket
+ * (ticket [heads] u32, zero before the first launch; left zero); the last arrival combines the records in split order.  The bits
+ * depend on the inputs and on nsplit alone: no floating-point atomics.
+ * Served: head_dim 32, 64, 128 or 256; heads % kv_heads == 0; rot_dim even, 2 <= rot_dim <= head_dim; 1 <= nsplit <= 16;
+ * ceil(cache_len / nsplit) <= 8192 (a split's scores sit in LDS): others MQ_EUNSUPPORTED with the rule in the message.  Null or
+ * misaligned pointers (qkv, k_cache, v_cache, out, part: 16 bytes; rope_row, pos, ticket: 4), heads / kv_heads < 1 and a cache_len
+ * outside 1 .. 2^24: MQ_EINVAL, before any HIP call.  One launch, no host synchronisation: capturable. */
+typedef struct mq_w4a16_decode_attention_args {
+  const float* qkv;
+  float* k_cache;
+  float* v_cache;
+  const float* rope_row;
+  const int* pos;
+  int heads, kv_heads, head_dim, cache_len, rot_dim;
+  int nsplit;
+  float* part;      /* [heads][nsplit][head_dim + 4], nsplit > 1 */
+  unsigned* ticket; /* [heads], nsplit > 1 */
+  float* out;       /* [heads * head_dim] */
+} mq_w4a16_decode_attention_args;
+int mq_w4a16_decode_attention(const mq_w4a16_decode_attention_args* args, mq_stream_t stream);
 
 /* ---- GPTQ: error-compensated rounding of a weight onto a fixed grid ---------------------------------------------------------------
  * Rounds w [N, K] (fp32, row-major) onto the per-(row, group) grid scale / offset [N, G] (fp32, G = K / group_size, in the ORIGINAL

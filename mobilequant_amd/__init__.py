@@ -6,6 +6,7 @@ quantization/ (the reference's qmodule API), calibration.py (generate_act_range 
 from . import _lib, ops, sampling, scoring  # noqa: F401
 from .decode import DecodeEngine, prompt_lookup_draft, spec_accept  # noqa: F401
 from .decode_batch import BatchDecodeEngine, BeamResult  # noqa: F401
+from .decode_weight_only import WeightOnlyDecodeEngine  # noqa: F401
 from .ops import beam_select, decode_cache_reorder  # noqa: F401
 from .quantization import *  # noqa: F401,F403
 from .sampling import SamplingParams, TokenLogprobs  # noqa: F401

@@ -151,6 +151,22 @@ class MqW4A16Args(ctypes.Structure):
                 ("w_packed", c_void_p), ("scales", c_void_p), ("zeros", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("out_dtype", c_int)]
 
 
+class MqW4A16DecodeGemvArgs(ctypes.Structure):
+    _fields_ = [("x", c_void_p), ("N", c_int64), ("K", c_int64), ("group_size", c_int64), ("w_packed", c_void_p), ("scales", c_void_p),
+                ("zeros", c_void_p), ("prologue", c_int), ("norm_weight", c_void_p), ("norm_bias", c_void_p), ("eps", c_float),
+                ("epilogue", c_int), ("bias", c_void_p), ("resid", c_void_p), ("act", c_int), ("out", c_void_p)]
+
+
+class MqW4A16DecodeAttentionArgs(ctypes.Structure):
+    _fields_ = [("qkv", c_void_p), ("k_cache", c_void_p), ("v_cache", c_void_p), ("rope_row", c_void_p), ("pos", c_void_p),
+                ("heads", c_int), ("kv_heads", c_int), ("head_dim", c_int), ("cache_len", c_int), ("rot_dim", c_int), ("nsplit", c_int),
+                ("part", c_void_p), ("ticket", c_void_p), ("out", c_void_p)]
+
+
+MQ_W4A16_PRO_PLAIN, MQ_W4A16_PRO_RMSNORM, MQ_W4A16_PRO_LAYERNORM = 0, 1, 2
+MQ_W4A16_EPI_BIAS, MQ_W4A16_EPI_RESID, MQ_W4A16_EPI_GATED = 0, 1, 2
+
+
 class MqGptqArgs(ctypes.Structure):
     _fields_ = [("w", c_void_p), ("N", c_int64), ("K", c_int64), ("group_size", c_int64), ("scale", c_void_p), ("offset", c_void_p),
                 ("qmin", c_float), ("qmax", c_float), ("u", c_void_p), ("perm", c_void_p), ("workspace", c_void_p),
@@ -276,6 +292,9 @@ _SIGNATURES = {
     "mq_decode_cache_reorder": (c_int, [POINTER(MqDecodeCacheForkArgs), _P]),
     "mq_w4a16_supported": (c_int, [c_int64, c_int64, c_int64, c_int64]),
     "mq_w4a16_linear": (c_int, [POINTER(MqW4A16Args), _P]),
+    "mq_w4a16_decode_supported": (c_int, [c_int64, c_int64, c_int64, c_int]),
+    "mq_w4a16_decode_gemv": (c_int, [POINTER(MqW4A16DecodeGemvArgs), _P]),
+    "mq_w4a16_decode_attention": (c_int, [POINTER(MqW4A16DecodeAttentionArgs), _P]),
     "mq_gptq_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "mq_gptq_round": (c_int, [POINTER(MqGptqArgs), _P]),
     "mq_calib_attention_probs": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_double, _P, _P, _P, _P, _P]),

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmobilequant_amd.so")
-SOURCES = ["mq_fake_quant.hip", "mq_lwc_search.hip", "mq_quantize.hip", "mq_reduce.hip", "mq_gemm.hip", "mq_gemm_grouped.hip", "mq_gemv.hip", "mq_norm.hip", "mq_activation.hip", "mq_decode.hip", "mq_decode_batch.hip", "mq_decode_grouped.hip", "mq_decode_rows.hip", "mq_attention.hip", "mq_attention_cache.hip", "mq_qmatmul.hip", "mq_score.hip", "mq_sample.hip", "mq_logprob.hip", "mq_decode_fork.hip", "mq_beam.hip", "mq_decode_reorder.hip", "mq_w4a16.hip", "mq_gptq.hip"]
+SOURCES = ["mq_fake_quant.hip", "mq_lwc_search.hip", "mq_quantize.hip", "mq_reduce.hip", "mq_gemm.hip", "mq_gemm_grouped.hip", "mq_gemv.hip", "mq_norm.hip", "mq_activation.hip", "mq_decode.hip", "mq_decode_batch.hip", "mq_decode_grouped.hip", "mq_decode_rows.hip", "mq_attention.hip", "mq_attention_cache.hip", "mq_qmatmul.hip", "mq_score.hip", "mq_sample.hip", "mq_logprob.hip", "mq_decode_fork.hip", "mq_beam.hip", "mq_decode_reorder.hip", "mq_w4a16.hip", "mq_w4a16_decode.hip", "mq_gptq.hip"]
 # per-file additions: the attention kernel is VALU-bound and consumes every MFMA result with VALU instructions -- keep the MFMA
 # results in VGPRs (no v_accvgpr_read per score element)
 # mq_decode.hip: no SLP vectorisation -- a v_pk_mul_f32 names a register PAIR although op_sel reads one half; when the other half

@@ -29,14 +29,9 @@
 // dword s}, kq = 0..3 -- a permutation of the chunk's k, the same on both operands.  x16 goes through a double-buffered LDS tile
 // [64][128] fp16 in unit order (row pitch 272 B), B fragment = one ds_read_b128.  With the weights as A the accumulator holds
 // out[m = lane & 15][n = 4 (lane >> 4) + reg]: four consecutive n per lane, one 16-byte (fp32) or 8-byte (fp16) store.
-#include "mq_common.h"
+#include "mq_w4a16_common.h"
 
 namespace mq {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 
 struct W4A16Args {
   const void* x;
@@ -51,29 +46,8 @@ struct W4A16Args {
   int out_f16;
 };
 
-#pragma clang fp contract(off)
-
-__device__ __forceinline__ unsigned pack_h2(float a, float b) {
-  return (unsigned)__half_as_ushort(__float2half_rn(a)) | ((unsigned)__half_as_ushort(__float2half_rn(b)) << 16);
-}
-
 // group of the 32-wide k block kb
 __device__ __forceinline__ int group_of(const W4A16Args& a, int kb) { return a.lg_gs32 >= 0 ? kb >> a.lg_gs32 : kb / (a.gs >> 5); }
-
-// eight dequantized weights of packed dword d, unit order; sz = (s16, s16), nz = -(1024 + z') twice
-__device__ __forceinline__ void dequant8(unsigned d, h2 sz, h2 nz, h2 (&w)[4]) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const unsigned p = ((d >> (4 * t)) & 0x000f000fu) | 0x64006400u;
-    w[t] = (__builtin_bit_cast(h2, p) + nz) * sz;
-  }
-}
-__device__ __forceinline__ h2 splat_scale(uint16_t s) { return __builtin_bit_cast(h2, (unsigned)s | ((unsigned)s << 16)); }
-__device__ __forceinline__ h2 splat_negzero(uint16_t z) {
-  const _Float16 zf = __builtin_bit_cast(_Float16, z);
-  const _Float16 v = -((_Float16)1024.0f + zf);              // exact: |z'| <= 1024, an integer
-  return h2{v, v};
-}
 
 // Four consecutive activations x[k .. k + 3] (k % 4 == 0) as the two dwords of the unit order: (j0, j2) and (j1, j3).
 template <typename XT>
@@ -91,14 +65,9 @@ __device__ __forceinline__ void load_quad<__half>(const void* x, size_t idx, flo
   v[2] = __half2float(__ushort_as_half((unsigned short)(u.y & 0xffff)));
   v[3] = __half2float(__ushort_as_half((unsigned short)(u.y >> 16)));
 }
-// byte offset inside a 16-byte unit of the (j0, j2) dword of the quad that is half h (k bit 4) of its 32-block; (j1, j3) sits 8 further
-__device__ __forceinline__ int quad_slot(int h) { return 4 * h; }
-
 // ---- M <= 8 -------------------------------------------------------------------------------------------------------------------------
 constexpr int WV_THREADS = 1024, WV_WAVES = 16;
 constexpr size_t WV_MAX_LDS = 128 * 1024;
-
-__device__ __forceinline__ int unit_rot(int c) { return (c + (c >> 2)) & 3; }
 
 template <int MT>
 __global__ void __launch_bounds__(WV_THREADS) w4a16_gemv_kernel(const W4A16Args a, const int rows_per_wg) {

@@ -125,3 +125,108 @@ def w4a16_linear(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, z
         _lib.call("mq_w4a16_linear", ctypes.byref(a), ops._stream())
     del b, x2d
     return out.reshape(*lead, N)
+
+
+# ---- the decode step's two launches (csrc/mq_w4a16_decode.hip) -------------------------------------------------------
+# Thin wrappers: every pointer goes to its entry as it is (ops._raw: device, dtype, contiguity and element count are checked here, the
+# 16-byte alignment by the entry), nothing is converted or copied, so both are capturable and write only `out` (and the cache row).
+_PROLOGUES = {"plain": _lib.MQ_W4A16_PRO_PLAIN, "rmsnorm": _lib.MQ_W4A16_PRO_RMSNORM, "layernorm": _lib.MQ_W4A16_PRO_LAYERNORM}
+_EPILOGUES = {"bias": _lib.MQ_W4A16_EPI_BIAS, "resid": _lib.MQ_W4A16_EPI_RESID, "gated": _lib.MQ_W4A16_EPI_GATED}
+_ACTS = {"silu": 0, "gelu": 1}
+DECODE_RULE = RULE + ", K <= 32768 (gated: N % 32 == 0)"
+
+
+def w4a16_decode_supported(N: int, K: int, group_size: int, epilogue: str = "bias") -> bool:
+    """mq_w4a16_decode_supported: whether mq_w4a16_decode_gemv serves a packed image of N rows (gated: both linears' rows) of length K."""
+    return bool(_lib.load().mq_w4a16_decode_supported(int(N), int(K), int(K if group_size == -1 else group_size), _EPILOGUES[epilogue]))
+
+
+def w4a16_decode_gemv_args(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor, out: torch.Tensor, *,
+                           group_size: int = -1, prologue: str = "plain", norm_weight: Optional[torch.Tensor] = None,
+                           norm_bias: Optional[torch.Tensor] = None, eps: float = 0.0, epilogue: str = "bias",
+                           bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                           act: str = "silu") -> "_lib.MqW4A16DecodeGemvArgs":
+    """The checked argument block of w4a16_decode_gemv (an engine fills it once and keeps the tensors alive)."""
+    who = "w4a16_decode_gemv"
+    if prologue not in _PROLOGUES or epilogue not in _EPILOGUES or act not in _ACTS:
+        raise ValueError(f"mobilequant_amd: {who} prologue {prologue!r} / epilogue {epilogue!r} / act {act!r}: one of {sorted(_PROLOGUES)}, "
+                         f"{sorted(_EPILOGUES)}, {sorted(_ACTS)}")
+    ops._dev(qweight, f"{who} qweight")
+    if qweight.dim() != 2:
+        raise RuntimeError(f"mobilequant_amd: {who} qweight must be [N, K / 2] (got {tuple(qweight.shape)})")
+    N, K = qweight.shape[0], qweight.shape[1] * 2
+    g, G = _groups(K, group_size)
+    ops._raw(x, f"{who} x", torch.float32, K)
+    ops._raw(qweight, f"{who} qweight", torch.uint8, N * K // 2)
+    ops._raw(scales, f"{who} scales", torch.float16, N * G)
+    ops._raw(zeros, f"{who} zeros", torch.float16, N * G)
+    ops._raw(out, f"{who} out", torch.float32, N // 2 if epilogue == "gated" else N)
+    for t, what, n in ((norm_weight, "norm_weight", K), (norm_bias, "norm_bias", K), (bias, "bias", N), (resid, "resid", N)):
+        if t is not None:
+            ops._raw(t, f"{who} {what}", torch.float32, n)
+    a = _lib.MqW4A16DecodeGemvArgs()
+    a.x, a.N, a.K, a.group_size = x.data_ptr(), N, K, g
+    a.w_packed, a.scales, a.zeros = qweight.data_ptr(), scales.data_ptr(), zeros.data_ptr()
+    a.prologue, a.eps, a.epilogue, a.act = _PROLOGUES[prologue], float(eps), _EPILOGUES[epilogue], _ACTS[act]
+    a.norm_weight = norm_weight.data_ptr() if norm_weight is not None else None
+    a.norm_bias = norm_bias.data_ptr() if norm_bias is not None else None
+    a.bias = bias.data_ptr() if bias is not None else None
+    a.resid = resid.data_ptr() if resid is not None else None
+    a.out = out.data_ptr()
+    return a
+
+
+def w4a16_decode_gemv(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor, out: torch.Tensor, **kw) -> torch.Tensor:
+    """mq_w4a16_decode_gemv: one fp32 row x [K] through a packed weight (w4a16_pack's tensors) into out (fp32 [N]; gated: [N / 2]), on
+    the current stream.  prologue "plain" | "rmsnorm" | "layernorm" (norm_weight / norm_bias fp32 [K], eps); epilogue "bias" (bias fp32
+    [N] or None) | "resid" (out = resid + (y + bias)) | "gated" (rows of the gate and the up linear interleaved; act "silu" | "gelu").
+    Every tensor is passed as it is: contiguous device tensors of exactly these dtypes and sizes, 16-byte aligned."""
+    a = w4a16_decode_gemv_args(x, qweight, scales, zeros, out, **kw)
+    with ops._on(x, qweight, scales, zeros, out, kw.get("norm_weight"), kw.get("norm_bias"), kw.get("bias"), kw.get("resid")):
+        _lib.call("mq_w4a16_decode_gemv", ctypes.byref(a), ops._stream())
+    return out
+
+
+def w4a16_decode_attention_args(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, rope_row: torch.Tensor, pos: torch.Tensor,
+                                out: torch.Tensor, *, heads: int, kv_heads: int, head_dim: int, rot_dim: int, nsplit: int = 1,
+                                part: Optional[torch.Tensor] = None,
+                                ticket: Optional[torch.Tensor] = None) -> "_lib.MqW4A16DecodeAttentionArgs":
+    """The checked argument block of w4a16_decode_attention."""
+    who = "w4a16_decode_attention"
+    H, KV, D, rot, ns = int(heads), int(kv_heads), int(head_dim), int(rot_dim), int(nsplit)
+    if min(H, KV, D, rot, ns) < 1:
+        raise ValueError(f"mobilequant_amd: {who} heads / kv_heads / head_dim / rot_dim / nsplit must be positive")
+    ops._raw(qkv, f"{who} qkv", torch.float32, (H + 2 * KV) * D)
+    ops._raw(k_cache, f"{who} k_cache", torch.float32)
+    if k_cache.numel() == 0 or k_cache.numel() % (KV * D):
+        raise RuntimeError(f"mobilequant_amd: {who} k_cache must hold [kv_heads = {KV}, cache_len, head_dim = {D}] (got {tuple(k_cache.shape)})")
+    T = k_cache.numel() // (KV * D)
+    ops._raw(v_cache, f"{who} v_cache", torch.float32, KV * T * D)
+    ops._raw(rope_row, f"{who} rope_row", torch.float32, 2 * rot)
+    ops._raw(pos, f"{who} pos", torch.int32, 1)
+    ops._raw(out, f"{who} out", torch.float32, H * D)
+    if ns > 1:
+        if part is None or ticket is None:
+            raise RuntimeError(f"mobilequant_amd: {who} nsplit = {ns} needs part (fp32 [heads, nsplit, head_dim + 4]) and ticket (int32 [heads], zeroed)")
+        ops._raw(part, f"{who} part", torch.float32, H * ns * (D + 4))
+        ops._raw(ticket, f"{who} ticket", torch.int32, H)
+    a = _lib.MqW4A16DecodeAttentionArgs()
+    a.qkv, a.k_cache, a.v_cache, a.rope_row, a.pos = qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), rope_row.data_ptr(), pos.data_ptr()
+    a.heads, a.kv_heads, a.head_dim, a.cache_len, a.rot_dim, a.nsplit = H, KV, D, T, rot, ns
+    a.part = part.data_ptr() if ns > 1 else None
+    a.ticket = ticket.data_ptr() if ns > 1 else None
+    a.out = out.data_ptr()
+    return a
+
+
+def w4a16_decode_attention(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, rope_row: torch.Tensor, pos: torch.Tensor,
+                           out: torch.Tensor, **kw) -> torch.Tensor:
+    """mq_w4a16_decode_attention: RoPE on q and the new k, the append of (k, v) at position pos[0] of the fp32 caches [kv_heads, cache_len,
+    head_dim] (one sequence of LlamaForCausalLM.new_cache) and the attention of the new token over positions 0 .. pos[0], into out
+    (fp32 [heads * head_dim]).  qkv fp32 [(heads + 2 kv_heads) * head_dim]; rope_row fp32 [2 rot_dim] = cos | sin of this position; pos
+    int32 [1] on the device.  nsplit > 1: part fp32 [heads, nsplit, head_dim + 4] and ticket int32 [heads] (zero).  A position outside
+    the cache does nothing.  Every tensor is passed as it is."""
+    a = w4a16_decode_attention_args(qkv, k_cache, v_cache, rope_row, pos, out, **kw)
+    with ops._on(qkv, k_cache, v_cache, rope_row, pos, out, kw.get("part"), kw.get("ticket")):
+        _lib.call("mq_w4a16_decode_attention", ctypes.byref(a), ops._stream())
+    return out
