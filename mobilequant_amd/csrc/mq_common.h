@@ -49,6 +49,44 @@ struct PerDeviceOnce {
     }                                                                                \
   } while (0)
 
+// CU count of the current device, read once per device (256 where the property cannot be read)
+inline int device_cus() {
+  static std::atomic<int> cus_of[kMaxDevices];      // 0 = not read yet
+  const int dev = current_device();
+  int cus = cus_of[dev].load(std::memory_order_relaxed);
+  if (!cus) {
+    hipDeviceProp_t prop;
+    cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    cus_of[dev].store(cus, std::memory_order_relaxed);
+  }
+  return cus;
+}
+// Launch geometry of the weight-streaming GEMVs, one fat workgroup per CU: `rows` spread over the device's CUs, at most max_rows_per_wg
+// per workgroup (16 waves x 64 row slots, whose per-row parameters live one per lane; the W4A8 decode kernels stream with 8 waves).
+inline void fat_row_geometry(int rows, int max_rows_per_wg, int* rows_per_wg, unsigned* grid) {
+  const int cus = device_cus();
+  int rpw = (rows + cus - 1) / cus;
+  if (rpw > max_rows_per_wg) rpw = max_rows_per_wg;
+  *rows_per_wg = rpw;
+  *grid = (unsigned)((rows + rpw - 1) / rpw);
+}
+
+// Raise a kernel's dynamic-LDS ceiling once per device, when a launch needs `lds` bytes above the 32 KiB every kernel may use as it
+// is.  The ceiling asked for is `lds` itself (the kernel is opted in size by size) or, where given, `ceiling`, the kernel's maximum:
+// one call then serves every later launch, so a larger launch inside a graph capture needs no attribute call.  cache: a slot per device.
+inline int set_lds(const void* fn, std::atomic<size_t>* cache, size_t lds, const char* name, size_t ceiling = 0) {
+  const int dev = current_device();
+  if (!ceiling) ceiling = lds;
+  if (lds > 32768 && cache[dev].load(std::memory_order_relaxed) < lds) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ceiling) != hipSuccess) {
+      set_error("%s: %zu bytes of dynamic LDS rejected", name, ceiling);
+      return MQ_EHIP;
+    }
+    cache[dev].store(ceiling, std::memory_order_relaxed);
+  }
+  return MQ_OK;
+}
+
 // x / s through the correctly rounded reciprocal inv_s = RN(1 / s) and one fma correction (Markstein): bit-identical to the IEEE
 // divide for |x / s| in [2^-2, 1e30] -- tools/div_check.cpp compares every fp32 dividend for 48 divisors on the GPU, incl. all-ones
 // significands and the scale clamps 1e-5 / 1e6 (profiles/r03/div_check.log) -- and faithful below 2^-2, where round(x / s) = 0 and
@@ -167,6 +205,31 @@ __device__ __forceinline__ T block_sum4(T v, T* slots, int wave) {
   if ((threadIdx.x & 63) == 0) slots[wave] = v;
   __syncthreads();
   return (slots[0] + slots[1]) + (slots[2] + slots[3]);
+}
+
+// Sum or maximum over ALL lanes of a WAVES-wave workgroup (4 or 16), for every thread, in a fixed order: the wave's own reduction, then
+// the wave totals through red[WAVES] met as ((0 + 1) + (2 + 3)) per four waves and the fours likewise.  Two barriers: the first because
+// the slots may still be read from the previous reduction.
+struct BlockSum {
+  static __device__ __forceinline__ float wave(float v) { return wave_sum_f_rowbcast(v); }
+  static __device__ __forceinline__ float two(float a, float b) { return a + b; }
+};
+struct BlockMax {                                                   // inputs are finite or -inf, never NaN
+  static __device__ __forceinline__ float wave(float v) { return wave_max_f(v); }
+  static __device__ __forceinline__ float two(float a, float b) { return fmaxf(a, b); }
+};
+template <int WAVES, class Op>
+__device__ __forceinline__ float block_reduce(float v, float* red, int wave, int lane) {
+  static_assert(WAVES == 4 || WAVES == 16, "four waves, or four fours");
+  v = Op::wave(v);
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  float t[WAVES / 4];
+#pragma unroll
+  for (int i = 0; i < WAVES / 4; ++i) t[i] = Op::two(Op::two(red[4 * i], red[4 * i + 1]), Op::two(red[4 * i + 2], red[4 * i + 3]));
+  if constexpr (WAVES == 4) return t[0];
+  else return Op::two(Op::two(t[0], t[1]), Op::two(t[2], t[3]));
 }
 
 // Exact float atomic min/max on the IEEE bit pattern (no CAS loop): non-negative floats order as

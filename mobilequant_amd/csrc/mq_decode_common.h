@@ -329,18 +329,7 @@ struct GemvBatchEpilogue {
 // rows per workgroup and grid: the NL logical rows (a gate launch's w1 | w3 pair is one) spread over the device's CUs, at most
 // DG_STR * 64 per workgroup
 inline int gemv_row_geometry(int NL, int* rows_per_wg, unsigned* grid) {
-  static std::atomic<int> cus_of[kMaxDevices];
-  const int dev = current_device();
-  int cus = cus_of[dev].load(std::memory_order_relaxed);
-  if (!cus) {
-    hipDeviceProp_t prop;
-    cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    cus_of[dev].store(cus, std::memory_order_relaxed);
-  }
-  int rpw = (NL + cus - 1) / cus;
-  if (rpw > DG_STR * 64) rpw = DG_STR * 64;
-  *rows_per_wg = rpw;
-  *grid = (unsigned)((NL + rpw - 1) / rpw);
+  fat_row_geometry(NL, DG_STR * 64, rows_per_wg, grid);
   return NL;
 }
 
@@ -397,14 +386,5 @@ inline int gemv_dispatch(const int xmode, const bool gate, const bool w4, Launch
 }
 // index of an instantiation in an entry's set_lds cache
 inline int gemv_kernel_index(const int xmode, const bool gate, const bool w4) { return (xmode * 2 + (gate ? 1 : 0)) * 2 + (w4 ? 1 : 0); }
-
-// raise a kernel's dynamic-LDS ceiling once per device (above the default 64 KiB)
-inline int set_lds(const void* fn, std::atomic<size_t>* cache, size_t lds, const char* name) {
-  if (lds > 32768 && cache[current_device()].load(std::memory_order_relaxed) < lds) {
-    MQ_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess, "%s: %zu bytes of dynamic LDS rejected", name, lds);
-    cache[current_device()].store(lds, std::memory_order_relaxed);
-  }
-  return MQ_OK;
-}
 
 }  // namespace mq

@@ -1062,19 +1062,6 @@ __global__ void __launch_bounds__(64 * Fr128<VAR>::NW) gemm_i8_fr128_kernel(cons
 // shapes the 128-column generated kernels serve (fragment-blocked activations, int8 weights)
 static bool gemm_fr128_shape(int64_t M, int64_t N, int64_t K) { return M > 0 && N % 128 == 0 && K % 256 == 0 && K >= 768; }
 
-static int device_cu_count() {
-  static std::atomic<int> cus[64];
-  const int dev = current_device();
-  if (dev < 0 || dev >= 64) return 0;
-  int c = cus[dev].load();
-  if (c == 0) {
-    hipDeviceProp_t prop;
-    c = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 1;
-    cus[dev] = c;
-  }
-  return c;
-}
-
 // Exchange area of the split-K residual GEMM: per device, grown on demand, never freed (128 tiles = 16.8 MB at M = 2048).  The flags
 // are zero between launches (every wave clears the flag it consumed).
 static int gemm_splitk_scratch(int tiles, char** xch, int** xfl) {
@@ -1784,7 +1771,7 @@ static int linear_tiled_residual(const char* fn, bool w4, const int8_t* a_tiled,
   // split-K on 256-row tiles (mq_gemm_set_residual_tile(512)): both halves of every tile resident at once (2 x tiles <= CUs), the two
   // workgroups of a tile on one XCD (tiles % 8 == 0), each half a valid K for the program (multiple of 256, >= 768)
   const int64_t tiles256 = ((M + 255) / 256) * (N / 128);
-  const bool can_split = K % 512 == 0 && K / 2 >= 768 && tiles256 % 8 == 0 && 2 * tiles256 <= (int64_t)device_cu_count();
+  const bool can_split = K % 512 == 0 && K / 2 >= 768 && tiles256 % 8 == 0 && 2 * tiles256 <= (int64_t)device_cus();
 #ifdef MQ_BUILD_EXPERIMENTS
   if (forced == 512 && can_split) return launch_fr128<FR128RS>(g, as_stream(stream));
 #else

@@ -17,10 +17,9 @@
 // and the activations are laid out in LDS in that same order (quad_slot), so neither side moves a byte to line the two up.
 // (1024 + u) - (1024 + z') is exact (integers below 2049), the multiply by s16 rounds once.
 //
-// M <= 8: weight-streaming GEMV, mq_gemv.hip's walk.  One 1024-thread workgroup per CU; a wave owns whole output rows (row0 + 16 t), its
-// lanes split K into 16-byte chunks (32 k; lane l takes chunks l, l + 64, ...), eight chunks with their group's s16 / z' are in flight
-// before the first wait.  x16 is staged once per workgroup ([M][K] fp16, unit order; the four 16-byte units of a chunk are rotated by
-// (c + (c >> 2)) & 3 so that 16 neighbouring lanes' ds_read_b128 cover all 64 banks).  fp32 fma per element, a DPP wave sum, one store.
+// M <= 8: weight-streaming GEMV.  The walk is mq_w4a16_stream.h's (w4_stream_walk, described there): here it runs over M <= MT row images of
+// x16, staged once per workgroup, with the packed 16-bit fetch of s16 / z' (scales and zeros 2-byte aligned: the entry's contract), and a
+// completed row gets its fp32 bias and one store per activation row.
 // M > 8 (and M <= 8 rows too long for the staging buffer): MFMA GEMM, 64 rows x 64 NT columns of outputs per 256-thread workgroup (NT = 2;
 // 1 when N <= 64), k in chunks of 128.  Wave w owns NT tiles of 16 weight rows (n0 + 16 NT w ..) and all 64 activation rows: its packed
 // weights go global -> registers (nobody else needs them), lane (n = lane & 15, kq = lane >> 4) holding the 16-byte group kq of the chunk
@@ -29,25 +28,19 @@
 // dword s}, kq = 0..3 -- a permutation of the chunk's k, the same on both operands.  x16 goes through a double-buffered LDS tile
 // [64][128] fp16 in unit order (row pitch 272 B), B fragment = one ds_read_b128.  With the weights as A the accumulator holds
 // out[m = lane & 15][n = 4 (lane >> 4) + reg]: four consecutive n per lane, one 16-byte (fp32) or 8-byte (fp16) store.
-#include "mq_w4a16_common.h"
+#include "mq_w4a16_stream.h"
 
 namespace mq {
 
 struct W4A16Args {
   const void* x;
   int x_f16;
-  int M, N, K, gs;
-  int lg_gs32;                    // group_size / 32 is a power of two: its log2, else -1 (a division per chunk)
-  const uint8_t* w;
-  const uint16_t* scales;
-  const uint16_t* zeros;
+  int M;
+  W4Image g;
   const float* bias;
   void* out;
   int out_f16;
 };
-
-// group of the 32-wide k block kb
-__device__ __forceinline__ int group_of(const W4A16Args& a, int kb) { return a.lg_gs32 >= 0 ? kb >> a.lg_gs32 : kb / (a.gs >> 5); }
 
 // Four consecutive activations x[k .. k + 3] (k % 4 == 0) as the two dwords of the unit order: (j0, j2) and (j1, j3).
 template <typename XT>
@@ -76,111 +69,41 @@ __global__ void __launch_bounds__(WV_THREADS) w4a16_gemv_kernel(const W4A16Args 
   constexpr int WV_INFLIGHT = MT == 8 ? 4 : 8;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int K = a.K, N = a.N, M = a.M;
-  const int kchunks = K >> 5;
-  const int wrow = K >> 1;
-  const int G = K / a.gs;
-  const int cpl = (kchunks + 63) >> 6;
+  const int K = a.g.K, N = a.g.N, M = a.M;
   const int row0 = blockIdx.x * rows_per_wg + wave;
   const int row_end = (blockIdx.x + 1) * rows_per_wg < N ? (blockIdx.x + 1) * rows_per_wg : N;
+  const int nslots = (row_end - row0 + WV_WAVES - 1) / WV_WAVES;  // (row_end - row0 > -WV_WAVES: a wave past the rows has none)
+  auto slot_row = [&](int t) { return row0 + WV_WAVES * t; };
+  float p_bias = 0.f;                                             // lane t keeps the bias of row slot t
 
-  // ---- the first pass of weight chunks and their groups' parameters go out first ----------------------------------------------------
-  v4i buf[WV_INFLIGHT];
-  unsigned bsz[WV_INFLIGHT];                                      // s16 | z' << 16 of the chunk's group
-  auto issue_pass = [&](int t, int j) {
+  w4_stream_walk<WV_INFLIGHT, false, MT>(
+      a.g, nslots, slot_row,
+      [&] {                                                       // behind the first requests: activations -> LDS as fp16, once per workgroup
+        if (a.bias && lane < nslots) p_bias = a.bias[slot_row(lane)];
+        const int qpr = K >> 2;                                   // quads per row
+        for (int i = threadIdx.x; i < M * qpr; i += WV_THREADS) {
+          const int m = i / qpr, kk = (i - m * qpr) << 2;
+          float v[4];
+          if (a.x_f16) load_quad<__half>(a.x, (size_t)m * K + kk, v);
+          else load_quad<float>(a.x, (size_t)m * K + kk, v);
+          stage_quad(smem + (size_t)m * K * 2, kk, v);
+        }
+        __syncthreads();
+      },
+      smem, M,
+      [&](int t, const float (&sums)[MT]) {                       // a completed row: bias, one store per activation row
+        const int row = slot_row(t);
+        const float bias = readlane_f(p_bias, t);
 #pragma unroll
-    for (int u = 0; u < WV_INFLIGHT; ++u) {
-      const int row = row0 + WV_WAVES * t;
-      const int c = lane + 64 * j;
-      if (row < row_end && c < kchunks) {
-        buf[u] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(a.w + (size_t)row * wrow) + c);
-        const size_t gi = (size_t)row * G + group_of(a, c);
-        bsz[u] = (unsigned)a.scales[gi] | ((unsigned)a.zeros[gi] << 16);
-      } else {
-        buf[u] = v4i{0, 0, 0, 0};
-        bsz[u] = 0;
-      }
-      if (++j == cpl) { j = 0; ++t; }
-    }
-  };
-  issue_pass(0, 0);
-  float p_bias = 0.f;
-  {
-    const int row = row0 + WV_WAVES * lane;                       // lane t keeps the bias of row slot t
-    if (a.bias && row < row_end) p_bias = a.bias[row];
-  }
-
-  // ---- activations -> LDS as fp16, once per workgroup ---------------------------------------------------------------------------------
-  {
-    const int qpr = K >> 2;                                       // quads per row
-    for (int i = threadIdx.x; i < M * qpr; i += WV_THREADS) {
-      const int m = i / qpr, kk = (i - m * qpr) << 2;
-      float v[4];
-      if (a.x_f16) load_quad<__half>(a.x, (size_t)m * K + kk, v);
-      else load_quad<float>(a.x, (size_t)m * K + kk, v);
-      const int c = kk >> 5, unit = (((kk & 15) >> 2) + unit_rot(c)) & 3;
-      char* dst = smem + (size_t)m * K * 2 + c * 64 + unit * 16 + quad_slot((kk >> 4) & 1);
-      *reinterpret_cast<unsigned*>(dst) = pack_h2(v[0], v[2]);
-      *reinterpret_cast<unsigned*>(dst + 8) = pack_h2(v[1], v[3]);
-    }
-  }
-  __syncthreads();
-  if (row0 >= row_end) return;
-
-  // ---- dequantize, fp32 fma, DPP reduction and store per completed row -----------------------------------------------------------------
-  const int nslots = (row_end - row0 + WV_WAVES - 1) / WV_WAVES;
-  float acc[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) acc[m] = 0.f;
-  int t = 0, j = 0;
-  while (t < nslots) {
-    int t2 = t, j2 = j;
-#pragma unroll
-    for (int u = 0; u < WV_INFLIGHT; ++u) {
-      if (t2 < nslots) {                                           // wave-uniform
-        int c = lane + 64 * j2;
-        c = c < kchunks ? c : kchunks - 1;                         // buf[u] and its scale are zero there
-        const h2 sz = splat_scale((uint16_t)(bsz[u] & 0xffff)), nz = splat_negzero((uint16_t)(bsz[u] >> 16));
-        const int rot = unit_rot(c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          h2 w[4];
-          dequant8((unsigned)buf[u][i], sz, nz, w);
-          const int uoff = c * 64 + (((i + rot) & 3) << 4);
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            if (m < M) {
-              const v8h xv = *reinterpret_cast<const v8h*>(smem + (size_t)m * K * 2 + uoff);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                acc[m] = __builtin_fmaf((float)w[e][0], (float)xv[2 * e], acc[m]);
-                acc[m] = __builtin_fmaf((float)w[e][1], (float)xv[2 * e + 1], acc[m]);
-              }
-            }
+        for (int m = 0; m < MT; ++m) {
+          if (m < M && lane == 0) {
+            const float f = __fadd_rn(sums[m], bias);
+            const size_t idx = (size_t)m * N + row;
+            if (a.out_f16) reinterpret_cast<__half*>(a.out)[idx] = __float2half_rn(f);
+            else reinterpret_cast<float*>(a.out)[idx] = f;
           }
         }
-        if (j2 == cpl - 1) {                                       // row slot t2 complete
-          const int row = row0 + WV_WAVES * t2;
-          const float bias = readlane_f(p_bias, t2);
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            const float sum = wave_sum_f_rowbcast(acc[m]);
-            acc[m] = 0.f;
-            if (m < M && lane == 0) {
-              const float f = __fadd_rn(sum, bias);
-              const size_t idx = (size_t)m * N + row;
-              if (a.out_f16) reinterpret_cast<__half*>(a.out)[idx] = __float2half_rn(f);
-              else reinterpret_cast<float*>(a.out)[idx] = f;
-            }
-          }
-        }
-        if (++j2 == cpl) { j2 = 0; ++t2; }
-      }
-    }
-    t = t2;
-    j = j2;
-    if (t < nslots) issue_pass(t, j);
-  }
+      });
 }
 
 // ---- M > 8 --------------------------------------------------------------------------------------------------------------------------
@@ -192,13 +115,13 @@ __global__ void __launch_bounds__(GM_THREADS) w4a16_gemm_kernel(const W4A16Args 
   __shared__ __attribute__((aligned(16))) char s_x[2][GM_BM * GM_PITCH];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int M = a.M, N = a.N, K = a.K;
+  const int M = a.M, N = a.g.N, K = a.g.K;
   const int m0 = blockIdx.x * GM_BM;
   const int n0 = blockIdx.y * (GM_BN * NT) + 16 * NT * wave;      // tile t of this wave: rows n0 + 16 t .. + 15
   const int ntiles = n0 >= N ? 0 : (N - n0) / 16 < NT ? (N - n0) / 16 : NT;   // wave-uniform (N % 16 == 0: a tile is all inside or all outside)
   const bool active = ntiles > 0;
   const int ln = lane & 15, kq = lane >> 4;
-  const int G = K / a.gs;
+  const int G = K / a.g.gs;
   const int nchunks = (K + GM_BK - 1) / GM_BK;
 
   // staging: thread t owns quad qi = t & 31 (k = 4 qi of the chunk) of rows (t >> 5) + 8 i
@@ -233,9 +156,9 @@ __global__ void __launch_bounds__(GM_THREADS) w4a16_gemm_kernel(const W4A16Args 
     for (int t = 0; t < NT; ++t) {
       if (t < ntiles && kb * 32 < K) {
         const int n = n0 + 16 * t + ln;
-        q[t] = *(reinterpret_cast<const v4i*>(a.w + (size_t)n * (K >> 1)) + kb);
-        const size_t gi = (size_t)n * G + group_of(a, kb);
-        sz[t] = (unsigned)a.scales[gi] | ((unsigned)a.zeros[gi] << 16);
+        q[t] = *(reinterpret_cast<const v4i*>(a.g.w + (size_t)n * (K >> 1)) + kb);
+        const size_t gi = (size_t)n * G + a.g.group_of(kb);
+        sz[t] = (unsigned)a.g.scales[gi] | ((unsigned)a.g.zeros[gi] << 16);
       } else {
         q[t] = v4i{0, 0, 0, 0};
         sz[t] = 0;
@@ -361,43 +284,22 @@ extern "C" int mq_w4a16_linear(const mq_w4a16_args* p, mq_stream_t stream) {
   a.x = p->x;
   a.x_f16 = p->x_dtype == MQ_F16;
   a.M = (int)p->M;
-  a.N = (int)p->N;
-  a.K = (int)p->K;
-  a.gs = (int)p->group_size;
-  const int g32 = a.gs >> 5;
-  a.lg_gs32 = (g32 & (g32 - 1)) == 0 ? __builtin_ctz(g32) : -1;
-  a.w = p->w_packed;
-  a.scales = static_cast<const uint16_t*>(p->scales);
-  a.zeros = static_cast<const uint16_t*>(p->zeros);
+  a.g = w4_image(p->w_packed, p->scales, p->zeros, p->N, p->K, p->group_size);
   a.bias = p->bias;
   a.out = p->out;
   a.out_f16 = p->out_dtype == MQ_F16;
   hipStream_t st = as_stream(stream);
   if (variant == 1) {
     // one fat workgroup per CU; a wave keeps at most 64 row slots (their bias lives one per lane)
-    static std::atomic<int> cus_of[kMaxDevices];
-    const int dev = current_device();
-    int cus = cus_of[dev].load(std::memory_order_relaxed);
-    if (!cus) {
-      hipDeviceProp_t prop;
-      cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-      cus_of[dev].store(cus, std::memory_order_relaxed);
-    }
-    int rows_per_wg = (a.N + cus - 1) / cus;
-    if (rows_per_wg > WV_WAVES * 64) rows_per_wg = WV_WAVES * 64;
-    const unsigned grid = (unsigned)((a.N + rows_per_wg - 1) / rows_per_wg);
-    const size_t lds = (size_t)a.M * a.K * 2;
+    int rows_per_wg;
+    unsigned grid;
+    fat_row_geometry(a.g.N, WV_WAVES * 64, &rows_per_wg, &grid);
+    const size_t lds = (size_t)a.M * a.g.K * 2;
     static std::atomic<size_t> lds_set[4][kMaxDevices];
     const int ki = a.M == 1 ? 0 : a.M == 2 ? 1 : a.M <= 4 ? 2 : 3;
     const void* fn = ki == 0 ? (const void*)w4a16_gemv_kernel<1> : ki == 1 ? (const void*)w4a16_gemv_kernel<2>
                    : ki == 2 ? (const void*)w4a16_gemv_kernel<4> : (const void*)w4a16_gemv_kernel<8>;
-    if (lds > 32768 && lds_set[ki][dev].load(std::memory_order_relaxed) < lds) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WV_MAX_LDS) != hipSuccess) {
-        set_error("mq_w4a16_linear: %zu bytes of dynamic LDS rejected", WV_MAX_LDS);
-        return MQ_EHIP;
-      }
-      lds_set[ki][dev].store(WV_MAX_LDS, std::memory_order_relaxed);
-    }
+    if (const int rc = set_lds(fn, lds_set[ki], lds, "mq_w4a16_linear", WV_MAX_LDS)) return rc;
     switch (ki) {
       case 0: w4a16_gemv_kernel<1><<<grid, WV_THREADS, lds, st>>>(a, rows_per_wg); break;
       case 1: w4a16_gemv_kernel<2><<<grid, WV_THREADS, lds, st>>>(a, rows_per_wg); break;
@@ -408,8 +310,8 @@ extern "C" int mq_w4a16_linear(const mq_w4a16_args* p, mq_stream_t stream) {
     return MQ_OK;
   }
   // 64 x 128 outputs per workgroup (two weight tiles per wave) once N has more than one 64-column block, 64 x 64 below
-  const int nt = a.N > GM_BN ? 2 : 1;
-  const dim3 grid((unsigned)((a.M + GM_BM - 1) / GM_BM), (unsigned)((a.N + GM_BN * nt - 1) / (GM_BN * nt)));
+  const int nt = a.g.N > GM_BN ? 2 : 1;
+  const dim3 grid((unsigned)((a.M + GM_BM - 1) / GM_BM), (unsigned)((a.g.N + GM_BN * nt - 1) / (GM_BN * nt)));
   if (nt == 2) {
     if (a.x_f16) w4a16_gemm_kernel<__half, 2><<<grid, GM_THREADS, 0, st>>>(a);
     else w4a16_gemm_kernel<float, 2><<<grid, GM_THREADS, 0, st>>>(a);

@@ -1,9 +1,7 @@
 // The two launches a weight-only (W4A16) model's decode step is made of (the engine: decode_weight_only.py).
 //
-// mq_w4a16_decode_gemv: w4a16_gemv_kernel<1>'s weight stream (mq_w4a16.hip) between a prologue and an epilogue chosen per launch.  The
-// walk is that kernel's: one 1024-thread workgroup per CU, a wave owns whole rows, its lanes split K into 16-byte chunks, eight chunks
-// with their group's s16 / z' are in flight before the first wait, x16 sits in LDS in unit order with the bank rotation, the dequantize
-// is the packed-fp16 one, products are accumulated by v_fma_mix_f32 and a row ends in the DPP wave sum.
+// mq_w4a16_decode_gemv: mq_w4a16_stream.h's weight-stream walk (w4_stream_walk, described there) over ONE row image, with the whole-dword
+// fetch of s16 / z' (scales and zeros 4-byte aligned: this entry's contract), between a prologue and an epilogue chosen per launch.
 //   prologue: the fp16 image of the row is formed from fp32 x -- as it is, behind HFRMSNorm or behind nn.LayerNorm; every workgroup
 //             recomputes the norm's statistics (x is one row: K floats out of L2), in the expressions of decode_head_kernel (mq_decode.hip)
 //   epilogue: + bias; resid + (sum + bias); or, on an image whose rows interleave the gate and the up linear, act(a_n) * b_n -- a wave
@@ -15,17 +13,13 @@
 //   every workgroup ropes the new k itself, and workgroup (first head of the kv group, split 0) writes it.  nsplit > 1: (max, sum,
 //   partial out) records, an integer ticket per head, the last arrival combines them in split order -- mq_decode_attention.h's protocol
 //   (write-through record stores, drained by every wave; agent-scope release on the ticket, agent-scope acquire in the last arrival).
-#include "mq_w4a16_common.h"
+#include "mq_w4a16_stream.h"
 
 namespace mq {
 
 struct W4DecArgs {
   const float* x;
-  int N, K, gs;
-  int lg_gs32;                    // group_size / 32 is a power of two: its log2, else -1 (a division per chunk)
-  const uint8_t* w;
-  const uint16_t* scales;
-  const uint16_t* zeros;
+  W4Image g;
   int prologue;
   const float* norm_w;
   const float* norm_b;
@@ -41,23 +35,78 @@ constexpr int WD_RED_BYTES = 64;                                   // 16 wave to
 constexpr int WD_MAX_K = 32768;
 constexpr size_t WD_MAX_LDS = (size_t)WD_MAX_K * 2 + WD_RED_BYTES;
 
-__device__ __forceinline__ int wd_group_of(const W4DecArgs& a, int kb) { return a.lg_gs32 >= 0 ? kb >> a.lg_gs32 : kb / (a.gs >> 5); }
-
-// sum of the 16 waves' (wave-uniform) values, for every thread, in wave order pairs: ((0 + 1) + (2 + 3)) + ... ; two barriers
-__device__ __forceinline__ float wd_block_sum(float v, float* red, int wave, int lane) {
-  v = wave_sum_f_rowbcast(v);
-  __syncthreads();                                                 // (the slots may still be read from the previous sum)
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float t[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) t[i] = (red[4 * i] + red[4 * i + 1]) + (red[4 * i + 2] + red[4 * i + 3]);
-  return (t[0] + t[1]) + (t[2] + t[3]);
-}
-
 __device__ __forceinline__ float wd_act(float a, int act) {
   if (act == 0) return __fdiv_rn(a, __fadd_rn(1.0f, expf(-a)));                               // SiLU
   return __fmul_rn(__fmul_rn(a, 0.5f), __fadd_rn(1.0f, erff(__fmul_rn(a, 0.70710678118654752440f))));   // GELU, erf form
+}
+
+// The prologue: x -> the row image in LDS as fp16 ([K], unit order, 16 floats of reduction slots behind it), plain or behind a norm whose
+// statistics every workgroup recomputes.  Every thread of the workgroup calls it; the caller's barrier completes the image.
+__device__ __forceinline__ void wd_stage_row(const W4DecArgs& a, char* smem, const int wave, const int lane) {
+  const int K = a.g.K;
+  float* red = reinterpret_cast<float*>(smem + (size_t)K * 2);
+  const int quads = K >> 2;
+  float r = 1.f, sh = 0.f;
+  if (a.prologue == MQ_W4A16_PRO_RMSNORM) {
+    float ss = 0.f;
+    for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
+      const float4 f = reinterpret_cast<const float4*>(a.x)[i];
+      ss += f.x * f.x;
+      ss += f.y * f.y;
+      ss += f.z * f.z;
+      ss += f.w * f.w;
+    }
+    const float mean = __fdiv_rn(block_reduce<WD_WAVES, BlockSum>(ss, red, wave, lane), (float)K);
+    r = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(mean, a.eps)));
+  } else if (a.prologue == MQ_W4A16_PRO_LAYERNORM) {
+    float s1 = 0.f;
+    for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
+      const float4 f = reinterpret_cast<const float4*>(a.x)[i];
+      s1 += (f.x + f.y) + (f.z + f.w);
+    }
+    const float mu = __fdiv_rn(block_reduce<WD_WAVES, BlockSum>(s1, red, wave, lane), (float)K);
+    float s2 = 0.f;
+    for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
+      const float4 f = reinterpret_cast<const float4*>(a.x)[i];
+      const float d0 = f.x - mu, d1 = f.y - mu, d2 = f.z - mu, d3 = f.w - mu;
+      s2 += d0 * d0;
+      s2 += d1 * d1;
+      s2 += d2 * d2;
+      s2 += d3 * d3;
+    }
+    const float var = __fdiv_rn(block_reduce<WD_WAVES, BlockSum>(s2, red, wave, lane), (float)K);
+    r = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, a.eps)));
+    sh = __fmul_rn(-r, mu);
+  }
+  for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
+    const float4 f = reinterpret_cast<const float4*>(a.x)[i];
+    float v[4] = {f.x, f.y, f.z, f.w};
+    if (a.prologue != MQ_W4A16_PRO_PLAIN) {
+      float w[4] = {1.f, 1.f, 1.f, 1.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+      if (a.norm_w) {
+        const float4 t = reinterpret_cast<const float4*>(a.norm_w)[i];
+        w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+      }
+      if (a.norm_b) {
+        const float4 t = reinterpret_cast<const float4*>(a.norm_b)[i];
+        b[0] = t.x; b[1] = t.y; b[2] = t.z; b[3] = t.w;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float y;
+        if (a.prologue == MQ_W4A16_PRO_RMSNORM) {
+          y = __fmul_rn(v[e], r);                                // x * rsqrt(mean + eps), then weight * y
+          if (a.norm_w) y = __fmul_rn(w[e], y);
+        } else {
+          y = __fadd_rn(__fmul_rn(v[e], r), sh);                 // (x - mu) * r as x r - r mu, then * weight
+          if (a.norm_w) y = __fmul_rn(y, w[e]);
+        }
+        if (a.norm_b) y = __fadd_rn(y, b[e]);
+        v[e] = y;
+      }
+    }
+    stage_quad(smem, i << 2, v);
+  }
 }
 
 template <bool GATED>
@@ -65,11 +114,7 @@ __global__ void __launch_bounds__(WD_THREADS) w4a16_decode_gemv_kernel(const W4D
   extern __shared__ __attribute__((aligned(16))) char smem[];     // [K] fp16, unit order | 16 floats
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int K = a.K, N = a.N;
-  const int kchunks = K >> 5;
-  const int wrow = K >> 1;
-  const int G = K / a.gs;
-  const int cpl = (kchunks + 63) >> 6;
+  const int N = a.g.N;
   const int base = blockIdx.x * rows_per_wg;
   const int row_end = base + rows_per_wg < N ? base + rows_per_wg : N;
   // row of this wave's slot t: plain -- base + wave + 16 t; gated -- the two rows of pair wave + 16 (t >> 1) (rows_per_wg is even)
@@ -77,162 +122,41 @@ __global__ void __launch_bounds__(WD_THREADS) w4a16_decode_gemv_kernel(const W4D
   const int nslots = GATED ? (((row_end - base) >> 1) > wave ? 2 * ((((row_end - base) >> 1) - wave + WD_WAVES - 1) / WD_WAVES) : 0)
                            : (row_end - base > wave ? (row_end - base - wave + WD_WAVES - 1) / WD_WAVES : 0);
 
-  // ---- the first pass of weight chunks and their groups' parameters go out first ----------------------------------------------------
-  constexpr int INFLIGHT = 8;
-  v4i buf[INFLIGHT];
-  // the dwords that hold s16 and z' of the chunk's group (scales / zeros are 4-byte aligned and N G is even): whole-dword loads whose
-  // halves are picked at use -- a 16-bit load, or packing the two here, makes hipcc wait for the chunk in front of the next request
-  typedef unsigned v2u __attribute__((ext_vector_type(2)));
-  v2u bsz[INFLIGHT];                                              // (scale dword, zero dword)
-  const unsigned* s32 = reinterpret_cast<const unsigned*>(a.scales);
-  const unsigned* z32 = reinterpret_cast<const unsigned*>(a.zeros);
-  auto issue_pass = [&](int t, int j) {
-#pragma unroll
-    for (int u = 0; u < INFLIGHT; ++u) {
-      const int row = slot_row(t);
-      const int c = lane + 64 * j;
-      if (t < nslots && c < kchunks) {
-        buf[u] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(a.w + (size_t)row * wrow) + c);
-        const size_t gi = (size_t)row * G + wd_group_of(a, c);
-        bsz[u] = v2u{s32[gi >> 1], z32[gi >> 1]};
-      } else {
-        buf[u] = v4i{0, 0, 0, 0};
-        bsz[u] = v2u{0, 0};
-      }
-      if (++j == cpl) { j = 0; ++t; }
-    }
-  };
-  issue_pass(0, 0);
   float p_bias = 0.f, p_resid = 0.f;                              // lane t keeps the bias and the residual of row slot t
-  if constexpr (!GATED) {
-    if (lane < nslots) {
-      const int row = slot_row(lane);
-      if (a.bias) p_bias = a.bias[row];
-      if (a.resid) p_resid = a.resid[row];
-    }
-  }
+  float held = 0.f;                                               // gated: a_n while b_n streams
 
-  // ---- prologue: x -> LDS as fp16, once per workgroup ----------------------------------------------------------------------------------
-  {
-    float* red = reinterpret_cast<float*>(smem + (size_t)K * 2);
-    const int quads = K >> 2;
-    float r = 1.f, sh = 0.f;
-    if (a.prologue == MQ_W4A16_PRO_RMSNORM) {
-      float ss = 0.f;
-      for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
-        const float4 f = reinterpret_cast<const float4*>(a.x)[i];
-        ss += f.x * f.x;
-        ss += f.y * f.y;
-        ss += f.z * f.z;
-        ss += f.w * f.w;
-      }
-      const float mean = __fdiv_rn(wd_block_sum(ss, red, wave, lane), (float)K);
-      r = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(mean, a.eps)));
-    } else if (a.prologue == MQ_W4A16_PRO_LAYERNORM) {
-      float s1 = 0.f;
-      for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
-        const float4 f = reinterpret_cast<const float4*>(a.x)[i];
-        s1 += (f.x + f.y) + (f.z + f.w);
-      }
-      const float mu = __fdiv_rn(wd_block_sum(s1, red, wave, lane), (float)K);
-      float s2 = 0.f;
-      for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
-        const float4 f = reinterpret_cast<const float4*>(a.x)[i];
-        const float d0 = f.x - mu, d1 = f.y - mu, d2 = f.z - mu, d3 = f.w - mu;
-        s2 += d0 * d0;
-        s2 += d1 * d1;
-        s2 += d2 * d2;
-        s2 += d3 * d3;
-      }
-      const float var = __fdiv_rn(wd_block_sum(s2, red, wave, lane), (float)K);
-      r = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, a.eps)));
-      sh = __fmul_rn(-r, mu);
-    }
-    for (int i = threadIdx.x; i < quads; i += WD_THREADS) {
-      const float4 f = reinterpret_cast<const float4*>(a.x)[i];
-      float v[4] = {f.x, f.y, f.z, f.w};
-      if (a.prologue != MQ_W4A16_PRO_PLAIN) {
-        float w[4] = {1.f, 1.f, 1.f, 1.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
-        if (a.norm_w) {
-          const float4 t = reinterpret_cast<const float4*>(a.norm_w)[i];
-          w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
-        }
-        if (a.norm_b) {
-          const float4 t = reinterpret_cast<const float4*>(a.norm_b)[i];
-          b[0] = t.x; b[1] = t.y; b[2] = t.z; b[3] = t.w;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float y;
-          if (a.prologue == MQ_W4A16_PRO_RMSNORM) {
-            y = __fmul_rn(v[e], r);                                // x * rsqrt(mean + eps), then weight * y
-            if (a.norm_w) y = __fmul_rn(w[e], y);
-          } else {
-            y = __fadd_rn(__fmul_rn(v[e], r), sh);                 // (x - mu) * r as x r - r mu, then * weight
-            if (a.norm_w) y = __fmul_rn(y, w[e]);
-          }
-          if (a.norm_b) y = __fadd_rn(y, b[e]);
-          v[e] = y;
-        }
-      }
-      char* dst = smem + gemv_quad_offset(i << 2);
-      *reinterpret_cast<unsigned*>(dst) = pack_h2(v[0], v[2]);
-      *reinterpret_cast<unsigned*>(dst + 8) = pack_h2(v[1], v[3]);
-    }
-  }
-  __syncthreads();
-  if (nslots == 0) return;
-
-  // ---- dequantize, fp32 fma, DPP reduction and the epilogue per completed row ----------------------------------------------------------
-  float acc = 0.f, held = 0.f;
-  int t = 0, j = 0;
-  while (t < nslots) {
-    int t2 = t, j2 = j;
-#pragma unroll
-    for (int u = 0; u < INFLIGHT; ++u) {
-      if (t2 < nslots) {                                           // wave-uniform
-        int c = lane + 64 * j2;
-        c = c < kchunks ? c : kchunks - 1;                         // buf[u] and its scale are zero there
-        const int half = 16 * ((slot_row(t2) * G + wd_group_of(a, c)) & 1);          // which half of the two dwords (zero dwords past the end)
-        const h2 sz = splat_scale((uint16_t)(bsz[u][0] >> half)), nz = splat_negzero((uint16_t)(bsz[u][1] >> half));
-        const int rot = unit_rot(c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          h2 w[4];
-          dequant8((unsigned)buf[u][i], sz, nz, w);
-          const v8h xv = *reinterpret_cast<const v8h*>(smem + c * 64 + (((i + rot) & 3) << 4));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            acc = __builtin_fmaf((float)w[e][0], (float)xv[2 * e], acc);
-            acc = __builtin_fmaf((float)w[e][1], (float)xv[2 * e + 1], acc);
+  w4_stream_walk<8, true, 1>(
+      a.g, nslots, slot_row,
+      [&] {                                                       // behind the first requests: per-row parameters, the row image
+        if constexpr (!GATED) {
+          if (lane < nslots) {
+            const int row = slot_row(lane);
+            if (a.bias) p_bias = a.bias[row];
+            if (a.resid) p_resid = a.resid[row];
           }
         }
-        if (j2 == cpl - 1) {                                       // row slot t2 complete
-          const int row = slot_row(t2);
-          const float sum = wave_sum_f_rowbcast(acc);
-          acc = 0.f;
-          if constexpr (GATED) {
-            if (!(t2 & 1)) {
-              held = sum;                                          // a_n; b_n is the next slot
-            } else if (lane == 0) {
-              a.out[row >> 1] = __fmul_rn(wd_act(held, a.act), sum);
-            }
-          } else {
-            const float bias = readlane_f(p_bias, t2), resid = readlane_f(p_resid, t2);
-            if (lane == 0) {
-              float f = __fadd_rn(sum, bias);
-              if (a.resid) f = __fadd_rn(resid, f);
-              a.out[row] = f;
-            }
+        wd_stage_row(a, smem, wave, lane);
+        __syncthreads();
+      },
+      smem, 1,
+      [&](int t, const float (&sums)[1]) {                        // a completed row: the epilogue
+        const int row = slot_row(t);
+        const float sum = sums[0];
+        if constexpr (GATED) {
+          if (!(t & 1)) {
+            held = sum;                                            // a_n; b_n is the next slot
+          } else if (lane == 0) {
+            a.out[row >> 1] = __fmul_rn(wd_act(held, a.act), sum);
+          }
+        } else {
+          const float bias = readlane_f(p_bias, t), resid = readlane_f(p_resid, t);
+          if (lane == 0) {
+            float f = __fadd_rn(sum, bias);
+            if (a.resid) f = __fadd_rn(resid, f);
+            a.out[row] = f;
           }
         }
-        if (++j2 == cpl) { j2 = 0; ++t2; }
-      }
-    }
-    t = t2;
-    j = j2;
-    if (t < nslots) issue_pass(t, j);
-  }
+      });
 }
 
 static const char* wd_rule(int64_t N, int64_t K, int64_t gs, int epilogue) {
@@ -262,21 +186,6 @@ struct W4AttnArgs {
 constexpr int WA_THREADS = 256;
 constexpr int WA_MAX_CHUNK = 8192;
 constexpr int WA_REC_PAD = 4;                                      // a record: {max, sum, -, -, out[D]}
-
-__device__ __forceinline__ float wa_block_max(float v, float* red, int wave, int lane) {
-  v = wave_max_f(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float wa_block_sum(float v, float* red, int wave, int lane) {
-  v = wave_sum_f_rowbcast(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // x[d] of a head roped with this position's row (cos | sin, rot each): two rounded products, one rounded add
 __device__ __forceinline__ float wa_rope(const float* x, int d, const float* rope_row, int rot) {
@@ -351,7 +260,7 @@ __global__ void __launch_bounds__(WA_THREADS) w4a16_decode_attention_kernel(cons
       }
     }
   }
-  mx = wa_block_max(mx, s_red, wave, lane);                        // -inf for an empty split (barriers inside: s_sc is written)
+  mx = block_reduce<WA_THREADS / 64, BlockMax>(mx, s_red, wave, lane);   // -inf for an empty split (barriers inside: s_sc is written)
 
   // ---- probabilities -----------------------------------------------------------------------------------------------------------------
   float ps = 0.f;
@@ -360,7 +269,7 @@ __global__ void __launch_bounds__(WA_THREADS) w4a16_decode_attention_kernel(cons
     s_sc[i] = e;
     ps += e;
   }
-  ps = wa_block_sum(ps, s_red, wave, lane);
+  ps = block_reduce<WA_THREADS / 64, BlockSum>(ps, s_red, wave, lane);
 
   // ---- p . v -------------------------------------------------------------------------------------------------------------------------
   const float4 vn4 = reinterpret_cast<const float4*>(s_v)[li];
@@ -469,14 +378,7 @@ extern "C" int mq_w4a16_decode_gemv(const mq_w4a16_decode_gemv_args* p, mq_strea
   }
   W4DecArgs a;
   a.x = p->x;
-  a.N = (int)p->N;
-  a.K = (int)p->K;
-  a.gs = (int)p->group_size;
-  const int g32 = a.gs >> 5;
-  a.lg_gs32 = (g32 & (g32 - 1)) == 0 ? __builtin_ctz(g32) : -1;
-  a.w = p->w_packed;
-  a.scales = static_cast<const uint16_t*>(p->scales);
-  a.zeros = static_cast<const uint16_t*>(p->zeros);
+  a.g = w4_image(p->w_packed, p->scales, p->zeros, p->N, p->K, p->group_size);
   a.prologue = p->prologue;
   a.norm_w = p->norm_weight;
   a.norm_b = p->norm_bias;
@@ -487,28 +389,17 @@ extern "C" int mq_w4a16_decode_gemv(const mq_w4a16_decode_gemv_args* p, mq_strea
   a.out = p->out;
   const bool gated = p->epilogue == MQ_W4A16_EPI_GATED;
   // one fat workgroup per CU; a wave keeps at most 64 row slots (their bias and residual live one per lane); gated: whole pairs
-  static std::atomic<int> cus_of[kMaxDevices];
-  const int dev = current_device();
-  int cus = cus_of[dev].load(std::memory_order_relaxed);
-  if (!cus) {
-    hipDeviceProp_t prop;
-    cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    cus_of[dev].store(cus, std::memory_order_relaxed);
+  int rows_per_wg;
+  unsigned grid;
+  fat_row_geometry(a.g.N, WD_WAVES * 64, &rows_per_wg, &grid);
+  if (gated && (rows_per_wg & 1)) {                                // (the cap is even: rounding up stays below it)
+    ++rows_per_wg;
+    grid = (unsigned)((a.g.N + rows_per_wg - 1) / rows_per_wg);
   }
-  int rows_per_wg = (a.N + cus - 1) / cus;
-  if (gated) rows_per_wg += rows_per_wg & 1;
-  if (rows_per_wg > WD_WAVES * 64) rows_per_wg = WD_WAVES * 64;
-  const unsigned grid = (unsigned)((a.N + rows_per_wg - 1) / rows_per_wg);
-  const size_t lds = (size_t)a.K * 2 + WD_RED_BYTES;
+  const size_t lds = (size_t)a.g.K * 2 + WD_RED_BYTES;
   static std::atomic<size_t> lds_set[2][kMaxDevices];
   const void* fn = gated ? (const void*)w4a16_decode_gemv_kernel<true> : (const void*)w4a16_decode_gemv_kernel<false>;
-  if (lds > 32768 && lds_set[gated][dev].load(std::memory_order_relaxed) < lds) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WD_MAX_LDS) != hipSuccess) {
-      set_error("mq_w4a16_decode_gemv: %zu bytes of dynamic LDS rejected", WD_MAX_LDS);
-      return MQ_EHIP;
-    }
-    lds_set[gated][dev].store(WD_MAX_LDS, std::memory_order_relaxed);
-  }
+  if (const int rc = set_lds(fn, lds_set[gated], lds, "mq_w4a16_decode_gemv", WD_MAX_LDS)) return rc;
   hipStream_t st = as_stream(stream);
   if (gated) w4a16_decode_gemv_kernel<true><<<grid, WD_THREADS, lds, st>>>(a, rows_per_wg);
   else w4a16_decode_gemv_kernel<false><<<grid, WD_THREADS, lds, st>>>(a, rows_per_wg);
@@ -558,14 +449,7 @@ extern "C" int mq_w4a16_decode_attention(const mq_w4a16_decode_attention_args* p
   const size_t lds = ((size_t)3 * a.D + 16 + 1024 + a.max_chunk) * sizeof(float);
   constexpr size_t max_lds = ((size_t)3 * 256 + 16 + 1024 + WA_MAX_CHUNK) * sizeof(float);
   static std::atomic<size_t> lds_set[kMaxDevices];
-  const int dev = current_device();
-  if (lds > 32768 && lds_set[dev].load(std::memory_order_relaxed) < lds) {
-    if (hipFuncSetAttribute((const void*)w4a16_decode_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) != hipSuccess) {
-      set_error("mq_w4a16_decode_attention: %zu bytes of dynamic LDS rejected", max_lds);
-      return MQ_EHIP;
-    }
-    lds_set[dev].store(max_lds, std::memory_order_relaxed);
-  }
+  if (const int rc = set_lds((const void*)w4a16_decode_attention_kernel, lds_set, lds, "mq_w4a16_decode_attention", max_lds)) return rc;
   w4a16_decode_attention_kernel<<<dim3((unsigned)a.H, (unsigned)a.nsplit), WA_THREADS, lds, as_stream(stream)>>>(a);
   MQ_LAUNCH_CHECK("mq_w4a16_decode_attention");
   return MQ_OK;

@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, weight_only
+from .decode import _eos_set
 from .llama import LlamaForCausalLM
 from .quantization import qmodule as Q
 from .quantization.fp_ops import FMatMul, HFRMSNorm
@@ -326,7 +327,7 @@ class WeightOnlyDecodeEngine:
             raise ValueError(f"WeightOnlyDecodeEngine.generate: {len(ids)} context tokens + {max_new_tokens} new ones need 1 .. {self.cache_len} positions")
         if sampling is not None:
             self.set_sampling(sampling, stream)
-        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        eos = _eos_set(eos_token_id)
         self._start_sequence(ids)
         out = list(ids)
         for made in range(1, max_new_tokens + 1):

@@ -74,9 +74,11 @@ def exact_weights(rng, N, K, g):
 
 
 def gemv_shapes(cus):
-    """N x K of 16 x 64, 48 x 128, 256 x 128, 128 x 256 at g 32, 64 and K; more rows than waves in a workgroup; two chunk passes per row."""
+    """N x K of 16 x 64, 48 x 128, 256 x 128, 128 x 256 at g 32, 64 and K; more rows than waves in a workgroup; two chunk passes per row;
+    group sizes with g / 32 = 3 and 6, the division arm of the group lookup: 2 groups per row, and 3 -- odd, so the half of the scale
+    dword a chunk's s16 sits in alternates with the row."""
     out = [(N, K, g) for N, K in ((16, 64), (48, 128), (256, 128), (128, 256)) for g in sorted({32, 64, K})]
-    return out + [(16 * cus + 32, 64, 32), (32, 2112, 64)]
+    return out + [(16 * cus + 32, 64, 32), (32, 2112, 64), (48, 192, 96), (32, 576, 192)]
 
 
 def gated_bound(a64, b64, kind):

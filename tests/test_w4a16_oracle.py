@@ -1,6 +1,7 @@
 """Host side of the W4A16 launch-branch pin (no GPU): tests/w4a16_cases.py against the source it mirrors and the oracle it trusts.
 
-- the launch constants of the case table are the ones in csrc/mq_w4a16.hip (read out of the source);
+- the launch constants of the case table are the ones in csrc/mq_w4a16.hip, csrc/mq_w4a16_stream.h (the walk) and csrc/mq_common.h (the
+  launch geometry and the LDS opt-in), read out of the source;
 - at 64, 256 and 304 CUs every case reaches the branch it is in the table for, said by plan(), and the table as a whole reaches every
   branch class of both kernels;
 - plan().variant is mq_w4a16_supported, for the table and around both sides of the GEMV / GEMM seam;
@@ -21,13 +22,16 @@ import w4a16_cases as C  # noqa: E402
 import w4a16_ref as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = open(os.path.join(ROOT, "mobilequant_amd", "csrc", "mq_w4a16.hip")).read()
+CSRC = os.path.join(ROOT, "mobilequant_amd", "csrc")
+SRC = open(os.path.join(CSRC, "mq_w4a16.hip")).read()
+STREAM = open(os.path.join(CSRC, "mq_w4a16_stream.h")).read()         # the weight-stream walk both W4A16 GEMVs run
+COMMON = open(os.path.join(CSRC, "mq_common.h")).read()               # the launch geometry and the LDS opt-in every fat GEMV shares
 F16, F32, F64 = np.float16, np.float32, np.float64
 
 
-def _one(pattern):
-    m = re.findall(pattern, SRC)
-    assert len(m) == 1, "%r: %d matches in mq_w4a16.hip" % (pattern, len(m))
+def _one(pattern, text=None, where="mq_w4a16.hip"):
+    m = re.findall(pattern, SRC if text is None else text)
+    assert len(m) == 1, "%r: %d matches in %s" % (pattern, len(m), where)
     return m[0]
 
 
@@ -38,20 +42,26 @@ def test_the_constants_of_the_mirror_are_the_sources():
     assert int(a) * int(b) == C.WV_MAX_LDS
     mt, yes, no = _one(r"constexpr int WV_INFLIGHT = MT == (\d+) \? (\d+) : (\d+);")
     assert C.WV_INFLIGHT == {1: int(no), 2: int(no), 4: int(no), int(mt): int(yes)}
-    assert len(re.findall(r"\bbuf\[WV_INFLIGHT\]", SRC)) == 1 and len(re.findall(r"u < WV_INFLIGHT", SRC)) == 2
-    assert int(_one(r"if \(lds > (\d+) && lds_set")) == C.LDS_ATTR_ABOVE
-    assert _one(r"hipFuncAttributeMaxDynamicSharedMemorySize, \(int\)(\w+)\)") == "WV_MAX_LDS"
-    slots = _one(r"if \(rows_per_wg > WV_WAVES \* (\d+)\) rows_per_wg = WV_WAVES \* (\d+);")
-    assert int(slots[0]) == int(slots[1]) == C.WV_MAX_SLOTS == 64                      # one bias per lane of a wave
-    _one(r"int rows_per_wg = \(a\.N \+ cus - 1\) / cus;")
-    _one(r"const unsigned grid = \(unsigned\)\(\(a\.N \+ rows_per_wg - 1\) / rows_per_wg\);")
-    _one(r"const size_t lds = \(size_t\)a\.M \* a\.K \* 2;")
-    _one(r"const int cpl = \(kchunks \+ 63\) >> 6;")
+    # the walk takes the kernel's count as INFLIGHT: one set of request registers, one issue loop and one consume loop over it
+    _one(r"w4_stream_walk<WV_INFLIGHT, false, MT>\(")
+    _one(r"template <int INFLIGHT, bool SZ_DWORDS, int MT, class SlotRow, class Stage, class RowDone>", STREAM, "mq_w4a16_stream.h")
+    assert len(re.findall(r"\bbuf\[INFLIGHT\]", STREAM)) == 1 and len(re.findall(r"u < INFLIGHT", STREAM)) == 2
+    # the LDS opt-in: above LDS_ATTR_ABOVE bytes, once, for the kernel's maximum
+    assert int(_one(r"if \(lds > (\d+) && cache\[dev\]", COMMON, "mq_common.h")) == C.LDS_ATTR_ABOVE
+    _one(r"hipFuncSetAttribute\(fn, hipFuncAttributeMaxDynamicSharedMemorySize, \(int\)ceiling\)", COMMON, "mq_common.h")
+    assert _one(r"set_lds\(fn, lds_set\[ki\], lds, \"mq_w4a16_linear\", (\w+)\)") == "WV_MAX_LDS"
+    # the launch geometry: rows over the CUs, capped at one bias per lane of a wave
+    assert int(_one(r"fat_row_geometry\(a\.g\.N, WV_WAVES \* (\d+), &rows_per_wg, &grid\);")) == C.WV_MAX_SLOTS == 64
+    _one(r"int rpw = \(rows \+ cus - 1\) / cus;", COMMON, "mq_common.h")
+    _one(r"if \(rpw > max_rows_per_wg\) rpw = max_rows_per_wg;", COMMON, "mq_common.h")
+    _one(r"\*grid = \(unsigned\)\(\(rows \+ rpw - 1\) / rpw\);", COMMON, "mq_common.h")
+    _one(r"const size_t lds = \(size_t\)a\.M \* a\.g\.K \* 2;")
+    _one(r"const int cpl = \(kchunks \+ 63\) >> 6;", STREAM, "mq_w4a16_stream.h")
     _one(r"const int ki = a\.M == 1 \? 0 : a\.M == 2 \? 1 : a\.M <= 4 \? 2 : 3;")
     _one(r"return \(M <= 8 && \(size_t\)M \* K \* 2 <= WV_MAX_LDS\) \? 1 : 2;")
     bm, bn, bk = _one(r"constexpr int GM_BM = (\d+), GM_BN = (\d+), GM_BK = (\d+),")
     assert (int(bm), int(bn), int(bk)) == (C.GM_BM, C.GM_BN, C.GM_BK)
-    _one(r"const int nt = a\.N > GM_BN \? 2 : 1;")
+    _one(r"const int nt = a\.g\.N > GM_BN \? 2 : 1;")
 
 
 # what each tag of a case's `reaches` says about plan()
